@@ -10,10 +10,16 @@ Workload at N=1: BASELINE.json configs[1] "VQ-VAE.yml full" = B=4096, T=34, D=13
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps and
+prints the line (metric, value, unit, ms_per_step, ...); with --dump-outputs DIR it also writes what the last timed step
+computed as DIR/<name>.npy (see dump_outputs).  Everything else is measured only with --full, among it:
+  sustained     300 more steps of the same replay behind the timed ones
   roofline      the VQ assign kernel (the kernel BASELINE.json's north star names), timed live with events on the
                 launch stream; fp32 MFMA bound (arithmetic intensity K/4 flop/B > fp32 ridge)
   cpu_baseline  the CPU oracle (oracle/g2v_oracle.py, kind "port") timed on this host's cores on a bounded sample
+  text2embedding, bulk_assign, gru_resident, shipped_config, train_iter, config.dp_diag   (see the functions below)
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
 """
 import argparse
 import json
@@ -43,6 +49,36 @@ CONFIGS = {
 }
 PEAK_F32_MFMA_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
 PEAK_HBM_GBS = 8000.0
+
+
+DUMP_ROWS = 1024               # --dump-outputs: batch rows of the reconstruction written (a fixed, seeded sample of larger batches)
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir: str, net, eng, B: int) -> dict:
+    """--dump-outputs DIR: what the last timed step computed, as a caller of train_iter_Autoencoder_VQ_seq2seq receives it --
+    the loss terms, the code index of every latent row, the reconstructed poses (B, T, D) of DUMP_ROWS batch rows drawn with a
+    fixed seed (all rows up to DUMP_ROWS) and the model's state_dict after the update (weights, codebook, EMA and BatchNorm
+    statistics).  One DIR/<name>.npy per array, float32 (float64 for scalars and integers); returns {name: shape}."""
+    import numpy as np
+    b = eng.buffers(B)
+    N = (2 * B * eng.H) // eng.E
+    rows = np.arange(B) if B <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(B, DUMP_ROWS, replace=False))
+    y = b["y"].index_select(1, torch.from_numpy(rows).to(b["y"].device)).transpose(0, 1)
+    lt = eng.loss_terms.double().cpu().numpy()
+    vs = eng.vq_scalars.double().cpu().numpy()
+    arrays = {"loss": np.array([lt[0] + vs[0] / 400]), "custom_loss_terms": lt, "loss_vq": vs[:1], "perplexity": vs[1:2],
+              "code_indices": b["idx"][:N].cpu().numpy().astype(np.float64),
+              "reconstruction": y.float().cpu().numpy(), "reconstruction_rows": rows.astype(np.float64)}
+    for k, v in net.state_dict().items():
+        v = v.detach().cpu()
+        arrays[f"state.{k}"] = v.numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def model_args():
@@ -572,8 +608,15 @@ def main():
     ap.add_argument("--no-part-d", action="store_true", help="skip the text2embedding (Part d) samples/s object of the line")
     ap.add_argument("--no-graph", action="store_true", help="do not replay the step from a hipGraph")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sustained", type=int, default=300,
-                    help="extra steps timed BEHIND the contract's --steps and reported as `sustained` (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline figure too: `sustained`, the roofline and calibration probes, "
+                         "the CPU baselines, Part d, bulk assignment, the resident GRU, the shipped configuration, train_iter "
+                         "and the data-parallel diagnostics (a plain run times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--sustained", type=int, default=None,
+                    help="extra steps timed BEHIND the contract's --steps and reported as `sustained` (0 = off; default 300 "
+                         "with --full, 0 without)")
     ap.add_argument("--dropout", type=float, default=None,
                     help="encoder-input / GRU inter-layer dropout_prob (config/VQ-VAE.yml ships 0.2; SURVEY.md 8(d) config 2 "
                          "and the default here use 0: the always-on Dropout(0.95) of the decoder input is drawn either way)")
@@ -584,6 +627,10 @@ def main():
     ap.add_argument("--force-dp", action="store_true",
                     help="run the data-parallel code path (split graphs + RCCL all-reduce) even with one rank (diagnostic)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.sustained is None:
+        a.sustained = 300 if a.full else 0
     CFG.update({k: v for k, v in CONFIGS[a.config].items() if k != "name"})
     CFG["config"] = a.config
     if a.batch is None:
@@ -714,6 +761,9 @@ def main():
         per_rank_ms = [round(float(v.item()) / a.steps * 1e3, 4) for v in allt]
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    dumped = None
+    if a.dump_outputs and rank == 0:        # before anything else runs on the step's buffers
+        dumped = dump_outputs(a.dump_outputs, net, eng, B)
     # sustained rate: 300 more steps of the same replay, behind the contract's K steps (round-4 verdict: 20 x 1.6 ms is a 32 ms sample)
     sustained = None
     if a.sustained > 0:
@@ -732,7 +782,7 @@ def main():
     # data parallel: where a step's time goes per rank -- eager launches with events around the collective (the timed region
     # replays it from inside the graph): the local half, the all-reduce as exposed on the stream, the apply half
     dp_diag = None
-    if use_dp:
+    if use_dp and a.full:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         acc = [0.0, 0.0, 0.0]
         n_diag = 10
@@ -796,7 +846,9 @@ def main():
         }
         if sustained is not None:
             out["sustained"] = sustained
-        if world == 1:
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "arrays": len(dumped)}
+        if world == 1 and a.full:
             out["roofline"] = vq_kernel_roofline(eng, B)
             # the whole step as EXECUTED (the dead encoder layer 1 of the reference is skipped): forward
             # flop per chunk x 3 (backward = data + weight gradients), against the same fp32 MFMA peak

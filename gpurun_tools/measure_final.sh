@@ -1,7 +1,8 @@
 #!/bin/bash
 # round-2 final measurements: default bench line, kernel stats + one-step timeline of the same command, Part d, variants
-python bench.py > gpurun_out/r02_c_bench_default.json 2> gpurun_out/r02_c_bench_default.err
-tail -c 600 gpurun_out/r02_c_bench_default.json
+out=${BENCH_OUT:-$PWD/bench_out}; mkdir -p "$out"      # full bench lines and their logs
+python bench.py --full > "$out"/r02_c_bench_default.json 2> "$out"/r02_c_bench_default.err
+tail -c 600 "$out"/r02_c_bench_default.json
 for v in "--steps 200 --warmup 10 --no-cpu-baseline" "--no-graph --no-cpu-baseline" "--batch 128 --no-cpu-baseline" "--dropout 0.2 --no-cpu-baseline"; do
   echo "== bench.py $v"; python bench.py $v 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({'args': '$v', 'ms_per_step': d['ms_per_step'], 'value': d['value'], 'launch': d['config']['launch']}))" | tee -a gpurun_out/r02_c_bench_variants.jsonl
 done

@@ -1,13 +1,14 @@
 #!/bin/bash
 # round-5 measurements on one box: full GPU suite, default bench line, kernel stats + one-step timeline of the same command,
 # FETCH / WRITE of the rollouts + the quantiser, variants, Part d kernel stats
+out=${BENCH_OUT:-$PWD/bench_out}; mkdir -p "$out"      # full bench lines and their logs
 tag=${1:-k}
 mkdir -p gpurun_out
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -6 > gpurun_out/r05_${tag}_gpu_tests.log; cat gpurun_out/r05_${tag}_gpu_tests.log
-timeout 900 python bench.py > gpurun_out/r05_${tag}_bench_default.json 2> gpurun_out/r05_${tag}_bench_default.err
+timeout 900 python bench.py --full > "$out"/r05_${tag}_bench_default.json 2> "$out"/r05_${tag}_bench_default.err
 python - <<P
 import json
-d = json.loads(open("gpurun_out/r05_${tag}_bench_default.json").read().strip().splitlines()[-1])
+d = json.loads(open("$out/r05_${tag}_bench_default.json").read().strip().splitlines()[-1])
 print("default", d["ms_per_step"], d["value"], d.get("sustained"), d["roofline"]["avg_us"], d["roofline"]["frac"], d["cpu_baseline"]["value"], d["cpu_baseline"]["functional_oracle"]["value"])
 print([(r["att"], r["B"], r["ms_per_step"], r["frac_of_f32_mfma_peak"]) for r in d["text2embedding"]["runs"]], d["text2embedding"].get("cpu_baseline"))
 P
@@ -20,7 +21,7 @@ rm -rf gpurun_out/prof_r5${tag}
 for args in "--steps 300 --warmup 10" "--steps 200 --warmup 10 --force-dp" "--steps 200 --warmup 10 --dropout 0.2" \
             "--batch 128 --steps 300" "--batch 1024 --steps 300" "--batch 2048 --steps 300" "--batch 4100 --steps 50" "--batch 8192 --steps 50" \
             "--config native --steps 200" "--config native --batch 4096 --steps 50" "--config genea --steps 50" "--config genea --batch 128 --steps 200"; do
-  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 300 python bench.py --no-cpu-baseline --no-part-d --sustained 0 $args 2>/dev/null | tail -1 | python -c "
+  HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 300 python bench.py --full --no-cpu-baseline --no-part-d --sustained 0 $args 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 keep = {k: d[k] for k in ('value', 'ms_per_step', 'steps')}

@@ -4,7 +4,7 @@ timeout 900 python -m pytest tests/test_gpu_ops.py -q -k "fold2 or small_row or 
 timeout 1200 python -m pytest tests/test_gpu_vqvae.py -q -x 2>&1 | tail -3
 : > gpurun_out/r05_an_bench_variants.jsonl
 for args in "--config native --steps 300" "--config native --steps 300" "--config native --batch 4096 --steps 50" "--config genea --steps 50" "--config genea --batch 128 --steps 300"; do
-  timeout 300 python bench.py --no-cpu-baseline --no-part-d --sustained 0 $args 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full --no-cpu-baseline --no-part-d --sustained 0 $args 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 keep = {k: d[k] for k in ('value', 'ms_per_step', 'steps')}

@@ -22,12 +22,12 @@ def test_parse_synthetic_config():
     assert a.learning_rate == 0.0005 and a.epochs == 2
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/config"), reason="reference tree not present")
 @pytest.mark.parametrize("name", ["VQ-VAE.yml", "VQ-VAE_GENEA.yml", "DAE.yml", "seq2seq.yml"])
-def test_parse_reference_yaml_files(name):
-    """The reference's own YAMLs parse (including the ones that omit Modality_* and break the reference's parser)."""
+def test_parse_reference_yaml_files(name, golden_dir):
+    """The reference's own YAMLs parse (including the ones that omit Modality_* and break the reference's parser).  Copies of
+    them, unchanged, are kept under tests/golden/reference_config/."""
     from config.parse_args import parse_args
-    a = parse_args(["-c", os.path.join("/root/reference/config", name)])
+    a = parse_args(["-c", os.path.join(golden_dir, "reference_config", name)])
     assert isinstance(a.hidden_size, int) and a.n_layers == 2
     assert a.autoencoder_vq in ("True", "False")
     assert isinstance(a.train_data_path, list) and isinstance(a.data_mean, list)
