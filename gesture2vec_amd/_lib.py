@@ -184,6 +184,9 @@ _SIGS = {
     "g2v_linear_set_smallm_rows": (c_int, [c_int]),
     "g2v_vq_assign_bulk_workspace": (c_sz, [c_int, c_int, c_int]),
     "g2v_vq_assign_bulk": (c_int, [c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_sz, c_fp, c_fp]),
+    "g2v_vq_assign_bulk_z_ok": (c_int, [c_int, c_int, c_int]),
+    "g2v_vq_assign_bulk_z_workspace": (c_sz, [c_int, c_int, c_int]),
+    "g2v_vq_assign_bulk_z": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_fp, c_sz, c_fp, c_fp]),
     "g2v_copy_segments": (c_int, [c_fp, c_fp, c_fp, c_int, c_fp]),
     "g2v_embedding_fwd": (c_int, [c_fp, c_fp, c_fp, c_f, c_fp, c_i64, c_i64, c_int, c_i64, c_fp]),
     "g2v_embedding_bwd_ws_bytes": (c_sz, [c_i64, c_int, c_i64]),

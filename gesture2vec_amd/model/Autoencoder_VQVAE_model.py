@@ -271,6 +271,10 @@ class Generator(nn.Module):
         return self.decoder(input_with_noise_vec, last_hidden, encoder_output, vid_indices, **kw)
 
 
+# rows from which VQ_Payam_EMA.assign takes g2v_vq_assign_bulk_z (where it serves the shape): measured break-even, DESIGN.md §3.5
+VQ_BULK_Z_MIN_ROWS = 32768   # K = 512: 0.139 (old) vs 0.176 ms at 16384 rows, 0.242 vs 0.188 ms at 32768
+
+
 class VQ_Payam_EMA(nn.Module):
     """EMA vector quantiser (reference :1182-1301).  forward(inputs) -> (loss, quantized, perplexity, encodings)."""
 
@@ -298,8 +302,12 @@ class VQ_Payam_EMA(nn.Module):
         """Code indices only (bulk code-assignment path): argmin_k ||pre_linear(x) - W_k||^2, int64 (N,)."""
         E, K = self._embedding_dim, self._num_embeddings
         z = inputs.contiguous().view(-1, E)
-        flat = ops.linear_fwd(z, self.pre_linear.weight.data, self.pre_linear.bias.data)
         W = self._embedding.weight.data
+        if z.shape[0] >= VQ_BULK_Z_MIN_ROWS and ops.vq_assign_bulk_z_ok(z.shape[0], E, K):
+            # the checkpoints' width (E = 400): z-space bf16 screening + exact re-check straight from the raw latents, bitwise
+            # the route below at the same N, without writing pre_linear(z) (g2v_vq_assign_bulk_z)
+            return ops.vq_assign_bulk_z(z, self.pre_linear.weight.data, self.pre_linear.bias.data, W, ops.vq_code_sqnorm(W))
+        flat = ops.linear_fwd(z, self.pre_linear.weight.data, self.pre_linear.bias.data)
         wsq = ops.vq_code_sqnorm(W)
         if z.shape[0] >= 131072 and E == 128 and K % 128 == 0:
             # a corpus' worth of rows: bf16 split screening on the bf16 matrix pipe + exact fp32 re-check of the undecided

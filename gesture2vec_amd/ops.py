@@ -377,6 +377,27 @@ def vq_assign_bulk(flat, codebook, code_sqnorm, want_undecided=False):
     return (idx, und) if want_undecided else idx
 
 
+def vq_assign_bulk_z_ok(N, E, K) -> bool:
+    """shapes g2v_vq_assign_bulk_z serves (E = 400, K % 16 == 0, 32 <= K <= 512, N >= 2048 and above smallm_max_rows)"""
+    return bool(_lib_().g2v_vq_assign_bulk_z_ok(int(N), int(E), int(K)))
+
+
+def vq_assign_bulk_z(z, w_pre, b_pre, codebook, code_sqnorm, want_undecided=False):
+    """idx (N,) = argmin_k |z w_pre^T + b_pre - W_k|^2 from RAW latents, bitwise linear_fwd + vq_assign at the same N:
+    z-space bf16 screening + exact fp32 re-check (g2v_vq_assign_bulk_z); the projected rows are never written."""
+    N, E = z.shape
+    K = codebook.shape[0]
+    lib = _lib_()
+    idx = torch.empty((N,), dtype=torch.int64, device=z.device)
+    nb = int(lib.g2v_vq_assign_bulk_z_workspace(N, E, K))
+    ws = workspace(nb, z.device, "vqbulkz")
+    und = torch.zeros((1,), dtype=torch.int32, device=z.device) if want_undecided else None
+    check(lib.g2v_vq_assign_bulk_z(_p(_chk(z, name="z")), _p(_chk(w_pre, name="w_pre")), _p(_chk(b_pre, name="b_pre")),
+                                   _p(_chk(codebook, name="codebook")), _p(_chk(code_sqnorm, name="code_sqnorm")), _p(idx), N, E, K,
+                                   _p(ws), nb, _p(und), _stream()), "vq_assign_bulk_z")
+    return (idx, und) if want_undecided else idx
+
+
 def vq_pack_codebook(codebook, out=None):
     """fragment-major image of the codebook for vq_fused_assign(..., codebook_frag=)"""
     K, E = codebook.shape

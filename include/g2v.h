@@ -239,6 +239,18 @@ int g2v_vq_assign_fwd(const float* flat, const float* z, const float* codebook, 
 size_t g2v_vq_assign_bulk_workspace(int N, int E, int K);
 int g2v_vq_assign_bulk(const float* flat, const float* codebook, const float* code_sqnorm, int64_t* idx, int N, int E, int K,
                        void* workspace, size_t workspace_bytes, int* undecided, g2v_stream_t stream);
+/* Bulk code assignment from RAW latents at the checkpoints' width (E = 400, K % 16 == 0, 32 <= K <= 512): idx = argmin_k
+ * |z w_pre^T + b_pre - codebook[k]|^2 without writing the projected rows.  The distances are screened in z-space on the bf16
+ * matrix pipe (u_k = w_pre^T w_k, 3-term hi / lo split); a row whose winner does not clear every other code by the per-code
+ * error radius is recomputed with the arithmetic of g2v_linear_fwd (tiled kernel) + g2v_vq_assign_packed_fwd, so idx is
+ * bitwise that route's at the same N (ties: lowest index; non-finite rows or codes included).  code_sqnorm must be
+ * g2v_vq_code_sqnorm's.  _ok also refuses N < 2048 and N <= the context's smallm_max_rows (other kernels there).
+ * undecided (device int, may be NULL): number of rows that took the exact path. */
+int g2v_vq_assign_bulk_z_ok(int N, int E, int K);
+size_t g2v_vq_assign_bulk_z_workspace(int N, int E, int K);
+int g2v_vq_assign_bulk_z(const float* z, const float* w_pre, const float* b_pre, const float* codebook, const float* code_sqnorm,
+                         int64_t* idx, int N, int E, int K, void* workspace, size_t workspace_bytes, int* undecided,
+                         g2v_stream_t stream);
 int g2v_vq_fused_assign_fwd(const float* z, const float* w_pre, const float* b_pre, const float* codebook,
                             const float* code_sqnorm, float* flat_out, int64_t* idx, float* quantized,
                             float* sse_partial, int N, int E, int K, g2v_stream_t stream);
