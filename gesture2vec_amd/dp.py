@@ -12,6 +12,10 @@ GLOBAL assignment statistics, so every rank applies the identical update and the
 batch statistics stay per rank (north star: "all-reduce on gradients and on codebook EMA statistics only").  The last slot
 carries each rank's fault latch of the persistent rollouts (0 / 1): a non-zero sum makes EVERY rank skip the step.
 
+Without a quantiser (autoencoder_vq == "False", VQVAEEngine(quantizer="none")) there are no statistics to exchange:
+
+        comm = [ flat parameter gradients | fault flag (4 floats, one used) ]
+
 Message size at the BASELINE shape: 188,700 grads + 512 + 65,536 stats floats = 1.0 MB: latency-bound, so a single
 fused collective per step is the right shape for the 7-link xGMI mesh (no bucketing, no overlap machinery)."""
 from __future__ import annotations

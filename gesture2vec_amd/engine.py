@@ -11,8 +11,9 @@ reference, but every tensor op is one of the HIP kernels behind include/g2v.h.  
     train step can be captured into a hipGraph);
   * explicit dropout keep-masks (drawn by the Philox kernel, or supplied by the caller for parity tests).
 
-Scope: autoencoder_vq == "True", autoencoder_vae == "False", autoencoder_att == "False", n_layers == 2 (every
-shipped VQ-VAE config).  With attention off the decoder only consumes encoder_hidden[:2] = the layer-0
+Scope: autoencoder_vae == "False", autoencoder_att == "False", n_layers == 2 (every shipped Part-b config), with a quantiser
+(autoencoder_vq == "True") or without one (quantizer="none", autoencoder_vq == "False": config/seq2seq.yml; the rollout then
+starts from the encoder's final states in place).  With attention off the decoder only consumes encoder_hidden[:2] = the layer-0
 forward/backward final states (:971-973), so encoder GRU layer 1 is never evaluated: its outputs reach nothing and
 its gradients are exactly zero in the reference [SURVEY.md §0]; its weights stay in the state_dict untouched.
 """
@@ -52,8 +53,9 @@ QUANTIZER_GSSOFT_PARAMS = ("vq_layer._embedding.weight", "vq_layer.mean_layer.we
 
 def quantizer_layout(quantizer: str, E: int, K: int):
     """trainable tensors of the quantiser itself.  EMA (:1182-1301): none (codebook moves by EMA, pre_linear gets no gradient).
-    GSSoft (:1304-1438, what the reference's Autoencoder_VQVAE ships with): codebook, mean_layer, logvar_layer."""
-    if quantizer == "ema":
+    GSSoft (:1304-1438, what the reference's Autoencoder_VQVAE ships with): codebook, mean_layer, logvar_layer.
+    "none" (autoencoder_vq == "False", :829-830): there is no quantiser."""
+    if quantizer in ("ema", "none"):
         return []
     if quantizer == "gssoft":
         return list(zip(QUANTIZER_GSSOFT_PARAMS, ((K, E), (E, E), (E,), (K, E), (K,))))
@@ -164,7 +166,10 @@ class VQVAEEngine:
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         # ONE communication buffer [flat grads | cnt (K) | dw (K*E)]: a single RCCL all-reduce per step under DP
         # [grads | cnt (K) | dw (K E) | fault flag (4 floats: one used)]: the flag travels in the same all-reduce (round 5)
-        self.comm = torch.zeros(off + K + K * (H * L) + 4, dtype=torch.float32, device=dev)
+        # quantizer "none": [grads | fault flag], there are no statistics
+        vq = quantizer != "none"
+        n_stats = K + K * (H * L) if vq else 0
+        self.comm = torch.zeros(off + n_stats + 4, dtype=torch.float32, device=dev)
         self.gflat = self.comm[:off]
         self.m = torch.zeros(off, dtype=torch.float32, device=dev)
         self.v = torch.zeros(off, dtype=torch.float32, device=dev)
@@ -174,19 +179,20 @@ class VQVAEEngine:
         self.gnorm = torch.zeros(1, dtype=torch.float32, device=dev)
         # [custom_loss, loss_vq, perplexity, fault latch] of the latest train_step_apply: train_iter's ONE device-to-host copy
         self.readback = torch.zeros(4, dtype=torch.float32, device=dev)
-        # quantiser state (not trainable by gradient: grad=None in the reference, :1276-1282)
+        # quantiser state (not trainable by gradient: grad=None in the reference, :1276-1282); quantizer "none" allocates none of it
         E = self.E
-        self.vq_pre_w = torch.zeros(E, E, device=dev)
-        self.vq_pre_b = torch.zeros(E, device=dev)
-        self.codebook = torch.zeros(K, E, device=dev)
-        self.ema_w = torch.zeros(K, E, device=dev)
-        self.ema_cs = torch.zeros(K, device=dev)
-        self.code_sqnorm = torch.zeros(K, device=dev)
+        qz = (lambda *s: torch.zeros(*s, device=dev)) if vq else (lambda *s: None)
+        self.vq_pre_w = qz(E, E)
+        self.vq_pre_b = qz(E)
+        self.codebook = qz(K, E)
+        self.ema_w = qz(K, E)
+        self.ema_cs = qz(K)
+        self.code_sqnorm = qz(K)
         # What the fused assign kernels read besides the codebook itself, all DERIVED from (codebook, pre_linear) by vq_derive():
         #   bf16-screened kernel (g2v_vq_fused_assign_bx_fwd, where g2v_vq_fused_assign_bx_ok says so: E == 128, K in {128..512}):
         #     pre_linear's weight as fp32 MFMA fragments + the screening image (bf16 fragments of U = W w_pre, s'_k, norm bounds);
         #   fp32 kernel (every other shape): fragment-major image of the codebook.
-        self._vq_bx = bool(self.lib.g2v_vq_fused_assign_bx_ok(1, self.E, K))
+        self._vq_bx = vq and bool(self.lib.g2v_vq_fused_assign_bx_ok(1, self.E, K))
         # custom_loss by the CHASER kernel beside the persistent forward rollout + the backward rollout's own tile load
         # (include/g2v.h: g2v_custom_loss_chase, g2v_dec_saved.loss_*) instead of its own launch between the rollouts, wherever the
         # fused train step runs its parallel branches and g2v_dec_rollout_fuses_loss says so.  Bitwise the same gradients.
@@ -201,23 +207,24 @@ class VQVAEEngine:
                             if self._vq_bx else None)
         self.vq_diag = torch.zeros(4, dtype=torch.int32, device=dev)          # [0] tiles on the exact sweep, [1] pairs re-evaluated
         self._vq_diag_on = False
-        self.codebook_frag = torch.zeros(K * self.E, device=dev) if (self.E == 128 and K % 128 == 0 and not self._vq_bx) else None
+        self.codebook_frag = (torch.zeros(K * self.E, device=dev)
+                              if (vq and self.E == 128 and K % 128 == 0 and not self._vq_bx) else None)
         # every other shape the packed kernel serves (E = 400: the reference's own): pre_linear as a dense launch + the eight-wave
         # assignment kernel on the fragment-major codebook image (round 5; g2v_vq_assign_packed_fwd), from 2048 rows
         self.codebook_frag_generic = (torch.zeros(K * self.E, device=dev)
-                                      if (not self._vq_bx and self.codebook_frag is None and
+                                      if (vq and not self._vq_bx and self.codebook_frag is None and
                                           self.lib.g2v_vq_assign_packed_ok(1, self.E, K)) else None)
         self.bn_rm = torch.zeros(H, device=dev)
         self.bn_rv = torch.ones(H, device=dev)
-        self.vq_stats = self.comm[self.n_flat:self.n_flat + K + K * self.E]
-        self.fault_flag = self.comm[self.n_flat + K + K * self.E:]
-        self.vq_scalars = torch.zeros(2, device=dev)          # loss_vq, perplexity
+        self.vq_stats = self.comm[self.n_flat:self.n_flat + n_stats] if vq else None
+        self.fault_flag = self.comm[self.n_flat + n_stats:]
+        self.vq_scalars = qz(2)                               # loss_vq, perplexity
         self.loss_terms = torch.zeros(5, device=dev)          # custom_loss total, l1, cont, var, mse
-        self.g_loss_vq = torch.full((1,), 1.0 / 400.0, device=dev)
+        self.g_loss_vq = torch.full((1,), 1.0 / 400.0, device=dev) if vq else None
         # the soft quantiser's fused sequence (_forward_gssoft / _backward_gssoft): d total / d loss_vq as the step has it (host
         # float baked into the launch arguments + the same value on the device), and 1 + beta
         self._g_vq_host, self._g_vq_dev = 1.0 / 400.0, self.g_loss_vq
-        self._one_plus_beta = torch.full((1,), 1.0 + float(beta), device=dev)
+        self._one_plus_beta = torch.full((1,), 1.0 + float(beta), device=dev) if vq else None
         self._bufs: Dict[int, dict] = {}
         self._wstruct = None
         # tensors with requires_grad == False in the reference (autoencoder_fixed_weight == "True" freezes the decoder GRU,
@@ -439,8 +446,6 @@ class VQVAEEngine:
             "hs_f": z(T + 1, B, H), "hs_b": z(T + 1, B, H),
             "gates_f": z(T, B, 4 * H), "gates_b": z(T, B, 4 * H),
             "enc_hidden": z(2, B, H),            # encoder_hidden[:2] = (layer-0 fwd, layer-0 bwd) final states
-            "flat": z(B, E), "idx": torch.zeros(B, dtype=torch.int64, device=dev), "quant": z(2, B, H),
-            "sse": z(self.lib.g2v_vq_assign_blocks(B)),
             "y": z(T, B, D), "dec_xin": z(T - 1, B, D), "u": z(T - 1, B, H), "a": z(T - 1, B, H),
             "h0": z(T, B, H), "h1": z(T, B, H), "x1": z(T - 1, B, H) if self.p > 0 else None,
             "gates0": z(T - 1, B, 4 * H), "gates1": z(T - 1, B, 4 * H),
@@ -452,12 +457,15 @@ class VQVAEEngine:
             "dy": z(T, B, D), "du": z(T - 1, B, H), "dbn": z(T - 1, B, H),
             "dgi0": z(T - 1, B, G), "dgh0": z(T - 1, B, G), "dgi1": z(T - 1, B, G), "dgh1": z(T - 1, B, G),
             "dh_init": z(2, B, H), "bn_bwd_partial": z(2, nblk, 2, H),
-            "gz": z(2, B, H),
             "dgi_f": z(T, B, G), "dgh_f": z(T, B, G), "dgi_b": z(T, B, G), "dgh_b": z(T, B, G),
             "dxin": z(T * B, H),
             "wc_in": z(2, 3 * H, D), "bc_in": z(2, 3 * H),     # W_ih W_in and W_ih b_in + b_ih per direction (g2v_linear_compose2)
             "p_in": z(2, 3 * H, D), "c_in": z(2, 3 * H),       # dgi^T x and the column sums of dgi per direction (g2v_linear_bwd_weight_fold2)
         }
+        vq = self.quantizer != "none"          # (without a quantiser the rollout starts from enc_hidden, its gradient seeds the BPTT)
+        if vq:
+            b.update({"flat": z(B, E), "idx": torch.zeros(B, dtype=torch.int64, device=dev), "quant": z(2, B, H),
+                      "sse": z(self.lib.g2v_vq_assign_blocks(B)), "gz": z(2, B, H)})
         sv = DecSaved()
         sv.y, sv.xin, sv.u, sv.a = _p(b["y"]), _p(b["dec_xin"]), _p(b["u"]), _p(b["a"])
         sv.h0, sv.h1, sv.x1 = _p(b["h0"]), _p(b["h1"]), _p(b["x1"])
@@ -491,14 +499,15 @@ class VQVAEEngine:
         b["gr"] = gr
         ws_bytes = max(self.lib.g2v_dec_rollout_bwd_workspace(D, H), self.lib.g2v_dec_rollout_fwd_workspace(D, H),
                        self.lib.g2v_gru_seq_bwd_workspace(2, H), self.lib.g2v_gru_seq_fwd_workspace(2, H),
-                       self.lib.g2v_vq_stats_workspace(B, E, K),
+                       self.lib.g2v_vq_stats_workspace(B, E, K) if vq else 0,
                        self.lib.g2v_linear_bwd_weight_workspace(T * B, max(D, H), 3 * H),
                        self.lib.g2v_linear_bwd_weight_workspace(T * B, H, max(D, 3 * H)),
                        4 * self.lib.g2v_linear_bwd_weight_workspace(T * B, H, 3 * H),     # batches of four GRU weight gradients
                        2 * self.lib.g2v_linear_bwd_weight_workspace(T * B, D, 3 * H))
         b["ws"] = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
         # scratch of the parallel branches (see _branch): never shared with the main chain
-        b["ws_stats"] = torch.zeros(max(self.lib.g2v_vq_stats_workspace(B, E, K), 256), dtype=torch.uint8, device=dev)
+        if vq:
+            b["ws_stats"] = torch.zeros(max(self.lib.g2v_vq_stats_workspace(B, E, K), 256), dtype=torch.uint8, device=dev)
         wsz = self.lib.g2v_linear_bwd_weight_workspace
         # (deferred reductions: the decoder branch's three calls keep their slabs side by side until the branch's one reduction)
         b["ws_dec_wgrad"] = torch.zeros(4 * wsz(T * B, H, 3 * H) + wsz(T * B, D, H) + wsz(T * B, H, D) + 1024,
@@ -577,6 +586,13 @@ class VQVAEEngine:
         Fills buffers: y (T,B,D), quant (2,B,H) first hidden, idx, vq_scalars (loss_vq, perplexity)."""
         if self.quantizer == "gssoft":
             return self._forward_gssoft(in_poses, out_poses, training, loss_w)
+        if self.quantizer == "none":
+            # autoencoder_vq == "False" (:971-973, 1018): the rollout starts from encoder_hidden[:2] itself -- forward_decoder reads
+            # buffers['enc_hidden'] in place.  custom_loss runs as its own launch (loss()): the chaser must be dispatched behind the
+            # rollout, which the quantiser's statistics kernels ensure in the branch above, and without them nothing does.
+            self.forward_encoder(in_poses, training)
+            self._join(0)                   # branch 0: keep masks, ahead-of-time packs, exchange pre-clears
+            return self.forward_decoder(out_poses, in_poses.shape[0], training)
         lib, st = self.lib, self._stream()
         B = in_poses.shape[0]
         H, E, K = self.H, self.E, self.K
@@ -751,7 +767,8 @@ class VQVAEEngine:
         return b
 
     def forward_decoder(self, out_poses: torch.Tensor, B: int, training: bool, chase: bool = False):
-        """decoder rollout (:1039-1054) from buffers['quant'] (2,B,H) = the initial hidden state; fills buffers['y'] (T,B,D).
+        """decoder rollout (:1039-1054) from buffers['quant'] (2,B,H) = the initial hidden state (quantizer "none": from
+        buffers['enc_hidden']); fills buffers['y'] (T,B,D).
         chase (forward() decides): the rollout hands every y_t over to the custom_loss chaser that forward() has forked;
         buffers['loss_folded'] then says so, loss() launches nothing and loss_terms is written by backward_decoder's launch."""
         lib, st = self.lib, self._stream()
@@ -764,7 +781,8 @@ class VQVAEEngine:
         if self._xch_pre and training:
             ws = b["ws_decf"]                  # its exchange records were cleared on branch 0 (side())
         fold = b["loss_folded"] = bool(training and chase)
-        check(fn(_p(out_poses), _p(b["quant"]), C.byref(self.dec_wstruct()),
+        h_init = b["enc_hidden"] if self.quantizer == "none" else b["quant"]
+        check(fn(_p(out_poses), _p(h_init), C.byref(self.dec_wstruct()),
                  C.byref((b["sv_loss"] if fold else b["sv"]) if training else b["sv_eval"]), _p(b["keep95"]),
                  _p(b["keep_l0"]) if drop_in else None, self.p, self.n_pre,
                  int(self.conditioned), int(training), T, B, D, H, _p(ws), ws.numel(), st))
@@ -819,6 +837,12 @@ class VQVAEEngine:
             return self._backward_gssoft(in_poses, B)
         H, E = self.H, self.E
         b = self.backward_decoder(B, wgrad_branch=True)
+        if self.quantizer == "none":
+            # the rollout's dh_init IS d loss / d encoder_hidden[:2]: it seeds the encoder's BPTT directly (backward_encoder)
+            self._release()
+            self.backward_encoder(in_poses, B)
+            self._join(2)
+            return
         # ---- quantiser backward: straight-through + commitment (:1285-1292) ------------------------------------
         N = (2 * B * H) // E
         gl = g_loss_vq if g_loss_vq is not None else self.g_loss_vq
@@ -1081,7 +1105,8 @@ class VQVAEEngine:
     def backward_encoder(self, in_poses: torch.Tensor, B: int, quant_bwd=None):
         """Encoder layer-0 BPTT from buffers['gz'] (2,B,H) = dLoss / d enc_hidden; writes the encoder's parameter gradients.
         quant_bwd = (g_loss_vq tensor, coef): the quantiser's backward has NOT been run -- the recurrent kernel forms
-        gz = dh_init + g_loss_vq coef (enc_hidden - quant) where it reads its incoming gradient (g2v_gru_dir_bwd.hn_*)."""
+        gz = dh_init + g_loss_vq coef (enc_hidden - quant) where it reads its incoming gradient (g2v_gru_dir_bwd.hn_*).
+        quantizer "none": from buffers['dh_init'] (the decoder's initial state IS enc_hidden)."""
         lib, st = self.lib, self._stream()
         T, D, H, G = self.T, self.D, self.H, 3 * self.H
         b = self.buffers(B)
@@ -1092,7 +1117,8 @@ class VQVAEEngine:
         dirs = (_lib.GruDirBwd * 2)()
         for k, (suf, key, hs_ptr) in enumerate((("", "f", b["hs_f"][1:].data_ptr()), ("_reverse", "b", b["hs_b"].data_ptr()))):
             dirs[k].d_hs = None
-            dirs[k].d_hn = b["gz"][k].data_ptr() if quant_bwd is None else b["dh_init"][k].data_ptr()
+            d_hn = b["gz"] if (quant_bwd is None and self.quantizer != "none") else b["dh_init"]
+            dirs[k].d_hn = d_hn[k].data_ptr()
             if quant_bwd is not None:
                 dirs[k].hn_z, dirs[k].hn_q = b["enc_hidden"][k].data_ptr(), b["quant"][k].data_ptr()
                 dirs[k].hn_gloss, dirs[k].hn_coef = _p(quant_bwd[0]), float(quant_bwd[1])
@@ -1229,12 +1255,14 @@ class VQVAEEngine:
     def optimizer_step(self, lr: float, betas=(0.5, 0.999), eps: float = 1e-8, max_norm: float = 5.0,
                        grad_scale: float = 1.0, readback: bool = False):
         """clip_grad_norm_ + Adam over the flat buffers; readback: the same launch also gathers [custom_loss, loss_vq, perplexity,
-        fault latch] into self.readback (train_iter's one device-to-host copy; written also when the latch holds the update back)"""
+        fault latch] into self.readback (train_iter's one device-to-host copy; written also when the latch holds the update back;
+        without a quantiser its two slots read 0)"""
         if readback:
+            vqs = self.vq_scalars
             check(self.lib.g2v_clip_adam_step_readback(_p(self.flat), _p(self.gflat), _p(self.m), _p(self.v), self.n_flat,
                                                        _p(self.adam_partial), _p(self.step_counter), _p(self.gnorm), max_norm,
                                                        grad_scale, lr, betas[0], betas[1], eps, _p(self.loss_terms),
-                                                       _p(self.vq_scalars), self.vq_scalars[1:].data_ptr(), _p(self.readback),
+                                                       _p(vqs), _p(vqs[1:]) if vqs is not None else None, _p(self.readback),
                                                        self._stream()))
             return
         check(self.lib.g2v_clip_adam_step(_p(self.flat), _p(self.gflat), _p(self.m), _p(self.v), self.n_flat,
@@ -1257,7 +1285,8 @@ class VQVAEEngine:
     # be captured in its own hipGraph; the RCCL all-reduce of `comm` runs between the two replays.
     def train_step_local(self, x: torch.Tensor, target: torch.Tensor, *, w_l1: float, w_cont: float, w_var: float,
                          epoch: int = 1, draw_masks: bool = True, dp: bool = False):
-        """masks -> forward -> loss -> backward; leaves comm = [grads | cnt | dw] holding this rank's contribution."""
+        """masks -> forward -> loss -> backward; leaves comm = [grads | cnt | dw] holding this rank's contribution ([grads] without
+        a quantiser; the fault flag slot follows under dp)."""
         B = x.shape[0]
         self._branches_on = self._branches_ok(B)
         self._prepared = self._branches_on and (self.overlap & 9) == 9
@@ -1281,7 +1310,8 @@ class VQVAEEngine:
         self._fused_in_drop = bool(draw_masks and self.p > 0)      # the encoder's input mask is drawn inside its dropout kernel
         def side():                            # branch 0: beside the encoder GRU (forked in forward_encoder), joined before the quantiser
             if self.xch_preclear and self.H != 64:
-                # generic dims at small batch: the exchange records of the three cluster launches behind the quantiser are cleared
+                # generic dims at small batch: the exchange records of the three cluster launches behind the encoder's forward (the
+                # rollout pair, the encoder's BPTT; named by kind and workspace, whatever sits between them) are cleared
                 # HERE, off the chain, in workspaces only those launches use (g2v_cluster_exchange_preclear; a no-op for shapes
                 # that do not run as clusters)
                 bb = self.buffers(B)
@@ -1308,8 +1338,10 @@ class VQVAEEngine:
             if draw_masks and self.side_early:
                 self.draw_masks(B, True, "rest")       # last: the one HBM-heavy kernel of the branch (see forward_encoder)
         self._side_work = side
-        g_vq = self.g_loss_vq if epoch > 0 else torch.zeros_like(self.g_loss_vq)
-        self._g_vq_host, self._g_vq_dev = (1.0 / 400.0 if epoch > 0 else 0.0), g_vq       # (:707, 738: loss + loss_vq / 400 from epoch 1)
+        g_vq = None                            # (no quantiser: loss = custom_loss alone, :702-707)
+        if self.quantizer != "none":
+            g_vq = self.g_loss_vq if epoch > 0 else torch.zeros_like(self.g_loss_vq)
+            self._g_vq_host, self._g_vq_dev = (1.0 / 400.0 if epoch > 0 else 0.0), g_vq   # (:707, 738: loss + loss_vq / 400 from epoch 1)
         self._defer_commit = True
         self._commit_pending = (B, self.quantizer == "ema")
         self._commit_in_apply = dp          # data parallel: every commit behind the all-reduce (global statistics, global fault flag)

@@ -15,8 +15,9 @@ Differences from the reference, all deliberate:
   * Dropout masks come from a counter-based Philox kernel (or are supplied explicitly, `set_dropout_masks`),
     because CPU and GPU RNG streams cannot agree anyway.
   * GPU only: `.forward` raises if the module is not on an MI355X (no CPU path).
-Supported configuration: autoencoder_vq "True", autoencoder_vae "False", n_layers 2; autoencoder_att "False" (fused engine +
-rollout kernels) and "True" (module-level path: step-level decoder with Bahdanau attention).
+Supported configuration: autoencoder_vq "True" and "False" (no quantiser: config/seq2seq.yml), autoencoder_vae "False",
+n_layers 2; autoencoder_att "False" (fused engine + rollout kernels) and "True" (module-level path: step-level decoder with
+Bahdanau attention).
 """
 from __future__ import annotations
 
@@ -353,7 +354,8 @@ class _VQFn(torch.autograd.Function):
 class Autoencoder_VQVAE(nn.Module):
     """Chunk autoencoder: EncoderRNN -> VQ_Payam_EMA on encoder_hidden[:L] -> T-1 autoregressive decode steps
     (reference :686-1085).  forward(in_poses, out_poses, vq_layer_active) ->
-    (outputs (B,T,D), decoder_first_hidden (L,B,H), loss_vq, perplexity_vq)."""
+    (outputs (B,T,D), decoder_first_hidden (L,B,H), loss_vq, perplexity_vq); with autoencoder_vq "False" there is no vq_layer
+    and forward returns (outputs, decoder_first_hidden = encoder_hidden[:L])."""
 
     def __init__(self, args, pose_dim: int, n_frames: int):
         super().__init__()
@@ -367,21 +369,21 @@ class Autoencoder_VQVAE(nn.Module):
         if args.autoencoder_vae == "True":
             raise NotImplementedError("autoencoder_vae == 'True' is outside the accelerated hot path")
         self.VAE = False
-        if args.autoencoder_vq != "True":
-            raise NotImplementedError("autoencoder_vq == 'False' is outside the accelerated hot path")
-        self.vq = True
-        self.vq_components = int(args.autoencoder_vq_components)
-        self.commitment_cost = float(args.autoencoder_vq_commitment_cost)
+        self.vq = args.autoencoder_vq == "True"
         # The reference builds VQ_Payam_EMA (:801-807) and then overwrites it with VQ_Payam_GSSoft (:816-820).  The EMA
         # quantiser is the north star and the fused engine path; `args.autoencoder_vq_quantizer = "gssoft"` (not a
         # reference key; load_checkpoint_and_model sets it when a checkpoint carries the soft quantiser's tensors) builds the
         # model exactly as the reference ships it: same state_dict, encoder / decoder stages of the engine around the module.
-        self.quantizer = str(getattr(args, "autoencoder_vq_quantizer", "ema")).lower()
+        # autoencoder_vq == "False" (config/seq2seq.yml, :829-830): no vq_layer; encoder_hidden[:L] is the decoder's initial state.
+        self.quantizer = str(getattr(args, "autoencoder_vq_quantizer", "ema")).lower() if self.vq else "none"
+        if self.vq:
+            self.vq_components = int(args.autoencoder_vq_components)
+            self.commitment_cost = float(args.autoencoder_vq_commitment_cost)
         if self.quantizer == "ema":
             self.vq_layer = VQ_Payam_EMA(self.vq_components, args.hidden_size * args.n_layers, self.commitment_cost, 0.85)
         elif self.quantizer == "gssoft":
             self.vq_layer = VQ_Payam_GSSoft(self.vq_components, args.hidden_size * args.n_layers, self.commitment_cost)
-        else:
+        elif self.quantizer != "none":
             raise ValueError(f"autoencoder_vq_quantizer must be 'ema' or 'gssoft', got {self.quantizer!r}")
         self.n_frames = n_frames
         self.n_pre_poses = args.n_pre_poses
@@ -423,8 +425,8 @@ class Autoencoder_VQVAE(nn.Module):
                 return eng
         sd_params = dict(self.named_parameters())
         if eng is None or eng.device != dev:
-            eng = VQVAEEngine(self.pose_dim, self.hidden_size, self.n_layers, self.vq_components, self.n_frames,
-                              beta=self.commitment_cost, dropout_prob=self.dropout_prob, n_pre_poses=self.n_pre_poses,
+            eng = VQVAEEngine(self.pose_dim, self.hidden_size, self.n_layers, self.vq_components if self.vq else 0, self.n_frames,
+                              beta=self.commitment_cost if self.vq else 0.0, dropout_prob=self.dropout_prob, n_pre_poses=self.n_pre_poses,
                               conditioned=self.autoencoder_conditioned, device=dev, seed=self.rng_seed,
                               quantizer=self.quantizer)
             self._engine = eng
@@ -440,15 +442,16 @@ class Autoencoder_VQVAE(nn.Module):
             g = eng.view(name, True)
             if p.grad is None or p.grad.data_ptr() != g.data_ptr():
                 p.grad = g
-        vq, bn = self.vq_layer, self.decoder.decoder.pre_linear[1]
+        bn = self.decoder.decoder.pre_linear[1]
         if self.quantizer == "ema":
+            vq = self.vq_layer
             eng.vq_pre_w, eng.vq_pre_b = vq.pre_linear.weight.data, vq.pre_linear.bias.data
             eng.codebook, eng.ema_w, eng.ema_cs = vq._embedding.weight.data, vq._ema_w.data, vq._ema_cluster_size
         if eng.bn_rm.data_ptr() != bn.running_mean.data_ptr() or eng.bn_rv.data_ptr() != bn.running_var.data_ptr():
             eng.bn_rm, eng.bn_rv = bn.running_mean, bn.running_var
             eng._wstruct = None
         first, last = sd_params[eng.layout[0][0]], sd_params[eng.layout[-1][0]]
-        cb = vq._embedding.weight if self.quantizer == "ema" else bn.running_mean
+        cb = self.vq_layer._embedding.weight if self.quantizer == "ema" else bn.running_mean
         self._engine_probe = (first, first.data_ptr(), last, last.data_ptr(), cb, cb.data_ptr())
         self._engine_bound = True
         return eng
@@ -506,7 +509,10 @@ class Autoencoder_VQVAE(nn.Module):
         enc_out, enc_hidden = self.encoder(x_tbd, None, keep_in=keep_in, in_scale=1.0 / (1.0 - p) if keep_in is not None else 1.0,
                                            keep_inter=keep_inter)
         decoder_hidden = enc_hidden[:L]                                                   # :971-973
-        loss_vq, quantized, perp, _ = self.vq_layer(decoder_hidden.contiguous())
+        if self.vq:
+            loss_vq, quantized, perp, _ = self.vq_layer(decoder_hidden.contiguous())
+        else:                                                                             # :1018, quantiser call left out
+            quantized = decoder_hidden
         hidden = quantized
         enc_proj = dec.attn.project_encoder(enc_out)                                      # shared by the T-1 steps
         outputs = [tgt[0]]
@@ -515,9 +521,13 @@ class Autoencoder_VQVAE(nn.Module):
             y, hidden, _ = self.decoder(None, dec_in, hidden, enc_out, None, enc_proj=enc_proj)
             outputs.append(y)
             dec_in = tgt[t] if t < self.n_pre_poses else y                                # :1049-1052
+        if not self.vq:
+            return torch.stack(outputs).transpose(0, 1), quantized[:L]                   # :1082-1085
         return torch.stack(outputs).transpose(0, 1), quantized[:L], loss_vq, perp
 
     def forward(self, in_poses: torch.Tensor, out_poses: torch.Tensor, vq_layer_active: bool = False):
+        """(outputs (B,T,D), decoder_first_hidden (L,B,H), loss_vq, perplexity_vq); without a quantiser (autoencoder_vq ==
+        "False") the reference's 2-tuple (outputs, decoder_first_hidden = encoder_hidden[:L]) (:1082-1085)."""
         if self.att_use:
             return self._forward_attention(in_poses, out_poses)
         eng = self.engine()
@@ -526,6 +536,15 @@ class Autoencoder_VQVAE(nn.Module):
         B = in_poses.shape[0]
         if not self._explicit_masks:
             eng.draw_masks(B, self.training)
+        if not self.vq:
+            if self.training and torch.is_grad_enabled():
+                y, first_hidden = _PlainAEFn.apply(self.encoder.in_layer.weight, self, in_poses, out_poses)
+            else:
+                b = eng.forward(in_poses, out_poses, self.training)
+                y, first_hidden = b["y"].clone(), b["enc_hidden"].clone()
+            if self.training:
+                self.decoder.decoder.pre_linear[1].num_batches_tracked += self.n_frames - 1   # one BN call per decode step
+            return y.transpose(0, 1), first_hidden[: self.n_layers]
         if self.quantizer != "ema":
             y, first_hidden, loss_vq, perp = self._forward_staged(eng, in_poses, out_poses)
         elif self.training and torch.is_grad_enabled():
@@ -650,6 +669,35 @@ class _VQVAEFn(torch.autograd.Function):
         if g_first_hidden is not None:
             raise NotImplementedError("gradient through decoder_first_hidden is not used by the reference's losses")
         eng.backward(in_poses, B, gl)
+        _rebind_grads(net, eng)
+        return None, None, None, None
+
+
+class _PlainAEFn(torch.autograd.Function):
+    """_VQVAEFn without a quantiser (autoencoder_vq == "False"): outputs and encoder_hidden[:2] of the whole module as ONE autograd
+    node; the backward writes every parameter gradient into the engine's flat grad buffer."""
+
+    @staticmethod
+    def forward(ctx, anchor, net: Autoencoder_VQVAE, in_poses, out_poses):
+        b = net._engine.forward(in_poses, out_poses, True)
+        ctx.net, ctx.B = net, in_poses.shape[0]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(in_poses)
+        return b["y"].clone(), b["enc_hidden"].clone()
+
+    @staticmethod
+    def backward(ctx, gy, g_first_hidden):
+        net, B = ctx.net, ctx.B
+        eng = net._engine
+        (in_poses,) = ctx.saved_tensors
+        b = eng.buffers(B)
+        if gy is None:
+            b["dy"].zero_()
+        else:
+            b["dy"].copy_(gy)
+        if g_first_hidden is not None:
+            raise NotImplementedError("gradient through decoder_first_hidden is not used by the reference's losses")
+        eng.backward(in_poses, B)
         _rebind_grads(net, eng)
         return None, None, None, None
 

@@ -35,6 +35,9 @@ def chunk_latents(net, chunks: torch.Tensor) -> torch.Tensor:
 @torch.no_grad()
 def chunks_to_codes(net, chunks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(N,T,D) pose chunks -> (latents (N,L*H), code ids (N,) int64) with the net's EMA codebook."""
+    if not getattr(net, "vq", True):
+        raise ValueError("chunks_to_codes: this autoencoder has no quantiser (autoencoder_vq == 'False'), so there are no codes "
+                         "to assign; chunk_latents gives its latent rows")
     lat = chunk_latents(net, chunks)
     return lat, net.vq_layer.assign(lat)
 
@@ -42,11 +45,14 @@ def chunks_to_codes(net, chunks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tens
 @torch.no_grad()
 def stacked_autoencode(dae, net, poses: torch.Tensor):
     """Config 3: raw (B,T,D_raw) poses -> DAE encoder (per frame) -> chunk VQ-VAE -> DAE decoder -> (B,T,D_raw).
-    Returns (reconstruction, vq-vae output in the DAE latent space, perplexity).  `net` decodes in whatever mode it is in
-    (its inline Dropout(0.95) is always active, as in the reference)."""
+    Returns (reconstruction, vq-vae output in the DAE latent space, perplexity; None for a net without a quantiser).  `net`
+    decodes in whatever mode it is in (its inline Dropout(0.95) is always active, as in the reference)."""
     _need_cuda(poses, "stacked_autoencode")
     B, T, D = poses.shape
     lat = dae.encode(poses.reshape(B * T, D).contiguous()).view(B, T, -1) if dae.encoder is not None else poses
-    out, _, _, perplexity = net(lat, lat)
+    if getattr(net, "vq", True):
+        out, _, _, perplexity = net(lat, lat)
+    else:
+        (out, _), perplexity = net(lat, lat), None
     rec = dae.decode(out.reshape(B * T, -1).contiguous()).view(B, T, D) if dae.decoder is not None else out
     return rec, out, perplexity

@@ -74,7 +74,9 @@ class FusedClipAdam:
 
 def train_iter_Autoencoder_VQ_seq2seq(args, epoch: int, input_poses: torch.Tensor, target_poses: torch.Tensor,
                                       net: torch.nn.Module, optim) -> Tuple[dict, torch.Tensor]:
-    """One training iteration of the chunk VQ-VAE; same signature / return value as the reference."""
+    """One training iteration of the chunk VQ-VAE; same signature / return value as the reference: ({"loss": float}, perplexity),
+    and without a quantiser (autoencoder_vq == "False", :702-703, 757-758) {"loss": custom_loss} alone."""
+    vq = getattr(net, "vq", True)
     if getattr(net, "att_use", False):
         # attention decoder: module-level autograd path; its parameter set (attn.*, the wider pre_linear) is not the fused
         # engine's flat layout, so clip + Adam run over a FlatClipAdam of net.parameters()
@@ -82,6 +84,12 @@ def train_iter_Autoencoder_VQ_seq2seq(args, epoch: int, input_poses: torch.Tenso
         if not isinstance(optim, FlatClipAdam):
             raise TypeError("autoencoder_att == 'True': use gesture2vec_amd.flat.FlatClipAdam(net.parameters(), lr, betas=(0.5, 0.999))")
         optim.zero_grad()
+        if not vq:
+            outputs, _ = net(input_poses, target_poses)
+            loss = custom_loss(outputs, target_poses, args)
+            loss.backward()
+            optim.step()
+            return {"loss": loss.item()}
         outputs, _, loss_vq, perplexity_vq = net(input_poses, target_poses, epoch > 0)
         loss = custom_loss(outputs, target_poses, args)
         if epoch > 0:
@@ -90,10 +98,16 @@ def train_iter_Autoencoder_VQ_seq2seq(args, epoch: int, input_poses: torch.Tenso
         optim.step()
         return {"loss": loss.item()}, perplexity_vq.detach()
     optim = _as_fused(net, optim)
-    if getattr(net, "quantizer", "ema") in ("ema", "gssoft") and optim.net is net and net.training and _FUSED_GSSOFT_OK(net):
+    if getattr(net, "quantizer", "ema") in ("ema", "gssoft", "none") and optim.net is net and net.training and _FUSED_GSSOFT_OK(net):
         # the whole iteration as ONE kernel sequence of the engine (no autograd graph, one host sync for loss.item())
         return _fused_iteration(args, epoch, input_poses, target_poses, net, optim, None, 1)
     optim.zero_grad()
+    if not vq:
+        outputs, _ = net(input_poses, target_poses)
+        loss = custom_loss(outputs, target_poses, args)
+        loss.backward()
+        optim.step()
+        return {"loss": loss.item()}
     vq_start_epoch = 0
     outputs, _, loss_vq, perplexity_vq = net(input_poses, target_poses, epoch > vq_start_epoch)
     loss = custom_loss(outputs, target_poses, args)
@@ -109,7 +123,8 @@ def train_iter_Autoencoder_VQ_seq2seq_dp(args, epoch: int, input_poses: torch.Te
     """The data-parallel form of train_iter_Autoencoder_VQ_seq2seq (one process per GPU): this rank's shard goes through
     forward / loss / backward, ONE all-reduce (`reduce_fn`, RCCL) sums [gradients | codebook EMA statistics] over the
     ranks, then every rank applies the identical EMA update (global statistics) and clip + Adam on the mean gradient
-    (gesture2vec_amd/dp.py).  Returns this rank's loss and the perplexity of the global code histogram."""
+    (gesture2vec_amd/dp.py).  Returns this rank's loss and the perplexity of the global code histogram (without a quantiser:
+    this rank's {"loss": custom_loss} alone, the exchange then carries the gradients and the fault flag only)."""
     return _fused_iteration(args, epoch, input_poses, target_poses, net, _as_fused(net, optim), reduce_fn, world)
 
 
@@ -171,6 +186,8 @@ def _fused_iteration(args, epoch, input_poses, target_poses, net, optim, reduce_
                 eng.check_faults()
     if eng.fault_policy.tick():    # enough fault-free iterations since the last fault: the persistent / cluster kernels are back
         eng.rearm()
+    if eng.quantizer == "none":
+        return {"loss": both[0]}   # custom_loss alone (:702-707, 757-758)
     loss = both[0] + (both[1] / 400 if epoch > 0 else 0.0)
     return {"loss": loss}, eng.readback[2].clone()
 
@@ -196,8 +213,9 @@ def _replayed_step(eng, x, tgt, kw):
     loader hands over a new tensor per batch) are copied into the engine's static input buffers first (75 MB at B = 4096:
     ~40 us).  Everything the step reads besides the inputs -- weights, Adam moments, step / RNG counters -- lives at fixed device
     addresses and is read by the kernels at replay time; the scalars baked into the graph are part of the cache key."""
+    ptr = lambda t: t.data_ptr() if t is not None else 0          # (no codebook without a quantiser)
     key = (tuple(x.shape), kw["lr"], tuple(kw["betas"]), kw["eps"], kw["max_norm"], kw["w_l1"], kw["w_cont"], kw["w_var"],
-           kw["epoch"] > 0, kw["draw_masks"], eng.flat.data_ptr(), eng.codebook.data_ptr(), eng.vq_pre_w.data_ptr(),
+           kw["epoch"] > 0, kw["draw_masks"], eng.flat.data_ptr(), ptr(eng.codebook), ptr(eng.vq_pre_w),
            eng.bn_rm.data_ptr(), eng.overlap, tuple((t.data_ptr(), n) for t, n in eng.tracked_counters))
     # one slot per configuration (a data loader's short last batch alternates with the full ones: neither may evict the other),
     # at most _GRAPH_SLOTS of them; eng._iter_graph = the slot of the latest call (tests / check_faults look at it)

@@ -116,7 +116,10 @@ def evaluate_testset(test_data_loader, generator, loss_fn, args) -> float:
         for in_poses, target_poses in test_data_loader:
             batch_size = in_poses.size(0)
             in_poses, target_poses = in_poses.to(device), target_poses.to(device)
-            out_poses, _latent, _loss_vq, _perp = generator(in_poses, target_poses)
+            if generator.vq:
+                out_poses, _latent, _loss_vq, _perp = generator(in_poses, target_poses)
+            else:
+                out_poses, _latent = generator(in_poses, target_poses)
             losses.update(float(loss_fn(out_poses, target_poses)), batch_size)
     generator.train(True)
     logging.info("[VAL] loss: {:.3f} / {:.1f}s".format(losses.avg, time.time() - start))
@@ -134,11 +137,15 @@ def train_epochs(args, train_data_loader, train_sim_dataset, test_data_loader, l
     if _DIST:
         from gesture2vec_amd.dp import GradStatsAllReduce, broadcast_state
         generator.rng_seed = 1234 + _RANK                               # independent dropout masks per shard
-        eng, vq = generator.engine(), generator.vq_layer
-        if generator.quantizer == "ema":
+        eng = generator.engine()
+        if generator.quantizer == "none":       # autoencoder_vq == "False": no quantiser tensors
+            broadcast_state([eng.flat, eng.bn_rm, eng.bn_rv])
+        elif generator.quantizer == "ema":
+            vq = generator.vq_layer
             broadcast_state([eng.flat, vq._embedding.weight.data, vq._ema_w.data, vq._ema_cluster_size,
                              vq.pre_linear.weight.data, vq.pre_linear.bias.data, eng.bn_rm, eng.bn_rv])
         else:       # the soft quantiser (what the reference ships): every trainable tensor lives in the flat buffer; gradients only
+            vq = generator.vq_layer
             broadcast_state([eng.flat, vq.pre_linear.weight.data, vq.pre_linear.bias.data, eng.bn_rm, eng.bn_rv])
         reduce_fn = GradStatsAllReduce()
     val_metrics_list, loss_list = [], []
@@ -177,11 +184,11 @@ def train_epochs(args, train_data_loader, train_sim_dataset, test_data_loader, l
             batch_size = encoded_output.size(0)
             encoded_input, encoded_output = encoded_input.to(device), encoded_output.to(device)
             if _DIST:
-                loss, perplexity = train_iter_Autoencoder_VQ_seq2seq_dp(args, epoch, encoded_input, encoded_output, generator,
-                                                                        gen_optimizer, reduce_fn, _WORLD)
+                ret = train_iter_Autoencoder_VQ_seq2seq_dp(args, epoch, encoded_input, encoded_output, generator,
+                                                           gen_optimizer, reduce_fn, _WORLD)
             else:
-                loss, perplexity = train_iter_Autoencoder_VQ_seq2seq(args, epoch, encoded_input, encoded_output, generator,
-                                                                     gen_optimizer)
+                ret = train_iter_Autoencoder_VQ_seq2seq(args, epoch, encoded_input, encoded_output, generator, gen_optimizer)
+            loss = ret[0] if generator.vq else ret           # (loss, perplexity); without a quantiser the loss dict alone
             loss_epoch.update(loss["loss"], batch_size)
             for m in loss_meters:
                 if m.name in loss:

@@ -48,8 +48,12 @@ def load_checkpoint_and_model(checkpoint_path, _device="cpu", what: str = ""):
     if what == "autoencoder_vq":
         from train_autoencoder_VQVAE import init_model as VQVAE_init
         # the reference as shipped trains the VQ_Payam_GSSoft override (Autoencoder_VQVAE_model.py:816-820): such
-        # checkpoints carry mean_layer / logvar_layer and no EMA buffers; the EMA quantiser has _ema_w / _ema_cluster_size
-        if "vq_layer.mean_layer.weight" in checkpoint["gen_dict"]:
+        # checkpoints carry mean_layer / logvar_layer and no EMA buffers; the EMA quantiser has _ema_w / _ema_cluster_size.
+        # args.autoencoder_vq == "False" (config/seq2seq.yml, e.g. the AI2_11_HQ checkpoint): no vq_layer.* keys, and no
+        # quantiser is guessed -- the model is built without one
+        if getattr(args, "autoencoder_vq", "True") != "True":
+            pass
+        elif "vq_layer.mean_layer.weight" in checkpoint["gen_dict"]:
             args.autoencoder_vq_quantizer = "gssoft"
         elif "vq_layer._ema_w" in checkpoint["gen_dict"]:
             args.autoencoder_vq_quantizer = "ema"
