@@ -241,6 +241,9 @@ _SIGS = {
     "g2v_mask_rows": (c_int, [c_fp, c_i64, c_int, c_i64, c_i64, c_fp, c_f, c_fp, c_i64, c_int, c_int, c_fp]),
     "g2v_transpose": (c_int, [c_fp, c_fp, c_int, c_int, c_fp]),
     "g2v_add_halves": (c_int, [c_fp, c_i64, c_fp, c_i64, c_fp, c_i64, c_i64, c_int, c_fp]),
+    "g2v_moments_workspace": (c_sz, [c_i64, c_int]),
+    "g2v_moments_accumulate": (c_int, [c_fp, c_i64, c_fp, c_fp, c_fp, c_i64, c_int, c_fp, c_sz, c_fp]),
+    "g2v_code_histogram": (c_int, [c_fp, c_i64, c_int, c_fp, c_fp]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -1030,3 +1030,30 @@ def ste(z, q):
     out = torch.empty_like(z)
     check(_lib_().g2v_ste_f32(_p(_chk(z)), _p(_chk(q)), _p(out), z.numel(), _stream()), "ste")
     return out
+
+
+# ------------------------------------------------------------------------------------------ evaluation statistics
+def moments_accumulate(x, shift, s1, s2, *, ld=None):
+    """s1 (E,) f64 += sum_n (x_n - shift), s2 (E,E) f64 += sum_n (x_n - shift)(x_n - shift)^T over the rows of x (N,E) fp32 with row
+    stride ld (g2v_moments_accumulate: fp32 MFMA on the upper triangle, mirrored; deterministic, additive for one shift)."""
+    N, E = x.shape
+    if not x.is_cuda:
+        raise _lib.G2VLibraryError("x must be a GPU tensor: the g2v kernels have no CPU path")
+    if x.dtype != torch.float32 or x.stride(1) != 1:
+        raise TypeError("moments_accumulate: x must be fp32 with unit column stride")
+    ld = int(x.stride(0) if ld is None else ld)
+    lib = _lib_()
+    nb = int(lib.g2v_moments_workspace(N, E))
+    ws = workspace(nb, x.device, "moments")
+    check(lib.g2v_moments_accumulate(_p(x), ld, _p(_chk(shift, name="shift")), _p(_chk(s1, torch.float64, "s1")),
+                                     _p(_chk(s2, torch.float64, "s2")), N, E, _p(ws), nb, _stream()), "moments_accumulate")
+    return s1, s2
+
+
+def code_histogram(idx, K, counts=None):
+    """counts (K+1,) int64 += histogram of the code ids idx (N,) int64; ids outside [0, K) land in counts[K] (g2v_code_histogram)."""
+    if counts is None:
+        counts = torch.zeros((K + 1,), dtype=torch.int64, device=idx.device)
+    check(_lib_().g2v_code_histogram(_p(_chk(idx, torch.int64, "idx")), idx.numel(), int(K), _p(_chk(counts, torch.int64, "counts")),
+                                     _stream()), "code_histogram")
+    return counts

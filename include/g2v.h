@@ -960,6 +960,22 @@ int g2v_transpose(const float* in, float* out, int rows, int cols, g2v_stream_t 
 int g2v_add_halves(const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldo,
                    int64_t M, int H, g2v_stream_t stream);
 
+/* ---- evaluation statistics (metrics.hip; gesture2vec_amd/metrics.py) ----------------------------------------------------------
+ * Shifted first and second moments of the rows of x (N x E fp32, row stride ld >= E elements), ADDED to float64 accumulators:
+ *   s1[E]    += sum_n (x_n - shift)
+ *   s2[E][E] += sum_n (x_n - shift)(x_n - shift)^T     stored full: the upper triangle is computed (fp32 MFMA, exact fp32 products)
+ *                                                       and mirrored, so s2[i][j] == s2[j][i] bit for bit.
+ * x - shift is rounded once to fp32; fp32 accumulation chains are at most 1024 rows long and are folded into float64 in a fixed
+ * order: no floating-point atomics, the same input gives the same bits.  The sums are additive over calls (and over ranks) that use
+ * the same shift.  1 <= E <= 512 (G2V_ERR_UNSUPPORTED beyond), any N >= 1.  x is read once for E <= 400, twice for wider rows.
+ * workspace: g2v_moments_workspace(N, E) bytes, 16-byte aligned; its contents are not trusted across calls. */
+size_t g2v_moments_workspace(int64_t N, int E);
+int g2v_moments_accumulate(const float* x, int64_t ld, const float* shift, double* s1, double* s2, int64_t N, int E,
+                           void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+/* counts[k] += #{n : idx[n] == k} for k < K; ids outside [0, K) are counted in counts[K] and never used as an address.
+ * counts: int64[K + 1].  Integer atomics only: exact and order-independent. */
+int g2v_code_histogram(const int64_t* idx, int64_t N, int K, int64_t* counts, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
