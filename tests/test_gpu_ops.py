@@ -1933,7 +1933,7 @@ def test_every_workspace_user_stays_inside_its_reported_size(ops, monkeypatch):
     """Each op that takes a caller-owned workspace is run on a buffer of EXACTLY the size its query reports, with a guard band
     behind it (ops.workspace is patched to hand those out): rollout forward / backward on the persistent path incl. the fused
     weight gradient's slabs, the GRU's fused weight-gradient slabs, weight gradients (batched, ragged), the sorted embedding
-    gradient, bulk code assignment, code statistics, attention backward."""
+    gradient, bulk code assignment, code statistics, attention backward, the soft quantiser's perplexity."""
     from gesture2vec_amd import _lib
     from gesture2vec_amd import ops as ops_mod
     lib = _lib.load()
@@ -2000,9 +2000,22 @@ def test_every_workspace_user_stays_inside_its_reported_size(ops, monkeypatch):
     hp, v = torch.randn(Ba, H, device=DEV), torch.randn(H, device=DEV)
     wts, ctx = ops.attn_fwd(hp, ep, enc, v)
     ops.attn_bwd(torch.randn(Ba, H, device=DEV), hp, ep, enc, v, wts)
+    # the soft quantiser's two-launch perplexity takes its workspace from the caller directly: N % 16 != 0, a ragged last block
+    Np, Kp = 517, 512
+    probs = torch.softmax(torch.randn(Np, Kp, generator=g), dim=1).to(DEV)
+    nb = int(lib.g2v_vq_soft_perplexity_workspace(Np, Kp))
+    assert nb > 0
+    pws = torch.full((nb + GUARD,), PAT, dtype=torch.uint8, device=DEV)
+    perp = torch.zeros(1, device=DEV)
+    _lib.check(lib.g2v_vq_soft_perplexity(probs.data_ptr(), perp.data_ptr(), Np, Kp, pws.data_ptr(), nb,
+                                          torch.cuda.current_stream().cuda_stream), "vq_soft_perplexity")
+    slabs.append((nb, pws))
+    avg = probs.double().mean(0)
+    perp_ref = float(torch.exp(-(avg * torch.log(avg + 1e-10)).sum()))
     torch.cuda.synchronize()
+    assert abs(float(perp) - perp_ref) <= 1e-5 * perp_ref
     assert len(handed) >= 10
     for tag, nbytes, buf in handed:
         assert int((buf[nbytes:] != PAT).sum()) == 0, f"{tag}: wrote past its {nbytes}-byte workspace"
     for nb, slab in slabs:
-        assert int((slab[nb:] != PAT).sum()) == 0, "GRU weight-gradient slabs overran"
+        assert int((slab[nb:] != PAT).sum()) == 0, "GRU weight-gradient slabs / perplexity partials overran"

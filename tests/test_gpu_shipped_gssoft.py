@@ -109,16 +109,28 @@ def test_reference_checkpoint_file_loads_and_reproduces_eval(golden_dir):
     _eval_check(net, fx, B, T, D)
 
 
-@pytest.mark.parametrize("B,p,mode", [(64, 0.0, "eager"), (48, 0.2, "eager"), (1024, 0.0, "graph")])
-def test_fused_soft_quantiser_step_equals_the_autograd_path(B, p, mode, monkeypatch):
+@pytest.mark.parametrize("B,p,mode,hidden", [
+    pytest.param(64, 0.0, "eager", None, id="64-0.0-eager"), pytest.param(48, 0.2, "eager", None, id="48-0.2-eager"),
+    pytest.param(1024, 0.0, "graph", None, id="1024-0.0-graph"), pytest.param(96, 0.0, "eager", 200, id="96-0.0-eager-h200")])
+def test_fused_soft_quantiser_step_equals_the_autograd_path(B, p, mode, hidden, monkeypatch):
     """Three iterations of train_iter with the soft quantiser: the engine's kernel sequence (eager, and replayed from the hipGraph
     train_iter captures at large batch) against the module-level autograd path over the same kernels.  Same products, same
-    element-wise kernels; the codebook gradient's two addends meet in the other order, so weights agree to fp32 rounding."""
+    element-wise kernels; the codebook gradient's two addends meet in the other order, so weights agree to fp32 rounding.
+    hidden = 200: the shipped width E = 400, which csrc/vq_soft.hip does not serve -- the engine's non-fused forward and
+    _backward_gssoft_chain."""
+    from gesture2vec_amd import _lib
     from gesture2vec_amd.model.Autoencoder_VQVAE_model import Autoencoder_VQVAE
     from gesture2vec_amd.train_eval.train_seq2seq import FusedClipAdam, train_iter_Autoencoder_VQ_seq2seq
     import bench
     args = bench.model_args()
     args.autoencoder_vq_quantizer = "gssoft"
+    if hidden is not None:
+        args.hidden_size = hidden
+        E = hidden * args.n_layers
+        assert E == 400 and _lib.load().g2v_vq_soft_fused_ok((2 * B * hidden) // E, E, args.autoencoder_vq_components) == 0
+    else:
+        E = args.hidden_size * args.n_layers
+        assert _lib.load().g2v_vq_soft_fused_ok((2 * B * args.hidden_size) // E, E, args.autoencoder_vq_components) == 1
     args.dropout_prob = p
     args.loss_l1_weight, args.loss_cont_weight, args.loss_var_weight, args.learning_rate = 5.0, 0.1, 0.5, 5e-4
     T, D = 34, 135

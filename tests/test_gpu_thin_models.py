@@ -210,11 +210,15 @@ def test_vq_gssoft_matches_reference_golden(golden_dir):
                 assert dict(q.named_parameters())[k[len(f"c{i}/gradnone/"):]].grad is None
 
 
-@pytest.mark.parametrize("N,K,scale", [(4096, 512, 0.3), (100, 512, 1.0), (37, 1024, 0.1), (16, 128, 0.5)])
-def test_fused_soft_quantiser_kernels_equal_the_separate_kernels(N, K, scale):
+@pytest.mark.parametrize("N,K,scale,lv", [
+    pytest.param(4096, 512, 0.3, (0.3, 0.1), id="4096-512-0.3"), pytest.param(100, 512, 1.0, (0.3, 0.1), id="100-512-1.0"),
+    pytest.param(37, 1024, 0.1, (0.3, 0.1), id="37-1024-0.1"), pytest.param(16, 128, 0.5, (0.3, 0.1), id="16-128-0.5"),
+    pytest.param(17, 1024, 0.3, (0.3, 0.1), id="17-1024-0.3"), pytest.param(1030, 512, 1.0, (1.0, 1.25), id="1030-512-1.0-peaked")])
+def test_fused_soft_quantiser_kernels_equal_the_separate_kernels(N, K, scale, lv):
     """csrc/vq_soft.hip (one launch forward, one backward) against the sequence of separate launches it replaces (dense products,
     vq_soft_fwd / _bwd, rowscale_combine, mse, ste, vq_bwd): same element-wise expressions, K- and E-long sums in another order.
-    N % 16 != 0 exercises the ragged row tile."""
+    N % 16 != 0 exercises the ragged row tile.  lv = (weight, bias) scale of logvar_layer: (0.3, 0.1) keeps s = exp(-2 logvar) near 1,
+    the peaked set spreads it over orders of magnitude (both routes against float64: tests/test_gpu_soft_quantiser.py)."""
     from gesture2vec_amd import ops
     E, beta, gs = 128, 0.25, 0.7
     assert ops.vq_soft_fused_ok(N, E, K) and not ops.vq_soft_fused_ok(N, 400, K) and not ops.vq_soft_fused_ok(N, E, 400)
@@ -222,7 +226,7 @@ def test_fused_soft_quantiser_kernels_equal_the_separate_kernels(N, K, scale):
     r = lambda *s, m=1.0: (torch.randn(*s, generator=g) * m).to(DEV)
     x = r(N, E, m=scale)
     Wm, bm = r(E, E, m=E ** -0.5), r(E, m=0.1)
-    Wl, bl = r(K, E, m=0.3 * E ** -0.5), r(K, m=0.1)
+    Wl, bl = r(K, E, m=lv[0] * E ** -0.5), r(K, m=lv[1])
     W = r(K, E, m=scale)
     dh, gl = r(N, E, m=1e-3), torch.full((1,), 0.4, device=DEV)
     # ---- the separate kernels ---------------------------------------------------------------------------------------------------
