@@ -244,6 +244,16 @@ _SIGS = {
     "g2v_moments_workspace": (c_sz, [c_i64, c_int]),
     "g2v_moments_accumulate": (c_int, [c_fp, c_i64, c_fp, c_fp, c_fp, c_i64, c_int, c_fp, c_sz, c_fp]),
     "g2v_code_histogram": (c_int, [c_fp, c_i64, c_int, c_fp, c_fp]),
+    "g2v_kmeans_update_workspace": (c_sz, [c_i64, c_int, c_int]),
+    "g2v_kmeans_update": (c_int, [c_fp, c_fp, c_fp, c_fp, c_i64, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz,
+                                  c_fp]),
+    "g2v_kmeans_commit": (c_int, [c_fp, c_fp, c_fp, c_i64, c_fp, c_fp, c_i64, c_fp]),
+    "g2v_kmeans_tolerance_workspace": (c_sz, [c_i64, c_int]),
+    "g2v_kmeans_tolerance": (c_int, [c_fp, c_i64, c_int, C.c_double, c_fp, c_fp, c_sz, c_fp]),
+    "g2v_kmeans_pp_blocks": (c_int, [c_i64]),
+    "g2v_kmeans_pp_workspace": (c_sz, [c_i64, c_int]),
+    "g2v_kmeans_pp_step": (c_int, [c_fp, c_i64, c_int, c_fp, C.POINTER(c_i64), C.POINTER(C.c_double), c_int, c_fp, c_fp, c_fp, c_sz,
+                                   c_fp]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -197,7 +197,7 @@ class TrinityDataset_sentencelevel:
         return lmdb_dir + suffix
 
     def __init__(self, args, lmdb_dir: str, n_poses: int, subdivision_stride: int, pose_resampling_fps: int,
-                 data_mean: Sequence[float], data_std: Sequence[float], lang_model=None, vq_net=None):
+                 data_mean: Sequence[float], data_std: Sequence[float], lang_model=None, vq_net=None, kmeans=None):
         preloaded_dir = self.cache_dir(args, lmdb_dir)
         if not os.path.exists(preloaded_dir):
             raise FileNotFoundError(f"{preloaded_dir}: the sentence-level cache is produced by the reference's DataPreprocessor "
@@ -207,6 +207,7 @@ class TrinityDataset_sentencelevel:
         self.data_mean = np.array(data_mean, dtype=np.float64).squeeze()
         self.data_std = np.array(data_std, dtype=np.float64).squeeze()
         self.lang_model, self.vq_net = lang_model, vq_net
+        self.kmeans = kmeans               # gesture2vec_amd.kmeans.KMeans: the cluster ids of an autoencoder without a vq_layer (:1287-1292)
 
     def set_lang_model(self, lang_model) -> None:
         self.lang_model = lang_model
@@ -260,6 +261,10 @@ class TrinityDataset_sentencelevel:
             lat_d = lat.to(device, non_blocking=True)
             B, S, E = lat_d.shape
             rows = lat_d.reshape(B * S, E).contiguous()
+            vq_layer = getattr(self.vq_net, "vq_layer", None)
+            if vq_layer is None and self.kmeans is not None:               # quantiser-free autoencoder: kmeanmodel.predict (:1287-1292)
+                yield words, lengths, poses, audio, aux, lat_d, self.kmeans.predict_device(rows).view(B, S), gpt3
+                continue
             assign = getattr(self.vq_net.vq_layer, "assign", None)         # one launch sequence for the batch
             if assign is not None:
                 codes = assign(rows).view(B, S)

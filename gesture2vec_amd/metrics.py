@@ -8,8 +8,9 @@
   the two code histograms (g2v_code_histogram: exact integer counts).
 
 The reference does all of it on the host with numpy / scipy / sklearn on latents pulled off the device chunk by chunk; nothing here
-needs scipy or sklearn.  Out of scope: BLEU over code sequences (`:1560-1609`, host string work on `torchtext`), t-SNE, k-means and
-the plots."""
+needs scipy or sklearn.  For an autoencoder without a quantiser the code ids come from a fitted `gesture2vec_amd.kmeans.KMeans`
+(`kmeans=`), as the reference takes them from its pickled k-means model.  Out of scope: BLEU over code sequences (`:1560-1609`, host
+string work on `torchtext`), t-SNE and the plots."""
 from __future__ import annotations
 
 from typing import Callable, Optional
@@ -178,7 +179,7 @@ def wasserstein(h1, h2) -> float:
 
 
 @torch.no_grad()
-def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int]):
+def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int], kmeans=None):
     from . import ops
     mom, counts = None, None
     for a in range(0, chunks.shape[0], batch_rows):
@@ -191,7 +192,7 @@ def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int]):
             mom = LatentMoments(lat.shape[1], lat.device)
         mom.update(lat)
         if K is not None:
-            counts = ops.code_histogram(net.vq_layer.assign(lat), K, counts)
+            counts = ops.code_histogram(kmeans.predict_device(lat) if kmeans is not None else net.vq_layer.assign(lat), K, counts)
     if K is not None:
         counts = counts.cpu().numpy()
         if counts[K]:
@@ -201,16 +202,21 @@ def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int]):
 
 
 @torch.no_grad()
-def gesture_metrics(net, real_chunks: torch.Tensor, generated_chunks: torch.Tensor, dae=None, batch_rows: int = 65536) -> dict:
+def gesture_metrics(net, real_chunks: torch.Tensor, generated_chunks: torch.Tensor, dae=None, batch_rows: int = 65536,
+                    kmeans=None) -> dict:
     """Both (N, T, D) chunk sets -> [dae.encode per frame ->] chunk_latents -> moments (+ vq_layer.assign -> histogram), streamed in
-    batches of `batch_rows` chunks.  A net without a quantiser gives the Frechet distance and None for the code metrics."""
+    batches of `batch_rows` chunks.  A net without a quantiser gives the Frechet distance and None for the code metrics, unless a
+    fitted `kmeans` (gesture2vec_amd.kmeans.KMeans) is given: its ids then fill the histogram columns."""
     _need_cuda(real_chunks, "gesture_metrics")
     _need_cuda(generated_chunks, "gesture_metrics")
     if real_chunks.shape[0] == 0 or generated_chunks.shape[0] == 0:
         raise ValueError("gesture_metrics: an empty chunk set")
-    K = int(net.vq_layer._num_embeddings) if getattr(net, "vq", True) else None
-    m_r, h_r = _scan(net, real_chunks, dae, int(batch_rows), K)
-    m_g, h_g = _scan(net, generated_chunks, dae, int(batch_rows), K)
+    if getattr(net, "vq", True):
+        K, kmeans = int(net.vq_layer._num_embeddings), None
+    else:
+        K = None if kmeans is None else int(kmeans.n_clusters)
+    m_r, h_r = _scan(net, real_chunks, dae, int(batch_rows), K, kmeans)
+    m_g, h_g = _scan(net, generated_chunks, dae, int(batch_rows), K, kmeans)
     n_r, mu_r, cov_r = m_r.finalize()
     n_g, mu_g, cov_g = m_g.finalize()
     out = {"frechet": frechet_distance(mu_r, cov_r, mu_g, cov_g), "hellinger": None, "perplexity_real": None,

@@ -1057,3 +1057,82 @@ def code_histogram(idx, K, counts=None):
     check(_lib_().g2v_code_histogram(_p(_chk(idx, torch.int64, "idx")), idx.numel(), int(K), _p(_chk(counts, torch.int64, "counts")),
                                      _stream()), "code_histogram")
     return counts
+
+
+# ------------------------------------------------------------------------------------------ k-means (kmeans.hip)
+KMEANS_STATE = ("done", "n_iter", "n_changed", "shift", "inertia", "n_relocated", "active", "tol_abs")   # the float64[8] state block
+
+
+def kmeans_update(x, labels, centers, prev_labels=None, *, relocate=True, state=None, out=None):
+    """One Lloyd update (g2v_kmeans_update): x (N,E) fp32, labels (N) int64, centers (K,E) -> dict(counts (K) int64, sums (K,E) f64,
+    centers_new (K,E) fp32, stats (4) f64 = [inertia vs `centers`, shift, n_changed, n_relocated], relocated_rows (K) int64).
+    `out`: the dict of an earlier call, written again.  `state`: the (8,) float64 device block (KMEANS_STATE) that gates the call."""
+    N, E = x.shape
+    K = centers.shape[0]
+    dev = x.device
+    if out is None:
+        out = {"counts": torch.empty((K,), dtype=torch.int64, device=dev), "sums": torch.empty((K, E), dtype=torch.float64, device=dev),
+               "centers_new": torch.empty((K, E), dtype=torch.float32, device=dev),
+               "stats": torch.zeros((4,), dtype=torch.float64, device=dev),
+               "relocated_rows": torch.full((K,), -1, dtype=torch.int64, device=dev)}
+    for key, shape, dtype in (("counts", (K,), torch.int64), ("sums", (K, E), torch.float64), ("centers_new", (K, E), torch.float32),
+                              ("stats", (4,), torch.float64), ("relocated_rows", (K,), torch.int64)):
+        if tuple(_chk(out[key], dtype, key).shape) != shape:
+            raise ValueError(f"kmeans_update: out[{key!r}] must have shape {shape}, got {tuple(out[key].shape)}")
+    if labels.numel() != N or (prev_labels is not None and prev_labels.numel() != N) or centers.shape[1] != E:
+        raise ValueError("kmeans_update: labels / prev_labels must hold N ids and centers must be (K, E)")
+    lib = _lib_()
+    nb = int(lib.g2v_kmeans_update_workspace(N, E, K))
+    ws = workspace(nb, dev, "kmeans")
+    check(lib.g2v_kmeans_update(_p(_chk(x, name="x")), _p(_chk(labels, torch.int64, "labels")),
+                                _p(None if prev_labels is None else _chk(prev_labels, torch.int64, "prev_labels")),
+                                _p(_chk(centers, name="centers")), N, E, K, 1 if relocate else 0, _p(out["counts"]), _p(out["sums"]),
+                                _p(out["centers_new"]), _p(out["stats"]), _p(out["relocated_rows"]),
+                                _p(None if state is None else _chk(state, torch.float64, "state")), _p(ws), nb, _stream()),
+          "kmeans_update")
+    return out
+
+
+def kmeans_commit(state, centers_new, centers, labels_new=None, labels=None):
+    """centers <- centers_new, labels <- labels_new when the last g2v_kmeans_update on `state` ran (g2v_kmeans_commit)."""
+    if centers_new.shape != centers.shape or (labels is None) != (labels_new is None):
+        raise ValueError("kmeans_commit: centers_new / centers must match in shape, labels_new / labels come together")
+    if labels is not None:
+        _chk(labels_new, torch.int64, "labels_new")
+        _chk(labels, torch.int64, "labels")
+        if labels_new.numel() != labels.numel():
+            raise ValueError("kmeans_commit: labels_new and labels differ in length")
+    check(_lib_().g2v_kmeans_commit(_p(_chk(state, torch.float64, "state")), _p(_chk(centers_new, name="centers_new")),
+                                    _p(_chk(centers, name="centers")), centers.numel(), _p(labels_new), _p(labels),
+                                    0 if labels is None else labels.numel(), _stream()), "kmeans_commit")
+
+
+def kmeans_tolerance(x, tol, out=None):
+    """(1,) float64 = tol * mean_e Var(x_e) (g2v_kmeans_tolerance; sklearn's _tolerance)."""
+    N, E = x.shape
+    if out is None:
+        out = torch.empty((1,), dtype=torch.float64, device=x.device)
+    lib = _lib_()
+    nb = int(lib.g2v_kmeans_tolerance_workspace(N, E))
+    ws = workspace(nb, x.device, "kmeans_tol")
+    check(lib.g2v_kmeans_tolerance(_p(_chk(x, name="x")), N, E, float(tol), _p(out), _p(ws), nb, _stream()), "kmeans_tolerance")
+    return out
+
+
+def kmeans_pp_blocks(N) -> int:
+    return int(_lib_().g2v_kmeans_pp_blocks(int(N)))
+
+
+def kmeans_pp_step(x, closest, pick_block, pick_resid, out, center_out):
+    """One greedy k-means++ step (g2v_kmeans_pp_step).  pick_block / pick_resid: host sequences (pick_resid None: pick_block holds the
+    candidate rows themselves); out (blocks + 11,) float64; center_out (E,) fp32."""
+    N, E = x.shape
+    n = len(pick_block)
+    blk = (C.c_int64 * n)(*[int(b) for b in pick_block])
+    res = None if pick_resid is None else (C.c_double * n)(*[float(r) for r in pick_resid])
+    lib = _lib_()
+    nb = int(lib.g2v_kmeans_pp_workspace(N, E))
+    ws = workspace(nb, x.device, "kmeans_pp")
+    check(lib.g2v_kmeans_pp_step(_p(_chk(x, name="x")), N, E, _p(_chk(closest, torch.float64, "closest")), blk, res, n,
+                                 _p(_chk(out, torch.float64, "out")), _p(_chk(center_out)), _p(ws), nb, _stream()), "kmeans_pp_step")
+    return out

@@ -33,9 +33,13 @@ def chunk_latents(net, chunks: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def chunks_to_codes(net, chunks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """(N,T,D) pose chunks -> (latents (N,L*H), code ids (N,) int64) with the net's EMA codebook."""
+def chunks_to_codes(net, chunks: torch.Tensor, kmeans=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(N,T,D) pose chunks -> (latents (N,L*H), code ids (N,) int64) with the net's EMA codebook; for a net without a quantiser,
+    with the fitted `kmeans` (gesture2vec_amd.kmeans.KMeans: the reference's `kmeanmodel.predict(latents)`)."""
     if not getattr(net, "vq", True):
+        if kmeans is not None:
+            lat = chunk_latents(net, chunks)
+            return lat, kmeans.predict_device(lat)
         raise ValueError("chunks_to_codes: this autoencoder has no quantiser (autoencoder_vq == 'False'), so there are no codes "
                          "to assign; chunk_latents gives its latent rows")
     lat = chunk_latents(net, chunks)

@@ -976,6 +976,52 @@ int g2v_moments_accumulate(const float* x, int64_t ld, const float* shift, doubl
  * counts: int64[K + 1].  Integer atomics only: exact and order-independent. */
 int g2v_code_histogram(const int64_t* idx, int64_t N, int K, int64_t* counts, g2v_stream_t stream);
 
+/* ---- k-means over latent rows (kmeans.hip; gesture2vec_amd/kmeans.py) -------------------------------------------------------------
+ * The reference fits sklearn.cluster.KMeans on the (N, L*H) chunk latents of a quantiser-free autoencoder (Clustering.py:705-725) and
+ * calls kmeanmodel.predict for Part d's cluster ids (lmdb_data_loader.py:1097-1103).  The assignment half of a Lloyd iteration is
+ * g2v_vq_assign_fwd / g2v_vq_assign_packed_fwd (exact fp32 argmin, lowest index on ties); the rest is here.
+ *
+ * g2v_kmeans_update: x (N,E) fp32, labels (N) int64 (ids outside [0,K) are ignored), prev_labels (N) or NULL, centers_old (K,E) ->
+ *   counts[K] int64, sums[K][E] float64, centers_new[K][E] = (float)(sum / count) (a cluster without rows keeps centers_old),
+ *   stats[4] float64 = { inertia = sum_n |x_n - centers_old[label_n]|^2 (from the rows, not from an assign kernel's distances),
+ *                        shift = sum_k |centers_new_k - centers_old_k|^2, n_changed = #{n: labels[n] != prev_labels[n]} (N when
+ *                        prev_labels is NULL), n_relocated }.
+ *   x is read once through an inverted index (stable counting sort of the row ids by label); lists are cut into chunks of 512 rows,
+ *   one wave sums a chunk in float64 and the chunks of a cluster are added in chunk order: no floating-point atomics, the same input
+ *   gives the same bits.  relocate != 0: sklearn's _relocate_empty_clusters_dense in a fixed order -- the empty clusters in ascending
+ *   id take the n_empty rows with the largest |x - centers_old[label]|^2, farthest first, lowest row among equals; a chosen row leaves
+ *   its cluster's sum and count and becomes the empty cluster's sum with count 1; labels are not touched.  relocated_rows (may be
+ *   NULL): its first n_relocated entries receive the chosen rows.
+ *   state (may be NULL): float64[8] = { done, n_iter, n_changed, shift, inertia, n_relocated, active, tol_abs }, zeroed by the caller
+ *   before a fit except tol_abs.  With a state block the call is a NO-OP once done != 0 (active = 0 then); otherwise it adds 1 to
+ *   n_iter, stores the scalars, sets active = 1, and sets done when prev_labels was given and no label changed, or shift <= tol_abs.
+ *   g2v_kmeans_commit copies centers_new -> centers and labels_new -> labels (either labels pointer may be NULL) when active != 0:
+ *   a host may enqueue several assign / update / commit rounds per read-back and what it reads is the state at convergence.
+ *   Needs E % 4 == 0, E <= 512 (G2V_ERR_UNSUPPORTED otherwise), 1 <= N < 2^31 - 2048, K >= 1; x, centers_old 16-byte aligned.
+ * g2v_kmeans_tolerance: out[0] = tol * mean_e Var(x_e) (population variance; float64 column moments in one pass, fixed order).
+ * g2v_kmeans_pp_step: one greedy k-means++ step (sklearn _kmeans_plusplus) over ncand <= 8 candidate rows.  closest (N) float64 holds
+ *   the running squared distance to the nearest chosen centre (+inf before the first).  The rows are cut into g2v_kmeans_pp_blocks(N)
+ *   blocks of 1024; candidate t is the first row of block pick_block[t] at which the running sum of closest[] over that block reaches
+ *   pick_resid[t] (the last row of the block if none does) -- the host finds the block from the block sums of the previous step; with
+ *   pick_resid == NULL pick_block[t] is the candidate row itself.  pick_block / pick_resid are HOST arrays, read at launch.
+ *   d_t[n] = min(closest[n], |x_n - x_cand(t)|^2) in float64, potential_t = sum_n d_t[n]; the candidate with the lowest potential
+ *   (lowest t among equals) wins: closest = d_best, center_out[E] = its row.
+ *   out: float64[blocks + 11] = { block sums of the new closest[], potential_0..7, best t, chosen row, its potential }. */
+size_t g2v_kmeans_update_workspace(int64_t N, int E, int K);
+int g2v_kmeans_update(const float* x, const int64_t* labels, const int64_t* prev_labels, const float* centers_old,
+                      int64_t N, int E, int K, int relocate, int64_t* counts, double* sums, float* centers_new,
+                      double* stats, int64_t* relocated_rows, double* state, void* workspace, size_t workspace_bytes,
+                      g2v_stream_t stream);
+int g2v_kmeans_commit(const double* state, const float* centers_new, float* centers, int64_t n_center_elems,
+                      const int64_t* labels_new, int64_t* labels, int64_t N, g2v_stream_t stream);
+size_t g2v_kmeans_tolerance_workspace(int64_t N, int E);
+int g2v_kmeans_tolerance(const float* x, int64_t N, int E, double tol, double* out, void* workspace, size_t workspace_bytes,
+                         g2v_stream_t stream);
+int g2v_kmeans_pp_blocks(int64_t N);
+size_t g2v_kmeans_pp_workspace(int64_t N, int E);
+int g2v_kmeans_pp_step(const float* x, int64_t N, int E, double* closest, const int64_t* pick_block, const double* pick_resid,
+                       int ncand, double* out, float* center_out, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

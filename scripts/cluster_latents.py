@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Fits the k-means model a quantiser-free chunk autoencoder (`autoencoder_vq: False`) needs downstream, on the MI355X kernels
+(gesture2vec_amd/kmeans.py): the reference's `Clustering.py:705-725`.
+
+    python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy [--n_clusters 300] [--scan-k 50:400:50]
+
+`--chunks` holds (N, T, D) pose chunks in the autoencoder's input space.  Their latents (`chunk_latents`) are clustered with
+`KMeans(n_clusters, max_iter=2500, random_state=0)` and the model is pickled to `<checkpoint dir>/clusters/kmeans_model.pk`, where the
+reference's data loader and inference script look for it; `n_iter`, inertia and the code-usage perplexity are printed.
+`--scan-k a:b:step` prints the inertia curve of `Clustering.py:586-600` (`init="random", n_init=10, max_iter=300` per k) instead of
+writing a model.  The silhouette curve of that scan is not computed."""
+from __future__ import annotations
+
+import argparse
+import os
+import pickle
+import sys
+
+import numpy as np
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(_HERE)
+for _p in (_HERE, _ROOT):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from utils.train_utils import load_checkpoint_and_model  # noqa: E402
+from gesture2vec_amd.kmeans import KMeans  # noqa: E402
+from gesture2vec_amd.pipeline import chunk_latents  # noqa: E402
+
+
+@torch.no_grad()
+def latents_of(net, chunks: torch.Tensor, batch_rows: int) -> torch.Tensor:
+    return torch.cat([chunk_latents(net, chunks[a:a + batch_rows]) for a in range(0, chunks.shape[0], batch_rows)])
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--checkpoint", required=True, help="chunk autoencoder checkpoint (train_autoencoder_VQVAE.py)")
+    ap.add_argument("--chunks", required=True, help=".npy of (N, T, D) pose chunks")
+    ap.add_argument("--n_clusters", type=int, default=300)
+    ap.add_argument("--max_iter", type=int, default=2500)
+    ap.add_argument("--n_init", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--check_every", type=int, default=4, help="Lloyd iterations enqueued per convergence read-back")
+    ap.add_argument("--scan-k", dest="scan_k", default=None, help="a:b:step -- print the inertia per k instead of writing a model")
+    ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk)")
+    ap.add_argument("--batch_rows", type=int, default=65536)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    dev = torch.device(a.device)
+    _, net, _, _, _ = load_checkpoint_and_model(a.checkpoint, dev, "autoencoder_vq")
+    net.eval()
+    chunks = torch.from_numpy(np.load(a.chunks).astype(np.float32, copy=False)).to(dev)
+    lat = latents_of(net, chunks, a.batch_rows)
+    print(f"latents: {tuple(lat.shape)}")
+    if a.scan_k:
+        lo, hi, step = (int(v) for v in a.scan_k.split(":"))
+        curve = []
+        for k in range(lo, hi, step):
+            km = KMeans(n_clusters=k, init="random", n_init=10, max_iter=300, random_state=a.seed, check_every=a.check_every).fit(lat)
+            curve.append((k, km.inertia_))
+            print(f"k = {k}: inertia {km.inertia_!r}")
+        return curve
+    km = KMeans(n_clusters=a.n_clusters, n_init=a.n_init, max_iter=a.max_iter, random_state=a.seed, check_every=a.check_every).fit(lat)
+    out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "clusters", "kmeans_model.pk")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "wb") as f:
+        pickle.dump(km, f)
+    print(f"n_iter: {km.n_iter_}")
+    print(f"inertia: {km.inertia_!r}")
+    print(f"code-usage perplexity: {km.code_perplexity()!r} of {km.n_clusters}")
+    print(f"wrote {out}")
+    return km
+
+
+if __name__ == "__main__":
+    main()
