@@ -619,6 +619,20 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// torch.argmin semantics (the reference's :1259): lowest index among equal minima; a NaN distance counts as smaller than every
+// number and the FIRST NaN wins.  A candidate therefore beats the incumbent when it is smaller, or when it is NaN and the
+// incumbent is not; on a tie (equal values, or both NaN) the lower index stays.  No sentinel index ever leaves a kernel:
+// the running pair starts at (+inf, code 0), so an all-+inf row resolves to code 0 exactly like torch.
+// One definition for every assignment kernel (vq.hip, vq_bulk_z.hip): their routes are compared bitwise.
+__device__ __forceinline__ bool argmin_better(float d2, float d) { return d2 < d || (d2 != d2 && d == d); }
+__device__ __forceinline__ void argmin_merge(float& d, int& k, float d2, int k2) {
+  const bool tie = (d2 == d) || (d2 != d2 && d != d);
+  if (argmin_better(d2, d) || (tie && k2 < k)) {
+    d = d2;
+    k = k2;
+  }
+}
+
 // ---- custom_loss (train_eval/train_seq2seq.py:40-88) gradient, in the one form every kernel that produces it uses (misc.hip's
 // custom_loss kernels and the persistent rollouts, which fold the loss in): bitwise identical results by construction.
 //   d loss / d y[t,b,d] = c1 sign(y_t - tgt_t) + c2 sign(y_t - y_{t-1}) - c2 sign(y_{t+1} - y_t) - c3 y_t / ||y[:,b,d]||_2

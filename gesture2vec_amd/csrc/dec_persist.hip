@@ -14,6 +14,7 @@
 //               Dropout(0.95) -> pre_linear -> partial sums -> publish
 #define G2V_PERSIST_DEVICE_CODE      // this translation unit owns the fault latch (dec_persist.hpp)
 #include "dec_persist.hpp"
+#include "gru_cells.hpp"
 #include <utility>
 #ifndef G2V_BWD_EPI
 #define G2V_BWD_EPI 1
@@ -193,11 +194,11 @@ __device__ __forceinline__ void cell_epilogue(const f32x4 (&ai)[3], const f32x4 
   float hn[4], xd[4], gr_[4], gz_[4], gn_[4], gh_[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float rr = sigmoidf_((ai[0][r] + bir[r]) + (ah[0][r] + bhr[r]));
-    const float zz = sigmoidf_((ai[1][r] + biz[r]) + (ah[1][r] + bhz[r]));
+    const float rr = gru_gate_rz(ai[0][r] + bir[r], ah[0][r] + bhr[r]);
+    const float zz = gru_gate_rz(ai[1][r] + biz[r], ah[1][r] + bhz[r]);
     const float ghn = ah[2][r] + bhn[r];
-    const float nn = tanhf_((ai[2][r] + bin[r]) + rr * ghn);
-    hn[r] = (1.0f - zz) * nn + zz * hp[r];
+    const float nn = gru_gate_n(ai[2][r] + bin[r], rr, ghn);
+    hn[r] = gru_h_new(zz, nn, hp[r]);
     xd[r] = drop ? (((kp >> (8 * r)) & 0xffu) ? hn[r] * keep_scale : 0.f) : hn[r];
     gr_[r] = rr; gz_[r] = zz; gn_[r] = nn; gh_[r] = ghn;
   }
@@ -1377,17 +1378,7 @@ __device__ __forceinline__ float4 cell_bwd(const float (&dh)[4], const CellSaved
   const float rr[4] = {c.r.x, c.r.y, c.r.z, c.r.w}, zz[4] = {c.z.x, c.z.y, c.z.z, c.z.w}, nn[4] = {c.n.x, c.n.y, c.n.z, c.n.w},
               gh[4] = {c.hn.x, c.hn.y, c.hn.z, c.hn.w}, hp[4] = {c.hp.x, c.hp.y, c.hp.z, c.hp.w};
   float g_r[4], g_z[4], g_n[4], g_hn[4], direct[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float dn = dh[r] * (1.0f - zz[r]);
-    const float dz = dh[r] * (hp[r] - nn[r]);
-    const float dnp = dn * (1.0f - nn[r] * nn[r]);
-    g_n[r] = dnp;
-    g_hn[r] = dnp * rr[r];
-    g_r[r] = dnp * gh[r] * rr[r] * (1.0f - rr[r]);
-    g_z[r] = dz * zz[r] * (1.0f - zz[r]);
-    direct[r] = dh[r] * zz[r];
-  }
+  gru_gates_bwd4(dh, rr, zz, nn, gh, hp, g_r, g_z, g_n, g_hn, direct);
   const float4 vr = make_float4(g_r[0], g_r[1], g_r[2], g_r[3]), vz = make_float4(g_z[0], g_z[1], g_z[2], g_z[3]),
                vn = make_float4(g_n[0], g_n[1], g_n[2], g_n[3]), vh = make_float4(g_hn[0], g_hn[1], g_hn[2], g_hn[3]);
   if (store) {

@@ -188,6 +188,50 @@ __device__ __forceinline__ void cx_publish4(__amdgpu_buffer_rsrc_t rr, unsigned 
     px_st(rr, off + 16u, b);
   }
 }
+// v[0..3] as the four tagged granules from `granule` on (no tile layout: the BatchNorm partial sums of the decoder clusters)
+__device__ __forceinline__ void cx_publish4_at(__amdgpu_buffer_rsrc_t rr, unsigned granule, const float* v, unsigned tag) {
+  u32x4 a, b;
+  a[0] = __float_as_uint(v[0]); a[1] = tag; a[2] = __float_as_uint(v[1]); a[3] = tag;
+  b[0] = __float_as_uint(v[2]); b[1] = tag; b[2] = __float_as_uint(v[3]); b[3] = tag;
+  px_st(rr, granule * 8u, a);
+  px_st(rr, granule * 8u + 16u, b);
+}
+// column f of the per-row-group partial sums, from the granule records [nblk][2][Hp], polled until every tag matches and summed
+// over the row groups in ascending order: the order of sum_partials() (dec_rollout.hip)
+__device__ __forceinline__ void cx_sum_partials(const unsigned long long* rec, int nblk, int Hp, int f, unsigned tag, unsigned* fault,
+                                                float& s1, float& s2) {
+  s1 = 0.f; s2 = 0.f;
+  for (int k0 = 0; k0 < nblk; k0 += 8) {
+    unsigned long long a[8], b[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool ok = k0 + j < nblk;
+      const unsigned long long* p = rec + (size_t)(ok ? k0 + j : 0) * 2 * Hp + f;
+      a[j] = ok ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((unsigned long long)tag << 32);
+      b[j] = ok ? __hip_atomic_load(p + Hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((unsigned long long)tag << 32);
+    }
+    unsigned spins = 0;
+    for (;;) {
+      bool ok = true;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ok &= (unsigned)(a[j] >> 32) == tag && (unsigned)(b[j] >> 32) == tag;
+      if (ok) break;
+      __builtin_amdgcn_s_sleep(1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned long long* p = rec + (size_t)(k0 + j < nblk ? k0 + j : 0) * 2 * Hp + f;
+        if ((unsigned)(a[j] >> 32) != tag) a[j] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)(b[j] >> 32) != tag) b[j] = __hip_atomic_load(p + Hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (cx_give_up(spins, fault)) break;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      s1 += __uint_as_float((unsigned)a[j]);
+      s2 += __uint_as_float((unsigned)b[j]);
+    }
+  }
+}
 // Do the `n` workgroups of this cluster (the ones that exchange row records with each other) run on ONE XCD?  Every workgroup
 // announces the XCC it runs on (HW_REG_XCC_ID + 1, write-through, into word `me` of `words`: zeroed with the exchange records) and
 // reads all n words: all equal => the cluster's records may go through that XCD's L2.  All n workgroups read the same n words, so

@@ -1229,11 +1229,11 @@ __global__ __launch_bounds__(128) void dec_cell_split_kernel(DecCellArgs a, int 
   float hn[4], xd[4], gr_[4], gz_[4], gn_[4], gh_[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float rr = sigmoidf_((acc[0][r] + bir[r]) + (ah[0][r] + bhr[r]));
-    const float zz = sigmoidf_((acc[1][r] + biz[r]) + (ah[1][r] + bhz[r]));
+    const float rr = gru_gate_rz(acc[0][r] + bir[r], ah[0][r] + bhr[r]);
+    const float zz = gru_gate_rz(acc[1][r] + biz[r], ah[1][r] + bhz[r]);
     const float ghn = ah[2][r] + bhn[r];
-    const float nn = tanhf_((acc[2][r] + bin[r]) + rr * ghn);
-    hn[r] = (1.0f - zz) * nn + zz * hp[r];
+    const float nn = gru_gate_n(acc[2][r] + bin[r], rr, ghn);
+    hn[r] = gru_h_new(zz, nn, hp[r]);
     xd[r] = a.keep ? (((kp >> (8 * r)) & 0xffu) ? hn[r] * a.keep_scale : 0.f) : hn[r];
     gr_[r] = rr; gz_[r] = zz; gn_[r] = nn; gh_[r] = ghn;
   }
@@ -1420,71 +1420,6 @@ struct DecClFwdArgs {
   float p_drop;
 };
 
-__device__ __forceinline__ void dcl_publish4(__amdgpu_buffer_rsrc_t rr, unsigned granule, const float* v, unsigned tag) {
-  u32x4 a, b;
-  a[0] = __float_as_uint(v[0]); a[1] = tag; a[2] = __float_as_uint(v[1]); a[3] = tag;
-  b[0] = __float_as_uint(v[2]); b[1] = tag; b[2] = __float_as_uint(v[3]); b[3] = tag;
-  px_st(rr, granule * 8u, a);
-  px_st(rr, granule * 8u + 16u, b);
-}
-// column f of the per-row-group partial sums, from the granule records [nblk][2][Hp]: the order of sum_partials()
-__device__ __forceinline__ void dcl_sum_partials(const unsigned long long* rec, int nblk, int Hp, int f, unsigned tag, unsigned* fault,
-                                                 float& s1, float& s2) {
-  s1 = 0.f; s2 = 0.f;
-  for (int k0 = 0; k0 < nblk; k0 += 8) {
-    unsigned long long a[8], b[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const bool ok = k0 + j < nblk;
-      const unsigned long long* p = rec + (size_t)(ok ? k0 + j : 0) * 2 * Hp + f;
-      a[j] = ok ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((unsigned long long)tag << 32);
-      b[j] = ok ? __hip_atomic_load(p + Hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((unsigned long long)tag << 32);
-    }
-    unsigned spins = 0;
-    for (;;) {
-      bool ok = true;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ok &= (unsigned)(a[j] >> 32) == tag && (unsigned)(b[j] >> 32) == tag;
-      if (ok) break;
-      __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const unsigned long long* p = rec + (size_t)(k0 + j < nblk ? k0 + j : 0) * 2 * Hp + f;
-        if ((unsigned)(a[j] >> 32) != tag) a[j] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(b[j] >> 32) != tag) b[j] = __hip_atomic_load(p + Hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (cx_give_up(spins, fault)) break;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s1 += __uint_as_float((unsigned)a[j]);
-      s2 += __uint_as_float((unsigned)b[j]);
-    }
-  }
-}
-
-// GRU cell epilogue of the lane's 4 units (the arithmetic of dec_cell_split_kernel); bs: [b_ih r z n, b_hh r z n][q] in LDS
-__device__ __forceinline__ void dcl_cell_epilogue(const float4* xcx, const float4* xch, const float4 (*bs)[4], int lane, int q,
-                                                  const float (&hown)[4], float (&hn)[4], float (&gr_)[4], float (&gz_)[4],
-                                                  float (&gn_)[4], float (&gh_)[4]) {
-  const float4 bi0 = bs[0][q], bi1 = bs[1][q], bi2 = bs[2][q], bh0 = bs[3][q], bh1 = bs[4][q], bh2 = bs[5][q];
-  const float bir[4] = {bi0.x, bi0.y, bi0.z, bi0.w}, biz[4] = {bi1.x, bi1.y, bi1.z, bi1.w}, bin[4] = {bi2.x, bi2.y, bi2.z, bi2.w};
-  const float bhr[4] = {bh0.x, bh0.y, bh0.z, bh0.w}, bhz[4] = {bh1.x, bh1.y, bh1.z, bh1.w}, bhn[4] = {bh2.x, bh2.y, bh2.z, bh2.w};
-  const float4 v0 = xch[lane], v1 = xch[64 + lane], v2 = xch[128 + lane];
-  const float ah[3][4] = {{v0.x, v0.y, v0.z, v0.w}, {v1.x, v1.y, v1.z, v1.w}, {v2.x, v2.y, v2.z, v2.w}};
-  const float4 c0 = xcx[lane], c1 = xcx[64 + lane], c2 = xcx[128 + lane];
-  const float acc[3][4] = {{c0.x, c0.y, c0.z, c0.w}, {c1.x, c1.y, c1.z, c1.w}, {c2.x, c2.y, c2.z, c2.w}};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float rr = sigmoidf_((acc[0][r] + bir[r]) + (ah[0][r] + bhr[r]));
-    const float zz = sigmoidf_((acc[1][r] + biz[r]) + (ah[1][r] + bhz[r]));
-    const float ghn = ah[2][r] + bhn[r];
-    const float nn = tanhf_((acc[2][r] + bin[r]) + rr * ghn);
-    hn[r] = (1.0f - zz) * nn + zz * hown[r];
-    gr_[r] = rr; gz_[r] = zz; gn_[r] = nn; gh_[r] = ghn;
-  }
-}
-
 template <int KS>      // k-steps over H the kernel is built for: 13 (H <= 208: the shipped configurations' H = 200)
 __global__ __launch_bounds__(256) void dec_cluster_fwd_kernel(DecClFwdArgs a) {
   __shared__ float st[2 * 16 * DSPLIT_KS];                                        // mean[H], invstd[H] (offsets as in the split kernels)
@@ -1647,7 +1582,7 @@ __global__ __launch_bounds__(256) void dec_cluster_fwd_kernel(DecClFwdArgs a) {
       float mean, var;
       if (a.training) {
         float s1, s2;
-        dcl_sum_partials(a.xp + (size_t)par_prev * nblk * prec, nblk, Hp, f, tag, a.fault, s1, s2);
+        cx_sum_partials(a.xp + (size_t)par_prev * nblk * prec, nblk, Hp, f, tag, a.fault, s1, s2);
         const float mv = s1 / (float)B;
         var = fmaxf(s2 / (float)B - mv * mv, 0.f);     // biased batch variance
         mean = mv + w.b_pre[f];
@@ -1707,7 +1642,7 @@ __global__ __launch_bounds__(256) void dec_cluster_fwd_kernel(DecClFwdArgs a) {
     DCL_STAMP(5);
     if (wave == 0 && rvalid && fok) {
       float hn[4], xd[4], gr_[4], gz_[4], gn_[4], gh_[4];
-      dcl_cell_epilogue(xcx, xch2[0], bias_s[0], lane, q, hown, hn, gr_, gz_, gn_, gh_);
+      gru_cell_epilogue_lds(xcx, xch2[0], bias_s[0], lane, q, hown, hn, gr_, gz_, gn_, gh_);
 #pragma unroll
       for (int r = 0; r < 4; ++r) xd[r] = drop ? (((kp >> (8 * r)) & 0xffu) ? hn[r] * scale_l0 : 0.f) : hn[r];
       cx_publish4(r_h0, (par * (unsigned)nblk + (unsigned)rg) * rowrec, ft, i, q, hn, tag, l2x);
@@ -1778,7 +1713,7 @@ __global__ __launch_bounds__(256) void dec_cluster_fwd_kernel(DecClFwdArgs a) {
     DCL_STAMP(9);
     if (wave == 2 && rvalid && fok) {
       float hn[4], gr_[4], gz_[4], gn_[4], gh_[4];
-      dcl_cell_epilogue(xcx, xch2[1], bias_s[1], lane, q, hown, hn, gr_, gz_, gn_, gh_);
+      gru_cell_epilogue_lds(xcx, xch2[1], bias_s[1], lane, q, hown, hn, gr_, gz_, gn_, gh_);
       cx_publish4(r_h1, (par * (unsigned)nblk + (unsigned)rg) * rowrec, ft, i, q, hn, tag, l2x);
       *reinterpret_cast<float4*>(sv.h1 + (int64_t)t * BH + (int64_t)b * H + f0) = make_float4(hn[0], hn[1], hn[2], hn[3]);
       if (sv.gates1) {
@@ -1895,8 +1830,8 @@ __global__ __launch_bounds__(256) void dec_cluster_fwd_kernel(DecClFwdArgs a) {
         }
         if (i == 0) {
           const unsigned g0 = (par * (unsigned)nblk + (unsigned)rg) * prec + (unsigned)f0;
-          dcl_publish4(r_p, g0, s1, tag + 1u);
-          dcl_publish4(r_p, g0 + (unsigned)Hp, s2, tag + 1u);
+          cx_publish4_at(r_p, g0, s1, tag + 1u);
+          cx_publish4_at(r_p, g0 + (unsigned)Hp, s2, tag + 1u);
         }
       }
     }
@@ -1926,25 +1861,6 @@ struct DecClBwdArgs {
   int T, B, D, H, n_pre, conditioned, nt, nblk;
   float p_drop;
 };
-
-// gate gradients of one GRU cell for the lane's (row, 4 units): the arithmetic of gru_cell_bwd_lane on values in registers
-__device__ __forceinline__ void dcl_cell_bwd(const float (&dh)[4], const float4 (&gt)[4], const float4& hp4, float (&g_r)[4],
-                                             float (&g_z)[4], float (&g_n)[4], float (&g_hn)[4], float (&direct)[4]) {
-  const float rr[4] = {gt[0].x, gt[0].y, gt[0].z, gt[0].w}, zz[4] = {gt[1].x, gt[1].y, gt[1].z, gt[1].w},
-              nn[4] = {gt[2].x, gt[2].y, gt[2].z, gt[2].w}, gh[4] = {gt[3].x, gt[3].y, gt[3].z, gt[3].w},
-              hp[4] = {hp4.x, hp4.y, hp4.z, hp4.w};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float dn = dh[r] * (1.0f - zz[r]);
-    const float dz = dh[r] * (hp[r] - nn[r]);
-    const float dnp = dn * (1.0f - nn[r] * nn[r]);
-    g_n[r] = dnp;
-    g_hn[r] = dnp * rr[r];
-    g_r[r] = dnp * gh[r] * rr[r] * (1.0f - rr[r]);
-    g_z[r] = dz * zz[r] * (1.0f - zz[r]);
-    direct[r] = dh[r] * zz[r];
-  }
-}
 
 template <int KS>
 __global__ __launch_bounds__(256) void dec_cluster_bwd_kernel(DecClBwdArgs a) {
@@ -2082,7 +1998,7 @@ __global__ __launch_bounds__(256) void dec_cluster_bwd_kernel(DecClBwdArgs a) {
                                    a.fault);
       if (tid < H) {
         float s1, s2;
-        dcl_sum_partials(a.xp + (size_t)par_next * nblk * prec, nblk, Hp, tid, tag - 1u, a.fault, s1, s2);
+        cx_sum_partials(a.xp + (size_t)par_next * nblk * prec, nblk, Hp, tid, tag - 1u, a.fault, s1, s2);
         st[tid] = s1;
         st[16 * DSPLIT_KS + tid] = s2;
         st[2 * 16 * DSPLIT_KS + tid] = sv.bn_stats[(int64_t)t * 2 * H + tid];
@@ -2165,7 +2081,7 @@ __global__ __launch_bounds__(256) void dec_cluster_bwd_kernel(DecClBwdArgs a) {
       float dh[4], g_r[4], g_z[4], g_n[4], g_hn[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) dh[r] = acc[r] + (last ? 0.f : carry1[r]);
-      dcl_cell_bwd(dh, gt1, hp1, g_r, g_z, g_n, g_hn, direct);
+      gru_cell_bwd_regs(dh, gt1, hp1, g_r, g_z, g_n, g_hn, direct);
       const float4 vr = own ? make_float4(g_r[0], g_r[1], g_r[2], g_r[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 vz = own ? make_float4(g_z[0], g_z[1], g_z[2], g_z[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 vn = own ? make_float4(g_n[0], g_n[1], g_n[2], g_n[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2227,7 +2143,7 @@ __global__ __launch_bounds__(256) void dec_cluster_bwd_kernel(DecClBwdArgs a) {
             if (drop) v = ((kp >> (8 * r)) & 0xffu) ? v * scale_l0 : 0.f;
             dh[r] = v + (last ? 0.f : carry0[r]);
           }
-          dcl_cell_bwd(dh, gt0, hp0, g_r, g_z, g_n, g_hn, direct);
+          gru_cell_bwd_regs(dh, gt0, hp0, g_r, g_z, g_n, g_hn, direct);
           const float4 vr = own ? make_float4(g_r[0], g_r[1], g_r[2], g_r[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
           const float4 vz = own ? make_float4(g_z[0], g_z[1], g_z[2], g_z[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
           const float4 vn = own ? make_float4(g_n[0], g_n[1], g_n[2], g_n[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2265,8 +2181,8 @@ __global__ __launch_bounds__(256) void dec_cluster_bwd_kernel(DecClBwdArgs a) {
           }
           if (i == 0 && fok) {
             const unsigned g0 = (par * (unsigned)nblk + (unsigned)rg) * prec + (unsigned)f0;
-            dcl_publish4(r_p, g0, s1, tag);
-            dcl_publish4(r_p, g0 + (unsigned)Hp, s2, tag);
+            cx_publish4_at(r_p, g0, s1, tag);
+            cx_publish4_at(r_p, g0 + (unsigned)Hp, s2, tag);
           }
         }
       }
@@ -2392,17 +2308,7 @@ __device__ __forceinline__ void gru_cell_bwd_lane(const float (&dh)[4], const fl
   const float rr[4] = {r4.x, r4.y, r4.z, r4.w}, zz[4] = {z4.x, z4.y, z4.z, z4.w}, nn[4] = {n4.x, n4.y, n4.z, n4.w},
               gh[4] = {h4.x, h4.y, h4.z, h4.w}, hp[4] = {p4.x, p4.y, p4.z, p4.w};
   float g_r[4], g_z[4], g_n[4], g_hn[4], direct[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float dn = dh[r] * (1.0f - zz[r]);
-    const float dz = dh[r] * (hp[r] - nn[r]);
-    const float dnp = dn * (1.0f - nn[r] * nn[r]);
-    g_n[r] = dnp;
-    g_hn[r] = dnp * rr[r];
-    g_r[r] = dnp * gh[r] * rr[r] * (1.0f - rr[r]);
-    g_z[r] = dz * zz[r] * (1.0f - zz[r]);
-    direct[r] = dh[r] * zz[r];
-  }
+  gru_gates_bwd4(dh, rr, zz, nn, gh, hp, g_r, g_z, g_n, g_hn, direct);
   const float4 vr = make_float4(g_r[0], g_r[1], g_r[2], g_r[3]), vz = make_float4(g_z[0], g_z[1], g_z[2], g_z[3]),
                vn = make_float4(g_n[0], g_n[1], g_n[2], g_n[3]), vh = make_float4(g_hn[0], g_hn[1], g_hn[2], g_hn[3]);
   *reinterpret_cast<float4*>(dgi + f0) = vr; *reinterpret_cast<float4*>(dgi + H + f0) = vz; *reinterpret_cast<float4*>(dgi + 2 * H + f0) = vn;

@@ -10,6 +10,7 @@
 // pre-activations with three v_mfma_f32_16x16x4_f32 accumulators so that the whole gate math for a
 // (row, feature) happens in one lane.
 #include "common.hpp"
+#include "gru_cells.hpp"
 #include "dec_persist.hpp"      // the exchange primitives (px_ld / px_st) of the cluster kernels; not the fault latch
 
 namespace g2v {
@@ -82,11 +83,11 @@ __device__ __forceinline__ void gru_seq_fwd_body(const float* __restrict__ gi, c
         for (int r = 0; r < 4; ++r) {
           const int f = f0 + r;
           if (f < H) {
-            const float rr = sigmoidf_(ir[r] + (acc[0][r] + b_hh[f]));
-            const float zz = sigmoidf_(iz[r] + (acc[1][r] + b_hh[H + f]));
+            const float rr = gru_gate_rz(ir[r], acc[0][r] + b_hh[f]);
+            const float zz = gru_gate_rz(iz[r], acc[1][r] + b_hh[H + f]);
             const float ghn = acc[2][r] + b_hh[2 * H + f];
-            const float nn = tanhf_(in_[r] + rr * ghn);
-            hn[r] = (1.0f - zz) * nn + zz * hp[r];
+            const float nn = gru_gate_n(in_[r], rr, ghn);
+            hn[r] = gru_h_new(zz, nn, hp[r]);
             gr[r] = rr; gz[r] = zz; gn[r] = nn; gh[r] = ghn;
           } else {
             hn[r] = 0.f; gr[r] = gz[r] = gn[r] = gh[r] = 0.f;
@@ -267,11 +268,11 @@ __device__ __forceinline__ void gru_seq_fwd_body_v4(const float* __restrict__ gi
         float hn[4], gr[4], gz[4], gn[4], gh[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float rr = sigmoidf_(ir[e] + (acc[0][r][e] + br[e]));
-          const float zz = sigmoidf_(iz[e] + (acc[1][r][e] + bz[e]));
+          const float rr = gru_gate_rz(ir[e], acc[0][r][e] + br[e]);
+          const float zz = gru_gate_rz(iz[e], acc[1][r][e] + bz[e]);
           const float ghn = acc[2][r][e] + bn[e];
-          const float nn = tanhf_(in_[e] + rr * ghn);
-          const float hnew = (1.0f - zz) * nn + zz * hp[e];
+          const float nn = gru_gate_n(in_[e], rr, ghn);
+          const float hnew = (1.0f - zz) * nn + zz * hp[e];      // hand-written copy of gru_h_new: calling it changes this kernel's code
           hn[e] = valid ? hnew : hp[e];
           gr[e] = valid ? rr : 0.f; gz[e] = valid ? zz : 0.f; gn[e] = valid ? nn : 0.f; gh[e] = valid ? ghn : 0.f;
         }
@@ -470,11 +471,11 @@ __device__ __forceinline__ void gru_res_fwd_wave(const GruGenF& d, const int32_t
         float hn[4], gr[4], gz[4], gn[4], gh[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float rr = sigmoidf_(ir[e] + (acc[0][e] + br[e]));
-          const float zz = sigmoidf_(iz[e] + (acc[1][e] + bz[e]));
+          const float rr = gru_gate_rz(ir[e], acc[0][e] + br[e]);
+          const float zz = gru_gate_rz(iz[e], acc[1][e] + bz[e]);
           const float ghn = acc[2][e] + bn[e];
-          const float nn = tanhf_(in_[e] + rr * ghn);
-          const float hnw = (1.0f - zz) * nn + zz * hp[e];
+          const float nn = gru_gate_n(in_[e], rr, ghn);
+          const float hnw = (1.0f - zz) * nn + zz * hp[e];      // hand-written copy of gru_h_new: calling it changes this kernel's code
           hn[e] = valid ? hnw : hp[e];
           gr[e] = valid ? rr : 0.f; gz[e] = valid ? zz : 0.f; gn[e] = valid ? nn : 0.f; gh[e] = valid ? ghn : 0.f;
         }
@@ -568,14 +569,8 @@ __device__ __forceinline__ void gru_seq_bwd_body(const float* __restrict__ d_hs,
         if (s == 0) hp = h0 ? h0[(int64_t)b * H + f] : 0.f;
         else if (tprev >= len) hp = h0 ? h0[(int64_t)b * H + f] : 0.f;   // reverse dir: first valid step
         else hp = hs[((int64_t)tprev * B + b) * hs_ld + f];
-        const float dn = dh * (1.0f - zz);
-        const float dz = dh * (hp - nn);
-        const float dnp = dn * (1.0f - nn * nn);
-        g_n = dnp;
-        g_hn = dnp * rr;
-        g_r = dnp * ghn * rr * (1.0f - rr);
-        g_z = dz * zz * (1.0f - zz);
-        direct = dh * zz;
+        const GruGateGrads g = gru_gates_bwd(dh, rr, zz, nn, ghn, hp);
+        g_n = g.g_n; g_hn = g.g_hn; g_r = g.g_r; g_z = g.g_z; direct = g.direct;
       }
       dgi[row * G + f] = g_r; dgi[row * G + H + f] = g_z; dgi[row * G + 2 * H + f] = g_n;
       dgh[row * G + f] = g_r; dgh[row * G + H + f] = g_z; dgh[row * G + 2 * H + f] = g_hn;
@@ -709,15 +704,8 @@ __device__ __forceinline__ void gru_seq_bwd_body_v4(const float* __restrict__ d_
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         if (live) {
-          const float dh = dh_in[e] + up[e];
-          const float dn = dh * (1.0f - zz[e]);
-          const float dz = dh * (hp[e] - nn[e]);
-          const float dnp = dn * (1.0f - nn[e] * nn[e]);
-          g_n[e] = dnp;
-          g_hn[e] = dnp * rr[e];
-          g_r[e] = dnp * gh[e] * rr[e] * (1.0f - rr[e]);
-          g_z[e] = dz * zz[e] * (1.0f - zz[e]);
-          direct[e] = dh * zz[e];
+          const GruGateGrads g = gru_gates_bwd(dh_in[e] + up[e], rr[e], zz[e], nn[e], gh[e], hp[e]);
+          g_n[e] = g.g_n; g_hn[e] = g.g_hn; g_r[e] = g.g_r; g_z[e] = g.g_z; direct[e] = g.direct;
         } else {
           g_r[e] = g_z[e] = g_n[e] = g_hn[e] = 0.f;
           direct[e] = dh_in[e];
@@ -950,15 +938,8 @@ __device__ __forceinline__ void gru_res_bwd_wave(const GruResB& d, const int32_t
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         if (live) {
-          const float dhv = dh_in[e] + up[e];
-          const float dn = dhv * (1.0f - zz[e]);
-          const float dz = dhv * (hp[e] - nn[e]);
-          const float dnp = dn * (1.0f - nn[e] * nn[e]);
-          g_n[e] = dnp;
-          g_hn[e] = dnp * rr[e];
-          g_r[e] = dnp * gh[e] * rr[e] * (1.0f - rr[e]);
-          g_z[e] = dz * zz[e] * (1.0f - zz[e]);
-          dir[e] = dhv * zz[e];
+          const GruGateGrads g = gru_gates_bwd(dh_in[e] + up[e], rr[e], zz[e], nn[e], gh[e], hp[e]);
+          g_n[e] = g.g_n; g_hn[e] = g.g_hn; g_r[e] = g.g_r; g_z[e] = g.g_z; dir[e] = g.direct;
         } else {
           g_r[e] = g_z[e] = g_n[e] = g_hn[e] = 0.f;
           dir[e] = dh_in[e];
@@ -1113,11 +1094,11 @@ __global__ __launch_bounds__(64) void gru_step_fwd_kernel(GruStepF d0, GruStepF 
   for (int r = 0; r < 4; ++r) {
     hn[r] = hp_[r]; gr[r] = gz[r] = gn[r] = gh[r] = 0.f;
     if (valid) {
-      gr[r] = sigmoidf_(gir_[0][r] + (acc[0][r] + bh_[0][r]));
-      gz[r] = sigmoidf_(gir_[1][r] + (acc[1][r] + bh_[1][r]));
+      gr[r] = gru_gate_rz(gir_[0][r], acc[0][r] + bh_[0][r]);
+      gz[r] = gru_gate_rz(gir_[1][r], acc[1][r] + bh_[1][r]);
       gh[r] = acc[2][r] + bh_[2][r];
-      gn[r] = tanhf_(gir_[2][r] + gr[r] * gh[r]);
-      hn[r] = (1.0f - gz[r]) * gn[r] + gz[r] * hp_[r];
+      gn[r] = gru_gate_n(gir_[2][r], gr[r], gh[r]);
+      hn[r] = gru_h_new(gz[r], gn[r], hp_[r]);
     }
   }
   *reinterpret_cast<float4*>(d.h_next + (int64_t)b * H + f0) = make_float4(hn[0], hn[1], hn[2], hn[3]);
@@ -1223,7 +1204,7 @@ __global__ __launch_bounds__(64) void gru_step_bwd_kernel(GruStepB d0, GruStepB 
     g_r[r] = g_z[r] = g_n[r] = g_hn[r] = 0.f;
     direct[r] = dh[r];
     if (act) {
-      const float dht = dh[r] + dd_[r];
+      const float dht = dh[r] + dd_[r];      // hand-written copy of gru_gates_bwd: calling it reorders this kernel's packed multiplies
       const float dn = dht * (1.0f - zz_[r]);
       const float dz = dht * (hp_[r] - nn_[r]);
       const float dnp = dn * (1.0f - nn_[r] * nn_[r]);
@@ -1374,11 +1355,11 @@ __global__ __launch_bounds__(192) void gru_cluster_fwd_kernel(GruClF d0, GruClF 
       for (int r = 0; r < 4; ++r) {
         hn[r] = hp_[r]; gr[r] = gz[r] = gn[r] = gh[r] = 0.f;
         if (valid) {      // (the arithmetic of gru_step_fwd_kernel)
-          gr[r] = sigmoidf_(gir_[0][r] + (acc[r] + bh_[0][r]));
-          gz[r] = sigmoidf_(gir_[1][r] + (a1[r] + bh_[1][r]));
+          gr[r] = gru_gate_rz(gir_[0][r], acc[r] + bh_[0][r]);
+          gz[r] = gru_gate_rz(gir_[1][r], a1[r] + bh_[1][r]);
           gh[r] = a2[r] + bh_[2][r];
-          gn[r] = tanhf_(gir_[2][r] + gr[r] * gh[r]);
-          hn[r] = (1.0f - gz[r]) * gn[r] + gz[r] * hp_[r];
+          gn[r] = gru_gate_n(gir_[2][r], gr[r], gh[r]);
+          hn[r] = gru_h_new(gz[r], gn[r], hp_[r]);
         }
       }
       if (s + 1 < T) cx_publish4(rr, ((unsigned)(s & 1) * (unsigned)nblk + (unsigned)rg) * rec_granules, ft, i, q, hn, (unsigned)(s + 1), l2x);
@@ -1549,7 +1530,7 @@ __global__ __launch_bounds__(192) void gru_cluster_bwd_kernel(GruClB d0, GruClB 
         for (int r = 0; r < 4; ++r) {
           carry[r] = dh[r];
           if (act) {
-            const float dht = dh[r] + dd_[r];
+            const float dht = dh[r] + dd_[r];      // hand-written copy of gru_gates_bwd: calling it reorders the packed multiplies
             const float dn = dht * (1.0f - zz_[r]);
             const float dz = dht * (hpv[r] - nn_[r]);
             const float dnp = dn * (1.0f - nn_[r] * nn_[r]);
@@ -1698,11 +1679,11 @@ __global__ __launch_bounds__(128) void gru_cell_fwd_kernel(const float* __restri
   float hn[4], gr[4], gz[4], gn[4], gh[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    gr[r] = sigmoidf_((acc[0][r] + bi_[0][r]) + (ah[0][r] + bh_[0][r]));
-    gz[r] = sigmoidf_((acc[1][r] + bi_[1][r]) + (ah[1][r] + bh_[1][r]));
+    gr[r] = gru_gate_rz(acc[0][r] + bi_[0][r], ah[0][r] + bh_[0][r]);
+    gz[r] = gru_gate_rz(acc[1][r] + bi_[1][r], ah[1][r] + bh_[1][r]);
     gh[r] = ah[2][r] + bh_[2][r];
     gn[r] = tanhf_(__fmaf_rn(gr[r], gh[r], acc[2][r] + bi_[2][r]));      // fused like gi_n + r * gh_n in gru_step_fwd_kernel
-    hn[r] = (1.0f - gz[r]) * gn[r] + gz[r] * hp_[r];
+    hn[r] = gru_h_new(gz[r], gn[r], hp_[r]);
   }
   *reinterpret_cast<float4*>(h_new + (int64_t)b * H + f0) = make_float4(hn[0], hn[1], hn[2], hn[3]);
   if (gates) {
@@ -1739,14 +1720,8 @@ __global__ __launch_bounds__(256) void gru_cell_gates_bwd_kernel(const float* __
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float dht = d1[r] + d0[r];                    // carry + gradient from above (the order of gru_step_bwd_kernel)
-    const float dn = dht * (1.0f - zz[r]);
-    const float dz = dht * (hp_[r] - nn[r]);
-    const float dnp = dn * (1.0f - nn[r] * nn[r]);
-    g_n[r] = dnp;
-    g_hn[r] = dnp * rr[r];
-    g_r[r] = dnp * gh[r] * rr[r] * (1.0f - rr[r]);
-    g_z[r] = dz * zz[r] * (1.0f - zz[r]);
-    dir[r] = dht * zz[r];
+    const GruGateGrads g = gru_gates_bwd(dht, rr[r], zz[r], nn[r], gh[r], hp_[r]);
+    g_n[r] = g.g_n; g_hn[r] = g.g_hn; g_r[r] = g.g_r; g_z[r] = g.g_z; dir[r] = g.direct;
   }
   float* gi_o = dgi + (int64_t)b * 3 * H + f0;
   float* gh_o = dgh + (int64_t)b * 3 * H + f0;
@@ -1907,11 +1882,11 @@ __device__ __forceinline__ void gru_fwd_fast_body(const GruDirF& d0, const GruDi
     float hn[4], gr_[4], gz_[4], gn_[4], gh_[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float rr = sigmoidf_(ir[r] + (acc[0][r] + br[r]));
-      const float zz = sigmoidf_(iz[r] + (acc[1][r] + bz[r]));
+      const float rr = gru_gate_rz(ir[r], acc[0][r] + br[r]);
+      const float zz = gru_gate_rz(iz[r], acc[1][r] + bz[r]);
       const float ghn = acc[2][r] + bn[r];
-      const float nn = tanhf_(in_[r] + rr * ghn);
-      const float hnew = (1.0f - zz) * nn + zz * hp[r];
+      const float nn = gru_gate_n(in_[r], rr, ghn);
+      const float hnew = (1.0f - zz) * nn + zz * hp[r];      // hand-written copy of gru_h_new: calling it changes this kernel's code
       hn[r] = valid ? hnew : hp[r];        // selects, not branches: the gate math runs for every lane
       gr_[r] = valid ? rr : 0.f; gz_[r] = valid ? zz : 0.f; gn_[r] = valid ? nn : 0.f; gh_[r] = valid ? ghn : 0.f;
     }
@@ -2033,7 +2008,7 @@ __global__ __launch_bounds__(256, FUSE_W == 2 ? 1 : 2) void gru_bwd_fast_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (valid) {
-        const float dd = dhv[r] + ds[r];
+        const float dd = dhv[r] + ds[r];      // hand-written copy of gru_gates_bwd: calling it reorders this kernel's packed multiplies
         const float dn = dd * (1.0f - zz[r]);
         const float dz = dd * (hp[r] - nn[r]);
         const float dnp = dn * (1.0f - nn[r] * nn[r]);

@@ -1,10 +1,86 @@
-// gru_cells.hpp -- one GRU cell (forward / backward) for the feature tiles of a wave, on 16 batch rows staged in LDS and weights
-// streamed from L2 as packed MFMA fragments: shared by the per-step kernels of the pose decoder (dec_rollout.hip) and of the
-// text -> gesture-code decoder (t2e_rollout.hip).  Moved here from dec_rollout.hip in round 5 (no change of arithmetic).
+// gru_cells.hpp -- the per-element gate arithmetic of a GRU cell (forward / backward), one definition for every kernel that has a
+// GRU cell in it (gru.hip, dec_persist.hip, dec_rollout.hip, t2e_rollout.hip), and one GRU cell for the feature tiles of a wave, on
+// 16 batch rows staged in LDS and weights streamed from L2 as packed MFMA fragments: shared by the per-step kernels of the pose
+// decoder (dec_rollout.hip) and of the text -> gesture-code decoder (t2e_rollout.hip).
 #pragma once
 #include "common.hpp"
 
 namespace g2v {
+
+// ---- the gate arithmetic of a GRU cell, per element: the ONE definition every kernel calls ------------------------------------------
+// (gru.hip, dec_rollout.hip, dec_persist.hip, t2e_rollout.hip and the cells below: the tests compare their paths bitwise.)
+//   r = gru_gate_rz(x_r, h_r)   z = gru_gate_rz(x_z, h_z)   ghn = a_hn + b_hn   n = gru_gate_n(x_n, r, ghn)   h = gru_h_new(z, n, h_prev)
+// The caller forms the operands: the "cell" form passes x = a_i + b_i, h = a_h + b_h (so r = sigma((a_i + b_i) + (a_h + b_h))), the
+// "sequence" form x = gi, h = acc + b_hh; ghn is the saved fourth gate.  Loads, stores, keep masks, the carry add and the zero
+// fill of padded rows / units stay with the caller.  Three small functions and not one that returns all five values: every call
+// site keeps its statement order that way, and with it the machine code it had when the expressions were written out.
+// Exceptions, on purpose:
+//   * gru_cell_fwd_kernel (gru.hip): n = tanh(fma(r, ghn, x_n)), "fused like gi_n + r * gh_n in gru_step_fwd_kernel" as its comment
+//     says: different arithmetic, kept as it is -- do not "fix" it to call gru_gate_n;
+//   * the sites in gru.hip marked "hand-written copy of ...": calling the function there changed the kernel's machine code (the
+//     blend of the three sequence kernels that select on `valid`; the gate gradients of gru_step_bwd_kernel, gru_cluster_bwd_kernel
+//     and gru_bwd_fast_kernel).  Whoever changes the arithmetic here changes those six places too.
+__device__ __forceinline__ float gru_gate_rz(float x, float h) { return sigmoidf_(x + h); }
+__device__ __forceinline__ float gru_gate_n(float x_n, float r, float ghn) { return tanhf_(x_n + r * ghn); }
+__device__ __forceinline__ float gru_h_new(float z, float n, float h_prev) { return (1.0f - z) * n + z * h_prev; }
+// Gate gradients from dh (the gradient arriving at h_new, carry included): dgi = (g_r, g_z, g_n), dgh = (g_r, g_z, g_hn) and the
+// direct path dh * z into h_prev.
+struct GruGateGrads {
+  float g_r, g_z, g_n, g_hn, direct;
+};
+__device__ __forceinline__ GruGateGrads gru_gates_bwd(float dh, float r, float z, float n, float ghn, float h_prev) {
+  GruGateGrads g;
+  const float dn = dh * (1.0f - z);
+  const float dz = dh * (h_prev - n);
+  const float dnp = dn * (1.0f - n * n);
+  g.g_n = dnp;
+  g.g_hn = dnp * r;
+  g.g_r = dnp * ghn * r * (1.0f - r);
+  g.g_z = dz * z * (1.0f - z);
+  g.direct = dh * z;
+  return g;
+}
+// the same for the 4 consecutive units of a lane
+__device__ __forceinline__ void gru_gates_bwd4(const float (&dh)[4], const float (&rr)[4], const float (&zz)[4], const float (&nn)[4],
+                                               const float (&gh)[4], const float (&hp)[4], float (&g_r)[4], float (&g_z)[4],
+                                               float (&g_n)[4], float (&g_hn)[4], float (&direct)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const GruGateGrads g = gru_gates_bwd(dh[r], rr[r], zz[r], nn[r], gh[r], hp[r]);
+    g_n[r] = g.g_n; g_hn[r] = g.g_hn; g_r[r] = g.g_r; g_z[r] = g.g_z; direct[r] = g.direct;
+  }
+}
+// ... and from the saved gates (r, z, n, ghn) and h_prev as loaded: float4 each
+__device__ __forceinline__ void gru_cell_bwd_regs(const float (&dh)[4], const float4 (&gt)[4], const float4& hp4, float (&g_r)[4],
+                                                  float (&g_z)[4], float (&g_n)[4], float (&g_hn)[4], float (&direct)[4]) {
+  const float rr[4] = {gt[0].x, gt[0].y, gt[0].z, gt[0].w}, zz[4] = {gt[1].x, gt[1].y, gt[1].z, gt[1].w},
+              nn[4] = {gt[2].x, gt[2].y, gt[2].z, gt[2].w}, gh[4] = {gt[3].x, gt[3].y, gt[3].z, gt[3].w},
+              hp[4] = {hp4.x, hp4.y, hp4.z, hp4.w};
+  gru_gates_bwd4(dh, rr, zz, nn, gh, hp, g_r, g_z, g_n, g_hn, direct);
+}
+
+// GRU cell epilogue of the lane's 4 units from the six accumulators in LDS ([gate][64] float4 each: xcx the input side, xch the hidden
+// side); bs: [b_ih r z n, b_hh r z n][q] in LDS.  The cluster kernels of dec_rollout.hip and t2e_rollout.hip.
+__device__ __forceinline__ void gru_cell_epilogue_lds(const float4* xcx, const float4* xch, const float4 (*bs)[4], int lane, int q,
+                                                      const float (&hown)[4], float (&hn)[4], float (&gr_)[4], float (&gz_)[4],
+                                                      float (&gn_)[4], float (&gh_)[4]) {
+  const float4 bi0 = bs[0][q], bi1 = bs[1][q], bi2 = bs[2][q], bh0 = bs[3][q], bh1 = bs[4][q], bh2 = bs[5][q];
+  const float bir[4] = {bi0.x, bi0.y, bi0.z, bi0.w}, biz[4] = {bi1.x, bi1.y, bi1.z, bi1.w}, bin[4] = {bi2.x, bi2.y, bi2.z, bi2.w};
+  const float bhr[4] = {bh0.x, bh0.y, bh0.z, bh0.w}, bhz[4] = {bh1.x, bh1.y, bh1.z, bh1.w}, bhn[4] = {bh2.x, bh2.y, bh2.z, bh2.w};
+  const float4 v0 = xch[lane], v1 = xch[64 + lane], v2 = xch[128 + lane];
+  const float ah[3][4] = {{v0.x, v0.y, v0.z, v0.w}, {v1.x, v1.y, v1.z, v1.w}, {v2.x, v2.y, v2.z, v2.w}};
+  const float4 c0 = xcx[lane], c1 = xcx[64 + lane], c2 = xcx[128 + lane];
+  const float acc[3][4] = {{c0.x, c0.y, c0.z, c0.w}, {c1.x, c1.y, c1.z, c1.w}, {c2.x, c2.y, c2.z, c2.w}};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float rr = gru_gate_rz(acc[0][r] + bir[r], ah[0][r] + bhr[r]);
+    const float zz = gru_gate_rz(acc[1][r] + biz[r], ah[1][r] + bhz[r]);
+    const float ghn = ah[2][r] + bhn[r];
+    const float nn = gru_gate_n(acc[2][r] + bin[r], rr, ghn);
+    hn[r] = gru_h_new(zz, nn, hown[r]);
+    gr_[r] = rr; gz_[r] = zz; gn_[r] = nn; gh_[r] = ghn;
+  }
+}
 
 // Gate math + stores of one GRU cell for the 4 consecutive features [f0, f0+4) of row i held by this lane.
 __device__ __forceinline__ void gru_cell_fwd_epilogue(const f32x4 (&ai)[3], const f32x4 (&ah)[3], const float4 (&bi)[3],
@@ -22,11 +98,11 @@ __device__ __forceinline__ void gru_cell_fwd_epilogue(const f32x4 (&ai)[3], cons
   float hn[4], xd[4], gr_[4], gz_[4], gn_[4], gh_[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float rr = sigmoidf_((ai[0][r] + bir[r]) + (ah[0][r] + bhr[r]));
-    const float zz = sigmoidf_((ai[1][r] + biz[r]) + (ah[1][r] + bhz[r]));
+    const float rr = gru_gate_rz(ai[0][r] + bir[r], ah[0][r] + bhr[r]);
+    const float zz = gru_gate_rz(ai[1][r] + biz[r], ah[1][r] + bhz[r]);
     const float ghn = ah[2][r] + bhn[r];
-    const float nn = tanhf_((ai[2][r] + bin[r]) + rr * ghn);
-    hn[r] = (1.0f - zz) * nn + zz * hp[r];
+    const float nn = gru_gate_n(ai[2][r] + bin[r], rr, ghn);
+    hn[r] = gru_h_new(zz, nn, hp[r]);
     xd[r] = keep ? (((kp >> (8 * r)) & 0xffu) ? hn[r] * keep_scale : 0.f) : hn[r];
     gr_[r] = rr; gz_[r] = zz; gn_[r] = nn; gh_[r] = ghn;
   }
@@ -95,11 +171,11 @@ __device__ __forceinline__ void gru_cell_fwd(const float* __restrict__ p_ih, con
         const int f = f0 + r;
         if (f >= H) continue;
         const float hp = Xh[i * ldh + f];
-        const float rr = sigmoidf_((ai[0][r] + b_ih[f]) + (ah[0][r] + b_hh[f]));
-        const float zz = sigmoidf_((ai[1][r] + b_ih[H + f]) + (ah[1][r] + b_hh[H + f]));
+        const float rr = gru_gate_rz(ai[0][r] + b_ih[f], ah[0][r] + b_hh[f]);
+        const float zz = gru_gate_rz(ai[1][r] + b_ih[H + f], ah[1][r] + b_hh[H + f]);
         const float ghn = ah[2][r] + b_hh[2 * H + f];
-        const float nn = tanhf_((ai[2][r] + b_ih[2 * H + f]) + rr * ghn);
-        const float hn = (1.0f - zz) * nn + zz * hp;
+        const float nn = gru_gate_n(ai[2][r] + b_ih[2 * H + f], rr, ghn);
+        const float hn = gru_h_new(zz, nn, hp);
         float xd = hn;
         if (keep) xd = (i < nrows && keep[(int64_t)i * H + f]) ? hn * keep_scale : 0.f;
         Hnext_lds[i * ldh + f] = xd;
@@ -177,14 +253,8 @@ __device__ __forceinline__ void gru_cell_bwd_tile(const f32x4& acc, const float*
         float dh = acc[r];
         if (keep) dh = ((kp >> (8 * r)) & 0xffu) ? dh * extra_scale : 0.f;
         dh += cc[r];
-        const float dn = dh * (1.0f - zz[r]);
-        const float dz = dh * (hp[r] - nn[r]);
-        const float dnp = dn * (1.0f - nn[r] * nn[r]);
-        g_n[r] = dnp;
-        g_hn[r] = dnp * rr[r];
-        g_r[r] = dnp * gh[r] * rr[r] * (1.0f - rr[r]);
-        g_z[r] = dz * zz[r] * (1.0f - zz[r]);
-        direct[r] = dh * zz[r];
+        const GruGateGrads g = gru_gates_bwd(dh, rr[r], zz[r], nn[r], gh[r], hp[r]);
+        g_n[r] = g.g_n; g_hn[r] = g.g_hn; g_r[r] = g.g_r; g_z[r] = g.g_z; direct[r] = g.direct;
       }
       float* o1 = dgi + (int64_t)i * G + f0;
       float* o2 = dgh + (int64_t)i * G + f0;
@@ -216,14 +286,8 @@ __device__ __forceinline__ void gru_cell_bwd_tile(const f32x4& acc, const float*
       const float* go = gates + (int64_t)i * 4 * H;
       const float rr = go[f], zz = go[H + f], nn = go[2 * H + f], ghn = go[3 * H + f];
       const float hp = hprev[(int64_t)i * H + f];
-      const float dn = dh * (1.0f - zz);
-      const float dz = dh * (hp - nn);
-      const float dnp = dn * (1.0f - nn * nn);
-      g_n = dnp;
-      g_hn = dnp * rr;
-      g_r = dnp * ghn * rr * (1.0f - rr);
-      g_z = dz * zz * (1.0f - zz);
-      direct = dh * zz;
+      const GruGateGrads g = gru_gates_bwd(dh, rr, zz, nn, ghn, hp);
+      g_n = g.g_n; g_hn = g.g_hn; g_r = g.g_r; g_z = g.g_z; direct = g.direct;
       float* o1 = dgi + (int64_t)i * G;
       float* o2 = dgh + (int64_t)i * G;
       o1[f] = g_r; o1[H + f] = g_z; o1[2 * H + f] = g_n;

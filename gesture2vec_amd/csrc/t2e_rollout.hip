@@ -870,69 +870,6 @@ struct CodeClArgs {
   int S1, B, H, K, n_pre, training, nt, nblk;
   float p_drop;
 };
-__device__ __forceinline__ void ccl_publish4(__amdgpu_buffer_rsrc_t rr, unsigned granule, const float* v, unsigned tag) {
-  u32x4 a, b;
-  a[0] = __float_as_uint(v[0]); a[1] = tag; a[2] = __float_as_uint(v[1]); a[3] = tag;
-  b[0] = __float_as_uint(v[2]); b[1] = tag; b[2] = __float_as_uint(v[3]); b[3] = tag;
-  px_st(rr, granule * 8u, a);
-  px_st(rr, granule * 8u + 16u, b);
-}
-// column f of the per-row-group partial sums [nblk][2][Hp] (granules), summed over the row groups in ascending order
-__device__ __forceinline__ void ccl_sum_partials(const unsigned long long* rec, int nblk, int Hp, int f, unsigned tag, unsigned* fault,
-                                                 float& s1, float& s2) {
-  s1 = 0.f; s2 = 0.f;
-  for (int k0 = 0; k0 < nblk; k0 += 8) {
-    unsigned long long a[8], b[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const bool ok = k0 + j < nblk;
-      const unsigned long long* p = rec + (size_t)(ok ? k0 + j : 0) * 2 * Hp + f;
-      a[j] = ok ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((unsigned long long)tag << 32);
-      b[j] = ok ? __hip_atomic_load(p + Hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((unsigned long long)tag << 32);
-    }
-    unsigned spins = 0;
-    for (;;) {
-      bool ok = true;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ok &= (unsigned)(a[j] >> 32) == tag && (unsigned)(b[j] >> 32) == tag;
-      if (ok) break;
-      __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const unsigned long long* p = rec + (size_t)(k0 + j < nblk ? k0 + j : 0) * 2 * Hp + f;
-        if ((unsigned)(a[j] >> 32) != tag) a[j] = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(b[j] >> 32) != tag) b[j] = __hip_atomic_load(p + Hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (cx_give_up(spins, fault)) break;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s1 += __uint_as_float((unsigned)a[j]);
-      s2 += __uint_as_float((unsigned)b[j]);
-    }
-  }
-}
-// GRU cell epilogue of the lane's 4 units from the six accumulators in LDS (the arithmetic of gru_cell_fwd_epilogue)
-__device__ __forceinline__ void ccl_cell_epilogue(const float4* xcx, const float4* xch, const float4 (*bs)[4], int lane, int q,
-                                                  const float (&hown)[4], float (&hn)[4], float (&gr_)[4], float (&gz_)[4],
-                                                  float (&gn_)[4], float (&gh_)[4]) {
-  const float4 bi0 = bs[0][q], bi1 = bs[1][q], bi2 = bs[2][q], bh0 = bs[3][q], bh1 = bs[4][q], bh2 = bs[5][q];
-  const float bir[4] = {bi0.x, bi0.y, bi0.z, bi0.w}, biz[4] = {bi1.x, bi1.y, bi1.z, bi1.w}, bin[4] = {bi2.x, bi2.y, bi2.z, bi2.w};
-  const float bhr[4] = {bh0.x, bh0.y, bh0.z, bh0.w}, bhz[4] = {bh1.x, bh1.y, bh1.z, bh1.w}, bhn[4] = {bh2.x, bh2.y, bh2.z, bh2.w};
-  const float4 v0 = xch[lane], v1 = xch[64 + lane], v2 = xch[128 + lane];
-  const float ah[3][4] = {{v0.x, v0.y, v0.z, v0.w}, {v1.x, v1.y, v1.z, v1.w}, {v2.x, v2.y, v2.z, v2.w}};
-  const float4 c0 = xcx[lane], c1 = xcx[64 + lane], c2 = xcx[128 + lane];
-  const float acc[3][4] = {{c0.x, c0.y, c0.z, c0.w}, {c1.x, c1.y, c1.z, c1.w}, {c2.x, c2.y, c2.z, c2.w}};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float rr = sigmoidf_((acc[0][r] + bir[r]) + (ah[0][r] + bhr[r]));
-    const float zz = sigmoidf_((acc[1][r] + biz[r]) + (ah[1][r] + bhz[r]));
-    const float ghn = ah[2][r] + bhn[r];
-    const float nn = tanhf_((acc[2][r] + bin[r]) + rr * ghn);
-    hn[r] = (1.0f - zz) * nn + zz * hown[r];
-    gr_[r] = rr; gz_[r] = zz; gn_[r] = nn; gh_[r] = ghn;
-  }
-}
 
 __global__ __launch_bounds__(256) void code_cluster_fwd_kernel(CodeClArgs a) {
   constexpr int KS = CCL_KS;
@@ -1093,7 +1030,7 @@ __global__ __launch_bounds__(256) void code_cluster_fwd_kernel(CodeClArgs a) {
         float mean, invstd;
         if (training) {
           float s1, s2;
-          ccl_sum_partials(a.xp + (size_t)ppar * nblk * prec, nblk, Hp, f, tag, a.fault, s1, s2);
+          cx_sum_partials(a.xp + (size_t)ppar * nblk * prec, nblk, Hp, f, tag, a.fault, s1, s2);
           const float mv = s1 / (float)B;
           const float var = fmaxf(s2 / (float)B - mv * mv, 0.f);   // biased batch variance
           mean = mv + w.b_pre[f];
@@ -1156,7 +1093,7 @@ __global__ __launch_bounds__(256) void code_cluster_fwd_kernel(CodeClArgs a) {
       lds_barrier();
       if (wave == 0 && rvalid && fok) {
         float hn[4], xd[4], gr_[4], gz_[4], gn_[4], gh_[4];
-        ccl_cell_epilogue(xcx, xch2[0], bias_s[0], lane, q, hown, hn, gr_, gz_, gn_, gh_);
+        gru_cell_epilogue_lds(xcx, xch2[0], bias_s[0], lane, q, hown, hn, gr_, gz_, gn_, gh_);
 #pragma unroll
         for (int r = 0; r < 4; ++r) xd[r] = drop ? (((kp >> (8 * r)) & 0xffu) ? hn[r] * scale_l0 : 0.f) : hn[r];
         cx_publish4(r_h0, (ppar * (unsigned)nblk + (unsigned)rg) * rowrec, ft, i, q, hn, tag, l2x);
@@ -1217,7 +1154,7 @@ __global__ __launch_bounds__(256) void code_cluster_fwd_kernel(CodeClArgs a) {
       lds_barrier();
       if (wave == 2 && rvalid && fok) {
         float hn[4], gr_[4], gz_[4], gn_[4], gh_[4];
-        ccl_cell_epilogue(xcx, xch2[1], bias_s[1], lane, q, hown, hn, gr_, gz_, gn_, gh_);
+        gru_cell_epilogue_lds(xcx, xch2[1], bias_s[1], lane, q, hown, hn, gr_, gz_, gn_, gh_);
         cx_publish4(r_h1, (ppar * (unsigned)nblk + (unsigned)rg) * rowrec, ft, i, q, hn, tag, l2x);
         *reinterpret_cast<float4*>(sv.h1 + (int64_t)(t + 1) * BH + (int64_t)b * H + f0) = make_float4(hn[0], hn[1], hn[2], hn[3]);
         if (sv.gates1) {
@@ -1427,8 +1364,8 @@ __global__ __launch_bounds__(256) void code_cluster_fwd_kernel(CodeClArgs a) {
           }
           if (i == 0) {
             const unsigned g0 = (jpar * (unsigned)nblk + (unsigned)rg) * prec + (unsigned)f0;
-            ccl_publish4(r_p, g0, s1, jtag);
-            ccl_publish4(r_p, g0 + (unsigned)Hp, s2, jtag);
+            cx_publish4_at(r_p, g0, s1, jtag);
+            cx_publish4_at(r_p, g0 + (unsigned)Hp, s2, jtag);
           }
         }
       }
@@ -1456,23 +1393,6 @@ struct CodeClBwdArgs {
   int S1, B, H, nt, nblk;
   float p_drop;
 };
-__device__ __forceinline__ void ccl_cell_bwd(const float (&dh)[4], const float4 (&gt)[4], const float4& hp4, float (&g_r)[4],
-                                             float (&g_z)[4], float (&g_n)[4], float (&g_hn)[4], float (&direct)[4]) {
-  const float rr[4] = {gt[0].x, gt[0].y, gt[0].z, gt[0].w}, zz[4] = {gt[1].x, gt[1].y, gt[1].z, gt[1].w},
-              nn[4] = {gt[2].x, gt[2].y, gt[2].z, gt[2].w}, gh[4] = {gt[3].x, gt[3].y, gt[3].z, gt[3].w},
-              hp[4] = {hp4.x, hp4.y, hp4.z, hp4.w};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float dn = dh[r] * (1.0f - zz[r]);
-    const float dz = dh[r] * (hp[r] - nn[r]);
-    const float dnp = dn * (1.0f - nn[r] * nn[r]);
-    g_n[r] = dnp;
-    g_hn[r] = dnp * rr[r];
-    g_r[r] = dnp * gh[r] * rr[r] * (1.0f - rr[r]);
-    g_z[r] = dz * zz[r] * (1.0f - zz[r]);
-    direct[r] = dh[r] * zz[r];
-  }
-}
 __global__ __launch_bounds__(256) void code_cluster_bptt_kernel(CodeClBwdArgs a) {
   constexpr int KS = CCL_KS, NU = (2 * KS + 3) / 4, NPW = (KS + 1) / 2;
   __shared__ __attribute__((aligned(16))) float4 xs_g[6][64];      // the stage's gate gradients: dgh r z hn, dgi r z n
@@ -1539,7 +1459,7 @@ __global__ __launch_bounds__(256) void code_cluster_bptt_kernel(CodeClBwdArgs a)
       const float4 d4 = ld4_or_zero(a.dh_top + o1, own);
       float dh[4] = {d4.x + carry1[0], d4.y + carry1[1], d4.z + carry1[2], d4.w + carry1[3]};
       float g_r[4], g_z[4], g_n[4], g_hn[4];
-      ccl_cell_bwd(dh, gt1, hp1, g_r, g_z, g_n, g_hn, direct);
+      gru_cell_bwd_regs(dh, gt1, hp1, g_r, g_z, g_n, g_hn, direct);
       const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 vr = own ? make_float4(g_r[0], g_r[1], g_r[2], g_r[3]) : z4, vz = own ? make_float4(g_z[0], g_z[1], g_z[2], g_z[3]) : z4;
       const float4 vn = own ? make_float4(g_n[0], g_n[1], g_n[2], g_n[3]) : z4, vh = own ? make_float4(g_hn[0], g_hn[1], g_hn[2], g_hn[3]) : z4;
@@ -1593,7 +1513,7 @@ __global__ __launch_bounds__(256) void code_cluster_bptt_kernel(CodeClBwdArgs a)
             if (drop) v = ((kp >> (8 * r)) & 0xffu) ? v * scale_l0 : 0.f;
             dh[r] = v + carry0[r];
           }
-          ccl_cell_bwd(dh, gt0, hp0, g_r, g_z, g_n, g_hn, direct);
+          gru_cell_bwd_regs(dh, gt0, hp0, g_r, g_z, g_n, g_hn, direct);
           const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
           const float4 vr = own ? make_float4(g_r[0], g_r[1], g_r[2], g_r[3]) : z4, vz = own ? make_float4(g_z[0], g_z[1], g_z[2], g_z[3]) : z4;
           const float4 vn = own ? make_float4(g_n[0], g_n[1], g_n[2], g_n[3]) : z4, vh = own ? make_float4(g_hn[0], g_hn[1], g_hn[2], g_hn[3]) : z4;

@@ -52,19 +52,6 @@ __global__ void code_sqnorm_kernel(const float* __restrict__ W, float* __restric
   if (lane == 0) out[wave] = s;
 }
 
-// torch.argmin semantics (the reference's :1259): lowest index among equal minima; a NaN distance counts as smaller than every
-// number and the FIRST NaN wins.  A candidate therefore beats the incumbent when it is smaller, or when it is NaN and the
-// incumbent is not; on a tie (equal values, or both NaN) the lower index stays.  No sentinel index ever leaves a kernel:
-// the running pair starts at (+inf, code 0), so an all-+inf row resolves to code 0 exactly like torch.
-__device__ __forceinline__ bool argmin_better(float d2, float d) { return d2 < d || (d2 != d2 && d == d); }
-__device__ __forceinline__ void argmin_merge(float& d, int& k, float d2, int k2) {
-  const bool tie = (d2 == d) || (d2 != d2 && d != d);
-  if (argmin_better(d2, d) || (tie && k2 < k)) {
-    d = d2;
-    k = k2;
-  }
-}
-
 __global__ __launch_bounds__(256) void vq_assign_kernel(const float* __restrict__ flat, const float* __restrict__ z,
                                                         const float* __restrict__ W, const float* __restrict__ wsq,
                                                         int64_t* __restrict__ idx_out, float* __restrict__ quant,

@@ -57,15 +57,6 @@ constexpr int BZ_RT = 2;                    // row tiles per wave: 32 rows
 constexpr int BZ_ROWS = 4 * 16 * BZ_RT;     // rows per workgroup
 constexpr int BZ_IMG = BZ_CH * BZ_PPAD * 8; // bf16 elements per chunk image (28 KiB)
 
-__device__ __forceinline__ bool bz_argmin_better(float d2, float d) { return d2 < d || (d2 != d2 && d == d); }
-__device__ __forceinline__ void bz_argmin_merge(float& d, int& k, float d2, int k2) {
-  const bool tie = (d2 == d) || (d2 != d2 && d != d);
-  if (bz_argmin_better(d2, d) || (tie && k2 < k)) {
-    d = d2;
-    k = k2;
-  }
-}
-
 __device__ __forceinline__ bool bz_finite(double v) { return fabs(v) <= 3.0e38; }
 
 // one workgroup per padded code row k < Kp; workgroup Kp: |W_pre|_F and |b|
@@ -351,7 +342,7 @@ __global__ __launch_bounds__(512) void vq_bulkz_recheck_kernel(const float* __re
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float d = (xr + sq[e]) - 2.0f * acc[e];
-        if (bz_argmin_better(d, bd)) {
+        if (argmin_better(d, bd)) {
           bd = d;
           bk = 16 * tl + 4 * q + e;
         }
@@ -359,10 +350,10 @@ __global__ __launch_bounds__(512) void vq_bulkz_recheck_kernel(const float* __re
     }
     float d2 = __shfl_xor(bd, 16);
     int k2 = __shfl_xor(bk, 16);
-    bz_argmin_merge(bd, bk, d2, k2);
+    argmin_merge(bd, bk, d2, k2);
     d2 = __shfl_xor(bd, 32);
     k2 = __shfl_xor(bk, 32);
-    bz_argmin_merge(bd, bk, d2, k2);
+    argmin_merge(bd, bk, d2, k2);
     if (lane < 16) {
       wbest_d[wave * 16 + lane] = bd;
       wbest_k[wave * 16 + lane] = bk;
@@ -372,7 +363,7 @@ __global__ __launch_bounds__(512) void vq_bulkz_recheck_kernel(const float* __re
       float d = wbest_d[tid];
       int k = wbest_k[tid];
 #pragma unroll
-      for (int w = 1; w < NW; ++w) bz_argmin_merge(d, k, wbest_d[w * 16 + tid], wbest_k[w * 16 + tid]);
+      for (int w = 1; w < NW; ++w) argmin_merge(d, k, wbest_d[w * 16 + tid], wbest_k[w * 16 + tid]);
       if (rows[tid] >= 0) idx_out[rows[tid]] = (int64_t)k;
     }
     __syncthreads();
