@@ -254,6 +254,8 @@ _SIGS = {
     "g2v_kmeans_pp_workspace": (c_sz, [c_i64, c_int]),
     "g2v_kmeans_pp_step": (c_int, [c_fp, c_i64, c_int, c_fp, C.POINTER(c_i64), C.POINTER(C.c_double), c_int, c_fp, c_fp, c_fp, c_sz,
                                    c_fp]),
+    "g2v_silhouette_workspace": (c_sz, [c_i64, c_int, c_int]),
+    "g2v_silhouette_samples": (c_int, [c_fp, c_i64, c_fp, c_i64, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_sz, c_fp]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

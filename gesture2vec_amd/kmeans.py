@@ -215,3 +215,8 @@ class KMeans:
     def code_perplexity(self) -> float:
         """exp(entropy) of the fitted labels' histogram (the usage figure the VQ-VAE path reports for its codebook)."""
         return _code_perplexity(np.bincount(self.labels_, minlength=self.n_clusters))
+
+    def silhouette(self, x, sample_size=None, random_state=None) -> float:
+        """Mean silhouette coefficient of the fitted labels over the rows `x` they were fitted on (silhouette.silhouette_score)."""
+        from .silhouette import silhouette_score
+        return silhouette_score(x, self.labels_, sample_size, random_state, self.n_clusters)

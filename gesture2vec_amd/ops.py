@@ -1136,3 +1136,29 @@ def kmeans_pp_step(x, closest, pick_block, pick_resid, out, center_out):
     check(lib.g2v_kmeans_pp_step(_p(_chk(x, name="x")), N, E, _p(_chk(closest, torch.float64, "closest")), blk, res, n,
                                  _p(_chk(out, torch.float64, "out")), _p(_chk(center_out)), _p(ws), nb, _stream()), "kmeans_pp_step")
     return out
+
+
+# ------------------------------------------------------------------------------------------ silhouette (silhouette.hip)
+def silhouette_samples(x, labels, K):
+    """Silhouette terms of the clustering `labels` (N) int64 of the rows of x (N,E) fp32, unit column stride, any row stride that is a
+    multiple of 4 (g2v_silhouette_samples) -> dict(a, b, s (N) f64, counts (K+1) int64 with the out-of-range labels in counts[K],
+    out (2) f64 = [sum of s, number of non-empty clusters]).  All device tensors; nothing is read back."""
+    if not x.is_cuda:
+        raise _lib.G2VLibraryError("x must be a GPU tensor: the g2v kernels have no CPU path")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise TypeError("silhouette_samples: x must be a (N, E) fp32 tensor with unit column stride")
+    N, E = x.shape
+    K = int(K)
+    if labels.numel() != N:
+        raise ValueError("silhouette_samples: labels must hold N ids")
+    dev = x.device
+    res = {"a": torch.empty((N,), dtype=torch.float64, device=dev), "b": torch.empty((N,), dtype=torch.float64, device=dev),
+           "s": torch.empty((N,), dtype=torch.float64, device=dev), "counts": torch.empty((K + 1,), dtype=torch.int64, device=dev),
+           "out": torch.empty((2,), dtype=torch.float64, device=dev)}
+    lib = _lib_()
+    nb = int(lib.g2v_silhouette_workspace(N, E, K))
+    ws = workspace(max(nb, 16), dev, "silhouette")
+    check(lib.g2v_silhouette_samples(_p(x), int(x.stride(0)), _p(_chk(labels, torch.int64, "labels")), N, E, K, _p(res["a"]),
+                                     _p(res["b"]), _p(res["s"]), _p(res["counts"]), _p(res["out"]), _p(ws), nb, _stream()),
+          "silhouette_samples")
+    return res

@@ -1022,6 +1022,26 @@ size_t g2v_kmeans_pp_workspace(int64_t N, int E);
 int g2v_kmeans_pp_step(const float* x, int64_t N, int E, double* closest, const int64_t* pick_block, const double* pick_resid,
                        int ncand, double* out, float* center_out, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
 
+/* ---- silhouette coefficient of a clustering of latent rows (silhouette.hip; gesture2vec_amd/silhouette.py) ------------------------
+ * The second curve of the reference's k scan (Clustering.py:608-624, sklearn.metrics.silhouette_score).  x (N,E) fp32 with row stride
+ * ld >= E elements, labels (N) int64.  With c = labels[i], n_c rows in c and d the Euclidean distance (not its square):
+ *   a[i] = sum_{j in c, j != i} d(i,j) / (n_c - 1)      b[i] = min over the non-empty clusters c' != c of sum_{j in c'} d(i,j) / n_c'
+ *   s[i] = (b - a) / max(a, b); 0 where n_c = 1 and where a = b = 0 (sklearn's nan_to_num).  The term i = j is exactly 0 by rule.
+ *   a, b, s: float64[N].  counts: int64[K + 1] = rows per cluster, and in counts[K] the rows whose label is outside [0, K): those
+ *   are in no cluster, are never used as an address, and keep a = b = s = 0.  out: float64[2] = { sum_i s[i] in a fixed order,
+ *   number of non-empty clusters }.  With one non-empty cluster b = +inf and s = 0.
+ *   The rows are sorted by label with the counting sort of g2v_kmeans_update; the Gram products run on the exact-fp32 MFMA from LDS
+ *   tiles with sqrt in the accumulator epilogue, and a row's running sum is closed at each cluster boundary: neither the N x N
+ *   distances nor an N x K table of sums exist.  A pair with d^2 < (|x_i|^2 + |x_j|^2) / 8 is re-evaluated as sum (x_i - x_j)^2 in
+ *   float64 (bitwise equal rows: exactly 0), so no distance carries the cancellation of |x|^2 + |y|^2 - 2 x.y.  Every sum is formed
+ *   in an order fixed by (N, E, K, ld), the data and the labels: no floating-point atomics, the same input gives the same bits.
+ *   Needs E % 4 == 0, E <= 512, N + 16 K + 64 < 2^31 (G2V_ERR_UNSUPPORTED otherwise), 2 <= N < 2^31 - 2048, K >= 1, ld % 4 == 0;
+ *   x and workspace 16-byte aligned.  workspace: g2v_silhouette_workspace(N, E, K) bytes (0 for an unsupported shape); its
+ *   contents are not trusted across calls. */
+size_t g2v_silhouette_workspace(int64_t N, int E, int K);
+int g2v_silhouette_samples(const float* x, int64_t ld, const int64_t* labels, int64_t N, int E, int K, double* a, double* b,
+                           double* s, int64_t* counts, double* out, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

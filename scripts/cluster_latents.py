@@ -3,12 +3,16 @@
 (gesture2vec_amd/kmeans.py): the reference's `Clustering.py:705-725`.
 
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy [--n_clusters 300] [--scan-k 50:400:50]
+                              [--silhouette-rows M | --no-silhouette]
 
 `--chunks` holds (N, T, D) pose chunks in the autoencoder's input space.  Their latents (`chunk_latents`) are clustered with
 `KMeans(n_clusters, max_iter=2500, random_state=0)` and the model is pickled to `<checkpoint dir>/clusters/kmeans_model.pk`, where the
-reference's data loader and inference script look for it; `n_iter`, inertia and the code-usage perplexity are printed.
-`--scan-k a:b:step` prints the inertia curve of `Clustering.py:586-600` (`init="random", n_init=10, max_iter=300` per k) instead of
-writing a model.  The silhouette curve of that scan is not computed."""
+reference's data loader and inference script look for it; `n_iter`, inertia, the code-usage perplexity and the silhouette coefficient
+of the fitted labels are printed.
+`--scan-k a:b:step` prints the two curves of `Clustering.py:586-624` (`init="random", n_init=10, max_iter=300` per k), inertia and
+silhouette coefficient (gesture2vec_amd/silhouette.py, on the device), instead of writing a model, and returns `(k, inertia,
+silhouette)` triples.  The silhouette is taken over all latents up to 65 536 rows and over `--silhouette-rows M` rows sampled as
+sklearn's `sample_size` (seeded with `--seed`) beyond that or when M is given; `--no-silhouette` leaves it out (None in the triples)."""
 from __future__ import annotations
 
 import argparse
@@ -30,6 +34,9 @@ from gesture2vec_amd.kmeans import KMeans  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents  # noqa: E402
 
 
+SILHOUETTE_ROWS = 65536        # latents beyond this many are sampled for the silhouette coefficient
+
+
 @torch.no_grad()
 def latents_of(net, chunks: torch.Tensor, batch_rows: int) -> torch.Tensor:
     return torch.cat([chunk_latents(net, chunks[a:a + batch_rows]) for a in range(0, chunks.shape[0], batch_rows)])
@@ -45,6 +52,9 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--check_every", type=int, default=4, help="Lloyd iterations enqueued per convergence read-back")
     ap.add_argument("--scan-k", dest="scan_k", default=None, help="a:b:step -- print the inertia per k instead of writing a model")
+    ap.add_argument("--silhouette-rows", dest="silhouette_rows", type=int, default=None,
+                    help="rows the silhouette is sampled over (default: all rows up to 65536, that many sampled beyond)")
+    ap.add_argument("--no-silhouette", dest="silhouette", action="store_false", help="do not compute silhouette coefficients")
     ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk)")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
@@ -55,13 +65,23 @@ def main(argv=None):
     chunks = torch.from_numpy(np.load(a.chunks).astype(np.float32, copy=False)).to(dev)
     lat = latents_of(net, chunks, a.batch_rows)
     print(f"latents: {tuple(lat.shape)}")
+
+    def silhouette_of(km):
+        if not a.silhouette:
+            return None
+        rows = a.silhouette_rows if a.silhouette_rows is not None else (SILHOUETTE_ROWS if lat.shape[0] > SILHOUETTE_ROWS else None)
+        if rows is not None and rows >= lat.shape[0]:
+            rows = None
+        return km.silhouette(lat, sample_size=rows, random_state=a.seed)
+
     if a.scan_k:
         lo, hi, step = (int(v) for v in a.scan_k.split(":"))
         curve = []
         for k in range(lo, hi, step):
             km = KMeans(n_clusters=k, init="random", n_init=10, max_iter=300, random_state=a.seed, check_every=a.check_every).fit(lat)
-            curve.append((k, km.inertia_))
-            print(f"k = {k}: inertia {km.inertia_!r}")
+            sil = silhouette_of(km)
+            curve.append((k, km.inertia_, sil))
+            print(f"k = {k}: inertia {km.inertia_!r}" + (f", silhouette {sil!r}" if a.silhouette else ""))
         return curve
     km = KMeans(n_clusters=a.n_clusters, n_init=a.n_init, max_iter=a.max_iter, random_state=a.seed, check_every=a.check_every).fit(lat)
     out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "clusters", "kmeans_model.pk")
@@ -71,6 +91,8 @@ def main(argv=None):
     print(f"n_iter: {km.n_iter_}")
     print(f"inertia: {km.inertia_!r}")
     print(f"code-usage perplexity: {km.code_perplexity()!r} of {km.n_clusters}")
+    if a.silhouette:
+        print(f"silhouette: {silhouette_of(km)!r}")
     print(f"wrote {out}")
     return km
 
