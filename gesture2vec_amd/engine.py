@@ -107,8 +107,8 @@ class _DeferredReductions:
     def flush(self):
         live = [p for p in self.pend if p.nprob > 0]
         self.pend, self.off = [], 0
-        for k in range(0, len(live), 8):
-            chunk = live[k:k + 8]
+        for k in range(0, len(live), _lib.WGRAD_PENDING_MAX):
+            chunk = live[k:k + _lib.WGRAD_PENDING_MAX]
             arr = (_lib.WgradPending * len(chunk))(*chunk)
             check(self.eng.lib.g2v_linear_bwd_weight_reduce(arr, len(chunk), self.eng._stream()))
 
@@ -1013,7 +1013,7 @@ class VQVAEEngine:
         lib = self.lib
         ws, wsn = _p(b[ws_key]), b[ws_key].numel()
         G, H = 3 * self.H, self.H
-        flags = 2 if self.wgrad_bf16x3 else 0
+        flags = _lib.WGRAD_BF16X3 if self.wgrad_bf16x3 else 0
 
         def wgrad(dy, lddy, x, ldx, wname, bname, N_, K_, rows=M_default, row_map=(0, 0, 0), keep=None, scale=1.0):
             if deferred is not None and keep is None:

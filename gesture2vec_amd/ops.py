@@ -192,6 +192,11 @@ def linear_bwd_data(dy, w, *, M=None, lddy=None, out=None, lddx=None, accumulate
     return out
 
 
+def _wgrad_flags(accumulate, bf16x3=False) -> int:
+    """the flag word of the g2v_linear_bwd_weight family (include/g2v.h G2V_WGRAD_*)"""
+    return (_lib.WGRAD_ACCUMULATE if accumulate else 0) | (_lib.WGRAD_BF16X3 if bf16x3 else 0)
+
+
 def linear_bwd_weight(dy, x, N, K, *, M=None, lddy=None, ldx=None, row_map=None, keep=None, scale=1.0,
                       dw=None, db=None, want_bias=True, accumulate=False, bf16x3=False):
     """dw = dy^T xin (+ db).  bf16x3=True allows the 3-term bf16 split products (G2V_WGRAD_BF16X3, ~1.5e-5 relative)."""
@@ -211,7 +216,7 @@ def linear_bwd_weight(dy, x, N, K, *, M=None, lddy=None, ldx=None, row_map=None,
     ws = workspace(nbytes, dev, "bwdw")
     ri, so, si = row_map if row_map is not None else (0, 0, 0)
     check(lib.g2v_linear_bwd_weight(_p(dy), lddy, _p(x), ldx, ri, so, si, _p(keep), float(scale), _p(dw), _p(db),
-                                    M, K, N, int(bool(accumulate)) | (2 if bf16x3 else 0), _p(ws), ws.numel(), _stream()),
+                                    M, K, N, _wgrad_flags(accumulate, bf16x3), _p(ws), ws.numel(), _stream()),
           "linear_bwd_weight")
     return dw, db
 
@@ -245,11 +250,11 @@ def linear_bwd_weight_batch(items, N, K, *, M, lddy=None, ldx=None, accumulate=F
     if row_map is not None:
         check(lib.g2v_linear_bwd_weight_batch_mapped(arr, len(items), lddy if lddy is not None else N, ldx if ldx is not None else K,
                                                      row_map[0], row_map[1], row_map[2], M, K, N,
-                                                     int(bool(accumulate)) | (2 if bf16x3 else 0), _p(ws), ws.numel(), _stream()),
+                                                     _wgrad_flags(accumulate, bf16x3), _p(ws), ws.numel(), _stream()),
               "linear_bwd_weight_batch_mapped")
         return
     check(lib.g2v_linear_bwd_weight_batch(arr, len(items), lddy if lddy is not None else N, ldx if ldx is not None else K, M, K, N,
-                                          int(bool(accumulate)) | (2 if bf16x3 else 0), _p(ws), ws.numel(), _stream()),
+                                          _wgrad_flags(accumulate, bf16x3), _p(ws), ws.numel(), _stream()),
           "linear_bwd_weight_batch")
 
 
@@ -273,12 +278,12 @@ def linear_bwd_weight_deferred(calls, *, accumulate=False):
         rm = c.get("row_map") or (0, 0, 0)
         pd = _lib.WgradPending()
         check(lib.g2v_linear_bwd_weight_deferred(arr, len(c["items"]), c.get("lddy", c["N"]), c.get("ldx", c["K"]), rm[0], rm[1], rm[2],
-                                                 _p(c.get("dy_b")), c["M"], c["K"], c["N"], int(bool(accumulate)), ws.data_ptr() + off, nb,
+                                                 _p(c.get("dy_b")), c["M"], c["K"], c["N"], _wgrad_flags(accumulate), ws.data_ptr() + off, nb,
                                                  C.byref(pd), _stream()), "linear_bwd_weight_deferred")
         pend.append(pd)
     live = [p_ for p_ in pend if p_.nprob > 0]
-    for k in range(0, len(live), 8):
-        chunk = live[k:k + 8]
+    for k in range(0, len(live), _lib.WGRAD_PENDING_MAX):
+        chunk = live[k:k + _lib.WGRAD_PENDING_MAX]
         check(lib.g2v_linear_bwd_weight_reduce((_lib.WgradPending * len(chunk))(*chunk), len(chunk), _stream()), "linear_bwd_weight_reduce")
     return [p_.nprob for p_ in pend]
 
@@ -428,7 +433,7 @@ def vq_fused_assign(z, w_pre, b_pre, codebook, code_sqnorm, codebook_frag=None):
     return flat, idx, quant, sse
 
 
-VQ_BX_EXACT = 1          # include/g2v.h G2V_VQ_BX_*
+VQ_BX_EXACT = _lib.VQ_BX_EXACT          # include/g2v.h G2V_VQ_BX_*
 
 
 def vq_bx_pack(codebook, code_sqnorm, w_pre, b_pre, out=None):

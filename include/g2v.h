@@ -29,6 +29,7 @@ extern "C" {
 #endif
 
 typedef void* g2v_stream_t; /* hipStream_t */
+#define G2V_HOST /* host memory; every untagged pointer is device memory or a caller-owned struct */
 
 #define G2V_OK 0
 #define G2V_ERR_ARG (-1)         /* bad argument (null pointer, non-positive size, misalignment) */
@@ -356,7 +357,7 @@ typedef struct {          /* one direction of one layer, forward */
    * (lengths sorted descending, as pack_padded_sequence(enforce_sorted) requires; gi_row_off[t] = n_0 + ... + n_{t-1}) -- the
    * dense product that makes gi runs over sum(lengths) rows instead of T x B.  T <= 64, the generic kernels with H % 4 == 0
    * (g2v_gru_seq_packed_ok); every direction of the call must carry the same offsets.  hs / gates keep the (T,B,.) layout. */
-  const int32_t* gi_row_off;
+  G2V_HOST const int32_t* gi_row_off;
   /* Gathered input projections (round 6; NULL = off): gi is a TABLE (V, 3H), and row r of the layout above -- r = t * B + b, or
    * gi_row_off[t] + b when packed -- is gi + gi_gather[r] * 3H.  The encoder the reference feeds straight from nn.Embedding
    * (model/text2embedding_model.py:126-131): the projected table G = E W_ih^T + b_ih is gathered inside the recurrent kernel
@@ -429,7 +430,7 @@ typedef struct {
   float hn_coef;
   /* Packed dgi (NULL = (T,B,3H)): as g2v_gru_dir.gi_row_off -- dgi row (t,b) at dgi + (dgi_row_off[t] + b) * 3H, only positions
    * inside their sequences are written (sum(lengths) rows); dgh keeps the (T,B,3H) layout with zero rows at padded positions. */
-  const int32_t* dgi_row_off;
+  G2V_HOST const int32_t* dgi_row_off;
 } g2v_gru_dir_bwd;
 size_t g2v_gru_seq_bwd_wslab_bytes(int B, int H);
 size_t g2v_gru_seq_bwd_workspace(int ndir, int H);   /* room for W_hh^T (fragment order) */
@@ -1019,8 +1020,9 @@ int g2v_kmeans_tolerance(const float* x, int64_t N, int E, double tol, double* o
                          g2v_stream_t stream);
 int g2v_kmeans_pp_blocks(int64_t N);
 size_t g2v_kmeans_pp_workspace(int64_t N, int E);
-int g2v_kmeans_pp_step(const float* x, int64_t N, int E, double* closest, const int64_t* pick_block, const double* pick_resid,
-                       int ncand, double* out, float* center_out, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+int g2v_kmeans_pp_step(const float* x, int64_t N, int E, double* closest, G2V_HOST const int64_t* pick_block,
+                       G2V_HOST const double* pick_resid, int ncand, double* out, float* center_out, void* workspace,
+                       size_t workspace_bytes, g2v_stream_t stream);
 
 /* ---- silhouette coefficient of a clustering of latent rows (silhouette.hip; gesture2vec_amd/silhouette.py) ------------------------
  * The second curve of the reference's k scan (Clustering.py:608-624, sklearn.metrics.silhouette_score).  x (N,E) fp32 with row stride
