@@ -586,7 +586,10 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
   if (lane == 0) row_loss[row] = lse - z[t];
   if (dlogits) {
     float* d = dlogits + (int64_t)row * ldd;
-    for (int k = lane; k < K; k += 64) d[k] = gcoef * (expf(z[k] - lse) - (k == t ? 1.0f : 0.0f));
+    // softmax as exp(z - mx) / s, not exp(z - lse): lse is rounded at ITS magnitude, and half an ulp of an lse near 5000 (2.4e-4)
+    // is a relative error of that size in every probability of the row (tests/test_gpu_loss_path.py: 8.5e-5 of the gradient)
+    const float inv_s = 1.0f / s;
+    for (int k = lane; k < K; k += 64) d[k] = gcoef * (expf(z[k] - mx) * inv_s - (k == t ? 1.0f : 0.0f));
   }
 }
 __global__ void mean_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
