@@ -265,6 +265,9 @@ class TrinityDataset_sentencelevel:
             if vq_layer is None and self.kmeans is not None:               # quantiser-free autoencoder: kmeanmodel.predict (:1287-1292)
                 yield words, lengths, poses, audio, aux, lat_d, self.kmeans.predict_device(rows).view(B, S), gpt3
                 continue
+            if vq_layer is None:            # neither a quantiser nor a k-means model: the latents alone (text2_embedding_discrete: False)
+                yield words, lengths, poses, audio, aux, lat_d, None, gpt3
+                continue
             assign = getattr(self.vq_net.vq_layer, "assign", None)         # one launch sequence for the batch
             if assign is not None:
                 codes = assign(rows).view(B, S)

@@ -226,6 +226,29 @@ class BatchNormReluFn(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+class BatchNormReluStatsFn(torch.autograd.Function):
+    """BatchNormReluFn in training mode that also returns the saved (mean, 1/sqrt(var + eps)) as non-differentiable outputs: a caller
+    that passed running_mean = running_var = None commits the running statistics later (ops.bn_running_update_invstd)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, relu):
+        x = x.contiguous()
+        y, sm, si = ops.batchnorm_fwd(x, weight, bias, running_mean, running_var, True, relu)
+        ctx.save_for_backward(x, y, weight, sm, si)
+        ctx.relu = relu
+        ctx.mark_non_differentiable(sm, si)
+        ctx.set_materialize_grads(False)
+        return y, sm, si
+
+    @staticmethod
+    def backward(ctx, gy, _gsm, _gsi):
+        if gy is None:
+            return (None,) * 6
+        x, y, weight, sm, si = ctx.saved_tensors
+        dx, dw, db = ops.batchnorm_bwd(gy.contiguous(), x, y, weight, sm, si, ctx.relu)
+        return dx, dw, db, None, None, None
+
+
 class GRUDirFn(torch.autograd.Function):
     """One direction of one GRU layer over a (T,B,.) sequence given its input projections gi = x W_ih^T + b_ih.
     Returns (hs (T,B,H), h_n (B,H)).  `lengths` (int32, B) gives pack_padded_sequence semantics (h0 must be None)."""

@@ -7,8 +7,10 @@ state_dict keys.  Every operator is a HIP kernel behind include/g2v.h, chained b
 
 Module-level switches of the reference (:40-43) are all False here: `use_TCN = True` as checked in makes the
 reference's forward crash, `audio_context`, `noisy`, `GPT3_embedding_active` select out-of-scope
-encoders.  Scope: text2_embedding_discrete == "True"; autoencoder_att == "False" (config/seq2seq.yml:27) and "True"
-(config/seq2seqtxt.yml:37, Bahdanau attention `Attn` :138-198 through g2v_attn_fwd / g2v_attn_bwd)."""
+encoders.  Scope: text2_embedding_discrete == "True" (codes, cross-entropy) and "False" (the chunks' latent vectors, width
+n_layers * hidden_size, regressed with MSE; the decoder then has no embedding / Dropout(0.5) / argmax and feeds its output back
+with the gradient attached, :741); autoencoder_att == "False" (config/seq2seq.yml:27) and "True" (config/seq2seqtxt.yml:37,
+Bahdanau attention `Attn` :138-198 through g2v_attn_fwd / g2v_attn_bwd)."""
 from __future__ import annotations
 
 import math
@@ -21,7 +23,8 @@ import torch.nn.functional as F
 
 from .. import functional as Fn
 from .. import ops
-from ..rollout_t2e import CodeDecoderRollout, RolloutSpec, decoder_params
+from ..rollout_t2e import (CodeDecoderRollout, LatentDecoderRollout, RolloutSpec, decoder_params, latent_decoder_params,
+                           latent_fused_ok)
 from .Autoencoder_VQVAE_model import Attn, _GRUParams
 
 debug = False
@@ -141,16 +144,16 @@ class BahdanauAttnDecoderRNN(nn.Module):
         super().__init__()
         self.hidden_size, self.output_size, self.n_layers, self.dropout_p = hidden_size, output_size, n_layers, dropout_p
         self.discrete_representation, self.speaker_model = discrete_representation, speaker_model
-        if not discrete_representation:
-            raise NotImplementedError("text2_embedding_discrete == 'False' is outside the accelerated hot path")
         if speaker_model:
             raise NotImplementedError("speaker embedding is outside the accelerated hot path")
-        self.embedding = nn.Embedding(output_size, hidden_size)
-        self.dropout = nn.Dropout(0.5)
+        if discrete_representation:                                                  # :258-267
+            self.embedding = nn.Embedding(output_size, hidden_size)
+            self.dropout = nn.Dropout(0.5)
+            input_size = hidden_size
         self.att_use = args.autoencoder_att == "True"
         if self.att_use:
             self.attn = Attn(hidden_size)
-        linear_input_size = 2 * hidden_size if self.att_use else hidden_size          # :277-281
+        linear_input_size = input_size + hidden_size if self.att_use else input_size   # :277-284
         self.pre_linear = nn.Sequential(nn.Linear(linear_input_size, hidden_size), nn.BatchNorm1d(hidden_size), nn.ReLU(inplace=True))
         self.gru = _GRUParams(hidden_size, hidden_size, n_layers, dropout=dropout_p)
         self.out = nn.Linear(hidden_size, output_size)
@@ -162,14 +165,19 @@ class BahdanauAttnDecoderRNN(nn.Module):
             param.requires_grad = False
 
     def forward(self, motion_input, last_hidden, encoder_outputs=None, vid_indices=None, keep_emb=None, keep_l0=None,
-                enc_proj=None):
-        """One decode step: code ids (B,) + hidden (L,B,H) [+ encoder outputs (T,B,H) with attention] -> logits (B,K),
-        new hidden (L,B,H), attention weights (B,1,T) or None.  `enc_proj` = Attn.project_encoder(encoder_outputs)
-        may be passed in so that the S-1 steps share it."""
+                enc_proj=None, bn_defer=None):
+        """One decode step: code ids (B,) [continuous mode: the input latents (B,E) as they come, :344-346] + hidden (L,B,H)
+        [+ encoder outputs (T,B,H) with attention] -> logits (B,K) [latents (B,E)], new hidden (L,B,H), attention weights (B,1,T)
+        or None.  `enc_proj` = Attn.project_encoder(encoder_outputs) may be passed in so that the S-1 steps share it.
+        `bn_defer` (a list, training): BatchNorm leaves its running statistics alone and appends what
+        text2embedding_model.commit_bn_running_stats applies later."""
         B = motion_input.shape[0]
         H, L = self.hidden_size, self.n_layers
         training = self.training
-        e = Fn.EmbeddingFn.apply(self.embedding.weight, motion_input, keep_emb if training else None, 2.0)   # Dropout(0.5)
+        if self.discrete_representation:
+            e = Fn.EmbeddingFn.apply(self.embedding.weight, motion_input, keep_emb if training else None, 2.0)   # Dropout(0.5)
+        else:
+            e = motion_input.reshape(B, -1)
         attn_weights = None
         if self.att_use:
             context, w = self.attn.context(last_hidden[-1], encoder_outputs, enc_proj)     # :353-359
@@ -177,7 +185,11 @@ class BahdanauAttnDecoderRNN(nn.Module):
             attn_weights = w.unsqueeze(1)
         lin, bn = self.pre_linear[0], self.pre_linear[1]
         u = Fn.linear(e, lin.weight, lin.bias)
-        a = Fn.BatchNormReluFn.apply(u, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, True)
+        if training and bn_defer is not None:
+            a, sm, si = Fn.BatchNormReluStatsFn.apply(u, bn.weight, bn.bias, None, None, True)
+            bn_defer.append((sm, si, H, 1, B, H))
+        else:
+            a = Fn.BatchNormReluFn.apply(u, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, True)
         if training:
             bn.num_batches_tracked += 1
         new_h, layer_in, keep, scale = [], a, None, 1.0
@@ -215,13 +227,11 @@ class text2embedding_model(nn.Module):
                  speaker_model=None):
         super().__init__()
         self.text2_embedding_discrete = args.text2_embedding_discrete == "True"
-        if not self.text2_embedding_discrete:
-            raise NotImplementedError("text2_embedding_discrete == 'False' is outside the accelerated hot path")
         self.n_layers = args.n_layers
-        pose_dim = int(args.autoencoder_vq_components)
+        pose_dim = int(args.autoencoder_vq_components) if self.text2_embedding_discrete else args.n_layers * args.hidden_size   # :543-546
         self.encoder = EncoderRNN(n_words, word_embed_size, args.hidden_size, args.n_layers, dropout=args.dropout_prob,
                                   pre_trained_embedding=word_embeddings)
-        self.decoder = Generator(args, pose_dim, discrete_representation=True, speaker_model=speaker_model)
+        self.decoder = Generator(args, pose_dim, discrete_representation=self.text2_embedding_discrete, speaker_model=speaker_model)
         self.n_frames, self.n_pre_poses, self.pose_dim = n_frames, args.n_pre_poses, pose_dim
         self.sentence_frame_length = args.sentence_frame_length
         self.dropout_prob = float(args.dropout_prob)
@@ -250,7 +260,8 @@ class text2embedding_model(nn.Module):
 
     def set_dropout_masks(self, mask_emb, mask_dec_l0=None, mask_enc_l0=None):
         """Explicit keep masks for the next training forward (parity tests): (S-1,B,H) for the code-embedding dropout and
-        the decoder GRU inter-layer dropout, (Tw,B,2H) for the encoder GRU inter-layer dropout (attention only)."""
+        the decoder GRU inter-layer dropout, (Tw,B,2H) for the encoder GRU inter-layer dropout (attention only).  The continuous
+        mode has no embedding dropout: `mask_emb` is ignored there (pass None)."""
         self._masks = (mask_emb, mask_dec_l0, mask_enc_l0)
 
     def _draw(self, shape, keep_prob, dev):
@@ -271,6 +282,8 @@ class text2embedding_model(nn.Module):
     def forward(self, in_text, in_lengths, in_audio, poses, GPT3_embeddings, vid_indices):
         if not in_text.is_cuda:
             raise RuntimeError("text2embedding_model runs on the MI355X kernels only (no CPU fallback)")
+        if not self.text2_embedding_discrete:
+            return self._forward_latents(in_text, in_lengths, poses, vid_indices)
         if vid_indices is not None and self.training:
             raise NotImplementedError("vid_indices is the reference's inference branch (:685-692): call it in eval mode")
         dev = in_text.device
@@ -335,6 +348,67 @@ class text2embedding_model(nn.Module):
             outs.append(logits)
             dec_in = cod[t] if t < self.n_pre_poses else ops.argmax_rows(logits.detach().contiguous())
         return torch.stack(outs).transpose(0, 1), attentions_list
+
+    def _forward_latents(self, in_text, in_lengths, poses, vid_indices):
+        """text2_embedding_discrete == "False" (reference :675-679, 701-746): poses (B,S,E) float, the chunks' latent vectors;
+        outputs[0] = poses[0]; step t reads poses[t-1] while t <= n_pre_poses and outputs[t-1] afterwards -- the tensor itself, so
+        the loss gradient of step t flows into step t-1 (:741).  Training without attention from LATENT_FUSED_MIN_ROWS rows: the
+        fused step kernels (rollout_t2e.LatentDecoderRollout); otherwise one autograd node per operator and step."""
+        if vid_indices is not None:
+            raise ValueError("vid_indices with text2_embedding_discrete == 'False': the reference's inference branch (:685-692) feeds "
+                             "integer ids into a float decoder and takes an argmax of latents; it is refused in this mode")
+        dev = in_text.device
+        ids = in_text.transpose(0, 1).contiguous()                                       # (Tw,B)
+        S_model = self.sentence_frame_length // self.n_frames
+        tgt = poses.transpose(0, 1).to(torch.float32).contiguous()                       # (S,B,E)
+        B, E, H, L = tgt.shape[1], self.pose_dim, self.encoder.hidden_size, self.n_layers
+        if tgt.shape[0] < S_model or tgt.shape[2] != E:
+            raise ValueError(f"poses: expected (B, >= {S_model}, {E}) latents, got {tuple(poses.shape)}")
+        training = self.training
+        dec = self.decoder.decoder
+        att = dec.att_use
+        Tw = ids.shape[0]
+        mask_l0 = mask_enc = None
+        if training:
+            if self._masks is not None:
+                _, mask_l0, mask_enc = self._masks
+            elif self.dropout_prob > 0:
+                want = [((S_model - 1, B, H), 1.0 - self.dropout_prob)]
+                if att and L > 1:
+                    want.append(((Tw, B, 2 * H), 1.0 - self.dropout_prob))
+                mask_l0, mask_enc = (self._draw_many(want, dev) + [None])[:2]
+        if att:
+            enc_out, enc_hidden = self.encoder(ids, in_lengths, None, keep_inter=mask_enc)
+            enc_proj = dec.attn.project_encoder(enc_out)
+        else:
+            _, enc_hidden = self.encoder(ids, in_lengths, None, n_layers_needed=1, want_outputs=False)
+            enc_out = enc_proj = None
+        hidden = enc_hidden[:L] if enc_hidden.shape[0] != L else enc_hidden
+        bn = dec.pre_linear[1]
+        if training and self.fused_rollout and S_model > 1 and latent_fused_ok(B, H, E, S_model - 1, L, att):
+            spec = RolloutSpec(tgt, S_model - 1, self.n_pre_poses, L, False, self.dropout_prob, None, mask_l0,
+                               bn.running_mean, bn.running_var, defer_bn=self.deferred_bn)
+            full = LatentDecoderRollout.apply(hidden, spec, *latent_decoder_params(dec))          # (S,B,E)
+            bn.num_batches_tracked += S_model - 1
+            attentions_list = []
+        else:
+            outs: List[torch.Tensor] = [tgt[0]]
+            dec_in = tgt[0]
+            attentions_list = []
+            for t in range(1, S_model):
+                kl = mask_l0[t - 1].contiguous() if (training and mask_l0 is not None) else None
+                y, hidden, attn_w = self.decoder(None, dec_in, hidden, enc_out, None, keep_l0=kl, enc_proj=enc_proj,
+                                                 bn_defer=self.deferred_bn if training else None)
+                if att:
+                    attentions_list.append(attn_w)
+                outs.append(y)
+                dec_in = tgt[t] if t < self.n_pre_poses else y                           # :734-741: the output, not detached
+            full = torch.stack(outs)
+        outputs = full.transpose(0, 1)                                                    # (B,S,E), a view
+        # the step-major array behind the view and the targets in the same order: train_seq2seq._latent_loss_backward
+        outputs._g2v_step_major = full
+        outputs._g2v_targets = tgt[:S_model]
+        return outputs, attentions_list
 
 
 # ---- the "*_New" tutorial-style classes (reference :754-1002; imported by train_text2embedding.py:57, never

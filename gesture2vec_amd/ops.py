@@ -708,6 +708,30 @@ def code_rollout_bwd(d_logits, enc, enc_proj, weights: dict, saved: dict, grads:
                                         _stream()), "attn_code_rollout_bwd")
 
 
+# ------------------------------------------------------------------------------------------ Part d on continuous latents
+def latent_rollout_ok(S1, B, H, E, att) -> bool:
+    return bool(_lib_().g2v_latent_rollout_ok(int(S1), int(B), int(H), int(E), int(bool(att))))
+
+
+def latent_rollout_fwd(target, h_init, weights: dict, saved: dict, keep_l0, p_drop, n_pre, S1, B, H, E):
+    """g2v_latent_rollout_fwd: S1 + 1 launches of the fused decoder-step kernel of the continuous mode (weights / saved: dicts of
+    tensors named as the fields of g2v_code_dec_weights / g2v_code_dec_saved with K := E; missing = NULL)."""
+    lib = _lib_()
+    ws = workspace(lib.g2v_latent_rollout_fwd_workspace(H, E), h_init.device, "latfwd")
+    check(lib.g2v_latent_rollout_fwd(_p(_chk(target)), _p(_chk(h_init)), C.byref(struct_from(CodeDecWeights, weights)),
+                                     C.byref(struct_from(CodeDecSaved, saved)), _p(keep_l0), float(p_drop), int(n_pre), S1, B, H, E,
+                                     _p(ws), ws.numel(), _stream()), "latent_rollout_fwd")
+
+
+def latent_rollout_bwd(d_out, weights: dict, saved: dict, grads: dict, keep_l0, p_drop, n_pre, S1, B, H, E):
+    lib = _lib_()
+    ws = workspace(lib.g2v_latent_rollout_bwd_workspace(S1, B, H, E), d_out.device, "latbwd")
+    check(lib.g2v_latent_rollout_bwd(_p(_chk(d_out)), C.byref(struct_from(CodeDecWeights, weights)),
+                                     C.byref(struct_from(CodeDecSaved, saved)), C.byref(struct_from(CodeDecGrads, grads)),
+                                     _p(keep_l0), float(p_drop), int(n_pre), S1, B, H, E, _p(ws), ws.numel(), _stream()),
+          "latent_rollout_bwd")
+
+
 # ------------------------------------------------------------------------------------------ loss / optimiser / rng
 def custom_loss_fwd_bwd(y_tbd, target_btd, w_l1, w_cont, w_var, g_scale=1.0, want_grad=True):
     T, B, D = y_tbd.shape
@@ -766,10 +790,13 @@ def scale(inp, scalar_dev, out=None):
     return out
 
 
-def mse_fwd_bwd(y, target, want_grad=True, g_scale=1.0):
+def mse_fwd_bwd(y, target, want_grad=True, g_scale=1.0, dy_out=None):
+    """dy_out: a contiguous buffer of y's size for the gradient (a slice of a larger array, say)"""
     lib = _lib_()
     n = y.numel()
-    dy = torch.empty_like(y) if want_grad else None
+    dy = (dy_out if dy_out is not None else torch.empty_like(y)) if want_grad else None
+    if dy is not None:
+        _chk(dy, name="dy_out")
     loss = torch.empty((1,), dtype=torch.float32, device=y.device)
     partial = torch.empty((lib.g2v_mse_blocks(n),), dtype=torch.float32, device=y.device)
     check(lib.g2v_mse_fwd_bwd(_p(_chk(y)), _p(_chk(target)), _p(dy), _p(loss), _p(partial), n, float(g_scale), _stream()),

@@ -405,3 +405,86 @@ class CodeDecoderRollout(torch.autograd.Function):
             dW_e, _ = ops.linear_bwd_weight(D_EP.view(Tw * B, H), b["enc"].view(Tw * B, H), H, H, want_bias=False)
             grads += [torch.cat([dW_h, dW_e], 1), d_attn_b, D_V]
         return (d_hidden0, d_enc, None, *grads)
+
+
+# ---- continuous latents (text2_embedding_discrete: False) -----------------------------------------------------------------------
+# The decoder regresses each chunk's latent vector and feeds its OUTPUT back with the gradient attached (reference :741), so
+# d loss / d y_t carries du_{t+1} W_pre, which needs BatchNorm's backward of step t+1 -- a sum over all batch rows.  The one-launch
+# BPTT above does not apply; csrc/t2e_latent.hip runs one forward and one backward launch per step (g2v_latent_rollout_fwd / _bwd).
+# Batch size from which those fused kernels serve the attention-free decoder; below it, and with attention, the steps are chained
+# from the per-operator autograd nodes (text2embedding_model.forward).  The value is INHERITED from FUSED_MIN_ROWS, not measured
+# for this decoder.
+LATENT_FUSED_MIN_ROWS = 1024
+LATENT_FUSED_CALLS = 0
+
+
+def latent_decoder_params(dec) -> List[torch.Tensor]:
+    """Parameter order of LatentDecoderRollout for a continuous BahdanauAttnDecoderRNN without attention (no embedding)."""
+    lin, bn, g = dec.pre_linear[0], dec.pre_linear[1], dec.gru
+    ps = [lin.weight, lin.bias, bn.weight, bn.bias]
+    for l in range(dec.n_layers):
+        ps += [getattr(g, f"weight_ih_l{l}"), getattr(g, f"weight_hh_l{l}"), getattr(g, f"bias_ih_l{l}"), getattr(g, f"bias_hh_l{l}")]
+    return ps + [dec.out.weight, dec.out.bias]
+
+
+def latent_fused_ok(B: int, H: int, E: int, steps: int, L: int, att: bool) -> bool:
+    return L == 2 and not att and B >= LATENT_FUSED_MIN_ROWS and ops.latent_rollout_ok(steps, B, H, E, att)
+
+
+class LatentDecoderRollout(torch.autograd.Function):
+    """(hidden0 (2,B,H), spec, *latent_decoder_params) -> outputs (S,B,E): slot 0 = target[0], slots 1.. = the S-1 decode steps'
+    outputs.  spec.cod = the targets (S,B,E) float, step-major; spec.mask_emb is unused (this mode has no embedding)."""
+
+    @staticmethod
+    def forward(ctx, hidden0, spec: RolloutSpec, *params):
+        global LATENT_FUSED_CALLS
+        LATENT_FUSED_CALLS += 1
+        S1 = spec.steps
+        B, H = hidden0.shape[1], hidden0.shape[2]
+        pre_w, pre_b, bn_w, bn_b = params[:4]
+        (w_ih0, w_hh0, b_ih0, b_hh0), (w_ih1, w_hh1, b_ih1, b_hh1) = params[4:8], params[8:12]
+        out_w, out_b = params[12:14]
+        E = out_w.shape[0]
+        dev = hidden0.device
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        wd = dict(w_pre=pre_w.contiguous(), b_pre=pre_b, bn_w=bn_w, bn_b=bn_b, bn_running_mean=spec.bn_running_mean,
+                  bn_running_var=spec.bn_running_var, w_ih0=w_ih0.contiguous(), w_hh0=w_hh0.contiguous(), b_ih0=b_ih0, b_hh0=b_hh0,
+                  w_ih1=w_ih1.contiguous(), w_hh1=w_hh1.contiguous(), b_ih1=b_ih1, b_hh1=b_hh1, w_out=out_w.contiguous(), b_out=out_b)
+        drop = spec.dropout_p > 0 and spec.mask_l0 is not None
+        mask_l0 = spec.mask_l0.contiguous() if drop else None
+        nblk = (B + 15) // 16
+        sv = dict(ec=f32(S1, B, E), u=f32(S1, B, H), a=f32(S1, B, H), bn_stats=f32(S1, 2, H), h0=f32(S1 + 1, B, H),
+                  h1=f32(S1 + 1, B, H), x1=f32(S1, B, H) if drop else None, gates0=f32(S1, B, 4 * H), gates1=f32(S1, B, 4 * H),
+                  bn_partial=f32(2, nblk, 2, H))
+        target = spec.cod
+        full = f32(S1 + 1, B, E)
+        full[0].copy_(target[0])                                       # outputs[0] = poses[0] (reference :678-679)
+        sv["logits"] = full[1:]
+        ops.latent_rollout_fwd(target, hidden0.contiguous(), wd, sv, mask_l0, spec.dropout_p if drop else 0.0, spec.n_pre,
+                               S1, B, H, E)
+        if spec.defer_bn is not None:
+            spec.defer_bn.append((sv["bn_stats"], sv["bn_stats"].view(-1)[H:], 2 * H, S1, B, H))
+        ctx.save_for_backward(hidden0, *params)
+        ctx.spec, ctx.dims = spec, (S1, B, H, E)
+        # (the outputs are this node's OUTPUT: see _fused_forward on why they are not kept on ctx)
+        ctx.bufs = dict(wd=wd, sv={k: t for k, t in sv.items() if k != "logits"}, mask_l0=mask_l0, drop=drop)
+        ctx.set_materialize_grads(False)
+        return full
+
+    @staticmethod
+    def backward(ctx, dFULL):
+        S1, B, H, E = ctx.dims
+        if dFULL is None:
+            return (None,) * (2 + 14)
+        b, spec = ctx.bufs, ctx.spec
+        d_out = dFULL.contiguous()[1:]                                  # slot 0 is a constant
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=d_out.device)
+        G = 3 * H
+        gr = dict(d_hidden0=f32(2, B, H), d_w_pre=f32(H, E), d_b_pre=f32(H), d_bn_w=f32(H), d_bn_b=f32(H),
+                  d_w_ih0=f32(G, H), d_w_hh0=f32(G, H), d_b_ih0=f32(G), d_b_hh0=f32(G),
+                  d_w_ih1=f32(G, H), d_w_hh1=f32(G, H), d_b_ih1=f32(G), d_b_hh1=f32(G), d_w_out=f32(E, H), d_b_out=f32(E))
+        ops.latent_rollout_bwd(d_out, b["wd"], b["sv"], gr, b["mask_l0"], spec.dropout_p if b["drop"] else 0.0, spec.n_pre,
+                               S1, B, H, E)
+        return (gr["d_hidden0"], None, gr["d_w_pre"], gr["d_b_pre"], gr["d_bn_w"], gr["d_bn_b"],
+                gr["d_w_ih0"], gr["d_w_hh0"], gr["d_b_ih0"], gr["d_b_hh0"], gr["d_w_ih1"], gr["d_w_hh1"], gr["d_b_ih1"], gr["d_b_hh1"],
+                gr["d_w_out"], gr["d_b_out"])

@@ -356,16 +356,39 @@ def _code_loss_backward(outputs, codes):
     return loss.view(())
 
 
+def _latent_loss_backward(outputs, target_poses):
+    """loss = F.mse_loss(outputs[:, 1:], target_poses[:, 1:]) (reference :509-510); loss.backward() -- returns the (detached) loss.
+    As in _code_loss_backward the loss is the root of the graph: on the model's step-major (S,B,E) outputs the MSE kernel's own
+    gradient, 2 (y - target) / (B (S-1) E), is handed to the rollout straight away.  Slot 0 is a constant (outputs[0] = poses[0])."""
+    from .. import ops
+    from ..functional import mse_loss
+    full = getattr(outputs, "_g2v_step_major", None)
+    tgt = getattr(outputs, "_g2v_targets", None)
+    if (full is None or tgt is None or not full.requires_grad or full.shape[0] != outputs.shape[1]
+            or full.shape[1] != outputs.shape[0] or tgt.shape != full.shape or not full.is_contiguous()):
+        loss = mse_loss(outputs[:, 1:].contiguous(), target_poses[:, 1:].to(torch.float32).contiguous())
+        loss.backward()
+        return loss.detach()
+    d_full = torch.empty_like(full)
+    d_full[0].zero_()
+    with torch.no_grad():
+        loss, _ = ops.mse_fwd_bwd(full[1:], tgt[1:], want_grad=True, dy_out=d_full[1:])
+    full.backward(gradient=d_full)
+    return loss.view(())
+
+
 def train_iter_text2embedding(args, epoch: int, in_text, in_lengths, in_audio, target_poses, cluster_targets,
                               GPT3_Embedding, net: torch.nn.Module, optim):
-    """One training iteration of Part d (reference :462-538), discrete codes: CrossEntropyLoss over decode steps 1..S-1,
+    """One training iteration of Part d (reference :462-538): CrossEntropyLoss over decode steps 1..S-1 on `cluster_targets`
+    (text2_embedding_discrete == "True"), or MSE over the same steps on the latents `target_poses` (B,S,E) ("False", :499-510);
     clip_grad_norm_(5) + Adam (fused in `optim`, a gesture2vec_amd.flat.FlatClipAdam)."""
     from ..flat import FlatClipAdam
     from ..functional import cross_entropy
     if not isinstance(optim, FlatClipAdam):
         raise TypeError("use gesture2vec_amd.flat.FlatClipAdam (clip + Adam are one fused HIP launch)")
-    if args.text2_embedding_discrete != "True":
-        raise NotImplementedError("text2_embedding_discrete == 'False' is outside the accelerated hot path")
+    discrete = args.text2_embedding_discrete == "True"
+    targets = cluster_targets if discrete else target_poses
+    loss_backward = _code_loss_backward if discrete else _latent_loss_backward
     from .. import _lib, ops
     lib = _lib.load()
     defer = hasattr(net, "commit_bn_running_stats")
@@ -373,9 +396,9 @@ def train_iter_text2embedding(args, epoch: int, in_text, in_lengths, in_audio, t
         optim.zero_grad()
         if defer:
             net.deferred_bn = []           # BatchNorm's running statistics: held back until the whole iteration is known to be valid
-        outputs, _ = net(in_text, in_lengths, in_audio, cluster_targets, GPT3_Embedding, None)
+        outputs, _ = net(in_text, in_lengths, in_audio, targets, GPT3_Embedding, None)
         with ops.side_branches():          # the backward's parameter gradients beside its chain; joined in front of the optimiser
-            loss = _code_loss_backward(outputs, cluster_targets)
+            loss = loss_backward(outputs, targets)
         if defer:
             net.commit_bn_running_stats()  # behind the backward, latch-gated on the device like clip + Adam below
         optim.step()
@@ -427,6 +450,9 @@ class GraphedText2EmbeddingStep:
         from ..flat import FlatClipAdam
         if not isinstance(optim, FlatClipAdam):
             raise TypeError("use gesture2vec_amd.flat.FlatClipAdam")
+        if getattr(args, "text2_embedding_discrete", "True") != "True" or not getattr(net, "text2_embedding_discrete", True):
+            raise ValueError("GraphedText2EmbeddingStep captures the discrete iteration only: text2_embedding_discrete == 'False' "
+                             "(continuous latents) is not graphed -- use train_iter_text2embedding")
         from .. import _lib
         self._lib = _lib.load()
         self.in_text = in_text

@@ -913,6 +913,34 @@ int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc, const flo
                               size_t workspace_bytes, g2v_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Part d on continuous latents (text2_embedding_discrete: False; reference model/text2embedding_model.py:338-395, 701-744):
+ * the attention-free decoder that regresses each chunk's latent vector (width E = n_layers * hidden_size), csrc/t2e_latent.hip.
+ *   x_t   = target[t] while t < max(1, n_pre), else y_{t-1} -- the previous OUTPUT, with its gradient (:741)
+ *   u_t   = x_t W_pre^T + b_pre;  a_t = ReLU(BatchNorm1d(u_t))  (batch statistics: this is the training forward)
+ *   h0_{t+1}, h1_{t+1} = GRU(a_t; h0_t, h1_t)  (inter-layer dropout p on h0: keep_l0)
+ *   y_t   = h1_{t+1} W_out^T + b_out
+ * for t = 0 .. S1-1.  No embedding, no Dropout(0.5), no argmax.  The forward is S1 + 1 launches of one kernel (the tiling of
+ * g2v_attn_code_rollout_fwd).  The backward cannot be the discrete decoder's single launch: d loss / d y_t = d_out_t +
+ * du_{t+1} W_pre where step t+1 was fed back, and du_{t+1} comes out of BatchNorm's backward of step t+1, a sum over all batch
+ * rows -- so it is S1 + 1 launches of one kernel, descending, a kernel boundary per step as the only grid-wide seam (no kernel waits
+ * on another workgroup); every weight and bias gradient is one batched product over the S1 x B rows behind the loop.
+ * The structs of the code decoder are reused with K := E: w_pre (H,E), w_out (E,H), b_out (E); s->ec (S1,B,E) = the x rows,
+ * s->logits (S1,B,E) = y; emb, ids, d_emb, hp, attw and every attention member are NULL (w_attn != NULL is refused).
+ * g2v_latent_rollout_ok() is 0 with attention and for shapes not served (H % 4 == 0, H <= 256, E % 4 == 0, E <= 1024, the
+ * tiles within the CU's 160 KB of LDS): chain the operators from the host there.  target (S1+1,B,E) step-major (slots
+ * 0 .. max(1, n_pre) - 1 are read); h_init (2,B,H); d_out (S1,B,E) = d loss / d y as the loss alone gives it.
+ * ------------------------------------------------------------------------------------------ */
+int g2v_latent_rollout_ok(int S1, int B, int H, int E, int attention);
+size_t g2v_latent_rollout_fwd_workspace(int H, int E);
+int g2v_latent_rollout_fwd(const float* target, const float* h_init, const g2v_code_dec_weights* w, const g2v_code_dec_saved* s,
+                           const uint8_t* keep_l0, float p_drop, int n_pre, int S1, int B, int H, int E, void* workspace,
+                           size_t workspace_bytes, g2v_stream_t stream);
+size_t g2v_latent_rollout_bwd_workspace(int S1, int B, int H, int E);
+int g2v_latent_rollout_bwd(const float* d_out, const g2v_code_dec_weights* w, const g2v_code_dec_saved* s,
+                           const g2v_code_dec_grads* g, const uint8_t* keep_l0, float p_drop, int n_pre, int S1, int B, int H, int E,
+                           void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Calibration probes used by bench.py to report what the box sustains next to the datasheet peaks (no counterpart in the
  * reference): g2v_probe_mfma_f32 runs `blocks` x 4 waves x `iters` x 8 independent v_mfma_f32_16x16x4_f32 (2048 flop each)
  * without memory traffic (scratch: blocks * 256 floats); g2v_probe_copy streams n floats from src to dst.

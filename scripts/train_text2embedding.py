@@ -5,6 +5,8 @@
 
 Same surface: `init_model(args, lang_model, pose_dim, _device)` (lang_model needs `.n_words` and
 `.word_embedding_weights`), `train_epochs`, `evaluate_testset` (cross-entropy + code-usage perplexity), `main`;
+with `text2_embedding_discrete: "False"` (config/seq2seq_latent_synthetic.yml) the decoder regresses the sentence-level latents
+(width n_layers * hidden_size) with MSE instead (`evaluate_testset`: MSE over all slots, perplexity 0 from the empty meter);
 Adam(lr, betas=(0.5, 0.999)) (:179-181), evaluation every epoch (:195), checkpoint every 10 epochs with the keys
 `args, epoch, lang_model, pose_dim, gen_dict` (:202-221).  Without `--synthetic` the sentence-level cache is read
 (`cached_sentence_loaders`: code ids from the frozen VQ-VAE in one device launch per batch); `--synthetic` feeds batches of
@@ -45,6 +47,8 @@ def init_model(args, lang_model, pose_dim: int, _device):
     n_frames = args.n_poses
     if args.text2_embedding_discrete == "True":
         pose_dim = int(args.autoencoder_vq_components)
+    else:
+        pose_dim = args.n_layers * args.hidden_size       # the reference's rule (model/text2embedding_model.py:543-546)
     generator = text2embedding_model(args, pose_dim, n_frames, lang_model.n_words, args.wordembed_dim,
                                      lang_model.word_embedding_weights).to(_device)
     return generator, None
@@ -52,12 +56,14 @@ def init_model(args, lang_model, pose_dim: int, _device):
 
 class SyntheticSentences:
     """Batches shaped like word_seq_collate_fn's 8-tuple: (in_text, text_lengths, target_vec, in_audio, aux_info,
-    sentence_level_latents, cluster_ids, GPT3_embeddings); only ids / lengths / cluster ids carry information."""
+    sentence_level_latents, cluster_ids, GPT3_embeddings); only ids / lengths / cluster ids carry information -- with
+    text2_embedding_discrete == "False" the latents do instead: (B, S, n_layers * hidden_size), tanh of seeded normals."""
 
     def __init__(self, args, n_words: int, n_batches: int, seed: int, max_len: int = 20):
         self.B, self.n_words, self.n_batches, self.seed, self.max_len = args.batch_size, n_words, n_batches, seed, max_len
         self.S = args.sentence_frame_length // args.n_poses
         self.K = int(args.autoencoder_vq_components)
+        self.E = None if args.text2_embedding_discrete == "True" else args.n_layers * args.hidden_size
 
     def __len__(self):
         return self.n_batches
@@ -72,18 +78,28 @@ class SyntheticSentences:
                 ids[b, : lengths[b]] = torch.randint(4, self.n_words, (int(lengths[b]),), generator=g)
             codes = torch.randint(0, self.K, (self.B, self.S), generator=g)
             dummy = torch.zeros(self.B, 1)
-            yield ids, lengths, dummy, dummy, {}, dummy, codes, dummy
+            latents = dummy if self.E is None else torch.tanh(torch.randn(self.B, self.S, self.E, generator=g))
+            yield ids, lengths, dummy, dummy, {}, latents, codes, dummy
 
 
 def evaluate_testset(test_data_loader, generator, loss_fn, args):
-    """-> (mean cross-entropy over ALL S decode slots, mean code-usage perplexity), reference :300-421."""
+    """-> (mean cross-entropy over ALL S decode slots, mean code-usage perplexity), reference :300-421.  Continuous latents
+    (:360-369): (mean MSE over all S slots, 0 -- the perplexity meter stays empty).  The reference calls the model with five
+    arguments there and dies with a TypeError; the sixth (vid_indices = None) is passed here."""
     generator.train(False)
     losses, perplexities = AverageMeter("loss"), AverageMeter("perplexity")
     start = time.time()
+    discrete = args.text2_embedding_discrete == "True"
     with torch.no_grad():
         for data in test_data_loader:
             in_text, text_lengths, target_vec, in_audio, aux_info, latents, cluster_ids, gpt3 = data
             batch_size = target_vec.size(0)
+            if not discrete:
+                in_text, latents = in_text.to(device), latents.to(device).float()
+                out_latents, _ = generator(in_text, text_lengths, None, latents, None, None)
+                loss, _ = ops.mse_fwd_bwd(out_latents.contiguous(), latents.contiguous(), want_grad=False)
+                losses.update(float(loss[0]), batch_size)
+                continue
             in_text, cluster_ids = in_text.to(device), cluster_ids.to(device)
             out_latents, _ = generator(in_text, text_lengths, None, cluster_ids, None, None)
             K = out_latents.shape[2]
@@ -119,8 +135,12 @@ def train_epochs(args, train_data_loader, test_data_loader, lang_model, pose_dim
         for iter_idx, data in enumerate(train_data_loader, 0):
             in_text, text_lengths, target_vec, in_audio, aux_info, latents, cluster_ids, gpt3 = data
             batch_size = target_vec.size(0)
-            in_text, cluster_ids = in_text.to(device), cluster_ids.to(device)
-            loss = train_iter_text2embedding(args, epoch, in_text, text_lengths, None, None, cluster_ids, None, generator,
+            in_text = in_text.to(device)
+            if args.text2_embedding_discrete == "True":
+                cluster_ids, target_poses = cluster_ids.to(device), None
+            else:                                           # the latents are the targets (reference :499-510); the codes are not read
+                cluster_ids, target_poses = None, latents.to(device).float()
+            loss = train_iter_text2embedding(args, epoch, in_text, text_lengths, None, target_poses, cluster_ids, None, generator,
                                              gen_optimizer)
             loss_epoch.update(loss["loss"], batch_size)
             for m in loss_meters:
