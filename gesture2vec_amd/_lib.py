@@ -3,6 +3,7 @@ device pointers, sizes and a hipStream_t.  Loading FAILS LOUDLY when the library
 no CPU or PyTorch fallback anywhere in the product path."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -144,10 +145,14 @@ def check(rc: int, what: str = ""):
 
 
 class Context:
-    """A caller-owned set of the library's three implementation switches (include/g2v.h: g2v_ctx).  `with ctx:` binds it to the
-    calling thread for the duration of the block (re-entrant: the previous binding comes back); every library call inside reads
-    ITS switches.  An engine owns one, so that two engines in one process do not share switches and a residency fault in one
-    does not switch off the fast path of the other (round-5 verdict: "no hidden global state")."""
+    """The ONE route to the library's implementation switches (include/g2v.h: G2V_OPT_*, g2v_ctx).  A Context() owns a set of
+    them; `with ctx:` binds it to the calling thread for the duration of the block (re-entrant: the previous binding comes
+    back) and every library call inside reads ITS switches.  An engine owns one, so that two engines in one process do not share
+    switches and a residency fault in one does not switch off the fast path of the other.  Context.current() owns nothing: it
+    addresses whatever the calling thread has bound at the moment of each call (the process's default context if nothing).
+    scoped(name=value, ...) changes options for a block and puts back exactly what was there: no hand-written save / restore."""
+
+    OPTIONS = {k[len("G2V_OPT_"):].lower(): v for k, v in CONSTANTS.items() if k.startswith("G2V_OPT_")}
 
     def __init__(self):
         self._lib = load()
@@ -156,13 +161,41 @@ class Context:
             raise MemoryError("g2v_ctx_create failed")
         self._stack = []
 
+    @classmethod
+    def current(cls) -> "Context":
+        """a non-owning handle: the calling thread's bound context, else the default one (g2v_ctx_set_option(NULL, ...))"""
+        self = object.__new__(cls)
+        self._lib, self._h = load(), None
+        return self
+
     def set(self, option: int, value: int) -> int:
-        return int(self._lib.g2v_ctx_set_option(self._h, int(option), int(value)))
+        """-> the previous value"""
+        prev = int(self._lib.g2v_ctx_set_option(self._h, int(option), int(value)))
+        if prev < 0:
+            check(prev, f"(g2v_ctx_set_option {option})")
+        return prev
 
     def get(self, option: int) -> int:
-        return int(self._lib.g2v_ctx_get_option(self._h, int(option)))
+        value = int(self._lib.g2v_ctx_get_option(self._h, int(option)))
+        if value < 0:
+            check(value, f"(g2v_ctx_get_option {option})")
+        return value
+
+    @contextlib.contextmanager
+    def scoped(self, **options):
+        """ctx.scoped(persistent=0, gru_cluster=0): set each option in order; on the way out -- also behind an exception --
+        restore, in reverse order, the values the sets returned."""
+        unknown = [k for k in options if k not in self.OPTIONS]
+        if unknown:
+            raise TypeError(f"scoped(): unknown option(s) {unknown}; the header has {sorted(self.OPTIONS)}")
+        with contextlib.ExitStack() as undo:
+            for name, value in options.items():
+                undo.callback(self.set, self.OPTIONS[name], self.set(self.OPTIONS[name], value))
+            yield self
 
     def __enter__(self):
+        if self._h is None:
+            raise G2VLibraryError("Context.current() is a handle on whatever is bound: it cannot be bound itself")
         self._stack.append(self._lib.g2v_ctx_bind(self._h))
         return self
 

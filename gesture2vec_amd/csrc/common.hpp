@@ -13,7 +13,7 @@
 // (which reads the latch at its next sync point) can simply repeat the step on the per-step kernels.
 const unsigned* g2v_internal_persist_fault_ptr();
 
-// The three implementation switches (include/g2v.h: g2v_ctx) of the context bound to the CALLING THREAD, or of the process's
+// The implementation switches (include/g2v.h: g2v_ctx) of the context bound to the CALLING THREAD, or of the process's
 // default context when the thread has bound none (misc.hip owns both).  Everything that used to read a file-scope `static int`
 // reads these.
 struct G2vOptions {
@@ -25,7 +25,38 @@ struct G2vOptions {
 };
 G2vOptions& g2v_internal_options();
 
+// Host functions that one .hip file defines and another calls: declared here, once.
+// misc.hip -- the "already clear" notes of the calling thread's context: make one, take the one at p, forget those inside a range
+void g2v_internal_preclear_note(const void* p, size_t n);
+int g2v_internal_preclear_take(const void* p, size_t need);
+void g2v_internal_preclear_drop(const void* base, size_t bytes);
+// dec_rollout.hip -- G2V_OPT_PERSISTENT != 0 (t2e_rollout.hip: the code decoder's cluster kernel)
+int g2v_internal_persist_enabled();
+// gru.hip -- the exchange region a cluster launch of this shape clears (offset 0 of its workspace); 0: not a cluster shape
+size_t g2v_internal_gru_cluster_region(int T, int B, int H, int ndir, int bwd);
+// linear.hip
+int g2v_internal_slab_reduce4(const float* const* slab_w, float* const* out_w, const float* const* slab_b, float* const* out_b,
+                              int nprob, int64_t n, int64_t nb, int nsplit, hipStream_t st);
+int g2v_internal_cell_bwd_products(const float* dgh, const float* w_hh, float* d_hprev, int H, const float* dgi,
+                                   const float* w_ih, float* dx, int in_dim, const uint8_t* x_keep, float x_scale, int B,
+                                   hipStream_t st);
+// dec_persist.hip
+int dec_persist_fwd_launch(const float* target, const float* h_init, const g2v_dec_weights* w, const g2v_dec_saved* s,
+                           const uint8_t* keep95, const uint8_t* keep_l0, float p_drop, int n_pre, int conditioned,
+                           int training, int T, int B, const float* p_pre, const float* p_ih0, const float* p_hh0,
+                           const float* p_ih1, const float* p_hh1, const float* p_out, void* xbase, hipStream_t st,
+                           bool clear, int tiles_per_wg);
+int dec_persist_bwd_launch(const g2v_dec_weights* w, const g2v_dec_saved* s, const g2v_dec_grads* g, const uint8_t* keep95,
+                           const uint8_t* keep_l0, float p_drop, int n_pre, int conditioned, int T, int B,
+                           const float* p_pre_t, const float* p_out_t, const float* p_ih0_t, const float* p_hh0_t,
+                           const float* p_ih1_t, const float* p_hh1_t, void* xbase, hipStream_t st, bool clear, float* wslab,
+                           int tiles_per_wg);
+int dec_persist_loss_chase_launch(const float* target, const g2v_dec_saved* s, const uint8_t* keep95, int T, int B, void* xbase,
+                                  hipStream_t st);
+
 namespace g2v {
+
+size_t dec_persist_bwd_wgrad_slab_floats();      // dec_persist.hip (per workgroup of the fused-weight-gradient persistent backward)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

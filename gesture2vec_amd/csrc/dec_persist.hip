@@ -1274,9 +1274,6 @@ int dec_persist_loss_chase_launch(const float* target, const g2v_dec_saved* s, c
 // Produces exactly the arrays the per-step kernels produce (du, dy total, dgi/dgh of both cells, d_bn_w/b, dh_init);
 // the dbn scratch array is not needed (the values stay in registers).
 // =====================================================================================================================
-int g2v_internal_slab_reduce4(const float* const* slab_w, float* const* out_w, const float* const* slab_b, float* const* out_b,
-                              int nprob, int64_t n, int64_t nb, int nsplit, hipStream_t st);      // linear.hip
-
 namespace g2v {
 namespace {
 constexpr int LDG = 4 * H + 4;                             // gate-gradient tile row stride

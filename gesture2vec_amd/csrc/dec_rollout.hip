@@ -22,23 +22,6 @@
 #include "dec_persist.hpp"
 #include "gru_cells.hpp"
 
-// dec_persist.hip
-int dec_persist_fwd_launch(const float* target, const float* h_init, const g2v_dec_weights* w, const g2v_dec_saved* s,
-                           const uint8_t* keep95, const uint8_t* keep_l0, float p_drop, int n_pre, int conditioned,
-                           int training, int T, int B, const float* p_pre, const float* p_ih0, const float* p_hh0,
-                           const float* p_ih1, const float* p_hh1, const float* p_out, void* xbase, hipStream_t st,
-                           bool clear, int tiles_per_wg);
-int dec_persist_bwd_launch(const g2v_dec_weights* w, const g2v_dec_saved* s, const g2v_dec_grads* g, const uint8_t* keep95,
-                           const uint8_t* keep_l0, float p_drop, int n_pre, int conditioned, int T, int B,
-                           const float* p_pre_t, const float* p_out_t, const float* p_ih0_t, const float* p_hh0_t,
-                           const float* p_ih1_t, const float* p_hh1_t, void* xbase, hipStream_t st, bool clear, float* wslab,
-                           int tiles_per_wg);
-int dec_persist_loss_chase_launch(const float* target, const g2v_dec_saved* s, const uint8_t* keep95, int T, int B, void* xbase,
-                                  hipStream_t st);
-namespace g2v {
-size_t dec_persist_bwd_wgrad_slab_floats();
-}
-
 namespace g2v {
 
 // The persistent path needs every workgroup of its launch resident at once: one per CU.
@@ -1000,9 +983,6 @@ extern "C" int g2v_read_spans(unsigned long long* out) {
 int g2v_internal_persist_enabled() { return g2v_internal_options().persist != 0 ? 1 : 0; }      // (t2e_rollout.hip: the code decoder's cluster kernel)
 extern "C" int g2v_dec_rollout_blocks(int B) { return B > 0 ? cdiv(B, 16) : 0; }
 
-int g2v_internal_preclear_take(const void* p, size_t need);      // dec_persist.hip
-void g2v_internal_preclear_note(const void* p, size_t n);
-void g2v_internal_preclear_drop(const void* base, size_t bytes);
 extern "C" int g2v_dec_rollout_set_persistent(int enable) {      // = g2v_ctx_set_option(NULL, G2V_OPT_PERSISTENT, enable)
   return g2v_ctx_set_option(nullptr, G2V_OPT_PERSISTENT, enable);
 }
@@ -2688,7 +2668,6 @@ extern "C" int g2v_dec_rollout_cluster_ok(int B, int D, int H) {
   const int nblk = cdiv(B, 16);
   return (nblk <= DSPLIT_MAX_NBLK && (int64_t)nblk * ((H + 15) >> 4) <= device_cu_count()) ? 1 : 0;
 }
-size_t g2v_internal_gru_cluster_region(int T, int B, int H, int ndir, int bwd);      // gru.hip
 // Clear the exchange records of the NEXT persistent cluster launch of this kind over `workspace` now, on `stream`, and note it: that
 // launch then starts with its kernel instead of a memset node (see g2v.h).  kind: 0 / 1 g2v_gru_seq_fwd / _bwd (T, B, H, ndir),
 // 2 / 3 g2v_dec_rollout_fwd / _bwd (B, D, H).  Shapes that do not run as a cluster: nothing happens.

@@ -2159,7 +2159,6 @@ static size_t gru_split_state_floats(int ndir, int H) { return (size_t)ndir * 2 
 // The cluster kernels (gru_cluster_*_kernel): the split path's shapes while the whole grid is resident at once -- at most one
 // 192-thread workgroup per CU (the workgroups of a row group wait for each other).  g2v_gru_seq_set_cluster(0) keeps the
 // per-step launches (parity tests, A/B).
-void g2v_internal_preclear_drop(const void* base, size_t bytes);
 extern "C" int g2v_gru_seq_set_cluster(int enable) {             // = g2v_ctx_set_option(NULL, G2V_OPT_GRU_CLUSTER, enable)
   return g2v_ctx_set_option(nullptr, G2V_OPT_GRU_CLUSTER, enable);
 }
@@ -2187,8 +2186,6 @@ static size_t gru_cluster_max_xch_bytes(int H, bool bwd) {
   const size_t Hp = (size_t)((H + 15) & ~15), nt = Hp / 16, cus = (size_t)gru_device_cus();
   return (bwd ? cus : cus / nt + 1) * 2 * 16 * Hp * 8 + cus * sizeof(unsigned) + 16;
 }
-int g2v_internal_preclear_take(const void* p, size_t need);      // dec_persist.hip
-void g2v_internal_preclear_drop(const void* base, size_t bytes);
 static bool gru_cluster_ok(int T, int B, int ndir, int H, const void* fn);
 // 1: g2v_gru_seq_fwd / _bwd run this shape as the persistent cluster kernels (small batch; see g2v_gru_seq_set_cluster)
 extern "C" int g2v_gru_seq_cluster_ok(int T, int B, int H, int ndir) {
@@ -2214,15 +2211,9 @@ extern "C" size_t g2v_gru_seq_fwd_workspace(int ndir, int H) {
   return ab > c ? ab : c;
 }
 
-int g2v_internal_slab_reduce4(const float* const* slab_w, float* const* out_w, const float* const* slab_b, float* const* out_b,
-                              int nprob, int64_t n, int64_t nb, int nsplit, hipStream_t st);      // linear.hip
 extern "C" size_t g2v_gru_seq_bwd_wslab_bytes(int B, int H) {
   return (B > 0 && H > 0) ? (size_t)cdiv(B, 16) * 2 * ((size_t)3 * H * H + 3 * H) * sizeof(float) : 0;
 }
-int g2v_internal_cell_bwd_products(const float* dgh, const float* w_hh, float* d_hprev, int H, const float* dgi,
-                                   const float* w_ih, float* dx, int in_dim, const uint8_t* x_keep, float x_scale, int B,
-                                   hipStream_t st);      // linear.hip
-
 static bool cell_shape_ok(int in_dim, int H) { return (in_dim & 3) == 0 && (H & 3) == 0 && in_dim <= 16 * GRU_STEP_KS && H <= 16 * GRU_STEP_KS; }
 
 extern "C" int g2v_gru_cell_fwd(const float* x, int in_dim, const uint8_t* x_keep, float x_scale, const float* h_prev,

@@ -2,6 +2,7 @@
 #include <stdarg.h>
 
 #include "common.hpp"
+#include <algorithm>
 #include <new>
 
 namespace g2v {
@@ -33,17 +34,19 @@ struct g2v_ctx {
 };
 static g2v_ctx g_default_ctx;
 static thread_local g2v_ctx* t_bound_ctx = nullptr;
-G2vOptions& g2v_internal_options() { return (t_bound_ctx ? t_bound_ctx : &g_default_ctx)->opt; }
-static g2v_ctx& cur_ctx() { return *(t_bound_ctx ? t_bound_ctx : &g_default_ctx); }
+static g2v_ctx& ctx_or_cur(const g2v_ctx* ctx = nullptr) {      // `ctx`, else the calling thread's bound context, else the default
+  return *(ctx ? const_cast<g2v_ctx*>(ctx) : (t_bound_ctx ? t_bound_ctx : &g_default_ctx));
+}
+G2vOptions& g2v_internal_options() { return ctx_or_cur().opt; }
 void g2v_internal_preclear_note(const void* p, size_t n) {
-  g2v_ctx& c = cur_ctx();
+  g2v_ctx& c = ctx_or_cur();
   for (auto& e : c.preclear)
     if (e.p == p) { e.n = n; return; }
   c.preclear[c.preclear_next] = PreclearNote{p, n};
   c.preclear_next = (c.preclear_next + 1) % 16;
 }
 int g2v_internal_preclear_take(const void* p, size_t need) {
-  for (auto& e : cur_ctx().preclear)
+  for (auto& e : ctx_or_cur().preclear)
     if (e.p == p && e.p != nullptr) {
       const bool ok = e.n >= need;
       e = PreclearNote{nullptr, 0};
@@ -51,12 +54,13 @@ int g2v_internal_preclear_take(const void* p, size_t need) {
     }
   return 0;
 }
-// forget every note inside [base, base + bytes) (a launch over that workspace that does not consume one), or all of them
-void g2v_internal_preclear_drop(const void* base, size_t bytes) {
-  for (auto& e : cur_ctx().preclear)
+// forget every note of `c` inside [base, base + bytes) (a launch over that workspace that does not consume one), or all of them
+static void g2v_internal_preclear_drop(g2v_ctx& c, const void* base, size_t bytes) {
+  for (auto& e : c.preclear)
     if (e.p != nullptr && (base == nullptr || ((const char*)e.p >= (const char*)base && (const char*)e.p < (const char*)base + bytes)))
       e = PreclearNote{nullptr, 0};
 }
+void g2v_internal_preclear_drop(const void* base, size_t bytes) { g2v_internal_preclear_drop(ctx_or_cur(), base, bytes); }
 extern "C" int g2v_cluster_exchange_preclear_drop(const void* workspace, size_t workspace_bytes) {
   g2v_internal_preclear_drop(workspace, workspace_bytes);
   return G2V_OK;
@@ -73,18 +77,19 @@ extern "C" g2v_ctx* g2v_ctx_bind(g2v_ctx* ctx) {
   return prev;
 }
 extern "C" int g2v_ctx_set_option(g2v_ctx* ctx, int option, int value) {
-  G2vOptions& o = (ctx ? ctx : (t_bound_ctx ? t_bound_ctx : &g_default_ctx))->opt;
+  g2v_ctx& c = ctx_or_cur(ctx);
+  G2vOptions& o = c.opt;
   int prev = -1;
   switch (option) {
     case G2V_OPT_PERSISTENT:
       prev = o.persist;
       o.persist = value <= 0 ? 0 : (value > 3 ? 3 : value);
-      g2v_internal_preclear_drop(nullptr, 0);      // (a kernel-family switch voids every "already clear" note)
+      g2v_internal_preclear_drop(c, nullptr, 0);      // (a kernel-family switch voids every "already clear" note of THAT context)
       break;
     case G2V_OPT_GRU_CLUSTER:
       prev = o.gru_cluster;
       o.gru_cluster = value ? 1 : 0;
-      g2v_internal_preclear_drop(nullptr, 0);
+      g2v_internal_preclear_drop(c, nullptr, 0);
       break;
     case G2V_OPT_SMALLM_ROWS:
       prev = o.smallm_max_rows;
@@ -98,20 +103,22 @@ extern "C" int g2v_ctx_set_option(g2v_ctx* ctx, int option, int value) {
       prev = o.gru_resident_bwd;
       o.gru_resident_bwd = value ? 1 : 0;
       break;
-    default:
-      g2v::set_error("g2v_ctx_set_option: unknown option %d", option);
+    default:      // (G2V_OPT_PRECLEAR_NOTES is read-only)
+      g2v::set_error("g2v_ctx_set_option: unknown or read-only option %d", option);
       return G2V_ERR_ARG;
   }
   return prev;
 }
 extern "C" int g2v_ctx_get_option(const g2v_ctx* ctx, int option) {
-  const G2vOptions& o = (ctx ? ctx : (t_bound_ctx ? t_bound_ctx : &g_default_ctx))->opt;
+  const g2v_ctx& c = ctx_or_cur(ctx);
+  const G2vOptions& o = c.opt;
   switch (option) {
     case G2V_OPT_PERSISTENT: return o.persist;
     case G2V_OPT_GRU_CLUSTER: return o.gru_cluster;
     case G2V_OPT_SMALLM_ROWS: return o.smallm_max_rows;
     case G2V_OPT_GRU_RESIDENT_ROWS: return o.gru_resident_rows;
     case G2V_OPT_GRU_RESIDENT_BWD: return o.gru_resident_bwd;
+    case G2V_OPT_PRECLEAR_NOTES: return (int)std::count_if(c.preclear, c.preclear + 16, [](const PreclearNote& e) { return e.p != nullptr; });
     default: g2v::set_error("g2v_ctx_get_option: unknown option %d", option); return G2V_ERR_ARG;
   }
 }

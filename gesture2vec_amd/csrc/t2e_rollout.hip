@@ -1326,7 +1326,6 @@ static int ct_device_cus() {
   }
   return n;
 }
-int g2v_internal_persist_enabled();      // dec_rollout.hip: g2v_dec_rollout_set_persistent != 0
 // 1: g2v_attn_code_rollout_fwd runs this shape as ONE persistent cluster launch (no attention, H <= 208, at most three K tiles per
 // hidden-unit tile, the (tile x row group) grid with a CU per workgroup) under the current g2v_dec_rollout_set_persistent setting
 extern "C" int g2v_attn_code_rollout_cluster_ok(int S1, int B, int H, int K, int attention) {

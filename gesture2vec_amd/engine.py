@@ -368,8 +368,7 @@ class VQVAEEngine:
 
     def rearm(self):
         """the fast path was switched back on (self.fault_policy.tick() returned True): forget what was planned and captured
-        for the per-step kernels"""
-        self.lib.g2v_cluster_exchange_preclear_drop(None, 0)
+        for the per-step kernels (the re-arming set has voided this context's "already clear" notes)"""
         self._iter_graph = None
         self._open.clear()
         self._deferred.clear()

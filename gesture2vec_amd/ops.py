@@ -557,13 +557,9 @@ def gru_dirs_bwd(dirs, T, B, H, *, lengths=None, d_hs_ld=None, hs_ld=None, row_o
         arr[k].in_dim = int(d.get("in_dim", 0))
     dev = dirs[0]["hs"].device
     ws = workspace(lib.g2v_gru_seq_bwd_workspace(len(dirs), H), dev, "grubwd")
-    prev = lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_BWD, 0) if not allow_resident else None
-    try:
+    with contextlib.nullcontext() if allow_resident else _lib.Context.current().scoped(gru_resident_bwd=0):
         check(lib.g2v_gru_seq_bwd(arr, len(dirs), _p(lengths), d_hs_ld if d_hs_ld is not None else H,
                                   hs_ld if hs_ld is not None else H, T, B, H, _p(ws), ws.numel(), _stream()), "gru_seq_bwd")
-    finally:
-        if prev is not None:
-            lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_BWD, prev)
 
 
 def gru_seq_fwd(gi, w_hh, b_hh, T, B, H, *, h0=None, lengths=None, reverse=False, hs=None, hs_ld=None,

@@ -377,6 +377,35 @@ def _latent_loss_backward(outputs, target_poses):
     return loss.view(())
 
 
+def _text2embedding_step(net, optim, in_text, in_lengths, in_audio, targets, GPT3_Embedding, loss_backward):
+    """One Part d iteration (train_iter_text2embedding runs it, GraphedText2EmbeddingStep captures it) -> (loss, outputs).
+    BatchNorm's running statistics are held back until the iteration is known to be valid (committed behind the backward, latch-
+    gated like clip + Adam); whatever is raised, net.deferred_bn is reset: a list left there would silently freeze them."""
+    from .. import ops
+    defer = hasattr(net, "commit_bn_running_stats")
+    optim.zero_grad()
+    try:
+        if defer:
+            net.deferred_bn = []
+        outputs, _ = net(in_text, in_lengths, in_audio, targets, GPT3_Embedding, None)
+        with ops.side_branches():          # the backward's parameter gradients beside its chain; joined in front of the optimiser
+            loss = loss_backward(outputs, targets)
+        if defer:
+            net.commit_bn_running_stats()
+    finally:
+        if defer:
+            net.deferred_bn = None
+    optim.step()
+    return loss, outputs
+
+
+def _uncount_decode_steps(net, n: int) -> None:
+    """unapplied iterations counted n decode steps in the decoder BatchNorm's num_batches_tracked: take them back"""
+    bn = getattr(getattr(getattr(net, "decoder", None), "decoder", None), "pre_linear", None)
+    if bn is not None and hasattr(bn[1], "num_batches_tracked"):
+        bn[1].num_batches_tracked -= n
+
+
 def train_iter_text2embedding(args, epoch: int, in_text, in_lengths, in_audio, target_poses, cluster_targets,
                               GPT3_Embedding, net: torch.nn.Module, optim):
     """One training iteration of Part d (reference :462-538): CrossEntropyLoss over decode steps 1..S-1 on `cluster_targets`
@@ -389,22 +418,13 @@ def train_iter_text2embedding(args, epoch: int, in_text, in_lengths, in_audio, t
     discrete = args.text2_embedding_discrete == "True"
     targets = cluster_targets if discrete else target_poses
     loss_backward = _code_loss_backward if discrete else _latent_loss_backward
-    from .. import _lib, ops
+    from .. import _lib
     lib = _lib.load()
-    defer = hasattr(net, "commit_bn_running_stats")
     for attempt in (0, 1):
-        optim.zero_grad()
-        if defer:
-            net.deferred_bn = []           # BatchNorm's running statistics: held back until the whole iteration is known to be valid
-        outputs, _ = net(in_text, in_lengths, in_audio, targets, GPT3_Embedding, None)
-        with ops.side_branches():          # the backward's parameter gradients beside its chain; joined in front of the optimiser
-            loss = loss_backward(outputs, targets)
-        if defer:
-            net.commit_bn_running_stats()  # behind the backward, latch-gated on the device like clip + Adam below
-        optim.step()
+        loss, outputs = _text2embedding_step(net, optim, in_text, in_lengths, in_audio, targets, GPT3_Embedding, loss_backward)
         ret = {"loss": loss.item()}
         # The encoder's small-batch GRU kernels keep their workgroups resident for the whole sequence (include/g2v.h:
-        # g2v_gru_seq_set_cluster) and latch the persistent kernels' fault word when a bounded wait runs out (a workgroup of the
+        # G2V_OPT_GRU_CLUSTER) and latch the persistent kernels' fault word when a bounded wait runs out (a workgroup of the
         # launch was not resident: CU mask, another tenant).  A faulted iteration changed nothing -- clip + Adam and the commit of
         # BatchNorm's running statistics sit BEHIND the backward and read the latch on the device (round 6: the statistics used
         # to be committed inside the forward rollout, before a fault of a later step or of the backward could be known) -- so it
@@ -420,9 +440,7 @@ def train_iter_text2embedding(args, epoch: int, in_text, in_lengths, in_audio, t
         import warnings
         warnings.warn(f"persistent GRU kernels: fault latch {f} (a workgroup of the launch was not resident); the iteration was not "
                       "applied and is repeated on the per-step kernels, which stay selected until re-armed", RuntimeWarning)
-        bn = getattr(getattr(getattr(net, "decoder", None), "decoder", None), "pre_linear", None)
-        if bn is not None and hasattr(bn[1], "num_batches_tracked"):
-            bn[1].num_batches_tracked -= outputs.shape[1] - 1      # (the repeated iteration counts its decode steps again)
+        _uncount_decode_steps(net, outputs.shape[1] - 1)      # (the repeated iteration counts its decode steps again)
     return ret
 
 
@@ -476,19 +494,7 @@ class GraphedText2EmbeddingStep:
             self._baked = None
 
     def _step(self):
-        from .. import ops
-        net, optim = self.net, self.optim
-        defer = hasattr(net, "commit_bn_running_stats")
-        optim.zero_grad()
-        if defer:
-            net.deferred_bn = []
-        outputs, _ = net(self.in_text, self.lengths, None, self.codes, None, None)
-        with ops.side_branches():
-            loss = _code_loss_backward(outputs, self.codes)
-        if defer:
-            net.commit_bn_running_stats()
-        optim.step()
-        return loss
+        return _text2embedding_step(self.net, self.optim, self.in_text, self.lengths, None, self.codes, None, _code_loss_backward)[0]
 
     def _capture(self, warmup: int):
         from ..fault_policy import POLICY
@@ -540,9 +546,7 @@ class GraphedText2EmbeddingStep:
         self.lost_replays += n
         warnings.warn(f"GraphedText2EmbeddingStep: persistent kernel fault latch {f}; the last {n} replay(s) were not applied -- "
                       "re-capturing on the per-step kernels and repeating one step", RuntimeWarning)
-        bn = getattr(getattr(getattr(self.net, "decoder", None), "decoder", None), "pre_linear", None)
-        if bn is not None and hasattr(bn[1], "num_batches_tracked"):
-            bn[1].num_batches_tracked -= n * (self.codes.shape[1] - 1)     # (the unapplied replays counted their decode steps)
+        _uncount_decode_steps(self.net, n * (self.codes.shape[1] - 1))     # (the unapplied replays counted their decode steps)
         self._capture(1)            # (its eager warm-up step IS the repeated step)
         self.recaptures += 1
         if int(self._lib.g2v_dec_rollout_persist_fault(0)) != 0:

@@ -54,14 +54,14 @@ int g2v_device_ok(void);
  * else at x + m * ldx.  x_keep (uint8, may be NULL) is indexed [m * K + k].
  * act: 0 = identity, 1 = ReLU, 2 = tanh.
  * ------------------------------------------------------------------------------------------ */
-/* measurement only: largest row count served by the wave-per-tile kernel of g2v_linear_fwd / g2v_linear_bwd_data
- * (0 = never); returns the previous value, rows < 0 only queries */
+/* LEGACY FORWARD = g2v_ctx_set_option(NULL, G2V_OPT_SMALLM_ROWS, rows) (measurement only): largest row count served by the
+ * wave-per-tile kernel of g2v_linear_fwd / g2v_linear_bwd_data (0 = never); returns the previous value, rows < 0 only queries */
 int g2v_linear_set_smallm_rows(int rows);
 /* IMPLEMENTATION SWITCHES, complete list (everything else is per call).  The library reads NO environment variable.  All of
  * them select between implementations that produce the same results (measurements, parity tests, and the fall-back after a latched
  * residency fault of the persistent kernels):
  *   G2V_OPT_SMALLM_ROWS   row count up to which the wave-per-tile dense kernels are used (default 1024)
- *   G2V_OPT_PERSISTENT    0..3: persistent rollout kernels vs one launch per step (default 1; see g2v_dec_rollout_set_persistent)
+ *   G2V_OPT_PERSISTENT    0..3: persistent rollout kernels vs one launch per step (default 1; levels: see g2v_dec_rollout_set_persistent)
  *   G2V_OPT_GRU_CLUSTER   0 / 1: small-batch g2v_gru_seq_fwd / _bwd as one persistent launch vs one launch per step
  *   G2V_OPT_GRU_RESIDENT_ROWS   batch rows from which g2v_gru_seq_fwd (192 < H <= 208) and g2v_gru_seq_bwd (H = 200) keep W_hh
  *                         resident in each CU's registers + LDS for the whole sequence instead of streaming it from L2 every step
@@ -70,7 +70,8 @@ int g2v_linear_set_smallm_rows(int rows);
  *   G2V_OPT_GRU_RESIDENT_BWD    0 / 1 (default 1): the BPTT too.  A resident launch takes a CU's whole LDS and register file, so
  *                         nothing co-resides with it: a caller that runs other launches BESIDE the BPTT (the VQ-VAE engine: the
  *                         decoder's weight gradients on other queues) turns it off in its context
- * They live in a CALLER-OWNED CONTEXT (round 6; until round 5 they were three process-global variables, so two engines in one
+ *   G2V_OPT_PRECLEAR_NOTES      READ-ONLY (set: G2V_ERR_ARG): the live "already clear" notes of g2v_cluster_exchange_preclear in the context
+ * They live in a CALLER-OWNED CONTEXT (round 6; until round 5 they were process-global variables, so two engines in one
  * process shared them and a fault in one switched off the fast path of the other):
  *   g2v_ctx_create()              a context with the defaults above (host memory; NULL on allocation failure)
  *   g2v_ctx_destroy(ctx)          (unbinds it from the calling thread if bound there; never destroy a context bound elsewhere)
@@ -79,8 +80,9 @@ int g2v_linear_set_smallm_rows(int rows);
  *                                 context at call time -- launches already captured in a hipGraph keep what they were captured with.
  *   g2v_ctx_set_option(ctx, option, value) / g2v_ctx_get_option(ctx, option)
  *                                 ctx = NULL: the calling thread's bound context (the default context if none).  set returns the
- *                                 previous value; both return G2V_ERR_ARG (< 0) for an unknown option.
- * g2v_linear_set_smallm_rows, g2v_dec_rollout_set_persistent and g2v_gru_seq_set_cluster are the same calls with ctx = NULL.
+ *                                 previous value; both return G2V_ERR_ARG (< 0) for an unknown option.  Setting
+ *                                 G2V_OPT_PERSISTENT or G2V_OPT_GRU_CLUSTER voids the "already clear" notes of THAT context.
+ * g2v_linear_set_smallm_rows, g2v_dec_rollout_set_persistent and g2v_gru_seq_set_cluster are LEGACY FORWARDS (ctx = NULL).
  * A thread that never binds a context behaves as before (one set of switches per process, in the default context).
  * What stays process-wide: one device-side error latch, g2v_dec_rollout_persist_fault (below) -- a fault of the DEVICE, not an
  * option.  (The "already clear" notes of g2v_cluster_exchange_preclear belong to the bound context too.) */
@@ -90,6 +92,7 @@ typedef struct g2v_ctx g2v_ctx;
 #define G2V_OPT_SMALLM_ROWS 3
 #define G2V_OPT_GRU_RESIDENT_ROWS 4
 #define G2V_OPT_GRU_RESIDENT_BWD 5
+#define G2V_OPT_PRECLEAR_NOTES 6
 g2v_ctx* g2v_ctx_create(void);
 void g2v_ctx_destroy(g2v_ctx* ctx);
 g2v_ctx* g2v_ctx_bind(g2v_ctx* ctx);
@@ -374,7 +377,8 @@ int g2v_gru_seq_gather_ok(int T, int B, int H, int ndir);
  * granules in the call's workspace (csrc/gru.hip: gru_cluster_*_kernel).  Forward results are bitwise those of the per-step
  * launches, backward results equal to summation order.  Like the persistent rollouts these kernels need their workgroups
  * co-resident; a bounded wait that runs out latches g2v_dec_rollout_persist_fault.  This switch (default 1; 0 = one launch per
- * step) exists for parity tests, A/B measurements and the fall-back after a latched fault.  Returns the previous setting. */
+ * step) exists for parity tests, A/B measurements and the fall-back after a latched fault.  Returns the previous setting.
+ * LEGACY FORWARD = g2v_ctx_set_option(NULL, G2V_OPT_GRU_CLUSTER, enable). */
 int g2v_gru_seq_set_cluster(int enable);
 /* 1: this shape runs as the cluster kernels under the current setting (then g2v_gru_dir_bwd.hn_z .. hn_coef, the fused quantiser
  * backward below, are honoured at H != 64 too) */
@@ -534,7 +538,8 @@ int g2v_dec_rollout_blocks(int B);
  * whole backward are ONE launch each with those workgroups resident: weight rows in registers, the rows a kernel boundary used to
  * hand over (u / h0 / h1 and the BatchNorm sums forward; dbn rows, BatchNorm-backward sums and the partial products of the
  * 3H-long contractions backward) exchanged through tagged 8-byte granules in the call's workspace (csrc/dec_rollout.hip:
- * dec_cluster_fwd_kernel / dec_cluster_bwd_kernel).  Same saved arrays, results equal to summation order, bitwise reproducible. */
+ * dec_cluster_fwd_kernel / dec_cluster_bwd_kernel).  Same saved arrays, results equal to summation order, bitwise reproducible.
+ * LEGACY FORWARD = g2v_ctx_set_option(NULL, G2V_OPT_PERSISTENT, enable). */
 int g2v_dec_rollout_set_persistent(int enable);
 /* which of the two g2v_dec_rollout_fwd / _bwd take for this shape under the current setting: 0 = one launch per time step,
  * R = 1..3 = the persistent pair with R row tiles per workgroup (B % 4 == 0; a ragged last tile where B % 16 != 0) */

@@ -79,7 +79,7 @@ def test_structs_and_constants_keep_their_names():
     for cname, cls in _lib.STRUCTS.items():
         assert getattr(_lib, cls.__name__) is cls and cls.__doc__ == cname and issubclass(cls, C.Structure)
     assert (_lib.OPT_PERSISTENT, _lib.OPT_GRU_CLUSTER, _lib.OPT_SMALLM_ROWS, _lib.OPT_GRU_RESIDENT_ROWS,
-            _lib.OPT_GRU_RESIDENT_BWD) == (1, 2, 3, 4, 5)
+            _lib.OPT_GRU_RESIDENT_BWD, _lib.OPT_PRECLEAR_NOTES) == (1, 2, 3, 4, 5, 6)
     assert (_lib.OK, _lib.ERR_ARG, _lib.ERR_LAUNCH, _lib.ERR_WORKSPACE, _lib.ERR_UNSUPPORTED) == (0, -1, -2, -3, -4)
     assert (_lib.WGRAD_ACCUMULATE, _lib.WGRAD_BF16X3, _lib.WGRAD_PENDING_MAX, _lib.VQ_BX_EXACT) == (1, 2, 8, 1)
     assert "HOST" not in _lib.CONSTANTS and "G2V_HOST" not in _lib.CONSTANTS      # a marker, not a value

@@ -170,7 +170,7 @@ def test_latched_fault_reaches_train_iter_and_the_step_is_not_applied(B):
         loss2, _ = train_iter_Autoencoder_VQ_seq2seq(args, 1, x, x, net, optim)
         assert lib.g2v_dec_rollout_persist_fault(0) == 0    # check_faults() cleared the latch ...
         assert eng.ctx.get(_lib.OPT_PERSISTENT) == 0        # ... and switched the persistent path off IN THE ENGINE'S OWN CONTEXT
-        assert lib.g2v_ctx_get_option(None, _lib.OPT_PERSISTENT) == 1     # (the process's default context is untouched: round 6)
+        assert _lib.Context.current().get(_lib.OPT_PERSISTENT) == 1     # (the process's default context is untouched: round 6)
         assert abs(loss2["loss"] - loss["loss"]) <= 0.05 * abs(loss["loss"]) and not torch.equal(snap[0], eng.flat)
         assert int(eng.step_counter) == int(snap[6]) + 1, "exactly one step was applied"
         assert int(net.decoder.decoder.pre_linear[1].num_batches_tracked) == nbt + (T - 1)
@@ -178,14 +178,12 @@ def test_latched_fault_reaches_train_iter_and_the_step_is_not_applied(B):
         assert abs(loss3["loss"] - loss["loss"]) <= 0.05 * abs(loss["loss"])
     finally:
         lib.g2v_dec_rollout_persist_fault(1)
-        lib.g2v_dec_rollout_set_persistent(1)
-        lib.g2v_gru_seq_set_cluster(1)
 
 
 def test_latched_fault_on_the_cluster_kernels_of_the_shipped_shape_is_repeated_on_the_per_step_launches():
     """config/VQ-VAE.yml as shipped (B = 128, H = 200): encoder GRU and decoder rollout run as persistent CLUSTER kernels (round 5),
     which latch the same fault word.  The same contract as above: a faulted step is not applied, train_iter repeats the iteration
-    on the per-step launches (g2v_dec_rollout_set_persistent(0) + g2v_gru_seq_set_cluster(0)) and training goes on."""
+    on the per-step launches (G2V_OPT_PERSISTENT = 0 + G2V_OPT_GRU_CLUSTER = 0) and training goes on."""
     import bench
     from gesture2vec_amd import _lib
     from gesture2vec_amd.model.Autoencoder_VQVAE_model import Autoencoder_VQVAE
@@ -226,8 +224,6 @@ def test_latched_fault_on_the_cluster_kernels_of_the_shipped_shape_is_repeated_o
         bench.CFG.clear()
         bench.CFG.update(saved_cfg)
         lib.g2v_dec_rollout_persist_fault(1)
-        lib.g2v_dec_rollout_set_persistent(1)
-        lib.g2v_gru_seq_set_cluster(1)
 
 
 @pytest.mark.parametrize("B", [256, 4096])
@@ -273,8 +269,6 @@ def test_fault_latched_in_the_middle_of_a_step_leaves_the_whole_model_state_unto
             assert not torch.equal(snap[n], getattr(eng, n)), f"{n} did not change in a valid step"
     finally:
         lib.g2v_dec_rollout_persist_fault(1)
-        lib.g2v_dec_rollout_set_persistent(1)
-        lib.g2v_gru_seq_set_cluster(1)
 
 
 def test_a_faulting_rank_makes_every_rank_skip_the_step_under_data_parallelism():
@@ -317,8 +311,6 @@ def test_a_faulting_rank_makes_every_rank_skip_the_step_under_data_parallelism()
             assert not torch.equal(snap[n], getattr(eng, n)), f"{n} did not change in a valid step"
     finally:
         lib.g2v_dec_rollout_persist_fault(1)
-        lib.g2v_dec_rollout_set_persistent(1)
-        lib.g2v_gru_seq_set_cluster(1)
 
 
 def test_two_engines_do_not_share_switches_and_a_fault_in_one_leaves_the_other_on_the_fast_path():

@@ -723,7 +723,6 @@ def test_gru_resident_kernels_match_the_streaming_kernels(ops, T, B, use_len, pa
     test_gru_seq's B = 2100 / 6200 cases take the resident kernels by default.)  G2V_OPT_GRU_RESIDENT_BWD = 0 keeps the BPTT on
     the streaming kernel (the VQ-VAE engine's setting)."""
     from gesture2vec_amd import _lib
-    lib = ops._lib_()
     H = 200
     g = torch.Generator().manual_seed(2000 + T + B)
     r = lambda *s: (torch.randn(*s, generator=g) * 0.3).to(DEV)
@@ -743,12 +742,9 @@ def test_gru_resident_kernels_match_the_streaming_kernels(ops, T, B, use_len, pa
     w_hh, b_hh = [r(3 * H, H) for _ in range(2)], [r(3 * H) for _ in range(2)]
     h0 = [r(B, H) if use_h0 else None for _ in range(2)]
     ups = [(r(T, B, H), r(B, H)) for _ in range(2)]
-    prev_rows, prev_bwd = lib.g2v_ctx_get_option(None, _lib.OPT_GRU_RESIDENT_ROWS), lib.g2v_ctx_get_option(None, _lib.OPT_GRU_RESIDENT_BWD)
-    try:
-        res = {}
-        for mode, rows, bwd_on in (("stream", 0, 1), ("resident", 1025, 1), ("resident_fwd_only", 1025, 0)):
-            lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_ROWS, rows)
-            lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_BWD, bwd_on)
+    res = {}
+    for mode, rows, bwd_on in (("stream", 0, 1), ("resident", 1025, 1), ("resident_fwd_only", 1025, 0)):
+        with _lib.Context.current().scoped(gru_resident_rows=rows, gru_resident_bwd=bwd_on):
             fw = [dict(gi=gi[k], w_hh=w_hh[k], b_hh=b_hh[k], h0=h0[k], hs=torch.full((T, B, H), 7.0, device=DEV),
                        h_n=torch.empty((B, H), device=DEV), gates=torch.zeros((T, B, 4 * H), device=DEV), reverse=bool(k)) for k in range(2)]
             ops.gru_dirs_fwd(fw, T, B, H, lengths=lens, row_off=row_off)
@@ -757,9 +753,6 @@ def test_gru_resident_kernels_match_the_streaming_kernels(ops, T, B, use_len, pa
                        dgh=torch.full((T, B, 3 * H), 7.0, device=DEV), dh0=torch.empty((B, H), device=DEV), reverse=bool(k)) for k in range(2)]
             ops.gru_dirs_bwd(bw, T, B, H, lengths=lens, row_off=row_off)
             res[mode] = (fw, bw)
-    finally:
-        lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_ROWS, prev_rows)
-        lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_BWD, prev_bwd)
     rel = lambda a, b: float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
     for k in range(2):
         for name in ("hs", "h_n", "gates"):
@@ -815,8 +808,9 @@ def test_gru_gathered_input_projections(ops):
 def test_gru_cluster_kernels_equal_the_per_step_launches(ops, T, B, H, ndir, use_len, packed, use_h0):
     """g2v_gru_seq_fwd / _bwd at small batch: ONE persistent launch for all steps (csrc/gru.hip, gru_cluster_*_kernel: W_hh rows
     resident, states / gate gradients exchanged through tagged granules) against one launch per step
-    (g2v_gru_seq_set_cluster(0)).  Equal to rounding: the forward runs the same k-ordered chain per gate (the blend of the new state
+    (G2V_OPT_GRU_CLUSTER = 0).  Equal to rounding: the forward runs the same k-ordered chain per gate (the blend of the new state
     is contracted differently: <= 1 ulp per step), the backward's 3H-long contraction is three partial chains there."""
+    from gesture2vec_amd import _lib
     lib = ops._lib_()
     g = torch.Generator().manual_seed(1000 + T + B)
     lengths = None
@@ -850,13 +844,11 @@ def test_gru_cluster_kernels_equal_the_per_step_launches(ops, T, B, H, ndir, use
         return fw, bw
 
     assert lib.g2v_dec_rollout_persist_fault(0) == 0
-    prev = lib.g2v_gru_seq_set_cluster(0)
-    try:
+    cur = _lib.Context.current()
+    with cur.scoped(gru_cluster=0):
         fw_s, bw_s = run()
-        lib.g2v_gru_seq_set_cluster(1)
+    with cur.scoped(gru_cluster=1):
         fw_c, bw_c = run()
-    finally:
-        lib.g2v_gru_seq_set_cluster(prev)
     assert lib.g2v_dec_rollout_persist_fault(0) == 0, "a bounded wait of the cluster kernels ran out"
     for k in range(ndir):
         for name in ("hs", "h_n", "gates"):
@@ -1048,20 +1040,16 @@ def test_dec_rollout_persistent_matches_per_step_kernels(ops, B, p, T):
     z = lambda *s: torch.zeros(*s, device=DEV)
 
     def fwd(persistent):
-        prev = lib.g2v_dec_rollout_set_persistent(int(persistent))
-        try:
+        with _lib.Context.current().scoped(persistent=int(persistent)):
             wt, _ = _dec_weight_tensors(sd, DEV)
             ws = ops.dec_weights_struct(wt)
             saved = _alloc_saved(T, B, D, H, nblk, DEV, p)
             ops.dec_rollout_fwd(target, h_init, ws, saved, k95, kl0, p, 1, True, True, T, B, D, H)
             torch.cuda.synchronize()
             return saved, ws, wt
-        finally:
-            lib.g2v_dec_rollout_set_persistent(prev)
 
     def bwd(persistent, saved, ws):
-        prev = lib.g2v_dec_rollout_set_persistent(int(persistent))
-        try:
+        with _lib.Context.current().scoped(persistent=int(persistent)):
             grads = {"dy": gy.clone(), "du": z(T - 1, B, H), "dbn": z(T - 1, B, H), "dgi0": z(T - 1, B, G),
                      "dgh0": z(T - 1, B, G), "dgi1": z(T - 1, B, G), "dgh1": z(T - 1, B, G), "dh_init": z(2, B, H),
                      "d_bn_w": z(H), "d_bn_b": z(H), "bn_bwd_partial": z(2, nblk, 2, H)}
@@ -1069,8 +1057,6 @@ def test_dec_rollout_persistent_matches_per_step_kernels(ops, B, p, T):
             torch.cuda.synchronize()
             # dbn is scratch of the per-step kernels only (the persistent kernel keeps those values in registers)
             return {k: v for k, v in grads.items() if k not in ("bn_bwd_partial", "dbn")}
-        finally:
-            lib.g2v_dec_rollout_set_persistent(prev)
 
     (sa, wsa, wta), (sb, wsb, wtb), (sc, _, wtc) = fwd(True), fwd(False), fwd(True)
     for k in sa:
@@ -1119,7 +1105,7 @@ def test_dec_rollout_persistent_matches_per_step_kernels(ops, B, p, T):
 def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n_pre, training):
     """Generic dims at small batch: the steps t >= 1 of g2v_dec_rollout_fwd as ONE persistent launch (csrc/dec_rollout.hip,
     dec_cluster_fwd_kernel: weights resident, u / h0 / h1 rows and the BatchNorm partial sums exchanged through tagged granules)
-    against three launches per step (g2v_dec_rollout_set_persistent(0)).  Same arithmetic and summation orders: every saved array
+    against three launches per step (G2V_OPT_PERSISTENT = 0).  Same arithmetic and summation orders: every saved array
     equal to rounding (the blend of a cell's new state is contracted differently by the compiler: <= 1 ulp per step), reproducible
     run to run bit for bit."""
     from gesture2vec_amd import _lib
@@ -1135,8 +1121,7 @@ def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n
     nblk = ops.dec_rollout_blocks(B)
 
     def fwd(setting):
-        prev = lib.g2v_dec_rollout_set_persistent(setting)
-        try:
+        with _lib.Context.current().scoped(persistent=setting):
             wt, _ = _dec_weight_tensors(sd, DEV)
             saved = _alloc_saved(T, B, D, H, nblk, DEV, p)
             for v in saved.values():
@@ -1145,8 +1130,6 @@ def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n
             ops.dec_rollout_fwd(target, h_init, ops.dec_weights_struct(wt), saved, k95, kl0, p, n_pre, True, training, T, B, D, H)
             torch.cuda.synchronize()
             return saved, wt
-        finally:
-            lib.g2v_dec_rollout_set_persistent(prev)
 
     assert lib.g2v_dec_rollout_persist_fault(0) == 0
     (sa, wa), (sb, wb), (sc, wc) = fwd(1), fwd(0), fwd(1)
@@ -1169,8 +1152,7 @@ def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n
     gy = (torch.randn(T, B, D, generator=g) / (T * B * D) * 100).to(DEV)
 
     def bwd(setting):
-        prev = lib.g2v_dec_rollout_set_persistent(setting)
-        try:
+        with _lib.Context.current().scoped(persistent=setting):
             grads = {"dy": gy.clone(), "du": z(T - 1, B, H), "dbn": z(T - 1, B, H), "dgi0": z(T - 1, B, G), "dgh0": z(T - 1, B, G),
                      "dgi1": z(T - 1, B, G), "dgh1": z(T - 1, B, G), "dh_init": z(2, B, H), "d_bn_w": z(H), "d_bn_b": z(H),
                      "bn_bwd_partial": z(2, nblk, 2, H)}
@@ -1180,8 +1162,6 @@ def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n
             ops.dec_rollout_bwd(ops.dec_weights_struct(wb), sb, grads, k95, kl0, p, n_pre, True, T, B, D, H)
             torch.cuda.synchronize()
             return {k: v for k, v in grads.items() if k != "bn_bwd_partial"}
-        finally:
-            lib.g2v_dec_rollout_set_persistent(prev)
 
     ga, gb, gc = bwd(1), bwd(0), bwd(1)
     assert lib.g2v_dec_rollout_persist_fault(0) == 0, "a bounded wait of the backward cluster kernel ran out"
@@ -1193,7 +1173,7 @@ def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n
 
 
 # More row tiles than CUs: R = 2 or 3 tiles per workgroup (csrc/dec_persist.hip, the *_mt kernels).  `mode` is what
-# g2v_dec_rollout_set_persistent gets: 1 = the library's own choice (8192 rows -> 2 tiles, 12288 -> 3, 4112 = 257 tiles: one
+# G2V_OPT_PERSISTENT is set to: 1 = the library's own choice (8192 rows -> 2 tiles, 12288 -> 3, 4112 = 257 tiles: one
 # workgroup with a single tile), 2 / 3 = at least that many, which reaches the same kernels at small batches (80 rows = 5 tiles
 # over 3 workgroups, 112 = 7 tiles over 3 workgroups, 32 = 2 tiles in ONE workgroup: no exchange partner).  The same kernels
 # (also with one tile per workgroup) serve a batch that is not a multiple of 16 rows.
@@ -1219,8 +1199,7 @@ def test_dec_rollout_multi_tile_persistent_matches_per_step_kernels(ops, B, mode
     z = lambda *s: torch.zeros(*s, device=DEV)
 
     def fwd(setting, training=True):
-        prev = lib.g2v_dec_rollout_set_persistent(setting)
-        try:
+        with _lib.Context.current().scoped(persistent=setting):
             assert lib.g2v_dec_rollout_fuses_loss(B, D, H, T) == 0      # no chaser beside the multi-tile kernel
             wt, _ = _dec_weight_tensors(sd, DEV)
             ws = ops.dec_weights_struct(wt)
@@ -1228,12 +1207,9 @@ def test_dec_rollout_multi_tile_persistent_matches_per_step_kernels(ops, B, mode
             ops.dec_rollout_fwd(target, h_init, ws, saved, k95, kl0, p, n_pre, True, training, T, B, D, H)
             torch.cuda.synchronize()
             return saved, ws, wt
-        finally:
-            lib.g2v_dec_rollout_set_persistent(prev)
 
     def bwd(setting, saved, ws):
-        prev = lib.g2v_dec_rollout_set_persistent(setting)
-        try:
+        with _lib.Context.current().scoped(persistent=setting):
             assert setting == 0 or lib.g2v_dec_rollout_bwd_fuses_wgrad(B, D, H) == 0      # the multi-tile kernel fuses nothing
             grads = {"dy": gy.clone(), "du": z(T - 1, B, H), "dbn": z(T - 1, B, H), "dgi0": z(T - 1, B, G),
                      "dgh0": z(T - 1, B, G), "dgi1": z(T - 1, B, G), "dgh1": z(T - 1, B, G), "dh_init": z(2, B, H),
@@ -1241,8 +1217,6 @@ def test_dec_rollout_multi_tile_persistent_matches_per_step_kernels(ops, B, mode
             ops.dec_rollout_bwd(ws, saved, grads, k95, kl0, p, n_pre, True, T, B, D, H)
             torch.cuda.synchronize()
             return {k: v for k, v in grads.items() if k not in ("bn_bwd_partial", "dbn")}
-        finally:
-            lib.g2v_dec_rollout_set_persistent(prev)
 
     (sa, _, wta), (sb, wsb, wtb), (sc, _, wtc) = fwd(mode), fwd(0), fwd(mode)
     for k in sa:
@@ -1750,14 +1724,11 @@ def test_cluster_exchange_preclear_clears_cluster_shapes_only(ops):
         _lib.check(lib.g2v_cluster_exchange_preclear(kind, T, 4096, D, H, 2, ws.data_ptr(), ws.numel(), st), "preclear")
         torch.cuda.synchronize()
         assert bool((ws == 0xAB).all()), f"kind {kind}: a shape that does not run as a cluster was touched"
-    prev = lib.g2v_gru_seq_set_cluster(0)
-    try:
+    with _lib.Context.current().scoped(gru_cluster=0):
         ws = torch.full((int(lib.g2v_gru_seq_bwd_workspace(2, H)),), 0xAB, dtype=torch.uint8, device=DEV)
         _lib.check(lib.g2v_cluster_exchange_preclear(1, T, B, D, H, 2, ws.data_ptr(), ws.numel(), st), "preclear")
         torch.cuda.synchronize()
         assert bool((ws == 0xAB).all()), "the disabled cluster path was pre-cleared"
-    finally:
-        lib.g2v_gru_seq_set_cluster(prev)
 
 
 @pytest.mark.parametrize("G,H,D,M", [(600, 200, 40, 2560), (600, 200, 45, 1280), (36, 12, 5, 100)])

@@ -16,9 +16,16 @@ def relerr(got, ref):
     return float((got - ref).abs().max()) / max(float(ref.abs().max()), 1e-12)
 
 
-@pytest.mark.parametrize("kernels", ["per_operator", "fused_step", "cluster_forward"])
+@pytest.fixture
+def kernels(request):
+    from gesture2vec_amd._lib import Context
+    with Context.current().scoped(persistent=0 if request.param == "fused_step" else 1):      # (fused_step: the step kernels, not the
+        yield request.param                                                                  #  cluster launch behind the same entry)
+
+
+@pytest.mark.parametrize("kernels", ["per_operator", "fused_step", "cluster_forward"], indirect=True)
 @pytest.mark.parametrize("name,att", [("t2e_noatt", "False"), ("t2e_att", "True")])
-def test_text2embedding_matches_reference_golden(golden_dir, name, att, kernels, monkeypatch, request):
+def test_text2embedding_matches_reference_golden(golden_dir, name, att, kernels, monkeypatch):
     """kernels = "fused_step": the decode steps run as g2v_attn_code_rollout_fwd / _bwd (csrc/t2e_rollout.hip; selected from 1024
     rows per batch in production, forced here) -- the fused per-step kernels against the REFERENCE's own numbers."""
     from gesture2vec_amd import rollout_t2e
@@ -28,9 +35,6 @@ def test_text2embedding_matches_reference_golden(golden_dir, name, att, kernels,
     monkeypatch.setattr(rollout_t2e, "CLUSTER_FORWARD", kernels == "cluster_forward")
     if kernels == "cluster_forward" and att == "True":
         pytest.skip("the cluster forward serves the attention-free decoder")
-    from gesture2vec_amd import _lib as _l
-    prev_persist = _l.load().g2v_dec_rollout_set_persistent(0 if kernels == "fused_step" else 1)     # (fused_step: the step kernels, not the
-    request.addfinalizer(lambda: _l.load().g2v_dec_rollout_set_persistent(prev_persist))              #  cluster launch behind the same entry)
     calls0, ccalls0 = rollout_t2e.FUSED_CALLS, rollout_t2e.CLUSTER_CALLS
     from gesture2vec_amd.model.text2embedding_model import text2embedding_model
     from gesture2vec_amd.train_eval.train_seq2seq import train_iter_text2embedding
@@ -328,18 +332,14 @@ def test_fused_step_kernels_match_per_operator_path(att, p, B, n_pre, H, K, monk
     outs = []
     calls0 = rollout_t2e.FUSED_CALLS
     monkeypatch.setattr(rollout_t2e, "CLUSTER_FORWARD", False)      # (the per-operator leg really is per-operator)
-    from gesture2vec_amd import _lib
-    lib = _lib.load()
-    prev = lib.g2v_dec_rollout_set_persistent(0)                    # (the fused leg really runs the step kernels: no cluster launch behind the entry)
-    try:
+    from gesture2vec_amd._lib import Context
+    with Context.current().scoped(persistent=0):      # (the fused leg really runs the step kernels: no cluster launch behind the entry)
         for net, min_rows in zip(nets, (1, 1 << 30)):
             monkeypatch.setattr(rollout_t2e, "FUSED_MIN_ROWS", min_rows)
             net.set_dropout_masks(*masks)
             out, attn = net(ids, lengths, None, codes, None, None)
             (out * w).sum().backward()
             outs.append((out.detach(), attn))
-    finally:
-        lib.g2v_dec_rollout_set_persistent(prev)
     assert rollout_t2e.FUSED_CALLS - calls0 == 1, "the fused step kernels did not serve this shape (g2v_attn_code_rollout_ok)"
     assert relerr(outs[0][0], outs[1][0].cpu()) < 3e-5
     same = (outs[0][0][:, 1:].argmax(2) == outs[1][0][:, 1:].argmax(2)).all(1)
@@ -484,7 +484,7 @@ def test_packed_encoder_inputs_equal_the_padded_grid(att, p, B, H):
 
 
 def test_train_iter_repeats_an_iteration_whose_persistent_kernels_faulted():
-    """The encoder's small-batch GRU kernels are persistent (g2v_gru_seq_set_cluster) and latch the fault word of the persistent
+    """The encoder's small-batch GRU kernels are persistent (G2V_OPT_GRU_CLUSTER) and latch the fault word of the persistent
     kernels when a bounded wait runs out.  A latched iteration must change NOTHING (clip + Adam and BatchNorm's running statistics
     read the latch on the device) and train_iter_text2embedding repeats it once on the per-step kernels: the model after a
     faulted-and-repeated iteration equals the model after a clean one."""
@@ -505,36 +505,36 @@ def test_train_iter_repeats_an_iteration_whose_persistent_kernels_faulted():
     masks = ((torch.rand(S - 1, B, H, generator=g) < 0.5).to(torch.uint8).to(DEV),
              (torch.rand(S - 1, B, H, generator=g) < 1 - p).to(torch.uint8).to(DEV), None)
     states = []
-    prev = lib.g2v_gru_seq_set_cluster(1)
-    try:
-        for fault in (False, True):
-            torch.manual_seed(9)
-            net = text2embedding_model(args, 135, 20, NW, EMB, np.random.RandomState(2).randn(NW, EMB).astype(np.float32), None).to(DEV)
-            net.train(True)
-            optim = FlatClipAdam(net.parameters(), lr=1e-3, betas=(0.5, 0.999))
-            net.set_dropout_masks(*masks)
-            assert lib.g2v_dec_rollout_persist_fault(1) == 0
-            lib.g2v_gru_seq_set_cluster(1 if fault else 0)      # (the clean run on the kernels the repeated iteration ends up on)
-            lib.g2v_dec_rollout_set_persistent(1 if fault else 0)
-            if fault:
-                lib.g2v_dec_rollout_persist_fault(-1)          # as a bounded wait running out would
-                orig = net.forward                               # (the repeated iteration needs the same explicit masks again)
+    cur = _lib.Context.current()
+    with cur.scoped(gru_cluster=1, persistent=1):
+        try:
+            for fault in (False, True):
+                torch.manual_seed(9)
+                net = text2embedding_model(args, 135, 20, NW, EMB, np.random.RandomState(2).randn(NW, EMB).astype(np.float32), None).to(DEV)
+                net.train(True)
+                optim = FlatClipAdam(net.parameters(), lr=1e-3, betas=(0.5, 0.999))
+                net.set_dropout_masks(*masks)
+                assert lib.g2v_dec_rollout_persist_fault(1) == 0
+                cur.set(_lib.OPT_GRU_CLUSTER, 1 if fault else 0)      # (the clean run on the kernels the repeated iteration ends up on)
+                cur.set(_lib.OPT_PERSISTENT, 1 if fault else 0)
+                if fault:
+                    lib.g2v_dec_rollout_persist_fault(-1)          # as a bounded wait running out would
+                    orig = net.forward                               # (the repeated iteration needs the same explicit masks again)
 
-                def fwd(*a, **k):
-                    net.set_dropout_masks(*masks)
-                    return orig(*a, **k)
-                net.forward = fwd
-                with pytest.warns(RuntimeWarning, match="repeated on the per-step kernels"):
+                    def fwd(*a, **k):
+                        net.set_dropout_masks(*masks)
+                        return orig(*a, **k)
+                    net.forward = fwd
+                    with pytest.warns(RuntimeWarning, match="repeated on the per-step kernels"):
+                        r = train_iter_text2embedding(args, 1, ids, lengths, None, None, codes, None, net, optim)
+                    assert cur.get(_lib.OPT_GRU_CLUSTER) == 0      # the per-step kernels were selected
+                    cur.set(_lib.OPT_GRU_CLUSTER, 1)
+                else:
                     r = train_iter_text2embedding(args, 1, ids, lengths, None, None, codes, None, net, optim)
-                assert lib.g2v_gru_seq_set_cluster(1) == 0      # the per-step kernels were selected
-            else:
-                r = train_iter_text2embedding(args, 1, ids, lengths, None, None, codes, None, net, optim)
-            assert lib.g2v_dec_rollout_persist_fault(0) == 0
-            states.append((r["loss"], {k: v.detach().clone() for k, v in net.state_dict().items()}))
-    finally:
-        lib.g2v_dec_rollout_persist_fault(1)
-        lib.g2v_gru_seq_set_cluster(prev)
-        lib.g2v_dec_rollout_set_persistent(1)
+                assert lib.g2v_dec_rollout_persist_fault(0) == 0
+                states.append((r["loss"], {k: v.detach().clone() for k, v in net.state_dict().items()}))
+        finally:
+            lib.g2v_dec_rollout_persist_fault(1)
     assert states[0][0] == states[1][0]
     for k, v in states[0][1].items():      # the same kernels on the same inputs: the discarded attempt left no trace at all
         assert torch.equal(v, states[1][1][k]), k
@@ -763,43 +763,42 @@ def test_a_fault_latched_after_the_forward_leaves_batchnorm_running_statistics_a
     from gesture2vec_amd.train_eval import train_seq2seq as TS
     lib = _lib.load()
     states = []
-    prev_c, prev_p = lib.g2v_gru_seq_set_cluster(1), lib.g2v_dec_rollout_set_persistent(1)
+    cur = _lib.Context.current()
     saved_policy = (POLICY.off, POLICY.clean, POLICY.faults, POLICY.rearms)
-    try:
-        for fault in (False, True):
-            args, net, optim, ids, lengths, codes, masks = _small_t2e()
-            lib.g2v_dec_rollout_persist_fault(1)
-            lib.g2v_gru_seq_set_cluster(1 if fault else 0)      # (the clean run on the kernels the repeated iteration ends up on)
-            lib.g2v_dec_rollout_set_persistent(1 if fault else 0)
-            orig_fwd = net.forward
+    with cur.scoped(gru_cluster=1, persistent=1):
+        try:
+            for fault in (False, True):
+                args, net, optim, ids, lengths, codes, masks = _small_t2e()
+                lib.g2v_dec_rollout_persist_fault(1)
+                cur.set(_lib.OPT_GRU_CLUSTER, 1 if fault else 0)      # (the clean run on the kernels the repeated iteration ends up on)
+                cur.set(_lib.OPT_PERSISTENT, 1 if fault else 0)
+                orig_fwd = net.forward
 
-            def fwd(*a, **k):
-                net.set_dropout_masks(*masks)                    # (the repeated iteration needs the same explicit masks again)
-                return orig_fwd(*a, **k)
-            net.forward = fwd
-            if fault:
-                orig_loss, fired = TS._code_loss_backward, []
+                def fwd(*a, **k):
+                    net.set_dropout_masks(*masks)                    # (the repeated iteration needs the same explicit masks again)
+                    return orig_fwd(*a, **k)
+                net.forward = fwd
+                if fault:
+                    orig_loss, fired = TS._code_loss_backward, []
 
-                def fault_then_loss_and_backward(outputs, codes_):
-                    if not fired:                                # behind the FORWARD of the first attempt, in front of its backward
-                        fired.append(1)
-                        torch.cuda.synchronize()
-                        lib.g2v_dec_rollout_persist_fault(-1)
-                    return orig_loss(outputs, codes_)
-                monkeypatch.setattr(TS, "_code_loss_backward", fault_then_loss_and_backward)
-                with pytest.warns(RuntimeWarning, match="repeated on the per-step kernels"):
+                    def fault_then_loss_and_backward(outputs, codes_):
+                        if not fired:                                # behind the FORWARD of the first attempt, in front of its backward
+                            fired.append(1)
+                            torch.cuda.synchronize()
+                            lib.g2v_dec_rollout_persist_fault(-1)
+                        return orig_loss(outputs, codes_)
+                    monkeypatch.setattr(TS, "_code_loss_backward", fault_then_loss_and_backward)
+                    with pytest.warns(RuntimeWarning, match="repeated on the per-step kernels"):
+                        r = TS.train_iter_text2embedding(args, 1, ids, lengths, None, None, codes, None, net, optim)
+                    monkeypatch.setattr(TS, "_code_loss_backward", orig_loss)
+                    assert fired
+                else:
                     r = TS.train_iter_text2embedding(args, 1, ids, lengths, None, None, codes, None, net, optim)
-                monkeypatch.setattr(TS, "_code_loss_backward", orig_loss)
-                assert fired
-            else:
-                r = TS.train_iter_text2embedding(args, 1, ids, lengths, None, None, codes, None, net, optim)
-            assert lib.g2v_dec_rollout_persist_fault(0) == 0
-            states.append((r["loss"], {k: v.detach().clone() for k, v in net.state_dict().items()}))
-    finally:
-        lib.g2v_dec_rollout_persist_fault(1)
-        lib.g2v_gru_seq_set_cluster(prev_c)
-        lib.g2v_dec_rollout_set_persistent(prev_p)
-        POLICY.off, POLICY.clean, POLICY.faults, POLICY.rearms = saved_policy
+                assert lib.g2v_dec_rollout_persist_fault(0) == 0
+                states.append((r["loss"], {k: v.detach().clone() for k, v in net.state_dict().items()}))
+        finally:
+            lib.g2v_dec_rollout_persist_fault(1)
+            POLICY.off, POLICY.clean, POLICY.faults, POLICY.rearms = saved_policy
     bn0 = states[0][1]["decoder.decoder.pre_linear.1.running_mean"]
     assert float(bn0.abs().max()) > 0, "the clean iteration did not update the running statistics at all"
     assert states[0][0] == states[1][0]
@@ -846,49 +845,48 @@ def test_graphed_step_detects_a_fault_recaptures_and_the_policy_rearms():
     from gesture2vec_amd.fault_policy import POLICY
     from gesture2vec_amd.train_eval.train_seq2seq import GraphedText2EmbeddingStep
     lib = _lib.load()
-    prev_c, prev_p = lib.g2v_gru_seq_set_cluster(1), lib.g2v_dec_rollout_set_persistent(1)
+    cur = _lib.Context.current()
     saved = (POLICY.off, POLICY.clean, POLICY.faults, POLICY.rearms, POLICY.rearm_after, POLICY.max_rearms)
-    try:
-        lib.g2v_dec_rollout_persist_fault(1)
-        POLICY.off, POLICY.clean, POLICY.rearms, POLICY.rearm_after, POLICY.max_rearms = False, 0, 0, 6, 1
-        args, net, optim, ids, lengths, codes, masks = _small_t2e()
-        step = GraphedText2EmbeddingStep(args, net, optim, ids, lengths, codes, check_every=4)
-        for _ in range(4):
-            step.replay()
-        assert step.lost_replays == 0 and step.recaptures == 0
-        w0 = {k: v.detach().clone() for k, v in net.state_dict().items()}
-        lib.g2v_dec_rollout_persist_fault(-1)                    # as a bounded wait running out would
-        with pytest.warns(RuntimeWarning, match="were not applied"):
+    with cur.scoped(gru_cluster=1, persistent=1):
+        try:
+            lib.g2v_dec_rollout_persist_fault(1)
+            POLICY.off, POLICY.clean, POLICY.rearms, POLICY.rearm_after, POLICY.max_rearms = False, 0, 0, 6, 1
+            args, net, optim, ids, lengths, codes, masks = _small_t2e()
+            step = GraphedText2EmbeddingStep(args, net, optim, ids, lengths, codes, check_every=4)
             for _ in range(4):
                 step.replay()
-        # the four replays behind the fault changed nothing; then ONE repeated step on the per-step kernels moved the weights
-        assert step.lost_replays == 4 and step.recaptures == 1
-        assert lib.g2v_dec_rollout_persist_fault(0) == 0
-        assert lib.g2v_gru_seq_set_cluster(0) == 0 and POLICY.off      # the per-step kernels are selected
-        moved = [k for k, v in net.state_dict().items() if v.dtype.is_floating_point and not torch.equal(v, w0[k])]
-        assert moved, "the repeated step was not applied"
-        # (3 warm-up steps of the first capture + 4 applied replays + the re-capture's eager step; the 4 unapplied ones do not count)
-        assert int(net.decoder.decoder.pre_linear[1].num_batches_tracked) == (3 + 4 + 1) * (codes.shape[1] - 1)
-        # six clean replays later the fast path is back, and the graph is captured again for it
-        for _ in range(8):
-            step.replay()
-        assert not POLICY.off and POLICY.rearms == 1
-        assert lib.g2v_gru_seq_set_cluster(1) == 1 and lib.g2v_dec_rollout_set_persistent(1) == 1
-        assert step.recaptures == 2
-        loss = step.read_loss()
-        assert np.isfinite(loss)
-        # a static-lengths graph refuses other lengths instead of replaying stale packing (advisor finding)
-        st2 = GraphedText2EmbeddingStep(args, net, optim, ids, lengths, codes, static_lengths=True, check_every=0)
-        other = lengths.clone(); other[-1] = max(1, int(other[-1]) - 1)
-        with pytest.raises(ValueError, match="set_lengths"):
+            assert step.lost_replays == 0 and step.recaptures == 0
+            w0 = {k: v.detach().clone() for k, v in net.state_dict().items()}
+            lib.g2v_dec_rollout_persist_fault(-1)                    # as a bounded wait running out would
+            with pytest.warns(RuntimeWarning, match="were not applied"):
+                for _ in range(4):
+                    step.replay()
+            # the four replays behind the fault changed nothing; then ONE repeated step on the per-step kernels moved the weights
+            assert step.lost_replays == 4 and step.recaptures == 1
+            assert lib.g2v_dec_rollout_persist_fault(0) == 0
+            assert cur.get(_lib.OPT_GRU_CLUSTER) == 0 and POLICY.off      # the per-step kernels are selected
+            moved = [k for k, v in net.state_dict().items() if v.dtype.is_floating_point and not torch.equal(v, w0[k])]
+            assert moved, "the repeated step was not applied"
+            # (3 warm-up steps of the first capture + 4 applied replays + the re-capture's eager step; the 4 unapplied ones do not count)
+            assert int(net.decoder.decoder.pre_linear[1].num_batches_tracked) == (3 + 4 + 1) * (codes.shape[1] - 1)
+            # six clean replays later the fast path is back, and the graph is captured again for it
+            for _ in range(8):
+                step.replay()
+            assert not POLICY.off and POLICY.rearms == 1
+            assert cur.get(_lib.OPT_GRU_CLUSTER) == 1 and cur.get(_lib.OPT_PERSISTENT) == 1
+            assert step.recaptures == 2
+            loss = step.read_loss()
+            assert np.isfinite(loss)
+            # a static-lengths graph refuses other lengths instead of replaying stale packing (advisor finding)
+            st2 = GraphedText2EmbeddingStep(args, net, optim, ids, lengths, codes, static_lengths=True, check_every=0)
+            other = lengths.clone(); other[-1] = max(1, int(other[-1]) - 1)
+            with pytest.raises(ValueError, match="set_lengths"):
+                st2.replay(other)
+            st2.set_lengths(other)
             st2.replay(other)
-        st2.set_lengths(other)
-        st2.replay(other)
-    finally:
-        lib.g2v_dec_rollout_persist_fault(1)
-        lib.g2v_gru_seq_set_cluster(prev_c)
-        lib.g2v_dec_rollout_set_persistent(prev_p)
-        POLICY.off, POLICY.clean, POLICY.faults, POLICY.rearms, POLICY.rearm_after, POLICY.max_rearms = saved
+        finally:
+            lib.g2v_dec_rollout_persist_fault(1)
+            POLICY.off, POLICY.clean, POLICY.faults, POLICY.rearms, POLICY.rearm_after, POLICY.max_rearms = saved
 
 
 @pytest.mark.parametrize("att,B,H,K", [("False", 2048, 200, 512), ("True", 2048, 200, 512), ("False", 128, 200, 512), ("True", 24, 48, 64)])
@@ -906,13 +904,9 @@ def test_side_branches_of_the_backward_change_nothing(att, B, H, K, graphed, mon
     # (the W_hh-resident BPTT is taken only while no side branch is in flight -- with the branches off it would serve BOTH encoder
     #  layers, with them on only the first, and it equals the streaming kernel to summation order only: pinned off here so that
     #  both runs launch the same kernels and the comparison stays bit for bit)
-    lib = _lib.load()
-    prev_res = lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_BWD, 0)
     monkeypatch.setattr(ops, "side_pending", lambda: False)
-    try:
+    with _lib.Context.current().scoped(gru_resident_bwd=0):
         _run_side_on_off(att, B, graphed, monkeypatch, ops, TS, mk, states)
-    finally:
-        lib.g2v_ctx_set_option(None, _lib.OPT_GRU_RESIDENT_BWD, prev_res)
     assert states[0][0] == states[1][0], (states[0][0], states[1][0])
     for k, v in states[0][1].items():
         assert torch.equal(v, states[1][1][k]), k

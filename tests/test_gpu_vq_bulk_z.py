@@ -131,14 +131,10 @@ def test_workspace_poisoned_short_and_unsupported_shapes():
 
 def test_smallm_rows_bound_follows_the_context():
     from gesture2vec_amd import _lib, ops
-    lib = _lib.load()
     assert ops.vq_assign_bulk_z_ok(4096, E, 512)
-    prev = lib.g2v_linear_set_smallm_rows(4096)               # (returns the previous value)
-    try:
+    with _lib.Context.current().scoped(smallm_rows=4096):
         assert not ops.vq_assign_bulk_z_ok(4096, E, 512)     # g2v_linear_fwd would take gemm_smallm_kernel there
         assert ops.vq_assign_bulk_z_ok(4097, E, 512)
-    finally:
-        lib.g2v_linear_set_smallm_rows(prev)
 
 
 def test_matches_the_oracle_outside_the_rounding_band():
