@@ -64,6 +64,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--dae_all_frames", action="store_true",
                     help="train_DAE.py: an epoch visits every frame of every cached chunk (the reference's epoch visits only the "
                          "first n_chunks frames: its __len__ counts LMDB entries, lmdb_data_loader.py:357-364)")
+    ap.add_argument("--embedding-maps", dest="embedding_maps", action="store_true",
+                    help="train_autoencoder_VQVAE.py: write the 2-D t-SNE map of the codebook to plots/Embedding_Epoch(<n>).npz "
+                         "before every epoch (where the reference saves the .png of plot_embedding)")
     for key, typ, _default, _req in _SPEC:
         ap.add_argument("--" + key, type=typ, default=None)
     for key in _LIST_PATH_KEYS:
@@ -74,7 +77,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     with open(cli.config) as f:
         cfg = yaml.safe_load(f) or {}
     out = argparse.Namespace(config=cli.config, synthetic=cli.synthetic, synthetic_batches=cli.synthetic_batches,
-                             save_every=cli.save_every, resume=cli.resume, dae_all_frames=cli.dae_all_frames)
+                             save_every=cli.save_every, resume=cli.resume, dae_all_frames=cli.dae_all_frames,
+                             embedding_maps=cli.embedding_maps)
     missing = []
     for key, typ, default, req in _SPEC:
         v = getattr(cli, key)

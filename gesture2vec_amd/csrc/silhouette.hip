@@ -29,6 +29,7 @@
 // along the lane direction as well.
 #include "common.hpp"
 #include "km_sort.hpp"
+#include "pair_dist.hpp"
 
 namespace g2v {
 namespace {
@@ -38,7 +39,7 @@ constexpr int SIL_SUB = 16;                 // slots per subtile (= one MFMA til
 constexpr int SIL_TILE = 64;                // slots per owner tile and per swept tile
 constexpr int SIL_KC = 32;                  // columns per staged chunk of the swept tile
 constexpr int SIL_SWLD = SIL_KC + 4;        // its LDS row stride (an odd number of 16-byte slots)
-constexpr float SIL_NEAR = 0.125f;
+constexpr float SIL_NEAR = PD_NEAR;
 
 struct SilLayout {
   int nb;                  // sort blocks
@@ -124,19 +125,7 @@ __device__ __forceinline__ float4 sil_keep(bool ok, const float4& v) {
 
 // |x_ri - x_rj| in float64 from the rows, by the whole wave; every lane returns the same bits
 __device__ __forceinline__ double sil_pair(const float* __restrict__ x, int64_t ld, int E, int ri, int rj, int lane) {
-  const float4* pi = reinterpret_cast<const float4*>(x + (int64_t)ri * ld);
-  const float4* pj = reinterpret_cast<const float4*>(x + (int64_t)rj * ld);
-  double acc = 0.0;
-  for (int v = lane; v < (E >> 2); v += 64) {
-    const float4 a = pi[v], b = pj[v];
-    const double d0 = (double)a.x - (double)b.x, d1 = (double)a.y - (double)b.y, d2 = (double)a.z - (double)b.z,
-                 d3 = (double)a.w - (double)b.w;
-    acc = fma(d0, d0, acc);
-    acc = fma(d1, d1, acc);
-    acc = fma(d2, d2, acc);
-    acc = fma(d3, d3, acc);
-  }
-  return sqrt(km_wave_sum(acc));
+  return sqrt(pd_pair_sq(x, ld, E, ri, rj, lane));
 }
 
 // LDS: own[64][E16 + 4] | swept[2][64][SIL_SWLD]

@@ -1,0 +1,249 @@
+"""2-D maps of latent rows and codebooks, on the device: the reference's `PCA(50)` + `TSNE(n_components=2, perplexity=30)` pictures of
+the codebook (`train_autoencoder_VQVAE.py:450-505`, `train_DAE.py:516-526`, `inference_Autoencoder.py:269-277`) and of all chunk
+latents coloured by code (`Clustering.py:1046-1056`, `:1411-1417`).  Arguments, attributes and the optimisation schedule follow
+`sklearn.decomposition.PCA` and `sklearn.manifold.TSNE(method="exact")` (sklearn 1.7); sklearn itself is not imported.
+
+* `PCA`: the float64 covariance comes from `metrics.LatentMoments` (g2v_moments_accumulate: one pass over the rows), a host
+  `numpy.linalg.eigh` of the E x E matrix gives the components, `transform` is one g2v_linear_fwd with bias -mean C^T.
+* `TSNE`: g2v_tsne_affinities builds the dense joint P once (csrc/tsne.hip), every iteration is g2v_tsne_gradient (one pass over P)
+  + g2v_tsne_update; the host reads the KL divergence and the gradient norm back every 50 iterations, where sklearn checks its two
+  stop rules.  Only `n_components == 2` and the exact method exist; N <= `ops.tsne_max_rows()` rows.
+
+Out of scope: openTSNE's `transform` of new points, Barnes-Hut / FFT approximations, 3-D maps, plots."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .pipeline import _need_cuda
+
+_N_ITER_CHECK = 50
+_EXPLORATION_MAX_ITER = 250
+
+
+def _rows(x, what):
+    _need_cuda(x, what)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise TypeError(f"{what}: expected a (N, E) fp32 tensor, got {tuple(x.shape)} {x.dtype}")
+    return x if x.stride(1) == 1 else x.contiguous()
+
+
+def _rng(random_state):
+    return random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+
+
+class PCA:
+    """`fit` / `transform` / `fit_transform` over (N, E) fp32 GPU rows; `mean_`, `components_` (k, E), `explained_variance_`,
+    `explained_variance_ratio_` as float64 numpy, each component signed so that its largest-magnitude entry is positive (sklearn's
+    svd_flip on V).  A streamed set takes one `update` per batch and then `fit()`.  As the reference does inside its `try`, data
+    with fewer than `n_components` rows or columns is passed through unchanged (`components_` stays None).  Pickles without device
+    state."""
+
+    def __init__(self, n_components=50):
+        if int(n_components) < 1:
+            raise ValueError("PCA: n_components must be positive")
+        self.n_components = int(n_components)
+        self.mean_ = self.components_ = self.explained_variance_ = self.explained_variance_ratio_ = None
+        self.n_samples_ = 0
+        self._mom = None
+        self._dev = {}                 # device -> (weights (k, E), bias (k,)); never pickled
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_mom"], state["_dev"] = None, {}
+        return state
+
+    def update(self, rows: torch.Tensor) -> "PCA":
+        from .metrics import LatentMoments
+        rows = _rows(rows, "PCA.update")
+        if self._mom is None:
+            self._mom = LatentMoments(rows.shape[1], rows.device)
+        self._mom.update(rows)
+        return self
+
+    def fit(self, x: torch.Tensor = None) -> "PCA":
+        if x is not None:
+            self._mom = None
+            self.update(x)
+        if self._mom is None:
+            raise ValueError("PCA.fit: no rows (pass x, or call update first)")
+        self._dev = {}
+        n, E = self._mom.n, self._mom.E
+        self.n_samples_ = n
+        self.mean_ = self.components_ = self.explained_variance_ = self.explained_variance_ratio_ = None
+        if min(n, E) < self.n_components:
+            return self
+        _, mean, cov = self._mom.finalize()
+        lam, v = np.linalg.eigh(0.5 * (cov + cov.T))
+        lam, v = np.clip(lam[::-1], 0.0, None), v[:, ::-1]
+        comp = v[:, :self.n_components].T.copy()
+        comp *= np.sign(comp[np.arange(comp.shape[0]), np.abs(comp).argmax(axis=1)])[:, None]
+        self.mean_, self.components_ = mean, comp
+        self.explained_variance_ = lam[:self.n_components].copy()
+        self.explained_variance_ratio_ = self.explained_variance_ / lam.sum()
+        return self
+
+    def _project(self, x, scale=1.0):
+        """x C^T scale - mean C^T scale as one dense layer; output rows padded to a multiple of 4 floats (a view is returned)"""
+        from . import ops
+        k = self.components_.shape[0]
+        key = (str(x.device), float(scale))
+        if key not in self._dev:
+            w = self.components_ * scale
+            self._dev = {key: (torch.from_numpy(w.astype(np.float32)).to(x.device).contiguous(),
+                               torch.from_numpy((-(w @ self.mean_)).astype(np.float32)).to(x.device).contiguous())}
+        w, b = self._dev[key]
+        ldy = (k + 3) & ~3
+        out = torch.zeros((x.shape[0], ldy), dtype=torch.float32, device=x.device)
+        ops.linear_fwd(x, w, b, M=x.shape[0], ldx=int(x.stride(0)), out=out, ldy=ldy)
+        return out[:, :k]
+
+    def transform(self, x: torch.Tensor) -> torch.Tensor:
+        x = _rows(x, "PCA.transform")
+        if self.n_samples_ == 0:
+            raise ValueError("PCA.transform: not fitted")
+        if self.components_ is None:
+            return x
+        if x.shape[1] != self.components_.shape[1]:
+            raise ValueError(f"PCA.transform: rows must have {self.components_.shape[1]} columns, got {x.shape[1]}")
+        return self._project(x)
+
+    def fit_transform(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fit(x).transform(x)
+
+
+class TSNE:
+    """Exact t-SNE of (N, d) fp32 GPU rows into the plane with sklearn's schedule: 250 exploration iterations at momentum 0.5 with
+    `early_exaggeration`, then momentum 0.8; velocity and gains start afresh in each phase; `learning_rate="auto"` is
+    max(N / early_exaggeration / 4, 50); the two stop rules (no progress of the KL divergence for `n_iter_without_progress`
+    iterations, gradient norm <= `min_grad_norm`) are looked at every 50 iterations.  `init`: "pca" (the first two principal
+    scores, scaled to a standard deviation of 1e-4 in column 0), "random" (1e-4 * RandomState(random_state).standard_normal((N, 2)))
+    or an (N, 2) array.  After `fit`: `embedding_` (N, 2) fp32 on the device, `kl_divergence_`, `n_iter_`, `learning_rate_`."""
+
+    def __init__(self, n_components=2, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_iter=1000,
+                 n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=None, method="exact"):
+        if int(n_components) != 2:
+            raise ValueError(f"TSNE: only n_components == 2 is built (got {n_components})")
+        if method != "exact":
+            raise ValueError(f"TSNE: only method == 'exact' is built (got {method!r})")
+        if not float(perplexity) > 0.0:
+            raise ValueError("TSNE: perplexity must be positive")
+        if not float(early_exaggeration) >= 1.0:
+            raise ValueError("TSNE: early_exaggeration must be at least 1")
+        if not (learning_rate == "auto" or (not isinstance(learning_rate, str) and float(learning_rate) > 0.0)):
+            raise ValueError("TSNE: learning_rate must be 'auto' or a positive number")
+        if int(max_iter) < _EXPLORATION_MAX_ITER:
+            raise ValueError(f"TSNE: max_iter must be at least {_EXPLORATION_MAX_ITER}")
+        if isinstance(init, str) and init not in ("pca", "random"):
+            raise ValueError(f"TSNE: init must be 'pca', 'random' or an (N, 2) array (got {init!r})")
+        self.n_components = 2
+        self.perplexity = float(perplexity)
+        self.early_exaggeration = float(early_exaggeration)
+        self.learning_rate = learning_rate
+        self.max_iter = int(max_iter)
+        self.n_iter_without_progress = int(n_iter_without_progress)
+        self.min_grad_norm = float(min_grad_norm)
+        self.init = init
+        self.random_state = random_state
+        self.method = method
+        self.embedding_ = self.kl_divergence_ = self.n_iter_ = self.learning_rate_ = None
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        if torch.is_tensor(state["embedding_"]):
+            state["embedding_"] = state["embedding_"].cpu()
+        return state
+
+    def _initial(self, x, N):
+        if isinstance(self.init, str) and self.init == "pca":
+            if x.shape[1] < 2:
+                raise ValueError("TSNE: init='pca' needs rows of at least 2 columns")
+            pca = PCA(2).fit(x)
+            std0 = float(np.sqrt(pca.explained_variance_[0] * (N - 1) / N))     # np.std of the first score
+            if not std0 > 0.0:
+                raise ValueError("TSNE: init='pca' on rows without variance")
+            return pca._project(x, 1e-4 / std0).contiguous()
+        if isinstance(self.init, str):
+            y = 1e-4 * _rng(self.random_state).standard_normal(size=(N, 2))
+        else:
+            y = np.asarray(self.init.detach().cpu() if torch.is_tensor(self.init) else self.init)
+            if y.shape != (N, 2):
+                raise ValueError(f"TSNE: init must be ({N}, 2), got {y.shape}")
+        return torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32)).to(x.device)
+
+    def _descent(self, P, y, it, max_iter, n_iter_without_progress, momentum, exaggeration, bufs):
+        """sklearn's _gradient_descent: -> (last KL read, last iteration)"""
+        from . import ops
+        grad, out, gnorm2 = bufs
+        velocity, gains = torch.zeros_like(y), torch.ones_like(y)
+        error = best_error = np.finfo(float).max
+        best_iter = i = it
+        for i in range(it, max_iter):
+            check = (i + 1) % _N_ITER_CHECK == 0
+            want_kl = check or i == max_iter - 1
+            ops.tsne_gradient(P, y, exaggeration, want_kl, grad=grad, out=out)
+            ops.tsne_update(y, velocity, gains, grad, momentum, self.learning_rate_, gnorm2 if check else None)
+            if want_kl:
+                error = float(out[0].item())
+            if check:
+                if error < best_error:
+                    best_error, best_iter = error, i
+                elif i - best_iter > n_iter_without_progress:
+                    break
+                if float(np.sqrt(gnorm2.item())) <= self.min_grad_norm:
+                    break
+        return error, i
+
+    @torch.no_grad()
+    def fit(self, x: torch.Tensor, y=None) -> "TSNE":
+        from . import ops
+        x = _rows(x, "TSNE.fit")
+        N = x.shape[0]
+        if self.perplexity >= N:
+            raise ValueError(f"perplexity ({self.perplexity}) must be less than n_samples ({N})")
+        if N > ops.tsne_max_rows():
+            raise ValueError(f"TSNE: {N} rows; the exact method holds the dense N x N joint and is built for at most "
+                             f"{ops.tsne_max_rows()} rows: map a sub-sample (latent_map(..., sample_size=M))")
+        if x.stride(0) % 4 != 0:                                   # rows on a 16-byte pitch: layout only
+            wide = torch.zeros((N, (x.shape[1] + 3) & ~3), dtype=torch.float32, device=x.device)
+            wide[:, :x.shape[1]] = x
+            x = wide[:, :x.shape[1]]
+        self.learning_rate_ = (max(N / self.early_exaggeration / 4.0, 50.0) if isinstance(self.learning_rate, str)
+                               else float(self.learning_rate))
+        emb = self._initial(x, N)
+        P = ops.tsne_affinities(x, self.perplexity)
+        bufs = (torch.empty_like(emb), torch.empty((3,), dtype=torch.float64, device=x.device),
+                torch.empty((1,), dtype=torch.float64, device=x.device))
+        kl, it = self._descent(P, emb, 0, _EXPLORATION_MAX_ITER, _EXPLORATION_MAX_ITER, 0.5, self.early_exaggeration, bufs)
+        if it < _EXPLORATION_MAX_ITER or self.max_iter - _EXPLORATION_MAX_ITER > 0:
+            kl, it = self._descent(P, emb, it + 1, self.max_iter, self.n_iter_without_progress, 0.8, 1.0, bufs)
+        self.embedding_, self.kl_divergence_, self.n_iter_ = emb, kl, it
+        return self
+
+    def fit_transform(self, x: torch.Tensor, y=None) -> torch.Tensor:
+        return self.fit(x).embedding_
+
+
+@torch.no_grad()
+def latent_map(latents: torch.Tensor, n_pca=50, sample_size=None, random_state=None, **tsne_kw):
+    """(N, E) fp32 GPU latent rows -> (coords (M, 2) fp32, row indices (M,) int64), both on the device: `PCA(n_pca)` (skipped for
+    fewer than n_pca rows or columns, as in the reference) and then `TSNE(random_state=random_state, **tsne_kw)`.  `sample_size`
+    rows are drawn as `silhouette_score` draws them: `numpy.random.RandomState(random_state).permutation(N)[:sample_size]`."""
+    latents = _rows(latents, "latent_map")
+    N = latents.shape[0]
+    rs = _rng(random_state)
+    if sample_size is not None:
+        idx = torch.from_numpy(rs.permutation(N)[:int(sample_size)].astype(np.int64)).to(latents.device)
+        latents = latents[idx].contiguous()                        # a gather: layout only
+    else:
+        idx = torch.arange(N, dtype=torch.int64, device=latents.device)
+    rows = PCA(n_pca).fit_transform(latents)
+    return TSNE(random_state=rs, **tsne_kw).fit_transform(rows), idx
+
+
+@torch.no_grad()
+def codebook_map(net, n_pca=50, **tsne_kw) -> torch.Tensor:
+    """The (K, 2) map of the quantiser's codebook, `net.vq_layer._embedding.weight`."""
+    if not getattr(net, "vq", True) or getattr(net, "vq_layer", None) is None:
+        raise ValueError("codebook_map: this autoencoder has no quantiser (autoencoder_vq == 'False'), so there is no codebook")
+    return latent_map(net.vq_layer._embedding.weight.detach().float(), n_pca=n_pca, **tsne_kw)[0]

@@ -10,7 +10,7 @@
 The reference does all of it on the host with numpy / scipy / sklearn on latents pulled off the device chunk by chunk; nothing here
 needs scipy or sklearn.  For an autoencoder without a quantiser the code ids come from a fitted `gesture2vec_amd.kmeans.KMeans`
 (`kmeans=`), as the reference takes them from its pickled k-means model.  Out of scope: BLEU over code sequences (`:1560-1609`, host
-string work on `torchtext`), t-SNE and the plots."""
+string work on `torchtext`) and the plots (the PCA + t-SNE maps are `gesture2vec_amd.embedding`)."""
 from __future__ import annotations
 
 from typing import Callable, Optional

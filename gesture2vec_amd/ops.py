@@ -1190,3 +1190,56 @@ def silhouette_samples(x, labels, K):
                                      _p(res["b"]), _p(res["s"]), _p(res["counts"]), _p(res["out"]), _p(ws), nb, _stream()),
           "silhouette_samples")
     return res
+
+
+# ------------------------------------------------------------------------------------------ exact t-SNE (tsne.hip)
+def tsne_max_rows() -> int:
+    return int(_lib_().g2v_tsne_max_rows())
+
+
+def tsne_affinities(x, perplexity):
+    """The joint P (N, N) fp32 of exact t-SNE over the rows of x (N, d) fp32, unit column stride, row stride a multiple of 4
+    (g2v_tsne_affinities: Gram distances, sklearn's per-row bisection of the precision, symmetrised; symmetric, diagonal 0)."""
+    if not x.is_cuda:
+        raise _lib.G2VLibraryError("x must be a GPU tensor: the g2v kernels have no CPU path")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise TypeError("tsne_affinities: x must be a (N, d) fp32 tensor with unit column stride")
+    N, d = x.shape
+    if not 2 <= N <= tsne_max_rows():
+        raise ValueError(f"tsne_affinities: N = {N} outside [2, {tsne_max_rows()}]")
+    lib = _lib_()
+    nb = int(lib.g2v_tsne_affinities_workspace(N, d))
+    ws = workspace(max(nb, 16), x.device, "tsne")
+    out = torch.empty((N, N), dtype=torch.float32, device=x.device)
+    check(lib.g2v_tsne_affinities(_p(x), int(x.stride(0)), N, d, float(perplexity), _p(out), _p(ws), nb, _stream()), "tsne_affinities")
+    return out
+
+
+def tsne_gradient(P, y, exaggeration=1.0, want_kl=True, *, grad=None, out=None):
+    """-> (grad (N, 2) fp32, out (3,) float64 = [KL, sum grad^2, Z]) of the t-SNE objective at y (N, 2) fp32 for the joint P
+    (g2v_tsne_gradient: one pass over P, float64 sums in a fixed order; KL is NaN with want_kl=False)."""
+    N = y.shape[0]
+    if tuple(y.shape) != (N, 2) or tuple(P.shape) != (N, N):
+        raise ValueError(f"tsne_gradient: y must be (N, 2) and P (N, N), got {tuple(y.shape)} and {tuple(P.shape)}")
+    if grad is None:
+        grad = torch.empty((N, 2), dtype=torch.float32, device=y.device)
+    if out is None:
+        out = torch.empty((3,), dtype=torch.float64, device=y.device)
+    lib = _lib_()
+    nb = int(lib.g2v_tsne_gradient_workspace(N))
+    ws = workspace(max(nb, 16), y.device, "tsne_grad")
+    check(lib.g2v_tsne_gradient(_p(_chk(P, name="P")), _p(_chk(y, name="y")), N, float(exaggeration), 1 if want_kl else 0,
+                                _p(_chk(grad, name="grad")), _p(_chk(out, torch.float64, "out")), _p(ws), nb, _stream()), "tsne_gradient")
+    return grad, out
+
+
+def tsne_update(y, velocity, gains, grad, momentum, learning_rate, gnorm2=None):
+    """One step of sklearn's _gradient_descent over y, velocity, gains (N, 2) fp32, in place (g2v_tsne_update); gnorm2: (1,) float64
+    that receives sum (gains grad)^2."""
+    N = y.shape[0]
+    for name, t in (("y", y), ("velocity", velocity), ("gains", gains), ("grad", grad)):
+        if tuple(_chk(t, name=name).shape) != (N, 2):
+            raise ValueError(f"tsne_update: {name} must be ({N}, 2), got {tuple(t.shape)}")
+    check(_lib_().g2v_tsne_update(_p(y), _p(velocity), _p(gains), _p(grad), N, float(momentum), float(learning_rate),
+                                  _p(None if gnorm2 is None else _chk(gnorm2, torch.float64, "gnorm2")), _stream()), "tsne_update")
+    return y

@@ -1077,6 +1077,41 @@ size_t g2v_silhouette_workspace(int64_t N, int E, int K);
 int g2v_silhouette_samples(const float* x, int64_t ld, const int64_t* labels, int64_t N, int E, int K, double* a, double* b,
                            double* s, int64_t* counts, double* out, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
 
+/* ---- exact t-SNE into the plane (tsne.hip; gesture2vec_amd/embedding.py) ------------------------------------------------------------
+ * The reference's 2-D maps of the codebook and of the chunk latents (train_autoencoder_VQVAE.py:450-505, Clustering.py:1046-1056:
+ * PCA(50) + sklearn.manifold.TSNE); the math is sklearn 1.7's exact method.  N <= g2v_tsne_max_rows() = 32768 rows (the joint P is
+ * dense: N x N fp32 with row stride N, 4 GiB at the limit; every offset is 64-bit), G2V_ERR_UNSUPPORTED beyond.
+ *
+ * g2v_tsne_affinities: x (N,d) fp32 with row stride ld >= d, ld % 4 == 0, 1 <= d <= 512; 0 < perplexity < N -> the joint P, symmetric
+ *   bit for bit, diagonal 0, every other entry >= DBL_EPSILON.  Squared distances |x_i|^2 + |x_j|^2 - 2 x_i.x_j with float64 norms and
+ *   Gram tiles from the exact-fp32 MFMA (chains of 32 columns, folded in float64), rounded to fp32 once; a pair with
+ *   d^2 < (|x_i|^2 + |x_j|^2) / 8 is re-evaluated as sum (x_i - x_j)^2 in float64 as g2v_silhouette_samples does (bitwise equal
+ *   rows: exactly 0).  Elsewhere d^2 carries ~3e-7 of the 32-column partial sums of x_i.x_j: centre rows that lie far from the
+ *   origin.  Per row, sklearn's
+ *   bisection of the precision in float64: beta = 1, doubled / halved while a bound is infinite, at most 100 steps, stop at
+ *   |H - log(perplexity)| <= 1e-5, a row sum of exactly 0 becomes 1e-8, the term j = i left out; the conditionals are kept as fp32.
+ *   P_ij = max((c_ij + c_ji) / sum(C + C^T), DBL_EPSILON), the sum in float64 in a fixed order.  P and workspace 16-byte aligned;
+ *   workspace: g2v_tsne_affinities_workspace(N, d) bytes (0 for an unsupported shape); its contents are not trusted across calls.
+ * g2v_tsne_gradient: P as above, y (N,2) fp32 (8-byte aligned), exaggeration > 0 -> grad (N,2) fp32 and out float64[3] =
+ *   { KL, sum grad^2 (of the fp32 values), Z } with p_ij = exaggeration P_ij, q_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} q_ij,
+ *     grad_i = 4 sum_j (p_ij - q_ij / Z) q_ij (y_i - y_j)      KL = sum_{i != j} p_ij log(max(p_ij, DBL_EPSILON) / (q_ij / Z))
+ *   (sklearn's _kl_divergence called with P * exaggeration; its clamp of q / Z at DBL_EPSILON is left out).  One pass over P; y_i - y_j
+ *   and q in fp32, the attractive and repulsive row sums, Z and the KL terms in float64, combined once Z is known.  want_kl == 0
+ *   skips the logarithms and stores NaN in out[0], as sklearn does.  workspace: g2v_tsne_gradient_workspace(N) bytes.
+ * g2v_tsne_update: one step of sklearn's _gradient_descent over y, velocity and gains (N,2) fp32, in its fp32 operation order:
+ *   gains += 0.2 where velocity * grad < 0, *= 0.8 elsewhere, floor 0.01; velocity = momentum velocity - learning_rate (gains grad);
+ *   y += velocity.  gnorm2 (may be NULL): float64[1] = sum (gains grad)^2, the norm its stop rule reads.
+ * No floating-point atomics anywhere: the same input gives the same bits. */
+int64_t g2v_tsne_max_rows(void);
+size_t g2v_tsne_affinities_workspace(int64_t N, int d);
+int g2v_tsne_affinities(const float* x, int64_t ld, int64_t N, int d, double perplexity, float* P, void* workspace,
+                        size_t workspace_bytes, g2v_stream_t stream);
+size_t g2v_tsne_gradient_workspace(int64_t N);
+int g2v_tsne_gradient(const float* P, const float* y, int64_t N, double exaggeration, int want_kl, float* grad, double* out,
+                      void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+int g2v_tsne_update(float* y, float* velocity, float* gains, const float* grad, int64_t N, float momentum, float learning_rate,
+                    double* gnorm2, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

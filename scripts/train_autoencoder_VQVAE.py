@@ -126,6 +126,20 @@ def evaluate_testset(test_data_loader, generator, loss_fn, args) -> float:
     return losses.avg
 
 
+def write_embedding_map(args, generator, epoch) -> None:
+    """--embedding-maps: the reference's plot_embedding (train_autoencoder_VQVAE.py:450-505: PCA(50) + TSNE(2, perplexity=30) of
+    vq_layer._embedding.weight) as data, <model_save_path>/plots/Embedding_Epoch(<epoch>).npz with `coords` (K, 2) where it saves
+    the .png.  As there, a codebook that cannot be mapped (no quantiser, no more rows than the perplexity) is skipped with a note."""
+    from gesture2vec_amd.embedding import codebook_map
+    try:
+        coords = codebook_map(generator)
+    except ValueError as e:
+        logging.info("embedding map of epoch {} skipped: {}".format(epoch, e))
+        return
+    os.makedirs(os.path.join(args.model_save_path, "plots"), exist_ok=True)
+    np.savez(os.path.join(args.model_save_path, "plots", "Embedding_Epoch({}).npz".format(epoch)), coords=coords.cpu().numpy())
+
+
 def train_epochs(args, train_data_loader, train_sim_dataset, test_data_loader, lang_model, pose_dim, trial_id=None):
     start = time.time()
     loss_meters = [AverageMeter("loss"), AverageMeter("var_loss")]
@@ -177,6 +191,8 @@ def train_epochs(args, train_data_loader, train_sim_dataset, test_data_loader, l
                  "resume": {"optim": {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in gen_optimizer.state_dict().items()},
                             "rng_counter": generator.engine().rng_counter.cpu().clone()}},
                 save_name)
+        if getattr(args, "embedding_maps", False) and _RANK == 0:
+            write_embedding_map(args, generator, epoch)
         iter_start_time = time.time()
         loss_epoch = AverageMeter("loss")
         for iter_idx, (encoded_input, encoded_output) in enumerate(train_data_loader, 0):
