@@ -1519,25 +1519,6 @@ extern "C" int g2v_linear_bwd_data(const float* dy, int64_t lddy, const float* w
   return G2V_OK;
 }
 
-extern "C" size_t g2v_linear_bwd_weight_workspace(int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0) return 0;
-  if ((M & 15) && M >= 4096 + 16) {      // ragged rows: the whole 16-row groups go through the kernels below as M & ~15 rows
-    const size_t a = g2v_linear_bwd_weight_workspace(M & ~15, K, N);
-    const size_t b = (size_t)tn_splits(M, K, N) * ((size_t)N * K + N) * sizeof(float);
-    return a > b ? a : b;
-  }
-  int splits = tn_splits(M, K, N);
-  for (int nr = 2; nr <= 4; nr += 2) {       // either row-range variant of the wave-autonomous path
-    const int wg = tn_wave_grid(M, K, N, false, nullptr, 1, nr);
-    if (wg > splits) splits = wg;
-  }
-  {
-    int gs = 0;
-    if (tn_gen_grid(M, K, N, false, 1, nullptr, nullptr, &gs) > 0 && gs > splits) splits = gs;
-  }
-  return (size_t)splits * ((size_t)N * K + N) * sizeof(float);
-}
-
 // ---- small M weight gradient (Part d at B = 128: 640 x 600 -> dW 600 x 200): one workgroup per 16 x 16 tile of dW ----------
 // dW[n][k] (+)= sum_m dy[m][n] xin[m][k], db[n] (+)= sum_m dy[m][n].  The four waves split the rows, each pulls both operands
 // straight from L2 as MFMA fragments (dword loads: 16 lanes x 4 B contiguous along n / k, 4 rows per MFMA; SMW_NB 16-row
@@ -2146,9 +2127,7 @@ extern "C" int g2v_linear_bwd_weight_fold_chain2(const float* w0, const float* w
   return G2V_OK;
 }
 
-// measured at the reference's own VQ-VAE.yml shape (B = 128, T = 20: 2432 / 2560 rows, 600 x 200): the LDS-tiled kernel + slab
-// pass 20.6 + 7 us per product, so the one-launch form keeps the rows BELOW 4096; from 4096 rows the output-blocked wave
-// kernel takes over (the soft quantiser's products at N = 4096: 512 x 128 22 us against 32, 128 x 128 16 against 31)
+// the one-launch kernels keep the rows BELOW 4096 (every threshold of this section and its measurement: DESIGN.md §3.6.1)
 static constexpr int g_smallm_wgrad_rows = 4095;
 template <int TN, int TK, int NW>
 static void smw_lds_launch(const SmallWgradBatch& sb, int64_t lddy, int64_t ldx, int M, int K, int N, int accumulate, int nprob,
@@ -2163,12 +2142,6 @@ static void smw_lds_launch(const SmallWgradBatch& sb, int64_t lddy, int64_t ldx,
                      lds, st, sb, lddy, ldx, M, K, N, accumulate, xpp);
 }
 
-
-// nprob problems of one shape: {dy, x, dw, db}[p].  The wave-autonomous path launches them together (grid.y = problem);
-// the LDS-tiled fallback runs them one after the other.  `slab_stride` floats of workspace per problem.
-struct WgradItem {
-  const float* dy; const float* x; float* dw; float* db;
-};
 // (dy_a + dy_b)^T x is served by the wave-autonomous kernel's two-addend instantiation: 64 x 135-shaped dW, whole 16-row
 // groups, more rows than the small-M kernel takes
 static bool wgrad_sum2_ok(int M, int K, int N) {
@@ -2176,188 +2149,258 @@ static bool wgrad_sum2_ok(int M, int K, int N) {
   return M > g_smallm_wgrad_rows && (M & 15) == 0 && cdiv(N, 16) == 4 && cdiv(K, 16) == 9 &&
          tn_wave_grid(M, K, N, false, &rpw, 1, 2) > 0;
 }
-static int wgrad_impl(const WgradItem* it, int nprob, int64_t lddy, int64_t ldx, int rows_inner, int64_t stride_outer,
+
+// Which kernel family a weight-gradient call runs on, and with which launch parameters: decided here, once, from the shape and
+// the flags (host arithmetic only: this is on the eager path of a launch-bound step).  wgrad_impl launches from it, the workspace
+// query takes its slab counts from it, g2v_linear_bwd_weight_route reports it.  The decision order: DESIGN.md §3.6.1.
+struct WgradPlan {
+  int route;                  // G2V_WGRAD_ROUTE_*; 0: a second addend on a shape wgrad_sum2_ok rejects
+  int tail_rows;              // ragged row count: the last M % 16 rows, added by gemm_tn_smallm_kernel<false> behind the main product
+  int M;                      // rows of the main product (the call's M - tail_rows): what every field below describes
+  bool bf3, mapped, vec2;     // wave-autonomous variants: bf16x3 products, row-mapped x, 8-byte operand loads
+  int xpp;                    // small routes: XCD-aware placement (smw_decode_grid), 0 = grid (groups, problems)
+  int splits;                 // slabs per problem; 0: the route writes dw / db itself, there is nothing to reduce
+  int rpw, nr;                // wave routes: rows per wave, row ranges per workgroup (tn_wave_body)
+  int gen_cfg, gen_nob;       // output-blocked: block shape and number of output blocks (tn_gen_grid)
+  int ntw, rows_per_split;    // LDS-tiled
+};
+// `align`: the largest power of two (up to 16) that divides every dy and x pointer of the call
+static WgradPlan wgrad_plan(int M, int K, int N, int nprob, int flags, bool keep, bool mapped, bool dual, int64_t lddy, int64_t ldx,
+                            int align) {
+  WgradPlan pl{};
+  pl.bf3 = (flags & G2V_WGRAD_BF16X3) != 0;
+  pl.mapped = mapped;
+  if (dual && !wgrad_sum2_ok(M, K, N)) return pl;
+  if ((M & 15) && M >= 4096 + 16 && !keep) {
+    pl.tail_rows = M & 15;
+    M -= pl.tail_rows;
+  }
+  pl.M = M;
+  const int tn = cdiv(N, 16), tk = cdiv(K, 16);
+  if (M <= g_smallm_wgrad_rows && !(mapped && keep) && !pl.bf3) {
+    pl.xpp = nprob > 1 && (8 % nprob) == 0 ? 8 / nprob : 0;      // the problems divide the 8 XCDs and there is more than one
+    const bool plain = !keep && !mapped && M >= 512;
+    if (plain && ((N | K | lddy | ldx) & 3) == 0 && (align & 15) == 0 && (int64_t)cdiv(tn, 2) * tk * nprob >= 256)
+      pl.route = G2V_WGRAD_ROUTE_SMALL_LDS;                      // (2 x 1 tiles per workgroup)
+    else if (plain && (int64_t)cdiv(tn, 2) * cdiv(tk, 2) * nprob >= 256)
+      pl.route = G2V_WGRAD_ROUTE_SMALL_RT;                       // (2 x 2)
+    else if (keep)
+      pl.route = G2V_WGRAD_ROUTE_SMALL_MASKED;
+    else
+      pl.route = M >= 512 && tn * tk * nprob <= 256 ? G2V_WGRAD_ROUTE_SMALL_WAVES16 : G2V_WGRAD_ROUTE_SMALL_TILE;
+    return pl;
+  }
+  pl.route = G2V_WGRAD_ROUTE_LDS_TILED;
+  pl.splits = tn_splits(M, K, N);
+  pl.rows_per_split = round_up(cdiv(M, pl.splits), TM);
+  pl.ntw = tn_ntw(N);
+  pl.nr = pl.bf3 ? 4 : 2;
+  int wg = tn_wave_grid(M, K, N, keep, &pl.rpw, nprob, pl.nr);
+  if (wg > 0) {
+    pl.route = dual ? G2V_WGRAD_ROUTE_WAVE_DUAL : G2V_WGRAD_ROUTE_WAVE;
+    // 8-byte vector operand loads need 8-byte-aligned rows on both sides and whole tiles
+    pl.vec2 = (N % 32 == 0) && (K % 32 == 0) && !mapped && (lddy % 2 == 0) && (ldx % 2 == 0) && (align & 7) == 0;
+  } else if (!pl.bf3 && (N > 64 || K > 64)) {      // shapes beyond one workgroup's accumulators: the output-blocked wave kernel
+    pl.gen_nob = tn_gen_grid(M, K, N, keep, nprob, &pl.gen_cfg, &pl.rpw, &wg);
+    if (pl.gen_nob > 0) pl.route = G2V_WGRAD_ROUTE_WAVE_GEN;
+  }
+  if (wg > 0) pl.splits = wg;
+  return pl;
+}
+
+template <int TN_, int TK_, int SN, int SK, int VW, bool BF, int NR, bool MP>
+static void tn_wave_launch_as(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
+                              hipStream_t st) {
+  const size_t lds = ((size_t)NR * TN_ * TK_ * 256 + 2 * NR * TN_ * 16) * sizeof(float);
+  (void)hipFuncSetAttribute((const void*)gemm_tn_wave_kernel<TN_, TK_, SN, SK, MP, VW, BF, NR>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((gemm_tn_wave_kernel<TN_, TK_, SN, SK, MP, VW, BF, NR>), dim3(pl.splits, nprob), dim3(128 * NR), lds, st, bt, lddy,
+                     xm, pl.M, K, N, pl.rpw);
+}
+template <int TN_, int TK_, int SN, int SK, int VW>
+static void tn_wave_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
+                           hipStream_t st) {
+  if (pl.bf3 && pl.mapped) tn_wave_launch_as<TN_, TK_, SN, SK, VW, true, 4, true>(pl, bt, lddy, xm, K, N, nprob, st);
+  else if (pl.bf3) tn_wave_launch_as<TN_, TK_, SN, SK, VW, true, 4, false>(pl, bt, lddy, xm, K, N, nprob, st);
+  else if (pl.mapped) tn_wave_launch_as<TN_, TK_, SN, SK, VW, false, 2, true>(pl, bt, lddy, xm, K, N, nprob, st);
+  else tn_wave_launch_as<TN_, TK_, SN, SK, VW, false, 2, false>(pl, bt, lddy, xm, K, N, nprob, st);
+}
+template <bool MP>
+static void tn_dual_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, hipStream_t st) {
+  const size_t lds = ((size_t)2 * 2 * 9 * 256 + 2 * 2 * 2 * 16) * sizeof(float);
+  (void)hipFuncSetAttribute((const void*)gemm_tn_wave_dual_kernel<MP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(gemm_tn_wave_dual_kernel<MP>, dim3(pl.splits, 1), dim3(256), lds, st, bt, lddy, xm, pl.M, K, N, pl.rpw);
+}
+template <int TN_, int TK_, bool MP>
+static void tn_gen_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
+                          hipStream_t st) {
+  const size_t lds = ((size_t)2 * TN_ * TK_ * 256 + 4 * TN_ * 16) * sizeof(float);
+  (void)hipFuncSetAttribute((const void*)gemm_tn_wave_gen_kernel<TN_, TK_, 2, 1, MP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds);
+  hipLaunchKernelGGL((gemm_tn_wave_gen_kernel<TN_, TK_, 2, 1, MP>), dim3(pl.splits, nprob, pl.gen_nob), dim3(256), lds, st, bt, lddy, xm,
+                     pl.M, K, N, pl.rpw);
+}
+// the operands of the small kernels: the items from row `row0` on (a row-mapped x keeps its base: the kernel adds the rows)
+static SmallWgradBatch smw_batch(const g2v_wgrad_item* it, int nprob, int64_t dy_off, int64_t x_off) {
+  SmallWgradBatch sb;
+  for (int p = 0; p < G2V_TN_BATCH; ++p) {
+    const int pp = p < nprob ? p : 0;
+    sb.dy[p] = it[pp].dy + dy_off; sb.x[p] = it[pp].x + x_off; sb.dw[p] = it[pp].dw; sb.db[p] = it[pp].db;
+  }
+  return sb;
+}
+
+// nprob problems of one shape: make the plan, launch it, reduce its slabs (`slab_stride` floats of workspace per problem) or
+// record the reduction in `pend`.  The wave routes launch the problems together (grid.y = problem); the LDS-tiled one runs them
+// one after the other.
+static int wgrad_impl(const g2v_wgrad_item* it, int nprob, int64_t lddy, int64_t ldx, int rows_inner, int64_t stride_outer,
                       int64_t stride_inner, const uint8_t* x_keep, float x_scale, int M, int K, int N, int flags,
                       float* workspace, g2v_stream_t stream, const float* dy2 = nullptr, g2v_wgrad_pending* pend = nullptr) {
-  if (pend) pend->nprob = 0;            // (paths without a slab reduction, or that need dw finished at once, leave it empty)
-  if (dy2 && !wgrad_sum2_ok(M, K, N)) {
+  if (pend) pend->nprob = 0;            // (routes without a slab reduction, or that need dw finished at once, leave it empty)
+  uintptr_t bits = 0;
+  for (int p = 0; p < nprob; ++p) bits |= reinterpret_cast<uintptr_t>(it[p].dy) | reinterpret_cast<uintptr_t>(it[p].x);
+  const int low = (int)(bits & 15);
+  const WgradPlan pl = wgrad_plan(M, K, N, nprob, flags, x_keep != nullptr, rows_inner > 0, dy2 != nullptr, lddy, ldx,
+                                  low ? (low & -low) : 16);
+  if (!pl.route) {
     set_error("g2v_linear_bwd_weight_sum2: shape not served (see g2v_linear_bwd_weight_sum2_ok)");
     return G2V_ERR_UNSUPPORTED;
   }
-  const int accumulate = flags & G2V_WGRAD_ACCUMULATE;
-  const bool bf3 = (flags & G2V_WGRAD_BF16X3) != 0;
-  if ((M & 15) && M >= 4096 + 16 && !x_keep) {
-    // ragged row count (T B not a multiple of 16: B = 4100): the wave-autonomous kernels take the whole 16-row groups, the
-    // M % 16 leftover rows are added by the small-M kernel (accumulate) -- instead of the whole product falling back to the
-    // LDS-tiled kernel (95 vs 35-45 us per product at the BASELINE shape)
-    const int Mt = M & 15, Mm = M - Mt;
-    const int rc = wgrad_impl(it, nprob, lddy, ldx, rows_inner, stride_outer, stride_inner, nullptr, 1.0f, Mm, K, N, flags,
-                              workspace, stream);
-    if (rc != G2V_OK) return rc;
-    const bool mapped = rows_inner > 0;
-    SmallWgradBatch sb;
-    for (int p = 0; p < G2V_TN_BATCH; ++p) {
-      const int pp = p < nprob ? p : 0;
-      sb.dy[p] = it[pp].dy + (int64_t)Mm * lddy; sb.x[p] = mapped ? it[pp].x : it[pp].x + (int64_t)Mm * ldx;
-      sb.dw[p] = it[pp].dw; sb.db[p] = it[pp].db;
+  const hipStream_t st = (hipStream_t)stream;
+  const int accumulate = flags & G2V_WGRAD_ACCUMULATE, tn = cdiv(N, 16), tk = cdiv(K, 16);
+  const RowMap xm{ldx, rows_inner, stride_outer, stride_inner};
+  if (!pl.splits) {
+    const SmallWgradBatch sb = smw_batch(it, nprob, 0, 0);
+    const RowMap xm1 = pl.mapped ? xm : RowMap{0, 0, 0, 0};      // (a row-mapped x: the one-tile kernels)
+    auto grid = [&](int groups) { return pl.xpp ? dim3(8 * cdiv(groups, pl.xpp), 1) : dim3(groups, nprob); };
+    switch (pl.route) {
+      case G2V_WGRAD_ROUTE_SMALL_LDS:
+        smw_lds_launch<2, 1, 4>(sb, lddy, ldx, M, K, N, accumulate, nprob, pl.xpp, st);
+        break;
+      case G2V_WGRAD_ROUTE_SMALL_RT:
+        hipLaunchKernelGGL((gemm_tn_smallm_rt_kernel<2, 2, 4>), grid(cdiv(tn, 2) * cdiv(tk, 2)), dim3(256), 0, st, sb, lddy, ldx, M, K, N,
+                           accumulate, pl.xpp);
+        break;
+      case G2V_WGRAD_ROUTE_SMALL_MASKED:
+        hipLaunchKernelGGL(gemm_tn_smallm_kernel<true>, grid(tn * tk), dim3(256), 0, st, sb, lddy, ldx, x_keep, x_scale, M, K, N,
+                           accumulate, RowMap{0, 0, 0, 0}, 0, pl.xpp);
+        break;
+      case G2V_WGRAD_ROUTE_SMALL_WAVES16:
+        hipLaunchKernelGGL((gemm_tn_smallm_kernel<false, 16, 4>), grid(tn * tk), dim3(1024), 0, st, sb, lddy, ldx, x_keep, x_scale, M, K,
+                           N, accumulate, xm1, 0, pl.xpp);
+        break;
+      default:
+        hipLaunchKernelGGL(gemm_tn_smallm_kernel<false>, grid(tn * tk), dim3(256), 0, st, sb, lddy, ldx, x_keep, x_scale, M, K, N,
+                           accumulate, xm1, 0, pl.xpp);
     }
-    hipLaunchKernelGGL(gemm_tn_smallm_kernel<false>, dim3(cdiv(N, 16) * cdiv(K, 16), nprob), dim3(256), 0, (hipStream_t)stream, sb,
-                       lddy, ldx, (const uint8_t*)nullptr, 1.0f, Mt, K, N, 1, RowMap{ldx, rows_inner, stride_outer, stride_inner},
-                       mapped ? Mm : 0);
     G2V_CHECK_LAUNCH();
     return G2V_OK;
   }
-  if (M <= g_smallm_wgrad_rows && (rows_inner == 0 || !x_keep) && !bf3) {
-    const bool mapped = rows_inner > 0;      // (a row-mapped x: the one-tile kernels)
-    const RowMap xm1 = mapped ? RowMap{ldx, rows_inner, stride_outer, stride_inner} : RowMap{0, 0, 0, 0};
-    SmallWgradBatch sb;
-    for (int p = 0; p < G2V_TN_BATCH; ++p) {
-      const int pp = p < nprob ? p : 0;
-      sb.dy[p] = it[pp].dy; sb.x[p] = it[pp].x; sb.dw[p] = it[pp].dw; sb.db[p] = it[pp].db;
-    }
-    // XCD-aware placement (smw_decode_grid) when the problems divide the 8 XCDs and there is more than one
-    const int xpp = nprob > 1 && (8 % nprob) == 0 ? 8 / nprob : 0;
-    const int groups1 = cdiv(N, 16) * cdiv(K, 16), groups2 = cdiv(cdiv(N, 16), 2) * cdiv(cdiv(K, 16), 2);
-    const dim3 grid = xpp ? dim3(8 * cdiv(groups1, xpp), 1) : dim3(groups1, nprob);
-    // enough tiles that 2 x 2 of them per workgroup still cover the chip, enough rows that the streaming dominates (four
-    // 600 x 200 products at 2432 rows: 72 us against 94; 4 x 2, 3 x 3 and 4 x 4 tiles measured within +-5 % of 2 x 2)
-    bool vec_ok = !x_keep && !mapped && M >= 512 && ((N | K | lddy | ldx) & 3) == 0;
-    for (int p2 = 0; p2 < nprob && vec_ok; ++p2)
-      vec_ok = ((reinterpret_cast<uintptr_t>(it[p2].dy) | reinterpret_cast<uintptr_t>(it[p2].x)) & 15) == 0;
-    if (vec_ok && (int64_t)cdiv(cdiv(N, 16), 2) * cdiv(K, 16) * nprob >= 256) {      // (2 x 1 tiles per workgroup)
-      // float4-aligned operands: the LDS-staged form (four 600 x 200 products at 2560 rows: 53 us against 70, bitwise the same dW)
-      // (NW = 8 waves per workgroup, 70 KB of LDS: 60 us against 54 alone, and starved beside the GRU backward cluster -- 110 us;
-      //  the counters of the 4-wave form: MFMA pipe 32 % busy, waves waiting on memory 52 % of their time, no LDS bank conflicts:
-      //  profiles/r05_ai_pmc_smallm_wgrad_4waves.json, r05_aj_lds_wgrad_8waves_ab.log)
-      // 2 x 1 tiles: two / four 600 x 200 products at 2560 rows 27.8 / 50.9 us (2 x 2: 38.6 / 56.6, 1 x 1: 34.8 / 67.1; r05_al log)
-      smw_lds_launch<2, 1, 4>(sb, lddy, ldx, M, K, N, accumulate, nprob, xpp, (hipStream_t)stream);
-    } else if (!x_keep && !mapped && M >= 512 && (int64_t)cdiv(cdiv(N, 16), 2) * cdiv(cdiv(K, 16), 2) * nprob >= 256)
-      hipLaunchKernelGGL((gemm_tn_smallm_rt_kernel<2, 2, 4>), xpp ? dim3(8 * cdiv(groups2, xpp), 1) : dim3(groups2, nprob), dim3(256), 0,
-                         (hipStream_t)stream, sb, lddy, ldx, M, K, N, accumulate, xpp);
-    else if (x_keep)
-      hipLaunchKernelGGL(gemm_tn_smallm_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, sb, lddy, ldx, x_keep, x_scale,
-                         M, K, N, accumulate, RowMap{0, 0, 0, 0}, 0, xpp);
-    else if (M >= 512 && groups1 * nprob <= 256)      // few tiles, many rows: 16 waves split the rows (2560 rows: 30 -> 19 us)
-      hipLaunchKernelGGL((gemm_tn_smallm_kernel<false, 16, 4>), grid, dim3(1024), 0, (hipStream_t)stream, sb, lddy, ldx, x_keep,
-                         x_scale, M, K, N, accumulate, xm1, 0, xpp);
-    else
-      hipLaunchKernelGGL(gemm_tn_smallm_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, sb, lddy, ldx, x_keep, x_scale,
-                         M, K, N, accumulate, xm1, 0, xpp);
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  int splits = tn_splits(M, K, N);
-  int rows_per_split = cdiv(M, splits);
-  rows_per_split = round_up(rows_per_split, TM);
-  RowMap xm{ldx, rows_inner, stride_outer, stride_inner};
-  int rpw = 0;
-  const int nr = bf3 ? 4 : 2;                  // row ranges (waves per tile group) per workgroup, see tn_wave_body
-  int wg = tn_wave_grid(M, K, N, x_keep != nullptr, &rpw, nprob, nr);
-  int gen_cfg = 0, gen_nob = 0;
-  if (wg == 0 && !bf3 && (N > 64 || K > 64)) {  // shapes beyond one workgroup's accumulators: output-blocked wave kernel
-    int gs = 0;
-    gen_nob = tn_gen_grid(M, K, N, x_keep != nullptr, nprob, &gen_cfg, &rpw, &gs);
-    if (gen_nob > 0) wg = gs;
-  }
-  if (wg > 0) splits = wg;
+  const int Mm = pl.M, splits = pl.splits;
   const size_t slab_stride = (size_t)splits * ((size_t)N * K + N);
   const int64_t n = (int64_t)N * K;
   bool any_db = false;
   for (int p = 0; p < nprob; ++p) any_db = any_db || it[p].db;
   auto slab_of = [&](int p) { return workspace + (size_t)p * slab_stride; };
   auto slab_db_of = [&](int p) { return it[p].db ? slab_of(p) + (size_t)splits * N * K : (float*)nullptr; };
-  if (wg > 0) {
+  if (pl.route == G2V_WGRAD_ROUTE_LDS_TILED) {
+    const auto kernel = pl.ntw == 1 ? gemm_tn_kernel<1> : pl.ntw == 2 ? gemm_tn_kernel<2> : gemm_tn_kernel<3>;
+    for (int p = 0; p < nprob; ++p)
+      hipLaunchKernelGGL(kernel, dim3(cdiv(N, 64 * pl.ntw), cdiv(K, 64), splits), dim3(256), 0, st, it[p].dy, lddy, it[p].x, xm, x_keep,
+                         pl.tail_rows ? 1.0f : x_scale, slab_of(p), slab_db_of(p), Mm, K, N, pl.rows_per_split);
+  } else {
     TnBatch bt;
-    bool vec2 = (N % 32 == 0) && (K % 32 == 0) && rows_inner == 0 && (lddy % 2 == 0) && (ldx % 2 == 0);
-    bool all_db = true;
     for (int p = 0; p < G2V_TN_BATCH; ++p) {
       const int pp = p < nprob ? p : 0;
       bt.dy[p] = it[pp].dy; bt.x[p] = it[pp].x; bt.slab[p] = slab_of(pp); bt.slab_db[p] = slab_db_of(pp);
       bt.dy2[p] = dy2;
-      vec2 = vec2 && (reinterpret_cast<uintptr_t>(it[pp].dy) % 8 == 0) && (reinterpret_cast<uintptr_t>(it[pp].x) % 8 == 0);
-      all_db = all_db && (it[pp].db != nullptr);
     }
-    (void)all_db;
-    const int tn = cdiv(N, 16), tk = cdiv(K, 16);
-    if (gen_nob > 0) {
-#define G2V_TNG(TN_, TK_, MP)                                                                                             \
-  do {                                                                                                                   \
-    const size_t lds = ((size_t)2 * TN_ * TK_ * 256 + 4 * TN_ * 16) * sizeof(float);                                      \
-    (void)hipFuncSetAttribute((const void*)gemm_tn_wave_gen_kernel<TN_, TK_, 2, 1, MP>,                                  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                     \
-    hipLaunchKernelGGL((gemm_tn_wave_gen_kernel<TN_, TK_, 2, 1, MP>), dim3(wg, nprob, gen_nob), dim3(256), lds,          \
-                       (hipStream_t)stream, bt, lddy, xm, M, K, N, rpw);                                                 \
-  } while (0)
-      if (gen_cfg == 0) { if (rows_inner > 0) G2V_TNG(6, 4, true); else G2V_TNG(6, 4, false); }
-      else { if (rows_inner > 0) G2V_TNG(4, 7, true); else G2V_TNG(4, 7, false); }
-#undef G2V_TNG
+    if (pl.route == G2V_WGRAD_ROUTE_WAVE_GEN) {
+      if (pl.gen_cfg == 0 && pl.mapped) tn_gen_launch<6, 4, true>(pl, bt, lddy, xm, K, N, nprob, st);
+      else if (pl.gen_cfg == 0) tn_gen_launch<6, 4, false>(pl, bt, lddy, xm, K, N, nprob, st);
+      else if (pl.mapped) tn_gen_launch<4, 7, true>(pl, bt, lddy, xm, K, N, nprob, st);
+      else tn_gen_launch<4, 7, false>(pl, bt, lddy, xm, K, N, nprob, st);
+    } else if (pl.route == G2V_WGRAD_ROUTE_WAVE_DUAL) {
+      if (pl.mapped) tn_dual_launch<true>(pl, bt, lddy, xm, K, N, st);
+      else tn_dual_launch<false>(pl, bt, lddy, xm, K, N, st);
+    } else if (tn == 12 && tk == 4) {
+      if (pl.vec2) tn_wave_launch<6, 4, 2, 1, 2>(pl, bt, lddy, xm, K, N, nprob, st);
+      else tn_wave_launch<6, 4, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
+    } else if (tn == 4 && tk == 9) {
+      tn_wave_launch<2, 9, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
+    } else if (tn == 9 && tk == 4) {
+      tn_wave_launch<9, 2, 1, 2, 1>(pl, bt, lddy, xm, K, N, nprob, st);
     } else {
-#define G2V_TNW2(TN_, TK_, SN, SK, VW, BF, NR, MP)                                                                       \
-  do {                                                                                                                   \
-    const size_t lds = ((size_t)NR * TN_ * TK_ * 256 + 2 * NR * TN_ * 16) * sizeof(float);                                \
-    (void)hipFuncSetAttribute((const void*)gemm_tn_wave_kernel<TN_, TK_, SN, SK, MP, VW, BF, NR>,                        \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                     \
-    hipLaunchKernelGGL((gemm_tn_wave_kernel<TN_, TK_, SN, SK, MP, VW, BF, NR>), dim3(wg, nprob), dim3(128 * NR), lds,    \
-                       (hipStream_t)stream, bt, lddy, xm, M, K, N, rpw);                                                 \
-  } while (0)
-#define G2V_TNW(TN_, TK_, SN, SK, VW)                                                                                    \
-  do {                                                                                                                   \
-    if (bf3) { if (rows_inner > 0) G2V_TNW2(TN_, TK_, SN, SK, VW, true, 4, true); else G2V_TNW2(TN_, TK_, SN, SK, VW, true, 4, false); } \
-    else { if (rows_inner > 0) G2V_TNW2(TN_, TK_, SN, SK, VW, false, 2, true); else G2V_TNW2(TN_, TK_, SN, SK, VW, false, 2, false); }  \
-  } while (0)
-    // 8-byte vector operand loads need 8-byte-aligned rows on both sides and whole tiles (checked above)
-    if (dy2) {
-      const size_t lds = ((size_t)2 * 2 * 9 * 256 + 2 * 2 * 2 * 16) * sizeof(float);
-      if (rows_inner > 0) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_wave_dual_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(gemm_tn_wave_dual_kernel<true>, dim3(wg, 1), dim3(256), lds, (hipStream_t)stream, bt, lddy, xm, M, K, N, rpw);
-      } else {
-        (void)hipFuncSetAttribute((const void*)gemm_tn_wave_dual_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(gemm_tn_wave_dual_kernel<false>, dim3(wg, 1), dim3(256), lds, (hipStream_t)stream, bt, lddy, xm, M, K, N, rpw);
-      }
+      if (pl.vec2) tn_wave_launch<2, 4, 2, 1, 2>(pl, bt, lddy, xm, K, N, nprob, st);
+      else tn_wave_launch<2, 4, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
     }
-    else if (tn == 12 && tk == 4) { if (vec2) G2V_TNW(6, 4, 2, 1, 2); else G2V_TNW(6, 4, 2, 1, 1); }
-    else if (tn == 4 && tk == 9) G2V_TNW(2, 9, 2, 1, 1);
-    else if (tn == 9 && tk == 4) G2V_TNW(9, 2, 1, 2, 1);
-    else { if (vec2) G2V_TNW(2, 4, 2, 1, 2); else G2V_TNW(2, 4, 2, 1, 1); }
-#undef G2V_TNW
-#undef G2V_TNW2
-    }
-    G2V_CHECK_LAUNCH();
-  } else {
-    const int ntw = tn_ntw(N);
-    dim3 grid(cdiv(N, 64 * ntw), cdiv(K, 64), splits);
-    for (int p = 0; p < nprob; ++p) {
-      if (ntw == 1)
-        hipLaunchKernelGGL(gemm_tn_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, it[p].dy, lddy, it[p].x, xm, x_keep,
-                           x_scale, slab_of(p), slab_db_of(p), M, K, N, rows_per_split);
-      else if (ntw == 2)
-        hipLaunchKernelGGL(gemm_tn_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, it[p].dy, lddy, it[p].x, xm, x_keep,
-                           x_scale, slab_of(p), slab_db_of(p), M, K, N, rows_per_split);
-      else
-        hipLaunchKernelGGL(gemm_tn_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, it[p].dy, lddy, it[p].x, xm, x_keep,
-                           x_scale, slab_of(p), slab_db_of(p), M, K, N, rows_per_split);
-    }
-    G2V_CHECK_LAUNCH();
   }
-  // one launch reduces the weight slabs and (where requested) the bias slabs of every problem
-  SlabBatch sb;
-  for (int p = 0; p < G2V_TN_BATCH; ++p) {
-    const int pp = p < nprob ? p : 0;
-    sb.slab_a[p] = slab_of(pp); sb.out_a[p] = it[pp].dw; sb.slab_b[p] = slab_db_of(pp); sb.out_b[p] = it[pp].db;
-  }
-  if (pend) {       // G2V_WGRAD_DEFER_REDUCE: the caller reduces later (g2v_linear_bwd_weight_reduce); the slabs stay in `workspace`
+  G2V_CHECK_LAUNCH();
+  if (pend && !pl.tail_rows) {       // the caller reduces later (g2v_linear_bwd_weight_reduce); the slabs stay in `workspace`
     for (int p = 0; p < nprob; ++p) {
       pend->slab_w[p] = slab_of(p); pend->out_w[p] = it[p].dw; pend->slab_b[p] = slab_db_of(p); pend->out_b[p] = it[p].db;
     }
     pend->n = n; pend->nb = N; pend->nsplit = splits; pend->nprob = nprob; pend->accumulate = accumulate;
     return G2V_OK;
   }
-  // problems without a bias gradient: their bias blocks find slab_b == nullptr and return
-  hipLaunchKernelGGL(slab_reduce2_kernel, dim3(cdiv(n, 32) + (any_db ? cdiv(N, 32) : 0), nprob), dim3(256), 0, (hipStream_t)stream,
-                     sb, n, (int64_t)N, splits, accumulate, cdiv(n, 32));
+  // one launch reduces the weight slabs and (where requested) the bias slabs of every problem; problems without a bias gradient:
+  // their bias blocks find slab_b == nullptr and return
+  SlabBatch sb;
+  for (int p = 0; p < G2V_TN_BATCH; ++p) {
+    const int pp = p < nprob ? p : 0;
+    sb.slab_a[p] = slab_of(pp); sb.out_a[p] = it[pp].dw; sb.slab_b[p] = slab_db_of(pp); sb.out_b[p] = it[pp].db;
+  }
+  hipLaunchKernelGGL(slab_reduce2_kernel, dim3(cdiv(n, 32) + (any_db ? cdiv(N, 32) : 0), nprob), dim3(256), 0, st, sb, n, (int64_t)N,
+                     splits, accumulate, cdiv(n, 32));
   G2V_CHECK_LAUNCH();
+  if (pl.tail_rows) {                // the M % 16 leftover rows, added to the reduced dw / db
+    const SmallWgradBatch tail = smw_batch(it, nprob, (int64_t)Mm * lddy, pl.mapped ? 0 : (int64_t)Mm * ldx);
+    hipLaunchKernelGGL(gemm_tn_smallm_kernel<false>, dim3(tn * tk, nprob), dim3(256), 0, st, tail, lddy, ldx, (const uint8_t*)nullptr,
+                       1.0f, pl.tail_rows, K, N, 1, xm, pl.mapped ? Mm : 0);
+    G2V_CHECK_LAUNCH();
+  }
   return G2V_OK;
+}
+
+// what the entry points share behind their own argument checks: complete items, a workspace of nprob slab sets, the plan
+static int wgrad_entry(const char* fn, const g2v_wgrad_item* items, int nprob, int64_t lddy, int64_t ldx, int rows_inner,
+                       int64_t stride_outer, int64_t stride_inner, const uint8_t* x_keep, float x_scale, int M, int K, int N, int flags,
+                       void* workspace, size_t workspace_bytes, g2v_stream_t stream, const float* dy2 = nullptr,
+                       g2v_wgrad_pending* pend = nullptr) {
+  for (int p = 0; p < nprob; ++p)
+    if (!(items[p].dy && items[p].x && items[p].dw)) {
+      set_error("%s: null pointer", fn);
+      return G2V_ERR_ARG;
+    }
+  if (workspace_bytes < (size_t)nprob * g2v_linear_bwd_weight_workspace(M, K, N)) {
+    set_error("%s: workspace too small", fn);
+    return G2V_ERR_WORKSPACE;
+  }
+  return wgrad_impl(items, nprob, lddy, ldx, rows_inner, stride_outer, stride_inner, x_keep, x_scale, M, K, N, flags,
+                    (float*)workspace, stream, dy2, pend);
+}
+
+// the most slabs of any plan one product of this shape can get (bf16x3 or not, keep mask or not), as bytes
+extern "C" size_t g2v_linear_bwd_weight_workspace(int M, int K, int N) {
+  if (M <= 0 || K <= 0 || N <= 0) return 0;
+  int splits = 0, Mm = M;
+  for (int v = 0; v < 4; ++v) {
+    const WgradPlan pl = wgrad_plan(M, K, N, 1, v & 1 ? G2V_WGRAD_BF16X3 : 0, (v & 2) != 0, false, false, N, K, 16);
+    if (pl.splits > splits) splits = pl.splits;
+    if (pl.M < Mm) Mm = pl.M;
+  }
+  // ... and the output-blocked grid also where that kernel is never chosen (N, K <= 64 outside the wave-autonomous shapes): the
+  // bound has always included it, and callers' buffers are sized by it
+  int gs = 0;
+  if (tn_gen_grid(Mm, K, N, false, 1, nullptr, nullptr, &gs) > 0 && gs > splits) splits = gs;
+  return (size_t)splits * ((size_t)N * K + N) * sizeof(float);
+}
+
+extern "C" int g2v_linear_bwd_weight_route(int M, int K, int N, int nprob, int flags, int has_keep, int mapped, int has_dy_b,
+                                           int64_t lddy, int64_t ldx, int align) {
+  if (M <= 0 || K <= 0 || N <= 0 || nprob < 1 || nprob > G2V_TN_BATCH) return 0;
+  const WgradPlan pl = wgrad_plan(M, K, N, nprob, flags, has_keep != 0, mapped != 0, has_dy_b != 0, lddy, ldx, align);
+  return pl.route | (pl.tail_rows ? G2V_WGRAD_ROUTE_RAGGED_TAIL : 0);
 }
 
 extern "C" int g2v_linear_bwd_weight(const float* dy, int64_t lddy, const float* x, int64_t ldx, int rows_inner,
@@ -2366,13 +2409,9 @@ extern "C" int g2v_linear_bwd_weight(const float* dy, int64_t lddy, const float*
                                      size_t workspace_bytes, g2v_stream_t stream) {
   G2V_REQUIRE(dy && x && dw && workspace, "null pointer");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0, "non-positive size");
-  if (workspace_bytes < g2v_linear_bwd_weight_workspace(M, K, N)) {
-    set_error("g2v_linear_bwd_weight: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  const WgradItem item{dy, x, dw, db};
-  return wgrad_impl(&item, 1, lddy, ldx, rows_inner, stride_outer, stride_inner, x_keep, x_scale, M, K, N, accumulate,
-                    (float*)workspace, stream);
+  const g2v_wgrad_item item{dy, x, dw, db};
+  return wgrad_entry(__func__, &item, 1, lddy, ldx, rows_inner, stride_outer, stride_inner, x_keep, x_scale, M, K, N, accumulate,
+                     workspace, workspace_bytes, stream);
 }
 
 extern "C" int g2v_linear_bwd_weight_sum2_ok(int M, int K, int N) { return wgrad_sum2_ok(M, K, N) ? 1 : 0; }
@@ -2383,13 +2422,9 @@ extern "C" int g2v_linear_bwd_weight_sum2(const float* dy_a, const float* dy_b, 
                                           g2v_stream_t stream) {
   G2V_REQUIRE(dy_a && dy_b && x && dw && workspace, "null pointer");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0, "non-positive size");
-  if (workspace_bytes < g2v_linear_bwd_weight_workspace(M, K, N)) {
-    set_error("g2v_linear_bwd_weight_sum2: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  const WgradItem item{dy_a, x, dw, db};
-  return wgrad_impl(&item, 1, lddy, ldx, rows_inner, stride_outer, stride_inner, nullptr, 1.0f, M, K, N,
-                    accumulate ? G2V_WGRAD_ACCUMULATE : 0, (float*)workspace, stream, dy_b);
+  const g2v_wgrad_item item{dy_a, x, dw, db};
+  return wgrad_entry(__func__, &item, 1, lddy, ldx, rows_inner, stride_outer, stride_inner, nullptr, 1.0f, M, K, N,
+                     accumulate ? G2V_WGRAD_ACCUMULATE : 0, workspace, workspace_bytes, stream, dy_b);
 }
 
 extern "C" int g2v_linear_bwd_weight_batch(const g2v_wgrad_item* items, int nprob, int64_t lddy, int64_t ldx, int M, int K,
@@ -2397,16 +2432,7 @@ extern "C" int g2v_linear_bwd_weight_batch(const g2v_wgrad_item* items, int npro
   G2V_REQUIRE(items && workspace, "null pointer");
   G2V_REQUIRE(nprob >= 1 && nprob <= G2V_TN_BATCH, "1..4 problems per call");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0, "non-positive size");
-  WgradItem it[G2V_TN_BATCH];
-  for (int p = 0; p < nprob; ++p) {
-    G2V_REQUIRE(items[p].dy && items[p].x && items[p].dw, "null pointer");
-    it[p] = WgradItem{items[p].dy, items[p].x, items[p].dw, items[p].db};
-  }
-  if (workspace_bytes < (size_t)nprob * g2v_linear_bwd_weight_workspace(M, K, N)) {
-    set_error("g2v_linear_bwd_weight_batch: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  return wgrad_impl(it, nprob, lddy, ldx, 0, 0, 0, nullptr, 1.0f, M, K, N, flags, (float*)workspace, stream);
+  return wgrad_entry(__func__, items, nprob, lddy, ldx, 0, 0, 0, nullptr, 1.0f, M, K, N, flags, workspace, workspace_bytes, stream);
 }
 extern "C" int g2v_linear_bwd_weight_batch_mapped(const g2v_wgrad_item* items, int nprob, int64_t lddy, int64_t ldx, int rows_inner,
                                                   int64_t stride_outer, int64_t stride_inner, int M, int K, int N, int flags,
@@ -2414,21 +2440,12 @@ extern "C" int g2v_linear_bwd_weight_batch_mapped(const g2v_wgrad_item* items, i
   G2V_REQUIRE(items && workspace, "null pointer");
   G2V_REQUIRE(nprob >= 1 && nprob <= G2V_TN_BATCH, "1..4 problems per call");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0 && rows_inner >= 0, "bad size");
-  WgradItem it[G2V_TN_BATCH];
-  for (int p = 0; p < nprob; ++p) {
-    G2V_REQUIRE(items[p].dy && items[p].x && items[p].dw, "null pointer");
-    it[p] = WgradItem{items[p].dy, items[p].x, items[p].dw, items[p].db};
-  }
-  if (workspace_bytes < (size_t)nprob * g2v_linear_bwd_weight_workspace(M, K, N)) {
-    set_error("g2v_linear_bwd_weight_batch_mapped: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  return wgrad_impl(it, nprob, lddy, ldx, rows_inner, stride_outer, stride_inner, nullptr, 1.0f, M, K, N, flags, (float*)workspace,
-                    stream);
+  return wgrad_entry(__func__, items, nprob, lddy, ldx, rows_inner, stride_outer, stride_inner, nullptr, 1.0f, M, K, N, flags,
+                     workspace, workspace_bytes, stream);
 }
 
 // One call for every weight-gradient form (a single product: nprob = 1; the batch; the row-mapped batch; (dy_a + dy_b)^T x: dy_b)
-// whose slab reduction is left to the caller: `pending` describes it (empty when the shape's path has none -- small row counts --
+// whose slab reduction is left to the caller: `pending` describes it (empty when the shape's route has none -- small row counts --
 // or needs dw at once -- ragged row counts, reduced here), g2v_linear_bwd_weight_reduce runs up to G2V_WGRAD_PENDING_MAX of them
 // in one launch.  The slabs live in `workspace` until then: one workspace per pending call.
 extern "C" int g2v_linear_bwd_weight_deferred(const g2v_wgrad_item* items, int nprob, int64_t lddy, int64_t ldx, int rows_inner,
@@ -2438,17 +2455,8 @@ extern "C" int g2v_linear_bwd_weight_deferred(const g2v_wgrad_item* items, int n
   G2V_REQUIRE(items && workspace && pending, "null pointer");
   G2V_REQUIRE(nprob >= 1 && nprob <= G2V_TN_BATCH && (!dy_b || nprob == 1), "1..4 problems per call (1 with dy_b)");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0 && rows_inner >= 0, "bad size");
-  WgradItem it[G2V_TN_BATCH];
-  for (int p = 0; p < nprob; ++p) {
-    G2V_REQUIRE(items[p].dy && items[p].x && items[p].dw, "null pointer");
-    it[p] = WgradItem{items[p].dy, items[p].x, items[p].dw, items[p].db};
-  }
-  if (workspace_bytes < (size_t)nprob * g2v_linear_bwd_weight_workspace(M, K, N)) {
-    set_error("g2v_linear_bwd_weight_deferred: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  return wgrad_impl(it, nprob, lddy, ldx, rows_inner, stride_outer, stride_inner, nullptr, 1.0f, M, K, N, flags, (float*)workspace,
-                    stream, dy_b, pending);
+  return wgrad_entry(__func__, items, nprob, lddy, ldx, rows_inner, stride_outer, stride_inner, nullptr, 1.0f, M, K, N, flags,
+                     workspace, workspace_bytes, stream, dy_b, pending);
 }
 
 extern "C" int g2v_linear_bwd_weight_reduce(const g2v_wgrad_pending* pending, int count, g2v_stream_t stream) {

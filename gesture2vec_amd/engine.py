@@ -83,36 +83,6 @@ def trainable_layout(D: int, H: int, L: int):
     return out
 
 
-class _DeferredReductions:
-    """The slab reductions of one branch's weight-gradient products, held back and run as ONE launch (include/g2v.h:
-    g2v_linear_bwd_weight_deferred / _reduce).  Every product gets a region of `ws` of its own (its slabs live there until
-    `flush`).  Round 6: a chain of immediate calls made every product wait for the reduction of the one in front of it, and
-    beside the encoder's BPTT kernel -- whose two workgroups per CU leave a late-dispatched kernel no registers -- those
-    reductions took 17-95 us instead of 5 (profiles/r05_az_step_timeline.txt: 133 us of them on the decoder branch's chain)."""
-
-    def __init__(self, eng, ws: torch.Tensor):
-        self.eng, self.ws, self.off, self.pend = eng, ws, 0, []
-
-    def call(self, items, nprob, lddy, ldx, row_map, dy_b, M, K, N, flags):
-        lib = self.eng.lib
-        need = int(nprob * lib.g2v_linear_bwd_weight_workspace(M, K, N))
-        off = self.off
-        self.off = (off + need + 255) & ~255
-        assert self.off <= self.ws.numel(), "deferred weight-gradient workspace too small"
-        pd = _lib.WgradPending()
-        check(lib.g2v_linear_bwd_weight_deferred(items, nprob, lddy, ldx, row_map[0], row_map[1], row_map[2], dy_b, M, K, N, flags,
-                                                 self.ws.data_ptr() + off, need, C.byref(pd), self.eng._stream()))
-        self.pend.append(pd)
-
-    def flush(self):
-        live = [p for p in self.pend if p.nprob > 0]
-        self.pend, self.off = [], 0
-        for k in range(0, len(live), _lib.WGRAD_PENDING_MAX):
-            chunk = live[k:k + _lib.WGRAD_PENDING_MAX]
-            arr = (_lib.WgradPending * len(chunk))(*chunk)
-            check(self.eng.lib.g2v_linear_bwd_weight_reduce(arr, len(chunk), self.eng._stream()))
-
-
 class VQVAEEngine:
     def __init__(self, D: int, H: int, L: int, K: int, T: int, *, beta: float, dropout_prob: float,
                  n_pre_poses: int = 1, conditioned: bool = True, decay: float = 0.85, eps: float = 1e-5,
@@ -134,7 +104,7 @@ class VQVAEEngine:
         # Opt-in: run the weight-gradient products on the bf16 matrix pipe as 3-term splits (G2V_WGRAD_BF16X3: ~3e-5 max-norm
         # relative error on dW instead of 3e-7; -0.17 ms / step at the BASELINE shape).  Default: exact fp32 MFMA.
         self.wgrad_bf16x3 = False
-        # Round 6: the slab reductions of a branch's weight-gradient products as ONE launch at the branch's end (_DeferredReductions)
+        # Round 6: the slab reductions of a branch's weight-gradient products as ONE launch at the branch's end (ops.WgradDeferred)
         # instead of one behind every product (the round-5 verdict's "deferred slab reductions").  Built, bitwise the same results,
         # and measured: 1.554-1.559 ms against 1.537-1.546 with the immediate calls (same box, 3 x 300 steps,
         # profiles/r06_c_defer_ab.log) -- the decoder branch's products then run entirely beside the encoder BPTT, which starves
@@ -976,11 +946,8 @@ class VQVAEEngine:
             st2 = self._stream()
             # the three (K x E) products -- dd^T flat (+ column sums of dd), probs^T dq, dlogvar^T flat (+ its bias gradient) -- have
             # one shape: ONE launch + one slab reduction (round 4; three of each before)
-            arr = (_lib.WgradItem * 3)()
-            arr[0].dy, arr[0].x, arr[0].dw, arr[0].db = _p(g["gs_dd"]), _p(g["gs_flat"]), _p(g["gs_tw"]), _p(g["gs_colsum"])
-            arr[1].dy, arr[1].x, arr[1].dw, arr[1].db = _p(g["gs_probs"]), _p(g["gs_dq"]), _p(g["gs_tp"]), None
-            arr[2].dy, arr[2].x, arr[2].dw, arr[2].db = (_p(g["gs_dlv"]), _p(g["gs_flat"]), self._g(vq + "logvar_layer.weight"),
-                                                         self._g(vq + "logvar_layer.bias"))
+            arr = ops.wgrad_items([(g["gs_dd"], g["gs_flat"], g["gs_tw"], g["gs_colsum"]), (g["gs_probs"], g["gs_dq"], g["gs_tp"], None),
+                                   (g["gs_dlv"], g["gs_flat"], self._g(vq + "logvar_layer.weight"), self._g(vq + "logvar_layer.bias"))])
             check(lib.g2v_linear_bwd_weight_batch(arr, 3, K, E, N, E, K, 0, ws, wsn, st2))
             check(lib.g2v_rowscale_combine(W, _p(g["gs_colsum"]), _p(g["gs_tw"]), gW, K, E, st2))           # 2 W sum_n dd - 2 dd^T f
             check(lib.g2v_add_halves(gW, E, _p(g["gs_tp"]), E, gW, E, K, E, st2))                            # += probs^T dq
@@ -1007,7 +974,7 @@ class VQVAEEngine:
         check(lib.g2v_rowscale_combine(_p(g["gs_flat"]), _p(g["gs_rowsum"]), _p(g["gs_t"]), _p(g["gs_dflat"]), N, E, st))
         check(lib.g2v_linear_bwd_data(_p(g["gs_dlv"]), K, self._w(vq + "logvar_layer.weight"), _p(g["gs_dflat"]), E, N, E, K, 1, st))
 
-    def _wgrad_fns(self, b, M_default, ws_key="ws", deferred: Optional[_DeferredReductions] = None):
+    def _wgrad_fns(self, b, M_default, ws_key="ws", deferred: Optional[ops.WgradDeferred] = None):
         """deferred: the products leave their slab reductions to deferred.flush() (and take their workspace from it)"""
         lib = self.lib
         ws, wsn = _p(b[ws_key]), b[ws_key].numel()
@@ -1016,9 +983,8 @@ class VQVAEEngine:
 
         def wgrad(dy, lddy, x, ldx, wname, bname, N_, K_, rows=M_default, row_map=(0, 0, 0), keep=None, scale=1.0):
             if deferred is not None and keep is None:
-                arr = (_lib.WgradItem * 1)()
-                arr[0].dy, arr[0].x, arr[0].dw, arr[0].db = dy, x, self._g(wname), self._g(bname) if bname else None
-                deferred.call(arr, 1, lddy, ldx, row_map, None, rows, K_, N_, flags)
+                deferred.call(ops.wgrad_items([(dy, x, self._g(wname), self._g(bname) if bname else None)]), lddy, ldx, row_map, None,
+                              rows, K_, N_, flags)
                 return
             check(lib.g2v_linear_bwd_weight(dy, lddy, x, ldx, row_map[0], row_map[1], row_map[2], keep, scale,
                                             self._g(wname), self._g(bname) if bname else None, rows, K_, N_,
@@ -1026,11 +992,9 @@ class VQVAEEngine:
 
         def wgrad4(rows, items):
             """four (3H x H) GRU weight gradients of one shape in ONE launch + one slab reduction"""
-            arr = (_lib.WgradItem * 4)()
-            for k, (dy, x, wname, bname) in enumerate(items):
-                arr[k].dy, arr[k].x, arr[k].dw, arr[k].db = dy, x, self._g(wname), self._g(bname)
+            arr = ops.wgrad_items([(dy, x, self._g(wname), self._g(bname)) for dy, x, wname, bname in items])
             if deferred is not None:
-                deferred.call(arr, len(items), G, H, (0, 0, 0), None, rows, H, G, flags)
+                deferred.call(arr, G, H, (0, 0, 0), None, rows, H, G, flags)
                 return
             check(lib.g2v_linear_bwd_weight_batch(arr, len(items), G, H, rows, H, G, flags, ws, wsn, self._stream()))
         return wgrad, wgrad4
@@ -1069,7 +1033,7 @@ class VQVAEEngine:
                  T, B, D, H, _p(wsd), wsd.numel(), st))
         x1 = b["x1"] if drop else b["h0"][1:]
         def products():
-            dfr = _DeferredReductions(self, b["ws_dec_wgrad"]) if (wgrad_branch and self.defer_reduce) else None
+            dfr = ops.WgradDeferred(b["ws_dec_wgrad"]) if (wgrad_branch and self.defer_reduce) else None
             wgrad, wgrad4 = self._wgrad_fns(b, M, "ws_dec_wgrad" if wgrad_branch else "ws", deferred=dfr)
             items = [(_p(b["dgi0"]), _p(b["a"]), pre + "gru.weight_ih_l0", pre + "gru.bias_ih_l0"),
                      (_p(b["dgh0"]), _p(b["h0"]), pre + "gru.weight_hh_l0", pre + "gru.bias_hh_l0"),
@@ -1154,12 +1118,10 @@ class VQVAEEngine:
 
         def p_products():
             nonlocal c_in
-            arr = (_lib.WgradItem * 4)()
             # (the column sums of dgi ARE the gradients of bias_ih: written in place when the W_ih gradients are folded too)
             c_in = [self._g(enc + "gru.bias_ih_l0" + suf) if chain_ih else b["c_in"][k].data_ptr() for k, suf in enumerate(("", "_reverse"))]
-            for k, key in enumerate(("f", "b")):
-                arr[k].dy, arr[k].x = _p(b["dgi_" + key]), _p(b["x_drop"]) if drop else _p(in_poses)
-                arr[k].dw, arr[k].db = b["p_in"][k].data_ptr(), c_in[k]
+            arr = ops.wgrad_items([(b["dgi_" + key], b["x_drop"] if drop else in_poses, b["p_in"][k], c_in[k])
+                                   for k, key in enumerate(("f", "b"))])
             if drop:        # the dropped input is a (T B, D) tensor of its own; without dropout the (B,T,D) input in (T,B) row order
                 check(lib.g2v_linear_bwd_weight_batch(arr, 2, G, D, TB, D, G, 0, ws, wsn, st))
             else:
@@ -1174,7 +1136,7 @@ class VQVAEEngine:
         # Round 6: at H = 64 (the W_ih gradients' product + the input layer's two-addend product behind the BPTT) both leave their
         # slab reductions to ONE launch behind the second product (dfr_e); the generic dims keep the immediate calls (their tail
         # is the fold / chain kernels, which read the reduced P, c).
-        dfr_e = _DeferredReductions(self, b["ws_enc_wgrad"]) if (self.defer_reduce and H == 64 and not self.wgrad_bf16x3) else None
+        dfr_e = ops.WgradDeferred(b["ws_enc_wgrad"]) if (self.defer_reduce and H == 64 and not self.wgrad_bf16x3) else None
         with self._branch(4):       # beside the input layer's gradient below (joined there)
             _, wgrad4s = self._wgrad_fns(b, TB, "ws_enc_wgrad" if (self.overlap >> 4) & 1 else "ws", deferred=dfr_e)
             items = [(_p(b["dgi_f"]), _p(b["xin"]), enc + "gru.weight_ih_l0", enc + "gru.bias_ih_l0"),
@@ -1196,10 +1158,9 @@ class VQVAEEngine:
                 wgrad4s(TB, items)
         sum2 = H == 64 and not self.wgrad_bf16x3 and lib.g2v_linear_bwd_weight_sum2_ok(TB, D, H)
         if sum2 and dfr_e is not None:
-            arr = (_lib.WgradItem * 1)()
-            arr[0].dy, arr[0].x = _p(b["gi_f"]), _p(b["x_drop"]) if drop else _p(in_poses)
-            arr[0].dw, arr[0].db = self._g(enc + "in_layer.weight"), self._g(enc + "in_layer.bias")
-            dfr_e.call(arr, 1, H, D, (0, 0, 0) if drop else (B, D, T * D), _p(b["gi_b"]), TB, D, H, 0)
+            arr = ops.wgrad_items([(b["gi_f"], b["x_drop"] if drop else in_poses, self._g(enc + "in_layer.weight"),
+                                    self._g(enc + "in_layer.bias"))])
+            dfr_e.call(arr, H, D, (0, 0, 0) if drop else (B, D, T * D), _p(b["gi_b"]), TB, D, H, 0)
             self._join(4)
             dfr_e.flush()
             return

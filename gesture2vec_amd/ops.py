@@ -197,6 +197,14 @@ def _wgrad_flags(accumulate, bf16x3=False) -> int:
     return (_lib.WGRAD_ACCUMULATE if accumulate else 0) | (_lib.WGRAD_BF16X3 if bf16x3 else 0)
 
 
+def wgrad_items(items):
+    """[(dy, x, dw, db-or-None), ...] of one shape, as tensors or raw device addresses -> the g2v_wgrad_item array of the batch calls"""
+    arr = (_lib.WgradItem * len(items))()
+    for a, item in zip(arr, items):
+        a.dy, a.x, a.dw, a.db = (v.data_ptr() if isinstance(v, torch.Tensor) else v for v in item)
+    return arr
+
+
 def linear_bwd_weight(dy, x, N, K, *, M=None, lddy=None, ldx=None, row_map=None, keep=None, scale=1.0,
                       dw=None, db=None, want_bias=True, accumulate=False, bf16x3=False):
     """dw = dy^T xin (+ db).  bf16x3=True allows the 3-term bf16 split products (G2V_WGRAD_BF16X3, ~1.5e-5 relative)."""
@@ -242,9 +250,7 @@ def linear_bwd_weight_batch(items, N, K, *, M, lddy=None, ldx=None, accumulate=F
     """items: up to 4 tuples (dy, x, dw, db-or-None) of ONE shape -> one launch + one slab reduction (large M).
     row_map = (rows_inner, stride_outer, stride_inner): x row-mapped as in linear_fwd (g2v_linear_bwd_weight_batch_mapped)."""
     lib = _lib_()
-    arr = (_lib.WgradItem * len(items))()
-    for k, (dy, x, dw, db) in enumerate(items):
-        arr[k].dy, arr[k].x, arr[k].dw, arr[k].db = _p(dy), _p(x), _p(dw), _p(db)
+    arr = wgrad_items(items)
     dev = items[0][0].device
     ws = workspace(len(items) * lib.g2v_linear_bwd_weight_workspace(M, K, N), dev, "bwdw")
     if row_map is not None:
@@ -258,34 +264,53 @@ def linear_bwd_weight_batch(items, N, K, *, M, lddy=None, ldx=None, accumulate=F
           "linear_bwd_weight_batch")
 
 
-def linear_bwd_weight_deferred(calls, *, accumulate=False):
-    """Several weight-gradient calls whose slab reductions run as ONE launch behind the last product (include/g2v.h:
-    g2v_linear_bwd_weight_deferred / _reduce).  calls: list of dicts {items: [(dy, x, dw, db-or-None), ...] of one shape, N, K, M,
-    lddy, ldx, row_map, dy_b}.  Results are bitwise those of the immediate calls."""
-    lib = _lib_()
-    dev = calls[0]["items"][0][0].device
-    need = [len(c["items"]) * int(lib.g2v_linear_bwd_weight_workspace(c["M"], c["K"], c["N"])) for c in calls]
-    offs, tot = [], 0
-    for nb in need:
-        offs.append(tot)
-        tot = (tot + nb + 255) & ~255
-    ws = workspace(tot + 256, dev, "bwdw_deferred")
-    pend = []
-    for c, off, nb in zip(calls, offs, need):
-        arr = (_lib.WgradItem * len(c["items"]))()
-        for k, (dy, x, dw, db) in enumerate(c["items"]):
-            arr[k].dy, arr[k].x, arr[k].dw, arr[k].db = _p(dy), _p(x), _p(dw), _p(db)
-        rm = c.get("row_map") or (0, 0, 0)
+class WgradDeferred:
+    """The slab reductions of several weight-gradient calls, held back and run as ONE launch (include/g2v.h:
+    g2v_linear_bwd_weight_deferred / _reduce).  Every call gets a 256-byte-aligned region of `ws` of its own (its slabs live there
+    until `flush`), `flush` reduces the pending records in chunks of G2V_WGRAD_PENDING_MAX.  Round 6: a chain of immediate calls
+    made every product wait for the reduction of the one in front of it, and beside the encoder's BPTT kernel -- whose two
+    workgroups per CU leave a late-dispatched kernel no registers -- those reductions took 17-95 us instead of 5
+    (profiles/r05_az_step_timeline.txt: 133 us of them on the decoder branch's chain)."""
+
+    def __init__(self, ws: torch.Tensor):
+        self.ws, self.off, self.pend = ws, 0, []
+
+    @staticmethod
+    def region(nprob, M, K, N) -> int:
+        return int(nprob * _lib_().g2v_linear_bwd_weight_workspace(M, K, N))
+
+    def call(self, items, lddy, ldx, row_map, dy_b, M, K, N, flags) -> int:
+        """items: a g2v_wgrad_item array (wgrad_items).  -> the record's nprob: 0 where the call completed dw / db itself"""
+        need, off = self.region(len(items), M, K, N), self.off
+        self.off = (off + need + 255) & ~255
+        assert self.off <= self.ws.numel(), "deferred weight-gradient workspace too small"
         pd = _lib.WgradPending()
-        check(lib.g2v_linear_bwd_weight_deferred(arr, len(c["items"]), c.get("lddy", c["N"]), c.get("ldx", c["K"]), rm[0], rm[1], rm[2],
-                                                 _p(c.get("dy_b")), c["M"], c["K"], c["N"], _wgrad_flags(accumulate), ws.data_ptr() + off, nb,
-                                                 C.byref(pd), _stream()), "linear_bwd_weight_deferred")
-        pend.append(pd)
-    live = [p_ for p_ in pend if p_.nprob > 0]
-    for k in range(0, len(live), _lib.WGRAD_PENDING_MAX):
-        chunk = live[k:k + _lib.WGRAD_PENDING_MAX]
-        check(lib.g2v_linear_bwd_weight_reduce((_lib.WgradPending * len(chunk))(*chunk), len(chunk), _stream()), "linear_bwd_weight_reduce")
-    return [p_.nprob for p_ in pend]
+        check(_lib_().g2v_linear_bwd_weight_deferred(items, len(items), lddy, ldx, row_map[0], row_map[1], row_map[2], dy_b, M, K, N,
+                                                     flags, self.ws.data_ptr() + off, need, C.byref(pd), _stream()),
+              "linear_bwd_weight_deferred")
+        self.pend.append(pd)
+        return pd.nprob
+
+    def flush(self):
+        live = [p for p in self.pend if p.nprob > 0]
+        self.pend, self.off = [], 0
+        for k in range(0, len(live), _lib.WGRAD_PENDING_MAX):
+            chunk = live[k:k + _lib.WGRAD_PENDING_MAX]
+            check(_lib_().g2v_linear_bwd_weight_reduce((_lib.WgradPending * len(chunk))(*chunk), len(chunk), _stream()),
+                  "linear_bwd_weight_reduce")
+
+
+def linear_bwd_weight_deferred(calls, *, accumulate=False, bf16x3=False):
+    """Several weight-gradient calls whose slab reductions run as ONE launch behind the last product (WgradDeferred).  calls: list
+    of dicts {items: [(dy, x, dw, db-or-None), ...] of one shape, N, K, M, lddy, ldx, row_map, dy_b}.  Results are bitwise those
+    of the immediate calls.  -> the pending problems per call (0: completed inside the call)."""
+    dev = calls[0]["items"][0][0].device
+    tot = sum((WgradDeferred.region(len(c["items"]), c["M"], c["K"], c["N"]) + 255) & ~255 for c in calls)
+    dfr = WgradDeferred(workspace(tot + 256, dev, "bwdw_deferred"))
+    nprob = [dfr.call(wgrad_items(c["items"]), c.get("lddy", c["N"]), c.get("ldx", c["K"]), c.get("row_map") or (0, 0, 0),
+                      _p(c.get("dy_b")), c["M"], c["K"], c["N"], _wgrad_flags(accumulate, bf16x3)) for c in calls]
+    dfr.flush()
+    return nprob
 
 
 def linear_bwd_weight_fold2(w0, w1, p0, p1, c0, c1, dw=None, db=None, accumulate=False):

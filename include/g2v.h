@@ -176,6 +176,23 @@ int g2v_linear_bwd_weight_deferred(const g2v_wgrad_item* items, int nprob, int64
                                    void* workspace, size_t workspace_bytes, g2v_wgrad_pending* pending, g2v_stream_t stream);
 int g2v_linear_bwd_weight_reduce(const g2v_wgrad_pending* pending, int count, g2v_stream_t stream);
 size_t g2v_linear_bwd_weight_workspace(int M, int K, int N);
+/* Which kernel family a weight-gradient call of the family above runs on (host arithmetic only, no launch): one of
+ * G2V_WGRAD_ROUTE_*, with G2V_WGRAD_ROUTE_RAGGED_TAIL or-ed in when M % 16 leftover rows are added by a second small launch and
+ * the route is that of the M & ~15 main product; 0 for a size or problem count the calls reject and for has_dy_b on a shape
+ * g2v_linear_bwd_weight_sum2_ok() rejects.  has_keep / mapped / has_dy_b: the call has a keep mask / rows_inner > 0 / a second
+ * addend; align: the largest power of two, up to 16, that divides every dy and x pointer of the call. */
+#define G2V_WGRAD_ROUTE_SMALL_LDS 1      /* M <= 4095: LDS-staged, float4 operands */
+#define G2V_WGRAD_ROUTE_SMALL_RT 2       /* ... register-tiled, 2 x 2 tiles per workgroup */
+#define G2V_WGRAD_ROUTE_SMALL_MASKED 3   /* ... one tile per workgroup, keep mask */
+#define G2V_WGRAD_ROUTE_SMALL_WAVES16 4  /* ... one tile per workgroup, 16 waves split the rows */
+#define G2V_WGRAD_ROUTE_SMALL_TILE 5     /* ... one tile per workgroup, 4 waves */
+#define G2V_WGRAD_ROUTE_WAVE 6           /* M >= 4096: wave-autonomous, slabs */
+#define G2V_WGRAD_ROUTE_WAVE_DUAL 7      /* ... its two-addend form */
+#define G2V_WGRAD_ROUTE_WAVE_GEN 8       /* ... output-blocked */
+#define G2V_WGRAD_ROUTE_LDS_TILED 9      /* everything else: LDS-tiled split kernel, slabs */
+#define G2V_WGRAD_ROUTE_RAGGED_TAIL 256
+int g2v_linear_bwd_weight_route(int M, int K, int N, int nprob, int flags, int has_keep, int mapped, int has_dy_b, int64_t lddy,
+                                int64_t ldx, int align);
 /* The weight gradient of a layer y = x W_in^T + b_in (W_in: [H][D]) that feeds TWO layers g_p = y W_p^T (W_p: [G][H]; the two
  * directions' input projections of the bidirectional encoder GRU, ref Autoencoder_VQVAE_model.py:447-464 + EncoderRNN.in_layer
  * :93), from the weight-gradient-shaped products p_p = dg_p^T x ([G][D]) and c_p = column sums of dg_p ([G]) -- both are what

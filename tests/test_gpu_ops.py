@@ -12,6 +12,7 @@ import torch
 
 from oracle import g2v_oracle as O
 from _f64 import as64, default64
+from _wgrad_shapes import WGRAD_ROUTE_SHAPES, route_name
 
 pytestmark = pytest.mark.gpu
 
@@ -203,7 +204,7 @@ def test_linear_bwd_weight_ragged_rows_through_a_row_map(ops):
     """The in_layer gradient of a ragged batch (T B % 16 != 0, x (B,T,D) read in (T,B) order): whole 16-row groups on the
     wave-autonomous kernel, the leftover rows through the same row map on the small-M kernel."""
     B, T, D, H = 129, 33, 135, 64
-    assert (T * B) % 16 == 1 and T * B >= 4112
+    assert (T * B) % 16 == 1 and T * B >= 4112 and route_name(T * B, D, H, row_map=(B, T)) == "WAVE|RAGGED_TAIL"
     x_btd, dy = rnd(B, T, D, seed=41), rnd(T * B, H, seed=42)
     x_tbd = x_btd.transpose(0, 1).reshape(T * B, D)
     dw, db = ops.linear_bwd_weight(dy.to(DEV), x_btd.to(DEV), H, D, M=T * B, row_map=(B, D, T * D))
@@ -231,6 +232,9 @@ def test_linear_bwd_weight_ragged_rows_through_a_row_map(ops):
                                    (128, 200, 600), (130, 600, 200), (16, 64, 514), (1024, 200, 600), (1000, 64, 2100), (2560, 200, 600), (4096, 40, 200),   # small-M data gradient / weight gradient up to 4096 rows
                                    (8192 + 5, 64, 192), (33 * 4100 // 4, 135, 64), (4096 + 31, 200, 600)])   # ragged rows: whole groups + leftover
 def test_linear_bwd(ops, M, K, N):
+    want = {(5000, 64, 192): "WAVE|RAGGED_TAIL", (139264 // 8, 64, 192): "WAVE", (1000, 64, 2100): "SMALL_LDS",
+            (8192 + 5, 64, 192): "WAVE|RAGGED_TAIL", (33 * 4100 // 4, 135, 64): "WAVE|RAGGED_TAIL", (4096 + 31, 200, 600): "WAVE_GEN|RAGGED_TAIL"}
+    assert route_name(M, K, N) == want.get((M, K, N), "WAVE_GEN" if M >= 4096 else "SMALL_TILE")
     x, w, dy = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.2), rnd(M, N, seed=3)
     dx = ops.linear_bwd_data(dy.to(DEV), w.to(DEV))
     relclose(dx, (dy.double() @ w.double()).float(), 2e-6 if N <= 1024 else 4e-6, "bwd_data")      # fp32 fma chain of length N
@@ -242,6 +246,92 @@ def test_linear_bwd(ops, M, K, N):
     # deterministic
     dw3, _ = ops.linear_bwd_weight(dy.to(DEV), x.to(DEV), N, K)
     assert torch.equal(dw3, dw)
+
+
+def _wgrad_case_inputs(case):
+    """seeded operands of one WGRAD_ROUTE_SHAPES entry on the device + its float64 dw / db per problem"""
+    M, K, N, nprob = case["M"], case["K"], case["N"], case.get("nprob", 1)
+    rm, ldx = case.get("row_map"), case.get("ldx")
+    keep = (torch.rand(M, K, generator=torch.Generator().manual_seed(7)) < 0.8).to(torch.uint8) if case.get("keep") else None
+    dy_b = rnd(M, N, seed=9) if case.get("dual") else None
+    probs, refs = [], []
+    for p in range(nprob):
+        dy, x = rnd(M, N, seed=100 + p), rnd(M, K, seed=200 + p)
+        g64, x64 = dy.double() + (dy_b.double() if dy_b is not None else 0.0), x.double()
+        if keep is not None:
+            x64 = x64 * keep * 1.25
+        refs.append(((g64.t() @ x64).float(), g64.sum(0).float()))
+        if rm is not None:      # the (B, T, K) tensor whose (T, B) row order is x
+            xd = x.view(rm[1], rm[0], K).transpose(0, 1).contiguous()
+        elif ldx is not None:
+            xd = torch.zeros(M, ldx)
+            xd[:, :K] = x
+        else:
+            xd = x
+        probs.append((dy.to(DEV), xd.to(DEV)))
+    return dict(probs=probs, keep=None if keep is None else keep.to(DEV), dy_b=None if dy_b is None else dy_b.to(DEV),
+                row_map=None if rm is None else (rm[0], K, rm[1] * K)), refs
+
+
+def _wgrad_case_run(ops, case, inp, outs, accumulate=False):
+    """the immediate ops.* call of the entry's form, into outs = [(dw, db)] per problem"""
+    M, K, N, kw = case["M"], case["K"], case["N"], dict(M=case["M"], ldx=case.get("ldx"), row_map=inp["row_map"], accumulate=accumulate)
+    if case.get("dual"):
+        ops.linear_bwd_weight_sum2(inp["probs"][0][0], inp["dy_b"], inp["probs"][0][1], N, K, dw=outs[0][0], db=outs[0][1], **kw)
+    elif len(outs) == 1:
+        ops.linear_bwd_weight(*inp["probs"][0], N, K, keep=inp["keep"], scale=1.25, dw=outs[0][0], db=outs[0][1],
+                              bf16x3=case.get("bf16x3", False), **kw)
+    else:
+        ops.linear_bwd_weight_batch([(dy, x, dw, db) for (dy, x), (dw, db) in zip(inp["probs"], outs)], N, K,
+                                    bf16x3=case.get("bf16x3", False), **kw)
+
+
+@pytest.mark.parametrize("case", WGRAD_ROUTE_SHAPES, ids=lambda c: c["name"])
+def test_linear_bwd_weight_on_every_route(ops, monkeypatch, case):
+    """Every route of the weight-gradient plan, and every variant of a route's launch, at the smallest shape that selects it
+    (tests/_wgrad_shapes.py; the selection itself is asserted here and, without a device, in tests/test_wgrad_plan_host.py):
+    against float64, deterministic, the deferred form bitwise the immediate one, accumulation, and the first call on a workspace of
+    exactly the queried size with a guard band behind it."""
+    from gesture2vec_amd import ops as ops_mod
+    assert route_name(**case) == case["route"]
+    M, K, N, nprob = case["M"], case["K"], case["N"], case.get("nprob", 1)
+    inp, refs = _wgrad_case_inputs(case)
+    fresh = lambda: [(torch.full((N, K), float("nan"), device=DEV), torch.full((N,), float("nan"), device=DEV)) for _ in range(nprob)]
+    GUARD, PAT, handed = 1 << 16, 0x5A, []
+
+    def exact_workspace(nbytes, device, tag="ws"):
+        handed.append((int(nbytes), torch.full((int(nbytes) + GUARD,), PAT, dtype=torch.uint8, device=device)))
+        return handed[-1][1][:int(nbytes)]
+
+    first = fresh()
+    with monkeypatch.context() as m:
+        m.setattr(ops_mod, "workspace", exact_workspace)
+        _wgrad_case_run(ops, case, inp, first)
+    torch.cuda.synchronize()
+    assert [nb for nb, _ in handed] == [nprob * int(ops_mod._lib_().g2v_linear_bwd_weight_workspace(M, K, N))]
+    assert int((handed[0][1][handed[0][0]:] != PAT).sum()) == 0, "wrote past the queried workspace size"
+    for p, ((dw, db), (dw64, db64)) in enumerate(zip(first, refs)):
+        if case.get("bf16x3"):      # (the bounds of test_linear_bwd_weight_bf16x3_option_is_bounded)
+            assert float((dw.double().cpu() - dw64.double()).abs().max()) <= 1e-4 * float(dw64.abs().max()), f"dw of problem {p}"
+            relclose(db, db64, 2e-6, f"db of problem {p}")
+        else:
+            relclose(dw, dw64, 1e-5, f"dw of problem {p} vs float64")
+            relclose(db, db64, 1e-5, f"db of problem {p} vs float64")
+    again = fresh()
+    _wgrad_case_run(ops, case, inp, again)
+    assert all(torch.equal(a, b) and torch.equal(c, d) for (a, c), (b, d) in zip(again, first)), "not deterministic"
+    _wgrad_case_run(ops, case, inp, again, accumulate=True)
+    for p in range(nprob):
+        relclose(again[p][0], 2 * first[p][0], 2e-6, f"dw of problem {p} accumulated")
+        relclose(again[p][1], 2 * first[p][1], 2e-6, f"db of problem {p} accumulated")
+    if not case.get("keep"):      # (g2v_linear_bwd_weight_deferred takes no keep mask)
+        later = fresh()
+        call = dict(items=[(dy, x, dw, db) for (dy, x), (dw, db) in zip(inp["probs"], later)], N=N, K=K, M=M, ldx=case.get("ldx", K),
+                    row_map=inp["row_map"], dy_b=inp["dy_b"])
+        pending = ops.linear_bwd_weight_deferred([call], bf16x3=case.get("bf16x3", False))
+        finished_inside = case["route"].startswith("SMALL_") or "RAGGED_TAIL" in case["route"]
+        assert pending == [0 if finished_inside else nprob]
+        assert all(torch.equal(a, b) and torch.equal(c, d) for (a, c), (b, d) in zip(later, first)), "deferred differs from immediate"
 
 
 # ----------------------------------------------------------------------------------------------- quantiser
@@ -1623,6 +1713,7 @@ def test_linear_bwd_weight_bf16x3_option_is_bounded():
     from gesture2vec_amd import ops
     torch.manual_seed(9)
     M, N, K = 34 * 512, 192, 64
+    assert route_name(M, K, N, bf16x3=True) == "WAVE"       # (the flag is honoured there only)
     dy = torch.randn(M, N, device=DEV)
     x = torch.randn(M, K, device=DEV)
     ref = dy.double().t() @ x.double()
@@ -1659,6 +1750,7 @@ def test_linear_wave_kernels_at_rollout_shapes(ops):
     dx2 = ops.linear_bwd_data(dgi.to(DEV), w_ih.to(DEV), out=dx.clone(), accumulate=True)
     relclose(dx2, 2 * (dgi.double() @ w_ih.double()).float(), 2e-6, "bwd_data accumulate")
     # weight gradients
+    assert [route_name(M, H, G), route_name(M, D, H, row_map=(B, T)), route_name(M, H, D)] == ["WAVE"] * 3
     dw, db = ops.linear_bwd_weight(dgi.to(DEV), xin.to(DEV), G, H)
     relclose(dw, (dgi.double().t() @ xin.double()).float(), 1e-5, "dW 192x64")
     relclose(db, dgi.double().sum(0).float(), 1e-5, "db 192")
@@ -1771,6 +1863,9 @@ def test_linear_bwd_weight_small_row_counts(ops, M, N, K, nprob):
     (same rows per MFMA, same accumulation order: BITWISE the same dW / db -- checked by handing the same x over with a row
     stride that is not a multiple of 4), and the 16-wave form of the one-tile kernel where a product has too few tiles to
     fill the chip.  All against float64, all deterministic."""
+    many_tiles = (N + 15) // 16 * ((K + 15) // 16) * nprob > 256
+    assert route_name(M, K, N, nprob=nprob) == ("SMALL_LDS" if many_tiles else "SMALL_WAVES16")
+    assert route_name(M, K, N, nprob=nprob, ldx=K + 1) == ("SMALL_RT" if many_tiles else "SMALL_WAVES16")
     items, wide = [], []
     for p in range(nprob):
         dy, x = rnd(M, N, seed=60 + p).to(DEV), rnd(M, K, seed=70 + p).to(DEV)
@@ -1787,7 +1882,7 @@ def test_linear_bwd_weight_small_row_counts(ops, M, N, K, nprob):
     ops.linear_bwd_weight_batch(wide, N, K, M=M, ldx=K + 1)
     for p in range(nprob):
         assert torch.equal(items[p][2], first[p][0]) and torch.equal(items[p][3], first[p][1]), f"problem {p} not deterministic"
-        if (N + 15) // 16 * ((K + 15) // 16) * nprob > 256:      # (the 16-wave kernel splits the rows differently)
+        if many_tiles:      # (the 16-wave kernel splits the rows differently)
             assert torch.equal(wide[p][2], first[p][0]), f"dw of problem {p}: unaligned-operand kernel differs"
             assert torch.equal(wide[p][3], first[p][1]), f"db of problem {p}: unaligned-operand kernel differs"
         else:
@@ -1861,6 +1956,7 @@ def test_linear_bwd_weight_output_blocked_with_row_map(ops):
     """dW of an in_layer-like product at generic dims (N = 200, K = 40) with the (B,T,D) -> (T,B,D) row map: the
     output-blocked wave kernel's MAPPED instantiation."""
     B, T, D, H = 1024, 4, 40, 200
+    assert route_name(T * B, D, H, row_map=(B, T)) == "WAVE_GEN"
     x = rnd(B, T, D, seed=71)
     dy = rnd(T * B, H, seed=72)
     dw, db = ops.linear_bwd_weight(dy.to(DEV), x.to(DEV), H, D, M=T * B, row_map=(B, D, T * D))
