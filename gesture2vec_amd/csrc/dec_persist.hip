@@ -1268,9 +1268,11 @@ int dec_persist_loss_chase_launch(const float* target, const g2v_dec_saved* s, c
 //   registers : W_ih0^T, W_hh0^T, W_ih1^T, W_hh1^T fragments (contraction over the 3H gate axis: 4 x 48 VGPRs), the two
 //               hidden-state gradient carries, dbn_t / xhat_t of the step whose BatchNorm-backward sums are in flight
 //   LDS       : W_pre^T (D rows) and W_out^T (K = D) fragments, du, dy, the gate-gradient tile [g_r | g_z | g_n | g_hn]
-//   per step t: [exchange of the BatchNorm-backward sums of step t+1] -> du_{t+1} -> feedback dxin = du W_pre through
-//               Dropout(0.95) into dy_t -> out_layer^T -> cell 1 backward -> cell 0 backward -> ReLU backward ->
-//               partial sums (sum dbn, sum dbn * xhat) over the block's rows -> publish
+//   per step t: [exchange of the BatchNorm-backward sums of step t+1; inside it the products of step t+1 that nothing on the
+//               chain waits for: dgh1^T h1_prev in front of hop 1, dgh1 W_hh1 and dgh0 W_hh0 -> the two carries inside hop 2]
+//               -> du_{t+1} -> feedback dxin = du W_pre through Dropout(0.95) into dy_t -> out_layer^T -> cell 1 backward ->
+//               dgi1 W_ih1 -> cell 0 backward -> dgi0 W_ih0 -> ReLU backward -> partial sums (sum dbn, sum dbn * xhat) over the
+//               block's rows -> publish
 // Produces exactly the arrays the per-step kernels produce (du, dy total, dgi/dgh of both cells, d_bn_w/b, dh_init);
 // the dbn scratch array is not needed (the values stay in registers).
 // =====================================================================================================================
@@ -1285,10 +1287,11 @@ constexpr int R_BNW = R_POUTT + 4 * KSD * 256;
 constexpr int R_RED = R_BNW + 64;
 constexpr int R_TOT = R_RED + 16 * 128;
 constexpr int R_END = R_TOT + 128;
-// fused weight gradient (FW): the cell-1 gate-gradient tile keeps its own LDS image (the cell-0 one stays in R_G), so that it
-// is still there when its weight-gradient MFMAs run in the shadow of the NEXT iteration's exchange; plus one 16 x 16
-// transpose scratch per wave (an operand's rows from accumulator layout to B-fragment layout)
-constexpr int R_G1 = R_END, TRW = 16 * 17, R_TR = R_G1 + 16 * LDG, R_END_FW = R_TR + 4 * TRW;
+// the cell-1 gate-gradient tile keeps its own LDS image (the cell-0 one stays in R_G), so that both are still there when the
+// products that nothing waits for -- dgh1 W_hh1, dgh0 W_hh0 and, fused weight gradient (FW), dgh1^T h1_prev -- run in the shadow
+// of the NEXT iteration's exchange; FW adds one 16 x 16 transpose scratch per wave (an operand's rows from accumulator layout to
+// B-fragment layout).  R_END is what the multi-tile kernel (one tile image, products on the chain) asks for.
+constexpr int R_G1 = R_END, R_END_G1 = R_G1 + 16 * LDG, TRW = 16 * 17, R_TR = R_END_G1, R_END_FW = R_TR + 4 * TRW;
 // loss fold: the column coefficients of the workgroup's tile (16 * D floats) and the 64 values of loss_grad_const live in the
 // three padding tiles at the end of the packed W_pre^T image (tiles 9..11: zero, never multiplied, never copied in)
 constexpr int R_LCN = R_PPRET + 9 * KSH * 256, R_LTAB = R_LCN + 2176;
@@ -1296,7 +1299,8 @@ static_assert(R_LTAB + 64 <= R_POUTT, "the loss-fold tiles fit the padding of th
 static_assert(R_END_FW * 4 <= 160 * 1024, "LDS budget of the fused-weight-gradient rollout backward");
 }  // namespace
 
-size_t dec_persist_bwd_lds_bytes(bool fw) { return (size_t)(fw ? R_END_FW : R_END) * sizeof(float); }
+size_t dec_persist_bwd_lds_bytes(bool fw) { return (size_t)(fw ? R_END_FW : R_END_G1) * sizeof(float); }
+size_t dec_persist_bwd_mt_lds_bytes() { return (size_t)R_END * sizeof(float); }
 size_t dec_persist_bwd_wgrad_slab_floats() { return (size_t)(3 * H * H + 3 * H); }      // per workgroup: dW_hh1 192 x 64, db_hh1 192
 
 struct DecPersistBwdArgs {
@@ -1354,6 +1358,32 @@ __device__ __forceinline__ void gate_frag_mma2(f32x4& a_hh, const WFrag<1, KSG>&
   }
 }
 
+// The two hidden-side products of one step in one pass: a1 += W_hh1^T-tile x [g_r | g_z | g_hn] of the cell-1 tile G1, a0 += W_hh0^T-tile
+// x the same columns of the cell-0 tile G0.  Two independent 48-long chains, alternated like the two of gate_frag_mma2; each keeps
+// the order of gate_frag_mma<true>.
+__device__ __forceinline__ void gate_frag_mma_hh2(f32x4& a1, const WFrag<1, KSG>& f1, const float* G1, f32x4& a0,
+                                                  const WFrag<1, KSG>& f0, const float* G0, int lane) {
+  const int off = (lane & 15) * LDG + 4 * (lane >> 4);
+  float4 n1 = *reinterpret_cast<const float4*>(G1 + off), n0 = *reinterpret_cast<const float4*>(G0 + off);
+#pragma unroll
+  for (int s = 0; s < KSG; ++s) {
+    const float4 x1 = n1, x0 = n0;
+    if (s + 1 < KSG) {
+      const int col = 16 * (s + 1) + (s + 1 >= 8 ? 64 : 0);
+      n1 = *reinterpret_cast<const float4*>(G1 + off + col);
+      n0 = *reinterpret_cast<const float4*>(G0 + off + col);
+    }
+    a1 = mfma16(f1.w[0][s].x, x1.x, a1);
+    a0 = mfma16(f0.w[0][s].x, x0.x, a0);
+    a1 = mfma16(f1.w[0][s].y, x1.y, a1);
+    a0 = mfma16(f0.w[0][s].y, x0.y, a0);
+    a1 = mfma16(f1.w[0][s].z, x1.z, a1);
+    a0 = mfma16(f0.w[0][s].z, x0.z, a0);
+    a1 = mfma16(f1.w[0][s].w, x1.w, a1);
+    a0 = mfma16(f0.w[0][s].w, x0.w, a0);
+  }
+}
+
 struct CellSaved {      // this lane's slice of what the forward saved for one cell and step
   float4 r, z, n, hn, hp;
 };
@@ -1404,7 +1434,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_bwd_kernel(DecPersistBwdAr
   float* Xdu = smem + R_XDU;
   float* Xdy = smem + R_XDY;
   float* Gt = smem + R_G;
-  float* Gt1 = FW ? smem + R_G1 : Gt;
+  float* Gt1 = smem + R_G1;
   float* Dt = smem + R_DT;
   uint32_t* Kt = reinterpret_cast<uint32_t*>(smem + R_KT);
   float* Ppre_t = smem + R_PPRET;
@@ -1527,7 +1557,13 @@ __global__ __launch_bounds__(256, 1) void dec_persist_bwd_kernel(DecPersistBwdAr
     dbc1 += sum;
   };
 
-  float4 carry0 = make_float4(0.f, 0.f, 0.f, 0.f), carry1 = carry0;   // d h0 / d h1 flowing to the earlier step
+  // d h0 / d h1 flowing to the earlier step: carry = dh * z + dgh W_hh.  Nothing reads a carry before the next iteration, so the
+  // two products run in the next iteration's exchange (Part A), off the chain from one publish to the next, from the gate tiles
+  // the step left in LDS.  What crosses the loop boundary is dh and z of both cells, not their product: with product and sum in
+  // one block the compiler contracts them into ONE fma (so do the multi-tile kernel and every earlier build of this one), and the
+  // carry is written as that fma here so that its bits do not hang on where the two halves happen to sit.
+  float4 carry0 = make_float4(0.f, 0.f, 0.f, 0.f), carry1 = carry0, pz0 = carry0, pz1 = carry0;
+  float pdh0[4] = {0.f, 0.f, 0.f, 0.f}, pdh1[4] = {0.f, 0.f, 0.f, 0.f};
   float dbn[4] = {0.f, 0.f, 0.f, 0.f}, xhat[4] = {0.f, 0.f, 0.f, 0.f}, gis[4] = {0.f, 0.f, 0.f, 0.f};   // of the step in flight
   float acc_w = 0.f, acc_b = 0.f;                                       // d gamma / d beta (workgroup 0, tid < H)
 
@@ -1538,7 +1574,7 @@ __global__ __launch_bounds__(256, 1) void dec_persist_bwd_kernel(DecPersistBwdAr
     // "stage the next step's tiles" below; the first iteration stages its own in the prologue), so the loop opens with the
     // exchange.  Holding every saved value of the step in registers across the exchange made hipcc park them in AGPRs
     // behind four `s_waitcnt vmcnt(0)` (+6 us per step): only the five cell-1 vectors are requested in front of the exchange
-    // (they travel while it is in flight), the cell-0 values after the cell-1 epilogue, behind the hh1 / ih1 products.
+    // (they travel while it is in flight), the cell-0 values after the cell-1 epilogue, behind the ih1 product.
     const int64_t tile = ((int64_t)t * B + b0) * D;
     const int64_t srow = (int64_t)(t - 1) * B + row_i;      // row of the saved arrays this step reads (t >= 1)
     CellSaved c1;
@@ -1548,7 +1584,24 @@ __global__ __launch_bounds__(256, 1) void dec_persist_bwd_kernel(DecPersistBwdAr
     // ---- Part A: finish BatchNorm backward of step t+1 -> du_{t+1} --------------------------------------------------------
     if (!last) {
       if (FW && pending) wgrad_hh1();      // in the shadow of the exchange: everybody's partial sums are still on the fabric
-      px_exchange(a.x, (t + 1) & 1, (unsigned)(T - 1 - t), a.nblk, b, red, tot, tid);
+      PSTAMP(1, 8);
+      const int xpar = (t + 1) & 1;
+      const unsigned xtag = (unsigned)(T - 1 - t);
+      px_hop1(a.x, xpar, xtag, a.nblk, b, red, tot, tid);
+      PSTAMP(1, 9);
+      // the pending step's hidden-side products: the filler of hop 2's sweep (MFMA and LDS instructions only), i.e. inside the
+      // fabric round trip behind the first requests for the column's row sums; a one-row grid has no second hop
+      auto hh_pair = [&]() {
+        f32x4 h1 = {0.f, 0.f, 0.f, 0.f}, h0 = {0.f, 0.f, 0.f, 0.f};
+        gate_frag_mma_hh2(h1, f_hh1, Gt1, h0, f_hh0, Gt, lane);
+        carry1 = make_float4(__builtin_fmaf(pdh1[0], pz1.x, h1[0]), __builtin_fmaf(pdh1[1], pz1.y, h1[1]),
+                             __builtin_fmaf(pdh1[2], pz1.z, h1[2]), __builtin_fmaf(pdh1[3], pz1.w, h1[3]));
+        carry0 = make_float4(__builtin_fmaf(pdh0[0], pz0.x, h0[0]), __builtin_fmaf(pdh0[1], pz0.y, h0[1]),
+                             __builtin_fmaf(pdh0[2], pz0.z, h0[2]), __builtin_fmaf(pdh0[3], pz0.w, h0[3]));
+      };
+      if (px_two_hops(a.nblk)) px_hop2(a.x, xpar, xtag, a.nblk, b, red, tot, tid, hh_pair);
+      else hh_pair();
+      PSTAMP(1, 11);
       const float4 s14 = *reinterpret_cast<const float4*>(tot + f0), s24 = *reinterpret_cast<const float4*>(tot + H + f0);
       const float a1[4] = {s14.x, s14.y, s14.z, s14.w}, a2[4] = {s24.x, s24.y, s24.z, s24.w};
       float du[4];
@@ -1632,13 +1685,15 @@ __global__ __launch_bounds__(256, 1) void dec_persist_bwd_kernel(DecPersistBwdAr
         *reinterpret_cast<float4*>(a.gr.dy + tile + 4 * (int64_t)e4) = reinterpret_cast<const float4*>(Dt)[e4];
     PSTAMP(1, 3);
     // ---- dh1 = carry1 + dy W_out ; GRU cell 1 backward ---------------------------------------------------------------------
-    float4 direct1;
     {
       const f32x4 acc0 = lds_frag_mma_2chain<KSD>(Pout_t, wave, Xdy, LDD, lane);
       const float dh[4] = {acc0[0] + carry1.x, acc0[1] + carry1.y, acc0[2] + carry1.z, acc0[3] + carry1.w};
-      direct1 = cell_bwd<!FW>(dh, c1, a.gr.dgi1 + srow * G3 + f0, a.gr.dgh1 + srow * G3 + f0, Gt1, i, f0);
+      cell_bwd<!FW>(dh, c1, a.gr.dgi1 + srow * G3 + f0, a.gr.dgh1 + srow * G3 + f0, Gt1, i, f0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pdh1[r] = dh[r];
+      pz1 = c1.z;
     }
-    // cell-0 / BatchNorm inputs of this step: in flight during the next two products (96 MFMAs)
+    // cell-0 / BatchNorm inputs of this step: in flight during the next product (48 MFMAs)
     CellSaved c0;
     load_cell(c0, a.sv.gates0, a.sv.h0, srow, f0);
     const float4 a4 = *reinterpret_cast<const float4*>(a.sv.a + srow * H + f0);
@@ -1652,12 +1707,11 @@ __global__ __launch_bounds__(256, 1) void dec_persist_bwd_kernel(DecPersistBwdAr
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();
     PSTAMP(1, 4);
-    // ---- carry1' = dh1 * z + dgh1 W_hh1 ;  dx1 = dgi1 W_ih1 -> dh0 (inter-layer dropout backward) -------------------------
+    // ---- dx1 = dgi1 W_ih1 -> dh0 (inter-layer dropout backward); dgh1 W_hh1 waits for the next exchange ---------------------
     float dh0[4];
     {
-      f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
-      gate_frag_mma2(a1, f_hh1, a2, f_ih1, Gt1, lane);
-      carry1 = make_float4(direct1.x + a1[0], direct1.y + a1[1], direct1.z + a1[2], direct1.w + a1[3]);
+      f32x4 a2 = {0.f, 0.f, 0.f, 0.f};
+      gate_frag_mma<false>(a2, f_ih1, Gt1, lane);
       const float c0v[4] = {carry0.x, carry0.y, carry0.z, carry0.w};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1666,19 +1720,19 @@ __global__ __launch_bounds__(256, 1) void dec_persist_bwd_kernel(DecPersistBwdAr
         dh0[r] = v + c0v[r];
       }
     }
-    if (t > 1) tile_commit(t - 1);
-    lds_barrier();                       // every wave is done reading the cell-1 tile
+    if (t > 1) tile_commit(t - 1);      // (no barrier: the cell-0 tile was last read in Part A, Dt / Kt are next read in Part B)
     PSTAMP(1, 5);
     // ---- GRU cell 0 backward ---------------------------------------------------------------------------------------------
-    float4 direct0;
-    direct0 = cell_bwd<true>(dh0, c0, a.gr.dgi0 + srow * G3 + f0, a.gr.dgh0 + srow * G3 + f0, Gt, i, f0);
+    cell_bwd<true>(dh0, c0, a.gr.dgi0 + srow * G3 + f0, a.gr.dgh0 + srow * G3 + f0, Gt, i, f0);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pdh0[r] = dh0[r];
+    pz0 = c0.z;
     lds_barrier();
     PSTAMP(1, 6);
-    // ---- carry0' = dh0 * z + dgh0 W_hh0 ;  da = dgi0 W_ih0 -> ReLU backward -> dbn_t, partial sums, publish -----------------
+    // ---- da = dgi0 W_ih0 -> ReLU backward -> dbn_t, partial sums, publish; dgh0 W_hh0 waits for the next exchange -----------
     {
-      f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
-      gate_frag_mma2(a1, f_hh0, a2, f_ih0, Gt, lane);
-      carry0 = make_float4(direct0.x + a1[0], direct0.y + a1[1], direct0.z + a1[2], direct0.w + a1[3]);
+      f32x4 a2 = {0.f, 0.f, 0.f, 0.f};
+      gate_frag_mma<false>(a2, f_ih0, Gt, lane);
       const float av[4] = {a4.x, a4.y, a4.z, a4.w}, uv[4] = {u4.x, u4.y, u4.z, u4.w}, mv[4] = {mean4.x, mean4.y, mean4.z, mean4.w},
                   vv[4] = {var4.x, var4.y, var4.z, var4.w};
       const float4 g4 = *reinterpret_cast<const float4*>(bnw + f0);
@@ -2004,7 +2058,7 @@ int dec_persist_bwd_launch(const g2v_dec_weights* w, const g2v_dec_saved* s, con
   }
   if (tiles_per_wg > 1 || (B & 15)) {
     const int R = tiles_per_wg, nwg = (a.nblk + R - 1) / R;
-    const size_t lds = dec_persist_bwd_lds_bytes(false);
+    const size_t lds = dec_persist_bwd_mt_lds_bytes();
     const void* fn = R == 1 ? (const void*)dec_persist_bwd_mt_kernel<1>
                             : (R == 2 ? (const void*)dec_persist_bwd_mt_kernel<2> : (const void*)dec_persist_bwd_mt_kernel<3>);
     static bool mt_set[3] = {false, false, false};
