@@ -8,8 +8,13 @@ latents coloured by code (`Clustering.py:1046-1056`, `:1411-1417`).  Arguments, 
 * `TSNE`: g2v_tsne_affinities builds the dense joint P once (csrc/tsne.hip), every iteration is g2v_tsne_gradient (one pass over P)
   + g2v_tsne_update; the host reads the KL divergence and the gradient norm back every 50 iterations, where sklearn checks its two
   stop rules.  Only `n_components == 2` and the exact method exist; N <= `ops.tsne_max_rows()` rows.
+* `TSNE.transform` places new rows into the fitted map, as the reference's `make_unity_scatter(latents, labels, file, pca, MyTSNE)`
+  does with `MyTSNE.transform(pca.transform(latents))` (`Clustering.py:1318-1350`): openTSNE's structure and `transform` defaults,
+  stated exactly in DESIGN 3.5e (csrc/tsne_place.hip: exact neighbours among the fitted rows, their conditionals, a median start,
+  then a per-row descent against the fixed map in one launch).  Every row is placed on its own, so a set of any size can be placed
+  against an exactly fitted sample.  `LatentMap` is the reference's `(pca, MyTSNE)` pair as one picklable object.
 
-Out of scope: openTSNE's `transform` of new points, Barnes-Hut / FFT approximations, 3-D maps, plots."""
+Out of scope: numerical parity with openTSNE, Barnes-Hut / FFT approximations, 3-D maps, plots."""
 from __future__ import annotations
 
 import numpy as np
@@ -26,6 +31,15 @@ def _rows(x, what):
     if x.dim() != 2 or x.dtype != torch.float32:
         raise TypeError(f"{what}: expected a (N, E) fp32 tensor, got {tuple(x.shape)} {x.dtype}")
     return x if x.stride(1) == 1 else x.contiguous()
+
+
+def _pitch4(x):
+    """the rows on a 16-byte aligned pitch of a multiple of 4 floats (a view of a zero-filled copy where they are not): layout only"""
+    if x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0:
+        return x
+    wide = torch.zeros((x.shape[0], (x.shape[1] + 3) & ~3), dtype=torch.float32, device=x.device)
+    wide[:, :x.shape[1]] = x
+    return wide[:, :x.shape[1]]
 
 
 def _rng(random_state):
@@ -118,7 +132,8 @@ class TSNE:
     max(N / early_exaggeration / 4, 50); the two stop rules (no progress of the KL divergence for `n_iter_without_progress`
     iterations, gradient norm <= `min_grad_norm`) are looked at every 50 iterations.  `init`: "pca" (the first two principal
     scores, scaled to a standard deviation of 1e-4 in column 0), "random" (1e-4 * RandomState(random_state).standard_normal((N, 2)))
-    or an (N, 2) array.  After `fit`: `embedding_` (N, 2) fp32 on the device, `kl_divergence_`, `n_iter_`, `learning_rate_`."""
+    or an (N, 2) array.  After `fit`: `embedding_` (N, 2) fp32 on the device, `kl_divergence_`, `n_iter_`, `learning_rate_`, and
+    `fit_rows_`, the rows it was given (on the device; `transform` measures new rows against them)."""
 
     def __init__(self, n_components=2, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_iter=1000,
                  n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=None, method="exact"):
@@ -147,11 +162,13 @@ class TSNE:
         self.random_state = random_state
         self.method = method
         self.embedding_ = self.kl_divergence_ = self.n_iter_ = self.learning_rate_ = None
+        self.fit_rows_ = self.transform_kl_ = None
 
     def __getstate__(self):
         state = dict(self.__dict__)
-        if torch.is_tensor(state["embedding_"]):
-            state["embedding_"] = state["embedding_"].cpu()
+        for name in ("embedding_", "fit_rows_", "transform_kl_"):
+            if torch.is_tensor(state.get(name)):
+                state[name] = state[name].cpu()
         return state
 
     def _initial(self, x, N):
@@ -218,10 +235,129 @@ class TSNE:
         if it < _EXPLORATION_MAX_ITER or self.max_iter - _EXPLORATION_MAX_ITER > 0:
             kl, it = self._descent(P, emb, it + 1, self.max_iter, self.n_iter_without_progress, 0.8, 1.0, bufs)
         self.embedding_, self.kl_divergence_, self.n_iter_ = emb, kl, it
+        self.fit_rows_, self.transform_kl_ = x, None
         return self
 
     def fit_transform(self, x: torch.Tensor, y=None) -> torch.Tensor:
         return self.fit(x).embedding_
+
+    @torch.no_grad()
+    def transform(self, x: torch.Tensor, perplexity=5, initialization="median", k=25, learning_rate=0.1, exaggeration=1.5,
+                  n_iter=250, momentum=0.8, max_grad_norm=0.25, batch_rows=262144) -> torch.Tensor:
+        """Places the rows of x (M, d) into the fitted map -> (M, 2) fp32 on the device; `embedding_` does not move and the rows do
+        not interact, so each row's result is the same bits whatever else is in x (openTSNE's `transform` defaults).
+        The `max(k_aff, k)` nearest fitted rows are found exactly, `k_aff = min(N - 1, floor(3 perplexity))` of them carry the
+        conditionals; `initialization`: "median" of the map over the `k` nearest, "weighted" by the conditionals, or an (M, 2)
+        array.  `transform_kl_` receives the per-row KL divergence (float64, on the device).  `batch_rows` bounds the rows per
+        kernel call (memory only)."""
+        from . import ops
+        if self.embedding_ is None or self.fit_rows_ is None:
+            raise ValueError("TSNE.transform: not fitted")
+        N, d = self.fit_rows_.shape
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != d:
+            raise ValueError(f"TSNE.transform: rows must have {d} columns, got {tuple(getattr(x, 'shape', ()))}")
+        M, k = x.shape[0], int(k)
+        k_aff = min(N - 1, int(3.0 * float(perplexity)))
+        if not 0.0 < float(perplexity) < k_aff:
+            raise ValueError(f"TSNE.transform: perplexity ({perplexity}) must be positive and less than the number of neighbours "
+                             f"that carry the conditionals, k_aff = min(N - 1, floor(3 perplexity)) = {k_aff}")
+        if not 1 <= k <= min(N, 128):
+            raise ValueError(f"TSNE.transform: k ({k}) must be in [1, min(N, 128) = {min(N, 128)}]")
+        if k_aff > 128:
+            raise ValueError(f"TSNE.transform: k_aff = {k_aff} neighbours; the kernels keep at most 128 (perplexity < 43)")
+        y0 = None
+        if isinstance(initialization, str):
+            if initialization not in ("median", "weighted"):
+                raise ValueError(f"TSNE.transform: initialization must be 'median', 'weighted' or an (M, 2) array "
+                                 f"(got {initialization!r})")
+        else:
+            y0 = initialization.detach() if torch.is_tensor(initialization) else torch.from_numpy(np.asarray(initialization))
+            if tuple(y0.shape) != (M, 2):
+                raise ValueError(f"TSNE.transform: initialization must be ({M}, 2), got {tuple(y0.shape)}")
+        if int(n_iter) < 0 or int(batch_rows) < 1:
+            raise ValueError("TSNE.transform: n_iter must not be negative and batch_rows must be positive")
+        x = _rows(x, "TSNE.transform")
+        dev = x.device
+        if self.fit_rows_.device != dev or self.embedding_.device != dev:      # (an unpickled object holds host tensors)
+            self.fit_rows_, self.embedding_ = self.fit_rows_.to(dev), self.embedding_.to(dev)
+        ref, emb = _pitch4(self.fit_rows_), self.embedding_.contiguous()
+        if y0 is not None:
+            y0 = y0.to(device=dev, dtype=torch.float32)
+        out = torch.empty((M, 2), dtype=torch.float32, device=dev)
+        kl = torch.empty((M,), dtype=torch.float64, device=dev)
+        kk = max(k_aff, k)
+        for s in range(0, M, int(batch_rows)):
+            z = _pitch4(x[s:s + int(batch_rows)])
+            idx, d2 = ops.tsne_place_neighbors(ref, z, kk)
+            p = ops.tsne_place_conditionals(d2, k_aff, perplexity)
+            if y0 is not None:
+                y = y0[s:s + int(batch_rows)].contiguous().clone()
+            else:
+                y = ops.tsne_place_init(emb, idx, p, initialization, k if initialization == "median" else k_aff)
+            res = ops.tsne_place_descent(emb, idx, p, y, None, None, n_iter, exaggeration, momentum, learning_rate, max_grad_norm,
+                                         want=("kl",))
+            out[s:s + z.shape[0]] = y
+            kl[s:s + z.shape[0]] = res["kl"]
+        self.transform_kl_ = kl
+        return out
+
+
+class LatentMap:
+    """The reference's `(pca, MyTSNE)` pair as one object: `fit(latents)` runs `PCA(n_pca)` and `TSNE(random_state=random_state,
+    **tsne_kw)` on the rows, or on `sample_size` rows drawn exactly as `latent_map` draws them, and sets `coords_` (the fitted map)
+    and `rows_` (the fitted rows' indices, int64); `transform(latents, **place_kw)` places further rows (`TSNE.transform` of their
+    PCA scores); `fit_all` maps a whole set of any size: the sample exactly, every other row placed against it.  Pickles without
+    device state."""
+
+    def __init__(self, n_pca=50, sample_size=None, random_state=None, **tsne_kw):
+        self.n_pca, self.sample_size, self.random_state = int(n_pca), sample_size, random_state
+        self.pca = PCA(n_pca)
+        self.tsne = TSNE(**tsne_kw)
+        self.coords_ = self.rows_ = None
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        for name in ("coords_", "rows_"):
+            if torch.is_tensor(state[name]):
+                state[name] = state[name].cpu()
+        return state
+
+    @torch.no_grad()
+    def fit(self, latents: torch.Tensor) -> "LatentMap":
+        latents = _rows(latents, "LatentMap.fit")
+        N = latents.shape[0]
+        rs = _rng(self.random_state)
+        if self.sample_size is not None:
+            idx = torch.from_numpy(rs.permutation(N)[:int(self.sample_size)].astype(np.int64)).to(latents.device)
+            latents = latents[idx].contiguous()                    # a gather: layout only
+        else:
+            idx = torch.arange(N, dtype=torch.int64, device=latents.device)
+        self.tsne.random_state = rs
+        self.coords_ = self.tsne.fit_transform(self.pca.fit_transform(latents))
+        self.tsne.random_state = self.random_state                 # (a RandomState that has been drawn from is not kept)
+        self.rows_ = idx
+        return self
+
+    @torch.no_grad()
+    def transform(self, latents: torch.Tensor, **place_kw) -> torch.Tensor:
+        if self.coords_ is None:
+            raise ValueError("LatentMap.transform: not fitted")
+        return self.tsne.transform(self.pca.transform(_rows(latents, "LatentMap.transform")), **place_kw)
+
+    @torch.no_grad()
+    def fit_all(self, latents: torch.Tensor, **place_kw):
+        """-> (coords (N, 2) fp32, fitted (N,) bool), in input row order: the fitted rows carry `coords_`, the others are placed"""
+        latents = _rows(latents, "LatentMap.fit_all")
+        self.fit(latents)
+        N = latents.shape[0]
+        fitted = torch.zeros((N,), dtype=torch.bool, device=latents.device)
+        fitted[self.rows_] = True
+        coords = torch.empty((N, 2), dtype=torch.float32, device=latents.device)
+        coords[self.rows_] = self.coords_
+        rest = (~fitted).nonzero().flatten()
+        if rest.numel():
+            coords[rest] = self.transform(latents[rest].contiguous(), **place_kw)
+        return coords, fitted
 
 
 @torch.no_grad()

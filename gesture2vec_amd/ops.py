@@ -1268,3 +1268,98 @@ def tsne_update(y, velocity, gains, grad, momentum, learning_rate, gnorm2=None):
     check(_lib_().g2v_tsne_update(_p(y), _p(velocity), _p(gains), _p(grad), N, float(momentum), float(learning_rate),
                                   _p(None if gnorm2 is None else _chk(gnorm2, torch.float64, "gnorm2")), _stream()), "tsne_update")
     return y
+
+
+# ------------------------------------------------------------------- new rows into a fitted t-SNE map (tsne_place.hip)
+def _place_rows(t, name, fn):
+    if not t.is_cuda:
+        raise _lib.G2VLibraryError(f"{name} must be a GPU tensor: the g2v kernels have no CPU path")
+    if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0:
+        raise TypeError(f"{fn}: {name} must be a 16-byte aligned (rows, d) fp32 tensor with unit column stride and a row stride "
+                        "that is a multiple of 4")
+    return t
+
+
+def tsne_place_neighbors(x, z, kk):
+    """-> (idx (M, kk) int32, d2 (M, kk) fp32): per row of z (M, d) its kk nearest rows of x (N, d) in ascending (d^2, index)
+    order, the squared distances formed as tsne_affinities forms them (g2v_tsne_place_neighbors; the M x N distances are never
+    stored)."""
+    fn = "tsne_place_neighbors"
+    x, z = _place_rows(x, "x", fn), _place_rows(z, "z", fn)
+    (N, d), M, kk = x.shape, z.shape[0], int(kk)
+    if z.shape[1] != d:
+        raise ValueError(f"{fn}: x has {d} columns and z {z.shape[1]}")
+    lib = _lib_()
+    nb = int(lib.g2v_tsne_place_neighbors_workspace(N, M, d, kk))
+    if nb == 0:
+        raise ValueError(f"{fn}: needs 1 <= d <= 512, 1 <= kk <= min(N, 128), N < 2^24 and M >= 1 (N = {N}, M = {M}, d = {d}, "
+                         f"kk = {kk})")
+    ws = workspace(nb, x.device, "tsne_place")
+    idx = torch.empty((M, kk), dtype=torch.int32, device=x.device)
+    d2 = torch.empty((M, kk), dtype=torch.float32, device=x.device)
+    check(lib.g2v_tsne_place_neighbors(_p(x), int(x.stride(0)), N, _p(z), int(z.stride(0)), M, d, kk, _p(idx), _p(d2), _p(ws), nb,
+                                       _stream()), fn)
+    return idx, d2
+
+
+def tsne_place_conditionals(d2, k_aff, perplexity):
+    """-> p (M, k_aff) fp32: the conditionals over the first k_aff columns of d2 (M, kk) at this perplexity, each row summing to 1
+    (g2v_tsne_place_conditionals: sklearn's bisection of the precision in float64)."""
+    M, kk = _chk(d2, name="d2").shape
+    p = torch.empty((M, int(k_aff)), dtype=torch.float32, device=d2.device)
+    check(_lib_().g2v_tsne_place_conditionals(_p(d2), M, kk, int(k_aff), float(perplexity), _p(p), _stream()),
+          "tsne_place_conditionals")
+    return p
+
+
+def tsne_place_init(Y, idx, p=None, mode="median", k_use=None):
+    """-> y (M, 2) fp32, the start of the new rows in the map Y (N, 2): "median" of Y over the first k_use columns of idx (M, kk)
+    (numpy's rule), or "weighted" = sum_j p_ij Y_j over the first k_use columns of p (M, k_aff) (g2v_tsne_place_init)."""
+    if mode not in ("median", "weighted"):
+        raise ValueError(f"tsne_place_init: mode must be 'median' or 'weighted' (got {mode!r})")
+    M, kk = _chk(idx, torch.int32, "idx").shape
+    N = _chk(Y, name="Y").shape[0]
+    if tuple(Y.shape) != (N, 2):
+        raise ValueError(f"tsne_place_init: Y must be (N, 2), got {tuple(Y.shape)}")
+    weighted = mode == "weighted"
+    if weighted and (p is None or _chk(p, name="p").shape[0] != M):
+        raise ValueError("tsne_place_init: the weighted start needs p (M, k_aff)")
+    k_aff = int(p.shape[1]) if p is not None else 0
+    k_use = int(k_use) if k_use is not None else (k_aff if weighted else kk)
+    y = torch.empty((M, 2), dtype=torch.float32, device=Y.device)
+    check(_lib_().g2v_tsne_place_init(_p(Y), N, _p(idx), _p(p), M, kk, k_aff, 1 if weighted else 0, k_use, _p(y), _stream()),
+          "tsne_place_init")
+    return y
+
+
+def tsne_place_descent(Y, idx, p, y, velocity=None, gains=None, n_iter=250, exaggeration=1.5, momentum=0.8, learning_rate=0.1,
+                       max_grad_norm=0.25, want=("kl", "zsum", "grad")):
+    """n_iter placement steps on y (M, 2) in place (velocity, gains too; fresh ones are made when they are None) against the fixed
+    map Y (N, 2), all inside one launch (g2v_tsne_place_descent) -> dict of the per-row outputs named in `want`, evaluated at the
+    final y at exaggeration 1: kl (M,) float64, zsum (M,) float64, grad (M, 2) fp32 (unclipped).  n_iter == 0 only evaluates them at
+    y, the gradient at the exaggeration given."""
+    M, kk = _chk(idx, torch.int32, "idx").shape
+    N, k_aff = _chk(Y, name="Y").shape[0], _chk(p, name="p").shape[1]
+    if tuple(Y.shape) != (N, 2) or tuple(_chk(y, name="y").shape) != (M, 2) or p.shape[0] != M:
+        raise ValueError(f"tsne_place_descent: Y must be (N, 2), y (M, 2), idx (M, kk) and p (M, k_aff); got {tuple(Y.shape)}, "
+                         f"{tuple(y.shape)}, {tuple(idx.shape)}, {tuple(p.shape)}")
+    if int(n_iter) > 0:
+        velocity = torch.zeros_like(y) if velocity is None else velocity
+        gains = torch.ones_like(y) if gains is None else gains
+        for name, t in (("velocity", velocity), ("gains", gains)):
+            if tuple(_chk(t, name=name).shape) != (M, 2):
+                raise ValueError(f"tsne_place_descent: {name} must be ({M}, 2), got {tuple(t.shape)}")
+    else:
+        velocity = gains = None
+    out = {}
+    if "kl" in want:
+        out["kl"] = torch.empty((M,), dtype=torch.float64, device=y.device)
+    if "zsum" in want:
+        out["zsum"] = torch.empty((M,), dtype=torch.float64, device=y.device)
+    if "grad" in want:
+        out["grad"] = torch.empty((M, 2), dtype=torch.float32, device=y.device)
+    check(_lib_().g2v_tsne_place_descent(_p(Y), N, _p(idx), _p(p), M, kk, k_aff, _p(y), _p(velocity), _p(gains), int(n_iter),
+                                         float(exaggeration), float(momentum), float(learning_rate), float(max_grad_norm),
+                                         _p(out.get("kl")), _p(out.get("zsum")), _p(out.get("grad")), _stream()),
+          "tsne_place_descent")
+    return out

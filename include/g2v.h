@@ -1129,6 +1129,51 @@ int g2v_tsne_gradient(const float* P, const float* y, int64_t N, double exaggera
 int g2v_tsne_update(float* y, float* velocity, float* gains, const float* grad, int64_t N, float momentum, float learning_rate,
                     double* gnorm2, g2v_stream_t stream);
 
+/* ---- new rows into a fitted t-SNE map (tsne_place.hip; gesture2vec_amd/embedding.py: TSNE.transform, LatentMap) --------------------
+ * The reference's make_unity_scatter(latents, labels, file, pca, MyTSNE) = MyTSNE.transform(pca.transform(latents))
+ * (Clustering.py:1318-1350): openTSNE's structure and transform defaults, stated exactly; bit parity with openTSNE (approximate
+ * neighbours, interpolated repulsion) is not claimed.  X (N,d) fp32 are the rows the map was fitted on, Y (N,2) fp32 their map,
+ * Z (M,d) fp32 the new rows.  Every new row is its own problem and Y does not move: a row's result depends on that row, X, Y and the
+ * parameters, not on M or on the other rows of the call, bit for bit.  1 <= N < 2^24, 1 <= M < 2^31, 1 <= kk <= min(N, 128).
+ *
+ * g2v_tsne_place_neighbors: X with row stride ldx, Z with row stride ldz (both >= d and % 4 == 0), 1 <= d <= 512 -> idx int32 (M,kk) and
+ *   d2 fp32 (M,kk): per new row the kk nearest reference rows in ascending (d^2, index) order, ties to the lower index.  They are
+ *   SELECTED on squared distances formed exactly as g2v_tsne_affinities forms them (float64 norms, Gram tiles on the exact-fp32 MFMA
+ *   in chains of 32 columns folded in float64, rounded to fp32 once; d^2 < (|z|^2 + |x|^2) / 8 re-evaluated from differences in
+ *   float64), so a row that differs from the kk-th nearest by less than ~3e-7 (|z|^2 + |x|^2) may take its place.  The kk kept
+ *   distances are then evaluated once more as sum (z - x)^2 in float64, rounded to fp32 once, and the list is sorted again: d2 is the
+ *   correctly rounded distance (a new row bitwise equal to a reference row is at exactly 0), which the conditionals need (the Gram
+ *   form's error is ~20 roundings of d^2 on centred rows).  Columns d .. ld - 1 are never read.  The M x N distances are selected
+ *   from as they are formed and never stored.  Any other shape: G2V_ERR_UNSUPPORTED.  X, Z and workspace 16-byte aligned;
+ *   workspace: g2v_tsne_place_neighbors_workspace(N, M, d, kk) bytes (0 for an unsupported shape), not trusted across calls.
+ * g2v_tsne_place_conditionals: d2 (M,kk) as above, 1 <= k_aff <= kk, 0 < perplexity < k_aff -> p fp32 (M,k_aff): over the first
+ *   k_aff neighbours, the bisection of the precision of g2v_tsne_affinities (float64, beta = 1, doubled / halved while a bound is
+ *   infinite, at most 100 steps, stop at |H - log(perplexity)| <= 1e-5, a row sum of exactly 0 becomes 1e-8) with no term left out.
+ *   p is the conditional: not symmetrised, each row sums to 1.
+ * g2v_tsne_place_init: the start y (M,2) fp32 from idx (M,kk) (and p (M,k_aff) for mode 1).  mode 0: per coordinate the median of Y
+ *   over the first k_use <= kk neighbours, numpy's rule (an even count gives (a + b) * 0.5f of the two middle values).  mode 1:
+ *   sum_j p_ij Y_j over the first k_use <= k_aff neighbours in float64, rounded once.
+ * g2v_tsne_place_descent: n_iter steps on y, velocity, gains (M,2) fp32 in place, all inside one launch.  With
+ *   w_ij = 1 / (1 + |y_i - Y_j|^2) and Z_i = sum_{j < N} w_ij,
+ *     g_i = 2 [ exaggeration sum_{j in the k_aff neighbours} p_ij w_ij (y_i - Y_j)  -  (1 / Z_i) sum_{j < N} w_ij^2 (y_i - Y_j) ]
+ *   y - Y and w in fp32 as g2v_tsne_gradient takes its q, the three sums and Z in float64 over j ascending, g rounded to fp32 once.
+ *   A step, in fp32 in this order: n = sqrt(gx^2 + gy^2); if max_grad_norm > 0 and n > max_grad_norm, g *= max_grad_norm / n; gains
+ *   += 0.2 where velocity * g < 0, *= 0.8 elsewhere, floor 0.01; velocity = momentum velocity - learning_rate (gains g);
+ *   y += velocity.  After the last step one more sweep at exaggeration 1 gives, per row, kl float64 (M) = sum_j p_ij log(p_ij /
+ *   (w_ij / Z_i)) (a p of exactly 0 adds nothing), zsum float64 (M) = Z_i and grad fp32 (M,2), the unclipped gradient; each may be
+ *   NULL.  n_iter == 0 moves nothing, only evaluates them at y -- grad at the exaggeration given, which a closing sweep replaces
+ *   by 1 -- and reads neither velocity nor gains (both may be NULL).  An entry of idx outside [0, N) is read as 0.  Y, y, velocity, gains and grad 8-byte aligned.  No workspace.
+ * No floating-point atomics anywhere: the same input gives the same bits. */
+size_t g2v_tsne_place_neighbors_workspace(int64_t N, int64_t M, int d, int kk);
+int g2v_tsne_place_neighbors(const float* X, int64_t ldx, int64_t N, const float* Z, int64_t ldz, int64_t M, int d, int kk,
+                             int32_t* idx, float* d2, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+int g2v_tsne_place_conditionals(const float* d2, int64_t M, int kk, int k_aff, double perplexity, float* p, g2v_stream_t stream);
+int g2v_tsne_place_init(const float* Y, int64_t N, const int32_t* idx, const float* p, int64_t M, int kk, int k_aff, int mode,
+                        int k_use, float* y, g2v_stream_t stream);
+int g2v_tsne_place_descent(const float* Y, int64_t N, const int32_t* idx, const float* p, int64_t M, int kk, int k_aff, float* y,
+                           float* velocity, float* gains, int n_iter, double exaggeration, float momentum, float learning_rate,
+                           float max_grad_norm, double* kl, double* zsum, float* grad, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,14 +3,20 @@
 reference's `PCA(50)` + `TSNE(2, perplexity=30)` picture of all latents coloured by code (`Clustering.py:1046-1056`, `:1411-1417`).
 
     python embed_latents.py --checkpoint ckpt.bin --chunks x.npy [--kmeans model.pk] [--sample-rows M] [--out map.npz]
-                            [--scatter-txt scatter.txt]
+                            [--scatter-txt scatter.txt] [--place-rest] [--save-map map.pk] [--map map.pk]
 
 `--chunks` holds (N, T, D) pose chunks in the autoencoder's input space.  Their latents and code ids (`chunks_to_codes`; for an
 autoencoder without a quantiser the ids of the pickled `--kmeans` model, or none) are taken on the device, `--sample-rows M` rows are
 drawn as sklearn's `sample_size` (seeded with `--seed`; needed beyond `ops.tsne_max_rows()` rows) and mapped with `latent_map`.
 `--out` (default `<checkpoint dir>/plots/latent_map.npz`) receives `coords` (M, 2) fp32, `codes` (M,) int64 (-1 without ids) and
 `rows` (M,) int64, the mapped rows of `--chunks`.  `--scatter-txt` also writes the text of the reference's `make_unity_scatter`
-(`Clustering.py:1339-1345`): a first line "512", then `<code>,<x>,<y>` with three decimals per row.  No plot is drawn."""
+(`Clustering.py:1339-1345`): a first line "512", then `<code>,<x>,<y>` with three decimals per row.  No plot is drawn.
+
+With `--sample-rows M --place-rest` every row of `--chunks` is mapped, however many there are: the sample exactly, each other row
+placed into the sample's map (`LatentMap.fit_all`); `coords`, `codes` and `rows` then cover all rows in input order and `fitted` (N,)
+bool marks the sample.  `--save-map PATH` pickles the fitted `LatentMap`.  `--map PATH` fits nothing: the rows of `--chunks` (a
+generated set, say) are placed into that saved map, which is how the reference's `Metrics_analysis` draws a generated sequence as a
+trajectory through the map of the real data (`Clustering.py:1318-1350`)."""
 from __future__ import annotations
 
 import argparse
@@ -28,7 +34,7 @@ for _p in (_HERE, _ROOT):
         sys.path.insert(0, _p)
 
 from utils.train_utils import load_checkpoint_and_model  # noqa: E402
-from gesture2vec_amd.embedding import latent_map  # noqa: E402
+from gesture2vec_amd.embedding import LatentMap, latent_map  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents, chunks_to_codes  # noqa: E402
 
 
@@ -50,9 +56,17 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="map path (default: <checkpoint dir>/plots/latent_map.npz)")
     ap.add_argument("--scatter-txt", dest="scatter_txt", default=None, help="also write the reference's make_unity_scatter text here")
+    ap.add_argument("--place-rest", dest="place_rest", action="store_true",
+                    help="with --sample-rows: place every other row into the sample's map and write all rows")
+    ap.add_argument("--save-map", dest="save_map", default=None, help="pickle the fitted LatentMap here")
+    ap.add_argument("--map", dest="map", default=None, help="a pickled LatentMap: fit nothing, place the rows of --chunks into it")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    if a.place_rest and a.sample_rows is None:
+        ap.error("--place-rest needs --sample-rows")
+    if a.map and (a.place_rest or a.save_map or a.sample_rows is not None):
+        ap.error("--map places into a saved map: it goes with neither --sample-rows, --place-rest nor --save-map")
     dev = torch.device(a.device)
     _, net, _, _, _ = load_checkpoint_and_model(a.checkpoint, dev, "autoencoder_vq")
     net.eval()
@@ -72,10 +86,29 @@ def main(argv=None):
     lat = torch.cat(lats)
     codes = None if ids[0] is None else torch.cat(ids)
     print(f"latents: {tuple(lat.shape)}")
-    coords, rows = latent_map(lat, n_pca=a.n_pca, sample_size=a.sample_rows, random_state=a.seed, perplexity=a.perplexity,
-                              max_iter=a.max_iter)
+    fitted = None
+    if a.map:
+        with open(a.map, "rb") as f:
+            lm = pickle.load(f)
+        coords, rows = lm.transform(lat), torch.arange(lat.shape[0], device=dev)
+    elif a.place_rest or a.save_map:
+        lm = LatentMap(n_pca=a.n_pca, sample_size=a.sample_rows, random_state=a.seed, perplexity=a.perplexity, max_iter=a.max_iter)
+        if a.place_rest:
+            (coords, fitted), rows = lm.fit_all(lat), torch.arange(lat.shape[0], device=dev)
+        else:
+            lm.fit(lat)
+            coords, rows = lm.coords_, lm.rows_
+        if a.save_map:
+            with open(a.save_map, "wb") as f:
+                pickle.dump(lm, f)
+            print(f"wrote {a.save_map}")
+    else:
+        coords, rows = latent_map(lat, n_pca=a.n_pca, sample_size=a.sample_rows, random_state=a.seed, perplexity=a.perplexity,
+                                  max_iter=a.max_iter)
     res = {"coords": coords.cpu().numpy(), "rows": rows.cpu().numpy(),
            "codes": np.full(rows.shape[0], -1, np.int64) if codes is None else codes[rows].cpu().numpy()}
+    if fitted is not None:
+        res["fitted"] = fitted.cpu().numpy()
     out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "plots", "latent_map.npz")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     np.savez(out, **res)
