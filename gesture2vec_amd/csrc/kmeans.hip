@@ -22,14 +22,16 @@
 //                       256 + 4l .. of the running float64 sum and of sum (x - c_old)^2 -> part[chunk][E + 1]
 //   km_fold_kernel      one workgroup per cluster adds its chunks' partials in chunk order -> sums[k][E], cl_inertia[k]
 //   km_rowdist_kernel, km_relocate_kernel   only when a cluster is empty (they return at once otherwise): |x - c_old[label]|^2 per row in
-//                       float64, then one workgroup picks the n_empty farthest rows (farthest first, lowest row on ties), takes each
-//                       out of its cluster's sum / count and makes it the sum of the next empty cluster in ascending id
+//                       float64 (pair_dist.hpp: pd_pair_sq), then one workgroup picks the n_empty farthest rows (farthest first,
+//                       lowest row on ties), takes each out of its cluster's sum / count and makes it the sum of the next empty
+//                       cluster in ascending id
 //   km_center_kernel    one workgroup per cluster: c_new = (float)(sum / count) (a cluster left without rows keeps c_old), its shift
 //   km_finish_kernel    one workgroup: shift and inertia summed over the clusters in a fixed tree, the state block
 // Every float64 sum is formed in an order fixed by (N, E, K) and the labels: no floating-point atomics, the same input gives the same
 // bits, and no result depends on how many workgroups a launch happens to use.
 #include "common.hpp"
 #include "km_sort.hpp"
+#include "pair_dist.hpp"
 
 #include <type_traits>
 
@@ -172,27 +174,15 @@ __global__ __launch_bounds__(256) void km_rowdist_kernel(const float* __restrict
                                                         const unsigned long long* __restrict__ hdr, double* __restrict__ rowdist,
                                                         const double* __restrict__ state) {
   if (km_gated(state) || hdr[HD_EMPTY] == 0) return;
+  __builtin_assume((E & 3) == 0);                             // (whole vectors only: pd_pair_sq has no tail here)
   const int lane = threadIdx.x & 63;
-  const int nv = E >> 2;
   for (int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); n < N; n += (int64_t)gridDim.x * 4) {
     const int64_t lab = labels[n];
     if (lab < 0 || lab >= K) {
       if (lane == 0) rowdist[n] = -1.0;
       continue;
     }
-    const float4* p = reinterpret_cast<const float4*>(x + n * E);
-    const float4* cp = reinterpret_cast<const float4*>(centers + (size_t)lab * E);
-    double dist = 0.0;
-    for (int v = lane; v < nv; v += 64) {
-      const float4 a = p[v], c = cp[v];
-      const double d0 = (double)a.x - (double)c.x, d1 = (double)a.y - (double)c.y, d2 = (double)a.z - (double)c.z,
-                   d3 = (double)a.w - (double)c.w;
-      dist = fma(d0, d0, dist);
-      dist = fma(d1, d1, dist);
-      dist = fma(d2, d2, dist);
-      dist = fma(d3, d3, dist);
-    }
-    dist = km_wave_sum(dist);
+    const double dist = pd_pair_sq(x + n * E, centers + (size_t)lab * E, E, lane);
     if (lane == 0) rowdist[n] = dist;
   }
 }

@@ -20,8 +20,9 @@
 //                       running sums in a fixed tree and the (row, cluster) sum goes into a(i) or min -> b(i): every such sum has one
 //                       owner, the wave, and is complete when it is used.
 //   near pairs          d^2 < 1/8 (n_i + n_j): the Gram form has lost >= 3 bits there (its absolute error is ~3e-7 (n_i + n_j)); the
-//                       wave re-evaluates such a pair as sum (x_i - x_j)^2 in float64 from the rows (64 lanes over the columns, fixed
-//                       xor tree), as vq_fused_bx_kernel screens and then decides exactly.  Everywhere else d carries <= 1.2e-6 d.
+//                       wave re-evaluates such a pair as sum (x_i - x_j)^2 in float64 from the rows (pair_dist.hpp: pd_pair_sq;
+//                       the loop is pd_near_pairs written out), as vq_fused_bx_kernel screens and then decides exactly.  Everywhere
+//                       else d carries <= 1.2e-6 d.
 //   sil_finish_kernel   out[0] = sum_i s(i) (one workgroup, rows dealt to threads by index, fixed tree), out[1] = non-empty clusters,
 //                       counts[K] = rows whose label is outside [0, K) (they are in no list: never used as an address)
 // Every sum is formed in an order fixed by (N, E, K, ld), the data and the labels: no floating-point atomics, and no result depends on
@@ -125,7 +126,7 @@ __device__ __forceinline__ float4 sil_keep(bool ok, const float4& v) {
 
 // |x_ri - x_rj| in float64 from the rows, by the whole wave; every lane returns the same bits
 __device__ __forceinline__ double sil_pair(const float* __restrict__ x, int64_t ld, int E, int ri, int rj, int lane) {
-  return sqrt(pd_pair_sq(x, ld, E, ri, rj, lane));
+  return sqrt(pd_pair_sq(x + (int64_t)ri * ld, x + (int64_t)rj * ld, E, lane));
 }
 
 // LDS: own[64][E16 + 4] | swept[2][64][SIL_SWLD]
@@ -135,6 +136,7 @@ __global__ __launch_bounds__(256) void sil_tile_kernel(const float* __restrict__
                                                       double* __restrict__ a_out, double* __restrict__ b_out,
                                                       double* __restrict__ s_out) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  __builtin_assume((E & 3) == 0);                           // (whole vectors only: pd_pair_sq has no tail here)
   const int n_sub = (int)hdr[HD_CHUNKS];
   const int n_mt = (n_sub + 3) >> 2;                        // tiles that hold a row
   if ((int)blockIdx.x >= n_mt) return;
@@ -229,6 +231,7 @@ __global__ __launch_bounds__(256) void sil_tile_kernel(const float* __restrict__
           dd[r] = (valid && !near) ? (double)sqrtf(fmaxf(d2, 0.f)) : 0.0;
           nm |= near ? (1u << r) : 0u;
         }
+        // (pd_near_pairs written out: through the helper this kernel took 0.3 % longer at 65536 rows, outside its own spread)
         unsigned long long pend = __ballot(nm != 0);
         while (pend) {                                      // (wave-uniform) one lane's near pairs at a time, by the whole wave
           const int L = __ffsll((long long)pend) - 1;

@@ -4,23 +4,15 @@
 //
 // g2v_tsne_affinities
 //   tsne_pad_kernel     x -> xp (N, E4 = d rounded up to 4, zero filled): rows 16-byte aligned whatever d and ld are
-//   tsne_norm_kernel    |x_i|^2 in float64 (exact products, one thread per row)
-//   tsne_dist_kernel    one workgroup (4 waves) per 64 x 64 tile of D = squared Euclidean distances, written into P.  Both row sets go
-//                       through LDS in k-chunks of 32; wave w owns tile rows 16 w .. 16 w + 15 as the A operand of
-//                       v_mfma_f32_16x16x4_f32 and the four 16-row groups of the column set as B, so that lane (i, q) ends with
-//                       G[row 4 q + r][col i] in register r and a tile row is stored 16 lanes wide.  The fp32 chains are 32 columns long: after
-//                       every chunk the accumulators are added into float64 ones and cleared, so G carries sqrt(d / 32) chunk errors
-//                       of ~3e-7 |partial sum over 32 columns| (2e-5 at d = 400 for rows of unit entries) instead of one chain
-//                       through all of d.  d^2 = n_i + n_j - 2 G in float64, rounded to fp32 once (sklearn rounds its float64
-//                       distances to fp32 too).  A NEAR pair (d^2 < (n_i + n_j) / 8, G as large as the norms) is
-//                       re-evaluated as sum (x_i - x_j)^2 in float64 by the whole wave, exactly as silhouette.hip does it
-//                       (pair_dist.hpp): a bitwise equal pair has d^2 = 0 exactly, the diagonal is 0 by rule, and D[i][j] == D[j][i]
-//                       bit for bit (the same products in the same order).  Rows far from the origin should be centred first
-//                       (embedding.PCA does): |G| is then small wherever the pair is not near.
+//   pd_norm_kernel      |x_i|^2 in float64 (pair_dist.hpp)
+//   tsne_dist_kernel    one workgroup (4 waves) per 64 x 64 tile of D = squared Euclidean distances, written into P: pd_tile
+//                       (pair_dist.hpp, which states the arithmetic and its error) over the padded copy, the row set against
+//                       itself.  A bitwise equal pair has d^2 = 0 exactly, the diagonal is 0 by rule, and D[i][j] == D[j][i] bit
+//                       for bit.  Rows far from the origin should be centred first (embedding.PCA does): |G| is then small
+//                       wherever the pair is not near.
 //   tsne_search_kernel  one workgroup per row i, the row of D staged in LDS (N * 4 B <= 128 KiB beside the reduction scratch: every
 //                       supported N fits, so there is no path that re-reads the row from global memory).  sklearn's bisection of the
-//                       precision beta in float64: beta = 1, doubled / halved while a bound is infinite, <= 100 steps, stop at
-//                       |H - log(perplexity)| <= 1e-5, a row sum of exactly 0 becomes 1e-8, the term j = i left out.  The row is
+//                       precision beta in float64 (tsne_cells.hpp), the sums over the block, the term j = i left out.  The row is
 //                       overwritten with c_j|i = exp(-beta d^2) / sum as fp32; the float64 sum of those fp32 values goes to rowsum[i].
 //   tsne_total_kernel   sigma = max(2 sum_i rowsum[i], eps) (= sum (C + C^T); one workgroup, rows dealt by index, fixed tree)
 //   tsne_sym_kernel     P_ij = max((c_ij + c_ji) / sigma, eps) in float64, rounded to fp32, in place: the workgroup of tile (a, b),
@@ -35,9 +27,8 @@
 //                       KL as well; that needs Z and changes a term by < eps q, below float64 resolution of the sums: left out.)
 //   tsne_finish_kernel  one workgroup: Z and KL = A + log(Z) S_p in a fixed order, then grad_i = 4 (att_i - rep_i / Z) as fp32 and the
 //                       float64 sum of the squared fp32 gradients.  out = { KL (NaN without want_kl, as sklearn), sum grad^2, Z }
-// g2v_tsne_update       sklearn's _gradient_descent step in its fp32 operation order (no contraction): gains += 0.2 where
-//                       velocity * grad < 0, *= 0.8 elsewhere, floor 0.01; velocity = momentum velocity - lr (gains grad);
-//                       y += velocity; gnorm2 (may be NULL) = float64 sum of (gains grad)^2, the norm sklearn's stop rule reads.
+// g2v_tsne_update       sklearn's _gradient_descent step per component (tsne_cells.hpp: ts_step); gnorm2 (may be NULL) = float64
+//                       sum of (gains grad)^2, the norm sklearn's stop rule reads.
 // Every sum is formed in an order fixed by (N, d): no floating-point atomics, the same input gives the same bits.  All offsets into P
 // are 64-bit; N <= 32768 (4 GiB of P), G2V_ERR_UNSUPPORTED beyond.  No environment variable is read.
 #include <float.h>
@@ -45,15 +36,13 @@
 #include "common.hpp"
 #include "km_sort.hpp"
 #include "pair_dist.hpp"
+#include "tsne_cells.hpp"
 
 namespace g2v {
 namespace {
 
 constexpr int64_t TSNE_MAX_N = 32768;
 constexpr int TSNE_MAX_D = 512;
-constexpr int TS_TILE = 64;
-constexpr int TS_KC = 32;
-constexpr int TS_LD = TS_KC + 4;            // LDS row stride of a staged chunk (an odd number of 16-byte slots)
 constexpr int TS_YCH = 2048;                // columns of y per LDS stage of the sweep
 constexpr int TS_SWEEP_ROWS = 8;            // rows per workgroup of the sweep (2 per wave)
 constexpr int TS_PART = 8;                  // doubles per row of the sweep's partials
@@ -84,115 +73,20 @@ __global__ __launch_bounds__(256) void tsne_pad_kernel(const float* __restrict__
   xp[e] = k < d ? x[r * ld + k] : 0.f;
 }
 
-__global__ __launch_bounds__(256) void tsne_norm_kernel(const float* __restrict__ xp, int64_t N, int E4, double* __restrict__ norm) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= N) return;
-  const float4* p = reinterpret_cast<const float4*>(xp + r * E4);
-  double acc = 0.0;
-  for (int k = 0; k < (E4 >> 2); ++k) {
-    const float4 v = p[k];
-    acc = fma((double)v.x, (double)v.x, acc);
-    acc = fma((double)v.y, (double)v.y, acc);
-    acc = fma((double)v.z, (double)v.z, acc);
-    acc = fma((double)v.w, (double)v.w, acc);
-  }
-  norm[r] = acc;
-}
-
-// LDS: rows[64][TS_LD] | cols[64][TS_LD]
 __global__ __launch_bounds__(256) void tsne_dist_kernel(const float* __restrict__ xp, int E4, int N, const double* __restrict__ norm,
                                                        float* __restrict__ D) {
-  __shared__ __attribute__((aligned(16))) float sa[TS_TILE * TS_LD];
-  __shared__ __attribute__((aligned(16))) float sb[TS_TILE * TS_LD];
-  const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, q = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int i0 = blockIdx.y * TS_TILE, j0 = blockIdx.x * TS_TILE;
-  const int64_t ld = E4;
-  const int lr = tid >> 3, lc = (tid & 7) * 4;               // staging: rows lr and lr + 32, columns lc .. lc + 3 of the chunk
-
-  f32x4 acc[4];
-  double accd[4][4];                                          // G, folded in float64 after every chunk of 32 columns
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) accd[j][r] = 0.0;
-  }
-
-  for (int k0 = 0; k0 < E4; k0 += TS_KC) {
-    __syncthreads();                                          // the previous chunk has been multiplied
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int r = lr + 32 * h, k = k0 + lc;
-      const int ra = i0 + r, rb = j0 + r;
-      *reinterpret_cast<float4*>(sa + r * TS_LD + lc) = ld4_or_zero(xp + (int64_t)(ra < N ? ra : 0) * ld + (k < E4 ? k : 0), ra < N && k < E4);
-      *reinterpret_cast<float4*>(sb + r * TS_LD + lc) = ld4_or_zero(xp + (int64_t)(rb < N ? rb : 0) * ld + (k < E4 ? k : 0), rb < N && k < E4);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      if (k0 + 16 * ks < E4) {
-        const float4 a = *reinterpret_cast<const float4*>(sa + (16 * wave + i) * TS_LD + 16 * ks + 4 * q);
-        float4 b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const float4*>(sb + (16 * j + i) * TS_LD + 16 * ks + 4 * q);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.x, b[j].x, acc[j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.y, b[j].y, acc[j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.z, b[j].z, acc[j]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.w, b[j].w, acc[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) accd[j][r] += (double)acc[j][r];
-      acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  }
-
-  // lane (i, q), register r of acc[j]: G[row i0 + 16 wave + 4 q + r][col j0 + 16 j + i]
-  const int row0 = i0 + 16 * wave + 4 * q;
+  __shared__ __attribute__((aligned(16))) float sa[PD_TILE * PD_LD];
+  __shared__ __attribute__((aligned(16))) float sb[PD_TILE * PD_LD];
+  __builtin_assume((E4 & 3) == 0);                            // (the padded copy, d = E4: none of pd_tile's loads is masked)
+  const int64_t i0 = (int64_t)blockIdx.y * PD_TILE;
   double nr[4];
+  pd_row_norms(norm, N, i0, nr);
+  pd_tile(xp, E4, N, i0, nr, xp, E4, N, (int)blockIdx.x * PD_TILE, norm, E4, true, sa, sb,
+          [&](int64_t row, int col, const float (&dd)[4]) {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) nr[r] = row0 + r < N ? norm[row0 + r] : 0.0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = j0 + 16 * j + i;
-    const double nc = col < N ? norm[col] : 0.0;
-    float dd[4];
-    unsigned nm = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const double sum = nr[r] + nc;
-      const double d2 = fma(-2.0, accd[j][r], sum);
-      const bool valid = row0 + r < N && col < N && row0 + r != col;
-      const bool near = valid && d2 < (double)PD_NEAR * sum;
-      dd[r] = (valid && !near) ? (float)d2 : 0.f;
-      nm |= near ? (1u << r) : 0u;
-    }
-    unsigned long long pend = __ballot(nm != 0);
-    while (pend) {                                            // (wave-uniform) one lane's near pairs at a time, by the whole wave
-      const int L = __ffsll((long long)pend) - 1;
-      pend &= pend - 1;
-      const unsigned m4 = (unsigned)__shfl((int)nm, L);
-      const int rb = __shfl(row0, L), cb = __shfl(col, L);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if ((m4 >> r) & 1u) {
-          const int lo = min(rb + r, cb), hi = max(rb + r, cb);   // (one argument order for (i, j) and (j, i))
-          const double v = pd_pair_sq(xp, ld, E4, lo, hi, lane);
-          if (lane == L) dd[r] = (float)v;
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (row0 + r < N && col < N) D[(int64_t)(row0 + r) * N + col] = dd[r];
-  }
+            for (int r = 0; r < 4; ++r)
+              if (row + r < N && col < N) D[(row + r) * N + col] = dd[r];
+          });
 }
 
 // sum of (a, b) over the 256 threads in a fixed tree; every thread returns the same bits.  sh: 8 doubles
@@ -219,34 +113,24 @@ __global__ __launch_bounds__(256) void tsne_search_kernel(float* __restrict__ P,
   for (int j = tid; j < N; j += 256) drow[j] = prow[j];
   __syncthreads();
 
-  double beta = 1.0, beta_eval = 1.0, beta_min = -__builtin_inf(), beta_max = __builtin_inf(), sum_p = 1.0;
-  for (int step = 0; step < 100; ++step) {
+  TsBisect bs;
+  for (int step = 0; step < TS_BISECT_STEPS; ++step) {
     double s0 = 0.0, s1 = 0.0;
-    beta_eval = beta;                                         // (sklearn keeps the probabilities of the last beta it EVALUATED)
     for (int j = tid; j < N; j += 256) {
       if (j != i) {
         const double dj = (double)drow[j];
-        const double e = exp(-dj * beta);
+        const double e = exp(-dj * bs.beta);
         s0 += e;
         s1 = fma(dj, e, s1);
       }
     }
     ts_block_sum2(s0, s1, sh);
-    sum_p = s0 == 0.0 ? 1e-8 : s0;
-    const double diff = log(sum_p) + beta * (s1 / sum_p) - log_perp;
-    if (fabs(diff) <= 1e-5) break;                            // (uniform: every thread holds the same bits)
-    if (diff > 0.0) {
-      beta_min = beta;
-      beta = beta_max == __builtin_inf() ? beta * 2.0 : (beta + beta_max) * 0.5;
-    } else {
-      beta_max = beta;
-      beta = beta_min == -__builtin_inf() ? beta * 0.5 : (beta + beta_min) * 0.5;
-    }
+    if (ts_bisect_next(bs, s0, s1, log_perp)) break;          // (uniform: every thread holds the same bits)
   }
   double rs = 0.0, unused = 0.0;
   for (int j = tid; j < N; j += 256) {
     float c = 0.f;
-    if (j != i) c = (float)(exp(-(double)drow[j] * beta_eval) / sum_p);
+    if (j != i) c = (float)(exp(-(double)drow[j] * bs.beta_eval) / bs.sum_p);
     prow[j] = c;
     rs += (double)c;
   }
@@ -263,19 +147,19 @@ __global__ __launch_bounds__(1024) void tsne_total_kernel(const double* __restri
 }
 
 __global__ __launch_bounds__(256) void tsne_sym_kernel(float* __restrict__ P, int N, const double* __restrict__ sigma) {
-  __shared__ float ta[TS_TILE][TS_TILE + 1];
-  __shared__ float tb[TS_TILE][TS_TILE + 1];
+  __shared__ float ta[PD_TILE][PD_TILE + 1];
+  __shared__ float tb[PD_TILE][PD_TILE + 1];
   const int a = blockIdx.y, b = blockIdx.x;
   if (a > b) return;
-  const int i0 = a * TS_TILE, j0 = b * TS_TILE;
+  const int i0 = a * PD_TILE, j0 = b * PD_TILE;
   const int c = threadIdx.x & 63, r0 = threadIdx.x >> 6;
   const double sg = sigma[0];
-  for (int r = r0; r < TS_TILE; r += 4) {
+  for (int r = r0; r < PD_TILE; r += 4) {
     ta[r][c] = (i0 + r < N && j0 + c < N) ? P[(int64_t)(i0 + r) * N + j0 + c] : 0.f;
     tb[r][c] = (j0 + r < N && i0 + c < N) ? P[(int64_t)(j0 + r) * N + i0 + c] : 0.f;
   }
   __syncthreads();
-  for (int r = r0; r < TS_TILE; r += 4) {
+  for (int r = r0; r < PD_TILE; r += 4) {
     if (i0 + r < N && j0 + c < N) {
       const double v = ((double)ta[r][c] + (double)tb[c][r]) / sg;
       P[(int64_t)(i0 + r) * N + j0 + c] = (i0 + r == j0 + c) ? 0.f : (float)fmax(v, DBL_EPSILON);
@@ -330,7 +214,7 @@ __global__ __launch_bounds__(256) void tsne_sweep_kernel(const float* __restrict
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const float dx = yi[h].x - yj.x, dy = yi[h].y - yj.y;
-            const float q = 1.0f / (1.0f + fmaf(dx, dx, dy * dy));
+            const float q = ts_q(dx, dy);
             const double qd = (double)q, p = exag * (double)pv[h][u];
             const double wa = p * qd, wr = qd * qd;
             att_x[h] = fma(wa, (double)dx, att_x[h]);
@@ -405,15 +289,11 @@ __global__ __launch_bounds__(1024) void tsne_update_kernel(float* __restrict__ y
   __shared__ double sh[1024];
   double acc = 0.0;
   for (int64_t e = threadIdx.x; e < n; e += 1024) {
-    const float g = grad[e], v = vel[e];
-    float gn = gains[e];
-    gn = (__fmul_rn(v, g) < 0.f) ? __fadd_rn(gn, 0.2f) : __fmul_rn(gn, 0.8f);
-    gn = fmaxf(gn, 0.01f);
-    const float gg = __fmul_rn(g, gn);
-    const float vn = __fsub_rn(__fmul_rn(momentum, v), __fmul_rn(lr, gg));
+    float ye = y[e], v = vel[e], gn = gains[e];
+    const float gg = ts_step(grad[e], momentum, lr, ye, v, gn);
     gains[e] = gn;
-    vel[e] = vn;
-    y[e] = __fadd_rn(y[e], vn);
+    vel[e] = v;
+    y[e] = ye;
     acc = fma((double)gg, (double)gg, acc);
   }
   if (gnorm2) {                                               // (uniform)
@@ -475,9 +355,9 @@ extern "C" int g2v_tsne_affinities(const float* x, int64_t ld, int64_t N, int d,
   double* norm = (double*)(ws + l.norm);
   double* rowsum = (double*)(ws + l.rowsum);
   double* sigma = (double*)(ws + l.sigma);
-  const int n = (int)N, T = cdiv(N, TS_TILE);
+  const int n = (int)N, T = cdiv(N, PD_TILE);
   hipLaunchKernelGGL(tsne_pad_kernel, dim3(cdiv(N * l.E4, 256)), dim3(256), 0, st, x, ld, N, d, l.E4, xp);
-  hipLaunchKernelGGL(tsne_norm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, (const float*)xp, N, l.E4, norm);
+  hipLaunchKernelGGL(pd_norm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, (const float*)xp, (int64_t)l.E4, N, l.E4, norm);
   hipLaunchKernelGGL(tsne_dist_kernel, dim3(T, T), dim3(256), 0, st, (const float*)xp, l.E4, n, (const double*)norm, P);
   hipLaunchKernelGGL(tsne_search_kernel, dim3(n), dim3(256), (size_t)N * sizeof(float), st, P, n, log(perplexity), rowsum);
   hipLaunchKernelGGL(tsne_total_kernel, dim3(1), dim3(1024), 0, st, (const double*)rowsum, n, sigma);

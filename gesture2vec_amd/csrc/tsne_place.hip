@@ -4,13 +4,10 @@
 // their map, Z (M, d) the new rows.  Every new row is its own problem and Y does not move.
 //
 // g2v_tsne_place_neighbors
-//   place_norm_kernel   |row|^2 in float64 over the d columns (one thread per row, the fma chain of tsne_norm_kernel)
+//   pd_norm_kernel      |row|^2 in float64 over the d columns (pair_dist.hpp)
 //   place_knn_kernel    one workgroup (4 waves) per 64 new rows, streaming over the 64-column tiles of the reference rows.  A tile of
-//                       squared distances is formed as tsne_dist_kernel forms it -- both row sets through LDS in k-chunks of 32,
-//                       v_mfma_f32_16x16x4_f32, the accumulators folded into float64 after every chunk, d^2 = n_i + n_j - 2 G in
-//                       float64 rounded to fp32 once, a NEAR pair (d^2 < (n_i + n_j) / 8) re-evaluated from differences in float64
-//                       by the whole wave -- the same bits as g2v_tsne_affinities gives for the same two rows; columns >= d are
-//                       masked at the load, so the rows need no padded copy.  The tile goes to LDS and never to memory.  Selection:
+//                       squared distances is formed by pd_tile (pair_dist.hpp), which tsne_dist_kernel calls too: the same bits as
+//                       g2v_tsne_affinities gives for the same two rows.  The tile goes to LDS and never to memory.  Selection:
 //                       wave w owns tile rows 16 w .. 16 w + 15 and their sorted lists of the kk best (d^2, index) in LDS.  Per row
 //                       the 64 candidates of the tile sit one per lane; a ballot against the running kk-th best finds the few that
 //                       enter, and each is inserted with the list in registers (slot s in lane s & 63): its place is a popcount,
@@ -22,14 +19,14 @@
 //                       the distance itself and moved the conditionals by 1.6e-5 of a row's largest (measured).
 // g2v_tsne_place_conditionals
 //   place_cond_kernel   one lane per row, 64 rows per workgroup, the first k_aff distances of each row in LDS: sklearn's bisection of
-//                       the precision in float64 exactly as tsne_search_kernel runs it, without a term to leave out; the sums
-//                       run over j ascending.
+//                       the precision (tsne_cells.hpp, as tsne_search_kernel), without a term to leave out; the sums run over
+//                       j ascending.
 // g2v_tsne_place_init
 //   place_init_kernel   one lane per row.  median: the k_use gathered coordinates in LDS, rank of each by counting (ties by
 //                       position), numpy's rule for an even count; weighted: sum p Y in float64 over j ascending.
 // g2v_tsne_place_descent
 //   ALL n_iter iterations and the closing sweep run in one launch; y, velocity and gains live in registers.  dy and
-//   w = 1 / (1 + |dy|^2) are fp32 as tsne_sweep_kernel takes its q; sum w and sum w^2 dy are float64, formed per BLOCK of 128
+//   w = 1 / (1 + |dy|^2) are fp32 (ts_q, tsne_cells.hpp); sum w and sum w^2 dy are float64, formed per BLOCK of 128
 //   reference points over j ascending and the block sums added in ascending block order; the attraction over the row's k_aff
 //   neighbours (gathered) is float64 over j ascending.  That order is fixed by N alone and both layouts keep it, so a row's bits
 //   depend on that row, Y and the parameters only: not on M, the layout, the grid or the row's place in the batch.
@@ -45,6 +42,7 @@
 #include "common.hpp"
 #include "km_sort.hpp"
 #include "pair_dist.hpp"
+#include "tsne_cells.hpp"
 
 namespace g2v {
 namespace {
@@ -53,9 +51,6 @@ constexpr int PL_MAX_D = 512;
 constexpr int PL_MAX_KK = 128;
 constexpr int64_t PL_MAX_N = (1 << 24) - 1;
 constexpr int64_t PL_MAX_M = 2147483647LL;
-constexpr int PL_TILE = 64;
-constexpr int PL_KC = 32;
-constexpr int PL_LD = PL_KC + 4;            // LDS row stride of a staged chunk (an odd number of 16-byte slots)
 constexpr int PL_YCH = 2048;                // points of Y per LDS stage of the descent
 constexpr int PL_GRID = 1024;               // workgroups of the descent (4 per CU); row groups beyond are taken in turn
 constexpr int PL_BLK = 128;                 // reference points per block: block sums are formed j ascending, then added b ascending
@@ -68,149 +63,34 @@ static_assert(PL_YCH % PL_BLK == 0, "a stage of Y holds whole blocks");
 
 inline size_t place_norm_offset(int64_t N) { return km_align((size_t)N * sizeof(double)); }
 
-__global__ __launch_bounds__(256) void place_norm_kernel(const float* __restrict__ x, int64_t ld, int64_t n, int d,
-                                                        double* __restrict__ norm) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= n) return;
-  const float* p = x + r * ld;
-  double acc = 0.0;
-  for (int k = 0; k < d; ++k) acc = fma((double)p[k], (double)p[k], acc);
-  norm[r] = acc;
-}
-
-// columns k .. k + 3 of a row of d columns (k % 4 == 0, the row 16-byte aligned), zero from column d on and where !ok
-__device__ __forceinline__ float4 pl_ld4(const float* __restrict__ row, int k, int d, bool ok) {
-  if (ok && k + 3 < d) return *reinterpret_cast<const float4*>(row + k);
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ok) {
-    if (k < d) v.x = row[k];
-    if (k + 1 < d) v.y = row[k + 1];
-    if (k + 2 < d) v.z = row[k + 2];
-  }
-  return v;
-}
-
-// |z - x|^2 in float64 by a whole wave: pd_pair_sq over two row sets, with the columns masked
-__device__ __forceinline__ double pl_pair_sq(const float* __restrict__ zr, const float* __restrict__ xr, int d, int lane) {
-  double acc = 0.0;
-  for (int v = lane; 4 * v < d; v += 64) {
-    const float4 a = pl_ld4(zr, 4 * v, d, true), b = pl_ld4(xr, 4 * v, d, true);
-    const double d0 = (double)a.x - (double)b.x, d1 = (double)a.y - (double)b.y, d2 = (double)a.z - (double)b.z,
-                 d3 = (double)a.w - (double)b.w;
-    acc = fma(d0, d0, acc);
-    acc = fma(d1, d1, acc);
-    acc = fma(d2, d2, acc);
-    acc = fma(d3, d3, acc);
-  }
-  return km_wave_sum(acc);
-}
-
-// dynamic LDS: best_d[64][kk] float | best_i[64][kk] int
-__global__ __launch_bounds__(256) void place_knn_kernel(const float* __restrict__ X, int64_t ldx, int N, const float* __restrict__ Z,
-                                                       int64_t ldz, int64_t M, int d, int kk, const double* __restrict__ nx,
-                                                       const double* __restrict__ nz, int* __restrict__ idx_out,
-                                                       float* __restrict__ d2_out) {
-  __shared__ __attribute__((aligned(16))) float sa[PL_TILE * PL_LD];
-  __shared__ __attribute__((aligned(16))) float sb[PL_TILE * PL_LD];
-  __shared__ float dt[PL_TILE][PL_TILE + 1];
+// dynamic LDS: best_d[64][kk] float | best_i[64][kk] int.  waves_per_eu(4): the LDS lets four workgroups share a CU up to kk = 11,
+// and the register allocator left alone lands a few registers either side of the 128 that allow them.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void place_knn_kernel(
+    const float* __restrict__ X, int64_t ldx, int N, const float* __restrict__ Z, int64_t ldz, int64_t M, int d, int kk,
+    const double* __restrict__ nx, const double* __restrict__ nz, int* __restrict__ idx_out, float* __restrict__ d2_out) {
+  __shared__ __attribute__((aligned(16))) float sa[PD_TILE * PD_LD];
+  __shared__ __attribute__((aligned(16))) float sb[PD_TILE * PD_LD];
+  __shared__ float dt[PD_TILE][PD_TILE + 1];
   extern __shared__ __attribute__((aligned(16))) float best[];
   float* best_d = best;
-  int* best_i = reinterpret_cast<int*>(best + PL_TILE * kk);
-  const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, q = lane >> 4;
+  int* best_i = reinterpret_cast<int*>(best + PD_TILE * kk);
+  const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t i0 = (int64_t)blockIdx.x * PL_TILE;
-  const int E4 = (d + 3) & ~3;
-  const int lr = tid >> 3, lc = (tid & 7) * 4;               // staging: rows lr and lr + 32, columns lc .. lc + 3 of the chunk
+  const int64_t i0 = (int64_t)blockIdx.x * PD_TILE;
   const float inf = __builtin_inff();
 
-  for (int e = tid; e < PL_TILE * kk; e += 256) {
+  for (int e = tid; e < PD_TILE * kk; e += 256) {
     best_d[e] = inf;
     best_i[e] = INT_MAX;
   }
-  const int64_t row0 = i0 + 16 * wave + 4 * q;                // lane (i, q), register r: new row row0 + r
   double nr[4];
+  pd_row_norms(nz, M, i0, nr);
+  for (int j0 = 0; j0 < N; j0 += PD_TILE) {
+    // (pd_tile's first barrier: the lists are set, the previous tile has been selected from)
+    pd_tile(Z, ldz, M, i0, nr, X, ldx, N, j0, nx, d, false, sa, sb, [&](int64_t row, int col, const float (&dd)[4]) {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) nr[r] = row0 + r < M ? nz[row0 + r] : 0.0;
-
-  for (int j0 = 0; j0 < N; j0 += PL_TILE) {
-    f32x4 acc[4];
-    double accd[4][4];                                        // G, folded in float64 after every chunk of 32 columns
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) accd[j][r] = 0.0;
-    }
-    for (int k0 = 0; k0 < E4; k0 += PL_KC) {
-      __syncthreads();                                        // the previous chunk has been multiplied (and the lists are set)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int r = lr + 32 * h, k = k0 + lc;
-        const int64_t ra = i0 + r;
-        const int rb = j0 + r;
-        *reinterpret_cast<float4*>(sa + r * PL_LD + lc) = pl_ld4(Z + (ra < M ? ra : 0) * ldz, k, d, ra < M);
-        *reinterpret_cast<float4*>(sb + r * PL_LD + lc) = pl_ld4(X + (int64_t)(rb < N ? rb : 0) * ldx, k, d, rb < N);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        if (k0 + 16 * ks < E4) {
-          const float4 a = *reinterpret_cast<const float4*>(sa + (16 * wave + i) * PL_LD + 16 * ks + 4 * q);
-          float4 b[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const float4*>(sb + (16 * j + i) * PL_LD + 16 * ks + 4 * q);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.x, b[j].x, acc[j]);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.y, b[j].y, acc[j]);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.z, b[j].z, acc[j]);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = mfma16(a.w, b[j].w, acc[j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) accd[j][r] += (double)acc[j][r];
-        acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
-    }
-
-    // lane (i, q), register r of acc[j]: G[new row row0 + r][reference row j0 + 16 j + i]
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int col = j0 + 16 * j + i;
-      const double nc = col < N ? nx[col] : 0.0;
-      float dd[4];
-      unsigned nm = 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const double sum = nr[r] + nc;
-        const double d2 = fma(-2.0, accd[j][r], sum);
-        const bool valid = row0 + r < M && col < N;
-        const bool near = valid && d2 < (double)PD_NEAR * sum;
-        dd[r] = valid ? (near ? 0.f : (float)d2) : inf;
-        nm |= near ? (1u << r) : 0u;
-      }
-      unsigned long long pend = __ballot(nm != 0);
-      while (pend) {                                          // (wave-uniform) one lane's near pairs at a time, by the whole wave
-        const int L = __ffsll((long long)pend) - 1;
-        pend &= pend - 1;
-        const unsigned m4 = (unsigned)__shfl((int)nm, L);
-        const int cb = __shfl(col, L);
-        const int64_t rb = i0 + 16 * wave + 4 * (L >> 4);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if ((m4 >> r) & 1u) {
-            const double v = pl_pair_sq(Z + (rb + r) * ldz, X + (int64_t)cb * ldx, d, lane);
-            if (lane == L) dd[r] = (float)v;
-          }
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dt[16 * wave + 4 * q + r][16 * j + i] = dd[r];
-    }
+      for (int r = 0; r < 4; ++r) dt[(int)(row - i0) + r][col - j0] = dd[r];
+    });
     __syncthreads();
 
     // selection: this wave's 16 rows, the tile's 64 candidates one per lane
@@ -278,7 +158,7 @@ __global__ __launch_bounds__(256) void place_refine_kernel(const float* __restri
   float e0 = __builtin_inff(), e1 = __builtin_inff();
   for (int s = 0; s < kk; ++s) {
     const int id = __shfl(s < 64 ? n0 : n1, s & 63);
-    const float v = (float)pl_pair_sq(zr, X + (int64_t)id * ldx, d, lane);
+    const float v = (float)pd_pair_sq(zr, X + (int64_t)id * ldx, d, lane);
     if (s == lane) e0 = v;
     if (s == lane + 64) e1 = v;
   }
@@ -312,28 +192,18 @@ __global__ __launch_bounds__(64) void place_cond_kernel(const float* __restrict_
   __syncthreads();
   const int64_t row = r0 + lane;
   if (row >= M) return;
-  double beta = 1.0, beta_eval = 1.0, beta_min = -__builtin_inf(), beta_max = __builtin_inf(), sum_p = 1.0;
-  for (int step = 0; step < 100; ++step) {
+  TsBisect bs;
+  for (int step = 0; step < TS_BISECT_STEPS; ++step) {
     double s0 = 0.0, s1 = 0.0;
-    beta_eval = beta;                                         // (sklearn keeps the probabilities of the last beta it EVALUATED)
     for (int j = 0; j < k_aff; ++j) {
       const double dj = (double)ds[j][lane];
-      const double e = exp(-dj * beta);
+      const double e = exp(-dj * bs.beta);
       s0 += e;
       s1 = fma(dj, e, s1);
     }
-    sum_p = s0 == 0.0 ? 1e-8 : s0;
-    const double diff = log(sum_p) + beta * (s1 / sum_p) - log_perp;
-    if (fabs(diff) <= 1e-5) break;
-    if (diff > 0.0) {
-      beta_min = beta;
-      beta = beta_max == __builtin_inf() ? beta * 2.0 : (beta + beta_max) * 0.5;
-    } else {
-      beta_max = beta;
-      beta = beta_min == -__builtin_inf() ? beta * 0.5 : (beta + beta_min) * 0.5;
-    }
+    if (ts_bisect_next(bs, s0, s1, log_perp)) break;
   }
-  for (int j = 0; j < k_aff; ++j) p[row * k_aff + j] = (float)(exp(-(double)ds[j][lane] * beta_eval) / sum_p);
+  for (int j = 0; j < k_aff; ++j) p[row * k_aff + j] = (float)(exp(-(double)ds[j][lane] * bs.beta_eval) / bs.sum_p);
 }
 
 __device__ __forceinline__ int pl_ref_index(int id, int N) { return (unsigned)id < (unsigned)N ? id : 0; }
@@ -382,7 +252,7 @@ __global__ __launch_bounds__(64) void place_init_kernel(const float* __restrict_
 // one reference point: sum w^2 (y - Y_j) and sum w of a block, in float64
 __device__ __forceinline__ void pl_pair(const float2 yi, const float2 yj, double& bx, double& by, double& bz) {
   const float dx = yi.x - yj.x, dy = yi.y - yj.y;
-  const float w = 1.0f / (1.0f + fmaf(dx, dx, dy * dy));
+  const float w = ts_q(dx, dy);
   const double wd = (double)w, wr = wd * wd;
   bx = fma(wr, (double)dx, bx);
   by = fma(wr, (double)dy, by);
@@ -396,7 +266,7 @@ __device__ __forceinline__ void pl_attract(const float2* __restrict__ Y, int N, 
   for (int j = 0; j < k_aff; ++j) {
     const float2 yj = Y[pl_ref_index(ir[j], N)];
     const float dx = yi.x - yj.x, dy = yi.y - yj.y;
-    const float w = 1.0f / (1.0f + fmaf(dx, dx, dy * dy));
+    const float w = ts_q(dx, dy);
     const double pd = (double)pr[j], wd = (double)w, pw = pd * wd;
     a[0] = fma(pw, (double)dx, a[0]);
     a[1] = fma(pw, (double)dy, a[1]);
@@ -413,7 +283,7 @@ __device__ __forceinline__ float2 pl_gradient(double ex, const double (&a)[4], d
 
 __device__ __forceinline__ double pl_kl(const double (&a)[4], double z) { return fma(log(z), a[3], a[2]); }
 
-// one step, fp32, no contraction: clip by the norm, gains, velocity, y
+// one step, fp32, no contraction: clip by the norm, then ts_step per component
 __device__ __forceinline__ void pl_step(float2 g, float momentum, float lr, float max_gnorm, float2& yi, float2& v, float2& gn) {
   const float n = __fsqrt_rn(__fadd_rn(__fmul_rn(g.x, g.x), __fmul_rn(g.y, g.y)));
   if (max_gnorm > 0.f && n > max_gnorm) {
@@ -421,12 +291,8 @@ __device__ __forceinline__ void pl_step(float2 g, float momentum, float lr, floa
     g.x = __fmul_rn(g.x, s);
     g.y = __fmul_rn(g.y, s);
   }
-  gn.x = fmaxf((__fmul_rn(v.x, g.x) < 0.f) ? __fadd_rn(gn.x, 0.2f) : __fmul_rn(gn.x, 0.8f), 0.01f);
-  gn.y = fmaxf((__fmul_rn(v.y, g.y) < 0.f) ? __fadd_rn(gn.y, 0.2f) : __fmul_rn(gn.y, 0.8f), 0.01f);
-  v.x = __fsub_rn(__fmul_rn(momentum, v.x), __fmul_rn(lr, __fmul_rn(g.x, gn.x)));
-  v.y = __fsub_rn(__fmul_rn(momentum, v.y), __fmul_rn(lr, __fmul_rn(g.y, gn.y)));
-  yi.x = __fadd_rn(yi.x, v.x);
-  yi.y = __fadd_rn(yi.y, v.y);
+  ts_step(g.x, momentum, lr, yi.x, v.x, gn.x);
+  ts_step(g.y, momentum, lr, yi.y, v.y, gn.y);
 }
 
 // one lane per row
@@ -583,7 +449,7 @@ extern "C" int g2v_tsne_place_neighbors(const float* X, int64_t ldx, int64_t N, 
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute((const void*)place_knn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            PL_TILE * PL_MAX_KK * 8) != hipSuccess) {
+                            PD_TILE * PL_MAX_KK * 8) != hipSuccess) {
       set_error("g2v_tsne_place_neighbors: cannot reserve LDS");
       return G2V_ERR_LAUNCH;
     }
@@ -592,9 +458,9 @@ extern "C" int g2v_tsne_place_neighbors(const float* X, int64_t ldx, int64_t N, 
   hipStream_t st = (hipStream_t)stream;
   double* nx = (double*)workspace;
   double* nz = (double*)((char*)workspace + place_norm_offset(N));
-  hipLaunchKernelGGL(place_norm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, X, ldx, N, d, nx);
-  hipLaunchKernelGGL(place_norm_kernel, dim3(cdiv(M, 256)), dim3(256), 0, st, Z, ldz, M, d, nz);
-  hipLaunchKernelGGL(place_knn_kernel, dim3(cdiv(M, PL_TILE)), dim3(256), (size_t)PL_TILE * kk * 8, st, X, ldx, (int)N, Z, ldz, M, d,
+  hipLaunchKernelGGL(pd_norm_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, X, ldx, N, d, nx);
+  hipLaunchKernelGGL(pd_norm_kernel, dim3(cdiv(M, 256)), dim3(256), 0, st, Z, ldz, M, d, nz);
+  hipLaunchKernelGGL(place_knn_kernel, dim3(cdiv(M, PD_TILE)), dim3(256), (size_t)PD_TILE * kk * 8, st, X, ldx, (int)N, Z, ldz, M, d,
                      kk, (const double*)nx, (const double*)nz, idx, d2);
   hipLaunchKernelGGL(place_refine_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, X, ldx, (int)N, Z, ldz, M, d, kk, idx, d2);
   G2V_CHECK_LAUNCH();
