@@ -33,19 +33,16 @@ static int device_cu_count() {
   }
   return n;
 }
-// (the switch lives in the calling thread's context: g2v_ctx, G2V_OPT_PERSISTENT; the library reads no environment variable)
-static bool persist_enabled() { return g2v_internal_options().persist != 0; }
-// Row tiles per workgroup of a persistent rollout over `nblk` row tiles: 1 while there is a CU per tile, 2 or 3 beyond that
-// (dec_persist.hip, the *_mt kernels); 0: not offered.  G2V_OPT_PERSISTENT 2 / 3 asks for at least that many (parity tests of the
+// Row tiles per workgroup of a persistent rollout over `nblk` row tiles on `cus` CUs under G2V_OPT_PERSISTENT = `level` (the switch
+// lives in the calling thread's context, g2v_ctx; the library reads no environment variable): 1 while there is a CU per tile, 2 or 3
+// beyond that (dec_persist.hip, the *_mt kernels); 0: not offered.  Levels 2 / 3 ask for at least that many (parity tests of the
 // multi-tile kernels at small batches).
 constexpr int PERSIST_MAX_TILES_PER_WG = 3;
-static int persist_tiles_per_wg(int nblk) {
-  if (!persist_enabled() || nblk <= 0) return 0;
-  const int cus = device_cu_count() < PX_MAX_NBLK ? device_cu_count() : PX_MAX_NBLK;
-  if (cus <= 0) return 0;
+static int persist_tiles(int nblk, int level, int cus) {
+  if (cus > PX_MAX_NBLK) cus = PX_MAX_NBLK;
+  if (level <= 0 || nblk <= 0 || cus <= 0) return 0;
   int r = cdiv(nblk, cus);
-  const int want = g2v_internal_options().persist;
-  if (want > r) r = want < nblk ? want : (nblk > 1 ? nblk : 1);
+  if (level > r) r = level < nblk ? level : (nblk > 1 ? nblk : 1);
   return r <= PERSIST_MAX_TILES_PER_WG ? r : 0;
 }
 
@@ -1031,15 +1028,16 @@ static size_t dec_cluster_bwd_dyn_lds() { return (size_t)4 * 13 /* DCL_KS */ * 6
 static size_t dec_cluster_fwd_dyn_lds() {      // W_out fragments, partial out-layer products, Dropout(h0) rows, input-side accumulators
   return ((size_t)4 * DCL_KS + (size_t)4 * 4 /* DSPLIT_DT */ + (size_t)DCL_KS + 3) * 64 * sizeof(float4);
 }
-static bool dec_cluster_shape(int D, int H) { return !(H == 64 && D == 135) && (H & 3) == 0 && H <= 16 * DCL_KS && D <= 64 && H >= 4; }
+// The three shape classes of the dispatch (dec_route_plan).  Prepared: the fused kernels whose dims are compile-time constants (the
+// BASELINE shape) -- the persistent pair, and the only shape whose *_prepared workspaces are honoured.  Cluster: what
+// dec_cluster_*_kernel is built for.  Split (dec_split_shape, below the split kernels' constants): the per-phase launches.
+static bool dec_prepared_shape(int D, int H) { return H == 64 && D == 135; }
+static bool dec_cluster_shape(int D, int H) { return !dec_prepared_shape(D, H) && (H & 3) == 0 && H <= 16 * DCL_KS && D <= 64 && H >= 4; }
+// the workspace queries size the cluster kernel's records for the largest grid it is admitted for: one workgroup per CU
+static int dec_cluster_max_nblk(int H) { return (device_cu_count() > 0 ? device_cu_count() : 256) / ((H + 15) >> 4) + 1; }
 extern "C" size_t g2v_dec_rollout_fwd_workspace(int D, int H) {
-  size_t x = PX_BYTES;
-  if (dec_cluster_shape(D, H)) {      // the largest grid the cluster kernel is admitted for: one workgroup per CU
-    const int nt = (H + 15) >> 4, cus = device_cu_count() > 0 ? device_cu_count() : 256;
-    const size_t c = dec_cluster_fwd_xch_bytes(cus / nt + 1, H);
-    if (c > x) x = c;
-  }
-  return fwd_pack_bytes_aligned(D, H) + x;
+  const size_t c = dec_cluster_shape(D, H) ? dec_cluster_fwd_xch_bytes(dec_cluster_max_nblk(H), H) : 0;
+  return fwd_pack_bytes_aligned(D, H) + (c > PX_BYTES ? c : PX_BYTES);
 }
 
 // ====================================================================================================================
@@ -2434,40 +2432,278 @@ __global__ __launch_bounds__(128) void dec_bwd_pair_split_kernel(DecBwdPairArgs 
   }
 }
 
-// The weight fragments of the fused kernels (per-step and persistent alike), in workspace order.
-static DecPackF dec_fwd_pack_layout(const g2v_dec_weights* w, int D, int H, void* workspace, PackBatch& pb) {
-  float* p = (float*)workspace;
-  DecPackF pk;
-  pb.n = 6;
-  pb.d[0] = PackDesc{w->w_pre, p, H, 1, 0, D, D, 0, 0}; pk.pre = p; p += pack_floats(H, 1, D);
-  pb.d[1] = PackDesc{w->w_ih0, p, H, 3, H, H, H, 0, 0}; pk.ih0 = p; p += pack_floats(H, 3, H);
-  pb.d[2] = PackDesc{w->w_hh0, p, H, 3, H, H, H, 0, 0}; pk.hh0 = p; p += pack_floats(H, 3, H);
-  pb.d[3] = PackDesc{w->w_ih1, p, H, 3, H, H, H, 0, 0}; pk.ih1 = p; p += pack_floats(H, 3, H);
-  pb.d[4] = PackDesc{w->w_hh1, p, H, 3, H, H, H, 0, 0}; pk.hh1 = p; p += pack_floats(H, 3, H);
-  pb.d[5] = PackDesc{w->w_out, p, D, 1, 0, H, H, 0, dtiles_pad(D)}; pk.out = p;
-  return pk;
-}
-static DecTW dec_bwd_pack_layout(const g2v_dec_weights* w, int D, int H, void* workspace, PackBatch& pb) {
-  float* p = (float*)workspace;
-  DecTW tw;
-  pb.n = 6;
-  const int G = 3 * H;
-  pb.d[0] = PackDesc{w->w_pre, p, D, 1, 0, H, D, 1, dtiles_pad(D)}; tw.w_pre_t = p; p += (size_t)dtiles_pad(D) * pack_ks(H) * 256;   // rows d, k = f: W_pre[f][d]
-  pb.d[1] = PackDesc{w->w_out, p, H, 1, 0, D, H, 1, 0}; tw.w_out_t = p; p += pack_floats(H, 1, D);   // rows f, k = d: W_out[d][f]
-  pb.d[2] = PackDesc{w->w_ih0, p, H, 1, 0, G, H, 1, 0}; tw.w_ih0_t = p; p += pack_floats(H, 1, G);   // rows k, contraction g: W[g][k]
-  pb.d[3] = PackDesc{w->w_hh0, p, H, 1, 0, G, H, 1, 0}; tw.w_hh0_t = p; p += pack_floats(H, 1, G);
-  pb.d[4] = PackDesc{w->w_ih1, p, H, 1, 0, G, H, 1, 0}; tw.w_ih1_t = p; p += pack_floats(H, 1, G);
-  pb.d[5] = PackDesc{w->w_hh1, p, H, 1, 0, G, H, 1, 0}; tw.w_hh1_t = p;
-  return tw;
-}
-// prepared workspaces are honoured by the fused H = 64, D = 135 kernels only (the split kernels of other shapes transpose)
-static bool dec_prepared_shape(int D, int H) { return H == 64 && D == 135; }
+// ====================================================================================================================
+// Host side.  Which of the five implementations a call runs on is decided in ONE place, dec_route_plan (DESIGN.md section 3.2.1;
+// each route's admission rule: include/g2v.h at g2v_dec_rollout_route).  g2v_dec_rollout_fwd / _bwd validate, plan and launch
+// from the plan; the public queries plan an ideal call and return a field of the result.
+// ====================================================================================================================
+template <class... P>
+static bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }      // (NULL counts as aligned)
 
+static bool dec_split_shape(int B, int D, int H) {
+  return !dec_prepared_shape(D, H) && cdiv(B, 16) <= DSPLIT_MAX_NBLK && (H & 3) == 0 && H <= 16 * DSPLIT_KS && 3 * H <= 16 * DSPLIT_KSG &&
+         D <= 16 * DSPLIT_DT;
+}
+
+// ---- workspaces: sizes, and one view per direction that names every region -----------------------------------------
+// split path (small batch): six plain transposes + two (B <= 1024, H) scratch arrays
+static size_t split_bwd_total(int D, int H) { return (size_t)2 * D * H + (size_t)12 * H * H + (size_t)2 * 16 * DSPLIT_MAX_NBLK * H; }
+static size_t bwd_pack_bytes_aligned(int D, int H) { return (pack_bwd_total(D, H) * sizeof(float) + 255) / 256 * 256; }
+// the fused-weight-gradient persistent backward appends its per-workgroup partial dW / db (PX_MAX_NBLK workgroups)
+static size_t bwd_wslab_bytes(int D, int H) {
+  return dec_prepared_shape(D, H) ? (size_t)PX_MAX_NBLK * dec_persist_bwd_wgrad_slab_floats() * sizeof(float) : 0;
+}
+extern "C" size_t g2v_dec_rollout_bwd_workspace(int D, int H) {
+  const size_t a = bwd_pack_bytes_aligned(D, H) + PX_BYTES + bwd_wslab_bytes(D, H), b = split_bwd_total(D, H) * sizeof(float);
+  const size_t c = dec_cluster_shape(D, H) ? dec_cluster_bwd_xch_bytes(dec_cluster_max_nblk(H), H) : 0;
+  const size_t ab = a > b ? a : b;
+  return ab > c ? ab : c;
+}
+
+// Forward: [six weight images in MFMA fragment order (the fused kernels, per-step and persistent alike) | 256-byte aligned: the
+// persistent kernel's PersistX (PX_BYTES), or in its place the cluster kernel's records over `cluster_nblk` row groups].
+struct DecFwdWs {
+  DecPackF pk; PackBatch pb;      // the images and the descriptors that fill them (launch_pack)
+  void* xbase;
+  unsigned long long *xu, *xh0, *xh1, *xp; unsigned* xcc;      // (cluster_nblk == 0: unused)
+};
+static DecFwdWs dec_fwd_ws(const g2v_dec_weights* w, int D, int H, void* workspace, int cluster_nblk = 0) {
+  DecFwdWs v;
+  float* p = (float*)workspace;
+  v.pb.n = 6;
+  v.pb.d[0] = PackDesc{w->w_pre, p, H, 1, 0, D, D, 0, 0}; v.pk.pre = p; p += pack_floats(H, 1, D);
+  v.pb.d[1] = PackDesc{w->w_ih0, p, H, 3, H, H, H, 0, 0}; v.pk.ih0 = p; p += pack_floats(H, 3, H);
+  v.pb.d[2] = PackDesc{w->w_hh0, p, H, 3, H, H, H, 0, 0}; v.pk.hh0 = p; p += pack_floats(H, 3, H);
+  v.pb.d[3] = PackDesc{w->w_ih1, p, H, 3, H, H, H, 0, 0}; v.pk.ih1 = p; p += pack_floats(H, 3, H);
+  v.pb.d[4] = PackDesc{w->w_hh1, p, H, 3, H, H, H, 0, 0}; v.pk.hh1 = p; p += pack_floats(H, 3, H);
+  v.pb.d[5] = PackDesc{w->w_out, p, D, 1, 0, H, H, 0, dtiles_pad(D)}; v.pk.out = p;
+  v.xbase = (char*)workspace + fwd_pack_bytes_aligned(D, H);
+  const size_t Hp = (size_t)((H + 15) & ~15), rowrec = (size_t)2 * cluster_nblk * 16 * Hp;
+  v.xu = reinterpret_cast<unsigned long long*>(v.xbase); v.xh0 = v.xu + rowrec; v.xh1 = v.xu + 2 * rowrec; v.xp = v.xu + 3 * rowrec;
+  v.xcc = reinterpret_cast<unsigned*>(v.xp + (size_t)2 * cluster_nblk * 2 * Hp);
+  return v;
+}
+// Backward, by route, each from offset 0.  Fused kernels: [six transposed weight images in fragment order | 256-byte aligned
+// PersistX | the wgrad slabs].  Split launches: [six plain transposes | direct1 (B,H) | direct0 (B,H)].  Cluster kernel: its records.
+struct DecBwdWs {
+  DecTW tw; PackBatch pb;
+  void* xbase; float* wslab;
+  float *t_pre, *t_out, *t_hh1, *t_ih1, *t_hh0, *t_ih0, *direct1, *direct0;
+  unsigned long long *xd, *xp, *xq; unsigned* xcc;      // (cluster_nblk == 0: unused)
+};
+static DecBwdWs dec_bwd_ws(const g2v_dec_weights* w, int B, int D, int H, void* workspace, int cluster_nblk = 0) {
+  DecBwdWs v;
+  float* p = (float*)workspace;
+  const int G = 3 * H;
+  v.pb.n = 6;
+  v.pb.d[0] = PackDesc{w->w_pre, p, D, 1, 0, H, D, 1, dtiles_pad(D)}; v.tw.w_pre_t = p; p += (size_t)dtiles_pad(D) * pack_ks(H) * 256;   // rows d, k = f: W_pre[f][d]
+  v.pb.d[1] = PackDesc{w->w_out, p, H, 1, 0, D, H, 1, 0}; v.tw.w_out_t = p; p += pack_floats(H, 1, D);   // rows f, k = d: W_out[d][f]
+  v.pb.d[2] = PackDesc{w->w_ih0, p, H, 1, 0, G, H, 1, 0}; v.tw.w_ih0_t = p; p += pack_floats(H, 1, G);   // rows k, contraction g: W[g][k]
+  v.pb.d[3] = PackDesc{w->w_hh0, p, H, 1, 0, G, H, 1, 0}; v.tw.w_hh0_t = p; p += pack_floats(H, 1, G);
+  v.pb.d[4] = PackDesc{w->w_ih1, p, H, 1, 0, G, H, 1, 0}; v.tw.w_ih1_t = p; p += pack_floats(H, 1, G);
+  v.pb.d[5] = PackDesc{w->w_hh1, p, H, 1, 0, G, H, 1, 0}; v.tw.w_hh1_t = p;
+  v.xbase = (char*)workspace + bwd_pack_bytes_aligned(D, H);
+  v.wslab = (float*)((char*)v.xbase + PX_BYTES);
+  const size_t DH = (size_t)D * H, GH = (size_t)G * H;
+  v.t_pre = (float*)workspace; v.t_out = v.t_pre + DH; v.t_hh1 = v.t_out + DH; v.t_ih1 = v.t_hh1 + GH; v.t_hh0 = v.t_ih1 + GH;
+  v.t_ih0 = v.t_hh0 + GH; v.direct1 = v.t_ih0 + GH; v.direct0 = v.direct1 + (size_t)B * H;
+  const size_t Hp = (size_t)((H + 15) & ~15);
+  v.xd = reinterpret_cast<unsigned long long*>(workspace);
+  v.xp = v.xd + (size_t)2 * cluster_nblk * 16 * Hp; v.xq = v.xp + (size_t)2 * cluster_nblk * 2 * Hp;
+  v.xcc = reinterpret_cast<unsigned*>(v.xq + (size_t)cluster_nblk * 4 * (Hp / 16) * 16 * Hp);
+  return v;
+}
+
+// ---- the plan ------------------------------------------------------------------------------------------------------------
+struct DecCallFacts {      // what the plan needs to know of ONE call beyond its sizes
+  bool persist_aligned, split_aligned, keep_l0_aligned;      // 16-byte alignment of every pointer that route reads as float4s
+  size_t workspace_bytes;
+  int wgrad_any, wgrad_both;      // backward, bit m: dw_gru[m] or db_gru[m] is set / both are
+  bool loss, loss_complete;       // loss_code is set / so is every companion the direction needs
+  bool cluster_resident;          // dec_cluster_resident: asked only once a plan says cluster (dec_plan_call)
+};
+// the queries' call: aligned pointers, a workspace that is large enough, no optional outputs
+constexpr DecCallFacts DEC_IDEAL_FACTS{true, true, true, ~(size_t)0, 0, 0, false, false, true};
+constexpr int DEC_FUSED_WGRAD = 8;      // bit m <-> matrix m of (ih0, hh0, ih1, hh1): W_hh1 is what the persistent backward has registers for
+
+struct DecRoutePlan {
+  int route;                      // G2V_DEC_ROUTE_*; 0: refused with `err` and `msg`
+  int tiles;                      // PERSIST: row tiles per workgroup
+  int fuses_loss, wgrad_mask;     // the loss_* fields / these dw_gru, db_gru entries are honoured (PERSIST with one full tile per workgroup)
+  bool pack;                      // the route reads the fragment images of the workspace (backward SPLIT: plain transposes, its own)
+  size_t xch_off, xch_bytes;      // its exchange records in the workspace (PERSIST, CLUSTER)
+  size_t lds;                     // dynamic LDS bytes, threads and reduce_partials scratch floats of the route's step kernel
+  int block, scratch, nblk;       // (STEP, STEP_FAST, SPLIT's step 0) or cluster kernel; nblk: 16-row tiles
+  int err; const char* msg;
+};
+static DecRoutePlan dec_route_plan(bool bwd, int T, int B, int D, int H, bool training, int level, int cus, const DecCallFacts& f) {
+  DecRoutePlan pl{};
+  auto refuse = [&pl](int err, const char* msg) { pl.route = 0; pl.err = err; pl.msg = msg; return pl; };
+  if (T < 2 || B <= 0 || D <= 0 || H <= 0) return refuse(G2V_ERR_ARG, "bad size");
+  pl.nblk = cdiv(B, 16);
+  pl.lds = bwd ? dec_bwd_lds(D, H, &pl.scratch) : dec_fwd_lds(D, H, &pl.scratch);
+  if (pl.lds > 160 * 1024) return refuse(G2V_ERR_UNSUPPORTED, "D/H too large for LDS");
+  const bool fast = dec_prepared_shape(D, H);
+  pl.tiles = (fast && (B % 4) == 0 && f.persist_aligned) ? persist_tiles(pl.nblk, level, cus) : 0;      // (B % 16 != 0: a ragged last tile)
+  if (pl.tiles >= 1) {
+    pl.route = G2V_DEC_ROUTE_PERSIST; pl.pack = true;
+    pl.xch_off = bwd ? bwd_pack_bytes_aligned(D, H) : fwd_pack_bytes_aligned(D, H); pl.xch_bytes = PX_BYTES;
+    const bool one_full_tile = pl.tiles == 1 && (B % 16) == 0;      // (no chaser, no fused weight gradient beside the multi-tile kernels)
+    pl.fuses_loss = (one_full_tile && T <= 256) ? 1 : 0;
+    pl.wgrad_mask = (bwd && one_full_tile) ? DEC_FUSED_WGRAD : 0;
+  } else if (dec_split_shape(B, D, H) && f.split_aligned) {
+    // ONE launch while the (row group x 16-unit tile) grid has a CU per workgroup, else three / four launches per step (crossover
+    // against the fused step kernel at the VQ-VAE.yml dims: split 6.9 ms vs fused 9.2 ms per train step at B = 1024, 12.5 vs 11.1 at 2048)
+    const size_t xoff = bwd ? 0 : fwd_pack_bytes_aligned(D, H), xb = bwd ? dec_cluster_bwd_xch_bytes(pl.nblk, H) : dec_cluster_fwd_xch_bytes(pl.nblk, H);
+    if (level > 0 && T >= 3 && dec_cluster_shape(D, H) && (int64_t)pl.nblk * ((H + 15) >> 4) <= cus && f.keep_l0_aligned &&
+        xoff + xb <= f.workspace_bytes && f.cluster_resident) {
+      pl.route = G2V_DEC_ROUTE_CLUSTER; pl.xch_off = xoff; pl.xch_bytes = xb;      // (weights read in place: no pack, no transposes)
+      pl.lds = bwd ? dec_cluster_bwd_dyn_lds() : dec_cluster_fwd_dyn_lds(); pl.block = 256;
+    } else {
+      pl.route = G2V_DEC_ROUTE_SPLIT; pl.pack = !bwd; pl.block = 512;      // (forward: step 0 is the generic kernel)
+    }
+  } else {
+    pl.route = fast ? G2V_DEC_ROUTE_STEP_FAST : G2V_DEC_ROUTE_STEP; pl.pack = true; pl.block = fast ? 256 : 512;
+  }
+  if (bwd && f.wgrad_any && !(pl.wgrad_mask && f.wgrad_any == pl.wgrad_mask && f.wgrad_both == pl.wgrad_mask))
+    return refuse(G2V_ERR_UNSUPPORTED, "dw_gru / db_gru must name exactly the matrices of g2v_dec_rollout_bwd_fuses_wgrad(B, D, H), both pointers "
+                                       "each, on a call that runs as the persistent kernel");
+  if (f.loss && !(pl.fuses_loss && f.loss_complete && (bwd || training)))
+    return refuse(G2V_ERR_UNSUPPORTED, "the loss_* fields are set where g2v_dec_rollout_fuses_loss(B, D, H, T) does not hold (or not training, "
+                                       "or one of them is NULL, or a pointer of the call is not 16-byte aligned)");
+  return pl;
+}
+// ... and of the queries
+static DecRoutePlan dec_plan_ideal(bool bwd, int T, int B, int D, int H, size_t workspace_bytes = DEC_IDEAL_FACTS.workspace_bytes) {
+  DecCallFacts f = DEC_IDEAL_FACTS;
+  f.workspace_bytes = workspace_bytes;
+  return dec_route_plan(bwd, T, B, D, H, true, g2v_internal_options().persist, device_cu_count(), f);
+}
+extern "C" int g2v_dec_rollout_route(int backward, int T, int B, int D, int H, int training, int persistent, int cus, int flags) {
+  DecCallFacts f = DEC_IDEAL_FACTS;
+  if (flags & G2V_DEC_PLAN_UNALIGNED) f.persist_aligned = f.split_aligned = f.keep_l0_aligned = false;
+  if (flags & G2V_DEC_PLAN_WGRAD) f.wgrad_any = f.wgrad_both = DEC_FUSED_WGRAD;
+  if (flags & G2V_DEC_PLAN_LOSS) f.loss = f.loss_complete = true;
+  const DecRoutePlan pl = dec_route_plan(backward != 0, T, B, D, H, training != 0,
+                                         persistent < 0 ? g2v_internal_options().persist : (persistent > 3 ? 3 : persistent),
+                                         cus > 0 ? cus : device_cu_count(), f);
+  return pl.route == G2V_DEC_ROUTE_PERSIST ? pl.route | (pl.tiles << 8) : pl.route;
+}
+// The older queries (include/g2v.h), each a field of the ideal call's plan.
+extern "C" int g2v_dec_rollout_cluster_ok(int B, int D, int H) { return dec_plan_ideal(false, 3, B, D, H).route == G2V_DEC_ROUTE_CLUSTER ? 1 : 0; }
+extern "C" int g2v_dec_rollout_tiles_per_workgroup(int B, int D, int H) { return dec_plan_ideal(false, 2, B, D, H).tiles; }
+extern "C" int g2v_dec_rollout_fuses_loss(int B, int D, int H, int T) { return dec_plan_ideal(false, T, B, D, H).fuses_loss; }
+extern "C" int g2v_dec_rollout_bwd_fuses_wgrad(int B, int D, int H) { return dec_plan_ideal(true, 2, B, D, H).wgrad_mask; }
+
+// Clear the exchange records of the NEXT persistent cluster launch of this kind over `workspace` now, on `stream`, and note it: that
+// launch then starts with its kernel instead of a memset node (see g2v.h).  kind: 0 / 1 g2v_gru_seq_fwd / _bwd (T, B, H, ndir),
+// 2 / 3 g2v_dec_rollout_fwd / _bwd (T, B, D, H).  Shapes that do not run as a cluster: nothing happens.
+extern "C" int g2v_cluster_exchange_preclear(int kind, int T, int B, int D, int H, int ndir, void* workspace, size_t workspace_bytes,
+                                             g2v_stream_t stream) {
+  G2V_REQUIRE(workspace, "null pointer");
+  G2V_REQUIRE(kind >= 0 && kind <= 3, "kind: 0 gru fwd, 1 gru bwd, 2 decoder fwd, 3 decoder bwd");
+  size_t off = 0, bytes = 0;
+  if (kind <= 1) {
+    bytes = g2v_internal_gru_cluster_region(T, B, H, ndir, kind);
+  } else if (const DecRoutePlan pl = dec_plan_ideal(kind == 3, T, B, D, H, workspace_bytes); pl.route == G2V_DEC_ROUTE_CLUSTER) {
+    off = pl.xch_off, bytes = pl.xch_bytes;
+  }
+  if (bytes == 0 || off + bytes > workspace_bytes) return G2V_OK;
+  if (hipMemsetAsync((char*)workspace + off, 0, bytes, (hipStream_t)stream) != hipSuccess) {
+    set_error("g2v_cluster_exchange_preclear: memset failed");
+    return G2V_ERR_LAUNCH;
+  }
+  g2v_internal_preclear_note((char*)workspace + off, bytes);
+  return G2V_OK;
+}
+
+// ---- forward: one launcher per route -------------------------------------------------------------------------------------
+struct DecFwdCall {
+  const float* target; const float* h_init; const g2v_dec_weights* w; const g2v_dec_saved* s; const uint8_t* keep95; const uint8_t* keep_l0;
+  float p_drop; int n_pre, conditioned, training, T, B, D, H;
+  hipStream_t st; bool prepared;
+};
+// STEP / STEP_FAST: one fused kernel per time step (also step 0 of SPLIT)
+static void dec_fwd_launch_steps(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws, int t_end) {
+  const bool fast = dec_prepared_shape(c.D, c.H);
+  auto* const kernel = !fast ? dec_step_fwd_kernel<0, 0> : dec_step_fwd_kernel<64, 135>;      // (same arguments)
+  if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, c.training, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch};
+  for (int t = 0; t < t_end; ++t)
+    hipLaunchKernelGGL(kernel, dim3(pl.nblk), dim3(pl.block), pl.lds, c.st, c.target, c.h_init, *c.w, ws.pk, *c.s, c.keep95, c.keep_l0, dm, t);
+}
+// CLUSTER: ONE launch for all steps while the tile grid has a CU per workgroup (dec_cluster_fwd_kernel)
+static int dec_fwd_launch_cluster(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws) {
+  DecClFwdArgs ca;
+  ca.target = c.target; ca.h_init = c.h_init; ca.keep95 = c.keep95; ca.keep_l0 = c.keep_l0; ca.w = *c.w; ca.sv = *c.s;
+  ca.xu = ws.xu; ca.xh0 = ws.xh0; ca.xh1 = ws.xh1; ca.xp = ws.xp; ca.xcc = ws.xcc;
+  ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
+  ca.T = c.T; ca.B = c.B; ca.D = c.D; ca.H = c.H; ca.n_pre = c.n_pre; ca.conditioned = c.conditioned; ca.training = c.training;
+  ca.nt = (c.H + 15) >> 4; ca.nblk = pl.nblk; ca.p_drop = c.p_drop;
+  if (!g2v_internal_preclear_take(ws.xbase, pl.xch_bytes) && hipMemsetAsync(ws.xbase, 0, pl.xch_bytes, c.st) != hipSuccess) return G2V_ERR_LAUNCH;
+  hipLaunchKernelGGL(dec_cluster_fwd_kernel<DCL_KS>, dim3(ca.nt * pl.nblk), dim3(pl.block), pl.lds, c.st, ca);
+  return G2V_OK;
+}
+// SPLIT: step 0 as the generic kernel, then steps t >= 1 as three launches over (rows x 16-unit tiles) workgroups (see the kernels)
+static void dec_fwd_launch_split(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws) {
+  const g2v_dec_weights* w = c.w; const g2v_dec_saved* s = c.s;
+  const int T = c.T, B = c.B, D = c.D, H = c.H, training = c.training, nblk = pl.nblk;
+  const float p_drop = c.p_drop;
+  dec_fwd_launch_steps(c, pl, ws, 1);
+  for (int t = 1; t < T; ++t) {
+    const int64_t BH = (int64_t)B * H, BD = (int64_t)B * D;
+    const bool drop = training && c.keep_l0 && p_drop > 0.f;
+    const dim3 grid(nblk, (H + 15) >> 4);
+    DecCellArgs c0{};
+    c0.x = s->u + (t - 1) * BH; c0.h_prev = s->h0 + (t - 1) * BH;
+    c0.w_ih = w->w_ih0; c0.w_hh = w->w_hh0; c0.b_ih = w->b_ih0; c0.b_hh = w->b_hh0;
+    c0.h_out = s->h0 + t * BH; c0.gates = s->gates0 ? s->gates0 + (t - 1) * 4 * BH : nullptr;
+    c0.keep = drop ? c.keep_l0 + (t - 1) * BH : nullptr; c0.keep_scale = 1.0f / (1.0f - p_drop);
+    c0.xdrop_out = (drop && s->x1) ? s->x1 + (t - 1) * BH : nullptr;
+    c0.bn_partial = s->bn_partial + (int64_t)((t - 1) & 1) * nblk * 2 * H;
+    c0.b_pre = w->b_pre; c0.bn_w = w->bn_w; c0.bn_b = w->bn_b; c0.run_mean = w->bn_running_mean; c0.run_var = w->bn_running_var;
+    c0.a_out = s->a ? s->a + (t - 1) * BH : nullptr;
+    c0.bn_stats = (training && s->bn_stats) ? s->bn_stats + (int64_t)(t - 1) * 2 * H : nullptr;
+    c0.nblk = nblk; c0.training = training;
+    hipLaunchKernelGGL(dec_cell_split_kernel<true>, grid, dim3(128), 0, c.st, c0, B, H);
+    DecCellArgs c1{};
+    c1.x = (drop && s->x1) ? s->x1 + (t - 1) * BH : s->h0 + t * BH; c1.h_prev = s->h1 + (t - 1) * BH;
+    c1.w_ih = w->w_ih1; c1.w_hh = w->w_hh1; c1.b_ih = w->b_ih1; c1.b_hh = w->b_hh1;
+    c1.h_out = s->h1 + t * BH; c1.gates = s->gates1 ? s->gates1 + (t - 1) * 4 * BH : nullptr;
+    c1.keep = nullptr; c1.keep_scale = 1.0f; c1.xdrop_out = nullptr;
+    hipLaunchKernelGGL(dec_cell_split_kernel<false>, grid, dim3(128), 0, c.st, c1, B, H);
+    DecOutPreArgs o{};
+    o.h1 = s->h1 + t * BH; o.w_out = w->w_out; o.b_out = w->b_out; o.w_pre = w->w_pre; o.b_pre = w->b_pre;
+    o.target = c.target; o.keep95 = c.keep95 + t * BD; o.y = s->y + t * BD; o.xin = s->xin ? s->xin + t * BD : nullptr;
+    o.u_next = s->u + t * BH; o.part = s->bn_partial + (int64_t)(t & 1) * nblk * 2 * H;
+    o.t = t; o.T = T; o.has_next = t < T - 1 ? 1 : 0; o.teacher = (t < T - 1 && t < c.n_pre) ? 1 : 0; o.conditioned = c.conditioned;
+    hipLaunchKernelGGL(dec_out_pre_split_kernel, grid, dim3(64), 0, c.st, o, B, D, H);
+  }
+}
+// Does the cluster kernel fit a CU (its dynamic LDS on top of ~60 KB of static arrays)?  The attribute is set once per process.
+static bool dec_cluster_resident(bool bwd) {
+  static bool attr_set[2] = {false, false};
+  const void* fn = bwd ? (const void*)dec_cluster_bwd_kernel<DCL_KS> : (const void*)dec_cluster_fwd_kernel<DCL_KS>;
+  const size_t dyn = bwd ? dec_cluster_bwd_dyn_lds() : dec_cluster_fwd_dyn_lds();
+  int nocc = 0;
+  if (!attr_set[bwd]) attr_set[bwd] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess;
+  return attr_set[bwd] && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, dyn) == hipSuccess && nocc >= 1;
+}
+// the plan of a real call: the bound context's level, this device's CUs, the call's facts
+static DecRoutePlan dec_plan_call(bool bwd, int T, int B, int D, int H, bool training, DecCallFacts f) {
+  const int level = g2v_internal_options().persist, cus = device_cu_count();
+  DecRoutePlan pl = dec_route_plan(bwd, T, B, D, H, training, level, cus, f);
+  if (pl.route == G2V_DEC_ROUTE_CLUSTER && !dec_cluster_resident(bwd)) {
+    f.cluster_resident = false;
+    pl = dec_route_plan(bwd, T, B, D, H, training, level, cus, f);
+  }
+  return pl;
+}
 static int dec_rollout_fwd_impl(const float* target, const float* h_init, const g2v_dec_weights* w,
                                 const g2v_dec_saved* s, const uint8_t* keep95, const uint8_t* keep_l0, float p_drop,
                                 int n_pre_poses, int conditioned, int training, int T, int B, int D, int H,
                                 void* workspace, size_t workspace_bytes, g2v_stream_t stream, bool prepared_req) {
-  const bool prepared = prepared_req && dec_prepared_shape(D, H);
+  // ---- 1. the arguments ----
   G2V_REQUIRE(target && h_init && w && s && keep95 && workspace, "null pointer");
   G2V_REQUIRE(T >= 2 && B > 0 && D > 0 && H > 0, "bad size");
   G2V_REQUIRE(s->y && s->u && s->h0 && s->h1 && s->bn_partial, "missing state buffer");
@@ -2481,133 +2717,42 @@ static int dec_rollout_fwd_impl(const float* target, const float* h_init, const 
     set_error("g2v_dec_rollout_fwd: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
-  const size_t lds = dec_fwd_lds(D, H);
-  if (lds > 160 * 1024) {
-    set_error("g2v_dec_rollout_fwd: D/H too large for LDS");
-    return G2V_ERR_UNSUPPORTED;
+  // ---- 2. the plan ----
+  const DecCallFacts f{
+      aligned16(h_init, s->y, s->u, s->h0, s->h1, s->xin, s->a, s->x1, s->gates0, s->gates1, keep95, keep_l0, workspace),
+      aligned16(s->u, s->h0, s->h1, s->a, s->x1, s->gates0, s->gates1, s->bn_partial, w->w_ih0, w->w_hh0, w->w_ih1, w->w_hh1, w->w_out,
+                w->b_ih0, w->b_hh0, w->b_ih1, w->b_hh1, w->b_pre, w->bn_w, w->bn_b),
+      aligned16(keep_l0), workspace_bytes, 0, 0, s->loss_code != nullptr, s->loss_coef && s->loss_partial && s->loss_terms, true};
+  const DecRoutePlan pl = dec_plan_call(false, T, B, D, H, training != 0, f);
+  if (pl.route == 0) {
+    set_error("g2v_dec_rollout_fwd: %s", pl.msg);
+    return pl.err;
   }
-  hipStream_t st = (hipStream_t)stream;
-  // ---- pack the weights into MFMA fragment order (one launch; the cluster kernel below reads them in place) ----
-  PackBatch pb;
-  const DecPackF pk = dec_fwd_pack_layout(w, D, H, workspace, pb);
-  const bool maybe_cluster = g2v_dec_rollout_cluster_ok(B, D, H) && T >= 3;
-  if (!prepared && !maybe_cluster) {
-    launch_pack(pb, st);
+  // ---- 3. the launches ----
+  const DecFwdCall c{target, h_init, w, s, keep95, keep_l0, p_drop, n_pre_poses, conditioned, training, T, B, D, H, (hipStream_t)stream,
+                     prepared_req && dec_prepared_shape(D, H)};
+  const DecFwdWs ws = dec_fwd_ws(w, D, H, workspace, pl.route == G2V_DEC_ROUTE_CLUSTER ? pl.nblk : 0);
+  if (pl.route != G2V_DEC_ROUTE_CLUSTER) g2v_internal_preclear_drop(workspace, workspace_bytes);      // (a pre-cleared note for this workspace is void)
+  if (pl.pack && !c.prepared) {      // the weights into MFMA fragment order (one launch)
+    launch_pack(ws.pb, c.st);
     G2V_CHECK_LAUNCH();
   }
-  int scratch = 1024;
-  (void)dec_fwd_lds(D, H, &scratch);
-  DecDims dm{T, B, D, H, p_drop, n_pre_poses, conditioned, training, cdiv(B, 16), (H == 64 && D == 135) ? dec_wt_stores() : 0, scratch};
-  const bool fast = (H == 64) && (D == 135);   // the BASELINE shape: dims are compile-time constants
-  {
-    auto a16 = [](const void* q_) { return (reinterpret_cast<uintptr_t>(q_) & 15) == 0; };
-    const int ptiles = persist_tiles_per_wg(dm.nblk);
-    const bool persist = fast && ptiles >= 1 && (B % 4) == 0 &&      // (B % 16 != 0: a ragged last tile, the multi-tile kernels)
-                        
-                         a16(h_init) && a16(s->y) && a16(s->u) && a16(s->h0) && a16(s->h1) && a16(s->xin) && a16(s->a) &&
-                         a16(s->x1) && a16(s->gates0) && a16(s->gates1) && a16(keep95) && a16(keep_l0) && a16(workspace);
-    if (s->loss_code && !(persist && training && s->loss_coef && s->loss_partial && s->loss_terms &&
-                          g2v_dec_rollout_fuses_loss(B, D, H, T))) {
-      set_error("g2v_dec_rollout_fwd: the loss_* fields are set where g2v_dec_rollout_fuses_loss(B, D, H, T) does not hold "
-                "(or not training, or one of them is NULL)");
-      return G2V_ERR_UNSUPPORTED;
-    }
-    if (persist) {
-      void* xbase = (char*)workspace + fwd_pack_bytes_aligned(D, H);
-      const int rc = dec_persist_fwd_launch(target, h_init, w, s, keep95, keep_l0, p_drop, n_pre_poses, conditioned, training, T,
-                                            B, pk.pre, pk.ih0, pk.hh0, pk.ih1, pk.hh1, pk.out, xbase, st, !prepared, ptiles);
-      return rc;       // (the running statistics are updated by the kernel itself)
-    }
-  }
-  if (lds > 48 * 1024) {
-    (void)hipFuncSetAttribute((const void*)dec_step_fwd_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)dec_step_fwd_kernel<64, 135>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  auto al16 = [](const void* q_) { return (reinterpret_cast<uintptr_t>(q_) & 15) == 0; };
-  // small batch, generic dims: steps t >= 1 as three launches over (rows x 16-unit tiles) workgroups (see the kernels)
-  // crossover measured at the VQ-VAE.yml dims: split 6.9 ms vs fused 9.2 ms per train step at B = 1024, 12.5 vs 11.1 at 2048
-  const bool split = !fast && dm.nblk <= DSPLIT_MAX_NBLK && (H & 3) == 0 && H <= 16 * DSPLIT_KS && D <= 16 * DSPLIT_DT &&
-                     al16(s->u) && al16(s->h0) && al16(s->h1) && al16(s->a) && al16(s->x1) && al16(s->gates0) &&
-                     al16(s->gates1) && al16(s->bn_partial) && al16(w->w_ih0) && al16(w->w_hh0) && al16(w->w_ih1) &&
-                     al16(w->w_hh1) && al16(w->w_out) && al16(w->b_ih0) && al16(w->b_hh0) && al16(w->b_ih1) && al16(w->b_hh1) &&
-                     al16(w->b_pre) && al16(w->bn_w) && al16(w->bn_b);
-  // ... or ONE persistent launch for all steps t >= 1 while the tile grid has a CU per workgroup (dec_cluster_fwd_kernel)
-  bool cluster = split && persist_enabled() && T >= 3 && dec_cluster_shape(D, H) &&
-                 (int64_t)dm.nblk * ((H + 15) >> 4) <= device_cu_count() && (!training || s->bn_stats) &&
-                 (!keep_l0 || al16(keep_l0)) &&
-                 fwd_pack_bytes_aligned(D, H) + dec_cluster_fwd_xch_bytes(dm.nblk, H) <= workspace_bytes;
-  if (cluster) {
-    int nocc = 0;
-    const void* fn = (const void*)dec_cluster_fwd_kernel<DCL_KS>;
-    const size_t dyn = dec_cluster_fwd_dyn_lds();      // W_out fragments + partial out-layer products (the static arrays take ~60 KB more)
-    static bool attr_set = false;
-    if (!attr_set) attr_set = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess;
-    cluster = attr_set && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, dyn) == hipSuccess && nocc >= 1;
-  }
-  if (!cluster) g2v_internal_preclear_drop(workspace, workspace_bytes);      // (a pre-cleared note for this workspace is void)
-  if (maybe_cluster && !cluster) {      // (the cluster path was declined after all: the per-step kernels need the packed weights)
-    launch_pack(pb, st);
-    G2V_CHECK_LAUNCH();
-  }
-  for (int t = 0; t < T; ++t) {
-    if (cluster && t == 0) {
-      const size_t Hp = (size_t)((H + 15) & ~15), rowrec = (size_t)2 * dm.nblk * 16 * Hp;
-      unsigned long long* x0 = reinterpret_cast<unsigned long long*>((char*)workspace + fwd_pack_bytes_aligned(D, H));
-      DecClFwdArgs ca;
-      ca.target = target; ca.h_init = h_init; ca.keep95 = keep95; ca.keep_l0 = keep_l0; ca.w = *w; ca.sv = *s;
-      ca.xu = x0; ca.xh0 = x0 + rowrec; ca.xh1 = x0 + 2 * rowrec; ca.xp = x0 + 3 * rowrec;
-      ca.xcc = reinterpret_cast<unsigned*>(ca.xp + (size_t)2 * dm.nblk * 2 * Hp);
-      ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
-      ca.T = T; ca.B = B; ca.D = D; ca.H = H; ca.n_pre = n_pre_poses; ca.conditioned = conditioned; ca.training = training;
-      ca.nt = (H + 15) >> 4; ca.nblk = dm.nblk;
-      ca.p_drop = p_drop;
-      if (!g2v_internal_preclear_take(x0, dec_cluster_fwd_xch_bytes(dm.nblk, H)) &&
-          hipMemsetAsync(x0, 0, dec_cluster_fwd_xch_bytes(dm.nblk, H), st) != hipSuccess) {
+  switch (pl.route) {
+    case G2V_DEC_ROUTE_PERSIST:      // (the running statistics are updated by the kernel itself)
+      return dec_persist_fwd_launch(target, h_init, w, s, keep95, keep_l0, p_drop, n_pre_poses, conditioned, training, T, B, ws.pk.pre,
+                                    ws.pk.ih0, ws.pk.hh0, ws.pk.ih1, ws.pk.hh1, ws.pk.out, ws.xbase, c.st, !c.prepared, pl.tiles);
+    case G2V_DEC_ROUTE_CLUSTER:
+      if (dec_fwd_launch_cluster(c, pl, ws) != G2V_OK) {
         set_error("g2v_dec_rollout_fwd: clearing the exchange records failed");
         return G2V_ERR_LAUNCH;
       }
-      hipLaunchKernelGGL(dec_cluster_fwd_kernel<DCL_KS>, dim3(((H + 15) >> 4) * dm.nblk), dim3(256), dec_cluster_fwd_dyn_lds(), st, ca);
       break;
-    }
-    if (fast) {
-      hipLaunchKernelGGL((dec_step_fwd_kernel<64, 135>), dim3(dm.nblk), dim3(256), lds, st, target, h_init, *w, pk, *s, keep95,
-                         keep_l0, dm, t);
-    } else if (!split || t == 0) {
-      hipLaunchKernelGGL((dec_step_fwd_kernel<0, 0>), dim3(dm.nblk), dim3(512), lds, st, target, h_init, *w, pk, *s, keep95,
-                         keep_l0, dm, t);
-    } else {
-      const int64_t BH = (int64_t)B * H, BD = (int64_t)B * D;
-      const bool drop = training && keep_l0 && p_drop > 0.f;
-      const dim3 grid(dm.nblk, (H + 15) >> 4);
-      DecCellArgs c0{};
-      c0.x = s->u + (t - 1) * BH; c0.h_prev = s->h0 + (t - 1) * BH;
-      c0.w_ih = w->w_ih0; c0.w_hh = w->w_hh0; c0.b_ih = w->b_ih0; c0.b_hh = w->b_hh0;
-      c0.h_out = s->h0 + t * BH; c0.gates = s->gates0 ? s->gates0 + (t - 1) * 4 * BH : nullptr;
-      c0.keep = drop ? keep_l0 + (t - 1) * BH : nullptr; c0.keep_scale = 1.0f / (1.0f - p_drop);
-      c0.xdrop_out = (drop && s->x1) ? s->x1 + (t - 1) * BH : nullptr;
-      c0.bn_partial = s->bn_partial + (int64_t)((t - 1) & 1) * dm.nblk * 2 * H;
-      c0.b_pre = w->b_pre; c0.bn_w = w->bn_w; c0.bn_b = w->bn_b; c0.run_mean = w->bn_running_mean; c0.run_var = w->bn_running_var;
-      c0.a_out = s->a ? s->a + (t - 1) * BH : nullptr;
-      c0.bn_stats = (training && s->bn_stats) ? s->bn_stats + (int64_t)(t - 1) * 2 * H : nullptr;
-      c0.nblk = dm.nblk; c0.training = training;
-      hipLaunchKernelGGL(dec_cell_split_kernel<true>, grid, dim3(128), 0, st, c0, B, H);
-      DecCellArgs c1{};
-      c1.x = (drop && s->x1) ? s->x1 + (t - 1) * BH : s->h0 + t * BH; c1.h_prev = s->h1 + (t - 1) * BH;
-      c1.w_ih = w->w_ih1; c1.w_hh = w->w_hh1; c1.b_ih = w->b_ih1; c1.b_hh = w->b_hh1;
-      c1.h_out = s->h1 + t * BH; c1.gates = s->gates1 ? s->gates1 + (t - 1) * 4 * BH : nullptr;
-      c1.keep = nullptr; c1.keep_scale = 1.0f; c1.xdrop_out = nullptr;
-      hipLaunchKernelGGL(dec_cell_split_kernel<false>, grid, dim3(128), 0, st, c1, B, H);
-      DecOutPreArgs o{};
-      o.h1 = s->h1 + t * BH; o.w_out = w->w_out; o.b_out = w->b_out; o.w_pre = w->w_pre; o.b_pre = w->b_pre;
-      o.target = target; o.keep95 = keep95 + t * BD; o.y = s->y + t * BD; o.xin = s->xin ? s->xin + t * BD : nullptr;
-      o.u_next = s->u + t * BH; o.part = s->bn_partial + (int64_t)(t & 1) * dm.nblk * 2 * H;
-      o.t = t; o.T = T; o.has_next = t < T - 1 ? 1 : 0; o.teacher = (t < T - 1 && t < n_pre_poses) ? 1 : 0; o.conditioned = conditioned;
-      hipLaunchKernelGGL(dec_out_pre_split_kernel, grid, dim3(64), 0, st, o, B, D, H);
-    }
+    case G2V_DEC_ROUTE_SPLIT: dec_fwd_launch_split(c, pl, ws); break;
+    default: dec_fwd_launch_steps(c, pl, ws, T); break;      // STEP, STEP_FAST
   }
   G2V_CHECK_LAUNCH();
   if (training && w->bn_running_mean) {      // (NULL: the caller commits them later, g2v_bn_running_update)
-    hipLaunchKernelGGL(bn_running_update_kernel, dim3(cdiv(H, 256)), dim3(256), 0, st, s->bn_stats,
+    hipLaunchKernelGGL(bn_running_update_kernel, dim3(cdiv(H, 256)), dim3(256), 0, c.st, s->bn_stats,
                        w->bn_running_mean, w->bn_running_var, T - 1, H, B, (const unsigned*)nullptr);
     G2V_CHECK_LAUNCH();
   }
@@ -2645,62 +2790,6 @@ extern "C" int g2v_dec_rollout_fwd_prepared(const float* target, const float* h_
                               workspace, workspace_bytes, stream, true);
 }
 
-// split path (small batch): six plain transposes + two (B <= 512, H) scratch arrays
-static size_t split_bwd_total(int D, int H) { return (size_t)2 * D * H + (size_t)12 * H * H + (size_t)2 * 16 * DSPLIT_MAX_NBLK * H; }
-static size_t bwd_pack_bytes_aligned(int D, int H) { return (pack_bwd_total(D, H) * sizeof(float) + 255) / 256 * 256; }
-// the fused-weight-gradient persistent backward appends its per-workgroup partial dW / db (PX_MAX_NBLK workgroups)
-static size_t bwd_wslab_bytes(int D, int H) {
-  return (H == 64 && D == 135) ? (size_t)PX_MAX_NBLK * dec_persist_bwd_wgrad_slab_floats() * sizeof(float) : 0;
-}
-extern "C" size_t g2v_dec_rollout_bwd_workspace(int D, int H) {
-  const size_t a = bwd_pack_bytes_aligned(D, H) + PX_BYTES + bwd_wslab_bytes(D, H), b = split_bwd_total(D, H) * sizeof(float);
-  size_t c = 0;
-  if (dec_cluster_shape(D, H)) {      // the cluster kernel's exchange records at the largest grid it is admitted for
-    const int nt = (H + 15) >> 4, cus = device_cu_count() > 0 ? device_cu_count() : 256;
-    c = dec_cluster_bwd_xch_bytes(cus / nt + 1, H);
-  }
-  const size_t ab = a > b ? a : b;
-  return ab > c ? ab : c;
-}
-// 1: g2v_dec_rollout_fwd / _bwd take the small-batch cluster kernels for this shape (T >= 3) under the current setting
-extern "C" int g2v_dec_rollout_cluster_ok(int B, int D, int H) {
-  if (B <= 0 || !persist_enabled() || !dec_cluster_shape(D, H)) return 0;
-  const int nblk = cdiv(B, 16);
-  return (nblk <= DSPLIT_MAX_NBLK && (int64_t)nblk * ((H + 15) >> 4) <= device_cu_count()) ? 1 : 0;
-}
-// Clear the exchange records of the NEXT persistent cluster launch of this kind over `workspace` now, on `stream`, and note it: that
-// launch then starts with its kernel instead of a memset node (see g2v.h).  kind: 0 / 1 g2v_gru_seq_fwd / _bwd (T, B, H, ndir),
-// 2 / 3 g2v_dec_rollout_fwd / _bwd (B, D, H).  Shapes that do not run as a cluster: nothing happens.
-extern "C" int g2v_cluster_exchange_preclear(int kind, int T, int B, int D, int H, int ndir, void* workspace, size_t workspace_bytes,
-                                             g2v_stream_t stream) {
-  G2V_REQUIRE(workspace, "null pointer");
-  G2V_REQUIRE(kind >= 0 && kind <= 3, "kind: 0 gru fwd, 1 gru bwd, 2 decoder fwd, 3 decoder bwd");
-  size_t off = 0, bytes = 0;
-  if (kind <= 1) {
-    bytes = g2v_internal_gru_cluster_region(T, B, H, ndir, kind);
-  } else if (g2v_dec_rollout_cluster_ok(B, D, H) && T >= 3) {
-    off = kind == 2 ? fwd_pack_bytes_aligned(D, H) : 0;
-    bytes = kind == 2 ? dec_cluster_fwd_xch_bytes(cdiv(B, 16), H) : dec_cluster_bwd_xch_bytes(cdiv(B, 16), H);
-  }
-  if (bytes == 0 || off + bytes > workspace_bytes) return G2V_OK;
-  if (hipMemsetAsync((char*)workspace + off, 0, bytes, (hipStream_t)stream) != hipSuccess) {
-    set_error("g2v_cluster_exchange_preclear: memset failed");
-    return G2V_ERR_LAUNCH;
-  }
-  g2v_internal_preclear_note((char*)workspace + off, bytes);
-  return G2V_OK;
-}
-// 0: one launch per time step; R >= 1: ONE persistent launch each way with R row tiles per workgroup (see g2v.h)
-extern "C" int g2v_dec_rollout_tiles_per_workgroup(int B, int D, int H) {
-  return (H == 64 && D == 135 && B > 0 && (B % 4) == 0) ? persist_tiles_per_wg(cdiv(B, 16)) : 0;
-}
-extern "C" int g2v_dec_rollout_fuses_loss(int B, int D, int H, int T) {
-  return (H == 64 && D == 135 && B > 0 && (B % 16) == 0 && persist_tiles_per_wg(B / 16) == 1 && T >= 2 && T <= 256) ? 1 : 0;
-}
-extern "C" int g2v_dec_rollout_bwd_fuses_wgrad(int B, int D, int H) {
-  return (H == 64 && D == 135 && B > 0 && (B % 16) == 0 && persist_tiles_per_wg(B / 16) == 1) ? 8 : 0;      // bit m <-> matrix m of (ih0, hh0, ih1, hh1): W_hh1
-}
-
 // custom_loss as a chaser of the persistent forward rollout (dec_persist.hip, loss_chase_kernel; include/g2v.h).
 extern "C" int g2v_custom_loss_chase(const float* target, const g2v_dec_saved* s, const uint8_t* keep95, int T, int B, int D, int H,
                                      void* fwd_workspace, size_t fwd_bytes, g2v_stream_t stream) {
@@ -2710,14 +2799,12 @@ extern "C" int g2v_custom_loss_chase(const float* target, const g2v_dec_saved* s
     set_error("g2v_custom_loss_chase: g2v_dec_rollout_fuses_loss(B, D, H, T) does not hold");
     return G2V_ERR_UNSUPPORTED;
   }
-  auto a16 = [](const void* q_) { return (reinterpret_cast<uintptr_t>(q_) & 15) == 0; };
-  G2V_REQUIRE(a16(s->y) && a16(s->loss_code) && a16(s->loss_coef) && a16(keep95) && a16(fwd_workspace), "16-byte alignment");
+  G2V_REQUIRE(aligned16(s->y, s->loss_code, s->loss_coef, keep95, fwd_workspace), "16-byte alignment");
   if (fwd_bytes < g2v_dec_rollout_fwd_workspace(D, H)) {
     set_error("g2v_custom_loss_chase: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
-  return dec_persist_loss_chase_launch(target, s, keep95, T, B, (char*)fwd_workspace + fwd_pack_bytes_aligned(D, H),
-                                       (hipStream_t)stream);
+  return dec_persist_loss_chase_launch(target, s, keep95, T, B, (char*)fwd_workspace + fwd_pack_bytes_aligned(D, H), (hipStream_t)stream);
 }
 
 // Everything of a rollout pair that depends on the WEIGHTS only -- the fragment packs of the forward and of the backward -- and
@@ -2734,14 +2821,13 @@ extern "C" int g2v_dec_rollout_prepare(const g2v_dec_weights* w, int D, int H, v
     return G2V_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  PackBatch pb;
-  (void)dec_fwd_pack_layout(w, D, H, fwd_workspace, pb);
-  launch_pack(pb, st);
-  (void)hipMemsetAsync((char*)fwd_workspace + fwd_pack_bytes_aligned(D, H), 0, PX_BYTES, st);
+  const DecFwdWs fw = dec_fwd_ws(w, D, H, fwd_workspace);
+  launch_pack(fw.pb, st);
+  (void)hipMemsetAsync(fw.xbase, 0, PX_BYTES, st);
   if (bwd_workspace) {
-    (void)dec_bwd_pack_layout(w, D, H, bwd_workspace, pb);
-    launch_pack(pb, st);
-    (void)hipMemsetAsync((char*)bwd_workspace + bwd_pack_bytes_aligned(D, H), 0, PX_BYTES, st);
+    const DecBwdWs bw = dec_bwd_ws(w, 0, D, H, bwd_workspace);
+    launch_pack(bw.pb, st);
+    (void)hipMemsetAsync(bw.xbase, 0, PX_BYTES, st);
   }
   G2V_CHECK_LAUNCH();
   return G2V_OK;
@@ -2771,13 +2857,12 @@ extern "C" int g2v_train_step_prepare(const g2v_dec_weights* w, int D, int H, vo
     set_error("g2v_train_step_prepare: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
+  const DecFwdWs fw = dec_fwd_ws(w, D, H, dec_fwd_workspace);
+  const DecBwdWs bw = dec_bwd_ws(w, 0, D, H, dec_bwd_workspace);
   PackBatchL L;
-  PackBatch pb;
   L.n = 0;
-  (void)dec_fwd_pack_layout(w, D, H, dec_fwd_workspace, pb);
-  for (int k = 0; k < pb.n; ++k) L.d[L.n++] = pb.d[k];
-  (void)dec_bwd_pack_layout(w, D, H, dec_bwd_workspace, pb);
-  for (int k = 0; k < pb.n; ++k) L.d[L.n++] = pb.d[k];
+  for (int k = 0; k < fw.pb.n; ++k) L.d[L.n++] = fw.pb.d[k];
+  for (int k = 0; k < bw.pb.n; ++k) L.d[L.n++] = bw.pb.d[k];
   const int ng = gru_bwd_prepare_descs(gru_w_hh, gru_w_ih, gru_ndir, H, gru_fused != 0, gru_bwd_workspace, gru_bwd_bytes,
                                        L.d + L.n, MAX_PACK_L - L.n);
   if (ng <= 0) {
@@ -2787,19 +2872,93 @@ extern "C" int g2v_train_step_prepare(const g2v_dec_weights* w, int D, int H, vo
   L.n += ng;
   static_assert(PX_BYTES % 16 == 0, "exchange region: whole float4s");
   L.nfill = 2;
-  L.fill_dst[0] = (float4*)((char*)dec_fwd_workspace + fwd_pack_bytes_aligned(D, H));
-  L.fill_dst[1] = (float4*)((char*)dec_bwd_workspace + bwd_pack_bytes_aligned(D, H));
+  L.fill_dst[0] = (float4*)fw.xbase;
+  L.fill_dst[1] = (float4*)bw.xbase;
   L.fill_n4[0] = L.fill_n4[1] = (int64_t)(PX_BYTES / 16);
   launch_pack_fill(L, (hipStream_t)stream);
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
 
+// ---- backward: one launcher per route ------------------------------------------------------------------------------------
+struct DecBwdCall {
+  const g2v_dec_weights* w; const g2v_dec_saved* s; const g2v_dec_grads* g; const uint8_t* keep95; const uint8_t* keep_l0;
+  float p_drop; int n_pre, conditioned, T, B, D, H;
+  hipStream_t st; bool prepared;
+};
+// CLUSTER: ONE persistent launch for the whole BPTT (dec_cluster_bwd_kernel): weights read in place, no transposes
+static int dec_bwd_launch_cluster(const DecBwdCall& c, const DecRoutePlan& pl, const DecBwdWs& ws) {
+  DecClBwdArgs ca;
+  ca.keep95 = c.keep95; ca.keep_l0 = c.keep_l0; ca.w = *c.w; ca.sv = *c.s; ca.g = *c.g;
+  ca.xd = ws.xd; ca.xp = ws.xp; ca.xq = ws.xq; ca.xcc = ws.xcc;
+  ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
+  ca.T = c.T; ca.B = c.B; ca.D = c.D; ca.H = c.H; ca.n_pre = c.n_pre; ca.conditioned = c.conditioned; ca.p_drop = c.p_drop;
+  ca.nt = (c.H + 15) >> 4; ca.nblk = pl.nblk;
+  if (!g2v_internal_preclear_take(ws.xd, pl.xch_bytes) && hipMemsetAsync(ws.xd, 0, pl.xch_bytes, c.st) != hipSuccess) return G2V_ERR_LAUNCH;
+  hipLaunchKernelGGL(dec_cluster_bwd_kernel<DCL_KS>, dim3(ca.nt * pl.nblk), dim3(pl.block), pl.lds, c.st, ca);
+  return G2V_OK;
+}
+
+// SPLIT: six plain transposes, then three / four launches per step over (rows x 16-unit tiles) workgroups
+static void dec_bwd_launch_split(const DecBwdCall& c, const DecRoutePlan& pl, const DecBwdWs& ws) {
+  const g2v_dec_weights* w = c.w; const g2v_dec_saved* s = c.s; const g2v_dec_grads* g = c.g;
+  const int T = c.T, B = c.B, D = c.D, H = c.H, nblk = pl.nblk;
+  hipStream_t st = c.st;
+  const int64_t BH = (int64_t)B * H, BD = (int64_t)B * D, BG = 3 * BH;
+  launch_transpose(w->w_pre, ws.t_pre, H, D, st);          // (H,D) -> (D,H)
+  launch_transpose(w->w_out, ws.t_out, D, H, st);          // (D,H) -> (H,D)
+  launch_transpose(w->w_hh1, ws.t_hh1, 3 * H, H, st);      // (3H,H) -> (H,3H)
+  launch_transpose(w->w_ih1, ws.t_ih1, 3 * H, H, st);
+  launch_transpose(w->w_hh0, ws.t_hh0, 3 * H, H, st);
+  launch_transpose(w->w_ih0, ws.t_ih0, 3 * H, H, st);
+  const bool drop = c.keep_l0 && c.p_drop > 0.f;
+  const int nht = (H + 15) >> 4, ndt = (D + 15) >> 4;
+  for (int t = T - 1; t >= 0; --t) {
+    const bool last = (t == T - 1);
+    if (!last) {
+      DecBwdDyArgs a{};
+      a.part = g->bn_bwd_partial + (int64_t)((t + 1) & 1) * nblk * 2 * H;
+      a.stats = s->bn_stats + (int64_t)t * 2 * H; a.u = s->u + t * BH; a.dbn = g->dbn + t * BH; a.bn_w = w->bn_w;
+      a.du = g->du + t * BH; a.d_bn_w = g->d_bn_w; a.d_bn_b = g->d_bn_b; a.w_pre_t = ws.t_pre;
+      a.dy = g->dy + t * BD; a.keep95 = c.keep95 + t * BD;
+      a.nblk = nblk; a.first_acc = (t == T - 2) ? 1 : 0; a.feedback = (c.conditioned && t >= c.n_pre) ? 1 : 0; a.only_a = (t == 0) ? 1 : 0;
+      hipLaunchKernelGGL(dec_bwd_dy_split_kernel, dim3(nblk, (a.feedback && !a.only_a) ? ndt : 1), dim3(64), 0, st, a, B, D, H);
+    }
+    if (t == 0) break;
+    DecBwdCell1Args e1{};
+    e1.dy = g->dy + t * BD; e1.w_out_t = ws.t_out; e1.carry = last ? nullptr : g->dh_init + BH;
+    e1.gates = s->gates1 + (t - 1) * 4 * BH; e1.hprev = s->h1 + (t - 1) * BH;
+    e1.dgi = g->dgi1 + (t - 1) * BG; e1.dgh = g->dgh1 + (t - 1) * BG; e1.direct = ws.direct1;
+    hipLaunchKernelGGL(dec_bwd_cell1_split_kernel, dim3(nblk, nht), dim3(64), 0, st, e1, B, D, H);
+    DecBwdPairArgs e{};
+    e.dgh = g->dgh1 + (t - 1) * BG; e.w_hh_t = ws.t_hh1; e.direct = ws.direct1; e.carry_out = g->dh_init + BH;
+    e.dgi = g->dgi1 + (t - 1) * BG; e.w_ih_t = ws.t_ih1;
+    e.keep = drop ? c.keep_l0 + (t - 1) * BH : nullptr; e.keep_scale = 1.0f / (1.0f - c.p_drop);
+    e.carry0 = last ? nullptr : g->dh_init; e.gates0 = s->gates0 + (t - 1) * 4 * BH; e.hprev0 = s->h0 + (t - 1) * BH;
+    e.dgi0 = g->dgi0 + (t - 1) * BG; e.dgh0 = g->dgh0 + (t - 1) * BG; e.direct0 = ws.direct0;
+    hipLaunchKernelGGL(dec_bwd_pair_split_kernel<false>, dim3(nblk, nht), dim3(128), 0, st, e, B, H);
+    DecBwdPairArgs f{};
+    f.dgh = g->dgh0 + (t - 1) * BG; f.w_hh_t = ws.t_hh0; f.direct = ws.direct0; f.carry_out = g->dh_init;
+    f.dgi = g->dgi0 + (t - 1) * BG; f.w_ih_t = ws.t_ih0;
+    f.a_act = s->a + (t - 1) * BH; f.u = s->u + (t - 1) * BH; f.stats = s->bn_stats + (int64_t)(t - 1) * 2 * H;
+    f.dbn = g->dbn + (t - 1) * BH; f.part = g->bn_bwd_partial + (int64_t)(t & 1) * nblk * 2 * H;
+    hipLaunchKernelGGL(dec_bwd_pair_split_kernel<true>, dim3(nblk, nht), dim3(128), 0, st, f, B, H);
+  }
+}
+// STEP / STEP_FAST: one fused kernel per time step
+static void dec_bwd_launch_steps(const DecBwdCall& c, const DecRoutePlan& pl, const DecBwdWs& ws) {
+  const bool fast = dec_prepared_shape(c.D, c.H);
+  auto* const kernel = !fast ? dec_step_bwd_kernel<0, 0> : dec_step_bwd_kernel<64, 135>;
+  if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, 1, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch};
+  for (int t = c.T - 1; t >= 0; --t)
+    hipLaunchKernelGGL(kernel, dim3(pl.nblk), dim3(pl.block), pl.lds, c.st, *c.w, ws.tw, *c.s, *c.g, c.keep95, c.keep_l0, dm, t);
+}
 static int dec_rollout_bwd_impl(const g2v_dec_weights* w, const g2v_dec_saved* s, const g2v_dec_grads* g,
                                 const uint8_t* keep95, const uint8_t* keep_l0, float p_drop, int n_pre_poses,
                                 int conditioned, int T, int B, int D, int H, void* workspace, size_t workspace_bytes,
                                 g2v_stream_t stream, bool prepared_req) {
-  const bool prepared = prepared_req && dec_prepared_shape(D, H);
+  // ---- 1. the arguments ----
   G2V_REQUIRE(w && s && g && keep95 && workspace, "null pointer");
   G2V_REQUIRE(T >= 2 && B > 0 && D > 0 && H > 0, "bad size");
   G2V_REQUIRE(g->dy && g->du && g->dbn && g->dgi0 && g->dgh0 && g->dgi1 && g->dgh1 && g->dh_init && g->d_bn_w &&
@@ -2810,154 +2969,45 @@ static int dec_rollout_bwd_impl(const g2v_dec_weights* w, const g2v_dec_saved* s
     set_error("g2v_dec_rollout_bwd: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
-  const size_t lds = dec_bwd_lds(D, H);
-  if (lds > 160 * 1024) {
-    set_error("g2v_dec_rollout_bwd: D/H too large for LDS");
-    return G2V_ERR_UNSUPPORTED;
+  // ---- 2. the plan ----
+  DecCallFacts f{
+      aligned16(s->u, s->a, s->h0, s->h1, s->gates0, s->gates1, s->bn_stats, g->dy, g->du, g->dgi0, g->dgh0, g->dgi1, g->dgh1, g->dh_init,
+                keep95, keep_l0, workspace),
+      aligned16(workspace, s->u, s->a, s->h0, s->h1, s->gates0, s->gates1, s->bn_stats, g->du, g->dbn, g->dgi0, g->dgh0, g->dgi1, g->dgh1,
+                g->dh_init, g->bn_bwd_partial, w->bn_w),
+      aligned16(keep_l0), workspace_bytes, 0, 0, s->loss_code != nullptr,
+      s->loss_coef && s->loss_partial && s->loss_terms && s->y && aligned16(s->y), true};
+  for (int m = 0; m < 4; ++m) {
+    f.wgrad_any |= (g->dw_gru[m] || g->db_gru[m]) ? 1 << m : 0;
+    f.wgrad_both |= (g->dw_gru[m] && g->db_gru[m]) ? 1 << m : 0;
   }
-  hipStream_t st = (hipStream_t)stream;
-  float* p = (float*)workspace;
-  {
-    auto al16 = [](const void* q_) { return (reinterpret_cast<uintptr_t>(q_) & 15) == 0; };
-    const int nblk = cdiv(B, 16);
-    const bool split = !((H == 64) && (D == 135)) && nblk <= DSPLIT_MAX_NBLK && (H & 3) == 0 && H <= 16 * DSPLIT_KS && 3 * H <= 16 * DSPLIT_KSG &&
-                       D <= 16 * DSPLIT_DT && al16(workspace) && al16(s->u) && al16(s->a) && al16(s->h0) && al16(s->h1) &&
-                       al16(s->gates0) && al16(s->gates1) && al16(s->bn_stats) && al16(g->du) && al16(g->dbn) && al16(g->dgi0) &&
-                       al16(g->dgh0) && al16(g->dgi1) && al16(g->dgh1) && al16(g->dh_init) && al16(g->bn_bwd_partial) &&
-                       al16(w->bn_w);
-    bool cluster = split && persist_enabled() && T >= 3 && dec_cluster_shape(D, H) && (int64_t)nblk * ((H + 15) >> 4) <= device_cu_count() &&
-                   (!keep_l0 || al16(keep_l0)) && dec_cluster_bwd_xch_bytes(nblk, H) <= workspace_bytes && !g->dw_gru[0] && !g->dw_gru[1] &&
-                   !g->dw_gru[2] && !g->dw_gru[3] && !s->loss_code;
-    if (cluster) {
-      const void* fn = (const void*)dec_cluster_bwd_kernel<DCL_KS>;
-      static bool attr_set = false;
-      int nocc = 0;
-      if (!attr_set) attr_set = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dec_cluster_bwd_dyn_lds()) == hipSuccess;
-      cluster = attr_set && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, dec_cluster_bwd_dyn_lds()) == hipSuccess && nocc >= 1;
-    }
-    if (!cluster) g2v_internal_preclear_drop(workspace, workspace_bytes);
-    if (cluster) {
-      // ONE persistent launch for the whole BPTT (dec_cluster_bwd_kernel): weights read in place, no transposes
-      const size_t Hp = (size_t)((H + 15) & ~15);
-      unsigned long long* x0 = reinterpret_cast<unsigned long long*>(workspace);
-      DecClBwdArgs ca;
-      ca.keep95 = keep95; ca.keep_l0 = keep_l0; ca.w = *w; ca.sv = *s; ca.g = *g;
-      ca.xd = x0; ca.xp = x0 + (size_t)2 * nblk * 16 * Hp; ca.xq = ca.xp + (size_t)2 * nblk * 2 * Hp;
-      ca.xcc = reinterpret_cast<unsigned*>(ca.xq + (size_t)nblk * 4 * (Hp / 16) * 16 * Hp);
-      ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
-      ca.T = T; ca.B = B; ca.D = D; ca.H = H; ca.n_pre = n_pre_poses; ca.conditioned = conditioned; ca.p_drop = p_drop;
-      ca.nt = (H + 15) >> 4; ca.nblk = nblk;
-      if (!g2v_internal_preclear_take(x0, dec_cluster_bwd_xch_bytes(nblk, H)) &&
-          hipMemsetAsync(x0, 0, dec_cluster_bwd_xch_bytes(nblk, H), st) != hipSuccess) {
+  const DecRoutePlan pl = dec_plan_call(true, T, B, D, H, true, f);
+  if (pl.route == 0) {
+    set_error("g2v_dec_rollout_bwd: %s", pl.msg);
+    return pl.err;
+  }
+  // ---- 3. the launches ----
+  const DecBwdCall c{w, s, g, keep95, keep_l0, p_drop, n_pre_poses, conditioned, T, B, D, H, (hipStream_t)stream,
+                     prepared_req && dec_prepared_shape(D, H)};
+  const DecBwdWs ws = dec_bwd_ws(w, B, D, H, workspace, pl.route == G2V_DEC_ROUTE_CLUSTER ? pl.nblk : 0);
+  if (pl.route != G2V_DEC_ROUTE_CLUSTER) g2v_internal_preclear_drop(workspace, workspace_bytes);
+  if (pl.pack && !c.prepared) {
+    launch_pack(ws.pb, c.st);
+    G2V_CHECK_LAUNCH();
+  }
+  switch (pl.route) {
+    case G2V_DEC_ROUTE_PERSIST:
+      return dec_persist_bwd_launch(w, s, g, keep95, keep_l0, p_drop, n_pre_poses, conditioned, T, B, ws.tw.w_pre_t, ws.tw.w_out_t,
+                                    ws.tw.w_ih0_t, ws.tw.w_hh0_t, ws.tw.w_ih1_t, ws.tw.w_hh1_t, ws.xbase, c.st, !c.prepared,
+                                    f.wgrad_any ? ws.wslab : nullptr, pl.tiles);
+    case G2V_DEC_ROUTE_CLUSTER:
+      if (dec_bwd_launch_cluster(c, pl, ws) != G2V_OK) {
         set_error("g2v_dec_rollout_bwd: clearing the exchange records failed");
         return G2V_ERR_LAUNCH;
       }
-      hipLaunchKernelGGL(dec_cluster_bwd_kernel<DCL_KS>, dim3(((H + 15) >> 4) * nblk), dim3(256), dec_cluster_bwd_dyn_lds(), st, ca);
-      G2V_CHECK_LAUNCH();
-      return G2V_OK;
-    }
-    if (split) {
-      const int64_t BH = (int64_t)B * H, BD = (int64_t)B * D, BG = 3 * BH;
-      float* w_pre_t = p;                 p += (size_t)D * H;
-      float* w_out_t = p;                 p += (size_t)H * D;
-      float* w_hh1_t = p;                 p += (size_t)3 * H * H;
-      float* w_ih1_t = p;                 p += (size_t)3 * H * H;
-      float* w_hh0_t = p;                 p += (size_t)3 * H * H;
-      float* w_ih0_t = p;                 p += (size_t)3 * H * H;
-      float* direct1 = p;                 p += (size_t)BH;
-      float* direct0 = p;
-      launch_transpose(w->w_pre, w_pre_t, H, D, st);          // (H,D) -> (D,H)
-      launch_transpose(w->w_out, w_out_t, D, H, st);          // (D,H) -> (H,D)
-      launch_transpose(w->w_hh1, w_hh1_t, 3 * H, H, st);      // (3H,H) -> (H,3H)
-      launch_transpose(w->w_ih1, w_ih1_t, 3 * H, H, st);
-      launch_transpose(w->w_hh0, w_hh0_t, 3 * H, H, st);
-      launch_transpose(w->w_ih0, w_ih0_t, 3 * H, H, st);
-      const bool drop = keep_l0 && p_drop > 0.f;
-      const int nht = (H + 15) >> 4, ndt = (D + 15) >> 4;
-      for (int t = T - 1; t >= 0; --t) {
-        const bool last = (t == T - 1);
-        if (!last) {
-          DecBwdDyArgs a{};
-          a.part = g->bn_bwd_partial + (int64_t)((t + 1) & 1) * nblk * 2 * H;
-          a.stats = s->bn_stats + (int64_t)t * 2 * H; a.u = s->u + t * BH; a.dbn = g->dbn + t * BH; a.bn_w = w->bn_w;
-          a.du = g->du + t * BH; a.d_bn_w = g->d_bn_w; a.d_bn_b = g->d_bn_b; a.w_pre_t = w_pre_t;
-          a.dy = g->dy + t * BD; a.keep95 = keep95 + t * BD;
-          a.nblk = nblk; a.first_acc = (t == T - 2) ? 1 : 0; a.feedback = (conditioned && t >= n_pre_poses) ? 1 : 0; a.only_a = (t == 0) ? 1 : 0;
-          hipLaunchKernelGGL(dec_bwd_dy_split_kernel, dim3(nblk, (a.feedback && !a.only_a) ? ndt : 1), dim3(64), 0, st, a, B, D, H);
-        }
-        if (t == 0) break;
-        DecBwdCell1Args c{};
-        c.dy = g->dy + t * BD; c.w_out_t = w_out_t; c.carry = last ? nullptr : g->dh_init + BH;
-        c.gates = s->gates1 + (t - 1) * 4 * BH; c.hprev = s->h1 + (t - 1) * BH;
-        c.dgi = g->dgi1 + (t - 1) * BG; c.dgh = g->dgh1 + (t - 1) * BG; c.direct = direct1;
-        hipLaunchKernelGGL(dec_bwd_cell1_split_kernel, dim3(nblk, nht), dim3(64), 0, st, c, B, D, H);
-        DecBwdPairArgs e{};
-        e.dgh = g->dgh1 + (t - 1) * BG; e.w_hh_t = w_hh1_t; e.direct = direct1; e.carry_out = g->dh_init + BH;
-        e.dgi = g->dgi1 + (t - 1) * BG; e.w_ih_t = w_ih1_t;
-        e.keep = drop ? keep_l0 + (t - 1) * BH : nullptr; e.keep_scale = 1.0f / (1.0f - p_drop);
-        e.carry0 = last ? nullptr : g->dh_init; e.gates0 = s->gates0 + (t - 1) * 4 * BH; e.hprev0 = s->h0 + (t - 1) * BH;
-        e.dgi0 = g->dgi0 + (t - 1) * BG; e.dgh0 = g->dgh0 + (t - 1) * BG; e.direct0 = direct0;
-        hipLaunchKernelGGL(dec_bwd_pair_split_kernel<false>, dim3(nblk, nht), dim3(128), 0, st, e, B, H);
-        DecBwdPairArgs f{};
-        f.dgh = g->dgh0 + (t - 1) * BG; f.w_hh_t = w_hh0_t; f.direct = direct0; f.carry_out = g->dh_init;
-        f.dgi = g->dgi0 + (t - 1) * BG; f.w_ih_t = w_ih0_t;
-        f.a_act = s->a + (t - 1) * BH; f.u = s->u + (t - 1) * BH; f.stats = s->bn_stats + (int64_t)(t - 1) * 2 * H;
-        f.dbn = g->dbn + (t - 1) * BH; f.part = g->bn_bwd_partial + (int64_t)(t & 1) * nblk * 2 * H;
-        hipLaunchKernelGGL(dec_bwd_pair_split_kernel<true>, dim3(nblk, nht), dim3(128), 0, st, f, B, H);
-      }
-      G2V_CHECK_LAUNCH();
-      return G2V_OK;
-    }
-  }
-  PackBatch pb;
-  const DecTW tw = dec_bwd_pack_layout(w, D, H, workspace, pb);
-  if (!prepared) {
-    launch_pack(pb, st);
-    G2V_CHECK_LAUNCH();
-  }
-  if (lds > 48 * 1024) {
-    (void)hipFuncSetAttribute((const void*)dec_step_bwd_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)dec_step_bwd_kernel<64, 135>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  int scratch = 1024;
-  (void)dec_bwd_lds(D, H, &scratch);
-  DecDims dm{T, B, D, H, p_drop, n_pre_poses, conditioned, 1, cdiv(B, 16), (H == 64 && D == 135) ? dec_wt_stores() : 0, scratch};
-  const bool fast = (H == 64) && (D == 135);
-  {
-    auto a16 = [](const void* q_) { return (reinterpret_cast<uintptr_t>(q_) & 15) == 0; };
-    const int ptiles = persist_tiles_per_wg(dm.nblk);
-    const bool persist = fast && ptiles >= 1 && (B % 4) == 0 &&      // (B % 16 != 0: a ragged last tile, the multi-tile kernels)
-                        
-                         a16(s->u) && a16(s->a) && a16(s->h0) && a16(s->h1) && a16(s->gates0) && a16(s->gates1) &&
-                         a16(s->bn_stats) && a16(g->dy) && a16(g->du) && a16(g->dgi0) && a16(g->dgh0) && a16(g->dgi1) &&
-                         a16(g->dgh1) && a16(g->dh_init) && a16(keep95) && a16(keep_l0) && a16(workspace);
-    bool want_w = false, ok_w = true;
-    const int fmask = g2v_dec_rollout_bwd_fuses_wgrad(B, D, H);
-    for (int m = 0; m < 4; ++m) {
-      const bool has = g->dw_gru[m] || g->db_gru[m];
-      want_w = want_w || has;
-      ok_w = ok_w && (((fmask >> m) & 1) ? (g->dw_gru[m] && g->db_gru[m]) : !has);      // exactly the fused matrices, both pointers
-    }
-    if (want_w && !(ok_w && persist && fmask != 0)) {
-      set_error("g2v_dec_rollout_bwd: dw_gru / db_gru must name exactly the matrices of g2v_dec_rollout_bwd_fuses_wgrad(B, D, H)");
-      return G2V_ERR_UNSUPPORTED;
-    }
-    if (s->loss_code && !(persist && s->loss_coef && s->loss_partial && s->loss_terms && s->y && a16(s->y) &&
-                          g2v_dec_rollout_fuses_loss(B, D, H, T))) {
-      set_error("g2v_dec_rollout_bwd: the loss_* fields are set where g2v_dec_rollout_fuses_loss(B, D, H, T) does not hold");
-      return G2V_ERR_UNSUPPORTED;
-    }
-    if (persist)
-      return dec_persist_bwd_launch(w, s, g, keep95, keep_l0, p_drop, n_pre_poses, conditioned, T, B, tw.w_pre_t, tw.w_out_t,
-                                    tw.w_ih0_t, tw.w_hh0_t, tw.w_ih1_t, tw.w_hh1_t, (char*)workspace + bwd_pack_bytes_aligned(D, H), st,
-                                    !prepared,
-                                    want_w ? (float*)((char*)workspace + bwd_pack_bytes_aligned(D, H) + PX_BYTES) : nullptr, ptiles);
-  }
-  for (int t = T - 1; t >= 0; --t) {
-    if (fast)
-      hipLaunchKernelGGL((dec_step_bwd_kernel<64, 135>), dim3(dm.nblk), dim3(256), lds, st, *w, tw, *s, *g, keep95, keep_l0, dm, t);
-    else
-      hipLaunchKernelGGL((dec_step_bwd_kernel<0, 0>), dim3(dm.nblk), dim3(512), lds, st, *w, tw, *s, *g, keep95, keep_l0, dm, t);
+      break;
+    case G2V_DEC_ROUTE_SPLIT: dec_bwd_launch_split(c, pl, ws); break;
+    default: dec_bwd_launch_steps(c, pl, ws); break;      // STEP, STEP_FAST
   }
   G2V_CHECK_LAUNCH();
   return G2V_OK;

@@ -541,28 +541,51 @@ typedef struct {           /* saved-for-backward / state arrays, all caller-owne
 } g2v_dec_saved;
 
 int g2v_dec_rollout_blocks(int B);
-/* Two interchangeable implementations sit behind g2v_dec_rollout_fwd / _bwd (same arguments, same saved arrays):
- * one launch per time step (any shape), and -- for H == 64, D == 135, B % 16 == 0, B / 16 <= 3 x the device's CU count --
- * ONE persistent launch for the whole rollout with register/LDS-resident weights and an in-kernel two-level exchange of
- * the BatchNorm partial sums (csrc/dec_persist.hpp): one 16-row tile per workgroup while there is a CU per tile, 2 or 3 tiles
- * per workgroup beyond that (no fused weight gradient / loss chaser there: the two queries below return 0).  The persistent
- * one is used whenever it applies; this switch (default 1; 0 = one launch per step; 2 / 3 = persistent with AT LEAST that many
- * tiles per workgroup, which is how the parity tests reach the multi-tile kernels at small batches) exists for A/B
- * measurements, parity tests and the fall-back after a latched fault.  Returns the previous setting.
- * Round 5: the same switch covers the CLUSTER kernels of the generic dims (H % 4 == 0, H <= 208, D <= 64 -- every shipped YAML's
- * H = 200 -- at small batch): where the per-step path runs three / four launches per step over (hidden-unit tile x row group)
- * workgroups, and that grid fits the device with one workgroup per CU (B <= 304 at H = 200), the steps t >= 1 of the forward and the
- * whole backward are ONE launch each with those workgroups resident: weight rows in registers, the rows a kernel boundary used to
- * hand over (u / h0 / h1 and the BatchNorm sums forward; dbn rows, BatchNorm-backward sums and the partial products of the
- * 3H-long contractions backward) exchanged through tagged 8-byte granules in the call's workspace (csrc/dec_rollout.hip:
- * dec_cluster_fwd_kernel / dec_cluster_bwd_kernel).  Same saved arrays, results equal to summation order, bitwise reproducible.
- * LEGACY FORWARD = g2v_ctx_set_option(NULL, G2V_OPT_PERSISTENT, enable). */
+/* Five implementations sit behind g2v_dec_rollout_fwd / _bwd (same arguments, same saved arrays, results equal to summation
+ * order, each bitwise reproducible).  Which one a call runs on is decided once, from its sizes, the G2V_OPT_PERSISTENT level
+ * (0..3, default 1), the device's CU count and a few facts of the call; g2v_dec_rollout_route reports the decision (host
+ * arithmetic only, no launch).  nblk = ceil(B / 16) row tiles, nt = ceil(H / 16) hidden-unit tiles.  In order:
+ *   PERSIST    H == 64, D == 135, B % 4 == 0 (a ragged last tile where B % 16 != 0), level >= 1, every array of the call 16-byte
+ *              aligned, and R = max(ceil(nblk / min(CUs, 256)), min(level, nblk)) <= 3 row tiles per workgroup: ONE launch for
+ *              the whole rollout, register / LDS-resident weights, an in-kernel two-level exchange of the BatchNorm partial sums
+ *              (csrc/dec_persist.hpp).  Levels 2 / 3 ask for AT LEAST that many tiles per workgroup: how the parity tests reach
+ *              the multi-tile kernels at small batches.  With R == 1 and B % 16 == 0 it also carries custom_loss
+ *              (g2v_dec_rollout_fuses_loss, 2 <= T <= 256) and the W_hh1 weight gradient (g2v_dec_rollout_bwd_fuses_wgrad).
+ *   CLUSTER    H != 64 or D != 135, H % 4 == 0, 4 <= H <= 208, D <= 64 (every shipped YAML's H = 200), T >= 3, level >= 1,
+ *              nblk <= 64 and nblk * nt <= CUs (B <= 304 at H = 200 on 256 CUs), the split route's arrays and keep_l0 16-byte
+ *              aligned, the exchange records within workspace_bytes, the kernel resident at one workgroup per CU: ONE launch for
+ *              the forward and one for the backward over (hidden-unit tile x row group) workgroups, weight rows in registers,
+ *              the rows a kernel boundary used to hand over (u / h0 / h1 and the BatchNorm sums forward; dbn rows, BatchNorm-
+ *              backward sums and the partial products of the 3H-long contractions backward) exchanged through tagged 8-byte
+ *              granules in the workspace (csrc/dec_rollout.hip: dec_cluster_fwd_kernel / dec_cluster_bwd_kernel).
+ *   SPLIT      H != 64 or D != 135, H % 4 == 0, H <= 256, D <= 64, nblk <= 64 (B <= 1024), its arrays 16-byte aligned: forward
+ *              step 0 as the generic per-step kernel, then three launches per step over the same workgroups; backward six
+ *              transposes, then three / four launches per step.
+ *   STEP_FAST  H == 64, D == 135 otherwise: one fused launch per time step, dims compile-time constants.
+ *   STEP       every other shape: the same with run-time dims.
+ * The optional fields no route but PERSIST honours -- the loss_* fields of g2v_dec_saved, dw_gru / db_gru of g2v_dec_grads -- are
+ * refused with G2V_ERR_UNSUPPORTED on every other route, nothing launched, never silently ignored; a shape whose step kernel
+ * would need more than 160 KB of LDS is refused likewise.
+ * g2v_dec_rollout_route returns G2V_DEC_ROUTE_* (PERSIST: with R in bits 8..9), or 0 for sizes the calls reject (T < 2, B, D or
+ * H < 1) and for flag combinations they refuse.  persistent: the level, -1 = the bound context's; cus: the CU count, 0 = the
+ * device's; flags: G2V_DEC_PLAN_* facts of the call (0: aligned arrays, a workspace of the queried size, no optional field). */
+#define G2V_DEC_ROUTE_STEP 1        /* generic per-step kernel */
+#define G2V_DEC_ROUTE_STEP_FAST 2   /* H = 64, D = 135 per-step kernel */
+#define G2V_DEC_ROUTE_SPLIT 3       /* step 0 generic, then per-phase launches */
+#define G2V_DEC_ROUTE_CLUSTER 4     /* one launch for t >= 1 (forward) / the whole backward */
+#define G2V_DEC_ROUTE_PERSIST 5     /* one launch; tiles per workgroup in bits 8..9 */
+#define G2V_DEC_PLAN_UNALIGNED 1    /* some pointer of the call is not 16-byte aligned */
+#define G2V_DEC_PLAN_WGRAD 2        /* dw_gru / db_gru of g2v_dec_rollout_bwd_fuses_wgrad() are set */
+#define G2V_DEC_PLAN_LOSS 4         /* the loss_* fields are set */
+int g2v_dec_rollout_route(int backward, int T, int B, int D, int H, int training, int persistent /* 0..3, -1: the bound context's */,
+                          int cus /* 0: the device's */, int flags);
+/* The G2V_OPT_PERSISTENT level of the calling thread's context (see g2v_dec_rollout_route; it also switches the code decoder's
+ * cluster kernel): exists for A/B measurements, parity tests and the fall-back after a latched fault.  Returns the previous
+ * setting.  LEGACY FORWARD = g2v_ctx_set_option(NULL, G2V_OPT_PERSISTENT, enable). */
 int g2v_dec_rollout_set_persistent(int enable);
-/* which of the two g2v_dec_rollout_fwd / _bwd take for this shape under the current setting: 0 = one launch per time step,
- * R = 1..3 = the persistent pair with R row tiles per workgroup (B % 4 == 0; a ragged last tile where B % 16 != 0) */
+/* 0, or R = 1..3 where a call of this shape runs as PERSIST with R row tiles per workgroup (g2v_dec_rollout_route, no flags) */
 int g2v_dec_rollout_tiles_per_workgroup(int B, int D, int H);
-/* 1: for this shape g2v_dec_rollout_fwd / _bwd run as the small-batch cluster kernels (one launch for the steps t >= 1 of the
- * forward, one for the backward; needs T >= 3 and a workspace of the queried size) under the current setting, 0: not */
+/* 1 where a call of this shape with T >= 3 runs as CLUSTER (g2v_dec_rollout_route, no flags), 0: not */
 int g2v_dec_rollout_cluster_ok(int B, int D, int H);
 /* The persistent kernels need every workgroup of their launch resident at once; what a plain launch can check is checked
  * (B / 16 <= CU count, the occupancy query).  What it cannot see -- a CU mask, another tenant or a second persistent launch
@@ -577,10 +600,9 @@ int g2v_dec_rollout_persist_fault(int clear);
  * else 0.0f -- in front of the SUM all-reduce, with `flag` a slot of the communication buffer; from_flag != 0: a non-zero
  * (reduced) flag latches this process too (value 3), so that EVERY rank's commit kernels skip the step a faulting rank poisoned. */
 int g2v_dec_rollout_fault_flag(float* flag, int from_flag, g2v_stream_t stream);
-/* 1 where the rollout pair + chaser can carry custom_loss (the loss_* fields of g2v_dec_saved): wherever the persistent path
- * applies with ONE row tile per workgroup (H == 64, D == 135, B % 16 == 0, B / 16 <= CU count, persistent setting 1), 2 <= T <= 256.  Elsewhere leave the loss_*
- * fields NULL and call g2v_custom_loss_fwd_bwd between the two rollouts (setting them anyway is refused with
- * G2V_ERR_UNSUPPORTED, never silently ignored). */
+/* 1 where the rollout pair + chaser can carry custom_loss (the loss_* fields of g2v_dec_saved; training only): PERSIST with one
+ * full row tile per workgroup and 2 <= T <= 256 (g2v_dec_rollout_route).  Elsewhere leave the loss_* fields NULL and call
+ * g2v_custom_loss_fwd_bwd between the two rollouts (setting them anyway is refused with G2V_ERR_UNSUPPORTED). */
 int g2v_dec_rollout_fuses_loss(int B, int D, int H, int T);
 /* The chaser (csrc/dec_persist.hip, loss_chase_kernel): one light workgroup per 16 batch rows (256 threads, <= 128 registers per
  * lane, 64 B of LDS) that is CO-RESIDENT with the persistent forward rollout -- which runs one wave per SIMD and leaves a third of
@@ -619,10 +641,10 @@ typedef struct {           /* gradient outputs of the rollout backward, caller-o
 
 /* workspace: transposed weights in MFMA fragment order. */
 size_t g2v_dec_rollout_bwd_workspace(int D, int H);
-/* Which GRU weight gradients g2v_dec_rollout_bwd can accumulate inside its persistent kernel at this batch / shape: bit m of
- * the result <-> matrix m of (W_ih0, W_hh0, W_ih1, W_hh1).  Today 8 (W_hh1: what the kernel's register budget has room for) where
- * the persistent path applies (H == 64, D == 135, B % 16 == 0, B / 16 <= CU count), else 0.
- * The caller sets dw_gru[m] / db_gru[m] for exactly those matrices (or for none) and forms the other products itself. */
+/* Which GRU weight gradients g2v_dec_rollout_bwd accumulates inside its persistent kernel at this batch / shape: bit m of the
+ * result <-> matrix m of (W_ih0, W_hh0, W_ih1, W_hh1).  Today 8 (W_hh1: what the kernel's register budget has room for) on
+ * PERSIST with one full row tile per workgroup (g2v_dec_rollout_route), else 0.  The caller sets dw_gru[m] / db_gru[m] for exactly
+ * those matrices (or for none) and forms the other products itself; anything else is refused with G2V_ERR_UNSUPPORTED. */
 int g2v_dec_rollout_bwd_fuses_wgrad(int B, int D, int H);
 int g2v_dec_rollout_bwd(const g2v_dec_weights* w, const g2v_dec_saved* s, const g2v_dec_grads* g,
                         const uint8_t* keep95, const uint8_t* keep_l0, float p_drop, int n_pre_poses,

@@ -1,0 +1,87 @@
+"""Shapes of the decoder-rollout dispatch tests (no torch, no device): the sweep of the workspace pin
+(tests/golden/dec_rollout_workspace.npz) and DEC_ROUTE_SHAPES -- for every route of g2v_dec_rollout_route and both directions the
+smallest shape that selects it and the nearest shapes that just miss it, at 256 CUs.  tests/test_dec_route_host.py holds the table to
+the query on the CPU; tests/test_gpu_ops.py checks the older queries against it at the device's own CU count."""
+from gesture2vec_amd import _lib
+
+WORKSPACE_D = (1, 16, 40, 45, 64, 65, 135, 200)
+WORKSPACE_H = (4, 50, 64, 200, 208, 212, 256, 300)
+
+ROUTES = {k[len("G2V_DEC_ROUTE_"):]: v for k, v in _lib.CONSTANTS.items() if k.startswith("G2V_DEC_ROUTE_")}
+FLAGS = {k[len("G2V_DEC_PLAN_"):]: v for k, v in _lib.CONSTANTS.items() if k.startswith("G2V_DEC_PLAN_")}
+
+
+def route_name(T, B, D, H, *, backward=False, training=True, persistent=1, cus=256, flags=(), **_):
+    """g2v_dec_rollout_route as a name: "STEP", "CLUSTER", "PERSIST*2" (two row tiles per workgroup), ...; "" where the call
+    would be rejected or refused.  persistent=-1 / cus=0: the bound context's level / the device's CU count."""
+    r = _lib.load().g2v_dec_rollout_route(int(backward), T, B, D, H, int(training), persistent, cus, sum(FLAGS[f] for f in flags))
+    if r == 0:
+        return ""
+    name = [k for k, v in ROUTES.items() if v == (r & 0xff)][0]
+    assert (r >> 8) == 0 or name == "PERSIST", r
+    return name + (f"*{r >> 8}" if name == "PERSIST" else "")
+
+
+def _case(name, route, T, B, D, H, **kw):
+    return dict(name=name, route=route, T=T, B=B, D=D, H=H, **kw)
+
+
+def _both(name, route, T, B, D, H, **kw):      # the same route forward and backward
+    return [_case(name, route, T, B, D, H, **kw), _case(name + ", backward", route, T, B, D, H, backward=True, **kw)]
+
+
+# fuses_loss / wgrad: what g2v_dec_rollout_fuses_loss(B, D, H, T) / g2v_dec_rollout_bwd_fuses_wgrad(B, D, H) say there (where stated)
+DEC_ROUTE_SHAPES = tuple(
+    _both("persistent, one tile", "PERSIST*1", 2, 16, 135, 64, fuses_loss=1, wgrad=8)
+    + _both("persistent, smallest batch", "PERSIST*1", 2, 4, 135, 64, fuses_loss=0, wgrad=0)
+    + _both("persistent, ragged last tile", "PERSIST*1", 2, 20, 135, 64, fuses_loss=0, wgrad=0)
+    + _both("fast per-step: B % 4 != 0", "STEP_FAST", 2, 37, 135, 64, fuses_loss=0, wgrad=0)
+    + _both("persistent, a CU per tile", "PERSIST*1", 2, 4096, 135, 64, fuses_loss=1, wgrad=8)
+    + _both("persistent, two tiles", "PERSIST*2", 2, 4112, 135, 64, fuses_loss=0, wgrad=0)
+    + _both("persistent, two tiles still", "PERSIST*2", 2, 8192, 135, 64)
+    + _both("persistent, three tiles", "PERSIST*3", 2, 8208, 135, 64, fuses_loss=0, wgrad=0)
+    + _both("persistent, three tiles still", "PERSIST*3", 2, 12288, 135, 64)
+    + _both("fast per-step: four tiles are not offered", "STEP_FAST", 2, 12304, 135, 64)
+    + _both("level 2 at two tiles", "PERSIST*2", 2, 32, 135, 64, persistent=2)
+    + _both("level 2 at one tile", "PERSIST*1", 2, 16, 135, 64, persistent=2)
+    + _both("level 3 at three tiles", "PERSIST*3", 2, 48, 135, 64, persistent=3)
+    + _both("level 0: fast per-step", "STEP_FAST", 2, 16, 135, 64, persistent=0)
+    + _both("unaligned: fast per-step", "STEP_FAST", 2, 16, 135, 64, flags=("UNALIGNED",))
+    + _both("eight CUs: two tiles", "PERSIST*2", 2, 256, 135, 64, cus=8)
+    + _both("cluster, smallest", "CLUSTER", 3, 1, 1, 4)
+    + _both("cluster, H = 208 up to the CU count", "CLUSTER", 3, 304, 64, 208)
+    + _both("cluster, shipped dims", "CLUSTER", 3, 128, 40, 200)
+    + _both("cluster, H = 64 off the fast D", "CLUSTER", 3, 16, 64, 64)
+    + _both("split: T = 2", "SPLIT", 2, 128, 40, 200)
+    + _both("split: the grid no longer fits", "SPLIT", 3, 305, 64, 208)
+    + _both("split: H = 212", "SPLIT", 3, 16, 40, 212)
+    + _both("split: H = 256", "SPLIT", 3, 16, 40, 256)
+    + _both("split: level 0", "SPLIT", 3, 128, 40, 200, persistent=0)
+    + _both("split: eight CUs", "SPLIT", 3, 128, 40, 200, cus=8)
+    + _both("split: 64 row groups", "SPLIT", 3, 1024, 40, 200)
+    + _both("generic per-step: D = 65", "STEP", 3, 16, 65, 200)
+    + _both("generic per-step: H % 4 != 0", "STEP", 3, 16, 40, 50)
+    + _both("generic per-step: 65 row groups", "STEP", 3, 1040, 40, 200)
+    + [_case("generic per-step: H = 260", "STEP", 3, 16, 40, 260),
+       _case("refused: H = 260 backward needs more than 160 KB of LDS", "", 3, 16, 40, 260, backward=True)]
+    + _both("generic per-step: unaligned", "STEP", 3, 128, 40, 200, flags=("UNALIGNED",))
+    + [
+        _case("wgrad set where nothing is fused: split shape", "", 3, 16, 40, 200, backward=True, flags=("WGRAD",)),
+        _case("wgrad set where nothing is fused: T = 2", "", 2, 128, 40, 200, backward=True, flags=("WGRAD",)),
+        _case("wgrad set where nothing is fused: ragged", "", 2, 20, 135, 64, backward=True, flags=("WGRAD",)),
+        _case("wgrad set where nothing is fused: two tiles", "", 2, 4112, 135, 64, backward=True, flags=("WGRAD",)),
+        _case("wgrad set where nothing is fused: per-step", "", 2, 16, 135, 64, backward=True, persistent=0, flags=("WGRAD",)),
+        _case("wgrad set, fused", "PERSIST*1", 2, 16, 135, 64, backward=True, flags=("WGRAD",)),
+        _case("loss set, fused", "PERSIST*1", 256, 16, 135, 64, flags=("LOSS",)),
+        _case("loss set, fused, backward", "PERSIST*1", 256, 16, 135, 64, backward=True, flags=("LOSS", "WGRAD")),
+        _case("loss set: T = 257", "", 257, 16, 135, 64, flags=("LOSS",)),
+        _case("loss set: T = 257, backward", "", 257, 16, 135, 64, backward=True, flags=("LOSS",)),
+        _case("loss set: not training", "", 2, 16, 135, 64, training=False, flags=("LOSS",)),
+        _case("loss set: ragged", "", 2, 20, 135, 64, flags=("LOSS",)),
+        _case("loss set: cluster shape, backward", "", 3, 128, 40, 200, backward=True, flags=("LOSS",)),
+        _case("loss set: unaligned", "", 2, 16, 135, 64, flags=("LOSS", "UNALIGNED")),
+        _case("rejected: T = 1", "", 1, 16, 135, 64),
+        _case("rejected: B = 0", "", 3, 0, 40, 200),
+        _case("rejected: H = 0", "", 3, 16, 40, 0, backward=True),
+        _case("rejected: D = 0", "", 3, 16, 0, 200),
+    ])

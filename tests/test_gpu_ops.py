@@ -13,6 +13,7 @@ import torch
 from oracle import g2v_oracle as O
 from _f64 import as64, default64
 from _wgrad_shapes import WGRAD_ROUTE_SHAPES, route_name
+from _dec_route_shapes import DEC_ROUTE_SHAPES, route_name as dec_route_name
 
 pytestmark = pytest.mark.gpu
 
@@ -1007,6 +1008,12 @@ def _alloc_saved(T, B, D, H, nblk, dev, p):
             "gates1": z(T - 1, B, 4 * H), "bn_partial": z(2, nblk, 2, H), "bn_stats": z(T - 1, 2, H)}
 
 
+def _dec_route_now(T, B, D, H, backward=False, training=True):
+    """the route g2v_dec_rollout_fwd / _bwd take for a call with aligned (torch) arrays, under the bound context's persistent
+    level and on this device: "STEP", "STEP_FAST", "SPLIT", "CLUSTER", "PERSIST*<tiles per workgroup>" """
+    return dec_route_name(T, B, D, H, backward=backward, training=training, persistent=-1, cus=0)
+
+
 # H = 64, D = 135 with B % 16 == 0 runs the PERSISTENT rollout kernels (csrc/dec_persist.hip): 32 rows = one exchange group of
 # two workgroups, 320 = a full group + a partial one, 4096 = the whole chip (256 workgroups, 16 groups).
 @pytest.mark.parametrize("T,B,D,H,p", [(34, 32, 135, 64, 0.0), (20, 8, 40, 50, 0.2), (6, 37, 135, 64, 0.3), (3, 16, 40, 200, 0.0),
@@ -1085,8 +1092,12 @@ def test_dec_rollout_fwd_bwd(ops, T, B, D, H, p):
             relclose(db, g_ref[pre + bname], 3e-3 if B >= 4096 else 3e-4, bname)
 
 
-@pytest.mark.parametrize("T,B,D,H", [(10, 20, 135, 64), (6, 20, 40, 200), (10, 48, 135, 64)])   # fused step / split / persistent kernels
+# persistent (ragged tile) / cluster / persistent / fused step / split / generic step kernels
+@pytest.mark.parametrize("T,B,D,H", [(10, 20, 135, 64), (6, 20, 40, 200), (10, 48, 135, 64), (10, 21, 135, 64), (6, 20, 40, 212),
+                                     (6, 19, 65, 200)])
 def test_dec_rollout_eval_mode(ops, T, B, D, H):
+    assert _dec_route_now(T, B, D, H, training=False) == {(20, 64): "PERSIST*1", (20, 200): "CLUSTER", (48, 64): "PERSIST*1",
+                                                          (21, 64): "STEP_FAST", (20, 212): "SPLIT"}.get((B, H), "STEP")
     sd = _dec_state(D, H, seed=9)
     g = torch.Generator().manual_seed(78)
     sd["decoder.decoder.pre_linear.1.running_mean"] = torch.randn(H, generator=g) * 0.1
@@ -1212,6 +1223,7 @@ def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n
 
     def fwd(setting):
         with _lib.Context.current().scoped(persistent=setting):
+            assert _dec_route_now(T, B, D, H, training=training) == ("CLUSTER" if setting else "SPLIT")
             wt, _ = _dec_weight_tensors(sd, DEV)
             saved = _alloc_saved(T, B, D, H, nblk, DEV, p)
             for v in saved.values():
@@ -1243,6 +1255,7 @@ def test_dec_cluster_forward_matches_the_per_step_launches(ops, T, B, D, H, p, n
 
     def bwd(setting):
         with _lib.Context.current().scoped(persistent=setting):
+            assert _dec_route_now(T, B, D, H, backward=True) == ("CLUSTER" if setting else "SPLIT")
             grads = {"dy": gy.clone(), "du": z(T - 1, B, H), "dbn": z(T - 1, B, H), "dgi0": z(T - 1, B, G), "dgh0": z(T - 1, B, G),
                      "dgi1": z(T - 1, B, G), "dgh1": z(T - 1, B, G), "dh_init": z(2, B, H), "d_bn_w": z(H), "d_bn_b": z(H),
                      "bn_bwd_partial": z(2, nblk, 2, H)}
@@ -1288,8 +1301,13 @@ def test_dec_rollout_multi_tile_persistent_matches_per_step_kernels(ops, B, mode
     G = 3 * H
     z = lambda *s: torch.zeros(*s, device=DEV)
 
+    cus = min(torch.cuda.get_device_properties(0).multi_processor_count, 256)
+    tiles = max(-(-nblk // cus), min(mode, nblk))      # one workgroup per CU, `mode` tiles at least where there are that many
+    assert 1 <= tiles <= 3 and (tiles > 1 or B % 16 != 0)
+
     def fwd(setting, training=True):
         with _lib.Context.current().scoped(persistent=setting):
+            assert _dec_route_now(T, B, D, H, training=training) == (f"PERSIST*{tiles}" if setting else "STEP_FAST")
             assert lib.g2v_dec_rollout_fuses_loss(B, D, H, T) == 0      # no chaser beside the multi-tile kernel
             wt, _ = _dec_weight_tensors(sd, DEV)
             ws = ops.dec_weights_struct(wt)
@@ -1300,6 +1318,7 @@ def test_dec_rollout_multi_tile_persistent_matches_per_step_kernels(ops, B, mode
 
     def bwd(setting, saved, ws):
         with _lib.Context.current().scoped(persistent=setting):
+            assert _dec_route_now(T, B, D, H, backward=True) == (f"PERSIST*{tiles}" if setting else "STEP_FAST")
             assert setting == 0 or lib.g2v_dec_rollout_bwd_fuses_wgrad(B, D, H) == 0      # the multi-tile kernel fuses nothing
             grads = {"dy": gy.clone(), "du": z(T - 1, B, H), "dbn": z(T - 1, B, H), "dgi0": z(T - 1, B, G),
                      "dgh0": z(T - 1, B, G), "dgi1": z(T - 1, B, G), "dgh1": z(T - 1, B, G), "dh_init": z(2, B, H),
@@ -1326,6 +1345,77 @@ def test_dec_rollout_multi_tile_persistent_matches_per_step_kernels(ops, B, mode
     (ea, _, wea), (eb, _, _) = fwd(mode, False), fwd(0, False)
     relclose(ea["y"], eb["y"], 2e-5, "multi-tile vs per-step eval forward")
     assert lib.g2v_dec_rollout_persist_fault(1) == 0
+
+
+def test_dec_rollout_queries_are_fields_of_the_route(ops):
+    """The four older queries against g2v_dec_rollout_route, at the shapes of the route table (tests/_dec_route_shapes.py), under
+    each persistent level the table uses and at this device's own CU count."""
+    from gesture2vec_amd import _lib
+    lib = _lib.load()
+    on_256 = torch.cuda.get_device_properties(0).multi_processor_count == 256
+    seen, met = set(), {False: set(), True: set()}
+    for c in DEC_ROUTE_SHAPES:
+        T, B, D, H, level = c["T"], c["B"], c["D"], c["H"], c.get("persistent", 1)
+        if c.get("flags") or min(T - 1, B, D, H) < 1 or (T, B, D, H, level) in seen:
+            continue
+        seen.add((T, B, D, H, level))
+        with _lib.Context.current().scoped(persistent=level):
+            tiles, cluster = lib.g2v_dec_rollout_tiles_per_workgroup(B, D, H), lib.g2v_dec_rollout_cluster_ok(B, D, H)
+            loss, wgrad = lib.g2v_dec_rollout_fuses_loss(B, D, H, T), lib.g2v_dec_rollout_bwd_fuses_wgrad(B, D, H)
+            for backward in (False, True):
+                r = _dec_route_now(T, B, D, H, backward)
+                if r == "":      # (H = 260: the backward step kernel's LDS)
+                    assert backward and H > 256, c["name"]
+                    continue
+                assert (tiles >= 1) == r.startswith("PERSIST") and (tiles == 0 or r == f"PERSIST*{tiles}"), (c["name"], r, tiles)
+                assert bool(cluster and T >= 3) == (r == "CLUSTER"), (c["name"], r, cluster)
+                assert (not loss and not wgrad) or r == "PERSIST*1", (c["name"], r, loss, wgrad)
+                met[backward].add(r.split("*")[0])
+            assert loss in (0, 1) and wgrad in (0, 8)
+            if on_256 and c.get("cus", 256) == 256:
+                assert c.get("fuses_loss", loss) == loss and c.get("wgrad", wgrad) == wgrad, (c["name"], loss, wgrad)
+    assert met[False] == met[True] == {k[len("G2V_DEC_ROUTE_"):] for k in _lib.CONSTANTS if k.startswith("G2V_DEC_ROUTE_")}, met
+
+
+def test_dec_rollout_bwd_refuses_weight_gradients_it_does_not_fuse(ops):
+    """dw_gru / db_gru on a route that does not accumulate them (here the small-batch cluster / split kernels): refused with
+    G2V_ERR_UNSUPPORTED, nothing launched -- never silently ignored.  The same call without them succeeds."""
+    T, B, D, H = 3, 16, 40, 200
+    G = 3 * H
+    assert _dec_route_now(T, B, D, H, backward=True) == "CLUSTER"
+    assert dec_route_name(T, B, D, H, backward=True, persistent=-1, cus=0, flags=("WGRAD",)) == ""
+    sd = _dec_state(D, H, seed=31)
+    g = torch.Generator().manual_seed(32)
+    wt, _ = _dec_weight_tensors(sd, DEV)
+    ws = ops.dec_weights_struct(wt)
+    nblk = ops.dec_rollout_blocks(B)
+    saved = _alloc_saved(T, B, D, H, nblk, DEV, 0.0)
+    k95 = (torch.rand(T - 1, B, D, generator=g) < 0.05).to(torch.uint8).to(DEV)
+    ops.dec_rollout_fwd(torch.randn(B, T, D, generator=g).to(DEV), (torch.randn(2, B, H, generator=g) * 0.5).to(DEV), ws, saved, k95,
+                        None, 0.0, 1, True, True, T, B, D, H)
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    SENTINEL = 7.0
+
+    def grads(**extra):
+        return dict({"dy": (torch.randn(T, B, D, generator=g) * 1e-3).to(DEV), "du": z(T - 1, B, H), "dbn": z(T - 1, B, H),
+                     "dgi0": z(T - 1, B, G), "dgh0": z(T - 1, B, G), "dgi1": z(T - 1, B, G),
+                     "dgh1": torch.full((T - 1, B, G), SENTINEL, device=DEV), "dh_init": z(2, B, H), "d_bn_w": z(H), "d_bn_b": z(H),
+                     "bn_bwd_partial": z(2, nblk, 2, H)}, **extra)
+
+    from gesture2vec_amd import _lib
+    for level in (1, 0):      # the cluster kernel and the per-phase launches alike
+        with _lib.Context.current().scoped(persistent=level):
+            assert _dec_route_now(T, B, D, H, backward=True) == ("CLUSTER" if level else "SPLIT")
+            bad = grads(dw_gru=[None, None, None, z(G, H)], db_gru=[None, None, None, z(G)])
+            with pytest.raises(RuntimeError, match=r"\(-4\).*exactly the matrices"):
+                ops.dec_rollout_bwd(ws, saved, bad, k95, None, 0.0, 1, True, T, B, D, H)
+            torch.cuda.synchronize()
+            assert float((bad["dgh1"] - SENTINEL).abs().max()) == 0.0, "a refused call wrote dgh1"
+            assert float(bad["dw_gru"][3].abs().max()) == 0.0 and float(bad["du"].abs().max()) == 0.0
+            good = grads()
+            ops.dec_rollout_bwd(ws, saved, good, k95, None, 0.0, 1, True, T, B, D, H)
+            torch.cuda.synchronize()
+            assert float((good["dgh1"] - SENTINEL).abs().min()) > 0.0 and bool(torch.isfinite(good["dgh1"]).all())
 
 
 # ----------------------------------------------------------------------------------------------- loss / optimiser / rng
@@ -1965,7 +2055,8 @@ def test_linear_bwd_weight_output_blocked_with_row_map(ops):
     relclose(db, dy.double().sum(0).float(), 1e-5, "db")
 
 
-@pytest.mark.parametrize("T,B,D,H", [(6, 32, 135, 64), (6, 24, 40, 200)])       # fused step kernels / per-phase split kernels
+# persistent / cluster / fused step / per-phase split kernels
+@pytest.mark.parametrize("T,B,D,H", [(6, 32, 135, 64), (6, 24, 40, 200), (6, 21, 135, 64), (6, 24, 40, 212)])
 @pytest.mark.parametrize("n_pre,conditioned", [(3, True), (1, False)])
 def test_dec_rollout_teacher_forcing_and_unconditioned(ops, T, B, D, H, n_pre, conditioned):
     """n_pre_poses > 1 feeds target frames for the first steps (:1049-1052, no feedback gradient there); conditioned ==
@@ -1978,6 +2069,9 @@ def test_dec_rollout_teacher_forcing_and_unconditioned(ops, T, B, D, H, n_pre, c
     k_or = keep95 if conditioned else torch.zeros_like(keep95)          # oracle: an all-zero mask IS the zeroed input
     h_leaf = h_init.clone().requires_grad_(True)
     y_ref, _ = _oracle_rollout(sd, target, h_leaf, k_or, None, 0.0, True, n_pre=n_pre)
+    for backward in (False, True):
+        assert _dec_route_now(T, B, D, H, backward) == {(32, 64): "PERSIST*1", (24, 200): "CLUSTER", (21, 64): "STEP_FAST",
+                                                        (24, 212): "SPLIT"}[(B, H)]
     gy = torch.randn(T, B, D, generator=g) / (T * B * D) * 100
     (g_h,) = torch.autograd.grad((y_ref * gy).sum(), [h_leaf])
     wt, _ = _dec_weight_tensors(sd, DEV)
