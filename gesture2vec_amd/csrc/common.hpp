@@ -739,12 +739,12 @@ static inline void launch_slab_reduce(const float* slab, int nsplit, int64_t n, 
 // Column sums of a [nblk][ncol] array of per-workgroup partials into LDS `out[ncol]`, by all 256 threads, in a fixed
 // order.  The partials were written by OTHER CUs in the previous launch, so every load is an L2 miss (~1500 cycles):
 // the point is to have (almost) all of a thread's loads in flight at once.  ncol % 4 == 0: float4 columns, up to
-// 8 row segments, 16 loads in flight per thread; else a scalar fallback.
+// 8 row segments, 16 loads in flight per thread; else (or with vec_ok false: `part` is not 16-byte aligned) a scalar fallback.
 // scratch: LDS, `scratch_floats` (>= 1024) floats: more of it = more row segments.  Ends with a __syncthreads(); out is valid for every thread afterwards.
 template <int NTHR = 256>
 __device__ __forceinline__ void reduce_partials(const float* __restrict__ part, int nblk, int ncol, float* out,
-                                                float* scratch, int tid, int scratch_floats = 1024) {
-  if ((ncol & 3) == 0 && ncol <= 1024) {
+                                                float* scratch, int tid, int scratch_floats = 1024, bool vec_ok = true) {
+  if (vec_ok && (ncol & 3) == 0 && ncol <= 1024) {
     const int nc4 = ncol >> 2;                       // float4 columns
     for (int c0 = 0; c0 < nc4; c0 += NTHR) {
       const int nc = min(NTHR, nc4 - c0);

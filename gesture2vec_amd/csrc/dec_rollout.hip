@@ -74,6 +74,8 @@ struct DecDims {
   int n_pre, conditioned, training, nblk;
   int wt;   // write-through (sc1) stores for the arrays only later kernels read (see st4 in common.hpp)
   int scratch;      // floats of reduce_partials scratch at the end of the kernel's LDS (1024, or 2048 where it fits)
+  int vec;          // every global array of the call is 16-byte aligned: rows may move as float4s / four keep flags as one word.
+                    // 0 (the plan sent an unaligned call here): element-wise accesses only, 4-byte alignment is all they need
 };
 static int dec_wt_stores() { return 1; }
 
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_fwd_kernel(const 
   const int nrows = min(16, B - b0);
   const int i = lane & 15, q = lane >> 4;
   const bool has_next = (t < T - 1);
-  const bool hvec = (H & 3) == 0;
+  const bool hvec = (H & 3) == 0 && dm.vec != 0;
   const int H4 = H >> 2;
 
   SPAN(2);
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_fwd_kernel(const 
     frag_load(f_hh1, pk.hh1, wave, 4, lane);
   }
   // keep flags of the Dropout(0.95) on y_t (dense epilogue below): requested now, consumed after the out_layer
-  const bool dense_e = (nrows == 16) && t > 0 && !(has_next && t < dm.n_pre) && ((((int64_t)t * B + b0) * D) & 3) == 0 &&
+  const bool dense_e = dm.vec != 0 && (nrows == 16) && t > 0 && !(has_next && t < dm.n_pre) && ((((int64_t)t * B + b0) * D) & 3) == 0 &&
                        ((16 * D) & 3) == 0 && (16 * D <= 2 * 16 * ldh) && dm.conditioned;
   constexpr int KPRE = FASTC ? (16 * DS / 4 + 255) / 256 : 1;
   uint32_t kpre[KPRE];
@@ -237,7 +239,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_fwd_kernel(const 
     if (dm.training) {
       const float* part = sv.bn_partial + (int64_t)((t - 1) & 1) * dm.nblk * 2 * H;
       if (early) reduce_partials_128_hook(part, dm.nblk, red, red_scratch, tid, early_products);
-      else reduce_partials<NTHR>(part, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch);
+      else reduce_partials<NTHR>(part, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch, dm.vec != 0);
       STAMP(2);
       for (int f = tid; f < H; f += NTHR) {
         const float s1 = red[f], s2 = red[H + f];
@@ -337,14 +339,14 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_fwd_kernel(const 
                  sv.h0 + ((int64_t)t * B + b0) * H,
                  sv.gates0 ? sv.gates0 + ((int64_t)(t - 1) * B + b0) * 4 * H : nullptr,
                  drop ? keep_l0 + ((int64_t)(t - 1) * B + b0) * H : nullptr, 1.0f / (1.0f - dm.p_drop),
-                 (drop && sv.x1) ? sv.x1 + ((int64_t)(t - 1) * B + b0) * H : nullptr, nrows, lane, wave, NW);
+                 (drop && sv.x1) ? sv.x1 + ((int64_t)(t - 1) * B + b0) * H : nullptr, nrows, lane, wave, NW, hvec);
     lds_barrier();
     STAMP(4);
     // ---- (d) GRU layer 1 ---------------------------------------------------------------------------
     gru_cell_fwd<KSH_T>(pk.ih1, pk.hh1, w.b_ih1, w.b_hh1, Xx1, Xh1, ldh, H, Hp, Xh1n,
                  sv.h1 + ((int64_t)t * B + b0) * H,
                  sv.gates1 ? sv.gates1 + ((int64_t)(t - 1) * B + b0) * 4 * H : nullptr, nullptr, 1.0f, nullptr, nrows,
-                 lane, wave, NW);
+                 lane, wave, NW, hvec);
     lds_barrier();
     STAMP(5);
     }
@@ -589,7 +591,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_bwd_kernel(g2v_de
   const int i = lane & 15, q = lane >> 4;
   const bool last = (t == T - 1);   // first kernel of the backward sweep
   const int nth = Hp >> 4, ntd = Dp >> 4;
-  const bool hvec = (H & 3) == 0;
+  const bool hvec = (H & 3) == 0 && dm.vec != 0;
   const int H4 = H >> 2;
 
   SPAN(0);
@@ -645,7 +647,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_bwd_kernel(g2v_de
   // ================= Part A: finish BatchNorm backward of step t+1 ===================================
   if (!last) {
     const float* part = gr.bn_bwd_partial + (int64_t)((t + 1) & 1) * dm.nblk * 2 * H;
-    reduce_partials<NTHR>(part, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch);
+    reduce_partials<NTHR>(part, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch, dm.vec != 0);
     STAMPB(1);
     for (int f = tid; f < H; f += NTHR) {
       const float s1 = red[f], s2 = red[H + f];
@@ -700,7 +702,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_bwd_kernel(g2v_de
 
   // ================= Part B: dy_t (loss + feedback) ===================================================
   // Same contiguity as in the forward: the block's 16 x D tile of dy / keep95 is one dense run in memory.
-  const bool dense_b = (nrows == 16) && ((((int64_t)t * B + b0) * D) & 3) == 0 && ((16 * D) & 3) == 0 && (16 * D <= 16 * ldg);
+  const bool dense_b = dm.vec != 0 && (nrows == 16) && ((((int64_t)t * B + b0) * D) & 3) == 0 && ((16 * D) & 3) == 0 && (16 * D <= 16 * ldg);
   if (dense_b) {
     const bool feedback = (!last) && dm.conditioned && (t >= dm.n_pre);
     float* Dt = Gi;                                        // dense dy tile [16*D]
@@ -825,7 +827,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_bwd_kernel(g2v_de
         gru_cell_bwd_tile(acc[0], carry1, 1.0f, nullptr, sv.gates1 + ((int64_t)(t - 1) * B + b0) * 4 * H,
                           sv.h1 + ((int64_t)(t - 1) * B + b0) * H, gr.dgi1 + ((int64_t)(t - 1) * B + b0) * G,
                           gr.dgh1 + ((int64_t)(t - 1) * B + b0) * G, Gi, Gh, ldg, Dd, ldh, H, ft, nrows, lane, dm.wt != 0,
-                          pf && ft == wave + NW * j, cin[j]);
+                          pf && ft == wave + NW * j, cin[j], 0, hvec);
       }
     }
   }
@@ -875,7 +877,7 @@ __global__ __launch_bounds__(HS > 0 ? 256 : 512) void dec_step_bwd_kernel(g2v_de
                           drop ? keep_l0 + ((int64_t)(t - 1) * B + b0) * H : nullptr,
                           sv.gates0 + ((int64_t)(t - 1) * B + b0) * 4 * H, sv.h0 + ((int64_t)(t - 1) * B + b0) * H,
                           gr.dgi0 + ((int64_t)(t - 1) * B + b0) * G, gr.dgh0 + ((int64_t)(t - 1) * B + b0) * G, Gi, Gh,
-                          ldg, Dd, ldh, H, ft, nrows, lane, dm.wt != 0, pf0 && ft == wave + NW * j, cin0[j]);
+                          ldg, Dd, ldh, H, ft, nrows, lane, dm.wt != 0, pf0 && ft == wave + NW * j, cin0[j], 0, hvec);
       }
     }
   }
@@ -2534,6 +2536,7 @@ struct DecRoutePlan {
   size_t xch_off, xch_bytes;      // its exchange records in the workspace (PERSIST, CLUSTER)
   size_t lds;                     // dynamic LDS bytes, threads and reduce_partials scratch floats of the route's step kernel
   int block, scratch, nblk;       // (STEP, STEP_FAST, SPLIT's step 0) or cluster kernel; nblk: 16-row tiles
+  bool vec;                       // the step kernels may move rows as 16-byte vectors: every array they touch that way is aligned
   int err; const char* msg;
 };
 static DecRoutePlan dec_route_plan(bool bwd, int T, int B, int D, int H, bool training, int level, int cus, const DecCallFacts& f) {
@@ -2541,6 +2544,7 @@ static DecRoutePlan dec_route_plan(bool bwd, int T, int B, int D, int H, bool tr
   auto refuse = [&pl](int err, const char* msg) { pl.route = 0; pl.err = err; pl.msg = msg; return pl; };
   if (T < 2 || B <= 0 || D <= 0 || H <= 0) return refuse(G2V_ERR_ARG, "bad size");
   pl.nblk = cdiv(B, 16);
+  pl.vec = f.persist_aligned && f.split_aligned;      // (between them the two lists name every array the step kernels touch as a vector)
   pl.lds = bwd ? dec_bwd_lds(D, H, &pl.scratch) : dec_fwd_lds(D, H, &pl.scratch);
   if (pl.lds > 160 * 1024) return refuse(G2V_ERR_UNSUPPORTED, "D/H too large for LDS");
   const bool fast = dec_prepared_shape(D, H);
@@ -2628,7 +2632,7 @@ static void dec_fwd_launch_steps(const DecFwdCall& c, const DecRoutePlan& pl, co
   const bool fast = dec_prepared_shape(c.D, c.H);
   auto* const kernel = !fast ? dec_step_fwd_kernel<0, 0> : dec_step_fwd_kernel<64, 135>;      // (same arguments)
   if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, c.training, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch};
+  const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, c.training, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch, pl.vec ? 1 : 0};
   for (int t = 0; t < t_end; ++t)
     hipLaunchKernelGGL(kernel, dim3(pl.nblk), dim3(pl.block), pl.lds, c.st, c.target, c.h_init, *c.w, ws.pk, *c.s, c.keep95, c.keep_l0, dm, t);
 }
@@ -2950,7 +2954,7 @@ static void dec_bwd_launch_steps(const DecBwdCall& c, const DecRoutePlan& pl, co
   const bool fast = dec_prepared_shape(c.D, c.H);
   auto* const kernel = !fast ? dec_step_bwd_kernel<0, 0> : dec_step_bwd_kernel<64, 135>;
   if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, 1, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch};
+  const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, 1, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch, pl.vec ? 1 : 0};
   for (int t = c.T - 1; t >= 0; --t)
     hipLaunchKernelGGL(kernel, dim3(pl.nblk), dim3(pl.block), pl.lds, c.st, *c.w, ws.tw, *c.s, *c.g, c.keep95, c.keep_l0, dm, t);
 }

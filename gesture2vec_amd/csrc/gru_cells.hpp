@@ -123,7 +123,8 @@ __device__ __forceinline__ void gru_cell_fwd_epilogue(const f32x4 (&ai)[3], cons
 // ---- one GRU cell for the feature tiles of this wave ------------------------------------------------
 // x-operand Xin [16][ldh] (layer input), Xh [16][ldh] (previous hidden).  Writes h_new (after optional
 // inter-layer dropout) to `Hnext_lds`, h_new to global h_out, and the gates.  When H % 4 == 0 every global /
-// LDS access of the epilogue is a 16-byte vector (4 consecutive features live in one lane).
+// LDS access of the epilogue is a 16-byte vector (4 consecutive features live in one lane); vec_ok false (a global
+// array of the call is not 16-byte aligned) takes the element-wise epilogue instead.
 template <int KSH_T>
 __device__ __forceinline__ void gru_cell_fwd(const float* __restrict__ p_ih, const float* __restrict__ p_hh,
                                              const float* __restrict__ b_ih, const float* __restrict__ b_hh,
@@ -133,10 +134,10 @@ __device__ __forceinline__ void gru_cell_fwd(const float* __restrict__ p_ih, con
                                              float* __restrict__ gates,   // global (B,4H) row block base or null
                                              const uint8_t* __restrict__ keep, float keep_scale,  // inter-layer dropout
                                              float* __restrict__ xdrop_out,  // global (B,H) dropped output or null
-                                             int nrows, int lane, int wave, int nwaves = 4) {
+                                             int nrows, int lane, int wave, int nwaves = 4, bool vec_ok = true) {
   const int i = lane & 15, q = lane >> 4;
   const int ntile = Hp >> 4, KS = Hp >> 4;
-  const bool hvec = (H & 3) == 0;
+  const bool hvec = vec_ok && (H & 3) == 0;
   for (int ft = wave; ft < ntile; ft += nwaves) {
     const int f0 = 16 * ft + 4 * q;
     const bool vec = hvec && (f0 + 3 < H);
@@ -195,7 +196,8 @@ __device__ __forceinline__ void gru_cell_fwd(const float* __restrict__ p_ih, con
 // GRU cell backward for one 16-feature tile of this wave.
 //   dh(row,f) = keep ? acc * extra_scale * keep : acc   (+ carry from the later time step)
 // writes dgi / dgh (global), Gi / Gh tiles (LDS, MFMA B operands for the next contractions) and
-// direct = dh * z into Dd (LDS).  H % 4 == 0: all accesses are 16-byte vectors.
+// direct = dh * z into Dd (LDS).  H % 4 == 0: all accesses are 16-byte vectors, unless vec_ok is false (a global array of the
+// call is not 16-byte aligned: element-wise).
 // what gru_cell_bwd_tile reads from memory for one lane (the 16-byte path), so that a caller can request it ahead of the
 // products / the barrier in front of the cell (one memory round trip per tile stood in front of every cell epilogue)
 struct CellBwdIn {
@@ -204,14 +206,14 @@ struct CellBwdIn {
 };
 __device__ __forceinline__ void cell_bwd_prefetch(CellBwdIn& in, const float* __restrict__ carry, const uint8_t* __restrict__ keep,
                                                   const float* __restrict__ gates, const float* __restrict__ hprev, int H, int ft,
-                                                  int nrows, int lane, int carry_ld = 0) {
+                                                  int nrows, int lane, int carry_ld = 0, bool vec_ok = true) {
   const int cld = carry_ld > 0 ? carry_ld : H;      // (the single-launch BPTT of t2e_rollout.hip keeps its carries in LDS)
   const int i = lane & 15, q = lane >> 4;
   const int f0 = 16 * ft + 4 * q;
   in.c4 = make_float4(0.f, 0.f, 0.f, 0.f);
   in.r4 = in.z4 = in.n4 = in.h4 = in.hp4 = in.c4;
   in.kp = 0x01010101u;
-  if (((H & 3) == 0) && f0 + 3 < H && i < nrows) {
+  if (vec_ok && ((H & 3) == 0) && f0 + 3 < H && i < nrows) {
     const float* go = gates + (int64_t)i * 4 * H + f0;
     in.r4 = *reinterpret_cast<const float4*>(go); in.z4 = *reinterpret_cast<const float4*>(go + H);
     in.n4 = *reinterpret_cast<const float4*>(go + 2 * H); in.h4 = *reinterpret_cast<const float4*>(go + 3 * H);
@@ -225,12 +227,12 @@ __device__ __forceinline__ void gru_cell_bwd_tile(const f32x4& acc, const float*
                                                   const float* __restrict__ gates, const float* __restrict__ hprev,
                                                   float* __restrict__ dgi, float* __restrict__ dgh, float* Gi, float* Gh,
                                                   int ldg, float* Dd, int ldh, int H, int ft, int nrows, int lane,
-                                                  bool wt, bool use_pre, const CellBwdIn& pre, int carry_ld = 0) {
+                                                  bool wt, bool use_pre, const CellBwdIn& pre, int carry_ld = 0, bool vec_ok = true) {
   const int cld = carry_ld > 0 ? carry_ld : H;
   const int i = lane & 15, q = lane >> 4;
   const int f0 = 16 * ft + 4 * q;
   const int G = 3 * H;
-  if (((H & 3) == 0) && f0 + 3 < H) {
+  if (vec_ok && ((H & 3) == 0) && f0 + 3 < H) {
     float g_r[4] = {0.f, 0.f, 0.f, 0.f}, g_z[4] = {0.f, 0.f, 0.f, 0.f}, g_n[4] = {0.f, 0.f, 0.f, 0.f},
           g_hn[4] = {0.f, 0.f, 0.f, 0.f}, direct[4] = {0.f, 0.f, 0.f, 0.f};
     if (i < nrows) {

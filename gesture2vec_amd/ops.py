@@ -681,6 +681,13 @@ def dec_rollout_bwd(wstruct, saved: dict, grads: dict, keep95, keep_l0, p_drop, 
                                   _stream()), "dec_rollout_bwd")
 
 
+def bn_running_update(bn_stats, running_mean, running_var, steps, H, B):
+    """Deferred commit of BatchNorm's running statistics from the bn_stats (steps,2,H) of a TRAINING rollout that was given
+    bn_running_mean = bn_running_var = NULL; a no-op on the device while the persistent kernels' fault latch is set (include/g2v.h)."""
+    check(_lib_().g2v_bn_running_update(_p(_chk(bn_stats)), _p(_chk(running_mean)), _p(_chk(running_var)), int(steps), int(H), int(B),
+                                        _stream()), "bn_running_update")
+
+
 # ------------------------------------------------------------------------------------------ Part d: fused code-decoder rollout
 def code_rollout_ok(S1, B, H, K, Tw, att) -> bool:
     return bool(_lib_().g2v_attn_code_rollout_ok(int(S1), int(B), int(H), int(K), int(Tw), int(bool(att))))
