@@ -650,6 +650,28 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// philox4x32-10, the project's one random stream: block g of the stream (seed, off) = four 32-bit words, counter (g, off), key =
+// seed.  g2v_keep_mask turns a block into four keep flags (misc.hip), g2v_vae_latent_fwd into four normal deviates.
+__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+  const uint32_t n1 = (uint32_t)p1;
+  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+  const uint32_t n3 = (uint32_t)p0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+__device__ __forceinline__ void philox4x32(int64_t g, uint64_t off, uint64_t seed, uint32_t (&c)[4]) {
+  c[0] = (uint32_t)g; c[1] = (uint32_t)((uint64_t)g >> 32); c[2] = (uint32_t)off; c[3] = (uint32_t)(off >> 32);
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
 // torch.argmin semantics (the reference's :1259): lowest index among equal minima; a NaN distance counts as smaller than every
 // number and the FIRST NaN wins.  A candidate therefore beats the incumbent when it is smaller, or when it is NaN and the
 // incumbent is not; on a tie (equal values, or both NaN) the lower index stays.  No sentinel index ever leaves a kernel:

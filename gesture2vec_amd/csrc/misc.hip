@@ -338,28 +338,12 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, c
 }
 
 // ---- philox4x32-10 keep masks ------------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  const uint32_t n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
 // One philox block = 4 consecutive outputs (block g <-> elements 4g .. 4g+3, counter (g, offset), key = seed): the mapping every
 // version of this kernel has had.  A thread takes FOUR consecutive blocks and stores its 16 flags with one 16-byte store (the
 // first version stored them byte by byte: 84 us for the 18 M flags of a B = 4096 step, store-issue bound; the arithmetic is ~10 us).
 __device__ __forceinline__ uint32_t philox_keep4(int64_t g, uint64_t off, uint64_t seed, float keep_prob) {
-  uint32_t c[4] = {(uint32_t)g, (uint32_t)((uint64_t)g >> 32), (uint32_t)off, (uint32_t)(off >> 32)};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
+  uint32_t c[4];
+  philox4x32(g, off, seed, c);
   uint32_t w = 0u;
 #pragma unroll
   for (int j = 0; j < 4; ++j) w |= (((float)(c[j] >> 8) * (1.0f / 16777216.0f) < keep_prob) ? 1u : 0u) << (8 * j);

@@ -11,9 +11,11 @@ reference, but every tensor op is one of the HIP kernels behind include/g2v.h.  
     train step can be captured into a hipGraph);
   * explicit dropout keep-masks (drawn by the Philox kernel, or supplied by the caller for parity tests).
 
-Scope: autoencoder_vae == "False", autoencoder_att == "False", n_layers == 2 (every shipped Part-b config), with a quantiser
+Scope: autoencoder_att == "False", n_layers == 2 (every shipped Part-b config), with a quantiser
 (autoencoder_vq == "True") or without one (quantizer="none", autoencoder_vq == "False": config/seq2seq.yml; the rollout then
-starts from the encoder's final states in place).  With attention off the decoder only consumes encoder_hidden[:2] = the layer-0
+starts from the encoder's final states in place).  autoencoder_vae == "True" (latent="vae"): the engine owns the variational
+block's six tensors and serves its encoder / decoder STAGES (forward_encoder, forward_decoder and their backwards); the block
+itself runs between them at module level, and the fused forward / backward / train_step refuse.  With attention off the decoder only consumes encoder_hidden[:2] = the layer-0
 forward/backward final states (:971-973), so encoder GRU layer 1 is never evaluated: its outputs reach nothing and
 its gradients are exactly zero in the reference [SURVEY.md §0]; its weights stay in the state_dict untouched.
 """
@@ -62,6 +64,20 @@ def quantizer_layout(quantizer: str, E: int, K: int):
     raise ValueError(f"unknown quantizer {quantizer!r}")
 
 
+LATENT_VAE_PARAMS = ("VAE_fc_mean.weight", "VAE_fc_mean.bias", "VAE_fc_std.weight", "VAE_fc_std.bias",
+                     "VAE_fc_decoder.weight", "VAE_fc_decoder.bias")
+
+
+def latent_layout(kind: str, E: int):
+    """trainable tensors of the block between the encoder state (or the quantiser) and the decoder's initial state.  "vae"
+    (autoencoder_vae == "True", :776-789): three nn.Linear(E, E); "none": the state goes to the decoder as it is."""
+    if kind == "none":
+        return []
+    if kind == "vae":
+        return list(zip(LATENT_VAE_PARAMS, ((E, E), (E,)) * 3))
+    raise ValueError(f"unknown latent block {kind!r}")
+
+
 def trainable_layout(D: int, H: int, L: int):
     """(name, shape) of every tensor that receives a gradient in the reference's step, in flat-buffer order."""
     out = [("encoder.in_layer.weight", (H, D)), ("encoder.in_layer.bias", (H,))]
@@ -86,7 +102,7 @@ def trainable_layout(D: int, H: int, L: int):
 class VQVAEEngine:
     def __init__(self, D: int, H: int, L: int, K: int, T: int, *, beta: float, dropout_prob: float,
                  n_pre_poses: int = 1, conditioned: bool = True, decay: float = 0.85, eps: float = 1e-5,
-                 device="cuda:0", seed: int = 0, quantizer: str = "ema"):
+                 device="cuda:0", seed: int = 0, quantizer: str = "ema", latent: str = "none"):
         if L != 2:
             raise NotImplementedError("the gfx950 rollout kernels implement n_layers == 2 (every shipped config)")
         self.lib = _lib.load()
@@ -120,7 +136,11 @@ class VQVAEEngine:
         # VQ_Payam_GSSoft module (model/Autoencoder_VQVAE_model.py); its trainable tensors live at the END of the same flat
         # buffer so that clip_grad_norm_ + Adam stay one fused launch over everything.
         self.quantizer = quantizer
-        self.layout = trainable_layout(D, H, L) + quantizer_layout(quantizer, H * L, K)
+        # "vae": the variational block's three layers at the very END of the flat buffer (every other configuration's layout,
+        # offsets and comm buffer are what they were); its stages run at module level (Autoencoder_VQVAE._forward_staged) around
+        # forward_encoder / forward_decoder, which then exchange the state through buffers['quant'] / ['gz'] as with a quantiser
+        self.latent = latent
+        self.layout = trainable_layout(D, H, L) + quantizer_layout(quantizer, H * L, K) + latent_layout(latent, H * L)
         self.offsets: Dict[str, tuple] = {}
         off = 0
         for name, shp in self.layout:
@@ -131,7 +151,9 @@ class VQVAEEngine:
             off += (n + 3) // 4 * 4          # keep every tensor 16-byte aligned inside the flat buffer
         self.n_flat = off
         q_names = [n for n, _ in quantizer_layout(quantizer, H * L, K)]
-        self.q_off = self.offsets[q_names[0]][0] if q_names else off        # start of the quantiser's slice
+        l_names = [n for n, _ in latent_layout(latent, H * L)]
+        self.q_end = self.offsets[l_names[0]][0] if l_names else off        # end of the quantiser's slice = start of the latent block's
+        self.q_off = self.offsets[q_names[0]][0] if q_names else self.q_end  # start of the quantiser's slice
         dev = self.device
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         # ONE communication buffer [flat grads | cnt (K) | dw (K*E)]: a single RCCL all-reduce per step under DP
@@ -435,6 +457,8 @@ class VQVAEEngine:
         if vq:
             b.update({"flat": z(B, E), "idx": torch.zeros(B, dtype=torch.int64, device=dev), "quant": z(2, B, H),
                       "sse": z(self.lib.g2v_vq_assign_blocks(B)), "gz": z(2, B, H)})
+        elif self.latent != "none":            # the latent block stands where the quantiser would: same hand-over buffers
+            b.update({"quant": z(2, B, H), "gz": z(2, B, H)})
         sv = DecSaved()
         sv.y, sv.xin, sv.u, sv.a = _p(b["y"]), _p(b["dec_xin"]), _p(b["u"]), _p(b["a"])
         sv.h0, sv.h1, sv.x1 = _p(b["h0"]), _p(b["h1"]), _p(b["x1"])
@@ -553,6 +577,7 @@ class VQVAEEngine:
                 n_global: Optional[int] = None, derived_ready: bool = False, loss_w=None, join_stats: bool = True):
         """Autoencoder_VQVAE.forward.  in_poses/out_poses (B,T,D) contiguous fp32 on the GPU.
         Fills buffers: y (T,B,D), quant (2,B,H) first hidden, idx, vq_scalars (loss_vq, perplexity)."""
+        self._no_latent_block("forward")
         if self.quantizer == "gssoft":
             return self._forward_gssoft(in_poses, out_poses, training, loss_w)
         if self.quantizer == "none":
@@ -622,6 +647,12 @@ class VQVAEEngine:
         if join_stats or chase:             # (the backward rollout reads what the chaser writes)
             self._join(1)
         return b
+
+    def _no_latent_block(self, what: str):
+        if self.latent != "none":
+            raise NotImplementedError(f"VQVAEEngine.{what}: the fused sequence does not contain the variational block "
+                                      "(autoencoder_vae == 'True'); such a net runs its stages through "
+                                      "Autoencoder_VQVAE.forward (forward_encoder -> block -> forward_decoder)")
 
     def _vq_bx_selfcheck(self, b, N):
         """Debug switch vq_bx_check_every = n (round-3 verdict: the screening's exactness rests on a hand-budgeted error radius, and
@@ -750,7 +781,7 @@ class VQVAEEngine:
         if self._xch_pre and training:
             ws = b["ws_decf"]                  # its exchange records were cleared on branch 0 (side())
         fold = b["loss_folded"] = bool(training and chase)
-        h_init = b["enc_hidden"] if self.quantizer == "none" else b["quant"]
+        h_init = b["enc_hidden"] if (self.quantizer == "none" and self.latent == "none") else b["quant"]
         check(fn(_p(out_poses), _p(h_init), C.byref(self.dec_wstruct()),
                  C.byref((b["sv_loss"] if fold else b["sv"]) if training else b["sv_eval"]), _p(b["keep95"]),
                  _p(b["keep_l0"]) if drop_in else None, self.p, self.n_pre,
@@ -802,6 +833,7 @@ class VQVAEEngine:
     def backward(self, in_poses: torch.Tensor, B: int, g_loss_vq: Optional[torch.Tensor] = None):
         """Backward of forward(training=True): expects buffers['dy'] = dLoss/d y (T,B,D).  Writes every parameter
         gradient into the flat grad buffer (overwrite, not accumulate)."""
+        self._no_latent_block("backward")
         if self.quantizer == "gssoft":
             return self._backward_gssoft(in_poses, B)
         H, E = self.H, self.E
@@ -1080,7 +1112,7 @@ class VQVAEEngine:
         dirs = (_lib.GruDirBwd * 2)()
         for k, (suf, key, hs_ptr) in enumerate((("", "f", b["hs_f"][1:].data_ptr()), ("_reverse", "b", b["hs_b"].data_ptr()))):
             dirs[k].d_hs = None
-            d_hn = b["gz"] if (quant_bwd is None and self.quantizer != "none") else b["dh_init"]
+            d_hn = b["gz"] if (quant_bwd is None and (self.quantizer != "none" or self.latent != "none")) else b["dh_init"]
             dirs[k].d_hn = d_hn[k].data_ptr()
             if quant_bwd is not None:
                 dirs[k].hn_z, dirs[k].hn_q = b["enc_hidden"][k].data_ptr(), b["quant"][k].data_ptr()
@@ -1247,6 +1279,7 @@ class VQVAEEngine:
                          epoch: int = 1, draw_masks: bool = True, dp: bool = False):
         """masks -> forward -> loss -> backward; leaves comm = [grads | cnt | dw] holding this rank's contribution ([grads] without
         a quantiser; the fault flag slot follows under dp)."""
+        self._no_latent_block("train_step")
         B = x.shape[0]
         self._branches_on = self._branches_ok(B)
         self._prepared = self._branches_on and (self.overlap & 9) == 9

@@ -15,9 +15,10 @@ Differences from the reference, all deliberate:
   * Dropout masks come from a counter-based Philox kernel (or are supplied explicitly, `set_dropout_masks`),
     because CPU and GPU RNG streams cannot agree anyway.
   * GPU only: `.forward` raises if the module is not on an MI355X (no CPU path).
-Supported configuration: autoencoder_vq "True" and "False" (no quantiser: config/seq2seq.yml), autoencoder_vae "False",
+Supported configuration: autoencoder_vq "True" and "False" (no quantiser: config/seq2seq.yml), autoencoder_vae "False" and
+"True" (the variational block between the encoder state / the quantiser and the decoder: csrc/vae_latent.hip, staged path),
 n_layers 2; autoencoder_att "False" (fused engine + rollout kernels) and "True" (module-level path: step-level decoder with
-Bahdanau attention).
+Bahdanau attention; not together with autoencoder_vae).
 """
 from __future__ import annotations
 
@@ -355,7 +356,10 @@ class Autoencoder_VQVAE(nn.Module):
     """Chunk autoencoder: EncoderRNN -> VQ_Payam_EMA on encoder_hidden[:L] -> T-1 autoregressive decode steps
     (reference :686-1085).  forward(in_poses, out_poses, vq_layer_active) ->
     (outputs (B,T,D), decoder_first_hidden (L,B,H), loss_vq, perplexity_vq); with autoencoder_vq "False" there is no vq_layer
-    and forward returns (outputs, decoder_first_hidden = encoder_hidden[:L])."""
+    and forward returns (outputs, decoder_first_hidden = encoder_hidden[:L]).
+    autoencoder_vae "True" (:776-789, 989-1010): VAE_fc_mean / VAE_fc_std / VAE_fc_decoder (E -> E) stand between the quantiser
+    (or the encoder state) and the decoder; forward returns (outputs, decoder_first_hidden, mean, logvar[, loss_vq, perplexity_vq])
+    and leaves the KL term of that forward in `self.latent_kl` (train_iter adds it, train_seq2seq.py:710-729)."""
 
     def __init__(self, args, pose_dim: int, n_frames: int):
         super().__init__()
@@ -366,9 +370,25 @@ class Autoencoder_VQVAE(nn.Module):
         self.out_layer_encoder = nn.Sequential(nn.Linear(args.hidden_size, args.hidden_size), nn.Tanh())
         self.out_layer_decoder = nn.Sequential(nn.Linear(args.hidden_size, pose_dim))
         self.decoder = Generator(args, pose_dim, speaker_model=None)
-        if args.autoencoder_vae == "True":
-            raise NotImplementedError("autoencoder_vae == 'True' is outside the accelerated hot path")
-        self.VAE = False
+        self.VAE = args.autoencoder_vae == "True"
+        if self.VAE:                                                                       # :776-789
+            if args.autoencoder_att == "True":
+                raise NotImplementedError("autoencoder_vae == 'True' together with autoencoder_att == 'True' is out of scope: the "
+                                          "variational block runs on the attention-free staged path only")
+            # The KL term enters the loss as KLD * 0.1 * epoch / args.epochs (train_seq2seq.py:729): a variational net is described
+            # by args that carry the schedule's length, as every config parse_args reads and every checkpoint's Namespace do.  A
+            # bare Namespace without it is not a configuration this mode is implemented for (and epochs < 1 would divide by zero).
+            epochs = getattr(args, "epochs", None)
+            if not isinstance(epochs, int) or isinstance(epochs, bool) or epochs < 1:
+                raise NotImplementedError("autoencoder_vae == 'True' is implemented for args that carry the reference's `epochs` "
+                                          f"(a positive int: the KL weight is 0.1 * epoch / epochs), got {epochs!r}")
+            self.kl_epochs = epochs
+            E = args.n_layers * args.hidden_size          # (a width g2v_vae_latent_ok rejects fails in forward, by the library's error)
+            self.VAE_fc_mean = nn.Linear(E, E)
+            self.VAE_fc_std = nn.Linear(E, E)
+            self.VAE_fc_decoder = nn.Linear(E, E)
+        self._latent_eps = None        # explicit noise for the next forward (set_latent_noise)
+        self.latent_kl = None          # 0.5 mean(exp(logvar) - logvar - 1 + mean^2) of the latest forward (variational nets)
         self.vq = args.autoencoder_vq == "True"
         # The reference builds VQ_Payam_EMA (:801-807) and then overwrites it with VQ_Payam_GSSoft (:816-820).  The EMA
         # quantiser is the north star and the fused engine path; `args.autoencoder_vq_quantizer = "gssoft"` (not a
@@ -428,7 +448,7 @@ class Autoencoder_VQVAE(nn.Module):
             eng = VQVAEEngine(self.pose_dim, self.hidden_size, self.n_layers, self.vq_components if self.vq else 0, self.n_frames,
                               beta=self.commitment_cost if self.vq else 0.0, dropout_prob=self.dropout_prob, n_pre_poses=self.n_pre_poses,
                               conditioned=self.autoencoder_conditioned, device=dev, seed=self.rng_seed,
-                              quantizer=self.quantizer)
+                              quantizer=self.quantizer, latent="vae" if self.VAE else "none")
             self._engine = eng
             if getattr(self.decoder.decoder, "autoencoder_fixed_weight", False):
                 eng.frozen = ["decoder.decoder.gru." + n for n, _ in self.decoder.decoder.gru.named_parameters()]
@@ -473,6 +493,34 @@ class Autoencoder_VQVAE(nn.Module):
 
     def use_random_masks(self):
         self._explicit_masks = False
+
+    # ------------------------------------------------------------------ variational block
+    def reparameterize(self, mu: torch.Tensor, logVar: torch.Tensor, train: bool = True) -> torch.Tensor:
+        """mu + exp(logVar / 2) * eps (train) or mu (reference :879-899).  A utility for callers: forward itself forms z inside
+        g2v_vae_latent_fwd.  eps comes from torch's generator here, as in the reference."""
+        if not train:
+            return mu
+        return mu + torch.exp(logVar / 2) * torch.randn_like(logVar)
+
+    def kl_weight(self, epoch: int, epochs: Optional[int] = None) -> float:
+        """the weight KLD enters the iteration's loss with: 0 at epoch 0, else 0.1 * epoch / epochs (train_seq2seq.py:727-729)"""
+        return 0.1 * epoch / (self.kl_epochs if epochs is None else epochs) if epoch > 0 else 0.0
+
+    def set_latent_noise(self, eps: Optional[torch.Tensor]):
+        """Explicit eps (B,E) for the NEXT forward of a variational net (parity tests), like set_dropout_masks; None: back to
+        the Philox stream."""
+        if not self.VAE:
+            raise RuntimeError("set_latent_noise: the net has no variational block (autoencoder_vae != 'True')")
+        self._latent_eps = None if eps is None else eps.to(torch.float32).contiguous()
+
+    def latent_code(self, hidden: torch.Tensor) -> torch.Tensor:
+        """The extractors' latent row of a variational net (data_preprocessor.get_pose_latent, Clustering, inference_Autoencoder):
+        VAE_fc_decoder(reparameterize(mean, logvar, train=False)) = VAE_fc_decoder(VAE_fc_mean(hf)), hidden (L,B,H) -> (B,E)."""
+        with torch.no_grad():
+            o = ops.vae_latent_fwd(hidden.contiguous(), self.VAE_fc_mean.weight.data, self.VAE_fc_mean.bias.data,
+                                   self.VAE_fc_std.weight.data, self.VAE_fc_std.bias.data, self.VAE_fc_decoder.weight.data,
+                                   self.VAE_fc_decoder.bias.data, sample=False, want_hf=False)
+            return o["d"].transpose(0, 1).reshape(hidden.shape[1], -1)
 
     # ------------------------------------------------------------------ attention model (module-level path)
     def set_attention_masks(self, keep_in, keep_enc_inter, keep95_list, keep_l0_list=None):
@@ -536,6 +584,12 @@ class Autoencoder_VQVAE(nn.Module):
         B = in_poses.shape[0]
         if not self._explicit_masks:
             eng.draw_masks(B, self.training)
+        if self.VAE:
+            y, first_hidden, mean, logvar, loss_vq, perp = self._forward_staged(eng, in_poses, out_poses)
+            if self.training:
+                self.decoder.decoder.pre_linear[1].num_batches_tracked += self.n_frames - 1   # one BN call per decode step
+            head = (y.transpose(0, 1), first_hidden[: self.n_layers], mean, logvar)
+            return head + (loss_vq, perp) if self.vq else head                               # :1056-1080
         if not self.vq:
             if self.training and torch.is_grad_enabled():
                 y, first_hidden = _PlainAEFn.apply(self.encoder.in_layer.weight, self, in_poses, out_poses)
@@ -563,17 +617,47 @@ class Autoencoder_VQVAE(nn.Module):
         slice is cleared here; everything else is overwritten by the stage backwards."""
         B = in_poses.shape[0]
         if self.training and torch.is_grad_enabled():
-            eng.gflat[eng.q_off:eng.n_flat].zero_()
+            # (the quantiser's slice only: the variational block's gradients behind it are written, not accumulated)
+            eng.gflat[eng.q_off:eng.q_end].zero_()
             hidden = _EncFn.apply(self.encoder.in_layer.weight, self, in_poses)
-            loss_vq, quantized, perp, _ = self.vq_layer(hidden)
-            y = _DecFn.apply(quantized, self, out_poses)
-            return y, quantized, loss_vq, perp
+            loss_vq = perp = None
+            if self.vq:
+                loss_vq, hidden, perp, _ = self.vq_layer(hidden)
+            if not self.VAE:
+                y = _DecFn.apply(hidden, self, out_poses)
+                return y, hidden, loss_vq, perp
+            # the quantiser runs BEFORE the variational block (:976-978, 989); the block draws noise in eval mode too (:1003)
+            first_hidden, mean, logvar, self.latent_kl = _VAELatentFn.apply(hidden, self, self._take_latent_noise())
+            y = _DecFn.apply(first_hidden, self, out_poses)
+            return y, first_hidden, mean, logvar, loss_vq, perp
         with torch.no_grad():
             b = eng.forward_encoder(in_poses, self.training)
-            loss_vq, quantized, perp, _ = self.vq_layer(b["enc_hidden"])
-            b["quant"].copy_(quantized.reshape(b["quant"].shape))
+            hidden, loss_vq, perp = b["enc_hidden"], None, None
+            if self.vq:
+                loss_vq, hidden, perp, _ = self.vq_layer(hidden)
+            if self.VAE:
+                o = self._latent_forward(hidden.contiguous().view(b["enc_hidden"].shape), self._take_latent_noise())
+                self.latent_kl = o["kl"][0]
+                hidden = o["d"]
+            b["quant"].copy_(hidden.reshape(b["quant"].shape))
             eng.forward_decoder(out_poses, B, self.training)
-            return b["y"].clone(), quantized.clone(), loss_vq, perp
+            if self.VAE:
+                return b["y"].clone(), hidden, o["mean"], o["logvar"], loss_vq, perp
+            return b["y"].clone(), hidden.clone(), loss_vq, perp
+
+    def _take_latent_noise(self):
+        eps, self._latent_eps = self._latent_eps, None
+        return eps
+
+    def _latent_forward(self, hidden, eps):
+        """g2v_vae_latent_fwd on hidden (L,B,H) with this net's three layers: explicit eps, or the engine's Philox stream"""
+        eng = self._engine
+        if eps is not None and tuple(eps.shape) != (hidden.shape[1], hidden.shape[0] * hidden.shape[2]):
+            raise ValueError(f"set_latent_noise: eps must be (B, E) = {(hidden.shape[1], hidden.shape[0] * hidden.shape[2])}, "
+                             f"got {tuple(eps.shape)}")
+        return ops.vae_latent_fwd(hidden, self.VAE_fc_mean.weight.data, self.VAE_fc_mean.bias.data, self.VAE_fc_std.weight.data,
+                                  self.VAE_fc_std.bias.data, self.VAE_fc_decoder.weight.data, self.VAE_fc_decoder.bias.data,
+                                  eps=eps, seed=eng.seed + 2, offset_counter=eng.rng_counter, sample=True)
 
 
 def _rebind_grads(net, eng):
@@ -638,6 +722,40 @@ class _DecFn(torch.autograd.Function):
             b["dy"].copy_(gy)
         eng.backward_decoder(B)
         return b["dh_init"].clone().reshape(ctx.hshape), None, None
+
+
+class _VAELatentFn(torch.autograd.Function):
+    """hidden (L,B,H) -> (decoder_first_hidden (L,B,H), mean (B,E), logvar (B,E), kl ()) through g2v_vae_latent_fwd / _bwd.  The
+    backward WRITES the six weight / bias gradients into the engine's flat grad buffer (the planned weight-gradient route:
+    dW_mean and dW_std share the operand hf and go as one batch; dW_dec = g_d^T z as one batch of its L row blocks, which are
+    contiguous in the (L,B,H) layout of g_d) and returns the gradient of `hidden`."""
+
+    @staticmethod
+    def forward(ctx, hidden, net, eps):
+        o = net._latent_forward(hidden.contiguous(), eps)
+        ctx.net = net
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(o["mean"], o["logvar"], o["eps"], o["z"], o["hf"])
+        return o["d"], o["mean"], o["logvar"], o["kl"][0]
+
+    @staticmethod
+    def backward(ctx, g_d, g_mean, g_logvar, g_kl):
+        net = ctx.net
+        eng = net._engine
+        mean, logvar, eps, z, hf = ctx.saved_tensors
+        B, E = mean.shape
+        L, H = net.n_layers, net.hidden_size
+        g_d = g_d.contiguous() if g_d is not None else torch.zeros((L, B, H), dtype=torch.float32, device=mean.device)
+        cont = lambda g: g.contiguous() if g is not None else None
+        dh, dmean, dlogvar = ops.vae_latent_bwd(g_d, g_kl.reshape(1).contiguous() if g_kl is not None else None, mean, logvar, eps,
+                                                net.VAE_fc_mean.weight.data, net.VAE_fc_std.weight.data,
+                                                net.VAE_fc_decoder.weight.data, g_mean=cont(g_mean), g_logvar=cont(g_logvar))
+        g = lambda name: eng.view(name, True)
+        ops.linear_bwd_weight_batch([(dmean, hf, g("VAE_fc_mean.weight"), g("VAE_fc_mean.bias")),
+                                     (dlogvar, hf, g("VAE_fc_std.weight"), g("VAE_fc_std.bias"))], E, E, M=B)
+        gw, gb = g("VAE_fc_decoder.weight"), g("VAE_fc_decoder.bias")
+        ops.linear_bwd_weight_batch([(g_d[l], z, gw[l * H:(l + 1) * H], gb[l * H:(l + 1) * H]) for l in range(L)], H, E, M=B)
+        return dh, None, None
 
 
 class _VQVAEFn(torch.autograd.Function):

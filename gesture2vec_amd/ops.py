@@ -1078,6 +1078,49 @@ def vq_soft_fused_bwd(dh, g_loss, x, fwd, w_mean, w_logvar, codebook, beta):
     return gz, dd, dlv, dflat
 
 
+def vae_latent_ok(B, E) -> bool:
+    return bool(_lib_().g2v_vae_latent_ok(B, E))
+
+
+def vae_latent_fwd(h, w_mean, b_mean, w_std, b_std, w_dec=None, b_dec=None, *, eps=None, seed=0, offset_counter=None,
+                   sample=True, want_hf=True):
+    """The variational block's forward (csrc/vae_latent.hip) on h (L,B,H): returns a dict mean, logvar, z (B,E), eps (B,E: the
+    noise used -- `eps` itself when given, the drawn one otherwise; None with sample=False), hf (B,E) or None, d (L,B,H) or None
+    (no w_dec), kl (1,).  Noise is drawn from the Philox stream (seed, offset_counter: device int64, advanced by 1) unless `eps`
+    is given; sample=False gives z = mean."""
+    lib = _lib_()
+    L, B, H = h.shape
+    E = L * H
+    dev = h.device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    draw = bool(sample) and eps is None
+    o = {"mean": f(B, E), "logvar": f(B, E), "z": f(B, E), "eps": (f(B, E) if draw else eps) if sample else None,
+         "hf": f(B, E) if want_hf else None, "d": f(L, B, H) if w_dec is not None else None, "kl": f(1)}
+    ws = f(max(int(lib.g2v_vae_latent_fwd_workspace(B, E)) // 4, 4))
+    check(lib.g2v_vae_latent_fwd(_p(_chk(h, name="h")), _p(_chk(w_mean, name="w_mean")), _p(_chk(b_mean, name="b_mean")),
+                                 _p(_chk(w_std, name="w_std")), _p(_chk(b_std, name="b_std")),
+                                 _p(_chk(w_dec, name="w_dec")) if w_dec is not None else None,
+                                 _p(_chk(b_dec, name="b_dec")) if b_dec is not None else None,
+                                 _p(_chk(eps, name="eps")) if eps is not None else None, int(seed), _p(offset_counter), int(bool(sample)),
+                                 _p(o["mean"]), _p(o["logvar"]), _p(o["z"]), _p(o["eps"]) if draw else None, _p(o["hf"]), _p(o["d"]),
+                                 _p(o["kl"]), _p(ws), ws.numel() * 4, B, L, H, _stream()), "vae_latent_fwd")
+    return o
+
+
+def vae_latent_bwd(g_d, g_kl, mean, logvar, eps, w_mean, w_std, w_dec, g_mean=None, g_logvar=None):
+    """Backward of vae_latent_fwd: g_d (L,B,H) = d loss / d d, g_kl = device scalar d loss / d kl or None (0), eps None when the
+    forward did not sample, g_mean / g_logvar (B,E) = gradients reaching mean / logvar directly or None
+    -> (dh (L,B,H), dmean (B,E), dlogvar (B,E))."""
+    L, B, H = g_d.shape
+    dh = torch.empty_like(g_d)
+    dmean, dlogvar = torch.empty_like(mean), torch.empty_like(mean)
+    check(_lib_().g2v_vae_latent_bwd(_p(_chk(g_d, name="g_d")), _p(g_kl), _p(_chk(g_mean)) if g_mean is not None else None,
+                                     _p(_chk(g_logvar)) if g_logvar is not None else None, _p(_chk(mean)), _p(_chk(logvar)),
+                                     _p(_chk(eps, name="eps")) if eps is not None else None, _p(_chk(w_mean)), _p(_chk(w_std)),
+                                     _p(_chk(w_dec)), _p(dmean), _p(dlogvar), _p(dh), B, L, H, _stream()), "vae_latent_bwd")
+    return dh, dmean, dlogvar
+
+
 def rowscale_combine(a, v, t):
     """out[r,c] = 2 a[r,c] v[r] - 2 t[r,c]"""
     rows, cols = a.shape

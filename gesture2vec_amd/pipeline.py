@@ -25,10 +25,14 @@ def _need_cuda(t: torch.Tensor, what: str) -> None:
 @torch.no_grad()
 def chunk_latents(net, chunks: torch.Tensor) -> torch.Tensor:
     """(N,T,D) pose chunks -> (N, L*H) latent rows, row n = [h_l0_fwd(n) ; h_l0_bwd(n)] = encoder_hidden[:L] of chunk n
-    laid out per chunk (the reference runs the encoder with batch 1, where `view(-1, E)` is exactly this concat)."""
+    laid out per chunk (the reference runs the encoder with batch 1, where `view(-1, E)` is exactly this concat).
+    A variational net (autoencoder_vae == "True"): VAE_fc_decoder(VAE_fc_mean(row n)), the reference extractors'
+    reparameterize(mean, logvar, train=False) (data_preprocessor.get_pose_latent, Clustering, inference_Autoencoder)."""
     _need_cuda(chunks, "chunk_latents")
     L = net.encoder.n_layers
     _, hidden = net.encoder(chunks.transpose(0, 1).contiguous(), None)        # (2L,N,H)
+    if getattr(net, "VAE", False):
+        return net.latent_code(hidden[:L]).contiguous()                         # g2v_vae_latent_fwd, sample = 0
     return hidden[:L].transpose(0, 1).reshape(chunks.shape[0], -1).contiguous()  # layout only
 
 
@@ -54,9 +58,7 @@ def stacked_autoencode(dae, net, poses: torch.Tensor):
     _need_cuda(poses, "stacked_autoencode")
     B, T, D = poses.shape
     lat = dae.encode(poses.reshape(B * T, D).contiguous()).view(B, T, -1) if dae.encoder is not None else poses
-    if getattr(net, "vq", True):
-        out, _, _, perplexity = net(lat, lat)
-    else:
-        (out, _), perplexity = net(lat, lat), None
+    res = net(lat, lat)         # (outputs, first_hidden[, mean, logvar][, loss_vq, perplexity]): autoencoder_vae / autoencoder_vq
+    out, perplexity = res[0], (res[-1] if getattr(net, "vq", True) else None)
     rec = dae.decode(out.reshape(B * T, -1).contiguous()).view(B, T, D) if dae.decoder is not None else out
     return rec, out, perplexity

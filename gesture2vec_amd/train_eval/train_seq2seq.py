@@ -75,8 +75,11 @@ class FusedClipAdam:
 def train_iter_Autoencoder_VQ_seq2seq(args, epoch: int, input_poses: torch.Tensor, target_poses: torch.Tensor,
                                       net: torch.nn.Module, optim) -> Tuple[dict, torch.Tensor]:
     """One training iteration of the chunk VQ-VAE; same signature / return value as the reference: ({"loss": float}, perplexity),
-    and without a quantiser (autoencoder_vq == "False", :702-703, 757-758) {"loss": custom_loss} alone."""
+    and without a quantiser (autoencoder_vq == "False", :702-703, 757-758) {"loss": custom_loss} alone.
+    A variational net (autoencoder_vae == "True") adds KLD * 0.1 * epoch / args.epochs for epoch > 0 (:710-729)."""
     vq = getattr(net, "vq", True)
+    if getattr(net, "VAE", False):
+        return _variational_iteration(args, epoch, input_poses, target_poses, net, _as_fused(net, optim))
     if getattr(net, "att_use", False):
         # attention decoder: module-level autograd path; its parameter set (attn.*, the wider pre_linear) is not the fused
         # engine's flat layout, so clip + Adam run over a FlatClipAdam of net.parameters()
@@ -125,7 +128,32 @@ def train_iter_Autoencoder_VQ_seq2seq_dp(args, epoch: int, input_poses: torch.Te
     ranks, then every rank applies the identical EMA update (global statistics) and clip + Adam on the mean gradient
     (gesture2vec_amd/dp.py).  Returns this rank's loss and the perplexity of the global code histogram (without a quantiser:
     this rank's {"loss": custom_loss} alone, the exchange then carries the gradients and the fault flag only)."""
+    if getattr(net, "VAE", False):
+        raise NotImplementedError(VAE_NOT_FUSED.format("train_iter_Autoencoder_VQ_seq2seq_dp (data parallel)"))
     return _fused_iteration(args, epoch, input_poses, target_poses, net, _as_fused(net, optim), reduce_fn, world)
+
+
+VAE_NOT_FUSED = ("{}: a variational net (autoencoder_vae == 'True') trains through the staged autograd path of "
+                 "train_iter_Autoencoder_VQ_seq2seq only; the variational block is not part of VQVAEEngine.train_step")
+
+
+def _variational_iteration(args, epoch, input_poses, target_poses, net, optim):
+    """autoencoder_vae == "True" (:692-701, 710-729, 738): encoder stage -> [quantiser] -> variational block -> decoder stage as
+    autograd nodes, the KL term from g2v_vae_latent_fwd (net.latent_kl), clip + Adam by the adopted FusedClipAdam."""
+    if optim.net is not net:
+        raise TypeError("the FusedClipAdam belongs to another net")
+    optim.zero_grad()
+    out = net(input_poses, target_poses, epoch > 0)
+    loss = custom_loss(out[0], target_poses, args)
+    if epoch > 0:
+        loss = loss + net.latent_kl * net.kl_weight(epoch, args.epochs)      # args.epochs read per call, as the reference does
+        if net.vq:
+            loss = loss + 1 * out[4] / 400
+    loss.backward()
+    optim.step()            # clip_grad_norm_(net.parameters(), 5) is fused into the step
+    if net.vq:
+        return {"loss": loss.item()}, out[5].detach()
+    return {"loss": loss.item()}
 
 
 def _as_fused(net, optim):
@@ -153,6 +181,8 @@ def _as_fused(net, optim):
 def _fused_iteration(args, epoch, input_poses, target_poses, net, optim, reduce_fn, world):
     """masks -> forward -> custom_loss + loss_vq / 400 -> backward -> [all-reduce] -> EMA update -> clip + Adam through
     VQVAEEngine.train_step; loss = custom_loss + loss_vq / 400 for epoch > 0 (:707,738)."""
+    if getattr(net, "VAE", False):
+        raise NotImplementedError(VAE_NOT_FUSED.format("the fused (and graph-replayed) iteration"))
     eng = net.engine()
     x, tgt = input_poses.contiguous(), target_poses.contiguous()
     kw = dict(lr=optim.lr, w_l1=float(args.loss_l1_weight), w_cont=float(args.loss_cont_weight),

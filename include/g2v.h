@@ -772,6 +772,42 @@ int g2v_vq_soft_fused_bwd(const float* dh, const float* g_loss, const float* x, 
                           g2v_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The variational block of the chunk autoencoder (autoencoder_vae == "True", model/Autoencoder_VQVAE_model.py:776-789, 879-899,
+ * 989-1010; train_eval/train_seq2seq.py:710-729), between the encoder state (or the quantiser's output) h (L,B,H) and the decoder's
+ * initial state d (L,B,H).  E = L H; row b of hf = h.transpose(1, 0).reshape(B, E) is [h[0, b] ; h[1, b] ; ...] and is read
+ * straight from the (L,B,H) layout (d and dh are written straight into it).  A workgroup owns 16 whole rows.
+ *   g2v_vae_latent_fwd   mean = hf w_mean^T + b_mean, logvar = hf w_std^T + b_std, z = mean + exp(logvar / 2) eps,
+ *                        d = z w_dec^T + b_dec, kl[0] = 0.5 mean(exp(logvar) - logvar - 1 + mean^2) over the B E elements -- one
+ *                        launch + a one-workgroup finish of kl (fixed-order sums, no atomics: the same input gives the same bits).
+ *                        sample != 0: eps = eps_in (B,E) when given, else drawn from the g2v_keep_mask stream (seed,
+ *                        offset_counter[0]; Philox block g <-> elements 4g .. 4g+3 of (B,E), two Box-Muller pairs per block), the
+ *                        counter then advances by 1; eps_out (B,E) receives the eps used (required when drawn, else may be NULL).
+ *                        sample == 0: z = mean bit for bit (reparameterize(train=False)), eps is neither read nor written.
+ *                        mean, logvar, z (B,E) are always written; hf (B,E) (the gathered rows, for the weight gradients) may be
+ *                        NULL; w_dec, b_dec, d may be NULL together (no third product).
+ *                        workspace >= g2v_vae_latent_fwd_workspace(B, E) bytes (the workgroups' KL partials).
+ *   g2v_vae_latent_bwd   dz = g_d w_dec (g_d (L,B,H): the decoder stage's dh_init), c = g_kl[0] / (B E) (g_kl: device scalar
+ *                        d loss / d kl, NULL = 0),
+ *                          dmean   = dz + c mean,    dlogvar = dz 0.5 exp(logvar / 2) eps + c 0.5 (exp(logvar) - 1),
+ *                          dh      = dmean w_mean + dlogvar w_std   (one accumulation over the concatenated K = 2 E) -> (L,B,H);
+ *                        dmean, dlogvar (B,E) are written for g2v_linear_bwd_weight.  eps NULL: the forward had sample == 0.
+ *                        g_mean, g_logvar (B,E; NULL = 0): gradients that reach mean / logvar directly (a caller's own loss on the
+ *                        returned tensors) are added to dmean / dlogvar.
+ * Served (g2v_vae_latent_ok): E % 16 == 0, E <= 512, any B >= 1; H % 4 == 0.  Anything else: G2V_ERR_UNSUPPORTED, no launch.
+ * All pointers 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int g2v_vae_latent_ok(int B, int E);
+int g2v_vae_latent_blocks(int B);
+size_t g2v_vae_latent_fwd_workspace(int B, int E);
+int g2v_vae_latent_fwd(const float* h, const float* w_mean, const float* b_mean, const float* w_std, const float* b_std,
+                       const float* w_dec, const float* b_dec, const float* eps_in, uint64_t seed, int64_t* offset_counter,
+                       int sample, float* mean, float* logvar, float* z, float* eps_out, float* hf, float* d, float* kl,
+                       void* workspace, size_t workspace_bytes, int B, int L, int H, g2v_stream_t stream);
+int g2v_vae_latent_bwd(const float* g_d, const float* g_kl, const float* g_mean, const float* g_logvar, const float* mean,
+                       const float* logvar, const float* eps, const float* w_mean, const float* w_std, const float* w_dec,
+                       float* dmean, float* dlogvar, float* dh, int B, int L, int H, g2v_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Remaining operators of Part d (text -> gesture-code seq2seq, model/text2embedding_model.py).
  *   g2v_embedding_fwd   out[r,:] = table[ids[r],:] * keep * scale   (nn.Embedding :90-92,126 / :252,340-343 with the
  *                       decoder's nn.Dropout(0.5) fused; keep may be NULL; row r of out starts at out + r * ldo, e.g. the

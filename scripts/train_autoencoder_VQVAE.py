@@ -116,10 +116,8 @@ def evaluate_testset(test_data_loader, generator, loss_fn, args) -> float:
         for in_poses, target_poses in test_data_loader:
             batch_size = in_poses.size(0)
             in_poses, target_poses = in_poses.to(device), target_poses.to(device)
-            if generator.vq:
-                out_poses, _latent, _loss_vq, _perp = generator(in_poses, target_poses)
-            else:
-                out_poses, _latent = generator(in_poses, target_poses)
+            # (outputs, first_hidden[, mean, logvar][, loss_vq, perplexity]): 2-, 4- or 6-tuple by autoencoder_vq / autoencoder_vae
+            out_poses = generator(in_poses, target_poses)[0]
             losses.update(float(loss_fn(out_poses, target_poses)), batch_size)
     generator.train(True)
     logging.info("[VAL] loss: {:.3f} / {:.1f}s".format(losses.avg, time.time() - start))
@@ -217,6 +215,8 @@ def train_epochs(args, train_data_loader, train_sim_dataset, test_data_loader, l
                     if m.count > 0:
                         summary += "{}: {:.3f}, ".format(m.name, m.avg)
                         m.reset()
+                if generator.VAE:       # the KL term of the latest iteration and the weight it entered the loss with (:715, 729)
+                    summary += "kld: {:.5f} x {:.4f}, ".format(float(generator.latent_kl.detach()), generator.kl_weight(epoch, args.epochs))
                 logging.info(summary)
             iter_start_time = time.time()
         loss_list.append(loss_epoch.avg)
