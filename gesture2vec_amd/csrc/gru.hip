@@ -2144,21 +2144,19 @@ __global__ __launch_bounds__(256, FUSE_W == 2 ? 1 : 2) void gru_bwd_fast_kernel(
 
 }  // namespace g2v
 
+// ====================================================================================================================
+// Host side.  Which of the five implementations a sequence call runs on is decided in ONE place, gru_route_plan (DESIGN.md section
+// 3.2.2; each route's admission rule: include/g2v.h at g2v_gru_seq_route).  g2v_gru_seq_fwd / _bwd validate, collect the facts of
+// the call, plan, and switch into one launcher per route; the public queries plan an ideal call and return a field of the result.
+// ====================================================================================================================
 using namespace g2v;
 
-static bool gru_fast_ok(int H, int64_t hs_ld) { return H == 64 && (hs_ld & 3) == 0; }
-// per-time-step launches (gru_step_*_kernel) while a direction would otherwise get only a handful of workgroups
-constexpr int GRU_SPLIT_MAX_B = 1024;
-static bool gru_split_ok(int B, int ndir, int H) {
-  // measured at H = 200 (VQ-VAE.yml dims, whole train step): split 3.0 vs 4.0 ms at B = 512, 5.1 vs 5.7 ms at B = 1024
-  return B <= GRU_SPLIT_MAX_B && cdiv(B, 16) * ndir <= 128 && (H & 3) == 0 && H <= 16 * GRU_STEP_KS && 3 * H <= 16 * GRU_STEP_KSB;
-}
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static size_t gru_split_state_floats(int ndir, int H) { return (size_t)ndir * 2 * GRU_SPLIT_MAX_B * H; }
+template <class... P>
+static bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }      // (NULL counts as aligned)
 
-// The cluster kernels (gru_cluster_*_kernel): the split path's shapes while the whole grid is resident at once -- at most one
-// 192-thread workgroup per CU (the workgroups of a row group wait for each other).  g2v_gru_seq_set_cluster(0) keeps the
-// per-step launches (parity tests, A/B).
+constexpr int GRU_SPLIT_MAX_B = 1024;      // the per-step and cluster routes end here (DESIGN.md 3.2.2 has the measurements)
+
+// g2v_gru_seq_set_cluster(0) keeps the per-step launches in place of the cluster kernels (parity tests, A/B).
 extern "C" int g2v_gru_seq_set_cluster(int enable) {             // = g2v_ctx_set_option(NULL, G2V_OPT_GRU_CLUSTER, enable)
   return g2v_ctx_set_option(nullptr, G2V_OPT_GRU_CLUSTER, enable);
 }
@@ -2170,6 +2168,8 @@ static int gru_device_cus() {
   }
   return n;
 }
+
+// ---- workspaces: sizes, and one view per direction of travel that names every region (each route's from offset 0) -----------
 // exchange records of the cluster kernels: forward one (16 x Hp) record of granules per (parity, row group, direction), backward one
 // per (parity, row group, producer tile, direction)
 static size_t gru_cluster_rec_bytes(int B, int ndir, int H, bool bwd) {
@@ -2181,39 +2181,202 @@ static size_t gru_cluster_xch_bytes(int B, int ndir, int H, bool bwd) {
   return gru_cluster_rec_bytes(B, ndir, H, bwd) + (size_t)ndir * cdiv(B, 16) * ((H + 15) >> 4) * sizeof(unsigned) + 16;
 }
 // the largest exchange region a cluster launch can need at this H: the grid has at most one workgroup per CU
-static size_t gru_cluster_max_xch_bytes(int H, bool bwd) {
+static size_t gru_cluster_max_xch_bytes(int H, bool bwd, int cus_) {
   if ((H & 3) != 0 || H > 16 * GRU_STEP_KS || H == 64 || H < 4) return 0;
-  const size_t Hp = (size_t)((H + 15) & ~15), nt = Hp / 16, cus = (size_t)gru_device_cus();
+  const size_t Hp = (size_t)((H + 15) & ~15), nt = Hp / 16, cus = (size_t)cus_;
   return (bwd ? cus : cus / nt + 1) * 2 * 16 * Hp * 8 + cus * sizeof(unsigned) + 16;
 }
-static bool gru_cluster_ok(int T, int B, int ndir, int H, const void* fn);
-// 1: g2v_gru_seq_fwd / _bwd run this shape as the persistent cluster kernels (small batch; see g2v_gru_seq_set_cluster)
-extern "C" int g2v_gru_seq_cluster_ok(int T, int B, int H, int ndir) {
-  return (ndir >= 1 && ndir <= 2 && gru_cluster_ok(T, B, ndir, H, nullptr)) ? 1 : 0;
-}
-static bool gru_cluster_ok(int T, int B, int ndir, int H, const void* fn) {
-  if (!g2v_internal_options().gru_cluster || !gru_split_ok(B, ndir, H) || T < 2 || T > (1 << 20)) return false;
-  if ((int64_t)cdiv(B, 16) * cdiv(H, 16) * ndir > gru_device_cus()) return false;
-  if (fn == nullptr) return true;      // (the shape query: the occupancy check is the launch's)
-  int n = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 192, 0) == hipSuccess && n >= 1;
-}
-
-// the exchange region a cluster launch of this shape clears (offset 0 of its workspace); 0: not a cluster shape
-size_t g2v_internal_gru_cluster_region(int T, int B, int H, int ndir, int bwd) {
-  if (ndir < 1 || ndir > 2 || !gru_cluster_ok(T, B, ndir, H, nullptr)) return 0;
-  return gru_cluster_xch_bytes(B, ndir, H, bwd != 0);
-}
-extern "C" size_t g2v_gru_seq_fwd_workspace(int ndir, int H) {
-  const size_t a = (size_t)2 * ndir * pack_floats(H, 3, H), b = gru_split_state_floats(ndir, H);
-  const size_t c = gru_cluster_max_xch_bytes(H, false);
-  const size_t ab = (a > b ? a : b) * sizeof(float);
+static size_t gru_pack_floats(bool bwd, int H) { return bwd ? pack_floats(H, 1, 3 * H) : pack_floats(H, 3, H); }
+static size_t gru_split_state_floats(int ndir, int H) { return (size_t)ndir * 2 * GRU_SPLIT_MAX_B * H; }
+// The largest of three regions: the fragment packs (per direction W_hh and W_ih), the per-step launches' state (backward: behind the
+// plain transposes), the cluster kernels' records.
+static size_t gru_workspace_bytes(bool bwd, int ndir, int H, int cus) {
+  const size_t a = (size_t)2 * ndir * gru_pack_floats(bwd, H);
+  const size_t b = (bwd ? (size_t)ndir * 3 * H * H : 0) + gru_split_state_floats(ndir, H);
+  const size_t ab = (a > b ? a : b) * sizeof(float), c = gru_cluster_max_xch_bytes(H, bwd, cus);
   return ab > c ? ab : c;
 }
-
+extern "C" size_t g2v_gru_seq_fwd_workspace(int ndir, int H) { return gru_workspace_bytes(false, ndir, H, gru_device_cus()); }
+extern "C" size_t g2v_gru_seq_bwd_workspace(int ndir, int H) { return gru_workspace_bytes(true, ndir, H, gru_device_cus()); }
 extern "C" size_t g2v_gru_seq_bwd_wslab_bytes(int B, int H) {
   return (B > 0 && H > 0) ? (size_t)cdiv(B, 16) * 2 * ((size_t)3 * H * H + 3 * H) * sizeof(float) : 0;
 }
+
+struct GruWs {
+  PackBatch pb; const float* p_hh[2]; const float* p_ih[2];      // fragment packs, per direction W_hh (, W_ih): descriptors and images
+  float* wt[2]; float* carry[2];                                  // backward STEP: plain transposes (3H x H), then the carry (B x H)
+  float* state[2];                                                // forward STEP: [parity][B][H] per direction
+  unsigned long long* rec[2]; unsigned* words;                    // CLUSTER: the exchange records, then one word per workgroup
+};
+// backward: W^T with rows k (hidden feature) and the contraction over the 3H gates.  w_ih / with_ih: the FAST kernels that fuse the
+// input projection / gradient.  rbytes: the plan's rec_bytes.  B = 0, rbytes = 0 (the prepare calls): the pack regions only.
+static GruWs gru_ws(bool bwd, const float* const* w_hh, const float* const* w_ih, int ndir, int B, int H, bool with_ih, size_t rbytes,
+                    void* workspace) {
+  GruWs v{};
+  float* p = (float*)workspace;
+  const size_t pf = gru_pack_floats(bwd, H);
+  auto desc = [&](const float* w, float* dst) { return bwd ? PackDesc{w, dst, H, 1, 0, 3 * H, H, 1, 0} : PackDesc{w, dst, H, 3, H, H, H, 0, 0}; };
+  for (int k = 0; k < ndir; ++k) {
+    v.pb.d[v.pb.n++] = desc(w_hh[k], p); v.p_hh[k] = p; p += pf;
+    if (with_ih) { v.pb.d[v.pb.n++] = desc(w_ih[k], p); v.p_ih[k] = p; p += pf; }
+    v.wt[k] = (float*)workspace + (size_t)k * 3 * H * H;
+    v.carry[k] = (float*)workspace + (size_t)ndir * 3 * H * H + (size_t)k * B * H;      // (3 H^2 floats: a 16-byte multiple)
+    v.state[k] = (float*)workspace + (size_t)k * 2 * B * H;
+    v.rec[k] = reinterpret_cast<unsigned long long*>((char*)workspace + (size_t)k * (rbytes / ndir));
+  }
+  v.words = reinterpret_cast<unsigned*>((char*)workspace + rbytes);
+  return v;
+}
+
+// ---- the plan ------------------------------------------------------------------------------------------------------------
+struct GruCallFacts {      // what the plan needs to know of ONE call beyond its sizes; the defaults are the queries' ideal call
+  // 16-byte alignment of every array a route reads or writes as float4s, over all directions.  Forward: split = gi, w_hh, b_hh, h0,
+  // gates, h_n, workspace; vec = gi, b_hh, hs, gates (resident: the same).  Backward: split = gates, dgi, dgh, d_hn, h0, dh0,
+  // workspace; vec = gates, dgi, dgh, hs, h0, dh0, d_hs; resident = vec and d_hn.
+  bool split_aligned = true, vec_aligned = true, res_aligned = true;
+  bool hs_ld4 = true, d_hs_ld4 = true;              // the leading dimensions are multiples of 4 (d_hs_ld: backward)
+  bool packed = false, gathered = false, lengths = true;      // gi_row_off / dgi_row_off, gi_gather, lengths are set
+  bool fused = false, in_dim_is_H = true;           // gi == NULL / dx != NULL; every direction's in_dim == H
+  int wgrad = 0;                                    // backward: 1 dw_hh is set, 2 dw_ih too (direction 0)
+  bool wgrad_any = false, wgrad_complete = true;    // some direction sets one of dw_hh, db_hh, dw_ih, db_ih, wslab / every one its whole group
+  bool hn = false, hn_usable = true;                // hn_z is set / with d_hn, hn_q, hn_gloss and aligned slices
+  bool dgi_dgh = true;                              // backward: both outputs are there
+  bool prepared = false;                            // g2v_gru_seq_prepare has filled the workspace (the *_prepared entry points, H == 64)
+  size_t workspace_bytes = ~(size_t)0;
+  bool cluster_resident = true;                     // gru_cluster_resident: asked only once a plan says cluster (gru_plan_call)
+};
+struct GruRoutePlan {
+  int route, variant;             // G2V_GRU_ROUTE_* and its variant (g2v.h); route 0: refused with `err` and `msg`
+  bool pack, transpose;           // the fragment packs / the plain transposes are launched in front
+  int grid[3], block; size_t lds; // of the route's kernel
+  size_t rec_bytes, xch_bytes;    // CLUSTER: the records end / the region to clear ends here (both from offset 0)
+  int note;                       // a pre-cleared note for the workspace: 1 taken, -1 dropped, 0 left alone
+  int err; const char* msg;
+};
+static GruRoutePlan gru_route_plan(bool bwd, int T, int B, int H, int ndir, int cluster, int res_rows, int res_bwd, int cus,
+                                   const GruCallFacts& f) {
+  GruRoutePlan pl{};
+  auto refuse = [&pl](int err, const char* msg) { pl.route = 0; pl.err = err; pl.msg = msg; return pl; };
+  auto launch = [&pl](int route, int variant, int gx, int gy, int gz, int block, size_t lds) {
+    pl.route = route; pl.variant = variant; pl.grid[0] = gx; pl.grid[1] = gy; pl.grid[2] = gz; pl.block = block; pl.lds = lds;
+  };
+  if (T <= 0 || B <= 0 || H <= 0 || ndir < 1 || ndir > 2) return refuse(G2V_ERR_ARG, "bad size");
+  if (f.workspace_bytes < gru_workspace_bytes(bwd, ndir, H, cus)) return refuse(G2V_ERR_WORKSPACE, "workspace too small");
+  if (f.packed && !(T <= GRU_MAX_OFF && H >= 4 && (H & 3) == 0 && H <= 256 && H != 64))
+    return refuse(G2V_ERR_UNSUPPORTED, bwd ? "packed dgi is not served for this shape (g2v_gru_seq_packed_ok)"
+                                           : "packed gi is not served for this shape (g2v_gru_seq_packed_ok)");
+  if (f.packed && !f.lengths)
+    return refuse(G2V_ERR_UNSUPPORTED, bwd ? "packed dgi needs lengths, T <= 64 and the generic kernels with H % 4 == 0 (g2v_gru_seq_packed_ok)"
+                                           : "packed gi needs lengths, T <= 64 and the generic kernels with H % 4 == 0 (g2v_gru_seq_packed_ok)");
+  const int Hp = (H + 15) & ~15, nt = Hp >> 4, nblk = cdiv(B, 16);
+  const bool ld4 = f.hs_ld4 && (!bwd || f.d_hs_ld4);
+  const bool split_shape = B <= GRU_SPLIT_MAX_B && nblk * ndir <= 128 && (H & 3) == 0 && H <= 16 * GRU_STEP_KS && 3 * H <= 16 * GRU_STEP_KSB;
+  const bool vec = (H & 3) == 0 && H <= 256 && ld4 && f.vec_aligned;
+  if (H == 64 && ld4) {
+    launch(G2V_GRU_ROUTE_FAST, !bwd ? (f.fused ? 1 : 0) : f.wgrad ? 1 + f.wgrad : (f.fused ? 1 : 0), nblk, ndir, 1, 256, 0);
+    pl.pack = !f.prepared;
+  } else if (split_shape && f.split_aligned) {
+    // small batch: (row groups x hidden-unit tiles x directions) workgroups, ONE launch for all steps while every workgroup has a CU
+    // of its own (they wait for each other), else one launch per step
+    const size_t xb = gru_cluster_xch_bytes(B, ndir, H, bwd);
+    if (cluster && T >= 2 && T <= (1 << 20) && (int64_t)nblk * nt * ndir <= cus && xb <= f.workspace_bytes && f.cluster_resident) {
+      launch(G2V_GRU_ROUTE_CLUSTER, 0, nt * nblk * ndir, 1, 1, 192, 0);
+      pl.rec_bytes = gru_cluster_rec_bytes(B, ndir, H, bwd); pl.xch_bytes = xb; pl.note = 1;
+    } else {
+      launch(G2V_GRU_ROUTE_STEP, 0, nblk, nt, ndir, 64, 0);
+      pl.transpose = bwd; pl.note = -1;
+    }
+  } else if (bwd ? (H == RESB_H && res_rows > 0 && B >= res_rows && res_bwd && ld4 && f.res_aligned)
+                 : (vec && Hp == 16 * RES_KB && res_rows > 0 && B >= res_rows)) {
+    // large batch: W_hh resident in the CU for the whole sequence.  Forward: one workgroup per CU, each walks its row tiles.
+    if (bwd) launch(G2V_GRU_ROUTE_RESIDENT, 0, nblk, ndir, 1, 256, RESB_LDS_BYTES);
+    else launch(G2V_GRU_ROUTE_RESIDENT, 0, min(nblk, max(1, (cus > 0 ? cus : 256) / ndir)), ndir, 1, 256, RES_LDS_BYTES);
+    pl.pack = !bwd;      // (the backward reads W_hh in place)
+  } else {
+    const size_t lds = bwd ? (size_t)16 * ((((3 * H + 15) & ~15) + 4) + (Hp + 4)) * sizeof(float) : (size_t)2 * 16 * (Hp + 4) * sizeof(float);
+    if (lds > 160 * 1024) return refuse(G2V_ERR_ARG, "hidden size too large for LDS");
+    if (f.packed && !vec) return refuse(G2V_ERR_ARG, bwd ? "packed dgi: the scalar generic body does not serve it"
+                                                        : "packed gi: the scalar generic body does not serve it");
+    // forward: two row tiles per workgroup once that still leaves a workgroup for most CUs
+    if (!bwd && vec && 2 * lds <= 160 * 1024 && cdiv(B, 32) * ndir >= 192) launch(G2V_GRU_ROUTE_STREAM, 2, cdiv(B, 32), ndir, 1, 512, 2 * lds);
+    else launch(G2V_GRU_ROUTE_STREAM, vec ? 1 : 0, nblk, ndir, 1, 256, lds);
+    pl.pack = true;
+  }
+  // what only some routes serve
+  if (f.gathered && !(!bwd && pl.route == G2V_GRU_ROUTE_RESIDENT && !split_shape))      // (a split shape off its route by alignment: still not)
+    return refuse(G2V_ERR_UNSUPPORTED, "gi_gather is served by the W_hh-resident forward only (g2v_gru_seq_gather_ok)");
+  if (f.hn && !((pl.route == G2V_GRU_ROUTE_FAST || pl.route == G2V_GRU_ROUTE_CLUSTER) && f.hn_usable))
+    return refuse(G2V_ERR_UNSUPPORTED, "the fused quantiser backward (hn_z, hn_q, hn_gloss) needs the H == 64 kernels or the cluster "
+                                       "kernels (g2v_gru_seq_cluster_ok), d_hn and 16-byte-aligned slices");
+  if (f.fused && !(pl.route == G2V_GRU_ROUTE_FAST && f.in_dim_is_H))
+    return refuse(G2V_ERR_UNSUPPORTED, bwd ? "fused input gradient needs H == in_dim == 64 (use g2v_linear_bwd_data otherwise)"
+                                           : "fused input projection needs H == in_dim == 64 (compute gi with g2v_linear_fwd otherwise)");
+  if (f.wgrad_any && pl.route != G2V_GRU_ROUTE_FAST)
+    return refuse(G2V_ERR_UNSUPPORTED, "fused weight gradients (dw_hh, db_hh, dw_ih, db_ih, wslab) need the H == 64 kernels");
+  if (f.wgrad_any && !(f.wgrad && f.wgrad_complete && f.fused))
+    return refuse(G2V_ERR_ARG, "fused weight gradients: dw_hh, db_hh, wslab (+ dw_ih, db_ih, x) for every direction, with the fused input gradient");
+  if (bwd && !f.dgi_dgh && !f.wgrad_any) return refuse(G2V_ERR_ARG, "null pointer");      // (with the weight gradients fused dgh, or both, may be NULL)
+  return pl;
+}
+// Is the cluster kernel resident with (at least) one 192-thread workgroup per CU?
+static bool gru_cluster_resident(bool bwd) {
+  int n = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bwd ? (const void*)gru_cluster_bwd_kernel : (const void*)gru_cluster_fwd_kernel, 192, 0) ==
+             hipSuccess && n >= 1;
+}
+// the plan of a real call (the bound context's options, this device's CUs, the call's facts) ...
+static GruRoutePlan gru_plan_call(bool bwd, int T, int B, int H, int ndir, GruCallFacts f) {
+  const G2vOptions& o = g2v_internal_options();
+  GruRoutePlan pl = gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, gru_device_cus(), f);
+  if (pl.route == G2V_GRU_ROUTE_CLUSTER && !gru_cluster_resident(bwd)) {
+    f.cluster_resident = false;
+    pl = gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, gru_device_cus(), f);
+  }
+  return pl;
+}
+// ... and of the queries (include/g2v.h), each a field of the ideal call's plan
+static GruRoutePlan gru_plan_ideal(bool bwd, int T, int B, int H, int ndir, const GruCallFacts& f = GruCallFacts{}) {
+  const G2vOptions& o = g2v_internal_options();
+  return gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, gru_device_cus(), f);
+}
+extern "C" int g2v_gru_seq_route(int backward, int T, int B, int H, int ndir, int cluster, int resident_rows, int resident_bwd, int cus,
+                                 int facts) {
+  const G2vOptions& o = g2v_internal_options();
+  const bool bwd = backward != 0;
+  GruCallFacts f;
+  f.split_aligned = !(facts & G2V_GRU_PLAN_SPLIT_UNALIGNED); f.vec_aligned = !(facts & G2V_GRU_PLAN_VEC_UNALIGNED);
+  f.res_aligned = f.vec_aligned && !(facts & G2V_GRU_PLAN_D_HN_UNALIGNED);
+  f.hs_ld4 = !(facts & G2V_GRU_PLAN_HS_LD); f.d_hs_ld4 = !(facts & G2V_GRU_PLAN_D_HS_LD);
+  f.packed = facts & G2V_GRU_PLAN_PACKED; f.gathered = facts & G2V_GRU_PLAN_GATHERED; f.lengths = !(facts & G2V_GRU_PLAN_NO_LENGTHS);
+  f.fused = facts & G2V_GRU_PLAN_FUSED; f.in_dim_is_H = !(facts & G2V_GRU_PLAN_IN_DIM);
+  f.wgrad = (facts & G2V_GRU_PLAN_WGRAD_HH) ? ((facts & G2V_GRU_PLAN_WGRAD_IH) ? 2 : 1) : 0;
+  f.wgrad_any = facts & (G2V_GRU_PLAN_WGRAD_HH | G2V_GRU_PLAN_WGRAD_IH); f.wgrad_complete = !(facts & G2V_GRU_PLAN_WGRAD_PARTIAL);
+  f.hn = facts & G2V_GRU_PLAN_HN; f.hn_usable = !(facts & G2V_GRU_PLAN_HN_UNUSABLE);
+  f.dgi_dgh = !(facts & G2V_GRU_PLAN_NO_DGI); f.prepared = facts & G2V_GRU_PLAN_PREPARED;
+  if (facts & G2V_GRU_PLAN_SMALL_WORKSPACE) f.workspace_bytes = 0;
+  f.cluster_resident = !(facts & G2V_GRU_PLAN_NOT_RESIDENT);
+  const GruRoutePlan pl = gru_route_plan(bwd, T, B, H, ndir, cluster < 0 ? o.gru_cluster : cluster, resident_rows < 0 ? o.gru_resident_rows : resident_rows,
+                                         resident_bwd < 0 ? o.gru_resident_bwd : resident_bwd, cus > 0 ? cus : gru_device_cus(), f);
+  return pl.route ? pl.route | (pl.variant << 8) : 0;
+}
+extern "C" int g2v_gru_seq_cluster_ok(int T, int B, int H, int ndir) { return gru_plan_ideal(false, T, B, H, ndir).route == G2V_GRU_ROUTE_CLUSTER ? 1 : 0; }
+extern "C" int g2v_gru_seq_gather_ok(int T, int B, int H, int ndir) {
+  GruCallFacts f;
+  f.gathered = true;
+  return gru_plan_ideal(false, T, B, H, ndir, f).route != 0 ? 1 : 0;
+}
+extern "C" int g2v_gru_seq_packed_ok(int T, int B, int H) {
+  GruCallFacts f;
+  f.packed = true;
+  return gru_plan_ideal(false, T, B, H, 1, f).route != 0 ? 1 : 0;
+}
+// the exchange region a cluster launch of this shape clears (offset 0 of its workspace); 0: not a cluster shape
+size_t g2v_internal_gru_cluster_region(int T, int B, int H, int ndir, int bwd) {
+  const GruRoutePlan pl = gru_plan_ideal(bwd != 0, T, B, H, ndir);
+  return pl.route == G2V_GRU_ROUTE_CLUSTER ? pl.xch_bytes : 0;
+}
+
+// ---- the cell entry points -----------------------------------------------------------------------------------------------
 static bool cell_shape_ok(int in_dim, int H) { return (in_dim & 3) == 0 && (H & 3) == 0 && in_dim <= 16 * GRU_STEP_KS && H <= 16 * GRU_STEP_KS; }
 
 extern "C" int g2v_gru_cell_fwd(const float* x, int in_dim, const uint8_t* x_keep, float x_scale, const float* h_prev,
@@ -2256,42 +2419,7 @@ extern "C" int g2v_gru_cell_bwd(const float* d_h_a, const float* d_h_b, const fl
   return G2V_OK;
 }
 
-// fragment packs of the H == 64 fast kernels, in workspace order: per direction W_hh (, W_ih when the projection is fused)
-static PackBatch gru_fwd_packs(const float* const* w_hh, const float* const* w_ih, int ndir, int H, bool fuse, float* p,
-                               const float** p_hh, const float** p_ih) {
-  PackBatch pb;
-  pb.n = 0;
-  for (int k = 0; k < ndir; ++k) {
-    pb.d[pb.n++] = PackDesc{w_hh[k], p, H, 3, H, H, H, 0, 0};
-    p_hh[k] = p;
-    p += pack_floats(H, 3, H);
-    p_ih[k] = nullptr;
-    if (fuse) {
-      pb.d[pb.n++] = PackDesc{w_ih[k], p, H, 3, H, H, H, 0, 0};
-      p_ih[k] = p;
-      p += pack_floats(H, 3, H);
-    }
-  }
-  return pb;
-}
-static PackBatch gru_bwd_packs(const float* const* w_hh, const float* const* w_ih, int ndir, int H, bool fuse, float* p,
-                               const float** p_hh_t, const float** p_ih_t) {
-  PackBatch pb;
-  pb.n = 0;
-  for (int k = 0; k < ndir; ++k) {
-    pb.d[pb.n++] = PackDesc{w_hh[k], p, H, 1, 0, 3 * H, H, 1, 0};   // rows k (hidden feature), contraction over the 3H gates
-    p_hh_t[k] = p;
-    p += pack_floats(H, 1, 3 * H);
-    p_ih_t[k] = nullptr;
-    if (fuse) {
-      pb.d[pb.n++] = PackDesc{w_ih[k], p, H, 1, 0, 3 * H, H, 1, 0};
-      p_ih_t[k] = p;
-      p += pack_floats(H, 1, 3 * H);
-    }
-  }
-  return pb;
-}
-
+// ---- ahead-of-time fragment packs ----------------------------------------------------------------------------------------
 // The weight-fragment packs of one g2v_gru_seq_fwd + one g2v_gru_seq_bwd call (H == 64 fast kernels), launched ahead of time
 // into the two workspaces (the engine runs this as a parallel branch at the start of the step); the *_prepared entry points
 // then skip their pack launch.  fused != 0: the calls fuse the input projection / input gradient (w_ih packed too).
@@ -2308,192 +2436,147 @@ extern "C" int g2v_gru_seq_prepare(const float* const* w_hh, const float* const*
     set_error("g2v_gru_seq_prepare: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
-  const float* a[2];
-  const float* b[2];
-  if (fwd_workspace) launch_pack(gru_fwd_packs(w_hh, w_ih, ndir, H, fused != 0, (float*)fwd_workspace, a, b), (hipStream_t)stream);
-  if (bwd_workspace) launch_pack(gru_bwd_packs(w_hh, w_ih, ndir, H, fused != 0, (float*)bwd_workspace, a, b), (hipStream_t)stream);
+  if (fwd_workspace) launch_pack(gru_ws(false, w_hh, w_ih, ndir, 0, H, fused != 0, 0, fwd_workspace).pb, (hipStream_t)stream);
+  if (bwd_workspace) launch_pack(gru_ws(true, w_hh, w_ih, ndir, 0, H, fused != 0, 0, bwd_workspace).pb, (hipStream_t)stream);
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
-
-// packed gi / dgi (g2v_gru_dir.gi_row_off): the generic kernels with 16-byte accesses, offsets by value in the kernel arguments
-// 1: g2v_gru_seq_fwd would run the W_hh-resident forward for this shape (aligned operands assumed), the one kernel that gathers gi
-extern "C" int g2v_gru_seq_gather_ok(int T, int B, int H, int ndir) {
-  const int res_rows = g2v_internal_options().gru_resident_rows;
-  return (T >= 1 && B >= 1 && ndir >= 1 && ndir <= 2 && (H & 3) == 0 && ((H + 15) & ~15) == 16 * RES_KB && res_rows > 0 && B >= res_rows &&
-          !gru_split_ok(B, ndir, H)) ? 1 : 0;
+// g2v_train_step_prepare (dec_rollout.hip): the pack descriptors of g2v_gru_seq_prepare's BACKWARD workspace, appended to `out`
+// (returns how many; 0: this hidden size reads its weights in place, or the workspace is too small)
+namespace g2v {
+int gru_bwd_prepare_descs(const float* const* w_hh, const float* const* w_ih, int ndir, int H, bool fused, void* bwd_workspace,
+                          size_t bwd_bytes, PackDesc* out, int max_out) {
+  if (H != 64 || !bwd_workspace || bwd_bytes < g2v_gru_seq_bwd_workspace(ndir, H)) return 0;
+  const PackBatch pb = gru_ws(true, w_hh, w_ih, ndir, 0, H, fused, 0, bwd_workspace).pb;
+  if (pb.n > max_out) return 0;
+  for (int k = 0; k < pb.n; ++k) out[k] = pb.d[k];
+  return pb.n;
 }
-extern "C" int g2v_gru_seq_packed_ok(int T, int B, int H) {
-  return (T >= 1 && T <= GRU_MAX_OFF && B >= 1 && H >= 4 && (H & 3) == 0 && H <= 256 && H != 64) ? 1 : 0;
+}  // namespace g2v
+
+// packed gi / dgi (g2v_gru_dir.gi_row_off, g2v_gru_dir_bwd.dgi_row_off): the T <= GRU_MAX_OFF offsets by value in the kernel arguments.
+// off[k]: direction k's host array, or NULL for the (T,B,3H) layout.  Returns what is wrong with them, or NULL.
+static const char* gru_row_off(const int32_t* const* off, int ndir, int T, RowOff* ro) {
+  ro->on = off[0] ? 1 : 0;
+  for (int t = 0; t < GRU_MAX_OFF; ++t) ro->off[t] = (ro->on && t < T) ? off[0][t] : 0;
+  for (int k = 1; k < ndir && ro->on; ++k)
+    for (int t = 0; t < T; ++t)
+      if (off[k][t] != ro->off[t]) return "the directions' offsets differ";
+  return nullptr;
+}
+
+// ---- forward: one launcher per route -------------------------------------------------------------------------------------
+struct GruFwdCall {
+  const g2v_gru_dir* dirs; int ndir; const int32_t* lengths; int64_t hs_ld; int T, B, H; hipStream_t st; RowOff ro;
+};
+static dim3 gru_grid(const GruRoutePlan& pl) { return dim3(pl.grid[0], pl.grid[1], pl.grid[2]); }
+// FAST: H = 64, the weights as fragment packs, the input projection fused or not
+static void gru_fwd_launch_fast(const GruFwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+  GruDirF f[2];
+  for (int k = 0; k < c.ndir; ++k) {
+    const g2v_gru_dir& d = c.dirs[k];
+    f[k] = GruDirF{d.gi, ws.p_hh[k], d.b_hh, d.h0, d.hs, d.h_n, d.gates, d.reverse, d.x, ws.p_ih[k], d.b_ih};
+  }
+  if (c.ndir == 1) f[1] = f[0];
+  auto* const kernel = pl.variant ? gru_fwd_fast_kernel<64, true> : gru_fwd_fast_kernel<64, false>;
+  hipLaunchKernelGGL(kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, f[0], f[1], c.lengths, c.hs_ld, c.T, c.B);
+}
+// CLUSTER: ONE launch for all steps, the same workgroups as STEP resident, the state rows exchanged through tagged granules
+static int gru_fwd_launch_cluster(const GruFwdCall& c, const GruRoutePlan& pl, const GruWs& ws, void* workspace) {
+  GruClF a[2];
+  for (int k = 0; k < c.ndir; ++k) {
+    const g2v_gru_dir& d = c.dirs[k];
+    a[k] = GruClF{d.gi, d.w_hh, d.b_hh, d.h0, d.hs, d.gates, d.h_n, ws.rec[k], d.reverse};
+  }
+  if (c.ndir == 1) a[1] = a[0];
+  if (!g2v_internal_preclear_take(workspace, pl.xch_bytes) && hipMemsetAsync(workspace, 0, pl.xch_bytes, c.st) != hipSuccess) return G2V_ERR_LAUNCH;
+  const int nt = (c.H + 15) >> 4, nblk = cdiv(c.B, 16);
+  hipLaunchKernelGGL(gru_cluster_fwd_kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, a[0], a[1], c.lengths, c.hs_ld, c.T, c.B, c.H, c.ro,
+                     ws.words, nt, nblk, c.ndir, const_cast<unsigned*>(g2v_internal_persist_fault_ptr()));
+  return G2V_OK;
+}
+// STEP: one launch per time step, (row groups x hidden-unit tiles x directions) single-wave workgroups
+static void gru_fwd_launch_steps(const GruFwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+  const int T = c.T, B = c.B, H = c.H;
+  for (int s_ = 0; s_ < T; ++s_) {
+    GruStepF g[2];
+    for (int k = 0; k < c.ndir; ++k) {
+      const g2v_gru_dir& d = c.dirs[k];
+      float* cur = ws.state[k] + (size_t)(s_ & 1) * B * H;
+      float* nxt = ws.state[k] + (size_t)((s_ + 1) & 1) * B * H;
+      const int tk = d.reverse ? T - 1 - s_ : s_;
+      g[k] = GruStepF{d.gi, d.w_hh, d.b_hh, s_ == 0 ? d.h0 : cur, nxt, d.hs, d.gates, d.h_n, tk, c.ro.on ? (int64_t)c.ro.off[tk] : (int64_t)tk * B};
+    }
+    if (c.ndir == 1) g[1] = g[0];
+    hipLaunchKernelGGL(gru_step_fwd_kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, g[0], g[1], c.lengths, c.hs_ld, T, B, H, s_ == T - 1 ? 1 : 0);
+  }
+}
+// RESIDENT (192 < H <= 208: W_hh in the CU for the whole sequence) and STREAM (W_hh streamed as fragment packs: coalesced 1 KiB
+// fragment loads, eight k-steps kept in flight by wave_gemm_p), with two row tiles, one row tile, or the scalar body
+static void gru_fwd_launch_packed_weights(const GruFwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+  GruGenF g[2];
+  for (int k = 0; k < c.ndir; ++k) {
+    const g2v_gru_dir& d = c.dirs[k];
+    g[k] = GruGenF{d.gi, ws.p_hh[k], d.b_hh, d.h0, d.hs, d.h_n, d.gates, d.reverse, d.gi_gather};
+  }
+  if (c.ndir == 1) g[1] = g[0];
+  auto* const kernel = pl.route == G2V_GRU_ROUTE_RESIDENT ? gru_res_fwd_kernel
+                       : pl.variant == 2 ? gru_seq_fwd_kernel<2> : pl.variant == 1 ? gru_seq_fwd_kernel<1> : gru_seq_fwd_kernel<0>;
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  hipLaunchKernelGGL(kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, g[0], g[1], c.lengths, c.hs_ld, c.T, c.B, c.H, c.ro);
 }
 
 static int gru_seq_fwd_impl(const g2v_gru_dir* dirs, int ndir, const int32_t* lengths, int64_t hs_ld, int T, int B,
                             int H, void* workspace, size_t workspace_bytes, g2v_stream_t stream, bool prepared) {
+  // ---- 1. the arguments ----
   G2V_REQUIRE(dirs && workspace, "null pointer");
   G2V_REQUIRE(ndir >= 1 && ndir <= 2, "1 or 2 directions per call");
   G2V_REQUIRE(T > 0 && B > 0 && H > 0 && hs_ld >= H, "bad size");
-  const bool gathered = dirs[0].gi_gather != nullptr;
-  for (int k = 0; k < ndir; ++k) G2V_REQUIRE((dirs[k].gi_gather != nullptr) == gathered && (!gathered || dirs[k].gi), "gathered gi: every direction or none, with its table");
-  if (gathered && !g2v_gru_seq_gather_ok(T, B, H, ndir)) {
-    set_error("g2v_gru_seq_fwd: gi_gather is served by the W_hh-resident forward only (g2v_gru_seq_gather_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
-  for (int k = 0; k < ndir; ++k) G2V_REQUIRE(dirs[k].w_hh && dirs[k].b_hh && dirs[k].hs, "null pointer");
-  if (dirs[0].gi_row_off && !g2v_gru_seq_packed_ok(T, B, H)) {
-    set_error("g2v_gru_seq_fwd: packed gi is not served for this shape (g2v_gru_seq_packed_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
   // gi == NULL: the input projection is fused (x, w_ih, b_ih given, in_dim == H == 64); all directions alike
-  const bool fuse = dirs[0].gi == nullptr;
+  GruCallFacts f;
+  f.gathered = dirs[0].gi_gather != nullptr; f.fused = dirs[0].gi == nullptr; f.packed = dirs[0].gi_row_off != nullptr;
+  f.lengths = lengths != nullptr; f.hs_ld4 = (hs_ld & 3) == 0; f.prepared = prepared; f.workspace_bytes = workspace_bytes;
+  const float* w_hh[2]; const float* w_ih[2]; const int32_t* off[2];
   for (int k = 0; k < ndir; ++k) {
-    G2V_REQUIRE((dirs[k].gi == nullptr) == fuse, "directions must agree on gi / fused input projection");
-    if (fuse) G2V_REQUIRE(dirs[k].x && dirs[k].w_ih && dirs[k].b_ih, "gi == NULL needs x, w_ih, b_ih");
+    const g2v_gru_dir& d = dirs[k];
+    G2V_REQUIRE((d.gi_gather != nullptr) == f.gathered && (!f.gathered || d.gi), "gathered gi: every direction or none, with its table");
+    G2V_REQUIRE(d.w_hh && d.b_hh && d.hs, "null pointer");
+    G2V_REQUIRE((d.gi == nullptr) == f.fused, "directions must agree on gi / fused input projection");
+    G2V_REQUIRE(!f.fused || (d.x && d.w_ih && d.b_ih), "gi == NULL needs x, w_ih, b_ih");
+    G2V_REQUIRE((d.gi_row_off != nullptr) == f.packed, "packed gi: every direction or none");
+    f.split_aligned = f.split_aligned && aligned16(d.gi, d.w_hh, d.b_hh, d.h0, d.gates, d.h_n, (const char*)workspace);
+    f.vec_aligned = f.vec_aligned && aligned16(d.gi, d.b_hh, d.hs, d.gates);
+    f.in_dim_is_H = f.in_dim_is_H && d.in_dim == H;
+    w_hh[k] = d.w_hh; w_ih[k] = d.w_ih; off[k] = d.gi_row_off;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (fuse && !(gru_fast_ok(H, hs_ld) && dirs[0].in_dim == H && (ndir == 1 || dirs[1].in_dim == H))) {
-    set_error("g2v_gru_seq_fwd: fused input projection needs H == in_dim == 64 (compute gi with g2v_linear_fwd otherwise)");
-    return G2V_ERR_UNSUPPORTED;
+  // ---- 2. the plan ----
+  const GruRoutePlan pl = gru_plan_call(false, T, B, H, ndir, f);
+  if (pl.route == 0) {
+    set_error("%s: %s", pl.err == G2V_ERR_ARG ? __func__ : "g2v_gru_seq_fwd", pl.msg);
+    return pl.err;
   }
-  if (gru_fast_ok(H, hs_ld)) {
-    if (workspace_bytes < g2v_gru_seq_fwd_workspace(ndir, H)) {
-      set_error("g2v_gru_seq_fwd: workspace too small");
-      return G2V_ERR_WORKSPACE;
-    }
-    const float* whh[2] = {dirs[0].w_hh, dirs[ndir - 1].w_hh};
-    const float* wih[2] = {dirs[0].w_ih, dirs[ndir - 1].w_ih};
-    const float* p_hh[2];
-    const float* p_ih[2];
-    const PackBatch pb = gru_fwd_packs(whh, wih, ndir, H, fuse, (float*)workspace, p_hh, p_ih);
-    GruDirF f[2];
-    for (int k = 0; k < ndir; ++k)
-      f[k] = GruDirF{dirs[k].gi, p_hh[k], dirs[k].b_hh, dirs[k].h0, dirs[k].hs, dirs[k].h_n, dirs[k].gates, dirs[k].reverse,
-                     dirs[k].x, p_ih[k], dirs[k].b_ih};
-    if (ndir == 1) f[1] = f[0];
-    if (!prepared) {
-      launch_pack(pb, st);
-      G2V_CHECK_LAUNCH();
-    }
-    if (fuse)
-      hipLaunchKernelGGL((gru_fwd_fast_kernel<64, true>), dim3(cdiv(B, 16), ndir), dim3(256), 0, st, f[0], f[1], lengths, hs_ld, T, B);
-    else
-      hipLaunchKernelGGL((gru_fwd_fast_kernel<64, false>), dim3(cdiv(B, 16), ndir), dim3(256), 0, st, f[0], f[1], lengths, hs_ld, T, B);
+  // ---- 3. the launches ----
+  GruFwdCall c{dirs, ndir, lengths, hs_ld, T, B, H, (hipStream_t)stream, {}};
+  if (const char* e = gru_row_off(off, ndir, T, &c.ro)) {
+    set_error("%s: packed gi: %s", __func__, e);
+    return G2V_ERR_ARG;
+  }
+  const GruWs ws = gru_ws(false, w_hh, w_ih, ndir, B, H, f.fused, pl.rec_bytes, workspace);
+  if (pl.note < 0) g2v_internal_preclear_drop(workspace, workspace_bytes);      // (a pre-cleared note for this workspace is void)
+  if (pl.pack) {      // the weights into MFMA fragment order (one launch)
+    launch_pack(ws.pb, c.st);
     G2V_CHECK_LAUNCH();
-    return G2V_OK;
   }
-  const int Hp = (H + 15) & ~15;
-  bool split = gru_split_ok(B, ndir, H);
-  for (int k = 0; k < ndir && split; ++k)
-    split = aligned16(dirs[k].gi) && aligned16(dirs[k].w_hh) && aligned16(dirs[k].b_hh) && aligned16(dirs[k].h0) &&
-            aligned16(dirs[k].gates) && aligned16(dirs[k].h_n) && aligned16(workspace);
-  RowOff ro;
-  ro.on = 0;
-  if (dirs[0].gi_row_off) {
-    for (int k = 0; k < ndir; ++k) G2V_REQUIRE(dirs[k].gi_row_off != nullptr, "packed gi: every direction or none");
-    if (!g2v_gru_seq_packed_ok(T, B, H) || lengths == nullptr) {
-      set_error("g2v_gru_seq_fwd: packed gi needs lengths, T <= 64 and the generic kernels with H %% 4 == 0 (g2v_gru_seq_packed_ok)");
-      return G2V_ERR_UNSUPPORTED;
-    }
-    ro.on = 1;
-    for (int t = 0; t < GRU_MAX_OFF; ++t) ro.off[t] = t < T ? dirs[0].gi_row_off[t] : 0;
-    for (int k = 1; k < ndir; ++k)
-      for (int t = 0; t < T; ++t) G2V_REQUIRE(dirs[k].gi_row_off[t] == ro.off[t], "packed gi: the directions' offsets differ");
-  } else {
-    for (int k = 0; k < ndir; ++k) G2V_REQUIRE(dirs[k].gi_row_off == nullptr, "packed gi: every direction or none");
-  }
-  if (split) {
-    // small batch: one launch per time step, (row groups x hidden-unit tiles x directions) single-wave workgroups
-    if (workspace_bytes < g2v_gru_seq_fwd_workspace(ndir, H)) {
-      set_error("g2v_gru_seq_fwd: workspace too small");
-      return G2V_ERR_WORKSPACE;
-    }
-    const size_t xbytes = gru_cluster_xch_bytes(B, ndir, H, false), rbytes = gru_cluster_rec_bytes(B, ndir, H, false);
-    if (gru_cluster_ok(T, B, ndir, H, (const void*)gru_cluster_fwd_kernel) && xbytes <= workspace_bytes) {
-      // ... or ONE launch for all steps: the same workgroups resident, the state rows exchanged through tagged granules
-      GruClF c[2];
-      for (int k = 0; k < ndir; ++k)
-        c[k] = GruClF{dirs[k].gi, dirs[k].w_hh, dirs[k].b_hh, dirs[k].h0, dirs[k].hs, dirs[k].gates, dirs[k].h_n,
-                      reinterpret_cast<unsigned long long*>((char*)workspace + (size_t)k * (rbytes / ndir)), dirs[k].reverse};
-      if (ndir == 1) c[1] = c[0];
-      if (!g2v_internal_preclear_take(workspace, xbytes) && hipMemsetAsync(workspace, 0, xbytes, st) != hipSuccess) {
+  switch (pl.route) {
+    case G2V_GRU_ROUTE_FAST: gru_fwd_launch_fast(c, pl, ws); break;
+    case G2V_GRU_ROUTE_CLUSTER:
+      if (gru_fwd_launch_cluster(c, pl, ws, workspace) != G2V_OK) {
         set_error("g2v_gru_seq_fwd: clearing the exchange records failed");
         return G2V_ERR_LAUNCH;
       }
-      hipLaunchKernelGGL(gru_cluster_fwd_kernel, dim3((Hp >> 4) * cdiv(B, 16) * ndir), dim3(192), 0, st, c[0], c[1], lengths, hs_ld, T,
-                         B, H, ro, reinterpret_cast<unsigned*>((char*)workspace + rbytes), Hp >> 4, cdiv(B, 16), ndir,
-                         const_cast<unsigned*>(g2v_internal_persist_fault_ptr()));
-      G2V_CHECK_LAUNCH();
-      return G2V_OK;
-    }
-    g2v_internal_preclear_drop(workspace, workspace_bytes);      // (per-step launches: a pre-cleared note for this workspace is void)
-    float* state = (float*)workspace;                  // [dir][2][B][H]
-    for (int s_ = 0; s_ < T; ++s_) {
-      GruStepF g[2];
-      for (int k = 0; k < ndir; ++k) {
-        float* cur = state + ((size_t)k * 2 + (s_ & 1)) * B * H;
-        float* nxt = state + ((size_t)k * 2 + ((s_ + 1) & 1)) * B * H;
-        const int tk = dirs[k].reverse ? T - 1 - s_ : s_;
-        g[k] = GruStepF{dirs[k].gi, dirs[k].w_hh, dirs[k].b_hh, s_ == 0 ? dirs[k].h0 : cur, nxt, dirs[k].hs, dirs[k].gates,
-                        dirs[k].h_n, tk, ro.on ? (int64_t)ro.off[tk] : (int64_t)tk * B};
-      }
-      if (ndir == 1) g[1] = g[0];
-      hipLaunchKernelGGL(gru_step_fwd_kernel, dim3(cdiv(B, 16), Hp >> 4, ndir), dim3(64), 0, st, g[0], g[1], lengths, hs_ld,
-                         T, B, H, s_ == T - 1 ? 1 : 0);
-    }
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  const size_t lds = (size_t)2 * 16 * (Hp + 4) * sizeof(float);
-  G2V_REQUIRE(lds <= 160 * 1024, "hidden size too large for LDS");
-  (void)hipFuncSetAttribute((const void*)gru_seq_fwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute((const void*)gru_seq_fwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (2 * lds <= 160 * 1024)
-    (void)hipFuncSetAttribute((const void*)gru_seq_fwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * lds));
-  if (workspace_bytes < g2v_gru_seq_fwd_workspace(ndir, H)) {
-    set_error("g2v_gru_seq_fwd: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  GruGenF g[2];
-  {
-    // W_hh in MFMA fragment order (coalesced 1 KiB fragment loads, eight k-steps kept in flight by wave_gemm_p)
-    float* pp = (float*)workspace;
-    PackBatch pb;
-    pb.n = 0;
-    for (int k = 0; k < ndir; ++k) {
-      pb.d[pb.n++] = PackDesc{dirs[k].w_hh, pp, H, 3, H, H, H, 0, 0};
-      g[k] = GruGenF{dirs[k].gi, pp, dirs[k].b_hh, dirs[k].h0, dirs[k].hs, dirs[k].h_n, dirs[k].gates, dirs[k].reverse, dirs[k].gi_gather};
-      pp += pack_floats(H, 3, H);
-    }
-    launch_pack(pb, st);
-    G2V_CHECK_LAUNCH();
-  }
-  if (ndir == 1) g[1] = g[0];
-  bool v4 = (H & 3) == 0 && H <= 256 && (hs_ld & 3) == 0;
-  for (int k = 0; k < ndir && v4; ++k)
-    v4 = aligned16(dirs[k].gi) && aligned16(dirs[k].b_hh) && aligned16(dirs[k].hs) && aligned16(dirs[k].gates);
-  // large batch, 192 < H <= 208: W_hh resident in the CU for the whole sequence (gru_res_fwd_kernel)
-  const int res_rows = g2v_internal_options().gru_resident_rows;
-  if (gathered && !(v4 && Hp == 16 * RES_KB && res_rows > 0 && B >= res_rows)) {
-    set_error("g2v_gru_seq_fwd: gi_gather is served by the W_hh-resident forward only (g2v_gru_seq_gather_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
-  if (v4 && Hp == 16 * RES_KB && res_rows > 0 && B >= res_rows) {
-    (void)hipFuncSetAttribute((const void*)gru_res_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RES_LDS_BYTES);
-    const int per_dir = max(1, (gru_device_cus() > 0 ? gru_device_cus() : 256) / ndir);      // one workgroup per CU; each walks its row tiles
-    hipLaunchKernelGGL(gru_res_fwd_kernel, dim3(min(cdiv(B, 16), per_dir), ndir), dim3(256), RES_LDS_BYTES, st, g[0], g[1], lengths, hs_ld,
-                       T, B, H, ro);
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  // two row tiles per workgroup (every weight fragment multiplies 32 rows: 0.73 against 0.80 ms at the native shape) once that
-  // still leaves a workgroup for most CUs
-  if (v4 && 2 * lds <= 160 * 1024 && cdiv(B, 32) * ndir >= 192)
-    hipLaunchKernelGGL(gru_seq_fwd_kernel<2>, dim3(cdiv(B, 32), ndir), dim3(512), 2 * lds, st, g[0], g[1], lengths, hs_ld, T, B, H, ro);
-  else if (v4)
-    hipLaunchKernelGGL(gru_seq_fwd_kernel<1>, dim3(cdiv(B, 16), ndir), dim3(256), lds, st, g[0], g[1], lengths, hs_ld, T, B, H, ro);
-  else
-  {
-    G2V_REQUIRE(!ro.on, "packed gi: the scalar generic body does not serve it");
-    hipLaunchKernelGGL(gru_seq_fwd_kernel<0>, dim3(cdiv(B, 16), ndir), dim3(256), lds, st, g[0], g[1], lengths, hs_ld, T, B, H, ro);
+      break;
+    case G2V_GRU_ROUTE_STEP: gru_fwd_launch_steps(c, pl, ws); break;
+    default: gru_fwd_launch_packed_weights(c, pl, ws); break;      // RESIDENT, STREAM
   }
   G2V_CHECK_LAUNCH();
   return G2V_OK;
@@ -2503,260 +2586,173 @@ extern "C" int g2v_gru_seq_fwd(const g2v_gru_dir* dirs, int ndir, const int32_t*
                                int H, void* workspace, size_t workspace_bytes, g2v_stream_t stream) {
   return gru_seq_fwd_impl(dirs, ndir, lengths, hs_ld, T, B, H, workspace, workspace_bytes, stream, false);
 }
-// g2v_train_step_prepare (dec_rollout.hip): the pack descriptors of g2v_gru_seq_prepare's BACKWARD workspace, appended to `out`
-// (returns how many; 0: this hidden size reads its weights in place, or the workspace is too small)
-namespace g2v {
-int gru_bwd_prepare_descs(const float* const* w_hh, const float* const* w_ih, int ndir, int H, bool fused, void* bwd_workspace,
-                          size_t bwd_bytes, PackDesc* out, int max_out) {
-  if (H != 64 || !bwd_workspace || bwd_bytes < g2v_gru_seq_bwd_workspace(ndir, H)) return 0;
-  const float* a[2];
-  const float* b[2];
-  const PackBatch pb = gru_bwd_packs(w_hh, w_ih, ndir, H, fused, (float*)bwd_workspace, a, b);
-  if (pb.n > max_out) return 0;
-  for (int k = 0; k < pb.n; ++k) out[k] = pb.d[k];
-  return pb.n;
-}
-}  // namespace g2v
-
 // as g2v_gru_seq_fwd / _bwd on workspaces that g2v_gru_seq_prepare has filled for THIS call (no pack launch)
 extern "C" int g2v_gru_seq_fwd_prepared(const g2v_gru_dir* dirs, int ndir, const int32_t* lengths, int64_t hs_ld, int T,
                                         int B, int H, void* workspace, size_t workspace_bytes, g2v_stream_t stream) {
   return gru_seq_fwd_impl(dirs, ndir, lengths, hs_ld, T, B, H, workspace, workspace_bytes, stream, H == 64);
 }
 
-extern "C" size_t g2v_gru_seq_bwd_workspace(int ndir, int H) {
-  const size_t a = (size_t)2 * ndir * pack_floats(H, 1, 3 * H), b = (size_t)ndir * 3 * H * H + gru_split_state_floats(ndir, H);
-  const size_t c = gru_cluster_max_xch_bytes(H, true);      // the cluster kernel's exchange records (whatever B it admits)
-  const size_t ab = (a > b ? a : b) * sizeof(float);
-  return ab > c ? ab : c;
+// ---- backward: one launcher per route ------------------------------------------------------------------------------------
+struct GruBwdCall {
+  const g2v_gru_dir_bwd* dirs; int ndir; const int32_t* lengths; int64_t d_hs_ld, hs_ld; int T, B, H; hipStream_t st; RowOff ro;
+};
+// FAST: plain, with dx = dgi W_ih, or with the weight gradients too (per-workgroup slabs, then one reduction)
+static int gru_bwd_launch_fast(const GruBwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+  const int ndir = c.ndir, H = c.H;
+  GruDirB f[2];
+  for (int k = 0; k < ndir; ++k) {
+    const g2v_gru_dir_bwd& d = c.dirs[k];
+    f[k] = GruDirB{d.d_hs, d.d_hn, d.hs, d.h0, d.gates, ws.p_hh[k], d.dgi, d.dgh, d.dh0, d.reverse, ws.p_ih[k], d.dx, d.x, d.wslab,
+                   d.hn_z, d.hn_q, d.hn_gloss, d.hn_coef};
+  }
+  if (ndir == 1) f[1] = f[0];
+  auto* const kernel = pl.variant == 3 ? gru_bwd_fast_kernel<64, true, 2> : pl.variant == 2 ? gru_bwd_fast_kernel<64, true, 1>
+                       : pl.variant == 1 ? gru_bwd_fast_kernel<64, true> : gru_bwd_fast_kernel<64, false>;
+  hipLaunchKernelGGL(kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, f[0], f[1], c.lengths, c.d_hs_ld, c.hs_ld, c.T, c.B);
+  if (pl.variant < 2) return G2V_OK;
+  if (hipGetLastError() != hipSuccess) return G2V_ERR_LAUNCH;
+  const int nblk = pl.grid[0];
+  const int64_t nw = (int64_t)3 * H * H, nb = 3 * H;
+  const float* sw[4]; const float* sb[4]; float* ow[4]; float* ob[4];
+  int np = 0;
+  for (int k = 0; k < ndir; ++k) {
+    const g2v_gru_dir_bwd& d = c.dirs[k];
+    sw[np] = d.wslab; ow[np] = d.dw_hh;
+    sb[np] = d.wslab + (int64_t)2 * nblk * nw; ob[np] = d.db_hh;
+    ++np;
+    if (pl.variant == 3) {
+      sw[np] = d.wslab + (int64_t)nblk * nw; ow[np] = d.dw_ih;
+      sb[np] = d.wslab + (int64_t)2 * nblk * nw + (int64_t)nblk * nb; ob[np] = d.db_ih;
+      ++np;
+    }
+  }
+  return g2v_internal_slab_reduce4(sw, ow, sb, ob, np, nw, nb, nblk, c.st) != 0 ? G2V_ERR_LAUNCH : G2V_OK;
+}
+static int gru_bwd_launch_cluster(const GruBwdCall& c, const GruRoutePlan& pl, const GruWs& ws, void* workspace) {
+  GruClB a[2];
+  for (int k = 0; k < c.ndir; ++k) {
+    const g2v_gru_dir_bwd& d = c.dirs[k];
+    a[k] = GruClB{d.hn_z, d.hn_q, d.hn_gloss, d.hn_coef, d.d_hs, d.hs, d.h0, d.gates, d.w_hh, d.d_hn, d.dgi, d.dgh, d.dh0, ws.rec[k], d.reverse};
+  }
+  if (c.ndir == 1) a[1] = a[0];
+  const bool want_dh0 = c.dirs[0].dh0 || (c.ndir == 2 && c.dirs[1].dh0);
+  if (!g2v_internal_preclear_take(workspace, pl.xch_bytes) && hipMemsetAsync(workspace, 0, pl.xch_bytes, c.st) != hipSuccess) return G2V_ERR_LAUNCH;
+  const int nt = (c.H + 15) >> 4, nblk = cdiv(c.B, 16);
+  hipLaunchKernelGGL(gru_cluster_bwd_kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, a[0], a[1], c.lengths, c.d_hs_ld, c.hs_ld, c.T, c.B, c.H,
+                     c.ro, want_dh0 ? c.T : c.T - 1, ws.words, nt, nblk, c.ndir, const_cast<unsigned*>(g2v_internal_persist_fault_ptr()));
+  return G2V_OK;
+}
+// STEP (behind the plain transposes): launch `it`: part A finishes the step of forward iteration T - it, part B opens forward iteration T - 1 - it
+static void gru_bwd_launch_steps(const GruBwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+  const int T = c.T, B = c.B, H = c.H, ndir = c.ndir;
+  for (int it = 0; it <= T; ++it) {
+    GruStepB g[2];
+    for (int k = 0; k < ndir; ++k) {
+      const g2v_gru_dir_bwd& d = c.dirs[k];
+      const bool rev = d.reverse != 0;
+      const int s_cur = T - it, s_next = T - 1 - it;
+      const int t_cur = it == 0 ? -1 : (rev ? T - 1 - s_cur : s_cur);
+      const int t_next = s_next < 0 ? -1 : (rev ? T - 1 - s_next : s_next);
+      const int tprev = (s_next <= 0) ? -1 : (rev ? t_next + 1 : t_next - 1);
+      g[k] = GruStepB{d.d_hs, d.hs, d.h0, d.gates, ws.wt[k], d.d_hn, ws.carry[k], d.dgi, d.dgh, d.dh0, t_cur, t_next, tprev,
+                      t_next < 0 ? (int64_t)0 : (c.ro.on ? (int64_t)c.ro.off[t_next] : (int64_t)t_next * B), c.ro.on};
+    }
+    if (ndir == 1) g[1] = g[0];
+    if (it == T && !c.dirs[0].dh0 && (ndir == 1 || !c.dirs[1].dh0)) break;      // nobody wants the initial-state gradient
+    hipLaunchKernelGGL(gru_step_bwd_kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, g[0], g[1], c.lengths, c.d_hs_ld, c.hs_ld, T, B, H);
+  }
+}
+// RESIDENT: H = 200, W_hh (read in place) resident in the CU for the whole sequence, one workgroup per row tile
+static void gru_bwd_launch_resident(const GruBwdCall& c, const GruRoutePlan& pl) {
+  GruResB r[2];
+  for (int k = 0; k < c.ndir; ++k) {
+    const g2v_gru_dir_bwd& d = c.dirs[k];
+    r[k] = GruResB{d.d_hs, d.d_hn, d.hs, d.h0, d.gates, d.w_hh, d.dgi, d.dgh, d.dh0, d.reverse};
+  }
+  if (c.ndir == 1) r[1] = r[0];
+  (void)hipFuncSetAttribute((const void*)gru_res_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  hipLaunchKernelGGL(gru_res_bwd_kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, r[0], r[1], c.lengths, c.d_hs_ld, c.hs_ld, c.T, c.B, c.ro);
+}
+// STREAM: W_hh^T streamed as fragment packs, the vector or the scalar body
+static void gru_bwd_launch_stream(const GruBwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+  GruGenB g[2];
+  for (int k = 0; k < c.ndir; ++k) {
+    const g2v_gru_dir_bwd& d = c.dirs[k];
+    g[k] = GruGenB{d.d_hs, d.d_hn, d.hs, d.h0, d.gates, ws.p_hh[k], d.dgi, d.dgh, d.dh0, d.reverse};
+  }
+  if (c.ndir == 1) g[1] = g[0];
+  auto* const kernel = pl.variant ? gru_seq_bwd_kernel<1> : gru_seq_bwd_kernel<0>;
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  hipLaunchKernelGGL(kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, g[0], g[1], c.lengths, c.d_hs_ld, c.hs_ld, c.T, c.B, c.H, c.ro);
 }
 
 static int gru_seq_bwd_impl(const g2v_gru_dir_bwd* dirs, int ndir, const int32_t* lengths, int64_t d_hs_ld,
                             int64_t hs_ld, int T, int B, int H, void* workspace, size_t workspace_bytes,
                             g2v_stream_t stream, bool prepared) {
+  // ---- 1. the arguments ----
   G2V_REQUIRE(dirs && workspace, "null pointer");
   G2V_REQUIRE(ndir >= 1 && ndir <= 2, "1 or 2 directions per call");
   G2V_REQUIRE(T > 0 && B > 0 && H > 0, "bad size");
-  for (int k = 0; k < ndir; ++k)
-    G2V_REQUIRE(dirs[k].hs && dirs[k].gates && dirs[k].w_hh && ((dirs[k].dgi && dirs[k].dgh) || dirs[k].dw_hh), "null pointer");
-  if (workspace_bytes < g2v_gru_seq_bwd_workspace(ndir, H)) {
-    set_error("g2v_gru_seq_bwd: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* p = (float*)workspace;
-  if (dirs[0].dgi_row_off && !g2v_gru_seq_packed_ok(T, B, H)) {
-    set_error("g2v_gru_seq_bwd: packed dgi is not served for this shape (g2v_gru_seq_packed_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
-  // dx != NULL: the input gradient dx = dgi W_ih is fused (w_ih given, in_dim == H == 64); all directions alike
-  const bool fuse = dirs[0].dx != nullptr;
+  // dx != NULL: the input gradient dx = dgi W_ih is fused (w_ih given, in_dim == H == 64); dw_hh != NULL: the weight gradients too,
+  // W_hh only (dw_hh, db_hh, wslab) or W_hh and W_ih (plus dw_ih, db_ih, x); all directions alike
+  GruCallFacts f;
+  f.fused = dirs[0].dx != nullptr; f.packed = dirs[0].dgi_row_off != nullptr; f.lengths = lengths != nullptr;
+  f.hs_ld4 = (hs_ld & 3) == 0; f.d_hs_ld4 = (d_hs_ld & 3) == 0; f.prepared = prepared; f.workspace_bytes = workspace_bytes;
+  f.wgrad = dirs[0].dw_hh ? (dirs[0].dw_ih ? 2 : 1) : 0;
+  const float* w_hh[2]; const float* w_ih[2]; const int32_t* off[2];
   for (int k = 0; k < ndir; ++k) {
-    G2V_REQUIRE((dirs[k].dx != nullptr) == fuse, "directions must agree on the fused input gradient");
-    if (fuse) G2V_REQUIRE(dirs[k].w_ih, "dx != NULL needs w_ih");
+    const g2v_gru_dir_bwd& d = dirs[k];
+    G2V_REQUIRE(d.hs && d.gates && d.w_hh, "null pointer");
+    G2V_REQUIRE((d.dx != nullptr) == f.fused, "directions must agree on the fused input gradient");
+    G2V_REQUIRE(!f.fused || d.w_ih, "dx != NULL needs w_ih");
+    G2V_REQUIRE((d.dgi_row_off != nullptr) == f.packed, "packed dgi: every direction or none");
+    f.split_aligned = f.split_aligned && aligned16(d.gates, d.dgi, d.dgh, d.d_hn, d.h0, d.dh0, (const float*)workspace);
+    f.vec_aligned = f.vec_aligned && aligned16(d.gates, d.dgi, d.dgh, d.hs, d.h0, d.dh0, d.d_hs);
+    f.res_aligned = f.res_aligned && aligned16(d.gates, d.dgi, d.dgh, d.hs, d.h0, d.dh0, d.d_hs, d.d_hn);
+    f.in_dim_is_H = f.in_dim_is_H && d.in_dim == H;
+    const bool hh = d.dw_hh && d.db_hh && d.wslab, ih = d.dw_ih && d.db_ih && d.x, no_ih = !d.dw_ih && !d.db_ih;
+    f.wgrad_any = f.wgrad_any || d.dw_hh || d.db_hh || d.wslab || d.dw_ih || d.db_ih;
+    f.wgrad_complete = f.wgrad_complete && hh && (f.wgrad == 2 ? (ih && aligned16(d.x)) : (no_ih && d.dgi != nullptr));
+    f.hn = f.hn || d.hn_z != nullptr;
+    f.hn_usable = f.hn_usable && (!d.hn_z || (d.d_hn && d.hn_q && d.hn_gloss && aligned16(d.hn_z, d.hn_q)));
+    f.dgi_dgh = f.dgi_dgh && d.dgi && d.dgh;
+    w_hh[k] = d.w_hh; w_ih[k] = d.w_ih; off[k] = d.dgi_row_off;
   }
-  const bool fast = gru_fast_ok(H, hs_ld) && (d_hs_ld & 3) == 0;
-  // (the fused quantiser backward: the H == 64 kernels, or the small-batch cluster kernel -- g2v_gru_seq_cluster_ok)
-  const bool hn_cluster = !fast && gru_cluster_ok(T, B, ndir, H, (const void*)gru_cluster_bwd_kernel) &&
-                          gru_cluster_xch_bytes(B, ndir, H, true) <= workspace_bytes;
-  bool hn_any = false;
-  for (int k = 0; k < ndir; ++k) {
-    hn_any = hn_any || dirs[k].hn_z != nullptr;
-    if (dirs[k].hn_z && !((fast || hn_cluster) && dirs[k].d_hn && dirs[k].hn_q && dirs[k].hn_gloss && aligned16(dirs[k].hn_z) &&
-                          aligned16(dirs[k].hn_q))) {
-      set_error("g2v_gru_seq_bwd: the fused quantiser backward (hn_z, hn_q, hn_gloss) needs the H == 64 kernels or the cluster "
-                "kernels (g2v_gru_seq_cluster_ok), d_hn and 16-byte-aligned slices");
-      return G2V_ERR_UNSUPPORTED;
-    }
+  // ---- 2. the plan ----
+  const GruRoutePlan pl = gru_plan_call(true, T, B, H, ndir, f);
+  if (pl.route == 0) {
+    set_error("%s: %s", pl.err == G2V_ERR_ARG ? __func__ : "g2v_gru_seq_bwd", pl.msg);
+    return pl.err;
   }
-  if (fuse && !(fast && dirs[0].in_dim == H && (ndir == 1 || dirs[1].in_dim == H))) {
-    set_error("g2v_gru_seq_bwd: fused input gradient needs H == in_dim == 64 (use g2v_linear_bwd_data otherwise)");
-    return G2V_ERR_UNSUPPORTED;
+  // ---- 3. the launches ----
+  GruBwdCall c{dirs, ndir, lengths, d_hs_ld, hs_ld, T, B, H, (hipStream_t)stream, {}};
+  if (const char* e = gru_row_off(off, ndir, T, &c.ro)) {
+    set_error("%s: packed dgi: %s", __func__, e);
+    return G2V_ERR_ARG;
   }
-  if (fast) {
-    const float* whh[2] = {dirs[0].w_hh, dirs[ndir - 1].w_hh};
-    const float* wih[2] = {dirs[0].w_ih, dirs[ndir - 1].w_ih};
-    const float* p_hh_t[2];
-    const float* p_ih_t[2];
-    const PackBatch pb = gru_bwd_packs(whh, wih, ndir, H, fuse, p, p_hh_t, p_ih_t);
-    GruDirB f[2];
-    // fused weight gradients: every direction names x, its four outputs and a slab buffer (or none does)
-    // fused weight gradients: W_hh only (dw_hh, db_hh, wslab) or W_hh and W_ih (plus dw_ih, db_ih, x); every direction alike
-    const bool fuse_w = dirs[0].dw_hh != nullptr, fuse_w2 = fuse_w && dirs[0].dw_ih != nullptr;
-    for (int k = 0; k < ndir; ++k) {
-      const bool hh = dirs[k].dw_hh && dirs[k].db_hh && dirs[k].wslab, ih = dirs[k].dw_ih && dirs[k].db_ih && dirs[k].x;
-      const bool no_hh = !dirs[k].dw_hh && !dirs[k].db_hh && !dirs[k].wslab, no_ih = !dirs[k].dw_ih && !dirs[k].db_ih;
-      G2V_REQUIRE(fuse_w ? (hh && fuse && (fuse_w2 ? (ih && aligned16(dirs[k].x)) : (no_ih && dirs[k].dgi != nullptr))) : (no_hh && no_ih),
-                  "fused weight gradients: dw_hh, db_hh, wslab (+ dw_ih, db_ih, x) for every direction, with the fused input gradient");
-    }
-    for (int k = 0; k < ndir; ++k)
-      f[k] = GruDirB{dirs[k].d_hs, dirs[k].d_hn, dirs[k].hs, dirs[k].h0, dirs[k].gates, p_hh_t[k],
-                     dirs[k].dgi, dirs[k].dgh, dirs[k].dh0, dirs[k].reverse, p_ih_t[k], dirs[k].dx, dirs[k].x, dirs[k].wslab,
-                     dirs[k].hn_z, dirs[k].hn_q, dirs[k].hn_gloss, dirs[k].hn_coef};
-    if (ndir == 1) f[1] = f[0];
-    if (!prepared) {
-      launch_pack(pb, st);
-      G2V_CHECK_LAUNCH();
-    }
-    if (fuse_w) {
-      const int nblk = cdiv(B, 16);
-      if (fuse_w2)
-        hipLaunchKernelGGL((gru_bwd_fast_kernel<64, true, 2>), dim3(nblk, ndir), dim3(256), 0, st, f[0], f[1], lengths, d_hs_ld,
-                           hs_ld, T, B);
-      else
-        hipLaunchKernelGGL((gru_bwd_fast_kernel<64, true, 1>), dim3(nblk, ndir), dim3(256), 0, st, f[0], f[1], lengths, d_hs_ld,
-                           hs_ld, T, B);
-      G2V_CHECK_LAUNCH();
-      const int64_t nw = (int64_t)3 * H * H, nb = 3 * H;
-      const float* sw[4]; const float* sb[4]; float* ow[4]; float* ob[4];
-      int np = 0;
-      for (int k = 0; k < ndir; ++k) {
-        sw[np] = dirs[k].wslab; ow[np] = dirs[k].dw_hh;
-        sb[np] = dirs[k].wslab + (int64_t)2 * nblk * nw; ob[np] = dirs[k].db_hh;
-        ++np;
-        if (fuse_w2) {
-          sw[np] = dirs[k].wslab + (int64_t)nblk * nw; ow[np] = dirs[k].dw_ih;
-          sb[np] = dirs[k].wslab + (int64_t)2 * nblk * nw + (int64_t)nblk * nb; ob[np] = dirs[k].db_ih;
-          ++np;
-        }
-      }
-      if (g2v_internal_slab_reduce4(sw, ow, sb, ob, np, nw, nb, nblk, st) != 0) {
+  const GruWs ws = gru_ws(true, w_hh, w_ih, ndir, B, H, f.fused, pl.rec_bytes, workspace);
+  if (pl.note < 0) g2v_internal_preclear_drop(workspace, workspace_bytes);
+  if (pl.pack) {
+    launch_pack(ws.pb, c.st);
+    G2V_CHECK_LAUNCH();
+  }
+  for (int k = 0; k < ndir && pl.transpose; ++k) launch_transpose(w_hh[k], ws.wt[k], 3 * H, H, c.st);
+  switch (pl.route) {
+    case G2V_GRU_ROUTE_FAST:
+      if (gru_bwd_launch_fast(c, pl, ws) != G2V_OK) {
         set_error("g2v_gru_seq_bwd: slab reduction launch failed");
         return G2V_ERR_LAUNCH;
       }
-      return G2V_OK;
-    }
-    if (fuse)
-      hipLaunchKernelGGL((gru_bwd_fast_kernel<64, true>), dim3(cdiv(B, 16), ndir), dim3(256), 0, st, f[0], f[1], lengths, d_hs_ld,
-                         hs_ld, T, B);
-    else
-      hipLaunchKernelGGL((gru_bwd_fast_kernel<64, false>), dim3(cdiv(B, 16), ndir), dim3(256), 0, st, f[0], f[1], lengths, d_hs_ld,
-                         hs_ld, T, B);
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  const int Hp = (H + 15) & ~15, Gp = (3 * H + 15) & ~15;
-  const size_t lds = (size_t)16 * ((Gp + 4) + (Hp + 4)) * sizeof(float);
-  G2V_REQUIRE(lds <= 160 * 1024, "hidden size too large for LDS");
-  (void)hipFuncSetAttribute((const void*)gru_seq_bwd_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  (void)hipFuncSetAttribute((const void*)gru_seq_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  bool split = gru_split_ok(B, ndir, H) && aligned16(workspace);
-  for (int k = 0; k < ndir && split; ++k)
-    split = aligned16(dirs[k].gates) && aligned16(dirs[k].dgi) && aligned16(dirs[k].dgh) && aligned16(dirs[k].d_hn) &&
-            aligned16(dirs[k].h0) && aligned16(dirs[k].dh0);
-  RowOff ro;
-  ro.on = 0;
-  if (dirs[0].dgi_row_off) {
-    for (int k = 0; k < ndir; ++k) G2V_REQUIRE(dirs[k].dgi_row_off != nullptr, "packed dgi: every direction or none");
-    if (!g2v_gru_seq_packed_ok(T, B, H) || lengths == nullptr) {
-      set_error("g2v_gru_seq_bwd: packed dgi needs lengths, T <= 64 and the generic kernels with H %% 4 == 0 (g2v_gru_seq_packed_ok)");
-      return G2V_ERR_UNSUPPORTED;
-    }
-    ro.on = 1;
-    for (int t = 0; t < GRU_MAX_OFF; ++t) ro.off[t] = t < T ? dirs[0].dgi_row_off[t] : 0;
-    for (int k = 1; k < ndir; ++k)
-      for (int t = 0; t < T; ++t) G2V_REQUIRE(dirs[k].dgi_row_off[t] == ro.off[t], "packed dgi: the directions' offsets differ");
-  } else {
-    for (int k = 0; k < ndir; ++k) G2V_REQUIRE(dirs[k].dgi_row_off == nullptr, "packed dgi: every direction or none");
-  }
-  if (split) {
-    const int Hp = (H + 15) & ~15;
-    const size_t xbytes = gru_cluster_xch_bytes(B, ndir, H, true), rbytes = gru_cluster_rec_bytes(B, ndir, H, true);
-    if (gru_cluster_ok(T, B, ndir, H, (const void*)gru_cluster_bwd_kernel) && xbytes <= workspace_bytes) {
-      GruClB c[2];
-      for (int k = 0; k < ndir; ++k)
-        c[k] = GruClB{dirs[k].hn_z, dirs[k].hn_q, dirs[k].hn_gloss, dirs[k].hn_coef,
-                      dirs[k].d_hs, dirs[k].hs, dirs[k].h0, dirs[k].gates, dirs[k].w_hh, dirs[k].d_hn, dirs[k].dgi, dirs[k].dgh,
-                      dirs[k].dh0, reinterpret_cast<unsigned long long*>((char*)workspace + (size_t)k * (rbytes / ndir)),
-                      dirs[k].reverse};
-      if (ndir == 1) c[1] = c[0];
-      const bool want_dh0 = dirs[0].dh0 || (ndir == 2 && dirs[1].dh0);
-      if (!g2v_internal_preclear_take(workspace, xbytes) && hipMemsetAsync(workspace, 0, xbytes, st) != hipSuccess) {
+      break;
+    case G2V_GRU_ROUTE_CLUSTER:
+      if (gru_bwd_launch_cluster(c, pl, ws, workspace) != G2V_OK) {
         set_error("g2v_gru_seq_bwd: clearing the exchange records failed");
         return G2V_ERR_LAUNCH;
       }
-      hipLaunchKernelGGL(gru_cluster_bwd_kernel, dim3((Hp >> 4) * cdiv(B, 16) * ndir), dim3(192), 0, st, c[0], c[1], lengths, d_hs_ld,
-                         hs_ld, T, B, H, ro, want_dh0 ? T : T - 1, reinterpret_cast<unsigned*>((char*)workspace + rbytes), Hp >> 4,
-                         cdiv(B, 16), ndir, const_cast<unsigned*>(g2v_internal_persist_fault_ptr()));
-      G2V_CHECK_LAUNCH();
-      return G2V_OK;
-    }
-    g2v_internal_preclear_drop(workspace, workspace_bytes);
-    if (hn_any) {
-      set_error("g2v_gru_seq_bwd: the fused quantiser backward was requested but the cluster kernel does not serve this call");
-      return G2V_ERR_UNSUPPORTED;
-    }
-    float* carry = p + (size_t)ndir * 3 * H * H;      // [dir][B][H], after the transposed weights (3 H^2 floats: 16-byte multiple)
-    for (int k = 0; k < ndir; ++k) launch_transpose(dirs[k].w_hh, p + (size_t)k * 3 * H * H, 3 * H, H, st);
-    // launch `it`: part A finishes the step of forward iteration T - it, part B opens forward iteration T - 1 - it
-    for (int it = 0; it <= T; ++it) {
-      GruStepB g[2];
-      for (int k = 0; k < ndir; ++k) {
-        const bool rev = dirs[k].reverse != 0;
-        const int s_cur = T - it, s_next = T - 1 - it;
-        const int t_cur = it == 0 ? -1 : (rev ? T - 1 - s_cur : s_cur);
-        const int t_next = s_next < 0 ? -1 : (rev ? T - 1 - s_next : s_next);
-        const int tprev = (s_next <= 0) ? -1 : (rev ? t_next + 1 : t_next - 1);
-        g[k] = GruStepB{dirs[k].d_hs, dirs[k].hs, dirs[k].h0, dirs[k].gates, p + (size_t)k * 3 * H * H, dirs[k].d_hn,
-                        carry + (size_t)k * B * H, dirs[k].dgi, dirs[k].dgh, dirs[k].dh0, t_cur, t_next, tprev,
-                        t_next < 0 ? (int64_t)0 : (ro.on ? (int64_t)ro.off[t_next] : (int64_t)t_next * B), ro.on};
-      }
-      if (ndir == 1) g[1] = g[0];
-      if (it == T && !dirs[0].dh0 && (ndir == 1 || !dirs[1].dh0)) break;      // nobody wants the initial-state gradient
-      hipLaunchKernelGGL(gru_step_bwd_kernel, dim3(cdiv(B, 16), Hp >> 4, ndir), dim3(64), 0, st, g[0], g[1], lengths,
-                         d_hs_ld, hs_ld, T, B, H);
-    }
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  // large batch, H == 200: W_hh resident in the CU for the whole sequence (gru_res_bwd_kernel)
-  {
-    const int res_rows = g2v_internal_options().gru_resident_rows;
-    bool res = H == RESB_H && res_rows > 0 && B >= res_rows && g2v_internal_options().gru_resident_bwd && (hs_ld & 3) == 0 &&
-               (d_hs_ld & 3) == 0;
-    for (int k = 0; k < ndir && res; ++k)
-      res = aligned16(dirs[k].gates) && aligned16(dirs[k].dgi) && aligned16(dirs[k].dgh) && aligned16(dirs[k].hs) && aligned16(dirs[k].h0) &&
-            aligned16(dirs[k].dh0) && aligned16(dirs[k].d_hs) && aligned16(dirs[k].d_hn);
-    if (res) {
-      GruResB r[2];
-      for (int k = 0; k < ndir; ++k)
-        r[k] = GruResB{dirs[k].d_hs, dirs[k].d_hn, dirs[k].hs, dirs[k].h0, dirs[k].gates, dirs[k].w_hh, dirs[k].dgi, dirs[k].dgh,
-                       dirs[k].dh0, dirs[k].reverse};
-      if (ndir == 1) r[1] = r[0];
-      (void)hipFuncSetAttribute((const void*)gru_res_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RESB_LDS_BYTES);
-      // (one workgroup per row tile here: with the forward's one-per-CU walk Part d with attention at B = 4096 lost 1.4 % -- the
-      //  side branch's weight gradients wait for a CU until a whole walk is through -- and without attention gained nothing)
-      hipLaunchKernelGGL(gru_res_bwd_kernel, dim3(cdiv(B, 16), ndir), dim3(256), RESB_LDS_BYTES, st, r[0], r[1], lengths, d_hs_ld, hs_ld,
-                         T, B, ro);
-      G2V_CHECK_LAUNCH();
-      return G2V_OK;
-    }
-  }
-  GruGenB g[2];
-  {
-    PackBatch pb;
-    pb.n = 0;
-    for (int k = 0; k < ndir; ++k) {
-      float* wt = p + (size_t)k * pack_floats(H, 1, 3 * H);
-      pb.d[pb.n++] = PackDesc{dirs[k].w_hh, wt, H, 1, 0, 3 * H, H, 1, 0};   // rows k (hidden unit), contraction over the 3H gates
-      g[k] = GruGenB{dirs[k].d_hs, dirs[k].d_hn, dirs[k].hs, dirs[k].h0, dirs[k].gates, wt, dirs[k].dgi, dirs[k].dgh,
-                     dirs[k].dh0, dirs[k].reverse};
-    }
-    launch_pack(pb, st);
-    G2V_CHECK_LAUNCH();
-  }
-  if (ndir == 1) g[1] = g[0];
-  bool v4 = (H & 3) == 0 && H <= 256 && (hs_ld & 3) == 0 && (d_hs_ld & 3) == 0;
-  for (int k = 0; k < ndir && v4; ++k)
-    v4 = aligned16(dirs[k].gates) && aligned16(dirs[k].dgi) && aligned16(dirs[k].dgh) && aligned16(dirs[k].hs) &&
-         aligned16(dirs[k].h0) && aligned16(dirs[k].dh0) && aligned16(dirs[k].d_hs);
-  if (v4)
-    hipLaunchKernelGGL(gru_seq_bwd_kernel<1>, dim3(cdiv(B, 16), ndir), dim3(256), lds, st, g[0], g[1], lengths, d_hs_ld, hs_ld, T,
-                       B, H, ro);
-  else {
-    G2V_REQUIRE(!ro.on, "packed dgi: the scalar generic body does not serve it");
-    hipLaunchKernelGGL(gru_seq_bwd_kernel<0>, dim3(cdiv(B, 16), ndir), dim3(256), lds, st, g[0], g[1], lengths, d_hs_ld, hs_ld, T,
-                       B, H, ro);
+      break;
+    case G2V_GRU_ROUTE_STEP: gru_bwd_launch_steps(c, pl, ws); break;
+    case G2V_GRU_ROUTE_RESIDENT: gru_bwd_launch_resident(c, pl); break;
+    default: gru_bwd_launch_stream(c, pl, ws); break;
   }
   G2V_CHECK_LAUNCH();
   return G2V_OK;
@@ -2772,3 +2768,4 @@ extern "C" int g2v_gru_seq_bwd_prepared(const g2v_gru_dir_bwd* dirs, int ndir, c
                                         g2v_stream_t stream) {
   return gru_seq_bwd_impl(dirs, ndir, lengths, d_hs_ld, hs_ld, T, B, H, workspace, workspace_bytes, stream, H == 64);
 }
+

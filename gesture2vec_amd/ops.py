@@ -540,6 +540,15 @@ def gru_gather_ok(T, B, H, ndir=2) -> bool:
     return bool(_lib_().g2v_gru_seq_gather_ok(int(T), int(B), int(H), int(ndir)))
 
 
+def gru_route(T, B, H, ndir=1, *, backward=False, cluster=-1, resident_rows=-1, resident_bwd=-1, cus=0, facts=()) -> str:
+    """g2v_gru_seq_route as a name: "FAST", "FAST*1" (variant 1), "CLUSTER", "STEP", "RESIDENT", "STREAM", "STREAM*2", ...; "" where
+    the call is refused.  facts: names of G2V_GRU_PLAN_* bits; -1 / cus=0: the bound context's options / the device's CU count."""
+    r = _lib_().g2v_gru_seq_route(int(backward), int(T), int(B), int(H), int(ndir), int(cluster), int(resident_rows), int(resident_bwd),
+                                  int(cus), sum(_lib.CONSTANTS["G2V_GRU_PLAN_" + f] for f in facts))
+    name = {v: k[len("G2V_GRU_ROUTE_"):] for k, v in _lib.CONSTANTS.items() if k.startswith("G2V_GRU_ROUTE_")}.get(r & 0xff, "")
+    return name + (f"*{r >> 8}" if r >> 8 else "")
+
+
 def gru_dirs_fwd(dirs, T, B, H, *, lengths=None, hs_ld=None, row_off=None):
     """dirs: list (1 or 2) of dicts gi, w_hh, b_hh, h0, hs, h_n, gates, reverse -- ONE launch for both directions.
     With gi=None and x, w_ih, b_ih, in_dim given the input projection is fused into the kernel (H == in_dim == 64).

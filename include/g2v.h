@@ -366,8 +366,8 @@ typedef struct {          /* one direction of one layer, forward */
   float* gates;           /* out: (T,B,4H) saved for backward (NULL = inference) */
   int reverse;            /* 0: t = 0..T-1, 1: t = T-1..0                   */
   /* Fused input projection (gi == NULL): gi_t = x_t W_ih^T + b_ih is computed inside the recurrent kernel, one step
-   * ahead of its use (the gi array, its GEMM and its HBM round trip disappear).  Supported for in_dim == H == 64;
-   * otherwise G2V_ERR_UNSUPPORTED and the caller computes gi with g2v_linear_fwd. */
+   * ahead of its use (the gi array, its GEMM and its HBM round trip disappear).  The FAST route with in_dim == H only
+   * (g2v_gru_seq_route below); otherwise G2V_ERR_UNSUPPORTED and the caller computes gi with g2v_linear_fwd. */
   const float* x;         /* (T,B,in_dim) layer input                       */
   const float* w_ih;      /* (3H,in_dim)                                    */
   const float* b_ih;      /* (3H)                                           */
@@ -375,14 +375,14 @@ typedef struct {          /* one direction of one layer, forward */
   /* Packed input projections (round 5; NULL = the (T,B,3H) layout): a HOST array of T row offsets.  gi then holds only the
    * positions inside their sequences, step-major: row (t,b) at gi + (gi_row_off[t] + b) * 3H for b < n_t = #{lengths > t}
    * (lengths sorted descending, as pack_padded_sequence(enforce_sorted) requires; gi_row_off[t] = n_0 + ... + n_{t-1}) -- the
-   * dense product that makes gi runs over sum(lengths) rows instead of T x B.  T <= 64, the generic kernels with H % 4 == 0
-   * (g2v_gru_seq_packed_ok); every direction of the call must carry the same offsets.  hs / gates keep the (T,B,.) layout. */
+   * dense product that makes gi runs over sum(lengths) rows instead of T x B.  Where g2v_gru_seq_packed_ok says so (the rule:
+   * g2v_gru_seq_route below); every direction of the call must carry the same offsets.  hs / gates keep the (T,B,.) layout. */
   G2V_HOST const int32_t* gi_row_off;
   /* Gathered input projections (round 6; NULL = off): gi is a TABLE (V, 3H), and row r of the layout above -- r = t * B + b, or
    * gi_row_off[t] + b when packed -- is gi + gi_gather[r] * 3H.  The encoder the reference feeds straight from nn.Embedding
    * (model/text2embedding_model.py:126-131): the projected table G = E W_ih^T + b_ih is gathered inside the recurrent kernel
-   * instead of being materialised per position.  Served by the W_hh-resident forward only: g2v_gru_seq_gather_ok(T, B, H, ndir);
-   * otherwise G2V_ERR_UNSUPPORTED.  Entries of positions outside their sequences are never read. */
+   * instead of being materialised per position.  Served by the W_hh-resident forward only: g2v_gru_seq_gather_ok(T, B, H, ndir)
+   * (the rule: g2v_gru_seq_route below); otherwise G2V_ERR_UNSUPPORTED.  Entries of positions outside their sequences are never read. */
   const int64_t* gi_gather;
 } g2v_gru_dir;
 int g2v_gru_seq_packed_ok(int T, int B, int H);
@@ -397,8 +397,8 @@ int g2v_gru_seq_gather_ok(int T, int B, int H, int ndir);
  * step) exists for parity tests, A/B measurements and the fall-back after a latched fault.  Returns the previous setting.
  * LEGACY FORWARD = g2v_ctx_set_option(NULL, G2V_OPT_GRU_CLUSTER, enable). */
 int g2v_gru_seq_set_cluster(int enable);
-/* 1: this shape runs as the cluster kernels under the current setting (then g2v_gru_dir_bwd.hn_z .. hn_coef, the fused quantiser
- * backward below, are honoured at H != 64 too) */
+/* 1: an ideal call of this shape runs as CLUSTER under the current setting (g2v_gru_seq_route below; then g2v_gru_dir_bwd.hn_z ..
+ * hn_coef, the fused quantiser backward, are honoured at H != 64 too).  0 at H == 64: that call runs as FAST. */
 int g2v_gru_seq_cluster_ok(int T, int B, int H, int ndir);
 /* A persistent cluster launch (g2v_gru_seq_fwd / _bwd, g2v_dec_rollout_fwd / _bwd at the shapes their *_cluster_ok queries
  * name) clears its exchange records in front of the kernel: a memset of 1-11 MB, 5-12 us on the caller's chain.  A caller that hands
@@ -415,8 +415,63 @@ int g2v_cluster_exchange_preclear(int kind, int T, int B, int D, int H, int ndir
  * would have taken the note, or frees / re-purposes the workspace.  The notes belong to the bound context (g2v_ctx above). */
 int g2v_cluster_exchange_preclear_drop(const void* workspace, size_t workspace_bytes);
 
-/* Up to 2 directions per call run in ONE launch (the two directions of a bidirectional layer are independent). */
-size_t g2v_gru_seq_fwd_workspace(int ndir, int H);   /* W_hh in MFMA fragment order */
+/* Which implementation a g2v_gru_seq_fwd / _bwd call runs on (csrc/gru.hip: gru_route_plan).  Plain
+ * arithmetic on the direction of travel, T, B, H, ndir, three options of the bound context, the device's CU count and the facts
+ * of the call; first match wins.  "Aligned": 16-byte aligned in every direction, NULL counts as aligned.
+ *   FAST      H == 64 and the leading dimensions (hs_ld; backward d_hs_ld too) multiples of 4.  The weights as fragment packs in the
+ *             workspace (g2v_gru_seq_prepare).  The only route that fuses the input projection (gi == NULL) / the input gradient
+ *             (dx != NULL), both with in_dim == H, and the weight gradients (dw_hh ...).  Variant forward: 0, 1 projection fused;
+ *             backward: 0, 1 dx fused, 2 and dW_hh, db_hh, 3 and dW_ih, db_ih.
+ *   CLUSTER   the conditions of STEP, and G2V_OPT_GRU_CLUSTER != 0, 2 <= T <= 2^20, ceil(B/16) * ceil(H/16) * ndir <= CUs, the
+ *             kernel resident with a workgroup per CU: ONE launch for all steps.
+ *   STEP      B <= 1024, ceil(B/16) * ndir <= 128, H % 4 == 0, H <= 256, and aligned forward gi, w_hh, b_hh, h0, gates, h_n,
+ *             workspace; backward gates, dgi, dgh, d_hn, h0, dh0, workspace: one launch per time step.
+ *   RESIDENT  W_hh kept in the CU.  Forward: 192 < H <= 208, B >= G2V_OPT_GRU_RESIDENT_ROWS > 0 and the vector conditions of STREAM.
+ *             Backward: H == 200, B >= G2V_OPT_GRU_RESIDENT_ROWS > 0, G2V_OPT_GRU_RESIDENT_BWD != 0, the leading dimensions
+ *             multiples of 4, aligned gates, dgi, dgh, hs, h0, dh0, d_hs, d_hn.
+ *   STREAM    everything else with at most 160 KB of LDS per workgroup (G2V_ERR_ARG beyond).  Variant 1, the vector body: H % 4 == 0,
+ *             H <= 256, the leading dimensions multiples of 4, aligned forward gi, b_hh, hs, gates; backward gates, dgi, dgh, hs,
+ *             h0, dh0, d_hs.  Variant 2 (forward): two row tiles per workgroup, from ceil(B/32) * ndir >= 192.  Variant 0: the scalar body.
+ * Optional fields, G2V_ERR_UNSUPPORTED off the routes that serve them, before anything is launched:
+ *   gi_gather              RESIDENT (forward) at a shape outside STEP's: g2v_gru_seq_gather_ok
+ *   gi_row_off/dgi_row_off T <= 64, 4 <= H <= 256, H % 4 == 0, H != 64 (g2v_gru_seq_packed_ok), with lengths; not STREAM's scalar body
+ *   gi == NULL, dx         FAST with in_dim == H
+ *   dw_hh ... wslab        FAST with dx; dgh (with dw_ih: dgi too) may then be NULL, nowhere else
+ *   hn_z ...               FAST or CLUSTER, with d_hn, hn_q, hn_gloss and aligned hn_z, hn_q
+ * g2v_gru_seq_route returns G2V_GRU_ROUTE_* with the variant in bits 8 and up, or 0 for a call the entry point refuses.  cluster,
+ * resident_rows, resident_bwd: the three options, -1 = the bound context's; cus <= 0: the device's; facts: an or of G2V_GRU_PLAN_*
+ * (0: the ideal call -- aligned arrays, a workspace of the queried size, lengths given, no optional field).  The queries
+ * g2v_gru_seq_cluster_ok / _gather_ok / _packed_ok are fields of the ideal call's plan. */
+#define G2V_GRU_ROUTE_FAST 1
+#define G2V_GRU_ROUTE_CLUSTER 2
+#define G2V_GRU_ROUTE_STEP 3
+#define G2V_GRU_ROUTE_RESIDENT 4
+#define G2V_GRU_ROUTE_STREAM 5
+#define G2V_GRU_PLAN_SPLIT_UNALIGNED 1     /* an array of STEP's list is not aligned */
+#define G2V_GRU_PLAN_VEC_UNALIGNED 2       /* an array of the vector body's list */
+#define G2V_GRU_PLAN_D_HN_UNALIGNED 4      /* d_hn (the backward RESIDENT's list beyond the vector body's) */
+#define G2V_GRU_PLAN_HS_LD 8               /* hs_ld % 4 != 0 */
+#define G2V_GRU_PLAN_D_HS_LD 16            /* d_hs_ld % 4 != 0 */
+#define G2V_GRU_PLAN_PACKED 32             /* gi_row_off / dgi_row_off is set */
+#define G2V_GRU_PLAN_GATHERED 64           /* gi_gather is set */
+#define G2V_GRU_PLAN_NO_LENGTHS 128        /* lengths == NULL */
+#define G2V_GRU_PLAN_FUSED 256             /* gi == NULL / dx != NULL */
+#define G2V_GRU_PLAN_IN_DIM 512            /* ... with in_dim != H */
+#define G2V_GRU_PLAN_WGRAD_HH 1024         /* dw_hh, db_hh, wslab are set */
+#define G2V_GRU_PLAN_WGRAD_IH 2048         /* dw_ih, db_ih, x are set */
+#define G2V_GRU_PLAN_WGRAD_PARTIAL 4096    /* ... but some direction lacks one of its group */
+#define G2V_GRU_PLAN_HN 8192               /* hn_z is set */
+#define G2V_GRU_PLAN_HN_UNUSABLE 16384     /* ... without d_hn, hn_q or hn_gloss, or hn_z / hn_q not aligned */
+#define G2V_GRU_PLAN_NO_DGI 32768          /* dgi or dgh is NULL */
+#define G2V_GRU_PLAN_PREPARED 65536        /* the *_prepared entry points: FAST launches no pack */
+#define G2V_GRU_PLAN_SMALL_WORKSPACE 131072 /* workspace_bytes below the queried size */
+#define G2V_GRU_PLAN_NOT_RESIDENT 262144   /* the cluster kernel does not fit a CU */
+int g2v_gru_seq_route(int backward, int T, int B, int H, int ndir, int cluster, int resident_rows, int resident_bwd, int cus, int facts);
+
+/* Up to 2 directions per call run in ONE launch (the two directions of a bidirectional layer are independent).  The workspace is
+ * the largest of three regions: the fragment packs (per direction W_hh and W_ih), the per-step launches' state, the cluster
+ * kernels' exchange records (which depend on the device's CU count). */
+size_t g2v_gru_seq_fwd_workspace(int ndir, int H);
 int g2v_gru_seq_fwd(const g2v_gru_dir* dirs, int ndir, const int32_t* lengths, int64_t hs_ld,
                     int T, int B, int H, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
 
@@ -428,20 +483,21 @@ typedef struct {
   float* dgi; float* dgh; float* dh0;         /* outputs (dh0 may be NULL)                          */
   int reverse;
   /* Fused input gradient (dx != NULL): dx (T,B,in_dim) = dgi W_ih is produced by the recurrent kernel itself (a second,
-   * independent MFMA chain next to the dh chain).  in_dim == H == 64 only; otherwise G2V_ERR_UNSUPPORTED and the caller
+   * independent MFMA chain next to the dh chain).  The FAST route with in_dim == H only; otherwise G2V_ERR_UNSUPPORTED and the caller
    * uses g2v_linear_bwd_data on dgi.  Each direction writes its own dx (the caller sums the two directions). */
   const float* w_ih;      /* (3H,in_dim) */
   float* dx;              /* out: (T,B,in_dim), overwritten */
   int in_dim;
-  /* Fused weight gradients (dw_hh != NULL; with the fused input gradient, H == in_dim == 64, every direction alike): the
+  /* Fused weight gradients (dw_hh != NULL; with the fused input gradient on the FAST route, every direction alike;
+   * G2V_ERR_UNSUPPORTED on any other route): the
    * recurrent kernel also accumulates dW_hh = sum dgh^T h_prev, dW_ih = sum dgi^T x and the two bias gradients (overwritten);
-   * dgi / dgh are then neither written nor needed (may be NULL).  x: the layer input (T,B,in_dim); wslab: scratch of
+   * dgh, and with dw_ih dgi too, are then neither written nor needed (may be NULL).  x: the layer input (T,B,in_dim); wslab: scratch of
    * g2v_gru_seq_bwd_wslab_bytes(B, H) bytes PER DIRECTION. */
   const float* x;
   float* dw_hh; float* db_hh; float* dw_ih; float* db_ih;
   float* wslab;
-  /* Optional (hn_z != NULL; the H == 64 fast kernels and the small-batch cluster kernels -- g2v_gru_seq_cluster_ok --,
-   * G2V_ERR_UNSUPPORTED elsewhere): the quantiser's backward (K5', g2v_vq_bwd
+  /* Optional (hn_z != NULL; the FAST and CLUSTER routes of g2v_gru_seq_route, G2V_ERR_UNSUPPORTED on any other, whatever took the
+   * call off them): the quantiser's backward (K5', g2v_vq_bwd
    * with a dense quantised tensor) applied where d_hn is read,
    *   d_hn_effective[b,h] = d_hn[b,h] + hn_gloss[0] * hn_coef * (hn_z[b,h] - hn_q[b,h]),
    * i.e. the straight-through gradient plus the commitment term (model/Autoencoder_VQVAE_model.py:1285-1292) when the final
@@ -454,7 +510,7 @@ typedef struct {
   G2V_HOST const int32_t* dgi_row_off;
 } g2v_gru_dir_bwd;
 size_t g2v_gru_seq_bwd_wslab_bytes(int B, int H);
-size_t g2v_gru_seq_bwd_workspace(int ndir, int H);   /* room for W_hh^T (fragment order) */
+size_t g2v_gru_seq_bwd_workspace(int ndir, int H);   /* the largest of its three regions, as g2v_gru_seq_fwd_workspace */
 int g2v_gru_seq_bwd(const g2v_gru_dir_bwd* dirs, int ndir, const int32_t* lengths, int64_t d_hs_ld, int64_t hs_ld,
                     int T, int B, int H, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
 

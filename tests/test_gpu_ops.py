@@ -14,6 +14,7 @@ from oracle import g2v_oracle as O
 from _f64 import as64, default64
 from _wgrad_shapes import WGRAD_ROUTE_SHAPES, route_name
 from _dec_route_shapes import DEC_ROUTE_SHAPES, route_name as dec_route_name
+from _gru_route_shapes import GRU_ROUTE_SHAPES
 
 pytestmark = pytest.mark.gpu
 
@@ -758,11 +759,14 @@ def test_vq_bwd(ops):
 
 # ----------------------------------------------------------------------------------------------- GRU direction
 @pytest.mark.parametrize("T,B,H", [(34, 32, 64), (20, 8, 50), (5, 19, 200), (12, 37, 64), (4, 530, 50), (3, 6200, 200), (2, 6145, 52),
-                                   (3, 2100, 200)])      # (the last three: the vector bodies, two row tiles / one row tile per workgroup)
+                                   (3, 2100, 200)])      # (the last three: the kernels named below)
 @pytest.mark.parametrize("reverse", [False, True])
 @pytest.mark.parametrize("use_len", [False, True])
 def test_gru_seq(ops, T, B, H, reverse, use_len):
     I = 24
+    want = {(3, 6200, 200): ("RESIDENT", "RESIDENT"), (2, 6145, 52): ("STREAM*2", "STREAM*1"), (3, 2100, 200): ("RESIDENT", "RESIDENT")}
+    if (T, B, H) in want:      # (W_hh resident in the CU; the streaming vector bodies with two row tiles / one row tile per workgroup)
+        assert (ops.gru_route(T, B, H), ops.gru_route(T, B, H, backward=True)) == want[(T, B, H)]
     x = rnd(T, B, I, seed=31)
     w_ih, w_hh = rnd(3 * H, I, seed=32, scale=0.2), rnd(3 * H, H, seed=33, scale=1 / math.sqrt(H))
     b_ih, b_hh = rnd(3 * H, seed=34, scale=0.1), rnd(3 * H, seed=35, scale=0.1)
@@ -836,6 +840,10 @@ def test_gru_resident_kernels_match_the_streaming_kernels(ops, T, B, use_len, pa
     res = {}
     for mode, rows, bwd_on in (("stream", 0, 1), ("resident", 1025, 1), ("resident_fwd_only", 1025, 0)):
         with _lib.Context.current().scoped(gru_resident_rows=rows, gru_resident_bwd=bwd_on):
+            facts = ("PACKED",) if packed else ()
+            stream_fwd = "STREAM*2" if -(-B // 32) * 2 >= 192 else "STREAM*1"      # (two row tiles per workgroup: the B = 4100 case)
+            assert ops.gru_route(T, B, H, 2, facts=facts) == ("RESIDENT" if rows else stream_fwd), mode
+            assert ops.gru_route(T, B, H, 2, backward=True, facts=facts) == ("RESIDENT" if rows and bwd_on else "STREAM*1"), mode
             fw = [dict(gi=gi[k], w_hh=w_hh[k], b_hh=b_hh[k], h0=h0[k], hs=torch.full((T, B, H), 7.0, device=DEV),
                        h_n=torch.empty((B, H), device=DEV), gates=torch.zeros((T, B, 4 * H), device=DEV), reverse=bool(k)) for k in range(2)]
             ops.gru_dirs_fwd(fw, T, B, H, lengths=lens, row_off=row_off)
@@ -872,6 +880,8 @@ def test_gru_gathered_input_projections(ops):
     ids = torch.randint(0, V, (n,), generator=g).to(DEV)
     tables, w_hh, b_hh = [r(V, 3 * H) for _ in range(2)], [r(3 * H, H) for _ in range(2)], [r(3 * H) for _ in range(2)]
     assert ops.gru_gather_ok(T, B, H, 2) and not ops.gru_gather_ok(T, 64, H, 2) and not ops.gru_gather_ok(T, B, 64, 2)
+    assert ops.gru_route(T, B, H, 2, facts=("PACKED", "GATHERED")) == "RESIDENT" and ops.gru_route(T, B, H, 2, facts=("PACKED",)) == "RESIDENT"
+    assert ops.gru_route(T, 64, H, 1, facts=("GATHERED", "NO_LENGTHS")) == "" and ops.gru_route(T, 64, H, 1, facts=("NO_LENGTHS",)) == "CLUSTER"
     outs = []
     for gathered in (False, True):
         dirs = [dict(gi=tables[k] if gathered else tables[k][ids].contiguous(), gi_gather=ids if gathered else None, w_hh=w_hh[k], b_hh=b_hh[k],
@@ -936,9 +946,12 @@ def test_gru_cluster_kernels_equal_the_per_step_launches(ops, T, B, H, ndir, use
 
     assert lib.g2v_dec_rollout_persist_fault(0) == 0
     cur = _lib.Context.current()
+    facts = ("PACKED",) if packed else () if use_len else ("NO_LENGTHS",)
     with cur.scoped(gru_cluster=0):
+        assert ops.gru_route(T, B, H, ndir, facts=facts) == ops.gru_route(T, B, H, ndir, backward=True, facts=facts) == "STEP"
         fw_s, bw_s = run()
     with cur.scoped(gru_cluster=1):
+        assert ops.gru_route(T, B, H, ndir, facts=facts) == ops.gru_route(T, B, H, ndir, backward=True, facts=facts) == "CLUSTER"
         fw_c, bw_c = run()
     assert lib.g2v_dec_rollout_persist_fault(0) == 0, "a bounded wait of the cluster kernels ran out"
     for k in range(ndir):
@@ -960,6 +973,120 @@ def test_gru_cluster_kernels_equal_the_per_step_launches(ops, T, B, H, ndir, use
 
 
 # ----------------------------------------------------------------------------------------------- decoder rollout
+def test_gru_seq_queries_are_fields_of_the_route(ops):
+    """The three older queries and pre-clear kinds 0 / 1 against g2v_gru_seq_route, at the shapes of the route table
+    (tests/_gru_route_shapes.py), under each row's options and at this device's own CU count: each is a field of the plan of the
+    ideal call (aligned arrays, a workspace of the queried size, lengths given, no optional field)."""
+    from gesture2vec_amd import _lib
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    ws = torch.empty(int(max(lib.g2v_gru_seq_fwd_workspace(2, 256), lib.g2v_gru_seq_bwd_workspace(2, 256))), dtype=torch.uint8, device=DEV)
+    seen, met = set(), {False: set(), True: set()}
+    for c in GRU_ROUTE_SHAPES:
+        T, B, H, ndir = c["T"], c["B"], c["H"], c.get("ndir", 2)
+        opts = dict(gru_cluster=c.get("cluster", 1), gru_resident_rows=c.get("resident_rows", 1025), gru_resident_bwd=c.get("resident_bwd", 1))
+        key = (T, B, H, ndir) + tuple(opts.values())
+        if "cus" in c or min(T, B, H) < 1 or ndir > 2 or key in seen:
+            continue
+        seen.add(key)
+        with _lib.Context.current().scoped(**opts):
+            route = {bwd: ops.gru_route(T, B, H, ndir, backward=bwd) for bwd in (False, True)}
+            assert lib.g2v_gru_seq_cluster_ok(T, B, H, ndir) == int(route[False] == "CLUSTER"), (c["name"], route)
+            assert (route[False] == "CLUSTER") == (route[True] == "CLUSTER"), (c["name"], route)
+            assert lib.g2v_gru_seq_gather_ok(T, B, H, ndir) == int(ops.gru_route(T, B, H, ndir, facts=("GATHERED",)) != ""), c["name"]
+            assert bool(lib.g2v_gru_seq_gather_ok(T, B, H, ndir)) == (route[False] == "RESIDENT"), (c["name"], route)
+            packed = ops.gru_route(T, B, H, 1, facts=("PACKED",))
+            assert lib.g2v_gru_seq_packed_ok(T, B, H) == int(packed != ""), c["name"]
+            assert (packed != "") == (T <= 64 and 4 <= H <= 256 and H % 4 == 0 and H != 64), (c["name"], packed)
+            for bwd in (False, True):      # kinds 0 / 1 clear the exchange region of a CLUSTER call and nothing else
+                if H <= 256:
+                    ws.fill_(0xAB)
+                    _lib.check(lib.g2v_cluster_exchange_preclear(int(bwd), T, B, 0, H, ndir, ws.data_ptr(), ws.numel(), st), "preclear")
+                    cleared = int((ws == 0).sum())
+                    assert (cleared > 0) == (route[bwd] == "CLUSTER") and bool((ws[cleared:] == 0xAB).all()), (c["name"], bwd, cleared)
+                    lib.g2v_cluster_exchange_preclear_drop(None, 0)
+                if route[bwd]:
+                    met[bwd].add(route[bwd].split("*")[0])
+    assert met[False] == met[True] == {k[len("G2V_GRU_ROUTE_"):] for k in _lib.CONSTANTS if k.startswith("G2V_GRU_ROUTE_")}, met
+
+
+def _gru_bwd_raw(ops, fields, T, B, H):
+    """g2v_gru_seq_bwd on one direction given as a dict of g2v_gru_dir_bwd fields (tensors, or hn_coef) -> the return code"""
+    from gesture2vec_amd import _lib
+    lib = _lib.load()
+    arr = (_lib.GruDirBwd * 1)()
+    for name, v in fields.items():
+        setattr(arr[0], name, float(v) if name == "hn_coef" else ops._p(v))
+    ws = torch.zeros(int(lib.g2v_gru_seq_bwd_workspace(1, H)), dtype=torch.uint8, device=DEV)
+    rc = lib.g2v_gru_seq_bwd(arr, 1, None, H, H, T, B, H, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return rc
+
+
+def _gru_small_cluster_case(ops, T, B, H):
+    w, bh, gi, h0 = rnd(3 * H, H, seed=1, scale=0.3).to(DEV), rnd(3 * H, seed=2, scale=0.1).to(DEV), rnd(T, B, 3 * H, seed=3).to(DEV), rnd(B, H, seed=4).to(DEV)
+    fw = dict(gi=gi, w_hh=w, b_hh=bh, h0=h0, hs=torch.zeros(T, B, H, device=DEV), h_n=torch.zeros(B, H, device=DEV),
+              gates=torch.zeros(T, B, 4 * H, device=DEV), reverse=False)
+    ops.gru_dirs_fwd([fw], T, B, H)
+    base = dict(d_hs=rnd(T, B, H, seed=5).to(DEV), d_hn=rnd(B, H, seed=6).to(DEV), hs=fw["hs"], h0=h0, gates=fw["gates"], w_hh=w)
+    outs = lambda: dict(dgi=torch.full((T, B, 3 * H), 7.0, device=DEV), dgh=torch.full((T, B, 3 * H), 7.0, device=DEV),
+                        dh0=torch.full((B, H), 7.0, device=DEV))
+    return base, outs
+
+
+def test_gru_bwd_refuses_the_quantiser_fields_off_its_routes(ops):
+    """g2v_gru_dir_bwd.hn_z .. hn_coef at a shape the cluster kernel admits (T = 2, B = 16, H = 8), but with dgi one float off
+    16-byte alignment: the call leaves the split routes for the streaming BPTT, which never reads hn_z -- G2V_ERR_UNSUPPORTED before
+    anything is launched, instead of a result without the straight-through + commitment term.  Aligned, the same call runs and is
+    bitwise the unfused form (g2v_vq_bwd into d_hn first: the same fma per element, as test_gpu_loss_chase.py
+    test_quantiser_backward_inside_the_bptt_kernel_changes_nothing asserts for the H = 64 kernels)."""
+    from gesture2vec_amd import _lib
+    lib = _lib.load()
+    T, B, H, beta = 2, 16, 8, 0.25
+    assert lib.g2v_gru_seq_cluster_ok(T, B, H, 1) == 1
+    facts = ("HN", "NO_LENGTHS")
+    assert ops.gru_route(T, B, H, 1, backward=True, facts=facts) == "CLUSTER" and ops.gru_route(T, B, H, 1, backward=True, facts=facts + ("SPLIT_UNALIGNED",)) == ""
+    assert ops.gru_route(T, B, H, 1, backward=True, facts=("NO_LENGTHS", "SPLIT_UNALIGNED")) == "STREAM*1"
+    base, outs = _gru_small_cluster_case(ops, T, B, H)
+    z, q, gloss = rnd(B, H, seed=7).to(DEV), rnd(B, H, seed=8).to(DEV), torch.tensor([0.7], device=DEV)
+    hn = dict(hn_z=z, hn_q=q, hn_gloss=gloss, hn_coef=2.0 * beta / (B * H))
+    o = outs()
+    buf = torch.full((T * B * 3 * H + 4,), 7.0, device=DEV)
+    off = buf[1:1 + T * B * 3 * H]
+    assert off.data_ptr() % 16 == 4 and all(t.data_ptr() % 16 == 0 for t in (*base.values(), *o.values(), z, q))
+    assert _gru_bwd_raw(ops, dict(base, **hn, dgi=off, dgh=o["dgh"], dh0=o["dh0"]), T, B, H) == _lib.ERR_UNSUPPORTED
+    assert b"fused quantiser backward" in lib.g2v_last_error()
+    for name, t in (("dgi", buf), ("dgh", o["dgh"]), ("dh0", o["dh0"])):
+        assert bool((t == 7.0).all()), f"{name} was written by a refused call"
+    fused, plain = outs(), outs()
+    assert _gru_bwd_raw(ops, dict(base, **hn, **fused), T, B, H) == 0, lib.g2v_last_error()
+    d_hn = ops.vq_bwd(base["d_hn"], gloss, z, q, None, beta)
+    assert _gru_bwd_raw(ops, dict(base, **plain, d_hn=d_hn), T, B, H) == 0, lib.g2v_last_error()
+    assert lib.g2v_dec_rollout_persist_fault(0) == 0
+    for name in ("dgi", "dgh", "dh0"):
+        print(name, "fused vs unfused: max abs difference", float((fused[name] - plain[name]).abs().max()))
+        assert not bool((fused[name] == 7.0).all()) and torch.equal(fused[name], plain[name]), name
+    assert not torch.equal(d_hn, base["d_hn"])
+
+
+def test_gru_bwd_refuses_the_weight_gradient_fields_off_the_fast_route(ops):
+    """dw_hh, db_hh and wslab at H = 8 (a cluster shape; only the H = 64 kernels fuse the weight gradients), with dgi and dgh valid:
+    G2V_ERR_UNSUPPORTED and nothing written, instead of fields that are ignored without a word.  (The dgi == NULL form is a row
+    of the host table, tests/_gru_route_shapes.py: it is not run on a device.)"""
+    from gesture2vec_amd import _lib
+    lib = _lib.load()
+    T, B, H = 2, 16, 8
+    assert ops.gru_route(T, B, H, 1, backward=True, facts=("WGRAD_HH", "NO_LENGTHS")) == "" and ops.gru_route(T, B, H, 1, backward=True) == "CLUSTER"
+    base, outs = _gru_small_cluster_case(ops, T, B, H)
+    o = outs()
+    w = dict(dw_hh=torch.full((3 * H, H), 9.0, device=DEV), db_hh=torch.full((3 * H,), 9.0, device=DEV),
+             wslab=torch.full((int(lib.g2v_gru_seq_bwd_wslab_bytes(B, H)) // 4,), 9.0, device=DEV))
+    assert _gru_bwd_raw(ops, dict(base, **o, **w), T, B, H) == _lib.ERR_UNSUPPORTED
+    assert b"fused weight gradients" in lib.g2v_last_error()
+    assert all(bool((t == 7.0).all()) for t in o.values()) and all(bool((t == 9.0).all()) for t in w.values())
+    assert _gru_bwd_raw(ops, dict(base, **o), T, B, H) == 0 and not bool((o["dgi"] == 7.0).all())
+
+
 def _dec_state(D, H, seed):
     sd = O.init_vqvae_state(D, H, 2, 8, seed=seed)
     pre = "decoder.decoder."
@@ -1693,6 +1820,7 @@ def test_gru_fused_input_projection_matches_unfused():
     lengths[0] = T
     ws = [dict(w_ih=torch.randn(3 * H, H, device=DEV) * 0.2, b_ih=torch.randn(3 * H, device=DEV) * 0.1,
                w_hh=torch.randn(3 * H, H, device=DEV) * 0.2, b_hh=torch.randn(3 * H, device=DEV) * 0.1) for _ in range(2)]
+    assert ops.gru_route(T, B, H, 2) == "FAST" and ops.gru_route(T, B, H, 2, facts=("FUSED",)) == "FAST*1"
     for use_len in (False, True):
         ln = lengths.to(DEV).to(torch.int32) if use_len else None
         outs = {}
@@ -1727,6 +1855,7 @@ def test_gru_bwd_fused_input_gradient_matches_unfused():
     lengths = torch.randint(2, T + 1, (B,)).sort(descending=True).values
     lengths[0] = T
     ln = lengths.to(DEV).to(torch.int32)
+    assert ops.gru_route(T, B, H, 1, backward=True) == "FAST" and ops.gru_route(T, B, H, 1, backward=True, facts=("FUSED",)) == "FAST*1"
     for k in range(2):
         w_ih, b_ih = torch.randn(3 * H, H, device=DEV) * 0.2, torch.randn(3 * H, device=DEV) * 0.1
         w_hh, b_hh = torch.randn(3 * H, H, device=DEV) * 0.2, torch.randn(3 * H, device=DEV) * 0.1
@@ -1779,6 +1908,8 @@ def test_gru_bwd_fused_weight_gradients_match_separate_products(mode):
         dirs_fused.append(f)
         zero = torch.zeros(1, B, H, device=DEV)
         hprevs.append(torch.cat([hs[1:], zero], 0) if k else torch.cat([zero, hs[:-1]], 0))
+    facts = ("FUSED", "WGRAD_HH") + (("WGRAD_IH",) if mode == 2 else ())
+    assert ops.gru_route(T, B, H, 2, backward=True, facts=("FUSED",)) == "FAST*1" and ops.gru_route(T, B, H, 2, backward=True, facts=facts) == f"FAST*{1 + mode}"
     ops.gru_dirs_bwd(dirs_ref, T, B, H, lengths=ln)
     ops.gru_dirs_bwd(dirs_fused, T, B, H, lengths=ln)
     for k in range(2):
