@@ -34,6 +34,9 @@ void g2v_internal_preclear_drop(const void* base, size_t bytes);
 int g2v_internal_persist_enabled();
 // gru.hip -- the exchange region a cluster launch of this shape clears (offset 0 of its workspace); 0: not a cluster shape
 size_t g2v_internal_gru_cluster_region(int T, int B, int H, int ndir, int bwd);
+// vq.hip -- does the plan (vq_route_plan) serve this call of g2v_vq_assign_bulk_z (vq_bulk_z.hip)?  G2V_OK, or the code with *msg set
+constexpr int VQ_BULK_Z_E = 400;            // the width vq_bulk_z.hip is built for
+int g2v_internal_vq_bulk_z_admits(int N, int E, int K, bool aligned, const char** msg);
 // linear.hip
 int g2v_internal_slab_reduce4(const float* const* slab_w, float* const* out_w, const float* const* slab_b, float* const* out_b,
                               int nprob, int64_t n, int64_t nb, int nsplit, hipStream_t st);

@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256) void vq_assign_fast_kernel(const float* __rest
 // RT MFMAs (one per row tile) instead of one, so the L2 traffic of the codebook stream drops RT-fold.  At N = 4096
 // the 16-rows-per-workgroup kernel above is L2-bandwidth-bound (256 workgroups x 256 KB = 64 MB per launch); RT = 2
 // halves that at the price of filling only half the CUs; for bulk assignment (N >= 16384) RT = 4 is MFMA-bound.
-// LIST: the rows to assign are row_list[0 .. *row_count) (the exact re-check of vq_bx3_sweep_kernel's undecided rows); the
+// LIST: the rows to assign are row_list[0 .. *row_count) (the exact re-check of vq_bulk_sweep_kernel's undecided rows); the
 // launch is sized for the worst case and workgroups beyond the count leave at once.  idx only (no quant / dist / SSE).
 template <int E, int RT, bool LIST = false>
 __global__ __launch_bounds__(256) void vq_assign_rt_kernel(const float* __restrict__ flat, const float* __restrict__ z,
@@ -1381,180 +1381,40 @@ extern "C" int g2v_vq_codebook_grad(const float* stats, const float* codebook, c
 // the fp32 matrix peak, i.e. it cannot get faster in fp32).  gfx950's bf16 MFMA moves 16x the FLOPs per cycle, and
 //     x . w  ~=  xh.wh + xh.wl + xl.wh        (xh = bf16(x), xl = bf16(x - xh); same for w)
 // misses only xl.wl and the second-order residuals: |error| <= 3 * 2^-16 * |x||w| + the fp32 accumulation of 3E terms.
-//   vq_bx3_split_kernel   codebook -> Wh, Wl (bf16, row-major), once per call
-//   vq_bx3_sweep_kernel   per row: best code, best and SECOND-best approximate distance; a row whose two best distances are
-//                         closer than margin = 2^-11 |x| max_k|w_k| (> 2x the bound above) is UNDECIDED: its id goes to a list
-//   vq_assign_rt_kernel<128,4,LIST>   the undecided rows again, in exact fp32 (the kernel the training path and the tests use)
+//   vq_bulk_split_kernel  codebook -> Wh, Wl (bf16, row-major) and {-|w_k|^2 / 2, |w_k|} per code, once per call
+//   vq_bulk_sweep_kernel  per row: best code, best and SECOND-best lower bound; a row whose two best are closer than the margin
+//                         (below) is UNDECIDED: its id goes to a list
+//   vq_assign_rt_kernel<128,1,LIST>   the undecided rows again, in exact fp32 (the kernel the training path and the tests use)
 // A decided row's approximate winner beats every other code by more than twice the error bound, so it is the exact-arithmetic
 // argmin as well; an undecided row gets exactly what the fp32 kernel gives.  Cost: 12 bf16 MFMAs (16 cycles) per 16 x 16 x 128
 // tile instead of 32 fp32 ones (32 cycles) = 5.3x fewer matrix cycles, plus the re-check on the undecided fraction.
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
-__global__ __launch_bounds__(256) void vq_bx3_split_kernel(const float* __restrict__ W, const float* __restrict__ wsq,
-                                                           __bf16* __restrict__ Wh, __bf16* __restrict__ Wl,
-                                                           float* __restrict__ wn, int64_t n, int K) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
-    const float w = W[e];
-    const __bf16 h = (__bf16)w;
-    Wh[e] = h;
-    Wl[e] = (__bf16)(w - (float)h);
-  }
-  // |w_k| (rounded up), for the PER-CODE error radius of the sweep
-  for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) wn[k] = sqrtf(wsq[k]) * 1.001f;
-}
-
-// 256 rows per workgroup: wave w owns rows 64 w .. 64 w + 63 (4 row tiles, fragments in registers for the whole sweep) and
-// walks ALL code tiles; the codebook passes through LDS in chunks of 64 codes (hi and lo images, double buffered, fetched
-// from L2 once per workgroup = 1 KiB per row -- with the codebook pulled per wave, as in vq_assign_rt_kernel, this kernel is
-// L2-bandwidth-bound at the fp32 kernel's speed: measured 1.28 vs 1.25 ms for 2^20 rows).
-constexpr int BX3_CODES = 64, BX3_LDW = 128 + 8;       // bf16 elements per LDS row: 272 B, conflict-free ds_read_b128 per 16 lanes
-// (best, second best) per row are kept as floats that carry the code index in their low mantissa bits (kbits = log2 K): one
-// v_and_or packs, med3(d1, d2, p) is the new second best, min(d1, p) the new best -- 3.5 VALU ops per candidate, which fit
-// into the issue slots the bf16 MFMAs leave; the 2^-(23 - kbits) relative truncation is added to the margin.
-// Round 5: the margin is PER CODE.  The sweep ranks LOWER BOUNDS  L_k = e_k - r_k,  r_k = 2^-12 |x| |w_k| (the 3-term split's
-// error bound, x 2 for the -2 x.w, with the same 2x allowance as before); U* = L_a + 2 r_a of the best-ranked code a bounds the
-// row's minimum from above, so the row is decided iff the second-smallest lower bound clears U*.  With the global margin
-// 2^-11 |x| max_k |w_k| a TRAINED codebook -- the EMA update leaves dead codes with norms hundreds of times the live ones' --
-// made every row undecided (all 2^20 rows through the fp32 kernel: 1.7 ms instead of 0.49); per code those are simply far away.
-__global__ __launch_bounds__(256, 2) void vq_bx3_sweep_kernel(const float* __restrict__ flat, const __bf16* __restrict__ Wh,
-                                                              const __bf16* __restrict__ Wl, const float* __restrict__ wsq,
-                                                              const float* __restrict__ wn,
-                                                              int64_t* __restrict__ idx_out, int* __restrict__ und_list,
-                                                              int* __restrict__ und_count, int N, int K, int kbits) {
-  constexpr int E = 128, KB = E / 32, RT = 4;
-  __shared__ __attribute__((aligned(16))) __bf16 Ls[2][2][BX3_CODES * BX3_LDW];      // [buffer][hi / lo][code][k]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, q = lane >> 4;
-  const int r0 = blockIdx.x * 256 + 64 * wave;
-  // ---- this wave's rows as B-operand fragments (hi / lo), straight from global; |x|^2 on the way ---------------------------
-  bf16x8 xh[RT][KB], xl[RT][KB];
-  float xr[RT];
-#pragma unroll
-  for (int t = 0; t < RT; ++t) {
-    const int row = r0 + 16 * t + i;
-    const float* xp = flat + (int64_t)(row < N ? row : N - 1) * E + 8 * q;
-    float ss = 0.f;
-#pragma unroll
-    for (int s = 0; s < KB; ++s) {
-      const float4 a = *reinterpret_cast<const float4*>(xp + 32 * s), b = *reinterpret_cast<const float4*>(xp + 32 * s + 4);
-      const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        xh[t][s][j] = h;
-        xl[t][s][j] = (__bf16)(v[j] - (float)h);
-        ss += v[j] * v[j];
-      }
-    }
-    ss += __shfl_xor(ss, 16);
-    ss += __shfl_xor(ss, 32);
-    xr[t] = ss;
-  }
-  float cx[RT];                                         // 2^-12 |x|
-#pragma unroll
-  for (int t = 0; t < RT; ++t) cx[t] = 2.44140625e-4f * sqrtf(xr[t]);
-  float d1[RT], d2[RT];
-#pragma unroll
-  for (int t = 0; t < RT; ++t) { d1[t] = INFINITY; d2[t] = INFINITY; }
-  const unsigned kmask = (1u << kbits) - 1u;
-  // ---- codebook chunks: thread -> (row tid >> 4 (+16 p), 16-byte piece tid & 15) of the hi and of the lo image -----------
-  const int frow = tid >> 4, fpc = tid & 15;
-  bf16x8 fh[4], fl[4];
-  auto fetch = [&](int c) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int64_t off = (int64_t)(c * BX3_CODES + frow + 16 * p) * E + 8 * fpc;
-      fh[p] = *reinterpret_cast<const bf16x8*>(Wh + off);
-      fl[p] = *reinterpret_cast<const bf16x8*>(Wl + off);
-    }
-  };
-  auto stash = [&](int buf) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      *reinterpret_cast<bf16x8*>(&Ls[buf][0][(frow + 16 * p) * BX3_LDW + 8 * fpc]) = fh[p];
-      *reinterpret_cast<bf16x8*>(&Ls[buf][1][(frow + 16 * p) * BX3_LDW + 8 * fpc]) = fl[p];
-    }
-  };
-  const int nch = K / BX3_CODES;
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  for (int c = 0; c < nch; ++c) {
-    const int buf = c & 1;
-    if (c + 1 < nch) fetch(c + 1);
-#pragma unroll
-    for (int tl = 0; tl < BX3_CODES / 16; ++tl) {
-      bf16x8 wh[KB], wl[KB];
-#pragma unroll
-      for (int s = 0; s < KB; ++s) {
-        wh[s] = *reinterpret_cast<const bf16x8*>(&Ls[buf][0][(16 * tl + i) * BX3_LDW + 32 * s + 8 * q]);
-        wl[s] = *reinterpret_cast<const bf16x8*>(&Ls[buf][1][(16 * tl + i) * BX3_LDW + 32 * s + 8 * q]);
-      }
-      const int c0 = c * BX3_CODES + 16 * tl + 4 * q;
-      const float4 sq = *reinterpret_cast<const float4*>(wsq + c0), nq = *reinterpret_cast<const float4*>(wn + c0);
-      f32x4 acc[RT];
-#pragma unroll
-      for (int t = 0; t < RT; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < KB; ++s) {
-#pragma unroll
-        for (int t = 0; t < RT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[s], xh[t][s], acc[t], 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < RT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[s], xl[t][s], acc[t], 0, 0, 0);
-      }
-#pragma unroll
-      for (int s = 0; s < KB; ++s) {        // the large term last: the small ones are not absorbed by its rounding
-#pragma unroll
-        for (int t = 0; t < RT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[s], xh[t][s], acc[t], 0, 0, 0);
-      }
-      const float sv[4] = {sq.x, sq.y, sq.z, sq.w}, nv[4] = {nq.x, nq.y, nq.z, nq.w};
-#pragma unroll
-      for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float d = (xr[t] + fmaf(-cx[t], nv[r], sv[r])) - 2.0f * acc[t][r];      // the LOWER bound e_k - r_k
-          const float pk = __uint_as_float((__float_as_uint(d) & ~kmask) | (unsigned)(c0 + r));
-          d2[t] = __builtin_amdgcn_fmed3f(d1[t], d2[t], pk);      // d1 <= d2 always: the median is the second smallest
-          d1[t] = fminf(d1[t], pk);                               // a NaN candidate leaves both untouched (minNum)
-        }
-    }
-    if (c + 1 < nch) stash(buf ^ 1);          // buffer buf ^ 1 was last read in iteration c - 1, before the barrier below
-    __syncthreads();
-  }
-  const float trunc = ldexpf(1.0f, kbits - 22);          // 2 x the relative truncation of a packed distance
-#pragma unroll
-  for (int t = 0; t < RT; ++t) {
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {                 // (best, second best) of two disjoint code sets
-      const float e1 = __shfl_xor(d1[t], o), e2 = __shfl_xor(d2[t], o);
-      d2[t] = fminf(fmaxf(d1[t], e1), fminf(d2[t], e2));
-      d1[t] = fminf(d1[t], e1);
-    }
-    const int row = r0 + 16 * t + i;
-    if (q == 0 && row < N) {
-      const int ca = (int)(__float_as_uint(d1[t]) & kmask);
-      idx_out[row] = (int64_t)ca;
-      const float margin = 2.0f * cx[t] * wn[ca < K ? ca : 0] + trunc * fabsf(d2[t]);       // 2 r_a + the packing's truncation
-      // NaN / inf - inf (rows with non-finite distances) compare false: undecided, the exact kernel follows torch.argmin
-      if (!(d2[t] - d1[t] >= margin)) und_list[atomicAdd(und_count, 1)] = row;
-    }
-  }
-}
-
-// ---- round 6: the sweep again, built around what limited vq_bx3_sweep_kernel (profiles/r06_d_bulk_*) ---------------------------
-// That kernel ran 560 us at 2^20 rows against 164 us of bf16 matrix-pipe time: (a) 14 vector instructions per (row, code) value
-// -- with two waves per SIMD the SIMD's issue slots, not its matrix pipe, were the bound --, (b) 72 spilled registers (the
-// codebook chunks passed through 32 staging registers on their way to LDS beside 128 registers of row fragments).  Here:
+// 256 rows per workgroup: wave w owns rows 64 w .. 64 w + 63 (4 row tiles, fragments in registers for the whole sweep) and walks
+// ALL code tiles; the codebook passes through LDS in chunks of 64 codes (hi and lo images, double buffered, fetched from L2 once
+// per workgroup = 1 KiB per row -- pulled per wave, as in vq_assign_rt_kernel, the sweep is L2-bandwidth-bound at the fp32
+// kernel's speed: measured 1.28 vs 1.25 ms for 2^20 rows).
+// (best, second best) per row are kept as floats that carry the code index in their low mantissa bits (kbits = log2 K); the
+// 2^-(23 - kbits) relative truncation is added to the margin.
+// The margin is PER CODE.  The sweep ranks LOWER BOUNDS  L_k = e_k - r_k,  r_k = 2^-12 |x| |w_k| (the 3-term split's error bound,
+// x 2 for the -2 x.w, x 2 allowance); U* = L_a + 2 r_a of the best-ranked code a bounds the row's minimum from above, so the row
+// is decided iff the second-smallest lower bound clears U*.  With a global margin 2^-11 |x| max_k |w_k| a TRAINED codebook -- the
+// EMA update leaves dead codes with norms hundreds of times the live ones' -- made every row undecided (all 2^20 rows through the
+// fp32 kernel: 1.7 ms instead of 0.49); per code those are simply far away.
+// The sweep is built around what limited its round-5 form (profiles/r06_d_bulk_*: 560 us at 2^20 rows against 164 us of bf16
+// matrix-pipe time, from 14 vector instructions per (row, code) value -- with two waves per SIMD the issue slots, not the matrix
+// pipe, were the bound -- and 72 spilled registers: codebook chunks staged through 32 registers beside 128 of row fragments):
 //   * the codebook chunks go global -> LDS by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write, no address
 //     arithmetic in the loop); the LDS image is linear, the 16-byte pieces of a code row XOR-swizzled by the row (source address
 //     and fragment read both: conflict-free ds_read_b128 without padding, which an LDS-DMA destination cannot have);
 //   * everything that is constant per code or per row sits in the ACCUMULATOR'S INITIAL VALUE: acc_0 = -|w_k|^2 / 2 + (c_x / 2) |w_k|
-//     (c_x = 2^-12 |x|: the per-code error radius of round 5), so that the finished accumulator is -L_k / 2 for the lower bound
+//     (c_x = 2^-12 |x|: the per-code error radius), so that the finished accumulator is -L_k / 2 for the lower bound
 //     L_k = e_k - r_k itself -- one fma per value, off the MFMA chain; the codes are ranked by LARGEST accumulator;
 //   * ranking = one v_and_or (code index into the low mantissa bits), one v_med3 (second largest), one v_max: 4 instructions per
 //     value in all, 64 per code tile and wave beside its 48 MFMAs.
-// Decided iff acc_1 - acc_2 >= c_x |w_a| + the packing's truncation (the same rule as before, halved); everything else -- ties,
-// non-finite rows -- goes to the list and gets the fp32 kernel's answer.  A codebook with a non-finite |w_k|^2 sends every row
-// there (flag from the split kernel): a NaN accumulator would otherwise just lose the ranking.
+// Decided iff acc_1 - acc_2 >= c_x |w_a| + the packing's truncation; everything else -- ties, non-finite rows -- goes to the
+// list and gets the fp32 kernel's answer.  A codebook with a non-finite |w_k|^2 sends every row there (flag from the split
+// kernel): a NaN accumulator would otherwise just lose the ranking.
 __global__ __launch_bounds__(256) void vq_bulk_split_kernel(const float* __restrict__ W, const float* __restrict__ wsq,
                                                             __bf16* __restrict__ Wh, __bf16* __restrict__ Wl,
                                                             float2* __restrict__ cst, int* __restrict__ flags, int64_t n, int K) {
@@ -2279,8 +2139,134 @@ __global__ __launch_bounds__(256) void vq_bx_pack_kernel(const float* __restrict
   }
 }
 
-// rows per workgroup: 16 (fill the chip; the codebook stream is then L2-bound), 64 for bulk assignment (MFMA-bound)
-static int vq_rows_per_block(int N) { return N >= 16384 ? 64 : 16; }   // measured: 32 rows at N = 4096 is slower (18.8 vs 13.7 us)
+// ====================================================================================================================
+// Host side of the code assignment.  Which kernel a call runs on is decided in ONE place, vq_route_plan (the rows and every
+// admission rule: include/g2v.h at g2v_vq_assign_route; the measurements behind the row counts: DESIGN.md section 3.5.1).  The
+// entry points validate, collect the facts of the call, plan, and switch into one launcher per route; the *_ok queries plan an
+// ideal call and return a field of the result.
+// ====================================================================================================================
+static bool vq_tuned_shape(int E, int K) { return E == 128 && (K & 127) == 0; }      // the E = 128 kernels: whole 128-code tiles
+struct VqCallFacts {      // what the plan needs to know of ONE call beyond its sizes; the defaults are the queries' ideal call
+  bool aligned = true;    // every array the vector kernels touch as float4s is 16-byte aligned
+  bool frag = true;       // the caller can hold a fragment-major codebook image
+  bool entry = false;     // the route's own entry point was called (G2V_VQ_PLAN_ENTRY)
+};
+struct VqRoutePlan {
+  int route, variant;             // G2V_VQ_ROUTE_* and its variant (g2v.h); route 0: refused with `err` and `msg`
+  int rows_route, rows_variant;   // PROJECT: what runs on the projected rows; every field below is then that route's
+  int tps;                        // SPLIT: code tiles per workgroup
+  int grid[2], block; size_t lds; // of the route's (first) kernel, where this file launches it
+  size_t frag_bytes;              // the fragment-major codebook image the route reads (g2v_vq_pack_codebook)
+  size_t screen_bytes;            // the screening operands: BX's image (g2v_vq_bx_pack), the bulk routes' workspace
+  int err; const char* msg;
+};
+static VqRoutePlan vq_route_plan(int form, int wants, int N, int E, int K, int smallm_rows, const VqCallFacts& f) {
+  VqRoutePlan pl{};
+  auto refuse = [&pl](int err, const char* msg) { pl.route = 0; pl.err = err; pl.msg = msg; return pl; };
+  auto launch = [&pl](int route, int variant, int gx, int gy, int block, size_t lds) {
+    pl.route = route; pl.variant = variant; pl.grid[0] = gx; pl.grid[1] = gy; pl.block = block; pl.lds = lds;
+    return pl;
+  };
+  if (N <= 0 || E <= 0 || K <= 0) return refuse(G2V_ERR_ARG, "non-positive size");
+  const bool tuned = vq_tuned_shape(E, K), bulk_ok = wants == G2V_VQ_WANTS_IDX_BULK;
+  const bool packed_serves = E >= 16 && (E & 15) == 0 && K >= 16 && (K & 15) == 0 &&
+                             ((size_t)64 * (E + 4) + 64 + 2 * 8 * 64 + 64 + 8) * sizeof(float) <= 160 * 1024;
+  if (form == G2V_VQ_FORM_RAW) {
+    if (wants == G2V_VQ_WANTS_FULL && tuned && f.aligned) {
+      if (K <= 512) {
+        launch(G2V_VQ_ROUTE_BX, 0, cdiv(N, VQ_ROWS), 1, 512, 0);
+        pl.screen_bytes = g2v_vq_bx_image_bytes(K, E);
+      } else {
+        launch(G2V_VQ_ROUTE_FUSED, f.frag ? 1 : 0, cdiv(N, VQ_ROWS), 1, 256, 0);
+        pl.frag_bytes = f.frag ? (size_t)K * E * sizeof(float) : 0;
+      }
+      return pl;
+    }
+    if (bulk_ok) {
+      const bool serves = N >= 2048 && N > smallm_rows && E == VQ_BULK_Z_E && K >= 32 && K <= 512 && (K & 15) == 0 && packed_serves;
+      if (serves && f.aligned && (f.entry || N >= G2V_VQ_BULK_Z_MIN_ROWS)) {
+        pl.route = G2V_VQ_ROUTE_BULK_Z;
+        pl.screen_bytes = g2v_vq_assign_bulk_z_workspace(N, E, K);
+        return pl;
+      }
+      if (f.entry)
+        return serves ? refuse(G2V_ERR_UNSUPPORTED, "needs 16-byte aligned z, w_pre, codebook, code_sqnorm and workspace")
+                      : refuse(G2V_ERR_UNSUPPORTED, "needs E == 400, K % 16 == 0 with 32 <= K <= 512, N >= 2048 and N above the context's "
+                                                    "smallm_max_rows (g2v_vq_assign_bulk_z_ok)");
+    }
+    pl = vq_route_plan(G2V_VQ_FORM_ROWS, wants, N, E, K, smallm_rows, VqCallFacts{f.aligned, f.frag, false});
+    if (pl.route) { pl.rows_route = pl.route; pl.rows_variant = pl.variant; pl.route = G2V_VQ_ROUTE_PROJECT; pl.variant = 0; }
+    return pl;
+  }
+  if (bulk_ok) {
+    int kbits = 1;
+    while ((1 << kbits) < K) ++kbits;
+    if (tuned && f.aligned && kbits <= 13 && (f.entry || N >= G2V_VQ_BULK_MIN_ROWS)) {
+      launch(G2V_VQ_ROUTE_BULK, kbits, cdiv(N, 256), 1, 256, 0);
+      pl.screen_bytes = g2v_vq_assign_bulk_workspace(N, E, K);
+      return pl;
+    }
+    if (f.entry)
+      return tuned && f.aligned ? refuse(G2V_ERR_ARG, "codebook larger than 8192 codes")
+                                : refuse(G2V_ERR_UNSUPPORTED, "needs E == 128, K % 128 == 0 and 16-byte aligned operands");
+  } else if (f.entry) {
+    if (!packed_serves || !f.frag) return refuse(G2V_ERR_UNSUPPORTED, "needs E % 16 == 0, K % 16 == 0 (g2v_vq_assign_packed_ok)");
+    if (!f.aligned) return refuse(G2V_ERR_ARG, "16-byte aligned operands");
+  }
+  if (f.entry || (N >= G2V_VQ_PACKED_MIN_ROWS && !tuned && packed_serves && f.frag && f.aligned)) {
+    // row tiles per workgroup: one while there is a CU per tile or two, more for bulk assignment (every fragment then feeds NR tiles)
+    const int nr = N >= G2V_VQ_PACKED_NR4_ROWS ? 4 : (N >= G2V_VQ_PACKED_NR2_ROWS ? 2 : 1);
+    launch(G2V_VQ_ROUTE_PACKED, nr, cdiv(N, 16 * nr), 1, 512,
+           ((size_t)16 * nr * (E + 4) + 16 * nr + 2 * 8 * 16 * nr + 16 * nr + 8) * sizeof(float));
+    pl.frag_bytes = (size_t)K * E * sizeof(float);
+    return pl;
+  }
+  // rows per workgroup: 16 (fill the chip; the codebook stream is then L2-bound), 64 for bulk assignment (MFMA-bound)
+  if (tuned && f.aligned)
+    return N >= G2V_VQ_RT_MIN_ROWS ? launch(G2V_VQ_ROUTE_RT, 4, cdiv(N, 64), 1, 256, 0) : launch(G2V_VQ_ROUTE_FAST, 1, cdiv(N, VQ_ROWS), 1, 256, 0);
+  const int Ep = (E + 15) & ~15, ntile = cdiv(K, 16), nrt = cdiv(N, VQ_ROWS);
+  const size_t lds = (size_t)(VQ_ROWS * (Ep + 4) + 16 + 64 + 64 + 16 + 4) * sizeof(float);
+  if (lds > 160 * 1024) return refuse(G2V_ERR_ARG, "embedding dim too large for LDS");
+  if (nrt <= G2V_VQ_SPLIT_MAX_ROW_TILES && ntile >= G2V_VQ_SPLIT_MIN_CODE_TILES) {
+    // few row tiles: split the codes over workgroups (see vq_assign_split_kernel)
+    int nsplit = ntile / 4;                          // >= one code tile per wave
+    if (nsplit > 8) nsplit = 8;
+    pl.tps = cdiv(ntile, nsplit);
+    nsplit = cdiv(ntile, pl.tps);
+    return launch(G2V_VQ_ROUTE_SPLIT, nsplit, nrt, nsplit, 256, lds);
+  }
+  return launch(G2V_VQ_ROUTE_GENERIC, 0, nrt, 1, 256, lds);
+}
+// the plan of a real call and of the queries' ideal call: the bound context's smallm_max_rows
+static VqRoutePlan vq_plan(int form, int wants, int N, int E, int K, const VqCallFacts& f = VqCallFacts{}) {
+  return vq_route_plan(form, wants, N, E, K, g2v_internal_options().smallm_max_rows, f);
+}
+extern "C" int g2v_vq_assign_route(int form, int wants, int N, int E, int K, int smallm_rows, int facts) {
+  VqCallFacts f;
+  f.aligned = !(facts & G2V_VQ_PLAN_UNALIGNED); f.frag = !(facts & G2V_VQ_PLAN_NO_FRAG); f.entry = facts & G2V_VQ_PLAN_ENTRY;
+  if ((form != G2V_VQ_FORM_ROWS && form != G2V_VQ_FORM_RAW) || wants < G2V_VQ_WANTS_FULL || wants > G2V_VQ_WANTS_IDX_BULK) return 0;
+  const VqRoutePlan pl = vq_route_plan(form, wants, N, E, K, smallm_rows < 0 ? g2v_internal_options().smallm_max_rows : smallm_rows, f);
+  return pl.route ? pl.route | (pl.variant << 8) | (pl.rows_route << 16) | (pl.rows_variant << 24) : 0;
+}
+extern "C" int g2v_vq_assign_packed_ok(int N, int E, int K) {
+  VqCallFacts f;
+  f.entry = true;
+  return vq_plan(G2V_VQ_FORM_ROWS, G2V_VQ_WANTS_FULL, N, E, K, f).route == G2V_VQ_ROUTE_PACKED ? 1 : 0;
+}
+extern "C" int g2v_vq_fused_assign_bx_ok(int N, int E, int K) {
+  return vq_plan(G2V_VQ_FORM_RAW, G2V_VQ_WANTS_FULL, N, E, K).route == G2V_VQ_ROUTE_BX ? 1 : 0;
+}
+// g2v_vq_assign_bulk_z (vq_bulk_z.hip) asks here whether it serves its call: G2V_OK, or the code with *msg set
+int g2v_internal_vq_bulk_z_admits(int N, int E, int K, bool aligned, const char** msg) {
+  const VqRoutePlan pl = vq_plan(G2V_VQ_FORM_RAW, G2V_VQ_WANTS_IDX_BULK, N, E, K, VqCallFacts{aligned, true, true});
+  *msg = pl.msg;
+  return pl.route == G2V_VQ_ROUTE_BULK_Z ? G2V_OK : pl.err;
+}
+extern "C" int g2v_vq_assign_bulk_z_ok(int N, int E, int K) {
+  const char* msg;
+  return g2v_internal_vq_bulk_z_admits(N, E, K, true, &msg) == G2V_OK ? 1 : 0;
+}
+
 // upper bound on the number of SSE partials any path writes for N rows (callers size sse_partial with it)
 extern "C" int g2v_vq_assign_blocks(int N) { return N > 0 ? cdiv(N, VQ_ROWS) : 0; }
 
@@ -2293,149 +2279,142 @@ extern "C" int g2v_vq_code_sqnorm(const float* codebook, float* code_sqnorm, int
   return G2V_OK;
 }
 
+// ---- one launcher per ROWS route (sse_partial: an array of g2v_vq_assign_blocks(N) floats, or NULL) -----------------------------
+struct VqRowsArgs {
+  const float *flat, *z, *codebook, *codebook_frag, *code_sqnorm;
+  int64_t* idx; float *quantized, *dist_min, *sse_partial;
+  int N, E, K; hipStream_t st;
+};
+static void vq_launch_tuned(const VqRoutePlan& pl, const VqRowsArgs& a) {      // RT / FAST
+  if (a.sse_partial && pl.route == G2V_VQ_ROUTE_RT)   // fewer, larger blocks leave the tail of the partial array untouched: zero it
+    (void)hipMemsetAsync(a.sse_partial, 0, sizeof(float) * (size_t)cdiv(a.N, VQ_ROWS), a.st);
+  if (pl.route == G2V_VQ_ROUTE_RT)
+    hipLaunchKernelGGL((vq_assign_rt_kernel<128, 4>), dim3(pl.grid[0]), dim3(pl.block), 0, a.st, a.flat, a.z, a.codebook, a.code_sqnorm, a.idx,
+                       a.quantized, a.dist_min, a.sse_partial, a.N, a.K);
+  else
+    hipLaunchKernelGGL(vq_assign_fast_kernel<128>, dim3(pl.grid[0]), dim3(pl.block), 0, a.st, a.flat, a.z, a.codebook, a.code_sqnorm, a.idx,
+                       a.quantized, a.dist_min, a.sse_partial, a.N, a.K);
+}
+static int vq_launch_split(const VqRoutePlan& pl, const VqRowsArgs& a) {
+  if (pl.lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)vq_assign_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (hipMemsetAsync(a.idx, 0xFF, sizeof(int64_t) * (size_t)a.N, a.st) != hipSuccess) {
+    set_error("g2v_vq_assign_fwd: memset failed");
+    return G2V_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(vq_assign_split_kernel, dim3(pl.grid[0], pl.grid[1]), dim3(pl.block), pl.lds, a.st, a.flat, a.codebook, a.code_sqnorm,
+                     reinterpret_cast<unsigned long long*>(a.idx), a.N, a.E, a.K, pl.tps);
+  G2V_CHECK_LAUNCH();
+  hipLaunchKernelGGL(vq_assign_finish_kernel, dim3(pl.grid[0]), dim3(256), 0, a.st, reinterpret_cast<unsigned long long*>(a.idx), a.z,
+                     a.codebook, a.quantized, a.dist_min, a.sse_partial, a.N, a.E);
+  return G2V_OK;
+}
+static void vq_launch_generic(const VqRoutePlan& pl, const VqRowsArgs& a) {
+  if (pl.lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)vq_assign_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  hipLaunchKernelGGL(vq_assign_kernel, dim3(pl.grid[0]), dim3(pl.block), pl.lds, a.st, a.flat, a.z, a.codebook, a.code_sqnorm, a.idx,
+                     a.quantized, a.dist_min, a.sse_partial, a.N, a.E, a.K);
+}
+template <int NR, int NT>
+static void vq_launch_packed_as(const VqRoutePlan& pl, const VqRowsArgs& a) {
+  if (pl.lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)vq_assign_p_kernel<NR, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  hipLaunchKernelGGL((vq_assign_p_kernel<NR, NT>), dim3(pl.grid[0]), dim3(pl.block), pl.lds, a.st, a.flat, a.z, a.codebook, a.codebook_frag,
+                     a.code_sqnorm, a.idx, a.quantized, a.dist_min, a.sse_partial, a.N, a.E, a.K);
+}
+static void vq_launch_packed(const VqRoutePlan& pl, const VqRowsArgs& a) {
+  if (pl.variant == 4) vq_launch_packed_as<4, 2>(pl, a);
+  else if (pl.variant == 2) vq_launch_packed_as<2, 4>(pl, a);
+  else vq_launch_packed_as<1, 4>(pl, a);
+}
+static int vq_launch_rows(const char* who, const VqRoutePlan& pl, const VqRowsArgs& a) {
+  switch (pl.route) {
+    case G2V_VQ_ROUTE_RT:
+    case G2V_VQ_ROUTE_FAST: vq_launch_tuned(pl, a); break;
+    case G2V_VQ_ROUTE_SPLIT: if (int rc = vq_launch_split(pl, a)) return rc; break;
+    case G2V_VQ_ROUTE_GENERIC: vq_launch_generic(pl, a); break;
+    case G2V_VQ_ROUTE_PACKED: vq_launch_packed(pl, a); break;
+    default: set_error("%s: %s", who, pl.msg ? pl.msg : "no route"); return pl.err ? pl.err : G2V_ERR_UNSUPPORTED;
+  }
+  G2V_CHECK_LAUNCH();
+  return G2V_OK;
+}
+
 extern "C" int g2v_vq_assign_fwd(const float* flat, const float* z, const float* codebook, const float* code_sqnorm,
                                  int64_t* idx, float* quantized, float* dist_min, float* sse_partial, int N, int E,
                                  int K, g2v_stream_t stream) {
   G2V_REQUIRE(flat && codebook && code_sqnorm && idx, "null pointer");
   G2V_REQUIRE(!quantized || z, "z required with quantized");
-  G2V_REQUIRE(N > 0 && E > 0 && K > 0, "non-positive size");
-  if (E == 128 && (K & 127) == 0 && ptr_aligned16(flat) && ptr_aligned16(codebook) && ptr_aligned16(code_sqnorm) &&
-      (!quantized || (ptr_aligned16(z) && ptr_aligned16(quantized)))) {
-    const int rows = vq_rows_per_block(N);
-    hipStream_t st = (hipStream_t)stream;
-    if (sse_partial && rows > VQ_ROWS) {   // fewer, larger blocks leave the tail of the partial array untouched: zero it
-      (void)hipMemsetAsync(sse_partial, 0, sizeof(float) * (size_t)cdiv(N, VQ_ROWS), st);
-    }
-    if (rows == 64)
-      hipLaunchKernelGGL((vq_assign_rt_kernel<128, 4>), dim3(cdiv(N, 64)), dim3(256), 0, st, flat, z, codebook,
-                         code_sqnorm, idx, quantized, dist_min, sse_partial, N, K);
-    else
-      hipLaunchKernelGGL(vq_assign_fast_kernel<128>, dim3(cdiv(N, VQ_ROWS)), dim3(256), 0, st, flat, z, codebook,
-                         code_sqnorm, idx, quantized, dist_min, sse_partial, N, K);
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  const int Ep = (E + 15) & ~15;
-  const size_t lds = (size_t)(VQ_ROWS * (Ep + 4) + 16 + 64 + 64 + 16 + 4) * sizeof(float);
-  G2V_REQUIRE(lds <= 160 * 1024, "embedding dim too large for LDS");
-  {
-    // few row tiles: split the codes over workgroups (see vq_assign_split_kernel)
-    const int ntile = cdiv(K, 16), nrt = cdiv(N, VQ_ROWS);
-    if (nrt <= 64 && ntile >= 8) {
-      int nsplit = ntile / 4;                          // >= one code tile per wave
-      if (nsplit > 8) nsplit = 8;
-      const int tps = cdiv(ntile, nsplit);
-      nsplit = cdiv(ntile, tps);
-      hipStream_t st = (hipStream_t)stream;
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)vq_assign_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (hipMemsetAsync(idx, 0xFF, sizeof(int64_t) * (size_t)N, st) != hipSuccess) {
-        set_error("g2v_vq_assign_fwd: memset failed");
-        return G2V_ERR_LAUNCH;
-      }
-      hipLaunchKernelGGL(vq_assign_split_kernel, dim3(nrt, nsplit), dim3(256), lds, st, flat, codebook, code_sqnorm,
-                         reinterpret_cast<unsigned long long*>(idx), N, E, K, tps);
-      G2V_CHECK_LAUNCH();
-      hipLaunchKernelGGL(vq_assign_finish_kernel, dim3(nrt), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(idx), z, codebook,
-                         quantized, dist_min, sse_partial, N, E);
-      G2V_CHECK_LAUNCH();
-      return G2V_OK;
-    }
-  }
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vq_assign_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(vq_assign_kernel, dim3(cdiv(N, VQ_ROWS)), dim3(256), lds, (hipStream_t)stream, flat, z, codebook,
-                     code_sqnorm, idx, quantized, dist_min, sse_partial, N, E, K);
-  G2V_CHECK_LAUNCH();
-  return G2V_OK;
+  VqCallFacts f;
+  f.aligned = ptr_aligned16(flat) && ptr_aligned16(codebook) && ptr_aligned16(code_sqnorm) &&
+              (!quantized || (ptr_aligned16(z) && ptr_aligned16(quantized)));
+  f.frag = false;
+  return vq_launch_rows(__func__, vq_plan(G2V_VQ_FORM_ROWS, quantized ? G2V_VQ_WANTS_FULL : G2V_VQ_WANTS_IDX, N, E, K, f),
+                        VqRowsArgs{flat, z, codebook, nullptr, code_sqnorm, idx, quantized, dist_min, sse_partial, N, E, K, (hipStream_t)stream});
 }
 
-// g2v_vq_assign_fwd on the fragment-major codebook image of g2v_vq_pack_codebook (K * E floats), any E % 16 == 0, K % 16 == 0:
-// the same outputs bit for bit (vq_assign_p_kernel above).
-extern "C" int g2v_vq_assign_packed_ok(int N, int E, int K) {
-  return (N > 0 && E >= 16 && (E & 15) == 0 && K >= 16 && (K & 15) == 0 &&
-          ((size_t)64 * (E + 4) + 64 + 2 * 8 * 64 + 64 + 8) * sizeof(float) <= 160 * 1024) ? 1 : 0;
-}
+// g2v_vq_assign_fwd on the fragment-major codebook image of g2v_vq_pack_codebook (K * E floats): the same outputs bit for bit
+// (vq_assign_p_kernel above).
 extern "C" int g2v_vq_assign_packed_fwd(const float* flat, const float* z, const float* codebook, const float* codebook_frag,
                                         const float* code_sqnorm, int64_t* idx, float* quantized, float* dist_min,
                                         float* sse_partial, int N, int E, int K, g2v_stream_t stream) {
   G2V_REQUIRE(flat && codebook && codebook_frag && code_sqnorm && idx, "null pointer");
   G2V_REQUIRE(!quantized || z, "z required with quantized");
-  if (!g2v_vq_assign_packed_ok(N, E, K)) {
-    set_error("g2v_vq_assign_packed_fwd: needs E %% 16 == 0, K %% 16 == 0 (g2v_vq_assign_packed_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
-  G2V_REQUIRE(ptr_aligned16(flat) && ptr_aligned16(codebook_frag) && ptr_aligned16(code_sqnorm), "16-byte aligned operands");
-  hipStream_t st = (hipStream_t)stream;
-  // row tiles per workgroup: one while there is a CU per tile or two, more for bulk assignment (every fragment then feeds NR tiles)
-  const int nr = N >= 32768 ? 4 : (N >= 8192 ? 2 : 1);
-  const size_t lds = ((size_t)16 * nr * (E + 4) + 16 * nr + 2 * 8 * 16 * nr + 16 * nr + 8) * sizeof(float);
-#define G2V_VQP(NR_, NT_)                                                                                                  \
-  do {                                                                                                                     \
-    if (lds > 48 * 1024)                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)vq_assign_p_kernel<NR_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((vq_assign_p_kernel<NR_, NT_>), dim3(cdiv(N, 16 * NR_)), dim3(512), lds, st, flat, z, codebook,     \
-                       codebook_frag, code_sqnorm, idx, quantized, dist_min, sse_partial, N, E, K);                        \
-  } while (0)
-  if (nr == 4) G2V_VQP(4, 2);
-  else if (nr == 2) G2V_VQP(2, 4);
-  else G2V_VQP(1, 4);
-#undef G2V_VQP
-  G2V_CHECK_LAUNCH();
-  return G2V_OK;
+  VqCallFacts f;
+  f.aligned = ptr_aligned16(flat) && ptr_aligned16(codebook_frag) && ptr_aligned16(code_sqnorm);
+  f.entry = true;
+  return vq_launch_rows(__func__, vq_plan(G2V_VQ_FORM_ROWS, quantized ? G2V_VQ_WANTS_FULL : G2V_VQ_WANTS_IDX, N, E, K, f),
+                        VqRowsArgs{flat, z, codebook, codebook_frag, code_sqnorm, idx, quantized, dist_min, sse_partial, N, E, K, (hipStream_t)stream});
 }
 
+// workspace of g2v_vq_assign_bulk: [hi image][lo image][counters][{-|w_k|^2 / 2, |w_k|} per code: 2 K floats in two padded
+// regions of K][list of undecided rows], every region but the last padded to 256 B
+struct VqBulkWs {
+  __bf16 *Wh, *Wl; int* count; float2* wn; int* list;
+  size_t bytes;
+  VqBulkWs(void* workspace, int N, int E, int K) {
+    const size_t half = ((size_t)K * E * 2 + 255) & ~(size_t)255, kpad = ((size_t)K * 4 + 255) & ~(size_t)255;
+    char* w = (char*)workspace;
+    Wh = (__bf16*)w;
+    Wl = (__bf16*)(w + half);
+    count = (int*)(w + 2 * half);              // [0] undecided rows, [1] the codebook has a non-finite code
+    wn = (float2*)(w + 2 * half + 256);
+    list = (int*)(w + 2 * half + 256 + 2 * kpad);
+    bytes = 2 * half + 256 + 2 * kpad + (size_t)N * 4;
+  }
+};
 extern "C" size_t g2v_vq_assign_bulk_workspace(int N, int E, int K) {
-  if (N <= 0 || E <= 0 || K <= 0) return 0;
-  // [hi image][lo image][counters][|w_k|][-|w_k|^2 / 2][list of undecided rows]
-  return 2 * (((size_t)K * E * 2 + 255) & ~(size_t)255) + 256 + 2 * (((size_t)K * 4 + 255) & ~(size_t)255) + (size_t)N * 4;
+  return (N <= 0 || E <= 0 || K <= 0) ? 0 : VqBulkWs(nullptr, N, E, K).bytes;
 }
 
 // idx[n] = argmin_k |flat[n] - W[k]|^2 for MANY rows (bulk latent -> code assignment): bf16 split screening + exact fp32
-// re-check of the undecided rows (see vq_bx3_sweep_kernel).  undecided (device int, may be NULL) receives their count.
+// re-check of the undecided rows (see vq_bulk_sweep_kernel).  undecided (device int, may be NULL) receives their count.
 extern "C" int g2v_vq_assign_bulk(const float* flat, const float* codebook, const float* code_sqnorm, int64_t* idx, int N,
                                   int E, int K, void* workspace, size_t workspace_bytes, int* undecided,
                                   g2v_stream_t stream) {
   G2V_REQUIRE(flat && codebook && code_sqnorm && idx && workspace, "null pointer");
-  G2V_REQUIRE(N > 0 && E > 0 && K > 0, "non-positive size");
-  if (!(E == 128 && (K & 127) == 0 && ptr_aligned16(flat) && ptr_aligned16(codebook) && ptr_aligned16(code_sqnorm) &&
-        ptr_aligned16(workspace))) {
-    set_error("g2v_vq_assign_bulk: needs E == 128, K %% 128 == 0 and 16-byte aligned operands");
-    return G2V_ERR_UNSUPPORTED;
+  VqCallFacts f;
+  f.aligned = ptr_aligned16(flat) && ptr_aligned16(codebook) && ptr_aligned16(code_sqnorm) && ptr_aligned16(workspace);
+  f.entry = true;
+  const VqRoutePlan pl = vq_plan(G2V_VQ_FORM_ROWS, G2V_VQ_WANTS_IDX_BULK, N, E, K, f);
+  if (pl.route != G2V_VQ_ROUTE_BULK) {
+    set_error("%s: %s", __func__, pl.msg);
+    return pl.err;
   }
-  if (workspace_bytes < g2v_vq_assign_bulk_workspace(N, E, K)) {
+  if (workspace_bytes < pl.screen_bytes) {
     set_error("g2v_vq_assign_bulk: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  const size_t half = ((size_t)K * E * 2 + 255) & ~(size_t)255;
-  char* w = (char*)workspace;
-  __bf16* Wh = (__bf16*)w;
-  __bf16* Wl = (__bf16*)(w + half);
-  int* count = (int*)(w + 2 * half);
-  const size_t kpad = ((size_t)K * 4 + 255) & ~(size_t)255;
-  float* wn = (float*)(w + 2 * half + 256);
-  float* msv = (float*)(w + 2 * half + 256 + kpad);
-  int* list = (int*)(w + 2 * half + 256 + 2 * kpad);
-  (void)hipMemsetAsync(count, 0, 2 * sizeof(int), st);        // [0] undecided rows, [1] the codebook has a non-finite code
-  int kbits = 1;
-  while ((1 << kbits) < K) ++kbits;
-  G2V_REQUIRE(kbits <= 13, "codebook larger than 8192 codes");
-#ifdef G2V_BULK_SWEEP_R5        // A/B build: the round-5 sweep (gpurun_tools/r06_bulk_ab.sh)
-  hipLaunchKernelGGL(vq_bx3_split_kernel, dim3(cdiv((int64_t)K * E, 256)), dim3(256), 0, st, codebook, code_sqnorm, Wh, Wl, wn,
-                     (int64_t)K * E, K);
-  hipLaunchKernelGGL(vq_bx3_sweep_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, flat, Wh, Wl, code_sqnorm, wn, idx, list, count, N,
-                     K, kbits);
-#else
-  (void)msv;
-  hipLaunchKernelGGL(vq_bulk_split_kernel, dim3(cdiv((int64_t)K * E, 256)), dim3(256), 0, st, codebook, code_sqnorm, Wh, Wl, (float2*)wn,
-                     count, (int64_t)K * E, K);          // (wn .. : 2 K floats, {-|w_k|^2 / 2, |w_k|} per code)
-  hipLaunchKernelGGL(vq_bulk_sweep_kernel, dim3(cdiv(N, 256)), dim3(256), 0, st, flat, Wh, Wl, (const float2*)wn, idx, list, count, N, K,
-                     kbits);
-#endif
+  const VqBulkWs ws(workspace, N, E, K);
+  (void)hipMemsetAsync(ws.count, 0, 2 * sizeof(int), st);
+  hipLaunchKernelGGL(vq_bulk_split_kernel, dim3(cdiv((int64_t)K * E, 256)), dim3(256), 0, st, codebook, code_sqnorm, ws.Wh, ws.Wl, ws.wn,
+                     ws.count, (int64_t)K * E, K);
+  hipLaunchKernelGGL(vq_bulk_sweep_kernel, dim3(pl.grid[0]), dim3(pl.block), 0, st, flat, ws.Wh, ws.Wl, (const float2*)ws.wn, idx, ws.list,
+                     ws.count, N, K, pl.variant /* bits of a code index */);
   hipLaunchKernelGGL((vq_assign_rt_kernel<128, 1, true>), dim3(min(cdiv(N, 16), 2048)), dim3(256), 0, st, flat, (const float*)nullptr,
-                     codebook, code_sqnorm, idx, (float*)nullptr, (float*)nullptr, (float*)nullptr, N, K, list, count);
-  if (undecided) (void)hipMemcpyAsync(undecided, count, sizeof(int), hipMemcpyDeviceToDevice, st);
+                     codebook, code_sqnorm, idx, (float*)nullptr, (float*)nullptr, (float*)nullptr, N, K, ws.list, ws.count);
+  if (undecided) (void)hipMemcpyAsync(undecided, ws.count, sizeof(int), hipMemcpyDeviceToDevice, st);
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
@@ -2445,7 +2424,7 @@ extern "C" int g2v_vq_fused_assign_fwd(const float* z, const float* w_pre, const
                                        float* sse_partial, int N, int E, int K, g2v_stream_t stream) {
   G2V_REQUIRE(z && w_pre && b_pre && codebook && code_sqnorm && flat_out && idx && quantized, "null pointer");
   G2V_REQUIRE(N > 0 && E > 0 && K > 0, "non-positive size");
-  if (!(E == 128 && (K & 127) == 0 && ptr_aligned16(z) && ptr_aligned16(w_pre) && ptr_aligned16(b_pre) &&
+  if (!(vq_tuned_shape(E, K) && ptr_aligned16(z) && ptr_aligned16(w_pre) && ptr_aligned16(b_pre) &&
         ptr_aligned16(codebook) && ptr_aligned16(code_sqnorm) && ptr_aligned16(flat_out) && ptr_aligned16(quantized))) {
     set_error("g2v_vq_fused_assign_fwd: needs E == 128, K %% 128 == 0 and 16-byte aligned operands");
     return G2V_ERR_UNSUPPORTED;
@@ -2484,7 +2463,7 @@ extern "C" int g2v_vq_fused_assign_packed_fwd(const float* z, const float* w_pre
                                               g2v_stream_t stream) {
   G2V_REQUIRE(z && w_pre && b_pre && codebook && codebook_frag && code_sqnorm && flat_out && idx && quantized, "null pointer");
   G2V_REQUIRE(N > 0 && E > 0 && K > 0, "non-positive size");
-  if (!(E == 128 && (K & 127) == 0 && ptr_aligned16(z) && ptr_aligned16(w_pre) && ptr_aligned16(b_pre) &&
+  if (!(vq_tuned_shape(E, K) && ptr_aligned16(z) && ptr_aligned16(w_pre) && ptr_aligned16(b_pre) &&
         ptr_aligned16(codebook) && ptr_aligned16(codebook_frag) && ptr_aligned16(code_sqnorm) && ptr_aligned16(flat_out) &&
         ptr_aligned16(quantized))) {
     set_error("g2v_vq_fused_assign_packed_fwd: needs E == 128, K %% 128 == 0 and 16-byte aligned operands");
@@ -2496,14 +2475,19 @@ extern "C" int g2v_vq_fused_assign_packed_fwd(const float* z, const float* w_pre
   return G2V_OK;
 }
 
-static inline size_t bx_pad256(size_t n) { return (n + 255) & ~(size_t)255; }
 // image layout: [U fragments, bf16: K * E * 2][s'_k: K floats][P_k / Q_k packed: K words][scalars], each part padded to 256 B
-extern "C" size_t g2v_vq_bx_image_bytes(int K, int E) {
-  if (K <= 0 || E <= 0) return 0;
-  return bx_pad256((size_t)K * E * 2) + 2 * bx_pad256((size_t)K * 4) + 256;
-}
-
-extern "C" int g2v_vq_fused_assign_bx_ok(int N, int E, int K) { return (N > 0 && E == 128 && (K & 127) == 0 && K >= 128 && K <= 512) ? 1 : 0; }
+struct VqBxImage {
+  __bf16* Uhf; float* sprime; unsigned* pqk; BxfScalars* scal;
+  size_t bytes;
+  VqBxImage(const void* image, int K, int E) {
+    auto pad256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t o1 = pad256((size_t)K * E * 2), o2 = o1 + pad256((size_t)K * 4), o3 = o2 + pad256((size_t)K * 4);
+    char* p = (char*)image;
+    Uhf = (__bf16*)p; sprime = (float*)(p + o1); pqk = (unsigned*)(p + o2); scal = (BxfScalars*)(p + o3);
+    bytes = o3 + 256;
+  }
+};
+extern "C" size_t g2v_vq_bx_image_bytes(int K, int E) { return (K <= 0 || E <= 0) ? 0 : VqBxImage(nullptr, K, E).bytes; }
 
 extern "C" int g2v_vq_bx_pack(const float* codebook, const float* code_sqnorm, const float* w_pre, const float* b_pre, void* image,
                               int K, int E, g2v_stream_t stream) {
@@ -2513,7 +2497,7 @@ extern "C" int g2v_vq_bx_pack(const float* codebook, const float* code_sqnorm, c
     return G2V_ERR_UNSUPPORTED;
   }
   G2V_REQUIRE(ptr_aligned16(codebook) && ptr_aligned16(image), "16-byte aligned operands");
-  const size_t o1 = bx_pad256((size_t)K * E * 2), o2 = o1 + bx_pad256((size_t)K * 4), o3 = o2 + bx_pad256((size_t)K * 4);
+  const VqBxImage im(image, K, E);
   const size_t pack_lds = ((size_t)E * (E + 1) + 2 * 16 * (E + 4)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
@@ -2524,7 +2508,7 @@ extern "C" int g2v_vq_bx_pack(const float* codebook, const float* code_sqnorm, c
     attr_set = true;
   }
   hipLaunchKernelGGL(vq_bx_pack_kernel, dim3(K / 16), dim3(256), pack_lds, (hipStream_t)stream, codebook, code_sqnorm, w_pre, b_pre,
-                     (__bf16*)image, (float*)((char*)image + o1), (unsigned*)((char*)image + o2), (BxfScalars*)((char*)image + o3), K);
+                     im.Uhf, im.sprime, im.pqk, im.scal, K);
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
@@ -2541,17 +2525,14 @@ extern "C" int g2v_vq_fused_assign_bx_fwd(const float* z, const float* w_pre_fra
     set_error("g2v_vq_fused_assign_bx_fwd: needs E == 128, K in {128, 256, 384, 512} and 16-byte aligned operands");
     return G2V_ERR_UNSUPPORTED;
   }
-  const size_t o1 = bx_pad256((size_t)K * E * 2), o2 = o1 + bx_pad256((size_t)K * 4), o3 = o2 + bx_pad256((size_t)K * 4);
-  if (flags & G2V_VQ_BX_EXACT)
-    hipLaunchKernelGGL(vq_fused_bx_exact_kernel, dim3(cdiv(N, VQ_ROWS)), dim3(512), 0, (hipStream_t)stream, z, w_pre_frag, b_pre,
-                       codebook, (const __bf16*)image, (const float*)((const char*)image + o1),
-                       (const unsigned*)((const char*)image + o2), (const BxfScalars*)((const char*)image + o3), code_sqnorm,
-                       flat_out, idx, quantized, sse_partial, diag, N, K);
-  else
-    hipLaunchKernelGGL(vq_fused_bx_kernel, dim3(cdiv(N, VQ_ROWS)), dim3(512), 0, (hipStream_t)stream, z, w_pre_frag, b_pre,
-                       codebook, (const __bf16*)image, (const float*)((const char*)image + o1),
-                       (const unsigned*)((const char*)image + o2), (const BxfScalars*)((const char*)image + o3), code_sqnorm,
-                       flat_out, idx, quantized, sse_partial, diag, N, K);
+  const VqBxImage im(image, K, E);
+#define G2V_VQ_BX(kernel_)                                                                                                 \
+  hipLaunchKernelGGL(kernel_, dim3(cdiv(N, VQ_ROWS)), dim3(512), 0, (hipStream_t)stream, z, w_pre_frag, b_pre, codebook,   \
+                     (const __bf16*)im.Uhf, (const float*)im.sprime, (const unsigned*)im.pqk, (const BxfScalars*)im.scal,  \
+                     code_sqnorm, flat_out, idx, quantized, sse_partial, diag, N, K)
+  if (flags & G2V_VQ_BX_EXACT) G2V_VQ_BX(vq_fused_bx_exact_kernel);
+  else G2V_VQ_BX(vq_fused_bx_kernel);
+#undef G2V_VQ_BX
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }

@@ -47,7 +47,7 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bz_bf16x8;
 
-constexpr int BZ_E = 400;                   // the shipped width: hidden_size 200 x n_layers 2
+constexpr int BZ_E = VQ_BULK_Z_E;           // the shipped width: hidden_size 200 x n_layers 2
 constexpr int BZ_EP = 416;                  // k zero-padded to 13 k-blocks of 32
 constexpr int BZ_KB = BZ_EP / 32;
 constexpr int BZ_PIECES = BZ_EP / 8;        // 16-byte pieces per code row: 52
@@ -377,11 +377,6 @@ inline size_t bz_pad(size_t n) { return (n + 255) & ~(size_t)255; }
 
 using namespace g2v;
 
-extern "C" int g2v_vq_assign_bulk_z_ok(int N, int E, int K) {
-  return (N >= 2048 && N > g2v_internal_options().smallm_max_rows && E == BZ_E && K >= 32 && K <= 512 && (K & 15) == 0 &&
-          g2v_vq_assign_packed_ok(N, E, K)) ? 1 : 0;
-}
-
 extern "C" size_t g2v_vq_assign_bulk_z_workspace(int N, int E, int K) {
   if (N <= 0 || E <= 0 || K <= 0) return 0;
   const size_t Kp = (size_t)round_up(K, BZ_CH);
@@ -394,16 +389,12 @@ extern "C" int g2v_vq_assign_bulk_z(const float* z, const float* w_pre, const fl
                                     size_t workspace_bytes, int* undecided, g2v_stream_t stream) {
   G2V_REQUIRE(z && w_pre && b_pre && codebook && code_sqnorm && idx && workspace, "null pointer");
   G2V_REQUIRE(N > 0 && E > 0 && K > 0, "non-positive size");
-  if (!g2v_vq_assign_bulk_z_ok(N, E, K)) {
-    set_error("g2v_vq_assign_bulk_z: needs E == 400, K %% 16 == 0 with 32 <= K <= 512, N >= 2048 and N above the context's "
-              "smallm_max_rows (g2v_vq_assign_bulk_z_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
   const uintptr_t mis = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(w_pre) | reinterpret_cast<uintptr_t>(codebook) |
                         reinterpret_cast<uintptr_t>(code_sqnorm) | reinterpret_cast<uintptr_t>(workspace);
-  if (mis & 15) {
-    set_error("g2v_vq_assign_bulk_z: needs 16-byte aligned z, w_pre, codebook, code_sqnorm and workspace");
-    return G2V_ERR_UNSUPPORTED;
+  const char* why = nullptr;
+  if (const int rc = g2v_internal_vq_bulk_z_admits(N, E, K, (mis & 15) == 0, &why)) {      // the plan's BULK_Z row (vq.hip)
+    set_error("g2v_vq_assign_bulk_z: %s", why);
+    return rc;
   }
   if (workspace_bytes < g2v_vq_assign_bulk_z_workspace(N, E, K)) {
     set_error("g2v_vq_assign_bulk_z: workspace too small");

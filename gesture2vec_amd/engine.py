@@ -180,11 +180,13 @@ class VQVAEEngine:
         self.ema_w = qz(K, E)
         self.ema_cs = qz(K)
         self.code_sqnorm = qz(K)
-        # What the fused assign kernels read besides the codebook itself, all DERIVED from (codebook, pre_linear) by vq_derive():
-        #   bf16-screened kernel (g2v_vq_fused_assign_bx_fwd, where g2v_vq_fused_assign_bx_ok says so: E == 128, K in {128..512}):
-        #     pre_linear's weight as fp32 MFMA fragments + the screening image (bf16 fragments of U = W w_pre, s'_k, norm bounds);
-        #   fp32 kernel (every other shape): fragment-major image of the codebook.
-        self._vq_bx = vq and bool(self.lib.g2v_vq_fused_assign_bx_ok(1, self.E, K))
+        # Which kernels quantise a batch is g2v_vq_assign_route's answer, taken once per batch size in buffers().
+        # What they read besides the codebook itself is DERIVED from (codebook, pre_linear) by vq_derive(); which image that is
+        # does not depend on the rows beyond PACKED's row count, so the answer at the largest row count names it for every batch:
+        #   BX: pre_linear's weight as fp32 MFMA fragments + the screening image (bf16 fragments of U = W w_pre, s'_k, norm bounds);
+        #   FUSED, PROJECT>PACKED: the fragment-major image of the codebook;  any other PROJECT: nothing.
+        self._vq_image_route = ops.vq_route("RAW", "FULL", 2 ** 31 - 1, self.E, K) if vq else ""
+        self._vq_bx = self._vq_image_route == "BX"
         # custom_loss by the CHASER kernel beside the persistent forward rollout + the backward rollout's own tile load
         # (include/g2v.h: g2v_custom_loss_chase, g2v_dec_saved.loss_*) instead of its own launch between the rollouts, wherever the
         # fused train step runs its parallel branches and g2v_dec_rollout_fuses_loss says so.  Bitwise the same gradients.
@@ -200,12 +202,7 @@ class VQVAEEngine:
         self.vq_diag = torch.zeros(4, dtype=torch.int32, device=dev)          # [0] tiles on the exact sweep, [1] pairs re-evaluated
         self._vq_diag_on = False
         self.codebook_frag = (torch.zeros(K * self.E, device=dev)
-                              if (vq and self.E == 128 and K % 128 == 0 and not self._vq_bx) else None)
-        # every other shape the packed kernel serves (E = 400: the reference's own): pre_linear as a dense launch + the eight-wave
-        # assignment kernel on the fragment-major codebook image (round 5; g2v_vq_assign_packed_fwd), from 2048 rows
-        self.codebook_frag_generic = (torch.zeros(K * self.E, device=dev)
-                                      if (vq and not self._vq_bx and self.codebook_frag is None and
-                                          self.lib.g2v_vq_assign_packed_ok(1, self.E, K)) else None)
+                              if self._vq_image_route.startswith(("FUSED", "PROJECT>PACKED")) else None)
         self.bn_rm = torch.zeros(H, device=dev)
         self.bn_rv = torch.ones(H, device=dev)
         self.vq_stats = self.comm[self.n_flat:self.n_flat + n_stats] if vq else None
@@ -456,7 +453,8 @@ class VQVAEEngine:
         vq = self.quantizer != "none"          # (without a quantiser the rollout starts from enc_hidden, its gradient seeds the BPTT)
         if vq:
             b.update({"flat": z(B, E), "idx": torch.zeros(B, dtype=torch.int64, device=dev), "quant": z(2, B, H),
-                      "sse": z(self.lib.g2v_vq_assign_blocks(B)), "gz": z(2, B, H)})
+                      "sse": z(self.lib.g2v_vq_assign_blocks(B)), "gz": z(2, B, H),
+                      "vq_route": ops.vq_route("RAW", "FULL", (2 * B * H) // E, E, self.K)})
         elif self.latent != "none":            # the latent block stands where the quantiser would: same hand-over buffers
             b.update({"quant": z(2, B, H), "gz": z(2, B, H)})
         sv = DecSaved()
@@ -596,7 +594,8 @@ class VQVAEEngine:
         self._join(0)                       # branch 0: keep masks, ahead-of-time packs and (derived_ready) vq_derive()
         if not derived_ready:
             self.vq_derive()
-        if self._vq_bx:
+        route = b["vq_route"]
+        if route == "BX":
             # pre_linear (fp32 MFMA) + distances screened on the bf16 pipe + exact fp32 re-evaluation of every candidate +
             # argmin + straight-through / SSE in one launch (flat is written for the statistics)
             check(lib.g2v_vq_fused_assign_bx_fwd(_p(b["enc_hidden"]), _p(self.vq_wpre_frag), _p(self.vq_pre_b), _p(self.codebook),
@@ -605,7 +604,7 @@ class VQVAEEngine:
                                                  N, E, K, self.vq_bx_flags, st))
             if training and self.vq_bx_check_every > 0 and self._steps % self.vq_bx_check_every == 0:
                 self._vq_bx_selfcheck(b, N)
-        elif self.codebook_frag is not None:
+        elif route.startswith("FUSED"):
             # pre_linear + distances + argmin + straight-through / SSE in one launch (flat is written for the statistics)
             check(lib.g2v_vq_fused_assign_packed_fwd(_p(b["enc_hidden"]), _p(self.vq_pre_w), _p(self.vq_pre_b),
                                                      _p(self.codebook), _p(self.codebook_frag), _p(self.code_sqnorm),
@@ -613,8 +612,8 @@ class VQVAEEngine:
         else:
             check(lib.g2v_linear_fwd(_p(b["enc_hidden"]), E, 0, 0, 0, None, 1.0, _p(self.vq_pre_w), _p(self.vq_pre_b),
                                      _p(b["flat"]), E, N, E, E, 0, st))
-            if self.codebook_frag_generic is not None and N >= ops.VQ_PACKED_MIN_ROWS:
-                check(lib.g2v_vq_assign_packed_fwd(_p(b["flat"]), _p(b["enc_hidden"]), _p(self.codebook), _p(self.codebook_frag_generic),
+            if route.startswith("PROJECT>PACKED"):
+                check(lib.g2v_vq_assign_packed_fwd(_p(b["flat"]), _p(b["enc_hidden"]), _p(self.codebook), _p(self.codebook_frag),
                                                    _p(self.code_sqnorm), _p(b["idx"]), _p(b["quant"]), None, _p(b["sse"]), N, E, K, st))
             else:
                 check(lib.g2v_vq_assign_fwd(_p(b["flat"]), _p(b["enc_hidden"]), _p(self.codebook), _p(self.code_sqnorm),
@@ -800,8 +799,6 @@ class VQVAEEngine:
                                      _p(self.vq_bx_image), K, E, st))
         elif self.codebook_frag is not None:
             check(lib.g2v_vq_pack_codebook(_p(self.codebook), _p(self.codebook_frag), K, E, st))
-        elif self.codebook_frag_generic is not None:
-            check(lib.g2v_vq_pack_codebook(_p(self.codebook), _p(self.codebook_frag_generic), K, E, st))
 
     def refresh_codebook_state(self):
         """kept for callers of round 2: the derived state is recomputed by every entry point now"""

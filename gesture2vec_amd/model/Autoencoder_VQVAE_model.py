@@ -273,10 +273,6 @@ class Generator(nn.Module):
         return self.decoder(input_with_noise_vec, last_hidden, encoder_output, vid_indices, **kw)
 
 
-# rows from which VQ_Payam_EMA.assign takes g2v_vq_assign_bulk_z (where it serves the shape): measured break-even, DESIGN.md §3.5
-VQ_BULK_Z_MIN_ROWS = 32768   # K = 512: 0.139 (old) vs 0.176 ms at 16384 rows, 0.242 vs 0.188 ms at 32768
-
-
 class VQ_Payam_EMA(nn.Module):
     """EMA vector quantiser (reference :1182-1301).  forward(inputs) -> (loss, quantized, perplexity, encodings)."""
 
@@ -302,23 +298,10 @@ class VQ_Payam_EMA(nn.Module):
 
     def assign(self, inputs: torch.Tensor) -> torch.Tensor:
         """Code indices only (bulk code-assignment path): argmin_k ||pre_linear(x) - W_k||^2, int64 (N,)."""
-        E, K = self._embedding_dim, self._num_embeddings
-        z = inputs.contiguous().view(-1, E)
-        W = self._embedding.weight.data
-        if z.shape[0] >= VQ_BULK_Z_MIN_ROWS and ops.vq_assign_bulk_z_ok(z.shape[0], E, K):
-            # the checkpoints' width (E = 400): z-space bf16 screening + exact re-check straight from the raw latents, bitwise
-            # the route below at the same N, without writing pre_linear(z) (g2v_vq_assign_bulk_z)
-            return ops.vq_assign_bulk_z(z, self.pre_linear.weight.data, self.pre_linear.bias.data, W, ops.vq_code_sqnorm(W))
-        flat = ops.linear_fwd(z, self.pre_linear.weight.data, self.pre_linear.bias.data)
-        wsq = ops.vq_code_sqnorm(W)
-        if z.shape[0] >= 131072 and E == 128 and K % 128 == 0:
-            # a corpus' worth of rows: bf16 split screening on the bf16 matrix pipe + exact fp32 re-check of the undecided
-            # rows (g2v_vq_assign_bulk: the fp32 kernel's indices, 2.0x faster at 2^18 rows and 2.6x at 2^20; break-even 2^16)
-            return ops.vq_assign_bulk(flat, W, wsq)
-        # (every other shape, e.g. the checkpoints' E = 400: ops.vq_assign takes the packed eight-wave kernel from 2048 rows, with
-        #  2 / 4 row tiles per workgroup for a corpus' worth of rows -- round 5; it used to degrade to the generic kernel)
-        idx, _, _, _ = ops.vq_assign(flat, None, W, wsq, want_quantized=False)
-        return idx
+        # one query decides (g2v_vq_assign_route, DESIGN.md 3.5.1): the screened bulk kernels for a corpus' worth of rows -- from the raw
+        # latents at the checkpoints' width E = 400, on the projected rows at E = 128 --, else pre_linear + the fp32 kernels
+        return ops.vq_assign_raw(inputs.contiguous().view(-1, self._embedding_dim), self.pre_linear.weight.data,
+                                 self.pre_linear.bias.data, self._embedding.weight.data)
 
 
 class _VQFn(torch.autograd.Function):

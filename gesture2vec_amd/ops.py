@@ -362,8 +362,21 @@ def vq_code_sqnorm(codebook, out=None):
     return out
 
 
-def vq_assign(flat, z, codebook, code_sqnorm, want_quantized=True, want_dist=False):
-    """-> idx (N) int64, quantized (N,E) | None, dist_min (N) | None, sse_partial | None"""
+def vq_route(form, wants, N, E, K, *, smallm_rows=-1, facts=()) -> str:
+    """g2v_vq_assign_route as a name: "BX", "FUSED*1" (variant 1), "PACKED*4", "SPLIT*8", "PROJECT>PACKED*2" (pre_linear, then that
+    route on the projected rows), ...; "" where the call is refused.  form "ROWS" / "RAW", wants "FULL" / "IDX" / "IDX_BULK", facts:
+    names of G2V_VQ_PLAN_* bits; smallm_rows -1: the bound context's."""
+    c = _lib.CONSTANTS
+    r = _lib_().g2v_vq_assign_route(c["G2V_VQ_FORM_" + form], c["G2V_VQ_WANTS_" + wants], int(N), int(E), int(K), int(smallm_rows),
+                                    sum(c["G2V_VQ_PLAN_" + f] for f in facts))
+    names = {v: k[len("G2V_VQ_ROUTE_"):] for k, v in c.items() if k.startswith("G2V_VQ_ROUTE_")}
+    one = lambda x: names.get(x & 0xff, "") + (f"*{(x >> 8) & 0xff}" if (x >> 8) & 0xff else "")
+    return one(r) + (">" + one(r >> 16) if r >> 16 else "")
+
+
+def vq_assign(flat, z, codebook, code_sqnorm, want_quantized=True, want_dist=False, route=None):
+    """-> idx (N) int64, quantized (N,E) | None, dist_min (N) | None, sse_partial | None.  route: vq_route's answer for these rows,
+    where the caller has asked already."""
     N, E = flat.shape
     K = codebook.shape[0]
     dev = flat.device
@@ -372,7 +385,9 @@ def vq_assign(flat, z, codebook, code_sqnorm, want_quantized=True, want_dist=Fal
     quant = torch.empty((N, E), dtype=torch.float32, device=dev) if want_quantized else None
     dmin = torch.empty((N,), dtype=torch.float32, device=dev) if want_dist else None
     sse = torch.empty((lib.g2v_vq_assign_blocks(N),), dtype=torch.float32, device=dev) if want_quantized else None
-    if vq_assign_packed_pays(N, E, K):
+    if route is None:
+        route = vq_route("ROWS", "FULL" if want_quantized else "IDX", N, E, K)
+    if route.startswith("PACKED"):
         # the reference's own quantiser shapes (E = 400): fragment-major codebook image + the eight-wave kernel, same outputs bit
         # for bit (g2v_vq_assign_packed_fwd); the image is rebuilt per call (6 us: nothing is trusted across calls)
         frag = workspace(K * E * 4, flat.device, "vqpack").view(torch.float32)[:K * E]
@@ -385,12 +400,20 @@ def vq_assign(flat, z, codebook, code_sqnorm, want_quantized=True, want_dist=Fal
     return idx, quant, dmin, sse
 
 
-VQ_PACKED_MIN_ROWS = 2048      # below: g2v_vq_assign_fwd splits the CODES over workgroups (few row tiles), which is faster there
-
-
-def vq_assign_packed_pays(N, E, K) -> bool:
-    """shapes g2v_vq_assign_fwd has no tuned kernel for (anything but E = 128 with K % 128 = 0) at enough rows to fill the chip"""
-    return bool(N >= VQ_PACKED_MIN_ROWS and not (E == 128 and K % 128 == 0) and _lib_().g2v_vq_assign_packed_ok(int(N), int(E), int(K)))
+def vq_assign_raw(z, w_pre, b_pre, codebook):
+    """Code indices (N) int64 from RAW latents: argmin_k |z w_pre^T + b_pre - W_k|^2 on the route g2v_vq_assign_route names for a
+    caller that accepts the screened bulk kernels (they return the fp32 kernels' indices)."""
+    N, E = z.shape
+    K = codebook.shape[0]
+    route = vq_route("RAW", "IDX_BULK", N, E, K)
+    wsq = vq_code_sqnorm(codebook)
+    if route == "BULK_Z":
+        return vq_assign_bulk_z(z, w_pre, b_pre, codebook, wsq)
+    flat = linear_fwd(z, w_pre, b_pre)
+    rows = route.partition(">")[2]          # PROJECT>...; a refused call ("") gets its error from g2v_vq_assign_fwd
+    if rows.startswith("BULK"):
+        return vq_assign_bulk(flat, codebook, wsq)
+    return vq_assign(flat, None, codebook, wsq, want_quantized=False, route=rows)[0]
 
 
 def vq_assign_bulk(flat, codebook, code_sqnorm, want_undecided=False):

@@ -248,24 +248,78 @@ int g2v_vq_assign_fwd(const float* flat, const float* z, const float* codebook, 
                       int64_t* idx, float* quantized, float* dist_min, float* sse_partial,
                       int N, int E, int K, g2v_stream_t stream);
 
-/* pre_linear + assign in ONE launch (E == 128, K % 128 == 0; G2V_ERR_UNSUPPORTED otherwise -> g2v_linear_fwd +
+/* Which kernel a code assignment runs on: ONE decision (vq_route_plan, csrc/vq.hip; DESIGN.md section 3.5.1 has the measurement behind
+ * every row count), asked by the entry points below, by their *_ok queries and by the Python dispatchers.  The first row that
+ * matches decides ("tuned shape": E == 128 and K % 128 == 0; "aligned": no G2V_VQ_PLAN_UNALIGNED):
+ *   form RAW (latents z and pre_linear are given)
+ *     BX       wants FULL, tuned shape with K <= 512 (K in {128, 256, 384, 512}), aligned: g2v_vq_fused_assign_bx_fwd
+ *     FUSED    wants FULL, any other tuned shape, aligned: g2v_vq_fused_assign_packed_fwd (variant 1), or with
+ *              G2V_VQ_PLAN_NO_FRAG g2v_vq_fused_assign_fwd on the codebook in place (variant 0)
+ *     BULK_Z   wants IDX_BULK, N >= G2V_VQ_BULK_Z_MIN_ROWS, and the kernels serve it: E == 400, K % 16 == 0, 32 <= K <= 512, N >= 2048,
+ *              N > smallm_rows (g2v_linear_fwd takes another kernel up to there: no longer its bits), aligned: g2v_vq_assign_bulk_z
+ *     PROJECT  anything else: g2v_linear_fwd, then the ROWS route of the same wants, N, E, K and facts
+ *   form ROWS (projected rows flat are given)
+ *     BULK     wants IDX_BULK, N >= G2V_VQ_BULK_MIN_ROWS, tuned shape with K <= 8192, aligned: g2v_vq_assign_bulk; variant = bits of a code index
+ *     PACKED   N >= G2V_VQ_PACKED_MIN_ROWS, not a tuned shape, no G2V_VQ_PLAN_NO_FRAG, aligned, and the kernel serves it: E % 16 == 0,
+ *              K % 16 == 0, 64 rows of E + 4 floats fit the LDS (E <= 608): g2v_vq_pack_codebook + g2v_vq_assign_packed_fwd; variant =
+ *              row tiles per workgroup, 4 / 2 / 1 at N >= G2V_VQ_PACKED_NR4_ROWS / >= G2V_VQ_PACKED_NR2_ROWS / below
+ *     RT, FAST tuned shape, aligned: g2v_vq_assign_fwd's own kernels, RT (64 rows per workgroup, variant 4) from
+ *              G2V_VQ_RT_MIN_ROWS rows, FAST (16 rows, variant 1) below
+ *     SPLIT    at most G2V_VQ_SPLIT_MAX_ROW_TILES tiles of 16 rows and at least G2V_VQ_SPLIT_MIN_CODE_TILES tiles of 16 codes: the
+ *              codes split over variant = 2 .. 8 workgroups per row tile, then a finishing launch (g2v_vq_assign_fwd)
+ *     GENERIC  the rest (g2v_vq_assign_fwd); refused where 16 rows of E floats exceed 160 KB of LDS (E > 2544)
+ * G2V_VQ_PLAN_ENTRY: the call came in through a route's own entry point (g2v_vq_assign_packed_fwd for ROWS, g2v_vq_assign_bulk for
+ * ROWS + IDX_BULK, g2v_vq_assign_bulk_z for RAW + IDX_BULK): the row counts G2V_VQ_*_MIN_ROWS and PACKED's "not a tuned shape" do not
+ * apply, only what the kernels serve, and a shape they do not serve is refused.  g2v_vq_assign_fwd plans with G2V_VQ_PLAN_NO_FRAG.
+ * g2v_vq_assign_route returns G2V_VQ_ROUTE_* in bits 0-7 and the variant in bits 8-15, or 0 for a refused call; a PROJECT answer
+ * carries the answer of its ROWS route (route and variant) in bits 16-31.  smallm_rows: -1 = the bound context's smallm_max_rows;
+ * facts: an or of G2V_VQ_PLAN_*.  A function of its arguments alone otherwise. */
+#define G2V_VQ_FORM_ROWS 0
+#define G2V_VQ_FORM_RAW 1
+#define G2V_VQ_WANTS_FULL 0         /* quantized + SSE partials (and idx) */
+#define G2V_VQ_WANTS_IDX 1          /* indices only */
+#define G2V_VQ_WANTS_IDX_BULK 2     /* indices only, and the caller supplies a workspace: the screened bulk routes are accepted */
+#define G2V_VQ_ROUTE_BX 1
+#define G2V_VQ_ROUTE_FUSED 2
+#define G2V_VQ_ROUTE_BULK_Z 3
+#define G2V_VQ_ROUTE_PROJECT 4
+#define G2V_VQ_ROUTE_BULK 5
+#define G2V_VQ_ROUTE_PACKED 6
+#define G2V_VQ_ROUTE_RT 7
+#define G2V_VQ_ROUTE_FAST 8
+#define G2V_VQ_ROUTE_SPLIT 9
+#define G2V_VQ_ROUTE_GENERIC 10
+#define G2V_VQ_PLAN_UNALIGNED 1     /* an array the vector kernels read or write as float4s is not 16-byte aligned */
+#define G2V_VQ_PLAN_NO_FRAG 2       /* the caller has no room for a fragment-major codebook image */
+#define G2V_VQ_PLAN_ENTRY 4         /* called through the route's own entry point (above) */
+#define G2V_VQ_PACKED_MIN_ROWS 2048
+#define G2V_VQ_PACKED_NR2_ROWS 8192
+#define G2V_VQ_PACKED_NR4_ROWS 32768
+#define G2V_VQ_RT_MIN_ROWS 16384
+#define G2V_VQ_BULK_Z_MIN_ROWS 32768
+#define G2V_VQ_BULK_MIN_ROWS 131072
+#define G2V_VQ_SPLIT_MAX_ROW_TILES 64
+#define G2V_VQ_SPLIT_MIN_CODE_TILES 8
+int g2v_vq_assign_route(int form, int wants, int N, int E, int K, int smallm_rows, int facts);
+
+/* pre_linear + assign in ONE launch (the FUSED row of g2v_vq_assign_route; G2V_ERR_UNSUPPORTED otherwise -> g2v_linear_fwd +
  * g2v_vq_assign_fwd): flat = z w_pre^T + b_pre (:1230) is written to flat_out (the code statistics read it), the
  * distances / argmin use it from LDS, quantized / sse_partial use the raw z as in g2v_vq_assign_fwd. */
 /* Bulk code assignment (row f-2: latents of a whole corpus -> code indices, pipeline.chunks_to_codes): idx only, N large.
  * The -2 x W^T contraction runs on the bf16 matrix pipe as a 3-term split (xh.wh + xh.wl + xl.wh, fp32 accumulate); a row
  * whose best and second-best approximate distances are closer than 2^-11 |x| max|w| (more than twice the split's error
  * bound) is assigned again by the exact fp32 kernel of g2v_vq_assign_fwd, so the result is the fp32 argmin
- * (Autoencoder_VQVAE_model.py:1234-1259) at ~5x fewer matrix cycles.  E == 128, K % 128 == 0.  undecided (device int, may be
+ * (Autoencoder_VQVAE_model.py:1234-1259) at ~5x fewer matrix cycles.  Shapes: the BULK row of g2v_vq_assign_route.  undecided (device int, may be
  * NULL): number of rows that took the exact path. */
 size_t g2v_vq_assign_bulk_workspace(int N, int E, int K);
 int g2v_vq_assign_bulk(const float* flat, const float* codebook, const float* code_sqnorm, int64_t* idx, int N, int E, int K,
                        void* workspace, size_t workspace_bytes, int* undecided, g2v_stream_t stream);
-/* Bulk code assignment from RAW latents at the checkpoints' width (E = 400, K % 16 == 0, 32 <= K <= 512): idx = argmin_k
+/* Bulk code assignment from RAW latents at the checkpoints' width (the BULK_Z row of g2v_vq_assign_route): idx = argmin_k
  * |z w_pre^T + b_pre - codebook[k]|^2 without writing the projected rows.  The distances are screened in z-space on the bf16
  * matrix pipe (u_k = w_pre^T w_k, 3-term hi / lo split); a row whose winner does not clear every other code by the per-code
  * error radius is recomputed with the arithmetic of g2v_linear_fwd (tiled kernel) + g2v_vq_assign_packed_fwd, so idx is
  * bitwise that route's at the same N (ties: lowest index; non-finite rows or codes included).  code_sqnorm must be
- * g2v_vq_code_sqnorm's.  _ok also refuses N < 2048 and N <= the context's smallm_max_rows (other kernels there).
+ * g2v_vq_code_sqnorm's.  _ok: 1 where a call through this entry point is served (G2V_VQ_PLAN_ENTRY, the bound context's smallm_max_rows).
  * undecided (device int, may be NULL): number of rows that took the exact path. */
 int g2v_vq_assign_bulk_z_ok(int N, int E, int K);
 size_t g2v_vq_assign_bulk_z_workspace(int N, int E, int K);
@@ -281,10 +335,11 @@ int g2v_vq_fused_assign_fwd(const float* z, const float* w_pre, const float* b_p
  * the row-major codebook is still read for the gather of the chosen codes.  Results are bitwise those of
  * g2v_vq_fused_assign_fwd. */
 int g2v_vq_pack_codebook(const float* codebook, float* codebook_frag, int K, int E, g2v_stream_t stream);
-/* Round 5: g2v_vq_assign_fwd for ANY E % 16 == 0, K % 16 == 0 on that image (K * E floats) -- the reference's own quantiser
+/* Round 5: g2v_vq_assign_fwd on that image (K * E floats; shapes: the PACKED row of g2v_vq_assign_route, _ok: 1 where a call through
+ * this entry point is served) -- the reference's own quantiser
  * shapes, E = hidden_size * n_layers = 400 with K = 512 (config/VQ-VAE.yml) or 400 (VQ-VAE_GENEA.yml), which g2v_vq_assign_fwd
  * serves at 0.22 of the fp32 matrix peak.  Same outputs bit for bit (idx, dist_min, quantized, the SSE partials per 16 rows);
- * eight waves per workgroup, 1 / 2 / 4 row tiles per workgroup by N (bulk assignment: every fragment feeds all of them). */
+ * eight waves per workgroup, 1 / 2 / 4 row tiles per workgroup (bulk assignment: every fragment feeds all of them). */
 int g2v_vq_assign_packed_ok(int N, int E, int K);
 int g2v_vq_assign_packed_fwd(const float* flat, const float* z, const float* codebook, const float* codebook_frag,
                              const float* code_sqnorm, int64_t* idx, float* quantized, float* dist_min, float* sse_partial,
@@ -300,8 +355,8 @@ int g2v_vq_fused_assign_packed_fwd(const float* z, const float* w_pre, const flo
  * is re-evaluated IN THE SAME LAUNCH with the exact fp32 chain of g2v_vq_fused_assign_fwd on the projected rows, the row's code
  * being the torch.argmin (:1259) of those exact distances: flat_out, idx and quantized are bitwise those of
  * g2v_vq_fused_assign_fwd (sse_partial: the same sum in another order).  A 16-row tile with a non-finite screening value or more
- * than 128 candidates takes the exact fp32 sweep over all K codes instead.  E == 128, K in {128, 256, 384, 512}
- * (g2v_vq_fused_assign_bx_ok).
+ * than 128 candidates takes the exact fp32 sweep over all K codes instead.  Shapes: the BX row of g2v_vq_assign_route
+ * (g2v_vq_fused_assign_bx_ok: 1 where an ideal RAW call that wants FULL runs as BX).
  *   w_pre_frag  g2v_vq_pack_codebook(w_pre, ., E, E): pre_linear's weight as fp32 MFMA fragments (E * E floats)
  *   image       g2v_vq_bx_pack(codebook, code_sqnorm, w_pre, b_pre, ., K, E): bf16 MFMA fragments of U = W w_pre, s'_k, the radius
  *               coefficients (g2v_vq_bx_image_bytes(K, E) bytes); rewrite it whenever the codebook / code_sqnorm / pre_linear changed

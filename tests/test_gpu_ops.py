@@ -15,6 +15,7 @@ from _f64 import as64, default64
 from _wgrad_shapes import WGRAD_ROUTE_SHAPES, route_name
 from _dec_route_shapes import DEC_ROUTE_SHAPES, route_name as dec_route_name
 from _gru_route_shapes import GRU_ROUTE_SHAPES
+import _vq_route_shapes as VS
 
 pytestmark = pytest.mark.gpu
 
@@ -379,6 +380,8 @@ def test_vq_assign_bulk_equals_exact_assignment(ops, N, K, scale):
     flat[11, 0] = float("inf")
     Wd, fd = W.to(DEV), flat.to(DEV)
     wsq = ops.vq_code_sqnorm(Wd)
+    assert VS.route("ROWS", "IDX_BULK", N, E, K, facts=("ENTRY",)) == {512: "BULK*9", 128: "BULK*7"}[K]
+    assert VS.route("ROWS", "IDX", N, E, K) == ("RT*4" if N >= 16384 else "FAST*1")                # (the fp32 kernel it must equal)
     exact = ops.vq_assign(fd, fd, Wd, wsq, want_quantized=False)[0]
     idx, und = ops.vq_assign_bulk(fd, Wd, wsq, want_undecided=True)
     n_und = int(und.item())
@@ -448,11 +451,12 @@ def test_vq_assign_packed_kernel_equals_the_generic_kernel_bitwise(ops, N, E, K)
         st = torch.cuda.current_stream().cuda_stream
         if packed:
             assert lib.g2v_vq_assign_packed_ok(N, E, K) == 1
+            assert VS.route("ROWS", "FULL", N, E, K, facts=("ENTRY",)) == f"PACKED*{4 if N >= 32768 else 2 if N >= 8192 else 1}"
             frag = torch.empty(K * E, device=DEV)
             assert lib.g2v_vq_pack_codebook(p(Wd), p(frag), K, E, st) == 0
             assert lib.g2v_vq_assign_packed_fwd(p(fd), p(zd), p(Wd), p(frag), p(wsq), p(idx), p(quant), p(dmin), p(sse), N, E, K, st) == 0
         else:
-            prev = ops.VQ_PACKED_MIN_ROWS
+            assert VS.route("ROWS", "FULL", N, E, K, facts=("NO_FRAG",)) == "GENERIC"
             assert lib.g2v_vq_assign_fwd(p(fd), p(zd), p(Wd), p(wsq), p(idx), p(quant), p(dmin), p(sse), N, E, K, st) == 0
         torch.cuda.synchronize()
         return idx, quant, dmin, sse
@@ -469,13 +473,16 @@ def test_vq_assign_packed_kernel_equals_the_generic_kernel_bitwise(ops, N, E, K)
     safe = ((top2[:, 1] - top2[:, 0]) > 1e-4 * torch.clamp(top2[:, 0].abs(), min=1.0)) & torch.isfinite(d).all(1)
     assert torch.equal(a[0].cpu()[safe], ref[safe])
     assert torch.equal(a[0].cpu()[[11, 13, 17]], ref[[11, 13, 17]])      # NaN / Inf rows follow torch.argmin
-    # ops.vq_assign takes the packed kernel by itself from VQ_PACKED_MIN_ROWS rows (shapes without a tuned kernel of their own)
+    # ops.vq_assign takes the packed kernel by itself from G2V_VQ_PACKED_MIN_ROWS rows (shapes without a tuned kernel of their own)
+    assert ops.vq_route("ROWS", "FULL", N, E, K).startswith("PACKED") == (not (E == 128 and K % 128 == 0))
     idx2, _, _, _ = ops.vq_assign(fd, zd, Wd, wsq)
     assert torch.equal(idx2, a[0])
 
 
 @pytest.mark.parametrize("N,E,K", [(40, 32, 48), (40, 100, 512), (40, 128, 512), (16384 + 5, 128, 512)])   # generic / generic with the codes split over workgroups / fast / row-tiled kernel
 def test_vq_assign_ties_pick_lowest_index(ops, N, E, K):
+    assert ops.vq_route("ROWS", "FULL", N, E, K) == {(40, 32, 48): "GENERIC", (40, 100, 512): "SPLIT*8", (40, 128, 512): "FAST*1",
+                                                     (16384 + 5, 128, 512): "RT*4"}[(N, E, K)]
     W = rnd(K, E, seed=3)
     W[17] = W[5]
     W[40] = W[5]
@@ -486,11 +493,14 @@ def test_vq_assign_ties_pick_lowest_index(ops, N, E, K):
     assert (idx.cpu() == 5).all()
 
 
-@pytest.mark.parametrize("N,E,K", [(40, 100, 512), (48, 128, 512), (16384 + 21, 128, 512)])    # generic / fast / row-tiled kernel
+# generic with the codes split over workgroups / fast / row-tiled / generic kernel
+@pytest.mark.parametrize("N,E,K", [(40, 100, 512), (48, 128, 512), (16384 + 21, 128, 512), (40, 32, 48)])
 def test_vq_assign_nonfinite_rows_follow_torch_argmin(ops, N, E, K):
     """A diverged step feeds NaN / Inf rows to the quantiser.  torch.argmin (reference :1259) returns a VALID index
     (first NaN, else first minimum); the kernels must do the same -- never an out-of-range sentinel that would then be
     used as a gather offset into the codebook."""
+    assert ops.vq_route("ROWS", "FULL", N, E, K) == {(40, 100, 512): "SPLIT*8", (48, 128, 512): "FAST*1", (16384 + 21, 128, 512): "RT*4",
+                                                     (40, 32, 48): "GENERIC"}[(N, E, K)]
     flat, z = rnd(N, E, seed=31), rnd(N, E, seed=32)
     W = torch.rand(K, E, generator=torch.Generator().manual_seed(33)) * 2 - 1
     flat[3, 7] = float("nan")
@@ -515,6 +525,76 @@ def test_vq_assign_nonfinite_rows_follow_torch_argmin(ops, N, E, K):
     # and the code statistics accept the result
     stats = ops.vq_stats(idx, flat.nan_to_num(0.0, 0.0, 0.0).to(DEV), K)
     assert torch.equal(stats[:K].cpu(), torch.bincount(got, minlength=K).float())
+
+
+_VQ_ENTRY_POINTS = ("g2v_linear_fwd", "g2v_vq_pack_codebook", "g2v_vq_assign_fwd", "g2v_vq_assign_packed_fwd", "g2v_vq_assign_bulk",
+                    "g2v_vq_assign_bulk_z", "g2v_vq_fused_assign_fwd", "g2v_vq_fused_assign_packed_fwd", "g2v_vq_fused_assign_bx_fwd")
+
+
+def _vq_calls_of(route):
+    """the library functions a dispatcher must call for an answer of ops.vq_route, in order"""
+    head, _, rows = route.partition(">")
+    one = {"BX": ["g2v_vq_fused_assign_bx_fwd"], "FUSED": ["g2v_vq_fused_assign_packed_fwd"], "BULK_Z": ["g2v_vq_assign_bulk_z"],
+           "PROJECT": ["g2v_linear_fwd"], "BULK": ["g2v_vq_assign_bulk"], "PACKED": ["g2v_vq_pack_codebook", "g2v_vq_assign_packed_fwd"],
+           "RT": ["g2v_vq_assign_fwd"], "FAST": ["g2v_vq_assign_fwd"], "SPLIT": ["g2v_vq_assign_fwd"], "GENERIC": ["g2v_vq_assign_fwd"]}
+    return one[head.split("*")[0]] + (one[rows.split("*")[0]] if rows else [])
+
+
+def _count_vq_calls(monkeypatch):
+    from gesture2vec_amd import _lib
+    lib, calls = _lib.load(), []
+    for name in _VQ_ENTRY_POINTS:
+        real = getattr(lib, name)
+        monkeypatch.setattr(lib, name, lambda *a, _real=real, _name=name: calls.append(_name) or _real(*a))
+    return calls
+
+
+@pytest.mark.parametrize("N,E,K", VS.DISPATCH_NEK)
+def test_python_dispatchers_call_what_the_route_query_names(ops, monkeypatch, N, E, K):
+    """ops.vq_assign (a ROWS caller that accepts no bulk route: k-means, the autograd function) and VQ_Payam_EMA.assign (RAW, the
+    only caller that accepts them) at the smallest shape of each route: the library functions they call are exactly those of the
+    query's answer, and the answer is the one the table names for the shape."""
+    from gesture2vec_amd.model.Autoencoder_VQVAE_model import VQ_Payam_EMA
+    want = {(40, 128, 512): "FAST*1", (16389, 128, 512): "RT*4", (40, 100, 512): "SPLIT*8", (40, 32, 48): "GENERIC",
+            (2048, 400, 512): "PACKED*1", (8192, 48, 64): "PACKED*2", (33000, 128, 48): "PACKED*4", (131077, 128, 128): "RT*4",
+            (32805, 400, 32): "PACKED*4"}[(N, E, K)]
+    raw = {(131077, 128, 128): "PROJECT>BULK*7", (32805, 400, 32): "BULK_Z"}.get((N, E, K), "PROJECT>" + want)
+    torch.manual_seed(N + E + K)
+    q = VQ_Payam_EMA(K, E, 0.25, 0.85).to(DEV)
+    z = torch.randn(N, E, device=DEV) * 0.3
+    W = q._embedding.weight.data
+    wsq = ops.vq_code_sqnorm(W)
+    flat = ops.linear_fwd(z, q.pre_linear.weight.data, q.pre_linear.bias.data)
+    calls = _count_vq_calls(monkeypatch)
+    for wants, full in (("FULL", True), ("IDX", False)):
+        assert ops.vq_route("ROWS", wants, N, E, K) == want
+        ref = ops.vq_assign(flat, z, W, wsq, want_quantized=full)[0]
+        assert calls == _vq_calls_of(want), (wants, calls)
+        calls.clear()
+    assert ops.vq_route("RAW", "IDX_BULK", N, E, K) == raw
+    idx = q.assign(z)
+    assert calls == _vq_calls_of(raw), calls
+    assert torch.equal(idx, ref)
+
+
+@pytest.mark.parametrize("B,T,D,H,K,route", [(16, 34, 135, 64, 512, "BX"), (16, 34, 135, 64, 640, "FUSED*1"), (2048, 10, 45, 200, 400, "PROJECT>PACKED*1"),
+                                             (48, 10, 45, 200, 400, "PROJECT>SPLIT*5")])
+def test_engine_forward_calls_what_the_route_query_names(ops, monkeypatch, B, T, D, H, K, route):
+    """One training step of the engine: its forward quantises the batch with exactly the library functions of the query's answer for
+    (N, E, K) = (2 B H / E, 2 H, K), taken once when the buffers of the batch size are made; vq_derive packs that route's image."""
+    from test_gpu_dp_engine import _engine
+    eng = _engine(O.init_vqvae_state(D, H, 2, K, seed=13), D, H, K, T, 0.0)
+    assert ops.vq_route("RAW", "FULL", B, 2 * H, K) == route == eng.buffers(B)["vq_route"]
+    assert eng._vq_bx == (route == "BX") and (eng.vq_bx_image is not None) == (eng.vq_wpre_frag is not None) == (route == "BX")
+    assert (eng.codebook_frag is not None) == (route == "FUSED*1" or H == 200)
+    x = torch.randn(B, T, D, generator=torch.Generator().manual_seed(7)).to(DEV)
+    calls = _count_vq_calls(monkeypatch)
+    eng.train_step(x, x, lr=5e-4, w_l1=5.0, w_cont=0.1, w_var=0.5)
+    eng.check_faults()
+    # (the step's other products call g2v_linear_fwd too; vq_derive packs W_pre's fragments for BX, else the codebook's image)
+    assign = lambda names: [c for c in names if c.startswith("g2v_vq_") and c != "g2v_vq_pack_codebook"]
+    assert assign(calls) == assign(_vq_calls_of(route)), calls
+    assert "g2v_vq_pack_codebook" in calls and ("g2v_linear_fwd" in calls or not route.startswith("PROJECT")), calls
 
 
 @pytest.mark.parametrize("N", [4096, 16, 37, 20000])

@@ -269,6 +269,8 @@ def test_bulk_assign_route_of_the_quantiser_module():
     torch.manual_seed(3)
     q = VQ_Payam_EMA(512, 128, 0.25, 0.85).to(DEV)
     z = torch.randn(131072 + 5, 128, device=DEV) * 0.3
+    assert ops.vq_route("RAW", "IDX_BULK", 131072 + 5, 128, 512) == "PROJECT>BULK*9"
+    assert ops.vq_route("ROWS", "IDX", 131072 + 5, 128, 512) == "RT*4"                  # (the reference below)
     idx = q.assign(z)
     flat = ops.linear_fwd(z, q.pre_linear.weight.data, q.pre_linear.bias.data)
     W = q._embedding.weight.data
@@ -288,6 +290,7 @@ def test_bulk_assign_route_of_the_quantiser_module_at_the_shipped_width():
     K, E, N = 512, 400, 131072 + 37
     q = VQ_Payam_EMA(K, E, 0.25, 0.85).to(DEV)
     z = torch.randn(N, E, device=DEV) * 0.3
+    assert ops.vq_route("RAW", "IDX_BULK", N, E, K) == "BULK_Z" and ops.vq_route("ROWS", "IDX", N, E, K) == "PACKED*4"
     idx = q.assign(z)
     assert idx.dtype == torch.int64 and idx.shape == (N,)
     flat = ops.linear_fwd(z, q.pre_linear.weight.data, q.pre_linear.bias.data)

@@ -58,6 +58,8 @@ def test_bitwise_equal_to_the_current_route(K, N, kind):
     from gesture2vec_amd import ops
     z, Wp, b, W, n_must = _operands(K, N, kind, seed=K + N)
     assert ops.vq_assign_bulk_z_ok(N, E, K)
+    assert ops.vq_route("RAW", "IDX_BULK", N, E, K, facts=("ENTRY",)) == "BULK_Z"
+    assert ops.vq_route("RAW", "IDX", N, E, K) == f"PROJECT>PACKED*{4 if N >= 32768 else 2 if N >= 8192 else 1}"      # (the current route)
     idx, und = ops.vq_assign_bulk_z(z, Wp, b, W, ops.vq_code_sqnorm(W), want_undecided=True)
     ref = _current_route(ops, z, Wp, b, W)
     torch.cuda.synchronize()
@@ -157,11 +159,13 @@ def test_matches_the_oracle_outside_the_rounding_band():
 
 @pytest.mark.parametrize("K", [512, 400])
 def test_quantiser_module_takes_the_new_route(K, monkeypatch):
-    from gesture2vec_amd import ops
+    from gesture2vec_amd import _lib, ops
     from gesture2vec_amd.model import Autoencoder_VQVAE_model as M
     torch.manual_seed(K)
     q = M.VQ_Payam_EMA(K, E, 0.25, 0.85).to(DEV)
-    N = max(M.VQ_BULK_Z_MIN_ROWS, 2048) + 37
+    min_rows = _lib.CONSTANTS["G2V_VQ_BULK_Z_MIN_ROWS"]
+    N = max(min_rows, 2048) + 37
+    assert ops.vq_route("RAW", "IDX_BULK", N, E, K) == "BULK_Z" and ops.vq_route("RAW", "IDX_BULK", min_rows - 1, E, K) == "PROJECT>PACKED*2"
     z = torch.randn(N, E, device=DEV) * 0.3
     calls = []
     real = ops.vq_assign_bulk_z
@@ -170,17 +174,18 @@ def test_quantiser_module_takes_the_new_route(K, monkeypatch):
     assert calls, "VQ_Payam_EMA.assign did not take vq_assign_bulk_z"
     assert torch.equal(idx, _current_route(ops, z, q.pre_linear.weight.data, q.pre_linear.bias.data, q._embedding.weight.data))
     calls.clear()
-    small = q.assign(z[:M.VQ_BULK_Z_MIN_ROWS - 1])           # below the threshold: the route of before
-    assert not calls and small.shape == (M.VQ_BULK_Z_MIN_ROWS - 1,)
+    small = q.assign(z[:min_rows - 1])                       # below the threshold: the route of before
+    assert not calls and small.shape == (min_rows - 1,)
 
 
 def test_chunks_to_codes_at_the_shipped_width():
-    from gesture2vec_amd import ops
+    from gesture2vec_amd import _lib, ops
     from gesture2vec_amd.model import Autoencoder_VQVAE_model as M
     from gesture2vec_amd.pipeline import chunk_latents, chunks_to_codes
     torch.manual_seed(17)
     D, H, L, K, T = 45, 200, 2, 512, 34
-    N = max(M.VQ_BULK_Z_MIN_ROWS, 2048) + 11
+    N = max(_lib.CONSTANTS["G2V_VQ_BULK_Z_MIN_ROWS"], 2048) + 11
+    assert ops.vq_route("RAW", "IDX_BULK", N, L * H, K) == "BULK_Z"
     args = argparse.Namespace(rep_learning_dim=D, hidden_size=H, n_layers=L, dropout_prob=0.0, autoencoder_vq="True",
                               autoencoder_vae="False", autoencoder_vq_components=K, autoencoder_vq_commitment_cost=0.25,
                               autoencoder_conditioned="True", autoencoder_att="False", autoencoder_fixed_weight="False",
