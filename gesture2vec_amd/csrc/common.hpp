@@ -30,8 +30,9 @@ G2vOptions& g2v_internal_options();
 void g2v_internal_preclear_note(const void* p, size_t n);
 int g2v_internal_preclear_take(const void* p, size_t need);
 void g2v_internal_preclear_drop(const void* base, size_t bytes);
-// dec_rollout.hip -- G2V_OPT_PERSISTENT != 0 (t2e_rollout.hip: the code decoder's cluster kernel)
-int g2v_internal_persist_enabled();
+// misc.hip -- the current device's CU count, asked once (0: no device).  The persistent and cluster kernels need every workgroup
+// of their launch resident at once, one per CU: every dispatch plan takes its `cus` from here.
+int g2v_internal_device_cus();
 // gru.hip -- the exchange region a cluster launch of this shape clears (offset 0 of its workspace); 0: not a cluster shape
 size_t g2v_internal_gru_cluster_region(int T, int B, int H, int ndir, int bwd);
 // vq.hip -- does the plan (vq_route_plan) serve this call of g2v_vq_assign_bulk_z (vq_bulk_z.hip)?  G2V_OK, or the code with *msg set

@@ -24,15 +24,6 @@
 
 namespace g2v {
 
-// The persistent path needs every workgroup of its launch resident at once: one per CU.
-static int device_cu_count() {
-  static int n = -1;
-  if (n < 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-  }
-  return n;
-}
 // Row tiles per workgroup of a persistent rollout over `nblk` row tiles on `cus` CUs under G2V_OPT_PERSISTENT = `level` (the switch
 // lives in the calling thread's context, g2v_ctx; the library reads no environment variable): 1 while there is a CU per tile, 2 or 3
 // beyond that (dec_persist.hip, the *_mt kernels); 0: not offered.  Levels 2 / 3 ask for at least that many (parity tests of the
@@ -979,7 +970,6 @@ extern "C" int g2v_read_spans(unsigned long long* out) {
 }
 #endif
 
-int g2v_internal_persist_enabled() { return g2v_internal_options().persist != 0 ? 1 : 0; }      // (t2e_rollout.hip: the code decoder's cluster kernel)
 extern "C" int g2v_dec_rollout_blocks(int B) { return B > 0 ? cdiv(B, 16) : 0; }
 
 extern "C" int g2v_dec_rollout_set_persistent(int enable) {      // = g2v_ctx_set_option(NULL, G2V_OPT_PERSISTENT, enable)
@@ -1036,7 +1026,7 @@ static size_t dec_cluster_fwd_dyn_lds() {      // W_out fragments, partial out-l
 static bool dec_prepared_shape(int D, int H) { return H == 64 && D == 135; }
 static bool dec_cluster_shape(int D, int H) { return !dec_prepared_shape(D, H) && (H & 3) == 0 && H <= 16 * DCL_KS && D <= 64 && H >= 4; }
 // the workspace queries size the cluster kernel's records for the largest grid it is admitted for: one workgroup per CU
-static int dec_cluster_max_nblk(int H) { return (device_cu_count() > 0 ? device_cu_count() : 256) / ((H + 15) >> 4) + 1; }
+static int dec_cluster_max_nblk(int H) { return (g2v_internal_device_cus() > 0 ? g2v_internal_device_cus() : 256) / ((H + 15) >> 4) + 1; }
 extern "C" size_t g2v_dec_rollout_fwd_workspace(int D, int H) {
   const size_t c = dec_cluster_shape(D, H) ? dec_cluster_fwd_xch_bytes(dec_cluster_max_nblk(H), H) : 0;
   return fwd_pack_bytes_aligned(D, H) + (c > PX_BYTES ? c : PX_BYTES);
@@ -2581,7 +2571,7 @@ static DecRoutePlan dec_route_plan(bool bwd, int T, int B, int D, int H, bool tr
 static DecRoutePlan dec_plan_ideal(bool bwd, int T, int B, int D, int H, size_t workspace_bytes = DEC_IDEAL_FACTS.workspace_bytes) {
   DecCallFacts f = DEC_IDEAL_FACTS;
   f.workspace_bytes = workspace_bytes;
-  return dec_route_plan(bwd, T, B, D, H, true, g2v_internal_options().persist, device_cu_count(), f);
+  return dec_route_plan(bwd, T, B, D, H, true, g2v_internal_options().persist, g2v_internal_device_cus(), f);
 }
 extern "C" int g2v_dec_rollout_route(int backward, int T, int B, int D, int H, int training, int persistent, int cus, int flags) {
   DecCallFacts f = DEC_IDEAL_FACTS;
@@ -2590,7 +2580,7 @@ extern "C" int g2v_dec_rollout_route(int backward, int T, int B, int D, int H, i
   if (flags & G2V_DEC_PLAN_LOSS) f.loss = f.loss_complete = true;
   const DecRoutePlan pl = dec_route_plan(backward != 0, T, B, D, H, training != 0,
                                          persistent < 0 ? g2v_internal_options().persist : (persistent > 3 ? 3 : persistent),
-                                         cus > 0 ? cus : device_cu_count(), f);
+                                         cus > 0 ? cus : g2v_internal_device_cus(), f);
   return pl.route == G2V_DEC_ROUTE_PERSIST ? pl.route | (pl.tiles << 8) : pl.route;
 }
 // The older queries (include/g2v.h), each a field of the ideal call's plan.
@@ -2695,7 +2685,7 @@ static bool dec_cluster_resident(bool bwd) {
 }
 // the plan of a real call: the bound context's level, this device's CUs, the call's facts
 static DecRoutePlan dec_plan_call(bool bwd, int T, int B, int D, int H, bool training, DecCallFacts f) {
-  const int level = g2v_internal_options().persist, cus = device_cu_count();
+  const int level = g2v_internal_options().persist, cus = g2v_internal_device_cus();
   DecRoutePlan pl = dec_route_plan(bwd, T, B, D, H, training, level, cus, f);
   if (pl.route == G2V_DEC_ROUTE_CLUSTER && !dec_cluster_resident(bwd)) {
     f.cluster_resident = false;

@@ -2160,14 +2160,6 @@ constexpr int GRU_SPLIT_MAX_B = 1024;      // the per-step and cluster routes en
 extern "C" int g2v_gru_seq_set_cluster(int enable) {             // = g2v_ctx_set_option(NULL, G2V_OPT_GRU_CLUSTER, enable)
   return g2v_ctx_set_option(nullptr, G2V_OPT_GRU_CLUSTER, enable);
 }
-static int gru_device_cus() {
-  static int n = -1;
-  if (n < 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-  }
-  return n;
-}
 
 // ---- workspaces: sizes, and one view per direction of travel that names every region (each route's from offset 0) -----------
 // exchange records of the cluster kernels: forward one (16 x Hp) record of granules per (parity, row group, direction), backward one
@@ -2196,8 +2188,8 @@ static size_t gru_workspace_bytes(bool bwd, int ndir, int H, int cus) {
   const size_t ab = (a > b ? a : b) * sizeof(float), c = gru_cluster_max_xch_bytes(H, bwd, cus);
   return ab > c ? ab : c;
 }
-extern "C" size_t g2v_gru_seq_fwd_workspace(int ndir, int H) { return gru_workspace_bytes(false, ndir, H, gru_device_cus()); }
-extern "C" size_t g2v_gru_seq_bwd_workspace(int ndir, int H) { return gru_workspace_bytes(true, ndir, H, gru_device_cus()); }
+extern "C" size_t g2v_gru_seq_fwd_workspace(int ndir, int H) { return gru_workspace_bytes(false, ndir, H, g2v_internal_device_cus()); }
+extern "C" size_t g2v_gru_seq_bwd_workspace(int ndir, int H) { return gru_workspace_bytes(true, ndir, H, g2v_internal_device_cus()); }
 extern "C" size_t g2v_gru_seq_bwd_wslab_bytes(int B, int H) {
   return (B > 0 && H > 0) ? (size_t)cdiv(B, 16) * 2 * ((size_t)3 * H * H + 3 * H) * sizeof(float) : 0;
 }
@@ -2327,17 +2319,17 @@ static bool gru_cluster_resident(bool bwd) {
 // the plan of a real call (the bound context's options, this device's CUs, the call's facts) ...
 static GruRoutePlan gru_plan_call(bool bwd, int T, int B, int H, int ndir, GruCallFacts f) {
   const G2vOptions& o = g2v_internal_options();
-  GruRoutePlan pl = gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, gru_device_cus(), f);
+  GruRoutePlan pl = gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, g2v_internal_device_cus(), f);
   if (pl.route == G2V_GRU_ROUTE_CLUSTER && !gru_cluster_resident(bwd)) {
     f.cluster_resident = false;
-    pl = gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, gru_device_cus(), f);
+    pl = gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, g2v_internal_device_cus(), f);
   }
   return pl;
 }
 // ... and of the queries (include/g2v.h), each a field of the ideal call's plan
 static GruRoutePlan gru_plan_ideal(bool bwd, int T, int B, int H, int ndir, const GruCallFacts& f = GruCallFacts{}) {
   const G2vOptions& o = g2v_internal_options();
-  return gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, gru_device_cus(), f);
+  return gru_route_plan(bwd, T, B, H, ndir, o.gru_cluster, o.gru_resident_rows, o.gru_resident_bwd, g2v_internal_device_cus(), f);
 }
 extern "C" int g2v_gru_seq_route(int backward, int T, int B, int H, int ndir, int cluster, int resident_rows, int resident_bwd, int cus,
                                  int facts) {
@@ -2356,7 +2348,7 @@ extern "C" int g2v_gru_seq_route(int backward, int T, int B, int H, int ndir, in
   if (facts & G2V_GRU_PLAN_SMALL_WORKSPACE) f.workspace_bytes = 0;
   f.cluster_resident = !(facts & G2V_GRU_PLAN_NOT_RESIDENT);
   const GruRoutePlan pl = gru_route_plan(bwd, T, B, H, ndir, cluster < 0 ? o.gru_cluster : cluster, resident_rows < 0 ? o.gru_resident_rows : resident_rows,
-                                         resident_bwd < 0 ? o.gru_resident_bwd : resident_bwd, cus > 0 ? cus : gru_device_cus(), f);
+                                         resident_bwd < 0 ? o.gru_resident_bwd : resident_bwd, cus > 0 ? cus : g2v_internal_device_cus(), f);
   return pl.route ? pl.route | (pl.variant << 8) : 0;
 }
 extern "C" int g2v_gru_seq_cluster_ok(int T, int B, int H, int ndir) { return gru_plan_ideal(false, T, B, H, ndir).route == G2V_GRU_ROUTE_CLUSTER ? 1 : 0; }

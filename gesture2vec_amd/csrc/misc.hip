@@ -38,6 +38,14 @@ static g2v_ctx& ctx_or_cur(const g2v_ctx* ctx = nullptr) {      // `ctx`, else t
   return *(ctx ? const_cast<g2v_ctx*>(ctx) : (t_bound_ctx ? t_bound_ctx : &g_default_ctx));
 }
 G2vOptions& g2v_internal_options() { return ctx_or_cur().opt; }
+int g2v_internal_device_cus() {
+  static int n = -1;
+  if (n < 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+  }
+  return n;
+}
 void g2v_internal_preclear_note(const void* p, size_t n) {
   g2v_ctx& c = ctx_or_cur();
   for (auto& e : c.preclear)

@@ -1293,189 +1293,39 @@ using namespace g2v;
 // host
 // ---------------------------------------------------------------------------------------------------------------------
 
-extern "C" int g2v_attn_code_rollout_blocks(int B) { return B > 0 ? cdiv(B, 16) : 0; }
+// Which kernels a call runs on is decided in ONE place, code_route_plan (each route's rule: include/g2v.h at
+// g2v_attn_code_rollout_route).  g2v_attn_code_rollout_fwd / _bwd and g2v_code_cluster_bptt validate, plan and launch; the size and
+// *_ok queries are fields of an ideal call's plan.
 
-extern "C" int g2v_attn_code_rollout_ok(int S1, int B, int H, int K, int Tw, int attention) {
-  if (S1 < 1 || B < 1 || H < 16 || (H & 3) || H > 256 || K < 4 || (K & 3) || K > 1024) return 0;
-  if (attention && (Tw < 1 || Tw > CT_MAX_TW)) return 0;
-  const int Hin = attention ? 2 * H : H;
-  const size_t lf = (size_t)ct_fwd_lds(H, Hin, attention ? Tw : 0, 1024).total * 4;
-  const size_t lb = (size_t)ct_bwd_lds(H, K).total * 4;
-  const int Hp = (H + 15) & ~15;
-  if (attention && (2 * Hp + 1024 > 16 * (((3 * H + 15) & ~15) + 4) || 2 * 16 * Tw > 16 * (Hp + 4))) return 0;   // what Part A borrows
-  return lf <= 160 * 1024 && lb <= 160 * 1024;
-}
+extern "C" int g2v_attn_code_rollout_blocks(int B) { return B > 0 ? cdiv(B, 16) : 0; }
 
 static size_t ct_fwd_pack_floats(int H, int K, int att) {
   const int Hin = att ? 2 * H : H;
   return pack_floats(H, 1, Hin) + 4 * pack_floats(H, 3, H) + (size_t)ct_ktiles_alloc(K) * pack_ks(H) * 256 +
          (att ? pack_floats(H, 1, H) : 0);
 }
-// exchange records of code_cluster_fwd_kernel: three row records + the BatchNorm sums + the argmax pairs per (parity, row group)
-static size_t code_cluster_xch_bytes(int nblk, int H) {
-  const size_t Hp = (size_t)((H + 15) & ~15), nt = Hp / 16;
-  return (size_t)2 * nblk * ((3 * 16 + 2) * Hp + nt * 32) * 8 + (size_t)nblk * nt * sizeof(unsigned) + 16;
-}
-static size_t code_cluster_rec_bytes(int nblk, int H) { return code_cluster_xch_bytes(nblk, H) - ((size_t)nblk * ((H + 15) >> 4) * sizeof(unsigned) + 16); }
-static size_t code_cluster_dyn_lds() { return ((size_t)CCL_KT * CCL_KS + CCL_KS + (size_t)4 * CCL_KT + CCL_KS) * 64 * sizeof(float4); }
-static int ct_device_cus() {
-  static int n = -1;
-  if (n < 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-  }
-  return n;
-}
-// 1: g2v_attn_code_rollout_fwd runs this shape as ONE persistent cluster launch (no attention, H <= 208, at most three K tiles per
-// hidden-unit tile, the (tile x row group) grid with a CU per workgroup) under the current g2v_dec_rollout_set_persistent setting
-extern "C" int g2v_attn_code_rollout_cluster_ok(int S1, int B, int H, int K, int attention) {
-  if (attention || S1 < 1 || B < 1 || H < 16 || (H & 3) || H > 16 * CCL_KS || K < 4 || (K & 3)) return 0;
-  const int nt = (H + 15) >> 4, nblk = (B + 15) >> 4;
-  if (((K + 15) >> 4) > CCL_KT * nt || (int64_t)nt * nblk > ct_device_cus()) return 0;
-  return g2v_internal_persist_enabled() ? 1 : 0;
-}
-// The cells' BPTT of the attention-free rollout at small batch as one persistent cluster launch (code_cluster_bptt_kernel; the
-// shapes of g2v_attn_code_rollout_cluster_ok).  dh_top (S1,B,H) = dLogits W_out for every step (g2v_linear_bwd_data); writes dgi0 /
-// dgh0 / dgi1 / dgh1 (S1,B,3H), da (S1,B,H) = the gradient w.r.t. a_t before its ReLU mask (BatchNorm's backward is the caller's
-// next launch), d_hidden0 (2,B,H).  s: gates0 / gates1 / h0 / h1 of the forward.
-extern "C" size_t g2v_code_cluster_bptt_workspace(int B, int H) {
-  const size_t Hp = (size_t)((H + 15) & ~15), nt = Hp / 16;
-  return (size_t)((B + 15) / 16) * 4 * nt * 16 * Hp * 8 + (size_t)((B + 15) / 16) * nt * sizeof(unsigned) + 16;
-}
-extern "C" int g2v_code_cluster_bptt(const float* dh_top, const g2v_code_dec_weights* w, const g2v_code_dec_saved* s,
-                                     const uint8_t* keep_l0, float p_drop, float* dgi0, float* dgh0, float* dgi1, float* dgh1,
-                                     float* da, float* d_hidden0, int S1, int B, int H, void* workspace, size_t workspace_bytes,
-                                     g2v_stream_t stream) {
-  G2V_REQUIRE(dh_top && w && s && dgi0 && dgh0 && dgi1 && dgh1 && da && d_hidden0 && workspace, "null pointer");
-  G2V_REQUIRE(w->w_ih0 && w->w_hh0 && w->w_ih1 && w->w_hh1 && s->gates0 && s->gates1 && s->h0 && s->h1, "missing array");
-  G2V_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "bad dropout probability");
-  if (!g2v_attn_code_rollout_cluster_ok(S1, B, H, 4, 0)) {
-    set_error("g2v_code_cluster_bptt: shape not served (g2v_attn_code_rollout_cluster_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
-  if (workspace_bytes < g2v_code_cluster_bptt_workspace(B, H)) {
-    set_error("g2v_code_cluster_bptt: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  const void* al[] = {dh_top, keep_l0, dgi0, dgh0, dgi1, dgh1, da, d_hidden0, s->gates0, s->gates1, s->h0, s->h1, workspace};
-  for (const void* p : al) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
-  hipStream_t st = (hipStream_t)stream;
-  const void* fn = (const void*)code_cluster_bptt_kernel;
-  int nocc = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, 0) != hipSuccess || nocc < 1) {
-    set_error("g2v_code_cluster_bptt: the kernel does not fit a CU");
-    return G2V_ERR_LAUNCH;
-  }
-  CodeClBwdArgs ca;
-  ca.dh_top = dh_top; ca.keep_l0 = keep_l0; ca.w = *w; ca.sv = *s;
-  ca.dgi0 = dgi0; ca.dgh0 = dgh0; ca.dgi1 = dgi1; ca.dgh1 = dgh1; ca.da = da; ca.d_hidden0 = d_hidden0;
-  ca.xq = reinterpret_cast<unsigned long long*>(workspace);
-  ca.nt = (H + 15) >> 4; ca.nblk = cdiv(B, 16);
-  ca.xcc = reinterpret_cast<unsigned*>((char*)workspace + (size_t)ca.nblk * 4 * ca.nt * 16 * (ca.nt * 16) * 8);
-  ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
-  ca.S1 = S1; ca.B = B; ca.H = H; ca.p_drop = p_drop;
-  if (hipMemsetAsync(workspace, 0, g2v_code_cluster_bptt_workspace(B, H), st) != hipSuccess) {
-    set_error("g2v_code_cluster_bptt: clearing the exchange records failed");
-    return G2V_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(code_cluster_bptt_kernel, dim3(((H + 15) >> 4) * cdiv(B, 16)), dim3(256), 0, st, ca);
-  G2V_CHECK_LAUNCH();
-  return G2V_OK;
-}
-extern "C" size_t g2v_attn_code_rollout_fwd_workspace(int H, int K, int attention) {
-  size_t x = al256(ct_fwd_pack_floats(H, K, attention) * sizeof(float));
-  if (!attention && (H & 3) == 0 && H >= 16 && H <= 16 * CCL_KS) {      // the cluster kernel's exchange records at its largest grid
-    const int nt = (H + 15) >> 4, cus = ct_device_cus() > 0 ? ct_device_cus() : 256;
-    const size_t c = code_cluster_xch_bytes(cus / nt + 1, H);
-    if (c > x) x = c;
-  }
+// ---- exchange records of the two cluster kernels, from offset 0 of the workspace ------------------------------------------------
+struct CodeXch {
+  size_t h0, h1, p, a;      // forward: 8-byte granules in front of the h0 / h1 row records (u's start at 0), the BatchNorm sums, the argmax pairs
+  size_t xcc, bytes;        // byte offset of the arrival counters; bytes the launch clears
+};
+// code_cluster_fwd_kernel: three (16 x Hp) row records + the BatchNorm sums + the argmax pairs per (parity, row group)
+static CodeXch code_cluster_fwd_xch(int nblk, int nt) {
+  const size_t Hp = (size_t)nt * 16, row = (size_t)2 * nblk * 16 * Hp;
+  CodeXch x{};
+  x.h0 = row; x.h1 = 2 * row; x.p = 3 * row; x.a = x.p + (size_t)2 * nblk * 2 * Hp;
+  x.xcc = (x.a + (size_t)2 * nblk * nt * 32) * 8;
+  x.bytes = x.xcc + (size_t)nblk * nt * sizeof(unsigned) + 16;
   return x;
 }
-
-
-extern "C" int g2v_attn_code_rollout_fwd(const int64_t* codes, const float* h_init, const float* enc, const float* enc_proj,
-                                         const g2v_code_dec_weights* w, const g2v_code_dec_saved* s, const uint8_t* keep_emb,
-                                         const uint8_t* keep_l0, float p_drop, int n_pre, int training, int S1, int B, int H,
-                                         int K, int Tw, void* workspace, size_t workspace_bytes, g2v_stream_t stream) {
-  G2V_REQUIRE(codes && h_init && w && s && workspace, "null pointer");
-  const int att = w->w_attn != nullptr;
-  G2V_REQUIRE((training ? (w->bn_running_mean == nullptr) == (w->bn_running_var == nullptr) : (w->bn_running_mean && w->bn_running_var)),
-              "BatchNorm running statistics: both or (training only) neither");
-  G2V_REQUIRE(w->emb && w->w_pre && w->b_pre && w->bn_w && w->bn_b && w->w_ih0 &&
-              w->w_hh0 && w->b_ih0 && w->b_hh0 && w->w_ih1 && w->w_hh1 && w->b_ih1 && w->b_hh1 && w->w_out && w->b_out,
-              "missing weight");
-  G2V_REQUIRE(!att || (w->b_attn && w->v_attn && enc && enc_proj && s->hp && s->attw), "attention: missing array");
-  G2V_REQUIRE(s->ids && s->ec && s->u && s->h0 && s->h1 && s->logits && s->bn_partial, "missing state buffer");
-  G2V_REQUIRE(!training || (s->a && s->bn_stats && s->gates0 && s->gates1), "missing saved buffer");
-  G2V_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "bad dropout probability");
-  if (!g2v_attn_code_rollout_ok(S1, B, H, K, Tw, att)) {
-    set_error("g2v_attn_code_rollout_fwd: shape not served (g2v_attn_code_rollout_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
-  if (workspace_bytes < g2v_attn_code_rollout_fwd_workspace(H, K, att)) {
-    set_error("g2v_attn_code_rollout_fwd: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
-  const void* al[] = {h_init, enc, enc_proj, w->emb, w->b_pre, w->bn_w, w->bn_b, w->b_ih0, w->b_hh0, w->b_ih1, w->b_hh1, w->b_out,
-                      w->b_attn, w->v_attn, s->ec, s->u, s->a, s->h0, s->h1, s->x1, s->gates0, s->gates1, s->logits, s->bn_partial,
-                      s->hp, keep_emb, keep_l0, workspace};
-  for (const void* p : al) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
-  hipStream_t st = (hipStream_t)stream;
-  const int Hin = att ? 2 * H : H;
-  if (g2v_attn_code_rollout_cluster_ok(S1, B, H, K, att) && code_cluster_xch_bytes(cdiv(B, 16), H) <= workspace_bytes &&
-      (!training || (s->a && s->bn_stats && s->gates0 && s->gates1))) {
-    // small batch: ONE persistent launch of (hidden-unit tile x row group) workgroups (code_cluster_fwd_kernel)
-    static bool attr_set = false;
-    const void* fn = (const void*)code_cluster_fwd_kernel;
-    int nocc = 0;
-    if (!attr_set) attr_set = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)code_cluster_dyn_lds()) == hipSuccess;
-    if (attr_set && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, code_cluster_dyn_lds()) == hipSuccess && nocc >= 1) {
-      const int nblk = cdiv(B, 16), nt = (H + 15) >> 4;
-      const size_t Hp = (size_t)nt * 16, rowrec = (size_t)2 * nblk * 16 * Hp;
-      unsigned long long* x0 = reinterpret_cast<unsigned long long*>(workspace);
-      CodeClArgs ca;
-      ca.codes = codes; ca.h_init = h_init; ca.keep_emb = keep_emb; ca.keep_l0 = keep_l0; ca.w = *w; ca.sv = *s;
-      ca.xu = x0; ca.xh0 = x0 + rowrec; ca.xh1 = x0 + 2 * rowrec; ca.xp = x0 + 3 * rowrec; ca.xa = ca.xp + (size_t)2 * nblk * 2 * Hp;
-      ca.xcc = reinterpret_cast<unsigned*>((char*)workspace + code_cluster_rec_bytes(nblk, H));
-      ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
-      ca.S1 = S1; ca.B = B; ca.H = H; ca.K = K; ca.n_pre = n_pre; ca.training = training; ca.p_drop = p_drop;
-      ca.nt = nt; ca.nblk = nblk;
-      if (hipMemsetAsync(x0, 0, code_cluster_xch_bytes(nblk, H), st) != hipSuccess) {
-        set_error("g2v_attn_code_rollout_fwd: clearing the exchange records failed");
-        return G2V_ERR_LAUNCH;
-      }
-      hipLaunchKernelGGL(code_cluster_fwd_kernel, dim3(nt * nblk), dim3(256), code_cluster_dyn_lds(), st, ca);
-      G2V_CHECK_LAUNCH();
-      return G2V_OK;
-    }
-  }
-  // ---- pack the weights into MFMA fragment order (one launch) ----
-  float* p = (float*)workspace;
-  PackBatch pb;
-  CodePackF pk{};
-  pb.n = 0;
-  pb.d[pb.n++] = PackDesc{w->w_pre, p, H, 1, 0, Hin, Hin, 0, 0}; pk.pre = p; p += pack_floats(H, 1, Hin);
-  pb.d[pb.n++] = PackDesc{w->w_ih0, p, H, 3, H, H, H, 0, 0}; pk.ih0 = p; p += pack_floats(H, 3, H);
-  pb.d[pb.n++] = PackDesc{w->w_hh0, p, H, 3, H, H, H, 0, 0}; pk.hh0 = p; p += pack_floats(H, 3, H);
-  pb.d[pb.n++] = PackDesc{w->w_ih1, p, H, 3, H, H, H, 0, 0}; pk.ih1 = p; p += pack_floats(H, 3, H);
-  pb.d[pb.n++] = PackDesc{w->w_hh1, p, H, 3, H, H, H, 0, 0}; pk.hh1 = p; p += pack_floats(H, 3, H);
-  pb.d[pb.n++] = PackDesc{w->w_out, p, K, 1, 0, H, H, 0, ct_ktiles_alloc(K)}; pk.out = p; p += (size_t)ct_ktiles_alloc(K) * pack_ks(H) * 256;
-  if (att) {
-    pb.d[pb.n++] = PackDesc{w->w_attn, p, H, 1, 0, H, 2 * H, 0, 0}; pk.attn_h = p; p += pack_floats(H, 1, H);
-  }
-  launch_pack(pb, st);
-  G2V_CHECK_LAUNCH();
-  const int scratch = ct_scratch((size_t)ct_fwd_lds(H, Hin, att ? Tw : 0, 0).total);
-  CodeDims dm{S1, B, H, K, Hin, att ? Tw : 0, p_drop, n_pre, training, cdiv(B, 16), att, scratch};
-  const size_t lds = (size_t)ct_fwd_lds(H, Hin, dm.Tw, scratch).total * sizeof(float);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)code_step_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  for (int j = 0; j <= S1; ++j)
-    hipLaunchKernelGGL(code_step_fwd_kernel, dim3(dm.nblk), dim3(CT_NTHR), lds, st, codes, h_init, enc, enc_proj, *w, pk, *s,
-                       keep_emb, keep_l0, dm, j);
-  G2V_CHECK_LAUNCH();
-  return G2V_OK;
+// code_cluster_bptt_kernel: the partial products of the 3H-long contractions, one (16 x Hp) record per (row group, matrix, producer tile)
+static CodeXch code_cluster_bptt_xch(int nblk, int nt) {
+  CodeXch x{};
+  x.xcc = (size_t)nblk * 4 * nt * 16 * ((size_t)nt * 16) * 8;
+  x.bytes = x.xcc + (size_t)nblk * nt * sizeof(unsigned) + 16;
+  return x;
 }
+static size_t code_cluster_dyn_lds() { return ((size_t)CCL_KT * CCL_KS + CCL_KS + (size_t)4 * CCL_KT + CCL_KS) * 64 * sizeof(float4); }
 
 // ---- backward workspace layout (bytes, every region 256-byte aligned) ----------------------------------------------------
 struct CtBwdWs {
@@ -1509,10 +1359,276 @@ static CtBwdWs ct_bwd_ws(int S1, int B, int H, int K, int Tw, int att) {
   l.total = o;
   return l;
 }
-extern "C" size_t g2v_attn_code_rollout_bwd_workspace(int S1, int B, int H, int K, int Tw, int attention) {
-  if (S1 < 1 || B < 1 || H < 1 || K < 1) return 0;
-  return ct_bwd_ws(S1, B, H, K, Tw, attention).total;
+
+// ---- the plan ------------------------------------------------------------------------------------------------------------
+enum CodeCall { CODE_FWD = 0, CODE_BWD = 1, CODE_BPTT = 2 };      // g2v_attn_code_rollout_fwd / _bwd, g2v_code_cluster_bptt
+struct CodeCallFacts {      // what the plan needs to know of ONE call beyond its sizes
+  bool entry;                     // the C entry itself is the caller: no row-count rule, and a shape it does not serve is refused (no CHAIN)
+  size_t workspace_bytes;
+  bool saved;                     // forward: not training, or a / bn_stats / gates0 / gates1 are there to be written
+  bool cluster_fwd, cluster_bptt; // the caller takes the cluster forward below the fused pair's row count / the cluster BPTT behind it
+  bool cluster_resident;          // code_cluster_fwd_resident: asked only once a plan says cluster (code_plan_call)
+};
+// the queries' call: a workspace that is large enough, everything accepted
+constexpr CodeCallFacts CODE_IDEAL_FACTS{true, ~(size_t)0, true, true, true, true};
+
+struct CodeRoutePlan {
+  int route, variant;             // G2V_CODE_ROUTE_*; 0: refused with `err` and `msg`.  variant 1: backward STEP with attention (a launch per step)
+  int nblk, nt;                   // 16-row groups, 16-unit tiles of H
+  size_t ws_need;                 // the call's size query: set for every shape, served or not
+  size_t pack_floats;             // forward STEP: the fragment images at the head of the workspace
+  CtBwdWs bw;                     // backward STEP: the workspace regions
+  size_t lds; int scratch;        // dynamic LDS bytes (STEP kernels, forward CLUSTER) and reduce_partials scratch floats (STEP)
+  CodeXch xch;                    // CLUSTER: the exchange records
+  int err; const char* msg;
+};
+static CodeRoutePlan code_route_plan(CodeCall call, int S1, int B, int H, int K, int Tw, bool att, int layers, int fused_min_rows,
+                                     int level, int cus, const CodeCallFacts& f) {
+  CodeRoutePlan pl{};
+  auto refuse = [&pl](int err, const char* msg) { pl.route = 0; pl.err = err; pl.msg = msg; return pl; };
+  auto chain = [&pl]() { pl.route = G2V_CODE_ROUTE_CHAIN; return pl; };
+  const int Hin = att ? 2 * H : H;
+  pl.nblk = B > 0 ? cdiv(B, 16) : 0; pl.nt = (H + 15) >> 4;
+  const bool cluster_dims = !att && H >= 16 && (H & 3) == 0 && H <= 16 * CCL_KS;
+  // sizes first: the size queries answer for every shape
+  if (call == CODE_FWD) {
+    pl.pack_floats = ct_fwd_pack_floats(H, K, att);
+    pl.ws_need = al256(pl.pack_floats * sizeof(float));
+    if (cluster_dims) {      // the cluster kernel's exchange records at its largest grid (no device: an MI355X's 256 CUs)
+      const size_t c = code_cluster_fwd_xch((cus > 0 ? cus : 256) / pl.nt + 1, pl.nt).bytes;
+      if (c > pl.ws_need) pl.ws_need = c;
+    }
+  } else if (call == CODE_BWD) {
+    if (S1 >= 1 && B >= 1 && H >= 1 && K >= 1) pl.bw = ct_bwd_ws(S1, B, H, K, Tw, att);
+    pl.ws_need = pl.bw.total;
+  } else {
+    pl.ws_need = code_cluster_bptt_xch(pl.nblk, pl.nt).bytes;
+  }
+  // the (hidden-unit tile x row group) grid of either cluster kernel with a CU per workgroup
+  const bool cluster_grid = S1 >= 1 && B >= 1 && cluster_dims && (int64_t)pl.nt * pl.nblk <= cus && level > 0;
+  if (call == CODE_BPTT) {
+    if (!cluster_grid) return refuse(G2V_ERR_UNSUPPORTED, "shape not served (g2v_attn_code_rollout_cluster_ok)");
+    if (f.workspace_bytes < pl.ws_need) return refuse(G2V_ERR_WORKSPACE, "workspace too small");
+    pl.route = G2V_CODE_ROUTE_CLUSTER; pl.xch = code_cluster_bptt_xch(pl.nblk, pl.nt);
+    return pl;
+  }
+  // what the step kernels serve, and with them the cluster forward
+  bool served = layers == 2 && S1 >= 1 && B >= 1 && H >= 16 && (H & 3) == 0 && H <= 256 && K >= 4 && (K & 3) == 0 && K <= 1024 &&
+                (!att || (Tw >= 1 && Tw <= CT_MAX_TW));
+  if (served) {
+    const int Hp = (H + 15) & ~15;
+    if (att && (2 * Hp + 1024 > 16 * (((3 * H + 15) & ~15) + 4) || 2 * 16 * Tw > 16 * (Hp + 4))) served = false;      // what Part A borrows
+    served = served && (size_t)ct_fwd_lds(H, Hin, att ? Tw : 0, 1024).total * 4 <= 160 * 1024 && (size_t)ct_bwd_lds(H, K).total * 4 <= 160 * 1024;
+  }
+  if (!served) return f.entry ? refuse(G2V_ERR_UNSUPPORTED, "shape not served (g2v_attn_code_rollout_ok)") : chain();
+  const bool cluster_shape = cluster_grid && ((K + 15) >> 4) <= CCL_KT * pl.nt;
+  const bool pair = f.entry || B >= fused_min_rows;      // forward and backward behind the C entries: g2v_attn_code_rollout_fwd / _bwd
+  if (!pair && !(cluster_shape && f.cluster_fwd)) return chain();
+  if (f.workspace_bytes < pl.ws_need) return refuse(G2V_ERR_WORKSPACE, "workspace too small");
+  if (call == CODE_BWD) {
+    if (!pair) {      // behind a cluster forward below the fused pair's row count: the cells' BPTT as a cluster launch, or the chain
+      pl.route = f.cluster_bptt ? G2V_CODE_ROUTE_CLUSTER : G2V_CODE_ROUTE_CHAIN;
+      return pl;
+    }
+    pl.route = G2V_CODE_ROUTE_STEP; pl.variant = att ? 1 : 0;
+    pl.lds = (size_t)ct_bwd_lds(H, K).total * sizeof(float);
+    pl.scratch = (2 * ((H + 15) & ~15) + 2048 <= 16 * (((3 * H + 15) & ~15) + 4)) ? 2048 : 1024;      // (Part A's reduction scratch lives in Gh)
+    return pl;
+  }
+  // The entry takes the cluster kernel wherever it can -- from fused_min_rows rows too, which no switch of the caller's turns off --
+  // and falls back to the step kernels where this call cannot: the records do not fit, nothing to save into, not resident.
+  pl.xch = code_cluster_fwd_xch(pl.nblk, pl.nt);
+  if (cluster_shape && pl.xch.bytes <= f.workspace_bytes && f.saved && f.cluster_resident) {
+    pl.route = G2V_CODE_ROUTE_CLUSTER; pl.lds = code_cluster_dyn_lds();
+  } else {
+    pl.route = G2V_CODE_ROUTE_STEP;
+    pl.scratch = ct_scratch((size_t)ct_fwd_lds(H, Hin, att ? Tw : 0, 0).total);
+    pl.lds = (size_t)ct_fwd_lds(H, Hin, att ? Tw : 0, pl.scratch).total * sizeof(float);
+  }
+  return pl;
 }
+// ... of the queries: the entry's own call of this shape under the bound context's level on this device
+static CodeRoutePlan code_plan_ideal(CodeCall call, int S1, int B, int H, int K, int Tw, int att) {
+  return code_route_plan(call, S1, B, H, K, Tw, att != 0, 2, 0, g2v_internal_options().persist, g2v_internal_device_cus(), CODE_IDEAL_FACTS);
+}
+extern "C" int g2v_attn_code_rollout_route(int backward, int S1, int B, int H, int K, int Tw, int attention, int layers, int fused_min_rows,
+                                           int persistent, int cus, int facts) {
+  if (backward < 0 || backward > 2) return 0;
+  CodeCallFacts f = CODE_IDEAL_FACTS;
+  f.entry = (facts & G2V_CODE_PLAN_ENTRY) != 0 || backward == 2;
+  f.cluster_fwd = !(facts & G2V_CODE_PLAN_NO_CLUSTER_FWD);
+  f.cluster_bptt = !(facts & G2V_CODE_PLAN_NO_CLUSTER_BPTT);
+  if (facts & G2V_CODE_PLAN_WS_SMALL) f.workspace_bytes = 0;
+  const CodeRoutePlan pl = code_route_plan((CodeCall)backward, S1, B, H, K, Tw, attention != 0, layers, fused_min_rows,
+                                           persistent < 0 ? g2v_internal_options().persist : persistent,
+                                           cus > 0 ? cus : g2v_internal_device_cus(), f);
+  return pl.route | (pl.variant << 8);
+}
+// The older queries (include/g2v.h), each a field of the ideal call's plan.
+extern "C" int g2v_attn_code_rollout_ok(int S1, int B, int H, int K, int Tw, int attention) {
+  return code_plan_ideal(CODE_FWD, S1, B, H, K, Tw, attention).route != 0;
+}
+extern "C" int g2v_attn_code_rollout_cluster_ok(int S1, int B, int H, int K, int attention) {
+  return code_plan_ideal(CODE_FWD, S1, B, H, K, 0, attention).route == G2V_CODE_ROUTE_CLUSTER;
+}
+extern "C" size_t g2v_attn_code_rollout_fwd_workspace(int H, int K, int attention) { return code_plan_ideal(CODE_FWD, 1, 16, H, K, 1, attention).ws_need; }
+extern "C" size_t g2v_attn_code_rollout_bwd_workspace(int S1, int B, int H, int K, int Tw, int attention) {
+  return code_plan_ideal(CODE_BWD, S1, B, H, K, Tw, attention).ws_need;
+}
+extern "C" size_t g2v_code_cluster_bptt_workspace(int B, int H) { return code_plan_ideal(CODE_BPTT, 1, B, H, 0, 0, 0).ws_need; }
+
+// The entries' plan: residency of the cluster forward is asked only once a plan says cluster.
+static bool code_cluster_fwd_resident() {
+  static bool attr_set = false;
+  const void* fn = (const void*)code_cluster_fwd_kernel;
+  int nocc = 0;
+  if (!attr_set) attr_set = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)code_cluster_dyn_lds()) == hipSuccess;
+  return attr_set && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, code_cluster_dyn_lds()) == hipSuccess && nocc >= 1;
+}
+static CodeRoutePlan code_plan_call(CodeCall call, int S1, int B, int H, int K, int Tw, bool att, CodeCallFacts f) {
+  const int level = g2v_internal_options().persist, cus = g2v_internal_device_cus();
+  CodeRoutePlan pl = code_route_plan(call, S1, B, H, K, Tw, att, 2, 0, level, cus, f);
+  if (call == CODE_FWD && pl.route == G2V_CODE_ROUTE_CLUSTER && !code_cluster_fwd_resident()) {
+    f.cluster_resident = false;
+    pl = code_route_plan(call, S1, B, H, K, Tw, att, 2, 0, level, cus, f);
+  }
+  return pl;
+}
+#define CODE_REFUSE(pl)                            \
+  do {                                             \
+    if ((pl).route == 0) {                         \
+      set_error("%s: %s", __func__, (pl).msg);     \
+      return (pl).err;                             \
+    }                                              \
+  } while (0)
+
+// The cells' BPTT of the attention-free rollout at small batch as one persistent cluster launch (code_cluster_bptt_kernel; the
+// grid rule of the cluster forward).  dh_top (S1,B,H) = dLogits W_out for every step (g2v_linear_bwd_data); writes dgi0 /
+// dgh0 / dgi1 / dgh1 (S1,B,3H), da (S1,B,H) = the gradient w.r.t. a_t before its ReLU mask (BatchNorm's backward is the caller's
+// next launch), d_hidden0 (2,B,H).  s: gates0 / gates1 / h0 / h1 of the forward.
+extern "C" int g2v_code_cluster_bptt(const float* dh_top, const g2v_code_dec_weights* w, const g2v_code_dec_saved* s,
+                                     const uint8_t* keep_l0, float p_drop, float* dgi0, float* dgh0, float* dgi1, float* dgh1,
+                                     float* da, float* d_hidden0, int S1, int B, int H, void* workspace, size_t workspace_bytes,
+                                     g2v_stream_t stream) {
+  G2V_REQUIRE(dh_top && w && s && dgi0 && dgh0 && dgi1 && dgh1 && da && d_hidden0 && workspace, "null pointer");
+  G2V_REQUIRE(w->w_ih0 && w->w_hh0 && w->w_ih1 && w->w_hh1 && s->gates0 && s->gates1 && s->h0 && s->h1, "missing array");
+  G2V_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "bad dropout probability");
+  CodeCallFacts f = CODE_IDEAL_FACTS;
+  f.workspace_bytes = workspace_bytes;
+  const CodeRoutePlan pl = code_plan_call(CODE_BPTT, S1, B, H, 0, 0, false, f);
+  CODE_REFUSE(pl);
+  const void* al[] = {dh_top, keep_l0, dgi0, dgh0, dgi1, dgh1, da, d_hidden0, s->gates0, s->gates1, s->h0, s->h1, workspace};
+  for (const void* p : al) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
+  hipStream_t st = (hipStream_t)stream;
+  int nocc = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, (const void*)code_cluster_bptt_kernel, 256, 0) != hipSuccess || nocc < 1) {
+    set_error("g2v_code_cluster_bptt: the kernel does not fit a CU");
+    return G2V_ERR_LAUNCH;
+  }
+  CodeClBwdArgs ca;
+  ca.dh_top = dh_top; ca.keep_l0 = keep_l0; ca.w = *w; ca.sv = *s;
+  ca.dgi0 = dgi0; ca.dgh0 = dgh0; ca.dgi1 = dgi1; ca.dgh1 = dgh1; ca.da = da; ca.d_hidden0 = d_hidden0;
+  ca.xq = reinterpret_cast<unsigned long long*>(workspace);
+  ca.nt = pl.nt; ca.nblk = pl.nblk;
+  ca.xcc = reinterpret_cast<unsigned*>((char*)workspace + pl.xch.xcc);
+  ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
+  ca.S1 = S1; ca.B = B; ca.H = H; ca.p_drop = p_drop;
+  if (hipMemsetAsync(workspace, 0, pl.xch.bytes, st) != hipSuccess) {
+    set_error("g2v_code_cluster_bptt: clearing the exchange records failed");
+    return G2V_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(code_cluster_bptt_kernel, dim3(pl.nt * pl.nblk), dim3(256), 0, st, ca);
+  G2V_CHECK_LAUNCH();
+  return G2V_OK;
+}
+
+// ---- forward: one launcher per route -------------------------------------------------------------------------------------
+struct CodeFwdCall {
+  const int64_t* codes; const float* h_init; const float* enc; const float* enc_proj; const g2v_code_dec_weights* w;
+  const g2v_code_dec_saved* s; const uint8_t* keep_emb; const uint8_t* keep_l0;
+  float p_drop; int n_pre, training, S1, B, H, K, Tw, att;
+  void* workspace; hipStream_t st;
+};
+// CLUSTER: ONE persistent launch of (hidden-unit tile x row group) workgroups at small batch (code_cluster_fwd_kernel)
+static int code_fwd_launch_cluster(const CodeFwdCall& c, const CodeRoutePlan& pl) {
+  unsigned long long* x0 = reinterpret_cast<unsigned long long*>(c.workspace);
+  CodeClArgs ca;
+  ca.codes = c.codes; ca.h_init = c.h_init; ca.keep_emb = c.keep_emb; ca.keep_l0 = c.keep_l0; ca.w = *c.w; ca.sv = *c.s;
+  ca.xu = x0; ca.xh0 = x0 + pl.xch.h0; ca.xh1 = x0 + pl.xch.h1; ca.xp = x0 + pl.xch.p; ca.xa = x0 + pl.xch.a;
+  ca.xcc = reinterpret_cast<unsigned*>((char*)c.workspace + pl.xch.xcc);
+  ca.fault = const_cast<unsigned*>(g2v_internal_persist_fault_ptr());
+  ca.S1 = c.S1; ca.B = c.B; ca.H = c.H; ca.K = c.K; ca.n_pre = c.n_pre; ca.training = c.training; ca.p_drop = c.p_drop;
+  ca.nt = pl.nt; ca.nblk = pl.nblk;
+  if (hipMemsetAsync(x0, 0, pl.xch.bytes, c.st) != hipSuccess) {
+    set_error("g2v_attn_code_rollout_fwd: clearing the exchange records failed");
+    return G2V_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(code_cluster_fwd_kernel, dim3(pl.nt * pl.nblk), dim3(256), pl.lds, c.st, ca);
+  G2V_CHECK_LAUNCH();
+  return G2V_OK;
+}
+// STEP: the weights into MFMA fragment order (one launch), then S1 + 1 launches of code_step_fwd_kernel
+static int code_fwd_launch_steps(const CodeFwdCall& c, const CodeRoutePlan& pl) {
+  const g2v_code_dec_weights* w = c.w;
+  const int H = c.H, K = c.K, Hin = c.att ? 2 * H : H;
+  float* p = (float*)c.workspace;
+  PackBatch pb;
+  CodePackF pk{};
+  pb.n = 0;
+  pb.d[pb.n++] = PackDesc{w->w_pre, p, H, 1, 0, Hin, Hin, 0, 0}; pk.pre = p; p += pack_floats(H, 1, Hin);
+  pb.d[pb.n++] = PackDesc{w->w_ih0, p, H, 3, H, H, H, 0, 0}; pk.ih0 = p; p += pack_floats(H, 3, H);
+  pb.d[pb.n++] = PackDesc{w->w_hh0, p, H, 3, H, H, H, 0, 0}; pk.hh0 = p; p += pack_floats(H, 3, H);
+  pb.d[pb.n++] = PackDesc{w->w_ih1, p, H, 3, H, H, H, 0, 0}; pk.ih1 = p; p += pack_floats(H, 3, H);
+  pb.d[pb.n++] = PackDesc{w->w_hh1, p, H, 3, H, H, H, 0, 0}; pk.hh1 = p; p += pack_floats(H, 3, H);
+  pb.d[pb.n++] = PackDesc{w->w_out, p, K, 1, 0, H, H, 0, ct_ktiles_alloc(K)}; pk.out = p; p += (size_t)ct_ktiles_alloc(K) * pack_ks(H) * 256;
+  if (c.att) {
+    pb.d[pb.n++] = PackDesc{w->w_attn, p, H, 1, 0, H, 2 * H, 0, 0}; pk.attn_h = p; p += pack_floats(H, 1, H);
+  }
+  launch_pack(pb, c.st);
+  G2V_CHECK_LAUNCH();
+  CodeDims dm{c.S1, c.B, H, K, Hin, c.att ? c.Tw : 0, c.p_drop, c.n_pre, c.training, pl.nblk, c.att, pl.scratch};
+  if (pl.lds > 48 * 1024)
+    (void)hipFuncSetAttribute((const void*)code_step_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  for (int j = 0; j <= c.S1; ++j)
+    hipLaunchKernelGGL(code_step_fwd_kernel, dim3(pl.nblk), dim3(CT_NTHR), pl.lds, c.st, c.codes, c.h_init, c.enc, c.enc_proj, *w, pk, *c.s,
+                       c.keep_emb, c.keep_l0, dm, j);
+  G2V_CHECK_LAUNCH();
+  return G2V_OK;
+}
+
+extern "C" int g2v_attn_code_rollout_fwd(const int64_t* codes, const float* h_init, const float* enc, const float* enc_proj,
+                                         const g2v_code_dec_weights* w, const g2v_code_dec_saved* s, const uint8_t* keep_emb,
+                                         const uint8_t* keep_l0, float p_drop, int n_pre, int training, int S1, int B, int H,
+                                         int K, int Tw, void* workspace, size_t workspace_bytes, g2v_stream_t stream) {
+  G2V_REQUIRE(codes && h_init && w && s && workspace, "null pointer");
+  const int att = w->w_attn != nullptr;
+  G2V_REQUIRE((training ? (w->bn_running_mean == nullptr) == (w->bn_running_var == nullptr) : (w->bn_running_mean && w->bn_running_var)),
+              "BatchNorm running statistics: both or (training only) neither");
+  G2V_REQUIRE(w->emb && w->w_pre && w->b_pre && w->bn_w && w->bn_b && w->w_ih0 &&
+              w->w_hh0 && w->b_ih0 && w->b_hh0 && w->w_ih1 && w->w_hh1 && w->b_ih1 && w->b_hh1 && w->w_out && w->b_out,
+              "missing weight");
+  G2V_REQUIRE(!att || (w->b_attn && w->v_attn && enc && enc_proj && s->hp && s->attw), "attention: missing array");
+  G2V_REQUIRE(s->ids && s->ec && s->u && s->h0 && s->h1 && s->logits && s->bn_partial, "missing state buffer");
+  const bool saved = s->a && s->bn_stats && s->gates0 && s->gates1;
+  G2V_REQUIRE(!training || saved, "missing saved buffer");
+  G2V_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "bad dropout probability");
+  CodeCallFacts f = CODE_IDEAL_FACTS;
+  f.workspace_bytes = workspace_bytes; f.saved = !training || saved;
+  const CodeRoutePlan pl = code_plan_call(CODE_FWD, S1, B, H, K, Tw, att != 0, f);
+  CODE_REFUSE(pl);
+  const void* al[] = {h_init, enc, enc_proj, w->emb, w->b_pre, w->bn_w, w->bn_b, w->b_ih0, w->b_hh0, w->b_ih1, w->b_hh1, w->b_out,
+                      w->b_attn, w->v_attn, s->ec, s->u, s->a, s->h0, s->h1, s->x1, s->gates0, s->gates1, s->logits, s->bn_partial,
+                      s->hp, keep_emb, keep_l0, workspace};
+  for (const void* p : al) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
+  const CodeFwdCall c{codes, h_init, enc, enc_proj, w, s, keep_emb, keep_l0, p_drop, n_pre, training, S1, B, H, K, Tw, att,
+                      workspace, (hipStream_t)stream};
+  switch (pl.route) {
+    case G2V_CODE_ROUTE_CLUSTER: return code_fwd_launch_cluster(c, pl);
+    default: return code_fwd_launch_steps(c, pl);
+  }
+}
+
+// ---- backward: STEP alone sits behind this entry (variant 0: one launch for the whole BPTT; variant 1: one per step) ------------
 
 extern "C" int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc, const float* enc_proj,
                                          const g2v_code_dec_weights* w, const g2v_code_dec_saved* s, const g2v_code_dec_grads* g,
@@ -1528,15 +1644,11 @@ extern "C" int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc
               "attention: missing array");
   const bool drop = keep_l0 && p_drop > 0.f;
   G2V_REQUIRE(!drop || s->x1, "inter-layer dropout: x1 was not saved");
-  if (!g2v_attn_code_rollout_ok(S1, B, H, K, Tw, att)) {
-    set_error("g2v_attn_code_rollout_bwd: shape not served (g2v_attn_code_rollout_ok)");
-    return G2V_ERR_UNSUPPORTED;
-  }
-  const CtBwdWs L = ct_bwd_ws(S1, B, H, K, Tw, att);
-  if (workspace_bytes < L.total) {
-    set_error("g2v_attn_code_rollout_bwd: workspace too small");
-    return G2V_ERR_WORKSPACE;
-  }
+  CodeCallFacts f = CODE_IDEAL_FACTS;
+  f.workspace_bytes = workspace_bytes;
+  const CodeRoutePlan pl = code_plan_call(CODE_BWD, S1, B, H, K, Tw, att != 0, f);
+  CODE_REFUSE(pl);
+  const CtBwdWs& L = pl.bw;
   G2V_REQUIRE(ct_al16(workspace) && ct_al16(d_logits) && ct_al16(g->d_hidden0), "16-byte alignment");
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)workspace;
@@ -1565,10 +1677,8 @@ extern "C" int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc
   a.dhp = att ? (float*)(base + L.dhp) : nullptr; a.d_ep = att ? (float*)(base + L.d_ep) : nullptr; a.d_enc = att ? g->d_enc : nullptr;
   a.dv_partial = att ? (float*)(base + L.dvp) : nullptr;
   a.bn_part = (float*)(base + L.bn_part); a.bn_sums = (float*)(base + L.bn_sums); a.d_hidden0 = g->d_hidden0;
-  const int Hp = (H + 15) & ~15;
-  const int scratch = (2 * Hp + 2048 <= 16 * (((3 * H + 15) & ~15) + 4)) ? 2048 : 1024;      // (Part A's reduction scratch lives in Gh)
-  CodeDims dm{S1, B, H, K, Hin, att ? Tw : 0, drop ? p_drop : 0.f, 0, 1, cdiv(B, 16), att, scratch};
-  const size_t lds = (size_t)ct_bwd_lds(H, K).total * sizeof(float);
+  CodeDims dm{S1, B, H, K, Hin, att ? Tw : 0, drop ? p_drop : 0.f, 0, 1, pl.nblk, att, pl.scratch};
+  const size_t lds = pl.lds;
   void* wgws = base + L.wg;
   const size_t wgn = L.emb - L.wg;
   int rc;
@@ -1576,14 +1686,14 @@ extern "C" int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc
   float* wae = wpe + (size_t)H * H;
   float* dwh = wae + (size_t)H * H;
   float* dwe = dwh + (size_t)H * H;
-  if (!att) {
+  if (pl.variant == 0) {      // no attention: the whole BPTT in one launch
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)code_bptt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(code_bptt_kernel, dim3(dm.nblk), dim3(CT_NTHR), lds, st, a, dm);
     hipLaunchKernelGGL(code_bn_bwd_apply_kernel, dim3(dm.nblk, S1), dim3(256), (2 * H + 1024) * sizeof(float), st, a, dm);
     G2V_CHECK_LAUNCH();
     // d e = du W_pre over all S1 x B rows
     if ((rc = g2v_linear_bwd_data(a.du, H, w->w_pre, a.dec, H, M, H, H, 0, stream)) != G2V_OK) return rc;
-  } else {
+  } else {                    // attention: one launch per step
     hipLaunchKernelGGL(code_split_cols_kernel, dim3(cdiv(H * H, 256)), dim3(256), 0, st, w->w_pre, w->w_attn, wpe, wae, H);
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute((const void*)code_step_bwd_att_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -572,6 +572,17 @@ def gru_route(T, B, H, ndir=1, *, backward=False, cluster=-1, resident_rows=-1, 
     return name + (f"*{r >> 8}" if r >> 8 else "")
 
 
+def code_route(S1, B, H, K, Tw=0, att=False, *, backward=False, layers=2, fused_min_rows=0, persistent=-1, cus=0, facts=()) -> str:
+    """g2v_attn_code_rollout_route as a name: "CLUSTER", "STEP", "STEP*1" (variant 1: a launch per step), "CHAIN"; "" where the call
+    is refused.  backward: False / True, or 2 for g2v_code_cluster_bptt called by itself; facts: names of G2V_CODE_PLAN_* bits;
+    -1 / cus=0: the bound context's level / the device's CU count."""
+    r = _lib_().g2v_attn_code_rollout_route(int(backward), int(S1), int(B), int(H), int(K), int(Tw), int(bool(att)), int(layers),
+                                            int(fused_min_rows), int(persistent), int(cus),
+                                            sum(_lib.CONSTANTS["G2V_CODE_PLAN_" + f] for f in facts))
+    name = {v: k[len("G2V_CODE_ROUTE_"):] for k, v in _lib.CONSTANTS.items() if k.startswith("G2V_CODE_ROUTE_")}.get(r & 0xff, "")
+    return name + (f"*{r >> 8}" if r >> 8 else "")
+
+
 def gru_dirs_fwd(dirs, T, B, H, *, lengths=None, hs_ld=None, row_off=None):
     """dirs: list (1 or 2) of dicts gi, w_hh, b_hh, h0, hs, h_n, gates, reverse -- ONE launch for both directions.
     With gi=None and x, w_ih, b_ih, in_dim given the input projection is fused into the kernel (H == in_dim == 64).
@@ -721,15 +732,6 @@ def bn_running_update(bn_stats, running_mean, running_var, steps, H, B):
 
 
 # ------------------------------------------------------------------------------------------ Part d: fused code-decoder rollout
-def code_rollout_ok(S1, B, H, K, Tw, att) -> bool:
-    return bool(_lib_().g2v_attn_code_rollout_ok(int(S1), int(B), int(H), int(K), int(Tw), int(bool(att))))
-
-
-def code_rollout_cluster_ok(S1, B, H, K, att) -> bool:
-    """g2v_attn_code_rollout_fwd runs this shape as one persistent cluster launch (small batch, no attention: include/g2v.h)"""
-    return bool(_lib_().g2v_attn_code_rollout_cluster_ok(int(S1), int(B), int(H), int(K), int(bool(att))))
-
-
 def code_cluster_bptt(dh_top, weights: dict, saved: dict, keep_l0, p_drop, S1, B, H):
     """g2v_code_cluster_bptt: the GRU cells' BPTT of the attention-free rollout as one persistent cluster launch (small batch).
     Returns (dgi0, dgh0, dgi1, dgh1 (S1,B,3H), da (S1,B,H), d_hidden0 (2,B,H))."""

@@ -51,39 +51,42 @@ def decoder_params(dec) -> List[torch.Tensor]:
     return ps
 
 
-# Batch size from which the decode steps run as the FUSED per-step kernels (g2v_attn_code_rollout_fwd / _bwd, csrc/t2e_rollout.hip:
-# one 512-thread workgroup per 16 batch rows, everything between two BatchNorm seams in one launch).  Below it a batch has too
-# few row tiles to fill the chip and the column-split per-operator kernels (one launch each, every CU streaming a slice of the
-# weights) are faster -- the same crossover as the pose decoder's (dec_rollout.hip, "split" kernels).
+# Which kernels run a call is decided once per forward, by the library's plan (include/g2v.h: g2v_attn_code_rollout_route; DESIGN.md
+# 3.3.1); the three switches below go into the query as its arguments and facts.
+# Batch size from which the decode steps run as the FUSED PAIR g2v_attn_code_rollout_fwd / _bwd (csrc/t2e_rollout.hip: one 512-thread
+# workgroup per 16 batch rows, everything between two BatchNorm seams in one launch).  Below it a batch has too few row tiles to
+# fill the chip and the column-split per-operator kernels (one launch each, every CU streaming a slice of the weights) are faster
+# -- the same crossover as the pose decoder's (dec_rollout.hip, "split" kernels).  Lowering it does NOT force the step forward:
+# the entry runs the cluster kernel wherever its grid fits (route "CLUSTER" / "STEP"); the persistent level 0 does.
 FUSED_MIN_ROWS = 1024
 # Below FUSED_MIN_ROWS, without attention, while the (hidden-unit tile x row group) grid has a CU per workgroup (B <= 304 at
-# H = 200): the FORWARD rollout is one persistent cluster launch behind the same C entry (csrc/t2e_rollout.hip:
-# code_cluster_fwd_kernel; round 5: ~9 launches per decode step at the reference's B = 128 before); the backward stays the
-# per-operator chain below, which reads the arrays that launch saved.  False = the per-operator forward (tests, A/B).
+# H = 200): the FORWARD rollout is one persistent cluster launch behind the same C entry (code_cluster_fwd_kernel; round 5: ~9
+# launches per decode step at the reference's B = 128 before).  False = the per-operator forward (tests, A/B).
 CLUSTER_FORWARD = True
-CLUSTER_BACKWARD = True      # behind a cluster forward: the GRU cells' BPTT as one persistent cluster launch too (g2v_code_cluster_bptt)
-CLUSTER_CALLS = 0
+CLUSTER_BACKWARD = True      # behind such a forward: the GRU cells' BPTT as one persistent cluster launch too (g2v_code_cluster_bptt);
+                             # False = the per-operator chain on the arrays the cluster forward saved
+FUSED_CALLS = 0          # forwards whose backward route is STEP (tests assert that the path under test actually ran)
+CLUSTER_CALLS = 0        # cluster forwards with a CLUSTER or CHAIN backward
 CLUSTER_BPTT_CALLS = 0
-FUSED_CALLS = 0          # forwards served by the fused kernels (tests assert that the path under test actually ran)
+LAST_PLAN = None         # (forward route, backward route) of the last forward, as ops.code_route names them
 LAST_SAVED = None        # the last forward's greedy codes and post-BatchNorm activations, whichever kernels served it (tests read the
                          # discrete decisions the kernels took and hand them to the oracle)
+CHAIN_SMALL_ROWS = 1024  # the per-operator chain's row count up to which a step's small pieces are worth fusing (RolloutPlan)
 
 
-def _cluster_ok(hidden0, enc_out, spec: RolloutSpec, params) -> bool:
-    if not CLUSTER_FORWARD or spec.L != 2 or spec.att or hidden0.shape[1] >= FUSED_MIN_ROWS:
-        return False
-    B, H = hidden0.shape[1], hidden0.shape[2]
-    K = params[5 + 4 * spec.L].shape[0]
-    return ops.code_rollout_ok(spec.steps, B, H, K, 0, False) and ops.code_rollout_cluster_ok(spec.steps, B, H, K, False)
+class RolloutPlan:
+    """What one forward + backward of CodeDecoderRollout runs on: the two routes of the library's plan and the four size rules of
+    the per-operator chain.  Built once by the forward, kept on ctx; the backward reads nothing else."""
 
-
-def _fused_ok(hidden0, enc_out, spec: RolloutSpec, params) -> bool:
-    if spec.L != 2 or hidden0.shape[1] < FUSED_MIN_ROWS:
-        return False
-    B, H = hidden0.shape[1], hidden0.shape[2]
-    K = params[5 + 4 * spec.L].shape[0]
-    Tw = enc_out.shape[0] if spec.att else 0
-    return ops.code_rollout_ok(spec.steps, B, H, K, Tw, spec.att)
+    def __init__(self, S1, B, H, K, Tw, L, att):
+        facts = (() if CLUSTER_FORWARD else ("NO_CLUSTER_FWD",)) + (() if CLUSTER_BACKWARD else ("NO_CLUSTER_BPTT",))
+        kw = dict(layers=L, fused_min_rows=FUSED_MIN_ROWS, facts=facts)
+        self.fwd = ops.code_route(S1, B, H, K, Tw, att, **kw)
+        self.bwd = ops.code_route(S1, B, H, K, Tw, att, backward=True, **kw)
+        self.cell = ops.gru_cell_ok(H, H, B)                     # input projection + GRU cell in one launch, both directions
+        self.fused_head = att and B <= CHAIN_SMALL_ROWS          # forward: argmax + embedding + attention in one launch, out + query in one
+        self.dv_slabs = att and B <= CHAIN_SMALL_ROWS            # backward: d_v's per-row partials of every step, ONE reduction behind the loop
+        self.bn_steps = B < CHAIN_SMALL_ROWS                     # behind the cluster BPTT: every step's BatchNorm backward in one launch
 
 
 def _fused_weights(spec, params, H):
@@ -101,14 +104,10 @@ def _fused_weights(spec, params, H):
     return wd
 
 
-def _fused_forward(ctx, hidden0, enc_out, spec: RolloutSpec, params, cluster: bool = False):
-    """The S1 decode steps as S1 + 1 launches of ONE kernel (include/g2v.h: g2v_attn_code_rollout_fwd); cluster=True: the same entry
-    at small batch (one persistent launch), with the context laid out for the PER-OPERATOR backward."""
-    global FUSED_CALLS, CLUSTER_CALLS, LAST_SAVED
-    if cluster:
-        CLUSTER_CALLS += 1
-    else:
-        FUSED_CALLS += 1
+def _entry_forward(ctx, plan: RolloutPlan, hidden0, enc_out, spec: RolloutSpec, params):
+    """Forward routes CLUSTER and STEP: the S1 decode steps behind ONE C entry (include/g2v.h: g2v_attn_code_rollout_fwd), which
+    runs one persistent cluster launch or S1 + 1 launches of the step kernel.  The context is laid out for plan.bwd."""
+    global LAST_SAVED
     S1, att = spec.steps, spec.att
     B, H = hidden0.shape[1], hidden0.shape[2]
     K = params[13].shape[0]
@@ -137,27 +136,23 @@ def _fused_forward(ctx, hidden0, enc_out, spec: RolloutSpec, params, cluster: bo
     if spec.defer_bn is not None:
         spec.defer_bn.append((sv["bn_stats"], sv["bn_stats"].view(-1)[H:], 2 * H, S1, B, H))
     ctx.save_for_backward(hidden0, enc_out, *params)
-    if cluster:
-        # what CodeDecoderRollout.backward's per-operator chain reads, as views of the arrays the launch saved
-        ctx.spec, ctx.dims, ctx.fused, ctx.cell = spec, (S1, B, H, K, Hin, spec.L), False, ops.gru_cell_ok(H, H, B)
+    ctx.spec, ctx.dims = spec, (S1, B, H, K, Hin, spec.L)
+    # (the logits are this node's OUTPUT: kept on ctx they would close a reference cycle output -> grad_fn -> ctx -> output, the
+    #  step's buffers would live until the garbage collector runs -- inside a hipGraph capture that ended in a segfault of
+    #  capture_end; no backward reads them)
+    saved = {k: t for k, t in sv.items() if k != "logits"}
+    if plan.bwd.startswith("STEP"):          # g2v_attn_code_rollout_bwd: the C structs of the same arrays
+        ctx.bufs = dict(wd=wd, sv=saved, enc=enc, ep=ep, mask_emb=mask_emb, mask_l0=mask_l0, drop=drop, Tw=Tw)
+    else:
+        # CHAIN: what the per-operator chain reads, as views of the arrays the launch saved; CLUSTER: what its batched tail reads of
+        # them, and for g2v_code_cluster_bptt the C structs
         gru = [(wd["w_ih0"], wd["w_hh0"], wd["b_ih0"], wd["b_hh0"]), (wd["w_ih1"], wd["w_hh1"], wd["b_ih1"], wd["b_hh1"])]
         ctx.bufs = dict(ids=sv["ids"], EC=sv["ec"], U=sv["u"], A=sv["a"], SM=sv["bn_stats"][:, 0], SI=sv["bn_stats"][:, 1],
                         Hs=[sv["h0"], sv["h1"]], GATES=[sv["gates0"], sv["gates1"]], mask_emb=mask_emb, mask_l0=mask_l0,
                         scale_l0=1.0 / (1.0 - spec.dropout_p) if drop else 1.0, emb_w=wd["emb"], pre_w=wd["w_pre"],
                         out_w=wd["w_out"], gru=gru)
-        # (and for the cells' BPTT as a cluster launch: the C structs of the same arrays, without this node's output)
-        ctx.cluster = dict(wd=wd, sv={k: t for k, t in sv.items() if k != "logits"}, p=spec.dropout_p if drop else 0.0)
-        LAST_SAVED = {"ids": sv["ids"], "a": sv["a"]}
-        AW = f32(0)
-        ctx.mark_non_differentiable(AW)
-        ctx.set_materialize_grads(False)
-        return full, AW
-    ctx.spec, ctx.dims, ctx.fused = spec, (S1, B, H, K, Hin, spec.L), True
-    # (the logits are this node's OUTPUT: kept on ctx they would close a reference cycle output -> grad_fn -> ctx -> output, the
-    #  step's buffers would live until the garbage collector runs -- inside a hipGraph capture that ended in a segfault of
-    #  capture_end; the backward does not read them)
-    ctx.bufs = dict(wd=wd, sv={k: t for k, t in sv.items() if k != "logits"}, enc=enc, ep=ep, mask_emb=mask_emb, mask_l0=mask_l0,
-                    drop=drop, Tw=Tw)
+        if plan.bwd == "CLUSTER":
+            ctx.bufs["bptt"] = dict(wd=wd, sv=saved, p=spec.dropout_p if drop else 0.0)
     LAST_SAVED = {"ids": sv["ids"], "a": sv["a"]}
     AW = sv["attw"] if att else f32(0)
     ctx.mark_non_differentiable(AW)
@@ -201,18 +196,19 @@ class CodeDecoderRollout(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hidden0, enc_out, spec: RolloutSpec, *params):
-        global LAST_SAVED
+        global LAST_SAVED, LAST_PLAN, FUSED_CALLS, CLUSTER_CALLS
         L, att, S1 = spec.L, spec.att, spec.steps
-        if _fused_ok(hidden0, enc_out, spec, params):
-            return _fused_forward(ctx, hidden0, enc_out, spec, params)
-        if _cluster_ok(hidden0, enc_out, spec, params):
-            return _fused_forward(ctx, hidden0, enc_out, spec, params, cluster=True)
-        ctx.fused = False
         emb_w, pre_w, pre_b, bn_w, bn_b = params[:5]
         gru = [params[5 + 4 * l: 9 + 4 * l] for l in range(L)]            # (w_ih, w_hh, b_ih, b_hh) per layer
         out_w, out_b = params[5 + 4 * L: 7 + 4 * L]
         B, H, K = hidden0.shape[1], hidden0.shape[2], out_w.shape[0]
         Hin = 2 * H if att else H
+        ctx.plan = plan = RolloutPlan(S1, B, H, K, enc_out.shape[0] if att else 0, L, att)
+        LAST_PLAN = (plan.fwd, plan.bwd)
+        FUSED_CALLS += plan.bwd.startswith("STEP")
+        CLUSTER_CALLS += plan.fwd == "CLUSTER" and not plan.bwd.startswith("STEP")
+        if plan.fwd != "CHAIN":
+            return _entry_forward(ctx, plan, hidden0, enc_out, spec, params)
         dev = hidden0.device
         f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         emb_w, pre_w, out_w = emb_w.contiguous(), pre_w.contiguous(), out_w.contiguous()
@@ -230,7 +226,6 @@ class CodeDecoderRollout(torch.autograd.Function):
         Hs = [f32(S1 + 1, B, H) for _ in range(L)]
         GATES = [f32(S1, B, 4 * H) for _ in range(L)]
         GI, HN = f32(B, 3 * H), f32(B, H)
-        cell = ops.gru_cell_ok(H, H, B)
         LOGF = _outputs_buffer(spec, S1, B, K, dev)
         LOG = LOGF[1:]
         for l in range(L):
@@ -248,7 +243,7 @@ class CodeDecoderRollout(torch.autograd.Function):
         # With attention a step's row-local head -- the greedy argmax of the previous logits, the code embedding, the attention
         # -- is one launch, and the top state is multiplied once for the logits and the NEXT step's query (round 6: at the
         # reference's batch size a step is a chain of dependent ~5 us launches, 9 -> 7 per step)
-        fused_head = att and B <= 1024
+        fused_head = plan.fused_head
         if fused_head:
             ops.linear_fwd(Hs[L - 1][0], W_h, attn_b, out=HP[0])
         for t in range(S1):
@@ -265,7 +260,7 @@ class CodeDecoderRollout(torch.autograd.Function):
                               save=(SM[t], SI[t]))
             layer_in, keep, scale = A[t], None, 1.0
             for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(gru):
-                if cell:        # small batch: input projection + cell in one launch
+                if plan.cell:   # small batch: input projection + cell in one launch
                     ops.gru_cell_fwd(layer_in, Hs[l][t], w_ih, w_hh, b_ih, b_hh, keep=keep, scale=scale, h_new=Hs[l][t + 1],
                                      gates=GATES[l][t])
                 else:
@@ -282,7 +277,7 @@ class CodeDecoderRollout(torch.autograd.Function):
             if not fused_head and t + 1 < S1 and t + 1 >= npre:
                 ops.argmax_rows(LOG[t], out=ids[t + 1])                  # greedy feedback (:740)
         ctx.save_for_backward(hidden0, enc_out, *params)
-        ctx.spec, ctx.dims, ctx.cell = spec, (S1, B, H, K, Hin, L), cell
+        ctx.spec, ctx.dims = spec, (S1, B, H, K, Hin, L)
         ctx.bufs = dict(ids=ids, EC=EC, U=U, A=A, SM=SM, SI=SI, Hs=Hs, GATES=GATES, mask_emb=mask_emb, mask_l0=mask_l0,
                         scale_l0=scale_l0, emb_w=emb_w, pre_w=pre_w, out_w=out_w, gru=gru)
         if att:
@@ -301,7 +296,8 @@ class CodeDecoderRollout(torch.autograd.Function):
         if dFULL is None:
             return (None,) * n_in
         dLOG = dFULL.contiguous()[1:]                                    # slot 0 is a constant
-        if ctx.fused:
+        plan = ctx.plan
+        if plan.bwd.startswith("STEP"):
             return _fused_backward(ctx, dLOG)
         b, att = ctx.bufs, ctx.spec.att
         bn_w = ctx.saved_tensors[2 + 3]
@@ -311,8 +307,7 @@ class CodeDecoderRollout(torch.autograd.Function):
         M = S1 * B
         dLOG = dLOG.contiguous()
         DH_top = ops.linear_bwd_data(dLOG.view(M, K), b["out_w"]).view(S1, B, H)        # every step's dLogits W_out at once
-        cl = getattr(ctx, "cluster", None)
-        cluster_bptt = cl is not None and CLUSTER_BACKWARD and not att
+        cluster_bptt = plan.bwd == "CLUSTER"
         if not cluster_bptt:
             carry = [torch.zeros((B, H), dtype=torch.float32, device=dev) for _ in range(L)]   # dLoss / d(previous state), per layer
             carry_next = [f32(B, H) for _ in range(L)]
@@ -324,19 +319,19 @@ class CodeDecoderRollout(torch.autograd.Function):
         if att:
             DEC, DHP = f32(S1, B, Hin), f32(S1, B, H)
             D_EP, D_ENC, D_V = torch.empty_like(b["EP"]), torch.empty_like(b["enc"]), f32(H)
-            DV_SLABS = f32(S1, B, H) if B <= 1024 else None      # d_v's per-row partials of every step: ONE reduction behind the loop
+            DV_SLABS = f32(S1, B, H) if plan.dv_slabs else None      # d_v's per-row partials of every step: ONE reduction behind the loop
         if cluster_bptt:
             # small batch (round 5): the cells' BPTT as ONE persistent cluster launch (include/g2v.h: g2v_code_cluster_bptt); BatchNorm's
             # backward per step behind it (nothing there feeds the recurrence: the greedy feedback carries no gradient)
             global CLUSTER_BPTT_CALLS
             CLUSTER_BPTT_CALLS += 1
-            DGI[0], DGH[0], DGI[1], DGH[1], DA, d_h0 = ops.code_cluster_bptt(DH_top, cl["wd"], cl["sv"], b["mask_l0"], cl["p"], S1, B, H)
+            DGI[0], DGH[0], DGI[1], DGH[1], DA, d_h0 = ops.code_cluster_bptt(DH_top, b["bptt"]["wd"], b["bptt"]["sv"], b["mask_l0"], b["bptt"]["p"], S1, B, H)
             d_hidden0 = d_h0          # (BatchNorm's backward feeds parameters and the code embedding only: the side branch below)
         for t in (reversed(range(S1)) if not cluster_bptt else ()):
             d_in = DH_top[t]                                             # gradient arriving at Hs[l][t+1] from above
             for l in reversed(range(L)):
                 w_ih, w_hh = gru[l][0], gru[l][1]
-                if ctx.cell:    # gate gradients, then d_hprev += dgh W_hh and dx = (dgi W_ih) * mask in one launch
+                if plan.cell:   # gate gradients, then d_hprev += dgh W_hh and dx = (dgi W_ih) * mask in one launch
                     ops.gru_cell_bwd(d_in, carry[l], GATES[l][t], Hs[l][t], w_ih, w_hh,
                                      keep=b["mask_l0"][t] if (drop and l > 0) else None, scale=b["scale_l0"] if l > 0 else 1.0,
                                      dgi=DGI[l][t], dgh=DGH[l][t], d_hprev=carry_next[l], dx=DXs[l])
@@ -369,7 +364,7 @@ class CodeDecoderRollout(torch.autograd.Function):
         # (Nothing downstream waits for the parameters' gradients, but as a side branch of the iteration beside the encoder's
         #  backward they never paid: ops.side_branch.)
         if cluster_bptt:
-            if B < 1024:     # every step's BatchNorm backward + the sums over the steps: one launch
+            if plan.bn_steps:     # every step's BatchNorm backward + the sums over the steps: one launch
                 DU, d_bn_w, d_bn_b = ops.batchnorm_bwd_steps(DA, b["U"], b["A"], bn_w, b["SM"], b["SI"], True)
             else:
                 DU, DBW, DBB = f32(S1, B, H), f32(S1, H), f32(S1, H)

@@ -1070,14 +1070,53 @@ typedef struct {                 /* gradients (overwritten)                     
   float* d_enc;                  /* (Tw,B,H)  w.r.t. the encoder outputs (context + energies)  */
 } g2v_code_dec_grads;
 
+/* Which kernels run one training call of the code decoder -- its forward and the backward behind it -- is decided once, from its
+ * sizes, the caller's row count for the fused pair, the G2V_OPT_PERSISTENT level, the device's CU count and a few facts of the
+ * call; g2v_attn_code_rollout_route reports the decision (host arithmetic only, no launch).  nblk = ceil(B / 16) row groups,
+ * nt = ceil(H / 16) hidden-unit tiles.
+ *   served    n_layers == 2, S1 >= 1, B >= 1, 16 <= H <= 256, H % 4 == 0, 4 <= K <= 1024, K % 4 == 0, with attention 1 <= Tw <= 64,
+ *             and the step kernels' LDS carves within 160 KB (which in effect ends H at 224, and K at 688 where H = 200).
+ *   grid      no attention, H <= 208, level >= 1 and nt * nblk <= CUs (B <= 304 at H = 200 on 256 CUs): a CU per workgroup of
+ *             the (hidden-unit tile x row group) grid of either cluster kernel.
+ *   pair      the caller is the C entry itself (G2V_CODE_PLAN_ENTRY), or B >= fused_min_rows.
+ *                           forward                                           backward
+ *   CLUSTER   code_cluster_fwd_kernel, ONE launch: served, grid,              g2v_code_cluster_bptt (code_cluster_bptt_kernel, ONE
+ *             ceil(K / 16) <= 3 nt; and pair, or the caller accepts it        launch), then the caller's batched tail: a forward
+ *             below the pair's row count                                      CLUSTER without pair, the cluster BPTT accepted
+ *   STEP      S1 + 1 launches of code_step_fwd_kernel: pair, served,          g2v_attn_code_rollout_bwd: pair.  Variant 0, no
+ *             not CLUSTER                                                     attention: code_bptt_kernel, one launch; variant 1,
+ *                                                                             attention: code_step_bwd_att_kernel, one per step
+ *   CHAIN     the operators one by one from the host: everything else         the same; also behind a forward CLUSTER without pair
+ *                                                                             where the cluster BPTT is not accepted
+ * So STEP goes with STEP and CHAIN with CHAIN; a forward CLUSTER goes with STEP from fused_min_rows rows on -- the entry takes the
+ * cluster kernel whenever it can, which no switch of the caller's but the level turns off: asking for the fused pair at a small
+ * batch does NOT force the step forward -- and with CLUSTER or CHAIN below.  CHAIN is an answer for the caller only: the entries
+ * never run it.  With G2V_CODE_PLAN_ENTRY a shape that is not served returns 0, as the entries refuse it (G2V_ERR_UNSUPPORTED).
+ * What only the call itself can tell may still move a forward CLUSTER to STEP inside the entry, silently and with equal results:
+ * the cluster kernel not resident at a workgroup per CU (asked of the runtime only once the plan says CLUSTER).
+ * g2v_attn_code_rollout_route returns G2V_CODE_ROUTE_* in bits 0..7 and the variant above, or 0 for a call the entries refuse.
+ * backward: 0 the forward, 1 the backward, 2 g2v_code_cluster_bptt called by itself (K, Tw, layers and fused_min_rows are not read;
+ * CLUSTER where grid holds, else 0).  persistent: the level, -1 = the bound context's; cus: the CU count, 0 = the device's (none:
+ * no grid fits); facts: G2V_CODE_PLAN_* (0: a caller above the entries that accepts both cluster kernels, workspaces as queried). */
+#define G2V_CODE_ROUTE_CLUSTER 1
+#define G2V_CODE_ROUTE_STEP 2
+#define G2V_CODE_ROUTE_CHAIN 3
+#define G2V_CODE_PLAN_ENTRY 1            /* the C entry itself is called: pair holds at every B; not served = refused */
+#define G2V_CODE_PLAN_NO_CLUSTER_FWD 2   /* without pair the caller does not take the cluster forward: CHAIN / CHAIN */
+#define G2V_CODE_PLAN_NO_CLUSTER_BPTT 4  /* ... takes the forward but not the cluster BPTT: CLUSTER / CHAIN */
+#define G2V_CODE_PLAN_WS_SMALL 8         /* the workspace is below the size query's answer, so too small for the records as well: a call
+                                            that runs a kernel is refused (G2V_ERR_WORKSPACE) */
+int g2v_attn_code_rollout_route(int backward, int S1, int B, int H, int K, int Tw, int attention, int layers, int fused_min_rows,
+                                int persistent /* -1: the bound context's */, int cus /* 0: the device's */, int facts);
+/* 1 where the entries serve the shape: g2v_attn_code_rollout_route(.., G2V_CODE_PLAN_ENTRY) != 0 (0: chain the operators above
+ * from the host, as rounds 1-4 did) */
 int g2v_attn_code_rollout_ok(int S1, int B, int H, int K, int Tw, int attention);
-/* Round 5: 1 where g2v_attn_code_rollout_fwd runs the shape as ONE persistent cluster launch of (hidden-unit tile x row group)
- * workgroups (csrc/t2e_rollout.hip: code_cluster_fwd_kernel -- the scheme of the pose decoder's cluster kernels, see
- * g2v_dec_rollout_set_persistent, which also switches this one): no attention, H <= 208, K <= 48 ceil(H / 16), the grid with a CU
- * per workgroup (B <= 304 at H = 200).  It writes the same arrays as the step kernels, so g2v_attn_code_rollout_bwd or a
- * per-operator backward run on them unchanged. */
+/* 1 where g2v_attn_code_rollout_fwd runs the shape as CLUSTER under the bound context's level on this device
+ * (g2v_attn_code_rollout_route, forward, G2V_CODE_PLAN_ENTRY).  The cluster kernel writes the same arrays as the step kernels,
+ * so g2v_attn_code_rollout_bwd or a per-operator backward run on them unchanged. */
 int g2v_attn_code_rollout_cluster_ok(int S1, int B, int H, int K, int attention);
-/* Round 5: for the same shapes, the BPTT through the two GRU cells of the attention-free rollout as ONE persistent cluster launch
+/* Round 5: where `grid` holds (g2v_attn_code_rollout_route, backward = 2), the BPTT through the two GRU cells of the attention-free
+ * rollout as ONE persistent cluster launch
  * (code_cluster_bptt_kernel: the partial-product exchange of the pose decoder's backward cluster).  Nothing but the cells couples
  * two steps there (the greedy feedback carries no gradient), so the caller forms dh_top (S1,B,H) = dLogits W_out for all steps
  * first (g2v_linear_bwd_data) and runs BatchNorm's backward, the embedding gradient and every weight gradient afterwards over all

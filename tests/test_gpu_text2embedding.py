@@ -71,6 +71,11 @@ def test_text2embedding_matches_reference_golden(golden_dir, name, att, kernels,
                     assert prm.grad is not None and relerr(prm.grad, ref) < 5e-4, (n, relerr(prm.grad, ref))
     assert rollout_t2e.FUSED_CALLS - calls0 == (2 if kernels == "fused_step" else 0)
     assert rollout_t2e.CLUSTER_CALLS - ccalls0 == (2 if kernels == "cluster_forward" else 0)
+    # what ran, as the plan names it.  fused_step: the `kernels` fixture holds the persistent level at 0 around this test, so the entry
+    # runs its step kernels; FUSED_MIN_ROWS = 1 alone would give ("CLUSTER", "STEP") without attention
+    # (test_rollout_calls_what_its_plan_names has that pair)
+    assert rollout_t2e.LAST_PLAN == {"per_operator": ("CHAIN", "CHAIN"), "cluster_forward": ("CLUSTER", "CLUSTER"),
+                                     "fused_step": ("STEP", "STEP*1" if att == "True" else "STEP")}[kernels]
     for k in fx.files:
         if k.startswith("wN/"):
             n = k[3:]
@@ -340,6 +345,8 @@ def test_fused_step_kernels_match_per_operator_path(att, p, B, n_pre, H, K, monk
             out, attn = net(ids, lengths, None, codes, None, None)
             (out * w).sum().backward()
             outs.append((out.detach(), attn))
+            if net.fused_rollout:      # (the other leg chains one autograd node per operator: no rollout node, no plan)
+                assert rollout_t2e.LAST_PLAN == ("STEP", "STEP*1" if att == "True" else "STEP")
     assert rollout_t2e.FUSED_CALLS - calls0 == 1, "the fused step kernels did not serve this shape (g2v_attn_code_rollout_ok)"
     assert relerr(outs[0][0], outs[1][0].cpu()) < 3e-5
     same = (outs[0][0][:, 1:].argmax(2) == outs[1][0][:, 1:].argmax(2)).all(1)
@@ -833,6 +840,94 @@ def test_deferred_batchnorm_commit_equals_the_in_rollout_updates():
         assert float(got[0][0].abs().max()) > 0
         assert relerr(got[1][0].cpu(), got[0][0].cpu()) < 1e-6, (att, B, route)
         assert relerr(got[1][1].cpu(), got[0][1].cpu()) < 2e-6, (att, B, route)
+
+
+_ROLLOUT_ENTRY_POINTS = ("g2v_attn_code_rollout_fwd", "g2v_attn_code_rollout_bwd", "g2v_code_cluster_bptt", "g2v_batchnorm_bwd_steps",
+                         "g2v_gru_cell_fwd", "g2v_gru_cell_bwd", "g2v_attn_step_fwd", "g2v_attn_fwd", "g2v_attn_bwd")
+# what each route calls of them at S1 = 3 decode steps of two GRU layers: (forward, backward) per route name
+_ROLLOUT_CALLS = {
+    ("CLUSTER", "fwd"): ["g2v_attn_code_rollout_fwd"], ("STEP", "fwd"): ["g2v_attn_code_rollout_fwd"],
+    ("CHAIN", "fwd"): ["g2v_gru_cell_fwd"] * 6, ("CHAIN+head", "fwd"): ["g2v_attn_step_fwd", "g2v_gru_cell_fwd", "g2v_gru_cell_fwd"] * 3,
+    ("CLUSTER", "bwd"): ["g2v_code_cluster_bptt", "g2v_batchnorm_bwd_steps"], ("STEP", "bwd"): ["g2v_attn_code_rollout_bwd"],
+    ("STEP*1", "bwd"): ["g2v_attn_code_rollout_bwd"], ("CHAIN", "bwd"): ["g2v_gru_cell_bwd"] * 6,
+    ("CHAIN+head", "bwd"): ["g2v_gru_cell_bwd", "g2v_gru_cell_bwd", "g2v_attn_bwd"] * 3,
+}
+
+
+@pytest.mark.parametrize("name,att,B,H,switches,level,plan", [
+    ("cluster pair", "False", 16, 48, {}, 1, ("CLUSTER", "CLUSTER")),
+    ("cluster forward, chain behind it", "False", 16, 48, dict(CLUSTER_BACKWARD=False), 1, ("CLUSTER", "CHAIN")),
+    ("chain", "False", 16, 48, dict(CLUSTER_FORWARD=False), 1, ("CHAIN", "CHAIN")),
+    ("cluster forward of the fused pair", "False", 16, 48, dict(FUSED_MIN_ROWS=1), 1, ("CLUSTER", "STEP")),
+    ("fused pair", "False", 16, 48, dict(FUSED_MIN_ROWS=1), 0, ("STEP", "STEP")),
+    ("fused pair with attention", "True", 24, 48, dict(FUSED_MIN_ROWS=1), 1, ("STEP", "STEP*1")),
+    ("chain with the fused head", "True", 24, 48, {}, 1, ("CHAIN", "CHAIN")),
+    ("chain: the grid does not fit this device", "False", None, 200, {}, 1, ("CHAIN", "CHAIN")),
+])
+def test_rollout_calls_what_its_plan_names(monkeypatch, name, att, B, H, switches, level, plan):
+    """One forward + backward of CodeDecoderRollout at the smallest shape of each pair of routes (three decode steps): the plan is
+    the one the switches and the level name, it is what the route query says for the call, the library functions called are
+    exactly that plan's, the counters count it, and no fault is latched.  B = None: the first batch whose (hidden-unit tile x row
+    group) grid has more workgroups than this device has CUs, worked out from the device's own count through the query."""
+    from gesture2vec_amd import _lib, ops, rollout_t2e
+    lib = _lib.load()
+    K, S1 = 40, 3
+    if B is None:
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        B = 16 * (cus // ((H + 15) // 16)) + 1
+        assert ops.code_route(S1, B - 1, H, K, fused_min_rows=1024) == "CLUSTER" and ops.code_route(S1, B, H, K, fused_min_rows=1024) == "CHAIN"
+        assert ops.code_route(S1, B - 1, H, K, fused_min_rows=1024, cus=cus) == "CLUSTER" and lib.g2v_attn_code_rollout_cluster_ok(S1, B, H, K, 0) == 0
+    for k, v in switches.items():
+        monkeypatch.setattr(rollout_t2e, k, v)
+    args, net, optim, ids, lengths, codes, masks = _small_t2e(att=att, B=B, H=H, K=K, S=S1 + 1)
+    net.set_dropout_masks(*masks)
+    counters = lambda: (rollout_t2e.FUSED_CALLS, rollout_t2e.CLUSTER_CALLS, rollout_t2e.CLUSTER_BPTT_CALLS)
+    before, calls = counters(), []
+    for fn in _ROLLOUT_ENTRY_POINTS:
+        real = getattr(lib, fn)
+        monkeypatch.setattr(lib, fn, lambda *a, _real=real, _name=fn: calls.append(_name) or _real(*a))
+    with _lib.Context.current().scoped(persistent=level):
+        facts = tuple(f for f, sw in (("NO_CLUSTER_FWD", "CLUSTER_FORWARD"), ("NO_CLUSTER_BPTT", "CLUSTER_BACKWARD")) if not switches.get(sw, True))
+        kw = dict(fused_min_rows=switches.get("FUSED_MIN_ROWS", 1024), facts=facts)
+        Tw = ids.shape[1] if att == "True" else 0
+        assert (ops.code_route(S1, B, H, K, Tw, att == "True", **kw), ops.code_route(S1, B, H, K, Tw, att == "True", backward=True, **kw)) == plan
+        out, _ = net(ids, lengths, None, codes, None, None)
+        fwd_calls, calls[:] = list(calls), []
+        out.square().sum().backward()
+        torch.cuda.synchronize()
+    assert rollout_t2e.LAST_PLAN == plan
+    head = "+head" if plan[0] == "CHAIN" and att == "True" else ""
+    assert fwd_calls == _ROLLOUT_CALLS[(plan[0] + head, "fwd")], fwd_calls
+    assert calls == _ROLLOUT_CALLS[(plan[1] + head, "bwd")], calls
+    after = counters()
+    assert tuple(a - b for a, b in zip(after, before)) == (int(plan[1].startswith("STEP")), int(plan[0] == "CLUSTER" and not plan[1].startswith("STEP")),
+                                                            int(plan[1] == "CLUSTER"))
+    assert lib.g2v_dec_rollout_persist_fault(0) == 0
+    assert all(p.grad is None or bool(torch.isfinite(p.grad).all()) for p in net.parameters()) and bool(torch.isfinite(out).all())
+
+
+def test_code_rollout_queries_are_fields_of_the_route():
+    """g2v_attn_code_rollout_ok and g2v_attn_code_rollout_cluster_ok against the conditions as they stood before the plan and against
+    g2v_attn_code_rollout_route, at this device's own CU count: over the sweep of tests/test_t2e_route_host.py under both levels,
+    and at every shape of the route table under the level the row names."""
+    import _t2e_route_shapes as TS
+    import test_t2e_route_host as TH
+    from gesture2vec_amd import _lib, ops
+    lib = _lib.load()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert TH.older_queries_are_fields_of_the_route(cus, (0, 1)) > 80000
+    met = set()
+    for c in TS.T2E_ROUTE_SHAPES:
+        S1, B, H, K, Tw, att, level = c["S1"], c["B"], c["H"], c["K"], c["Tw"], c["att"], c["persistent"]
+        with _lib.Context.current().scoped(persistent=level):
+            ok, cl = lib.g2v_attn_code_rollout_ok(S1, B, H, K, Tw, int(att)), lib.g2v_attn_code_rollout_cluster_ok(S1, B, H, K, int(att))
+            r = ops.code_route(S1, B, H, K, Tw, att, facts=("ENTRY",))
+            assert ok == int(r != "") == int(TH.rollout_ok_as_it_stood(S1, B, H, K, Tw, att)), c["name"]
+            assert cl == int(r == "CLUSTER") == int(TH.cluster_ok_as_it_stood(S1, B, H, K, att, level, cus)), c["name"]
+            if cus == c["cus"] and c["layers"] == 2 and c["facts"] == ("ENTRY",):      # (then the row's own answer is this device's)
+                assert r == c["route"][0], c["name"]
+            met.add(r)
+    assert met == {"CLUSTER", "STEP", ""}
 
 
 def test_graphed_step_detects_a_fault_recaptures_and_the_policy_rearms():
