@@ -791,6 +791,46 @@ int g2v_dec_rollout_bwd_prepared(const g2v_dec_weights* w, const g2v_dec_saved* 
                                  g2v_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gesture generation: the decoder's chain over the chunks of a clip, in ONE launch (csrc/dec_chain.hip).  Replaces the decode
+ * loops of Clustering.py:198-261 (make_VQ_Centers), inference_Autoencoder.py:124-244 and inference_text2embedding.py:400-547.
+ * step(x, h, keep) is the recurrence stated above g2v_dec_weights in EVAL mode (running statistics, no inter-layer dropout;
+ * the inline Dropout(0.95) stays active).  For clip b, with S = warmup + T - 1 steps per chunk:
+ *   carry = start[b] (NULL: zeros)
+ *   for c in 0..C-1:
+ *     h = rows[ids[b,c]] (ids NULL: rows[b C + c]), split as [layer 0 | layer 1];  inp = carry;  out[b, c T + 0] = inp
+ *     for s in 0..warmup-1:  _, h = step(inp, h, keep95[c,s,b])                      (output discarded)
+ *     for t in 1..T-1:       y, h = step(inp, h, keep95[c,warmup+t-1,b]);  out[b, c T + t] = y
+ *                            inp = teacher[b,c,t] if teacher != NULL and t < n_pre_poses else y
+ *     carry = inp            (conditioned == 0: xin is zero in every step and carry = zeros)
+ * rows (R,2H); ids (B,C) int64 or NULL; start (B,D) or NULL; teacher (B,C,T,D) or NULL; keep95 (C,S,B,D) uint8 (may be NULL when
+ * conditioned == 0); out (B,C T,D); h_last (2,B,H) or NULL: the hidden state after the last step.  Arrays need their natural
+ * alignment only (4 bytes, ids 8, masks 1); the workspace 16 bytes.  An id outside [0, R) reads nothing and seeds a ZERO hidden state (callers check ids
+ * first).  w: bn_running_mean / bn_running_var are required and not modified.
+ * One workgroup owns 16 clips and is independent of every other: no exchange, no wait, nothing for the fault latch.  BatchNorm
+ * is folded into pre_linear when the weights are packed into the workspace (once per call), so `a` differs from the unfused
+ * kernels' by rounding; results are bitwise reproducible and a clip's bits do not depend on the batch it is decoded in.
+ * g2v_dec_chain_ok: 1 for exactly C >= 1, T >= 2, warmup >= 0, B >= 1, 1 <= D <= 256, 1 <= H <= 256, C <= 2^20 and
+ * warmup + T - 1 <= 2^20; else 0, and g2v_dec_chain_fwd returns G2V_ERR_UNSUPPORTED (host arithmetic only).
+ * g2v_dec_chain_workspace: bytes (0 where D or H is outside the served set).
+ * ------------------------------------------------------------------------------------------ */
+int g2v_dec_chain_ok(int C, int T, int warmup, int B, int D, int H);
+size_t g2v_dec_chain_workspace(int D, int H);
+int g2v_dec_chain_fwd(const float* rows, int64_t R, const int64_t* ids, const float* start, const float* teacher,
+                      const uint8_t* keep95, const g2v_dec_weights* w, float* out, float* h_last, int n_pre_poses,
+                      int conditioned, int C, int T, int warmup, int B, int D, int H, void* workspace, size_t workspace_bytes,
+                      g2v_stream_t stream);
+/* The tail of a generated clip, r (B,F,Dr) -> out (B,F,Dr), F = C T, r != out:
+ *   1. blend across every chunk boundary o = c T, c >= 1 (inference_Autoencoder.py:388-395 with its literal 30 as T), n = blend:
+ *        r'[o+i] = r[o-i] (n-i)/(n+1) + r[o+i] (i+1)/(n+1),  i = 0..n-1, reading the un-blended r.
+ *      blend == 0: none.  This equals the reference's in-place loop only for T >= 2 n - 1; below that: G2V_ERR_ARG.
+ *   2. * max(std, 0.01) + mean (:400-403); mean, std (Dr) or both NULL: none.
+ *   3. savgol != NULL: a Savitzky-Golay filter along time, window 25 (inference_text2embedding_GENEA.py:600), from a host-made
+ *      table of 625 floats: 25 interior taps, then the 12 x 25 matrices that give the first / last 12 frames from the first /
+ *      last 25 (scipy's mode="interp").  Needs F >= 25 (else G2V_ERR_ARG) and tmp (B,F,Dr), distinct from r and out. */
+int g2v_clip_finish(const float* r, float* out, const float* mean, const float* std, const float* savgol, float* tmp, int T,
+                    int blend, int B, int F, int Dr, g2v_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * custom_loss forward + gradient (K10), train_eval/train_seq2seq.py:40-88.
  *   loss = w_l1*mean|y-tgt| + w_cont*sum_t|y_t-y_{t-1}|/numel - w_var*sum_{b,d}||y[b,:,d]||_2/numel
  * y is time-major (T,B,D) (the rollout's buffer), target is (B,T,D).  dy (T,B,D) = g_scale * dloss/dy
