@@ -444,37 +444,102 @@ __global__ __launch_bounds__(256) void gemm_smallm_dual_nt_kernel(const float* _
                                   blockIdx.x * 4 + (threadIdx.x >> 6), nullptr, 1.0f);
 }
 
-// measured (gpurun_tools/gemm_bench.py, 200..400 -> 200..600): forward 9.7 vs 10.4 us and data gradient 11 vs 22 us at 128..640
-// rows, break-even near 2560 rows, the LDS-tiled kernel ahead beyond (50..86 TF/s at 4096..81920 rows)
 extern "C" int g2v_linear_set_smallm_rows(int rows) {            // = g2v_ctx_set_option(NULL, G2V_OPT_SMALLM_ROWS, rows) (measurement only)
   return g2v_ctx_set_option(nullptr, G2V_OPT_SMALLM_ROWS, rows);
 }
 
-static bool launch_smallm(bool trans_b, const float* A, int64_t lda, const uint8_t* keep, float scale, const float* Bm,
-                          int64_t ldb, const float* bias, float* Cout, int64_t ldc, int M, int C, int N, int act,
+// Which kernel a forward / data-gradient product runs on, and with which launch parameters: decided here, once, from integers
+// (host arithmetic only, nothing is launched).  g2v_linear_fwd, _bwd_data, _fwd_pair and _fwd_dual launch from it,
+// g2v_linear_route reports it.  The decision order, every threshold and its measurement: DESIGN.md §3.6.2.
+struct DensePlan {
+  int route;            // G2V_DENSE_ROUTE_*; 0: a size the entry points reject
+  int variant;          // SMALLM: tn, 16-column tiles per wave; STREAM: ntw << 4 | ks; K4: 1 = row-mapped; TILED: 4 = float4 operands, 1 = scalar
+  int tn;               // SMALLM: gemm_smallm_kernel<.., tn, 8 / 4 / 4>
+  int ntw, ks;          // STREAM: gemm_nt_stream_kernel<ntw, ks, ..>
+  bool one_launch;      // pair: the TILED kernel with grid.z = 2; dual: gemm_smallm_dual_nt_kernel; false: two single calls
+  dim3 grid;
+  size_t lds;           // dynamic LDS bytes
+  bool set_attr;        // lds is above the 48 KB a kernel gets without hipFuncSetAttribute
+};
+static int dense_smallm_rows(int given) { return given < 0 ? g2v_internal_options().smallm_max_rows : given; }
+// K, N: the forward weight is [N][K] in every form (the data gradient contracts over N and writes K columns); ldx / ldy: row strides
+// of the array read (x, dy) and of the array written (y, dx); align: G2V_DENSE_ALIGN_* facts about the call's pointers (pair and
+// dual: W holds for both weights).  What a form's entry point has no argument for is ignored.
+static DensePlan dense_plan(int form, int M, int K, int N, int N_b, int act, bool has_bias, bool has_keep, int rows_inner,
+                            int64_t stride_outer, int64_t stride_inner, int64_t ldx, int64_t ldy, int smallm_rows, int align) {
+  DensePlan pl{};
+  if (form < G2V_DENSE_FORM_FWD || form > G2V_DENSE_FORM_FWD_DUAL || M <= 0 || K <= 0 || N <= 0 || act < 0 || act > 2) return pl;
+  if (form == G2V_DENSE_FORM_FWD_PAIR) {
+    pl = dense_plan(G2V_DENSE_FORM_FWD, M, K, N, 0, act, has_bias, false, 0, 0, 0, ldx, ldy, smallm_rows, align);
+    pl.one_launch = pl.route == G2V_DENSE_ROUTE_TILED && pl.variant == 4 && N > 192 && M <= 16384;
+    if (pl.one_launch) pl.grid.z = 2;
+    return pl;
+  }
+  if (form == G2V_DENSE_FORM_FWD_DUAL) {
+    if (N_b <= 0) return pl;
+    pl = dense_plan(G2V_DENSE_FORM_FWD, M, K, N, 0, 0, has_bias, false, 0, 0, 0, ldx, ldy, smallm_rows, align);
+    const DensePlan pb = dense_plan(G2V_DENSE_FORM_FWD, M, K, N_b, 0, 0, has_bias, false, 0, 0, 0, ldx, ldy, smallm_rows, align);
+    pl.one_launch = pl.route == G2V_DENSE_ROUTE_SMALLM && pl.tn == 1 && pb.route == G2V_DENSE_ROUTE_SMALLM && pb.tn == 1;
+    if (pl.one_launch) pl.grid = dim3(pl.grid.x > pb.grid.x ? pl.grid.x : pb.grid.x, 2);
+    return pl;
+  }
+  const bool bwd = form == G2V_DENSE_FORM_BWD_DATA;
+  if (bwd) { act = 0; has_bias = false; has_keep = false; rows_inner = 0; }
+  const int C = bwd ? N : K, O = bwd ? K : N;      // contraction length, output columns
+  const bool x16 = align & G2V_DENSE_ALIGN_X, w16 = align & G2V_DENSE_ALIGN_W, y_vec = (align & G2V_DENSE_ALIGN_Y) && (ldy & 3) == 0;
+  const bool bias_ok = !has_bias || (align & G2V_DENSE_ALIGN_BIAS), keep_ok = !has_keep || (align & G2V_DENSE_ALIGN_KEEP);
+  const bool plain_x_vec = rows_inner == 0 && (C & 3) == 0 && (ldx & 3) == 0 && x16;
+  if (plain_x_vec && M <= smallm_rows && (bwd || w16) && keep_ok) {
+    // wider wave tiles (more re-use of the A fragment, fewer waves) once 16 x 16 tiles alone fill the chip a few times over
+    const int64_t tiles16 = (int64_t)cdiv(M, 16) * cdiv(O, 16);
+    pl.route = G2V_DENSE_ROUTE_SMALLM;
+    pl.variant = pl.tn = tiles16 <= 2048 ? 1 : (tiles16 <= 8192 ? 2 : 4);
+    pl.grid = dim3(cdiv(cdiv(M, 16) * cdiv(O, 16 * pl.tn), 4));
+    return pl;
+  }
+  const int ks = (C + 15) >> 4, ntw = O >> 4;
+  if (plain_x_vec && !has_keep && M >= 1024 && (O & 15) == 0 && O <= 192 && act != 2 && y_vec && bias_ok &&
+      ((ntw == 12 && ks == 4) || (ntw == 4 && ks == 12) || (ntw == 8 && ks == 8) || (ntw == 4 && ks == 4))) {
+    pl.route = G2V_DENSE_ROUTE_STREAM;
+    pl.ntw = ntw; pl.ks = ks; pl.variant = ntw << 4 | ks;
+    // large M: >= 4 row groups per wave (the per-workgroup weight pack amortises); small M: one group per wave so that the launch
+    // still covers the chip; never more than one workgroup per CU
+    const int gx = M >= 65536 ? cdiv(M, 16 * 4 * 4) : cdiv(M, 16 * 4);
+    pl.grid = dim3(gx > 256 ? 256 : gx);
+    pl.lds = (size_t)ntw * ks * 256 * sizeof(float);
+    pl.set_attr = pl.lds > 48 * 1024;
+    return pl;
+  }
+  if (!bwd && !has_keep && N == 64 && K == 135 && M >= 4096 && (M & 15) == 0 && act != 2 && y_vec && bias_ok) {
+    pl.route = G2V_DENSE_ROUTE_K4;
+    pl.variant = rows_inner > 0;
+    const int gx = cdiv(M, 16 * 4 * 4);
+    pl.grid = dim3(gx > 256 ? 256 : gx);      // one workgroup per CU, one wave per SIMD
+    return pl;
+  }
+  pl.route = G2V_DENSE_ROUTE_TILED;
+  const bool x_vec = rows_inner > 0 ? (stride_outer & 3) == 0 && (stride_inner & 3) == 0 : (ldx & 3) == 0;
+  pl.variant = !has_keep && (K & 3) == 0 && (!bwd || (N & 3) == 0) && x16 && x_vec && w16 ? 4 : 1;
+  pl.grid = dim3(cdiv(M, BM), cdiv(O, BN));
+  return pl;
+}
+
+static void launch_smallm(const DensePlan& pl, bool trans_b, const float* A, int64_t lda, const uint8_t* keep, float scale,
+                          const float* Bm, int64_t ldb, const float* bias, float* Cout, int64_t ldc, int M, int C, int N, int act,
                           int accumulate, hipStream_t st) {
-  if (M > g2v_internal_options().smallm_max_rows || (C & 3) || (lda & 3) || (reinterpret_cast<uintptr_t>(A) & 15)) return false;
-  if (!trans_b && ((ldb & 3) || (reinterpret_cast<uintptr_t>(Bm) & 15))) return false;
-  if (keep && (reinterpret_cast<uintptr_t>(keep) & 3)) return false;
-  // wider wave tiles (more re-use of the A fragment, fewer waves) once 16 x 16 tiles alone fill the chip a few times over
-  const int64_t tiles16 = (int64_t)cdiv(M, 16) * cdiv(N, 16);
-  const int tn = tiles16 <= 2048 ? 1 : (tiles16 <= 8192 ? 2 : 4);
-  const int tiles = cdiv(M, 16) * cdiv(N, 16 * tn);
-  const dim3 grid(cdiv(tiles, 4));
-#define G2V_SMALLM(TB, KP, TN, NB)                                                                                        \
-  hipLaunchKernelGGL((gemm_smallm_kernel<TB, KP, TN, NB>), grid, dim3(256), 0, st, A, lda, keep, scale, Bm, ldb, bias,  \
+#define G2V_SMALLM(TB, KP, TN, NB)                                                                                           \
+  hipLaunchKernelGGL((gemm_smallm_kernel<TB, KP, TN, NB>), pl.grid, dim3(256), 0, st, A, lda, keep, scale, Bm, ldb, bias,  \
                      Cout, ldc, M, C, N, act, accumulate)
-#define G2V_SMALLM_TN(TB, KP)                     \
-  do {                                            \
-    if (tn == 1) G2V_SMALLM(TB, KP, 1, 8);        \
-    else if (tn == 2) G2V_SMALLM(TB, KP, 2, 4);   \
-    else G2V_SMALLM(TB, KP, 4, 4);                \
+#define G2V_SMALLM_TN(TB, KP)                        \
+  do {                                               \
+    if (pl.tn == 1) G2V_SMALLM(TB, KP, 1, 8);        \
+    else if (pl.tn == 2) G2V_SMALLM(TB, KP, 2, 4);   \
+    else G2V_SMALLM(TB, KP, 4, 4);                   \
   } while (0)
   if (trans_b) { if (keep) G2V_SMALLM_TN(true, true); else G2V_SMALLM_TN(true, false); }
   else { if (keep) G2V_SMALLM_TN(false, true); else G2V_SMALLM_TN(false, false); }
 #undef G2V_SMALLM_TN
 #undef G2V_SMALLM
-  return true;
 }
 
 }  // namespace g2v
@@ -494,32 +559,21 @@ int g2v_internal_cell_bwd_products(const float* dgh, const float* w_hh, float* d
 namespace g2v {
 
 template <bool TRANS_B>
-static bool launch_stream(const float* A, int64_t lda, const float* Bm, int64_t ldb, const float* bias, float* Cout,
-                          int64_t ldc, int M, int C, int N, int act, int accumulate, hipStream_t st) {
-  // eligibility: aligned rows, whole float4s, N a multiple of 16 up to 192, identity / ReLU epilogue, enough rows
-  if (M < 1024 || (C & 3) || (N & 15) || N > 192 || act == 2) return false;
-  if (!ptr_vec_ok(A, lda) || !ptr_vec_ok(Cout, ldc) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15))) return false;
-  const int ks = (C + 15) >> 4, ntw = N >> 4;
-  // large M: >= 4 row groups per wave (the per-workgroup weight pack amortises); small M: one group per wave so that
-  // the launch still covers the chip
-  int gx = (M >= 65536) ? cdiv(M, 16 * 4 * 4) : cdiv(M, 16 * 4);
-  if (gx > 256) gx = 256;      // one workgroup per CU (measured: 512 workgroups +8..17 %, 1024 +40 %)
+static void launch_stream(const DensePlan& pl, const float* A, int64_t lda, const float* Bm, int64_t ldb, const float* bias,
+                          float* Cout, int64_t ldc, int M, int C, int N, int act, int accumulate, hipStream_t st) {
 #define G2V_STREAM(NTW, KS)                                                                                              \
   do {                                                                                                                   \
-    const size_t lds = (size_t)NTW * KS * 256 * sizeof(float);                                                           \
-    if (lds > 48 * 1024)                                                                                                 \
+    if (pl.set_attr)                                                                                                     \
       (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<NTW, KS, TRANS_B>,                                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                   \
-    hipLaunchKernelGGL((gemm_nt_stream_kernel<NTW, KS, TRANS_B>), dim3(gx), dim3(256), lds, st, A, lda, Bm, ldb, bias,    \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);                                \
+    hipLaunchKernelGGL((gemm_nt_stream_kernel<NTW, KS, TRANS_B>), pl.grid, dim3(256), pl.lds, st, A, lda, Bm, ldb, bias,  \
                        Cout, ldc, M, C, N, act, accumulate);                                                             \
-    return true;                                                                                                         \
   } while (0)
-  if (ntw == 12 && ks == 4) G2V_STREAM(12, 4);       // gi = xin W_ih^T            (64 -> 192)
-  if (ntw == 4 && ks == 12) G2V_STREAM(4, 12);       // dxin = dgi W_ih            (192 -> 64)
-  if (ntw == 8 && ks == 8) G2V_STREAM(8, 8);         // VQ pre_linear              (128 -> 128)
-  if (ntw == 4 && ks == 4) G2V_STREAM(4, 4);         // 64 -> 64
+  if (pl.ntw == 12) G2V_STREAM(12, 4);               // gi = xin W_ih^T            (64 -> 192)
+  else if (pl.ks == 12) G2V_STREAM(4, 12);           // dxin = dgi W_ih            (192 -> 64)
+  else if (pl.ntw == 8) G2V_STREAM(8, 8);            // VQ pre_linear              (128 -> 128)
+  else G2V_STREAM(4, 4);                             // 64 -> 64
 #undef G2V_STREAM
-  return false;
 }
 
 // ---- wave-autonomous forward for UNALIGNED / row-mapped inputs (encoder in_layer: x (B,T,135) read as (T,B,135)) ----
@@ -553,7 +607,7 @@ __global__ __launch_bounds__(256) void gemm_nt_k4_kernel(const float* __restrict
   for (int t = 0; t < 4; ++t)
     bia[t] = bias ? *reinterpret_cast<const float4*>(bias + 16 * t + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
   __syncthreads();
-  const int ngroups = M >> 4;                         // M is a multiple of 16 (checked by the launcher)
+  const int ngroups = M >> 4;                         // M is a multiple of 16 (dense_plan)
   const int gstride = gridDim.x * 4;
   // the lane's run of columns, and the clamped column of a slot past the row (its weight is zero: any finite value will do)
   const int c0 = KS4 * q;
@@ -626,17 +680,12 @@ __global__ __launch_bounds__(256) void gemm_nt_k4_kernel(const float* __restrict
   }
 }
 
-static bool launch_k4(const float* A, const RowMap& am, const float* W, const float* bias, float* Cout, int64_t ldc, int M,
-                      int C, int N, int act, hipStream_t st) {
-  if (N != 64 || C != 135 || M < 4096 || (M & 15) || act == 2) return false;
-  if (!ptr_vec_ok(Cout, ldc) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15))) return false;
-  int gx = cdiv(M, 16 * 4 * 4);
-  if (gx > 256) gx = 256;      // one workgroup per CU, one wave per SIMD: measured optimum (512: +10 %, 320: +40 %, 128: +60 %)
-  if (am.rows_inner > 0)
-    hipLaunchKernelGGL((gemm_nt_k4_kernel<34, true>), dim3(gx), dim3(256), 0, st, A, am, W, bias, Cout, ldc, M, C, act);
+static void launch_k4(const DensePlan& pl, const float* A, const RowMap& am, const float* W, const float* bias, float* Cout,
+                      int64_t ldc, int M, int C, int act, hipStream_t st) {
+  if (pl.variant)
+    hipLaunchKernelGGL((gemm_nt_k4_kernel<34, true>), pl.grid, dim3(256), 0, st, A, am, W, bias, Cout, ldc, M, C, act);
   else
-    hipLaunchKernelGGL((gemm_nt_k4_kernel<34, false>), dim3(gx), dim3(256), 0, st, A, am, W, bias, Cout, ldc, M, C, act);
-  return true;
+    hipLaunchKernelGGL((gemm_nt_k4_kernel<34, false>), pl.grid, dim3(256), 0, st, A, am, W, bias, Cout, ldc, M, C, act);
 }
 
 // ---- weight gradient: slab[split][n][k] = sum_{m in split} dy[m][n] * xin[m][k] -------------------
@@ -1339,36 +1388,42 @@ int g2v_internal_slab_reduce4(const float* const* slab_w, float* const* out_w, c
 
 using namespace g2v;
 
+// the G2V_DENSE_ALIGN_* facts of a call's pointers (a NULL pointer counts as aligned: nothing is read through it)
+static int dense_align(const void* x, const void* w, const void* y, const void* bias, const void* keep, const void* w_b = nullptr) {
+  auto a = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; };
+  return (a(x, 15) ? G2V_DENSE_ALIGN_X : 0) | (a(w, 15) && a(w_b, 15) ? G2V_DENSE_ALIGN_W : 0) | (a(y, 15) ? G2V_DENSE_ALIGN_Y : 0) |
+         (a(bias, 15) ? G2V_DENSE_ALIGN_BIAS : 0) | (a(keep, 3) ? G2V_DENSE_ALIGN_KEEP : 0);
+}
+
+extern "C" int g2v_linear_route(int form, int M, int K, int N, int N_b, int act, int has_bias, int has_keep, int rows_inner,
+                                int64_t stride_outer, int64_t stride_inner, int64_t ldx, int64_t ldy, int smallm_rows, int align) {
+  const DensePlan pl = dense_plan(form, M, K, N, N_b, act, has_bias != 0, has_keep != 0, rows_inner, stride_outer, stride_inner, ldx,
+                                  ldy, dense_smallm_rows(smallm_rows), align);
+  return pl.route ? pl.route | (pl.variant << 8) | (pl.one_launch ? G2V_DENSE_ROUTE_ONE_LAUNCH : 0) : 0;
+}
+
 extern "C" int g2v_linear_fwd(const float* x, int64_t ldx, int rows_inner, int64_t stride_outer, int64_t stride_inner,
                               const uint8_t* x_keep, float x_scale, const float* w, const float* bias, float* y,
                               int64_t ldy, int M, int K, int N, int act, g2v_stream_t stream) {
   G2V_REQUIRE(x && w && y, "null pointer");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0, "non-positive size");
   G2V_REQUIRE(act >= 0 && act <= 2, "bad activation");
-  RowMap am{ldx, rows_inner, stride_outer, stride_inner};
-  if (rows_inner == 0 && launch_smallm(false, x, ldx, x_keep, x_scale, w, (int64_t)K, bias, y, ldy, M, K, N, act, 0,
-                                       (hipStream_t)stream)) {
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
+  const DensePlan pl = dense_plan(G2V_DENSE_FORM_FWD, M, K, N, 0, act, bias != nullptr, x_keep != nullptr, rows_inner, stride_outer,
+                                  stride_inner, ldx, ldy, dense_smallm_rows(-1), dense_align(x, w, y, bias, x_keep));
+  const RowMap am{ldx, rows_inner, stride_outer, stride_inner};
+  const hipStream_t st = (hipStream_t)stream;
+  switch (pl.route) {
+    case G2V_DENSE_ROUTE_SMALLM: launch_smallm(pl, false, x, ldx, x_keep, x_scale, w, (int64_t)K, bias, y, ldy, M, K, N, act, 0, st); break;
+    case G2V_DENSE_ROUTE_STREAM: launch_stream<false>(pl, x, ldx, w, (int64_t)K, bias, y, ldy, M, K, N, act, 0, st); break;
+    case G2V_DENSE_ROUTE_K4: launch_k4(pl, x, am, w, bias, y, ldy, M, K, act, st); break;
+    default:
+      if (pl.variant == 4)
+        hipLaunchKernelGGL((gemm_nt_kernel<false, true>), pl.grid, dim3(256), 0, st, x, am, x_keep, x_scale, w, (int64_t)K, bias, y, ldy,
+                           M, K, N, act, 0);
+      else
+        hipLaunchKernelGGL(gemm_nt_kernel<false>, pl.grid, dim3(256), 0, st, x, am, x_keep, x_scale, w, (int64_t)K, bias, y, ldy, M, K,
+                           N, act, 0);
   }
-  if (rows_inner == 0 && !x_keep &&
-      launch_stream<false>(x, ldx, w, (int64_t)K, bias, y, ldy, M, K, N, act, 0, (hipStream_t)stream)) {
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  if (!x_keep && launch_k4(x, am, w, bias, y, ldy, M, K, N, act, (hipStream_t)stream)) {
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  dim3 grid(cdiv(M, BM), cdiv(N, BN));
-  const bool a_vec = !x_keep && (K & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                     (rows_inner > 0 ? ((stride_outer & 3) == 0 && (stride_inner & 3) == 0) : ((ldx & 3) == 0));
-  if (a_vec && (reinterpret_cast<uintptr_t>(w) & 15) == 0)
-    hipLaunchKernelGGL((gemm_nt_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, x, am, x_keep, x_scale, w,
-                       (int64_t)K, bias, y, ldy, M, K, N, act, 0);
-  else
-  hipLaunchKernelGGL(gemm_nt_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, am, x_keep, x_scale, w,
-                     (int64_t)K, bias, y, ldy, M, K, N, act, 0);
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
@@ -1443,23 +1498,21 @@ extern "C" int g2v_linear_compose2(const float* w0, const float* b0, const float
 }
 
 // y_a = act(x w_a^T + b_a), y_b = act(x w_b^T + b_b): the two directions' input projections of a bidirectional GRU layer (ref
-// Autoencoder_VQVAE_model.py:94, nn.GRU(bidirectional=True): weight_ih_l0 / weight_ih_l0_reverse) read the same x.  At small row
-// counts (2560 rows: 400 workgroups per product, 16 us each, back to back) ONE launch with grid.z = 2 runs both; each workgroup's
-// arithmetic is that of g2v_linear_fwd's LDS-tiled kernel (bitwise the same y).  Shapes the other dense kernels serve, and
-// unaligned operands, are two g2v_linear_fwd calls.
+// Autoencoder_VQVAE_model.py:94, nn.GRU(bidirectional=True): weight_ih_l0 / weight_ih_l0_reverse) read the same x.  Where the plan
+// says ONE launch (the LDS-tiled kernel with float4 operands, N > 192, at most 16384 rows) grid.z = 2 runs both;
+// each workgroup's arithmetic is that of g2v_linear_fwd's LDS-tiled kernel (bitwise the same y).  Two g2v_linear_fwd calls otherwise.
 extern "C" int g2v_linear_fwd_pair(const float* x, int64_t ldx, const float* w_a, const float* bias_a, float* y_a, const float* w_b,
                                    const float* bias_b, float* y_b, int64_t ldy, int M, int K, int N, int act,
                                    g2v_stream_t stream) {
   G2V_REQUIRE(x && w_a && w_b && y_a && y_b, "null pointer");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0, "non-positive size");
   G2V_REQUIRE(act >= 0 && act <= 2, "bad activation");
-  const bool tiled = M > g2v_internal_options().smallm_max_rows && N > 192 && !(N == 64 && K == 135);      // (neither launch_smallm, _stream nor _k4)
-  const bool vec = (K & 3) == 0 && (ldx & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_a) |
-                                                       reinterpret_cast<uintptr_t>(w_b)) & 15) == 0;
-  if (tiled && vec && M <= 16384) {
+  const DensePlan pl = dense_plan(G2V_DENSE_FORM_FWD_PAIR, M, K, N, 0, act, bias_a != nullptr, false, 0, 0, 0, ldx, ldy,
+                                  dense_smallm_rows(-1), dense_align(x, w_a, y_a, bias_a, nullptr, w_b));
+  if (pl.one_launch) {
     RowMap am{ldx, 0, 0, 0};
-    hipLaunchKernelGGL((gemm_nt_kernel<false, true>), dim3(cdiv(M, BM), cdiv(N, BN), 2), dim3(256), 0, (hipStream_t)stream, x, am,
-                       (const uint8_t*)nullptr, 1.0f, w_a, (int64_t)K, bias_a, y_a, ldy, M, K, N, act, 0, w_b, bias_b, y_b);
+    hipLaunchKernelGGL((gemm_nt_kernel<false, true>), pl.grid, dim3(256), 0, (hipStream_t)stream, x, am, (const uint8_t*)nullptr, 1.0f,
+                       w_a, (int64_t)K, bias_a, y_a, ldy, M, K, N, act, 0, w_b, bias_b, y_b);
     G2V_CHECK_LAUNCH();
     return G2V_OK;
   }
@@ -1475,15 +1528,13 @@ extern "C" int g2v_linear_fwd_dual(const float* x, int64_t ldx, const float* w_a
                                    g2v_stream_t stream) {
   G2V_REQUIRE(x && w_a && w_b && y_a && y_b, "null pointer");
   G2V_REQUIRE(M > 0 && K > 0 && N_a > 0 && N_b > 0 && ldx >= K && ldya >= N_a && ldyb >= N_b, "bad size");
-  auto a16 = [](const void* q_) { return (reinterpret_cast<uintptr_t>(q_) & 15) == 0; };
-  const int64_t tiles_a = (int64_t)cdiv(M, 16) * cdiv(N_a, 16), tiles_b = (int64_t)cdiv(M, 16) * cdiv(N_b, 16);
-  if (M <= g2v_internal_options().smallm_max_rows && (K & 3) == 0 && (ldx & 3) == 0 && a16(x) && a16(w_a) && a16(w_b) &&
-      tiles_a <= 2048 && tiles_b <= 2048) {
+  const DensePlan pl = dense_plan(G2V_DENSE_FORM_FWD_DUAL, M, K, N_a, N_b, 0, bias_a != nullptr, false, 0, 0, 0, ldx, ldya,
+                                  dense_smallm_rows(-1), dense_align(x, w_a, y_a, bias_a, nullptr, w_b));
+  if (pl.one_launch) {
     DualNT d;
     d.W[0] = w_a; d.bias[0] = bias_a; d.out[0] = y_a; d.ldc[0] = ldya; d.N[0] = N_a;
     d.W[1] = w_b; d.bias[1] = bias_b; d.out[1] = y_b; d.ldc[1] = ldyb; d.N[1] = N_b;
-    const int64_t tiles = tiles_a > tiles_b ? tiles_a : tiles_b;
-    hipLaunchKernelGGL(gemm_smallm_dual_nt_kernel, dim3(cdiv(tiles, 4), 2), dim3(256), 0, (hipStream_t)stream, x, ldx, d, M, K);
+    hipLaunchKernelGGL(gemm_smallm_dual_nt_kernel, pl.grid, dim3(256), 0, (hipStream_t)stream, x, ldx, d, M, K);
     G2V_CHECK_LAUNCH();
     return G2V_OK;
   }
@@ -1496,25 +1547,22 @@ extern "C" int g2v_linear_bwd_data(const float* dy, int64_t lddy, const float* w
                                    int N, int accumulate, g2v_stream_t stream) {
   G2V_REQUIRE(dy && w && dx, "null pointer");
   G2V_REQUIRE(M > 0 && K > 0 && N > 0, "non-positive size");
-  RowMap am{lddy, 0, 0, 0};
-  if (launch_smallm(true, dy, lddy, nullptr, 1.0f, w, (int64_t)K, nullptr, dx, lddx, M, N, K, 0, accumulate,
-                    (hipStream_t)stream)) {
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  if (launch_stream<true>(dy, lddy, w, (int64_t)K, nullptr, dx, lddx, M, N, K, 0, accumulate, (hipStream_t)stream)) {
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  dim3 grid(cdiv(M, BM), cdiv(K, BN));
+  const DensePlan pl = dense_plan(G2V_DENSE_FORM_BWD_DATA, M, K, N, 0, 0, false, false, 0, 0, 0, lddy, lddx, dense_smallm_rows(-1),
+                                  dense_align(dy, w, dx, nullptr, nullptr));
+  const RowMap am{lddy, 0, 0, 0};
+  const hipStream_t st = (hipStream_t)stream;
   // output feature = k (K of them), contraction over n (N): Bop[k][n] = w[n*K + k]
-  if ((N & 3) == 0 && (K & 3) == 0 && (lddy & 3) == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(w) & 15) == 0)
-    hipLaunchKernelGGL((gemm_nt_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, dy, am, (const uint8_t*)nullptr,
-                       1.0f, w, (int64_t)K, (const float*)nullptr, dx, lddx, M, N, K, 0, accumulate);
-  else
-  hipLaunchKernelGGL(gemm_nt_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, dy, am, (const uint8_t*)nullptr,
-                     1.0f, w, (int64_t)K, (const float*)nullptr, dx, lddx, M, N, K, 0, accumulate);
+  switch (pl.route) {
+    case G2V_DENSE_ROUTE_SMALLM: launch_smallm(pl, true, dy, lddy, nullptr, 1.0f, w, (int64_t)K, nullptr, dx, lddx, M, N, K, 0, accumulate, st); break;
+    case G2V_DENSE_ROUTE_STREAM: launch_stream<true>(pl, dy, lddy, w, (int64_t)K, nullptr, dx, lddx, M, N, K, 0, accumulate, st); break;
+    default:
+      if (pl.variant == 4)
+        hipLaunchKernelGGL((gemm_nt_kernel<true, true>), pl.grid, dim3(256), 0, st, dy, am, (const uint8_t*)nullptr, 1.0f, w, (int64_t)K,
+                           (const float*)nullptr, dx, lddx, M, N, K, 0, accumulate);
+      else
+        hipLaunchKernelGGL(gemm_nt_kernel<true>, pl.grid, dim3(256), 0, st, dy, am, (const uint8_t*)nullptr, 1.0f, w, (int64_t)K,
+                           (const float*)nullptr, dx, lddx, M, N, K, 0, accumulate);
+  }
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }

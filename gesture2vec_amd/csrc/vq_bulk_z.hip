@@ -1,8 +1,10 @@
 // vq_bulk_z.hip -- bulk code assignment from RAW latents at the checkpoints' width (E = 400): idx = argmin_k |W_pre z + b - w_k|^2
 // without writing the projected rows (pipeline.chunks_to_codes, VQ_Payam_EMA.assign; lmdb_data_loader.py:1274-1281).
 //
-// The contract is bitwise: idx equals g2v_linear_fwd (the tiled gemm_nt_kernel<false, true> above smallm_max_rows rows) followed by
-// g2v_vq_assign_packed_fwd (vq_assign_p_kernel, 2048 rows and up) on every row -- ties, near-ties and non-finite rows included.
+// The contract is bitwise: idx equals g2v_linear_fwd on the route g2v_linear_route names TILED with float4 operands (the forward
+// product M = N rows, 400 -> 400, bias, no mask: what the rows this kernel serves, N > smallm_rows, select -- held to the query by
+// tests/test_dense_route_host.py) followed by g2v_vq_assign_packed_fwd (vq_assign_p_kernel, 2048 rows and up) on every row -- ties,
+// near-ties and non-finite rows included.
 //
 //   vq_bulkz_pack_kernel     once per call: U = W W_pre (K x E, fp64 sums rounded once to fp32) as bf16 hi / lo images zero-padded
 //                            to [Kp][416], per-code constants {c'_k, P_k, Q_k, R0_k} (below), |W_pre|_F, |b| and a non-finite flag.

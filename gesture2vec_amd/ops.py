@@ -153,6 +153,26 @@ def linear_fwd(x, w, bias=None, act=0, *, M=None, ldx=None, row_map=None, keep=N
     return out
 
 
+def linear_route(form, M, K, N, *, N_b=0, act=0, bias=True, keep=False, row_map=None, ldx=None, ldy=None, smallm_rows=-1,
+                 unaligned=()) -> str:
+    """g2v_linear_route as a name: "SMALLM*2" (tn = 2), "STREAM*12x4" (the (NTW, KS) instance), "K4", "K4*1" (row-mapped),
+    "TILED*4" / "TILED*1" (float4 / scalar operands), "TILED*4|ONE_LAUNCH" (pair and dual forms: both products in one launch); ""
+    where the call is refused.  form "FWD" / "BWD_DATA" / "FWD_PAIR" / "FWD_DUAL"; w is (N, K) in every form; ldx / ldy: row strides
+    of the array read and written (default: dense); unaligned: names of the G2V_DENSE_ALIGN_* facts that do NOT hold (torch
+    allocations are 16-byte aligned: none); smallm_rows -1: the bound context's."""
+    c = _lib.CONSTANTS
+    bwd = form == "BWD_DATA"
+    ri, so, si = row_map if row_map is not None else (0, 0, 0)
+    align = sum(v for k, v in c.items() if k.startswith("G2V_DENSE_ALIGN_") and k[len("G2V_DENSE_ALIGN_"):] not in unaligned)
+    r = _lib_().g2v_linear_route(c["G2V_DENSE_FORM_" + form], int(M), int(K), int(N), int(N_b), int(act), int(bool(bias)), int(bool(keep)),
+                                 int(ri), int(so), int(si), int((N if bwd else K) if ldx is None else ldx),
+                                 int((K if bwd else N) if ldy is None else ldy), int(smallm_rows), align)
+    names = {v: k[len("G2V_DENSE_ROUTE_"):] for k, v in c.items() if k.startswith("G2V_DENSE_ROUTE_")}
+    route, v = names.get(r & 0xff, ""), (r >> 8) & 0xff
+    variant = f"*{v >> 4}x{v & 15}" if route == "STREAM" else (f"*{v}" if v else "")
+    return route + variant + ("|ONE_LAUNCH" if r & c["G2V_DENSE_ROUTE_ONE_LAUNCH"] else "")
+
+
 def linear_compose2(w0, b0, w1, b1, w_in, b_in):
     """(w_p w_in, w_p b_in + b_p) for p = 0, 1 (g2v_linear_compose2): two linear layers in a row as one."""
     G, H = w0.shape
@@ -431,7 +451,8 @@ def vq_assign_bulk(flat, codebook, code_sqnorm, want_undecided=False):
 
 
 def vq_assign_bulk_z_ok(N, E, K) -> bool:
-    """shapes g2v_vq_assign_bulk_z serves (E = 400, K % 16 == 0, 32 <= K <= 512, N >= 2048 and above smallm_max_rows)"""
+    """shapes g2v_vq_assign_bulk_z serves (E = 400, K % 16 == 0, 32 <= K <= 512, N >= 2048 and above smallm_rows: the rows whose
+    pre_linear product linear_route("FWD", N, 400, 400) names "TILED*4", the kernel whose bits it promises)"""
     return bool(_lib_().g2v_vq_assign_bulk_z_ok(int(N), int(E), int(K)))
 
 

@@ -128,6 +128,44 @@ int g2v_linear_fwd_dual(const float* x, int64_t ldx, const float* w_a, const flo
 int g2v_linear_bwd_data(const float* dy, int64_t lddy, const float* w, float* dx, int64_t lddx,
                         int M, int K, int N, int accumulate, g2v_stream_t stream);
 
+/* Which kernel a forward / data-gradient product above runs on: ONE decision (dense_plan, csrc/linear.hip; DESIGN.md section 3.6.2 has
+ * the measurement behind every row count), asked by the four entry points (host arithmetic only, no launch).  The first row that
+ * matches decides; C is the contraction length and O the output columns (forward: C = K, O = N; data gradient: C = N, O = K),
+ * "float4 rows": no row map, C % 4 == 0, ldx % 4 == 0 and ALIGN_X:
+ *   SMALLM   float4 rows, M <= smallm_rows, a keep mask only with ALIGN_KEEP, and for the forward ALIGN_W: one wave per 16 x 16 tn
+ *            output tile; variant tn = 1 / 2 / 4 while the 16 x 16 tiles number <= 2048 / <= 8192 / more
+ *   STREAM   float4 rows, no keep mask, M >= 1024, (C, O) in {(64, 192), (192, 64), (128, 128), (64, 64)} (C rounded up to 16),
+ *            act != 2, ALIGN_Y with ldy % 4 == 0, a bias only with ALIGN_BIAS (the weights' alignment is not asked): the streaming
+ *            kernel; variant = O / 16 << 4 | ceil(C / 16)
+ *   K4       forward, no keep mask, K == 135, N == 64, M >= 4096, M % 16 == 0, act != 2, ALIGN_Y with ldy % 4 == 0, a bias only
+ *            with ALIGN_BIAS: the kernel of unaligned 135-float rows; variant 1 with a row map
+ *   TILED    everything else: the LDS-tiled kernel; variant 4 (float4 operand loads) without a keep mask when K % 4 == 0 (data
+ *            gradient: and N % 4 == 0), ALIGN_X, ALIGN_W and ldx % 4 == 0 (row map: both strides % 4 == 0), variant 1 otherwise
+ * forms FWD_PAIR / FWD_DUAL answer for the single g2v_linear_fwd call on (M, K, N) and add G2V_DENSE_ROUTE_ONE_LAUNCH where the
+ * entry point runs both products in one launch: pair on TILED*4 with N > 192 and M <= 16384; dual where N and N_b are both SMALLM
+ * with tn = 1.  Otherwise they are two g2v_linear_fwd calls, each planned from its own pointers.
+ * g2v_linear_route returns G2V_DENSE_ROUTE_* in bits 0-7, the variant in bits 8-15 and ONE_LAUNCH above, or 0 for a refused call
+ * (a size <= 0, act outside 0..2, an unknown form).  K, N: the weight is [N][K] in every form; ldx / ldy: row strides of the array
+ * read (x, dy) and written (y, dx); what a form's entry point has no argument for is ignored (N_b outside FWD_DUAL; act, bias, keep
+ * and row map of BWD_DATA; keep and row map of the pair and dual forms, whose ALIGN_W speaks of both weights).  smallm_rows: -1 =
+ * the bound context's G2V_OPT_SMALLM_ROWS; align: an or of G2V_DENSE_ALIGN_*.  A function of its arguments alone otherwise. */
+#define G2V_DENSE_FORM_FWD 0
+#define G2V_DENSE_FORM_BWD_DATA 1
+#define G2V_DENSE_FORM_FWD_PAIR 2
+#define G2V_DENSE_FORM_FWD_DUAL 3
+#define G2V_DENSE_ROUTE_SMALLM 1
+#define G2V_DENSE_ROUTE_STREAM 2
+#define G2V_DENSE_ROUTE_K4 3
+#define G2V_DENSE_ROUTE_TILED 4
+#define G2V_DENSE_ROUTE_ONE_LAUNCH 65536
+#define G2V_DENSE_ALIGN_X 1         /* x (dy) is 16-byte aligned */
+#define G2V_DENSE_ALIGN_W 2         /* w is */
+#define G2V_DENSE_ALIGN_Y 4         /* y (dx) is */
+#define G2V_DENSE_ALIGN_BIAS 8      /* bias is */
+#define G2V_DENSE_ALIGN_KEEP 16     /* the keep mask is 4-byte aligned */
+int g2v_linear_route(int form, int M, int K, int N, int N_b, int act, int has_bias, int has_keep, int rows_inner,
+                     int64_t stride_outer, int64_t stride_inner, int64_t ldx, int64_t ldy, int smallm_rows, int align);
+
 /* dw[n, k] (+)= sum_m dy[m, n] * xin[m, k];  db[n] (+)= sum_m dy[m, n]  (db may be NULL).
  * xin addressing / keep-mask exactly as in g2v_linear_fwd.  Deterministic (split-M slabs + ordered
  * reduction, no float atomics).  workspace >= g2v_linear_bwd_weight_workspace(M,K,N) bytes.

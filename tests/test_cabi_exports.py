@@ -30,6 +30,7 @@ PINNED_SIGS = {
                                     c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_sz, c_fp]),
     "g2v_gru_seq_route": (c_int, [c_int] * 10),
     "g2v_vq_assign_route": (c_int, [c_int] * 7),
+    "g2v_linear_route": (c_int, [c_int] * 9 + [c_i64] * 4 + [c_int] * 2),
     "g2v_attn_code_rollout_route": (c_int, [c_int] * 12),
     "g2v_ctx_destroy": (None, [C.c_void_p]),
     "g2v_version": (C.c_char_p, []),

@@ -16,6 +16,7 @@ from _wgrad_shapes import WGRAD_ROUTE_SHAPES, route_name
 from _dec_route_shapes import DEC_ROUTE_SHAPES, route_name as dec_route_name
 from _gru_route_shapes import GRU_ROUTE_SHAPES
 import _vq_route_shapes as VS
+import _dense_route_shapes as DS
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +69,9 @@ def relclose(got, ref, rel=1e-4, msg=""):
                                    (1024, 200, 600), (1000, 64, 2100)])                                              # ... 2 / 4 tiles per wave
 @pytest.mark.parametrize("act", [0, 1])
 def test_linear_fwd(ops, M, K, N, act):
+    want = {(200, 135, 64): "TILED*1", (37, 50, 150): "TILED*1", (4096, 128, 128): "STREAM*8x8", (1, 3, 5): "TILED*1", (1024, 200, 600): "SMALLM*2",
+            (1000, 64, 2100): "SMALLM*4"}
+    assert ops.linear_route("FWD", M, K, N, act=act, smallm_rows=1024) == want.get((M, K, N), "SMALLM*1")
     x, w, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.2), rnd(N, seed=3)
     ref = O.linear(x, w, b)
     if act == 1:
@@ -80,6 +84,9 @@ def test_linear_fwd(ops, M, K, N, act):
 def test_linear_small_m_mask_tanh_and_data_gradient(ops, M, K, N):
     """M <= 1024 rows: gemm_smallm_kernel (one wave per 16 x 16 output tile) -- keep mask on the input, tanh epilogue, output
     into a wider buffer, data gradient with and without accumulation."""
+    assert ops.linear_route("FWD", M, K, N, keep=True, smallm_rows=1024) == ops.linear_route("FWD", M, K, N, act=2, smallm_rows=1024) == "SMALLM*1"
+    assert ops.linear_route("FWD", M, K, N, bias=False, ldy=N + 8, smallm_rows=1024) == "SMALLM*1"
+    assert ops.linear_route("BWD_DATA", M, K, N, smallm_rows=1024) == ("SMALLM*1" if N % 4 == 0 else "TILED*1")      # (contraction over N)
     x, w, b = rnd(M, K, seed=11), rnd(N, K, seed=12, scale=0.2), rnd(N, seed=13)
     keep = (torch.rand(M, K, generator=torch.Generator().manual_seed(14)) < 0.8).to(torch.uint8)
     ref = O.linear(x * keep * 1.25, w, b)
@@ -119,8 +126,109 @@ def test_linear_small_m_mask_tanh_and_data_gradient(ops, M, K, N):
     assert torch.equal(dw3, dw)
 
 
+def _dense_case_inputs(case):
+    """seeded operands of one DENSE_ROUTE_SHAPES entry on the device, as the entry's form reads them, + the float64 result(s)"""
+    form, M, K, N = case["form"], case["M"], case["K"], case["N"]
+    w, b = rnd(N, K, seed=2, scale=0.2), rnd(N, seed=3) if case.get("bias", True) else None
+    f = {0: lambda v: v, 1: torch.relu, 2: torch.tanh}[case.get("act", 0)]
+    lin64 = lambda x64, w_, b_: f(x64 @ w_.double().t() + (b_.double() if b_ is not None else 0.0)).float()
+    dev = lambda t: None if t is None else t.to(DEV)
+    if form == "BWD_DATA":
+        dy = rnd(M, N, seed=1)
+        return dict(dy=dev(dy), w=dev(w)), [(dy.double() @ w.double()).float()]
+    x = rnd(M, K, seed=1)
+    x64, keep, rm, ldx, off = x.double(), None, case.get("row_map"), case.get("ldx"), case.get("x_offset", 0)
+    if case.get("keep"):
+        keep = (torch.rand(M, K, generator=torch.Generator().manual_seed(7)) < 0.8).to(torch.uint8)
+        x64 = x64 * keep * 1.25
+    if rm is not None:      # the (B, T, K) tensor whose (T, B) row order is x
+        xd = dev(x.view(rm[1], rm[0], K).transpose(0, 1).contiguous())
+    elif ldx is not None:
+        xd = torch.zeros(M, ldx)
+        xd[:, :K] = x
+        xd = dev(xd)
+    elif off:               # a view that starts `off` floats into its allocation
+        xd = torch.zeros(M * K + off, device=DEV)[off:]
+        xd.copy_(x.reshape(-1))
+        assert xd.data_ptr() % 16 == 4 * off
+    else:
+        xd = dev(x)
+    inp = dict(x=xd, w=dev(w), b=dev(b), keep=dev(keep), row_map=DS.strides(K, rm))
+    refs = [lin64(x64, w, b)]
+    if form in ("FWD_PAIR", "FWD_DUAL"):
+        Nb = case["N_b"] if form == "FWD_DUAL" else N
+        wb, bb = rnd(Nb, K, seed=4, scale=0.2), rnd(Nb, seed=5) if b is not None else None
+        inp.update(w_b=dev(wb), b_b=dev(bb))
+        refs.append(lin64(x64, wb, bb))
+    return inp, refs
+
+
+def _dense_case_run(ops, case, inp, ldy=None, base=None):
+    """the ops.* call of the entry's form -> its outputs, (M, ldy) buffers pre-filled with 7 where ldy is given; base: the data
+    gradient accumulates into a copy of it"""
+    form, M, K, N = case["form"], case["M"], case["K"], case["N"]
+    out = lambda n: None if ldy is None else torch.full((M, ldy), 7.0, device=DEV)
+    if form == "BWD_DATA":
+        o = base.clone() if base is not None else out(K)
+        return [ops.linear_bwd_data(inp["dy"], inp["w"], M=M, out=o, lddx=ldy, accumulate=base is not None)]
+    fwd = lambda w_, b_, o: ops.linear_fwd(inp["x"], w_, b_, act=case.get("act", 0), M=M, ldx=case.get("ldx"), row_map=inp["row_map"], keep=inp["keep"],
+                                           scale=1.25, out=o, ldy=ldy)
+    if form == "FWD":
+        return [fwd(inp["w"], inp["b"], out(N))]
+    if form == "FWD_PAIR":
+        if ldy is None:
+            return list(ops.linear_fwd_pair(inp["x"], inp["w"], inp["b"], inp["w_b"], inp["b_b"], case.get("act", 0), M=M))
+        return [fwd(inp["w"], inp["b"], out(N)), fwd(inp["w_b"], inp["b_b"], out(N))]       # (the two single calls)
+    Nb = case["N_b"]
+    if ldy is None:
+        outs = [torch.empty(M, N, device=DEV), torch.empty(M, Nb, device=DEV)]
+        ops.linear_fwd_dual(inp["x"], inp["w"], inp["b"], outs[0], inp["w_b"], inp["b_b"], outs[1])
+        return outs
+    return [fwd(inp["w"], inp["b"], out(N)), fwd(inp["w_b"], inp["b_b"], out(Nb))]
+
+
+@pytest.mark.parametrize("case", DS.DENSE_ROUTE_SHAPES, ids=lambda c: c["name"])
+def test_linear_on_every_route(ops, case):
+    """Every route of the dense forward / data-gradient plan, every variant and every form, at the smallest shape that selects it,
+    and the nearest shapes that miss it (tests/_dense_route_shapes.py; the selection itself is asserted here and, without a device,
+    in tests/test_dense_route_host.py): against float64, deterministic, a strided output with its padding untouched, the data
+    gradient's accumulation, and the pair / dual forms bitwise their two single calls."""
+    from gesture2vec_amd import _lib
+    form, M, K, N = case["form"], case["M"], case["K"], case["N"]
+    widths = [K] if form == "BWD_DATA" else [N, case["N_b"] if form == "FWD_DUAL" else N][:1 if form == "FWD" else 2]
+    with _lib.Context.current().scoped(smallm_rows=case.get("smallm_rows", 1024)):
+        assert DS.route(**case) == DS.route(**{**case, "smallm_rows": -1}) == case["route"]
+        inp, refs = _dense_case_inputs(case)
+        first = _dense_case_run(ops, case, inp, ldy=case.get("ldy") if form == "FWD" else None)
+        tol = 5e-6 if case.get("act") == 2 else (4e-6 if form == "BWD_DATA" and N > 1024 else 2e-6)
+        for p, (got, ref) in enumerate(zip(first, refs)):
+            relclose(got[:, :widths[p]], ref, tol, f"output {p} vs float64")
+        again = _dense_case_run(ops, case, inp, ldy=case.get("ldy") if form == "FWD" else None)
+        assert all(torch.equal(a, b) for a, b in zip(again, first)), "not deterministic"
+        # a strided output: the same kernel (the route does not change), the same bits, the padding untouched; for the pair and
+        # dual forms these are the two single calls
+        ldys = [case.get("ldy") or wd + 8 for wd in widths]
+        singles = []
+        for p, wd in enumerate(widths):
+            if form in ("FWD", "BWD_DATA"):
+                assert DS.route(**{**case, "ldy": ldys[p]}) == case["route"]
+                wide = _dense_case_run(ops, case, inp, ldy=ldys[p])[0]
+            else:
+                one = dict(case, form="FWD", N=wd, ldy=ldys[p])
+                assert DS.route(**one) == case["route"].split("|")[0] or p == 1
+                wide = _dense_case_run(ops, one, dict(inp, w=inp["w_b"], b=inp["b_b"]) if p else inp, ldy=ldys[p])[0]
+            assert torch.equal(wide[:, :wd], first[p][:, :wd]), f"output {p}: strided differs from dense"
+            assert float((wide[:, wd:] - 7.0).abs().max()) == 0.0, f"output {p}: wrote into the padding"
+            singles.append(wide)
+        if form == "BWD_DATA":
+            base = rnd(M, K, seed=16)
+            acc = _dense_case_run(ops, case, inp, base=base.to(DEV))[0]
+            relclose(acc, (base.double() + refs[0].double()).float(), tol, "data gradient, accumulate")
+
+
 def test_linear_fwd_rowmap_and_mask(ops):
     B, T, D, H = 7, 5, 135, 64
+    assert ops.linear_route("FWD", T * B, D, H, keep=True, row_map=(B, D, T * D)) == "TILED*1"
     x_btd = rnd(B, T, D, seed=4)
     keep = (torch.rand(T, B, D, generator=torch.Generator().manual_seed(5)) < 0.8).to(torch.uint8)
     w, b = rnd(H, D, seed=6, scale=0.1), rnd(H, seed=7)
@@ -238,6 +346,8 @@ def test_linear_bwd(ops, M, K, N):
     want = {(5000, 64, 192): "WAVE|RAGGED_TAIL", (139264 // 8, 64, 192): "WAVE", (1000, 64, 2100): "SMALL_LDS",
             (8192 + 5, 64, 192): "WAVE|RAGGED_TAIL", (33 * 4100 // 4, 135, 64): "WAVE|RAGGED_TAIL", (4096 + 31, 200, 600): "WAVE_GEN|RAGGED_TAIL"}
     assert route_name(M, K, N) == want.get((M, K, N), "WAVE_GEN" if M >= 4096 else "SMALL_TILE")
+    assert ops.linear_route("BWD_DATA", M, K, N, smallm_rows=1024) == (
+        "SMALLM*1" if M <= 1024 and N % 4 == 0 else "STREAM*4x12" if (K, N) == (64, 192) else "TILED*4" if K % 4 == 0 and N % 4 == 0 else "TILED*1")
     x, w, dy = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.2), rnd(M, N, seed=3)
     dx = ops.linear_bwd_data(dy.to(DEV), w.to(DEV))
     relclose(dx, (dy.double() @ w.double()).float(), 2e-6 if N <= 1024 else 4e-6, "bwd_data")      # fp32 fma chain of length N
@@ -2146,6 +2256,9 @@ def test_linear_compose2_equals_the_two_layers_in_a_row(ops, G, H, D, M):
 def test_linear_fwd_pair_equals_two_calls(ops, M, K, N, act):
     """g2v_linear_fwd_pair (both directions' GRU input projections in one launch at small row counts) is BITWISE two
     g2v_linear_fwd calls, on the shapes it serves itself and on the ones it hands on."""
+    want = {(2560, 200, 600): "TILED*4|ONE_LAUNCH", (1280, 200, 600): "TILED*4|ONE_LAUNCH", (2560, 64, 192): "STREAM*12x4", (300, 50, 150): "TILED*1",
+            (2560, 202, 600): "TILED*1"}[(M, K, N)]
+    assert ops.linear_route("FWD_PAIR", M, K, N, act=act, smallm_rows=1024) == want
     x = rnd(M, K, seed=100).to(DEV)
     wa, wb = rnd(N, K, seed=101).to(DEV), rnd(N, K, seed=102).to(DEV)
     ba, bb = rnd(N, seed=103).to(DEV), rnd(N, seed=104).to(DEV)
