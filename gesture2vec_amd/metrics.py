@@ -9,11 +9,17 @@
 
 The reference does all of it on the host with numpy / scipy / sklearn on latents pulled off the device chunk by chunk; nothing here
 needs scipy or sklearn.  For an autoencoder without a quantiser the code ids come from a fitted `gesture2vec_amd.kmeans.KMeans`
-(`kmeans=`), as the reference takes them from its pickled k-means model.  Out of scope: BLEU over code sequences (`:1560-1609`, host
-string work on `torchtext`) and the plots (the PCA + t-SNE maps are `gesture2vec_amd.embedding`)."""
+(`kmeans=`), as the reference takes them from its pickled k-means model.
+* BLEU of each test case's code sequence against the ground truth's sequence of the same test case (`:1560-1609`:
+  `torchtext.data.metrics.bleu_score(max_n=4, weights=[.25] * 4)`, one sentence and one reference per call): `code_bleu` -- the clipped
+  n-gram counts over the integer ids come from g2v_ngram_clipped_counts, `bleu_from_counts` turns them into scores in float64 where
+  the ids are.  torchtext forms the score in float32 and is not installed where this was written: parity with it is claimed from its
+  definition, to float32 rounding, not from a recorded run.
+
+Out of scope: the plots (the PCA + t-SNE maps are `gesture2vec_amd.embedding`)."""
 from __future__ import annotations
 
-from typing import Callable, Optional
+from typing import Callable, Optional, Sequence
 
 import numpy as np
 import torch
@@ -178,10 +184,116 @@ def wasserstein(h1, h2) -> float:
     return float(np.abs(np.cumsum(_pdf(h1)) - np.cumsum(_pdf(h2)))[:-1].sum())
 
 
+BLEU_MAX_LEN, BLEU_MAX_K = 4096, 65536                     # g2v_ngram_clipped_counts: longest sequence, largest codebook
+
+
+def bleu_from_counts(clipped: torch.Tensor, cand_len: torch.Tensor, ref_len: torch.Tensor, weights=None, corpus: bool = False):
+    """torchtext's `bleu_score` formula on clipped n-gram counts: clipped (B, max_n) integers, cand_len / ref_len (B,) -> (B,) float64
+    scores on the inputs' device (any device; pure torch).  Per pair, with total_n = max(cand_len - n + 1, 0):
+        0 if any clipped_n == 0, else exp(min(1 - ref_len / cand_len, 0)) * exp(sum_n w_n log(clipped_n / total_n)).
+    weights: max_n numbers, default 1 / max_n each.  corpus=True: counts, totals and lengths are summed over the pairs first and ONE
+    0-d score is returned (torchtext's corpus of several sentences with one reference each)."""
+    if clipped.dim() != 2 or cand_len.shape != (clipped.shape[0],) or ref_len.shape != (clipped.shape[0],):
+        raise ValueError(f"bleu_from_counts: clipped must be (B, max_n) and the lengths (B,), got {tuple(clipped.shape)}, "
+                         f"{tuple(cand_len.shape)}, {tuple(ref_len.shape)}")
+    max_n = clipped.shape[1]
+    w = torch.full((max_n,), 1.0 / max_n, dtype=torch.float64) if weights is None else torch.as_tensor(weights, dtype=torch.float64)
+    if w.shape != (max_n,):
+        raise ValueError(f"bleu_from_counts: {max_n} orders need {max_n} weights, got {tuple(w.shape)}")
+    w = w.to(clipped.device)
+    clipped, lc, lr = clipped.to(torch.int64), cand_len.to(torch.int64), ref_len.to(torch.int64)
+    n = torch.arange(1, max_n + 1, dtype=torch.int64, device=clipped.device)
+    total = (lc[:, None] - n[None, :] + 1).clamp_min(0)
+    if corpus:
+        clipped, total, lc, lr = clipped.sum(0, keepdim=True), total.sum(0, keepdim=True), lc.sum(0, keepdim=True), lr.sum(0, keepdim=True)
+    zero = (clipped <= 0).any(dim=1)                       # (clipped_n <= total_n: a zero total is a zero count)
+    one = torch.ones((), dtype=torch.float64, device=clipped.device)
+    pn = torch.where(zero[:, None], one, clipped.to(torch.float64) / total.clamp_min(1).to(torch.float64))
+    bp = torch.exp((1.0 - lr.to(torch.float64) / lc.clamp_min(1).to(torch.float64)).clamp_max(0.0))
+    score = torch.where(zero, torch.zeros_like(bp), bp * torch.exp((w[None, :] * torch.log(pn)).sum(dim=1)))
+    return score[0] if corpus else score
+
+
+def _flat_sequences(seqs, lengths, what: str):
+    """-> (flat int64 ids, start (B,), len (B,), longest possible length, B); every tensor stays on the device"""
+    if torch.is_tensor(seqs):
+        if seqs.dim() != 2 or seqs.dtype != torch.int64:
+            raise ValueError(f"code_bleu: {what} must be a (B, L) int64 tensor or a list of 1-D int64 tensors")
+        _need_cuda(seqs, "code_bleu")
+        B, L = seqs.shape
+        if L > BLEU_MAX_LEN:
+            raise ValueError(f"code_bleu: {what} rows hold {L} ids, the kernel takes at most {BLEU_MAX_LEN} per sequence")
+        if B and L and (seqs.stride(1) != 1 or seqs.stride(0) < L):
+            seqs = seqs.contiguous()
+        stride = seqs.stride(0) if B and L else max(L, 1)
+        flat = torch.as_strided(seqs, ((B - 1) * stride + L,), (1,)) if B and L else seqs.reshape(-1)
+        start = torch.arange(B, dtype=torch.int64, device=seqs.device) * stride
+        if lengths is None:
+            lens = torch.full((B,), L, dtype=torch.int64, device=seqs.device)
+        else:
+            lens = torch.as_tensor(lengths).to(device=seqs.device, dtype=torch.int64).contiguous()
+            if lens.shape != (B,):
+                raise ValueError(f"code_bleu: {what} has {B} rows and {tuple(lens.shape)} lengths")
+        return flat, start, lens, L, B
+    seqs = list(seqs)
+    if lengths is not None:
+        raise ValueError(f"code_bleu: lengths go with a padded (B, L) tensor; a list of {what} carries its own")
+    for t in seqs:
+        if not torch.is_tensor(t) or t.dim() != 1 or t.dtype != torch.int64:
+            raise ValueError(f"code_bleu: {what} must be a (B, L) int64 tensor or a list of 1-D int64 tensors")
+        _need_cuda(t, "code_bleu")
+    sizes = [int(t.numel()) for t in seqs]                  # (shapes: host knowledge, nothing is read back)
+    if sizes and max(sizes) > BLEU_MAX_LEN:
+        raise ValueError(f"code_bleu: a sequence of {what} holds {max(sizes)} ids, the kernel takes at most {BLEU_MAX_LEN}")
+    dev = seqs[0].device if seqs else torch.device("cuda:0")
+    flat = torch.cat(seqs) if seqs else torch.zeros((0,), dtype=torch.int64, device=dev)
+    lens_h = np.asarray(sizes, dtype=np.int64)
+    start_h = np.concatenate([[0], np.cumsum(lens_h)[:-1]]).astype(np.int64) if sizes else lens_h
+    return flat, torch.from_numpy(start_h).to(dev), torch.from_numpy(lens_h).to(dev), max(sizes, default=0), len(sizes)
+
+
 @torch.no_grad()
-def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int], kmeans=None):
+def code_bleu(candidates, references, *, cand_lengths=None, ref_lengths=None, K: int, max_n: int = 4, weights=None) -> torch.Tensor:
+    """BLEU of B candidate code sequences, each against ITS reference sequence -> (B,) float64 scores on the GPU: torchtext's
+    `bleu_score([cand], [[ref]], max_n, weights)` per pair, as `Metrics_analysis` calls it per test case.  ONE reference per candidate
+    is supported (all the reference program uses); several references per candidate are not.
+
+    candidates / references: each a (B, L) int64 GPU tensor of ids in [0, K) (rows may be strided; `cand_lengths` / `ref_lengths`,
+    tensors or sequences of B numbers, give shorter rows -- what lies past a length is not read), or a list of B 1-D int64 GPU
+    tensors.  The padded route reads nothing back; the scores stay on the device.  After the launch ONE number comes back: the count
+    of pairs with an id outside [0, K) or a length outside [0, L]; a non-zero count raises ValueError."""
     from . import ops
-    mom, counts = None, None
+    if not 1 <= int(K) <= BLEU_MAX_K:
+        raise ValueError(f"code_bleu: K = {K} outside [1, {BLEU_MAX_K}] (an n-gram is packed from 16-bit ids)")
+    if not 1 <= int(max_n) <= 4:
+        raise ValueError(f"code_bleu: max_n = {max_n} outside [1, 4]")
+    c, cs, cl, c_max, Bc = _flat_sequences(candidates, cand_lengths, "candidates")
+    r, rs, rl, r_max, Br = _flat_sequences(references, ref_lengths, "references")
+    if Bc != Br:
+        raise ValueError(f"code_bleu: {Bc} candidates against {Br} references: one reference per candidate")
+    if c.device != r.device:
+        raise ValueError("code_bleu: candidates and references are on different devices")
+    if Bc == 0:
+        return torch.zeros((0,), dtype=torch.float64, device=c.device)
+    clipped, bad = ops.ngram_clipped_counts(c, cs, cl, r, rs, rl, int(K), int(max_n), max(c_max, r_max))
+    n_bad = int(bad.item())
+    if n_bad:
+        raise ValueError(f"code_bleu: {n_bad} of {Bc} pairs hold a code id outside [0, {K}) or a length outside its row")
+    return bleu_from_counts(clipped, cl, rl, weights)
+
+
+def _clip_counts(clips, n_chunks: int, what: str) -> list:
+    counts = [int(v) for v in np.asarray(clips).reshape(-1)]
+    if any(v < 0 for v in counts) or sum(counts) != n_chunks:
+        raise ValueError(f"gesture_metrics: {what} must be non-negative chunk counts that sum to the set's {n_chunks} chunks, "
+                         f"got a sum of {sum(counts)}")
+    return counts
+
+
+@torch.no_grad()
+def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int], kmeans=None, keep_ids: bool = False):
+    from . import ops
+    mom, counts, kept = None, None, []
     for a in range(0, chunks.shape[0], batch_rows):
         x = chunks[a:a + batch_rows]
         if dae is not None and dae.encoder is not None:
@@ -192,31 +304,51 @@ def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int], kme
             mom = LatentMoments(lat.shape[1], lat.device)
         mom.update(lat)
         if K is not None:
-            counts = ops.code_histogram(kmeans.predict_device(lat) if kmeans is not None else net.vq_layer.assign(lat), K, counts)
+            ids = kmeans.predict_device(lat) if kmeans is not None else net.vq_layer.assign(lat)
+            counts = ops.code_histogram(ids, K, counts)
+            if keep_ids:
+                kept.append(ids)
     if K is not None:
         counts = counts.cpu().numpy()
         if counts[K]:
             raise ValueError(f"gesture_metrics: {int(counts[K])} code ids outside [0, {K})")
         counts = counts[:K]
+    if keep_ids:
+        return mom, counts, torch.cat(kept)
     return mom, counts
 
 
 @torch.no_grad()
 def gesture_metrics(net, real_chunks: torch.Tensor, generated_chunks: torch.Tensor, dae=None, batch_rows: int = 65536,
-                    kmeans=None) -> dict:
+                    kmeans=None, real_clips: Optional[Sequence[int]] = None, generated_clips: Optional[Sequence[int]] = None) -> dict:
     """Both (N, T, D) chunk sets -> [dae.encode per frame ->] chunk_latents -> moments (+ vq_layer.assign -> histogram), streamed in
     batches of `batch_rows` chunks.  A net without a quantiser gives the Frechet distance and None for the code metrics, unless a
-    fitted `kmeans` (gesture2vec_amd.kmeans.KMeans) is given: its ids then fill the histogram columns."""
+    fitted `kmeans` (gesture2vec_amd.kmeans.KMeans) is given: its ids then fill the histogram columns.
+
+    real_clips / generated_clips (both or neither; equally many): the number of consecutive chunks of each clip (test case) of the
+    set, summing to its N.  The code ids of the scan are then kept, and clip i of the generated set is scored against clip i of the
+    real set with `code_bleu`; the result gains `bleu` (mean over the clips), `bleu_var` (np.var: what the reference prints behind
+    `+-`), `bleu_sum` and `bleu_scores` (float64 numpy, per clip).  Needs code ids: a quantiser or `kmeans=`."""
     _need_cuda(real_chunks, "gesture_metrics")
     _need_cuda(generated_chunks, "gesture_metrics")
     if real_chunks.shape[0] == 0 or generated_chunks.shape[0] == 0:
         raise ValueError("gesture_metrics: an empty chunk set")
+    if (real_clips is None) != (generated_clips is None):
+        raise ValueError("gesture_metrics: real_clips and generated_clips go together (clip i is scored against clip i)")
+    clips = real_clips is not None
+    if clips:
+        real_clips = _clip_counts(real_clips, real_chunks.shape[0], "real_clips")
+        generated_clips = _clip_counts(generated_clips, generated_chunks.shape[0], "generated_clips")
+        if len(real_clips) != len(generated_clips) or not real_clips:
+            raise ValueError(f"gesture_metrics: {len(real_clips)} real clips against {len(generated_clips)} generated ones")
     if getattr(net, "vq", True):
         K, kmeans = int(net.vq_layer._num_embeddings), None
     else:
         K = None if kmeans is None else int(kmeans.n_clusters)
-    m_r, h_r = _scan(net, real_chunks, dae, int(batch_rows), K, kmeans)
-    m_g, h_g = _scan(net, generated_chunks, dae, int(batch_rows), K, kmeans)
+    if clips and K is None:
+        raise ValueError("gesture_metrics: BLEU is scored over code ids: a net without a quantiser needs a fitted kmeans=")
+    m_r, h_r, *ids_r = _scan(net, real_chunks, dae, int(batch_rows), K, kmeans, keep_ids=clips)
+    m_g, h_g, *ids_g = _scan(net, generated_chunks, dae, int(batch_rows), K, kmeans, keep_ids=clips)
     n_r, mu_r, cov_r = m_r.finalize()
     n_g, mu_g, cov_g = m_g.finalize()
     out = {"frechet": frechet_distance(mu_r, cov_r, mu_g, cov_g), "hellinger": None, "perplexity_real": None,
@@ -224,4 +356,8 @@ def gesture_metrics(net, real_chunks: torch.Tensor, generated_chunks: torch.Tens
     if K is not None:
         out.update(hellinger=hellinger(h_r, h_g), perplexity_real=histogram_perplexity(h_r),
                    perplexity_generated=histogram_perplexity(h_g), wasserstein=wasserstein(h_r, h_g))
+    if clips:
+        scores = code_bleu(list(torch.split(ids_g[0], generated_clips)), list(torch.split(ids_r[0], real_clips)), K=K)
+        scores = scores.cpu().numpy()
+        out.update(bleu=float(np.mean(scores)), bleu_var=float(np.var(scores)), bleu_sum=float(np.sum(scores)), bleu_scores=scores)
     return out

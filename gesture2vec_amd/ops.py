@@ -1217,6 +1217,32 @@ def code_histogram(idx, K, counts=None):
     return counts
 
 
+NGRAM_MAX_LEN, NGRAM_MAX_K, NGRAM_MAX_N = 4096, 65536, 4        # the limits of g2v_ngram_clipped_counts (include/g2v.h)
+
+
+def ngram_clipped_counts(cand, cand_start, cand_len, ref, ref_start, ref_len, K, max_n=4, max_len=NGRAM_MAX_LEN):
+    """-> (clipped (B, max_n) int64, bad (1,) int64) of B (candidate, reference) pairs of code-id sequences (g2v_ngram_clipped_counts):
+    clipped[b, n-1] = sum over candidate b's distinct n-grams of min(count in the candidate, count in the reference).  cand / ref: flat
+    int64 id arrays; sequence b is the *_len[b] ids from element *_start[b] on (all (B,) int64, on the device, not read back).  max_len:
+    the caller's upper bound on every length (it picks the kernel: give the tightest one known).  A pair with an id outside [0, K) or a
+    length outside [0, max_len] has -1 in its row and counts in bad[0]."""
+    B = cand_start.numel()
+    for name, t in (("cand_len", cand_len), ("ref_start", ref_start), ("ref_len", ref_len)):
+        if t.numel() != B:
+            raise ValueError(f"ngram_clipped_counts: {name} has {t.numel()} entries, cand_start has {B}")
+    if cand.numel() == 0 or ref.numel() == 0:                      # (every length on that side is 0: nothing is read, but the
+        pad = torch.zeros((1,), dtype=torch.int64, device=cand.device)     # entry refuses a null pointer)
+        cand, ref = (pad if cand.numel() == 0 else cand), (pad if ref.numel() == 0 else ref)
+    clipped = torch.empty((B, int(max_n)), dtype=torch.int64, device=cand.device)
+    bad = torch.zeros((1,), dtype=torch.int64, device=cand.device)
+    i64 = torch.int64
+    check(_lib_().g2v_ngram_clipped_counts(_p(_chk(cand, i64, "cand")), _p(_chk(cand_start, i64, "cand_start")),
+                                           _p(_chk(cand_len, i64, "cand_len")), _p(_chk(ref, i64, "ref")),
+                                           _p(_chk(ref_start, i64, "ref_start")), _p(_chk(ref_len, i64, "ref_len")), _p(clipped), _p(bad),
+                                           B, int(K), int(max_n), int(max_len), _stream()), "ngram_clipped_counts")
+    return clipped, bad
+
+
 # ------------------------------------------------------------------------------------------ k-means (kmeans.hip)
 KMEANS_STATE = ("done", "n_iter", "n_changed", "shift", "inertia", "n_relocated", "active", "tol_abs")   # the float64[8] state block
 

@@ -1312,6 +1312,24 @@ int g2v_moments_accumulate(const float* x, int64_t ld, const float* shift, doubl
 /* counts[k] += #{n : idx[n] == k} for k < K; ids outside [0, K) are counted in counts[K] and never used as an address.
  * counts: int64[K + 1].  Integer atomics only: exact and order-independent. */
 int g2v_code_histogram(const int64_t* idx, int64_t N, int K, int64_t* counts, g2v_stream_t stream);
+/* Clipped n-gram match counts of B independent (candidate, reference) pairs of code-id sequences (ngram.hip): the integer half of
+ * BLEU over code sequences (torchtext's bleu_score with one reference per candidate, Clustering.py:1560-1609):
+ *   clipped[b][n-1] = sum over the distinct n-grams g of candidate b of min(count in the candidate, count in the reference), n = 1 .. max_n
+ *   (= sum((Counter(candidate n-grams) & Counter(reference n-grams)).values())).
+ * Sequence b of `cand` is the cand_len[b] ids from element cand_start[b] on, the same for `ref`: one entry serves a padded (B, L)
+ * tensor (start = b * row stride; what lies past a length is not read) and a ragged concatenation.  The starts are the caller's
+ * addresses and are trusted; the lengths live on the device and are not read back: max_len is the caller's upper bound on all of
+ * them and picks the kernel (max_len <= 64: one wavefront per pair, the rank form over LDS broadcasts; longer: one workgroup per
+ * pair, both key arrays sorted in LDS, run starts matched by binary search).
+ * 1 <= max_n <= 4, 1 <= K <= 65536 (an n-gram is one 64-bit key of 16-bit ids), 0 <= max_len <= 4096: G2V_ERR_UNSUPPORTED above,
+ * G2V_ERR_ARG below, B < 1 or a null pointer, all before any launch (nothing is written).  A length below n gives 0 for order n.
+ * A pair with a length outside [0, max_len] or an id outside [0, K) gets -1 in its max_n slots and adds 1 to bad[0] (int64[1],
+ * cleared by the caller; an integer atomic); its out-of-range values are never used as an address or a key, the other pairs are
+ * untouched.  clipped: int64[B][max_n].  Integer arithmetic only: exact, the same bits on every run, a pair's counts do not depend on
+ * the rest of the batch.  No workspace. */
+int g2v_ngram_clipped_counts(const int64_t* cand, const int64_t* cand_start, const int64_t* cand_len, const int64_t* ref,
+                             const int64_t* ref_start, const int64_t* ref_len, int64_t* clipped, int64_t* bad, int64_t B, int K,
+                             int max_n, int max_len, g2v_stream_t stream);
 
 /* ---- k-means over latent rows (kmeans.hip; gesture2vec_amd/kmeans.py) -------------------------------------------------------------
  * The reference fits sklearn.cluster.KMeans on the (N, L*H) chunk latents of a quantiser-free autoencoder (Clustering.py:705-725) and

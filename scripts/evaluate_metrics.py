@@ -6,8 +6,12 @@
 
 Both arrays hold (N, T, D) pose chunks: D = the chunk autoencoder's `rep_learning_dim`, or the raw pose dimension when a DAE
 checkpoint is given (frames then go through its encoder first, as in `stacked_autoencode`).  Prints the four numbers in the order of
-the reference's Metrics.txt lines (:1546-1558); the code metrics read "None" for a checkpoint without a quantiser.  BLEU over code
-sequences, t-SNE, k-means and the plots of `Metrics_analysis` are not computed."""
+the reference's Metrics.txt lines (:1546-1558); the code metrics read "None" for a checkpoint without a quantiser.
+
+    ... --real_clips a.npy --generated_clips b.npy        (or --clip_chunks N: every clip holds N chunks)
+
+adds the BLEU line (:1601-1608): the code sequence of generated clip i scored against that of real clip i.  Both .npy files hold
+the number of consecutive chunks of each clip.  t-SNE, k-means and the plots of `Metrics_analysis` are not computed."""
 from __future__ import annotations
 
 import argparse
@@ -33,6 +37,9 @@ def main(argv=None):
     ap.add_argument("--dae_checkpoint", default=None, help="frame DAE checkpoint (train_DAE.py): chunks are raw poses")
     ap.add_argument("--real", required=True, help=".npy of (N, T, D) ground-truth chunks")
     ap.add_argument("--generated", required=True, help=".npy of (N, T, D) generated chunks")
+    ap.add_argument("--real_clips", default=None, help=".npy of ints: chunks per ground-truth clip (adds the BLEU line)")
+    ap.add_argument("--generated_clips", default=None, help=".npy of ints: chunks per generated clip")
+    ap.add_argument("--clip_chunks", type=int, default=None, help="shorthand: every clip of both sets holds this many chunks")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -43,12 +50,26 @@ def main(argv=None):
         _, dae, _, _, _ = load_checkpoint_and_model(a.dae_checkpoint, dev, "DAE")
     real = torch.from_numpy(np.load(a.real).astype(np.float32, copy=False)).to(dev)
     gen = torch.from_numpy(np.load(a.generated).astype(np.float32, copy=False)).to(dev)
-    m = gesture_metrics(net, real, gen, dae=dae, batch_rows=a.batch_rows)
+    clips = {}
+    if a.clip_chunks is not None:
+        if a.real_clips or a.generated_clips or a.clip_chunks < 1:
+            ap.error("--clip_chunks is a positive count and replaces --real_clips / --generated_clips")
+        if real.shape[0] % a.clip_chunks or gen.shape[0] % a.clip_chunks:
+            ap.error(f"--clip_chunks {a.clip_chunks} does not divide {real.shape[0]} real and {gen.shape[0]} generated chunks")
+        clips = dict(real_clips=[a.clip_chunks] * (real.shape[0] // a.clip_chunks),
+                     generated_clips=[a.clip_chunks] * (gen.shape[0] // a.clip_chunks))
+    elif a.real_clips or a.generated_clips:
+        if not (a.real_clips and a.generated_clips):
+            ap.error("--real_clips and --generated_clips go together")
+        clips = dict(real_clips=np.load(a.real_clips), generated_clips=np.load(a.generated_clips))
+    m = gesture_metrics(net, real, gen, dae=dae, batch_rows=a.batch_rows, **clips)
     print(f"chunks: {m['n_real']} real, {m['n_generated']} generated")
     print(" Perplexity: " + repr(m["perplexity_generated"]))
     print("hell_dist --> " + repr(m["hellinger"]))
     print("Frechet Distance --> " + repr(m["frechet"]))
     print("wasserstein_distance -> " + repr(m["wasserstein"]))
+    if clips:
+        print(" BLEU: " + repr(m["bleu_sum"]) + " AVG_BLEU Score:" + repr(m["bleu"]) + " +-" + repr(m["bleu_var"]))
     return m
 
 

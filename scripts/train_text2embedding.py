@@ -4,7 +4,8 @@
     python train_text2embedding.py --config=../config/seq2seq_synthetic.yml --synthetic
 
 Same surface: `init_model(args, lang_model, pose_dim, _device)` (lang_model needs `.n_words` and
-`.word_embedding_weights`), `train_epochs`, `evaluate_testset` (cross-entropy + code-usage perplexity), `main`;
+`.word_embedding_weights`), `train_epochs`, `evaluate_testset` (cross-entropy + code-usage perplexity), `evaluate_bleu` (mean BLEU of the predicted code
+sentences against `cluster_ids`; logged per epoch with `val_bleu: True`), `main`;
 with `text2_embedding_discrete: "False"` (config/seq2seq_latent_synthetic.yml) the decoder regresses the sentence-level latents
 (width n_layers * hidden_size) with MSE instead (`evaluate_testset`: MSE over all slots, perplexity 0 from the empty meter);
 Adam(lr, betas=(0.5, 0.999)) (:179-181), evaluation every epoch (:195), checkpoint every 10 epochs with the keys
@@ -115,6 +116,27 @@ def evaluate_testset(test_data_loader, generator, loss_fn, args):
     return losses.avg, perplexities.avg
 
 
+def evaluate_bleu(test_data_loader, generator, args):
+    """-> mean BLEU over all sentences of the loader (discrete mode): per batch the argmax of the eval-mode logits, (B, S) code ids,
+    is scored against `cluster_ids` in one `code_bleu` call -- the `# 3. BLEU Score` the reference left empty (:412)."""
+    from gesture2vec_amd.metrics import code_bleu
+    if args.text2_embedding_discrete != "True":
+        raise ValueError("evaluate_bleu scores code ids: text2_embedding_discrete must be \"True\"")
+    generator.train(False)
+    total, count = torch.zeros((), dtype=torch.float64, device=device), 0
+    with torch.no_grad():
+        for data in test_data_loader:
+            in_text, text_lengths, target_vec, in_audio, aux_info, latents, cluster_ids, gpt3 = data
+            in_text, cluster_ids = in_text.to(device), cluster_ids.to(device).to(torch.int64)
+            out_latents, _ = generator(in_text, text_lengths, None, cluster_ids, None, None)
+            B, S, K = out_latents.shape
+            pred = ops.argmax_rows(out_latents.reshape(-1, K).contiguous()).view(B, S)
+            total += code_bleu(pred, cluster_ids.contiguous(), K=K).sum()
+            count += B
+    generator.train(True)
+    return float(total) / max(count, 1)
+
+
 def train_epochs(args, train_data_loader, test_data_loader, lang_model, pose_dim, trial_id=None):
     start = time.time()
     loss_meters = [AverageMeter("loss"), AverageMeter("var_loss")]
@@ -125,6 +147,8 @@ def train_epochs(args, train_data_loader, test_data_loader, lang_model, pose_dim
     val_metrics_list, loss_list = [], []
     for epoch in range(1, args.epochs + 1):
         val_metrics_list.append(evaluate_testset(test_data_loader, generator, loss_fn, args))
+        if getattr(args, "val_bleu", False):
+            logging.info("[VAL] BLEU: {:.4f}".format(evaluate_bleu(test_data_loader, generator, args)))
         if epoch % save_model_epoch_interval == 0 and epoch > 0:
             save_name = "{}/{}_checkpoint_{:03d}.bin".format(args.model_save_path, args.name, epoch)
             utils.train_utils.save_checkpoint(

@@ -5,8 +5,11 @@
 at E = 400 and E = 128, N in {4096, 65536, 2^20}: device-synchronised medians (events around each call).  One JSON line per shape
 with the times and the kernel's two roofline fractions: executed upper-triangle FLOP (2 N * 256 * tile pairs, ET (ET + 1) / 2 pairs
 of 16-column tiles) over 157.3 TF/s, and the bytes of x over 8 TB/s.  --e2e also times gesture_metrics on 2^20 + 2^20 chunks.
+--bleu times BLEU over code sequences (K = 512) at (B, L) = (65536, 8) and (256, 1024): the clipped-count kernel alone
+(g2v_ngram_clipped_counts), `code_bleu` end to end (scores on the device, one number read back), and the host route a user had without
+them: read the ids back, `Counter`s per pair (the restatement in tests/_bleu_ref.py), timed once.
 
-    python tools/bench_metrics.py --out profiles/metrics_moments.jsonl [--e2e] [--only-new]"""
+    python tools/bench_metrics.py --out profiles/metrics_moments.jsonl [--e2e] [--only-new] [--bleu] [--shapes ""]"""
 import argparse
 import json
 import os
@@ -112,22 +115,58 @@ def bench_e2e(n_chunks):
             "share_new_kernels": (t_mom + t_hist) * 1e-3 / total, "frechet": m["frechet"]}
 
 
+def bench_bleu(B, L, K=512, reps=50):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import _bleu_ref as R
+    from gesture2vec_amd.metrics import code_bleu
+    g = torch.Generator(device=DEV).manual_seed(B + L)
+    ref = torch.randint(0, K, (B, L), generator=g, device=DEV)
+    cand = torch.where(torch.rand(B, L, generator=g, device=DEV) < 0.1, torch.randint(0, K, (B, L), generator=g, device=DEV), ref)
+    start = torch.arange(B, dtype=torch.int64, device=DEV) * L
+    lens = torch.full((B,), L, dtype=torch.int64, device=DEV)
+    kernel = lambda: ops.ngram_clipped_counts(cand.view(-1), start, lens, ref.view(-1), start, lens, K, 4, L)
+    for _ in range(3):
+        kernel()
+        code_bleu(cand, ref, K=K)
+    torch.cuda.synchronize()
+    t_kernel = [timed(kernel) for _ in range(reps)]                        # (with the two small allocations of the binding)
+    t_e2e = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        scores = code_bleu(cand, ref, K=K)
+        torch.cuda.synchronize()
+        t_e2e.append((time.perf_counter() - t0) * 1e3)
+    t0 = time.perf_counter()
+    c_h, r_h = cand.cpu().numpy(), ref.cpu().numpy()
+    host = [R.bleu(c, r) for c, r in zip(c_h, r_h)]
+    t_host = (time.perf_counter() - t0) * 1e3
+    err = max(abs(a - b) for a, b in zip(scores.cpu().tolist(), host))
+    return {"bleu_B": B, "bleu_L": L, "K": K, "reps": reps, "kernel_ms_median": statistics.median(t_kernel), "kernel_ms_min": min(t_kernel),
+            "code_bleu_ms_median": statistics.median(t_e2e), "host_counter_route_ms": t_host,
+            "host_over_code_bleu": t_host / statistics.median(t_e2e), "mean_bleu": sum(host) / B, "max_abs_score_diff": err}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--e2e", action="store_true")
+    ap.add_argument("--bleu", action="store_true", help="BLEU over code sequences: kernel, code_bleu and the host Counter route")
     ap.add_argument("--only-new", action="store_true", help="the new kernel alone (for a rocprofv3 --kernel-trace --stats run)")
     ap.add_argument("--shapes", default="400x4096,400x65536,400x1048576,128x4096,128x65536,128x1048576")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X: there is nothing to time on a CPU"
     recs = []
-    for s in a.shapes.split(","):
+    for s in filter(None, a.shapes.split(",")):
         E, N = (int(v) for v in s.split("x"))
         recs.append(bench_shape(N, E, 30 if N >= 2 ** 20 else 100, a.only_new))
         print(json.dumps(recs[-1]), flush=True)
     if a.e2e:
         recs.append(bench_e2e(2 ** 20))
         print(json.dumps(recs[-1]), flush=True)
+    if a.bleu:
+        for B, L in ((65536, 8), (256, 1024)):
+            recs.append(bench_bleu(B, L))
+            print(json.dumps(recs[-1]), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
