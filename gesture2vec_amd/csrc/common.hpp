@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/g2v.h"
+#include "launch_ledger.hpp"
 
 // Device address of the persistent rollouts' fault latch (dec_persist.hip; NULL if it cannot be resolved).  The kernels that
 // COMMIT a training step's results to the model state -- clip + Adam, the EMA codebook update, the BatchNorm running statistics --
@@ -30,9 +31,16 @@ G2vOptions& g2v_internal_options();
 void g2v_internal_preclear_note(const void* p, size_t n);
 int g2v_internal_preclear_take(const void* p, size_t need);
 void g2v_internal_preclear_drop(const void* base, size_t bytes);
-// misc.hip -- the current device's CU count, asked once (0: no device).  The persistent and cluster kernels need every workgroup
-// of their launch resident at once, one per CU: every dispatch plan takes its `cus` from here.
+// misc.hip -- the current device's CU count, asked once per device (0: no device).  The persistent and cluster kernels need every
+// workgroup of their launch resident at once, one per CU: every dispatch plan takes its `cus` from here.
 int g2v_internal_device_cus();
+// misc.hip -- what stands between a plan and its launch, kept per device in one ledger (launch_ledger.hpp).
+// g2v_internal_lds_reserve: may `fn` be launched on the current device with `bytes` of dynamic LDS (the byte count that very
+// launch passes)?  Asks the runtime only above g2v::LDS_NO_RESERVE_LIMIT and above what the kernel already has.  false: refused;
+// the message is set, the runtime's error is cleared, and the entry point returns G2V_ERR_LAUNCH without launching anything more.
+// g2v_internal_kernel_resident: the same reservation, then: does at least one workgroup of `block` threads fit a CU (asked once)?
+bool g2v_internal_lds_reserve(const void* fn, size_t bytes);
+bool g2v_internal_kernel_resident(const void* fn, int block, size_t bytes);
 // gru.hip -- the exchange region a cluster launch of this shape clears (offset 0 of its workspace); 0: not a cluster shape
 size_t g2v_internal_gru_cluster_region(int T, int B, int H, int ndir, int bwd);
 // vq.hip -- does the plan (vq_route_plan) serve this call of g2v_vq_assign_bulk_z (vq_bulk_z.hip)?  G2V_OK, or the code with *msg set

@@ -418,8 +418,7 @@ extern "C" int g2v_dec_chain_fwd(const float* rows, int64_t R, const int64_t* id
   const bool fast = H == CHAIN_FAST_H && D == CHAIN_FAST_D;
   const void* fn = fast ? (const void*)dec_chain_kernel<4, true>
                         : wide ? (const void*)dec_chain_kernel<8, false> : (const void*)dec_chain_kernel<4, false>;
-  if (lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!g2v_internal_lds_reserve(fn, lds)) {
     set_error("g2v_dec_chain_fwd: %zu bytes of LDS refused", lds);
     return G2V_ERR_LAUNCH;
   }

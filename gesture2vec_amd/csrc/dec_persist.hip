@@ -1172,13 +1172,9 @@ const unsigned* g2v_internal_persist_fault_ptr() {
   return p;
 }
 
-// Residency check of a persistent kernel (once per kernel): at least one workgroup of its shape must fit a CU; together with
-// nblk <= CU count (dec_rollout.hip) this is what a plain launch can know.  It cannot see CU masks or other tenants of the
-// device: that is what the fault latch is for.
-static bool persist_fits(const void* fn, size_t lds) {
-  int n = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256, lds) == hipSuccess && n >= 1;
-}
+// Residency check of a persistent kernel (g2v_internal_kernel_resident: asked once per kernel and device): at least one workgroup
+// of its shape must fit a CU; together with nblk <= CU count (dec_rollout.hip) this is what a plain launch can know.  It cannot see
+// CU masks or other tenants of the device: that is what the fault latch is for.
 
 // Host side: called by g2v_dec_rollout_fwd (dec_rollout.hip) when the persistent path applies.  `packed` points at the
 // six fragment-major matrices in the order pre, ih0, hh0, ih1, hh1, out; `xbase` at PX_BYTES of exchange state.
@@ -1200,17 +1196,13 @@ int dec_persist_fwd_launch(const float* target, const float* h_init, const g2v_d
     const size_t lds = dec_persist_fwd_lds_bytes(R);
     const void* fn = R == 1 ? (const void*)dec_persist_fwd_mt_kernel<1>
                             : (R == 2 ? (const void*)dec_persist_fwd_mt_kernel<2> : (const void*)dec_persist_fwd_mt_kernel<3>);
-    static bool mt_set[3] = {false, false, false};
     if (R < 1 || R > 3 || s->loss_code) {
       set_error("dec_persist_fwd: %d tiles per workgroup / a chased rollout is not offered", R);
       return G2V_ERR_ARG;
     }
-    if (!mt_set[R - 1]) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess || !persist_fits(fn, lds)) {
-        set_error("dec_persist_fwd: the %d-tile kernel does not fit a CU (%zu bytes of LDS)", R, lds);
-        return G2V_ERR_LAUNCH;
-      }
-      mt_set[R - 1] = true;
+    if (!g2v_internal_kernel_resident(fn, 256, lds)) {
+      set_error("dec_persist_fwd: the %d-tile kernel does not fit a CU (%zu bytes of LDS)", R, lds);
+      return G2V_ERR_LAUNCH;
     }
     if (training && clear) (void)hipMemsetAsync(xbase, 0, PX_BYTES, st);
     if (R == 1) hipLaunchKernelGGL(dec_persist_fwd_mt_kernel<1>, dim3(nwg), dim3(256), lds, st, a, nwg);
@@ -1223,17 +1215,13 @@ int dec_persist_fwd_launch(const float* target, const float* h_init, const g2v_d
     return G2V_OK;
   }
   const size_t lds = dec_persist_fwd_lds_bytes(1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)dec_persist_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      set_error("dec_persist_fwd: cannot reserve %zu bytes of LDS", lds);
-      return G2V_ERR_LAUNCH;
-    }
-    if (!persist_fits((const void*)dec_persist_fwd_kernel, lds)) {
-      set_error("dec_persist_fwd: the kernel does not fit a CU (occupancy query)");
-      return G2V_ERR_LAUNCH;
-    }
-    attr_set = true;
+  if (!g2v_internal_lds_reserve((const void*)dec_persist_fwd_kernel, lds)) {
+    set_error("dec_persist_fwd: cannot reserve %zu bytes of LDS", lds);
+    return G2V_ERR_LAUNCH;
+  }
+  if (!g2v_internal_kernel_resident((const void*)dec_persist_fwd_kernel, 256, lds)) {
+    set_error("dec_persist_fwd: the kernel does not fit a CU (occupancy query)");
+    return G2V_ERR_LAUNCH;
   }
   // every polled word, every call (tags count steps 1..T); !clear: g2v_dec_rollout_prepare has done it for this call
   if (training && clear) (void)hipMemsetAsync(xbase, 0, PX_BYTES, st);
@@ -2061,17 +2049,13 @@ int dec_persist_bwd_launch(const g2v_dec_weights* w, const g2v_dec_saved* s, con
     const size_t lds = dec_persist_bwd_mt_lds_bytes();
     const void* fn = R == 1 ? (const void*)dec_persist_bwd_mt_kernel<1>
                             : (R == 2 ? (const void*)dec_persist_bwd_mt_kernel<2> : (const void*)dec_persist_bwd_mt_kernel<3>);
-    static bool mt_set[3] = {false, false, false};
     if (R < 1 || R > 3 || fw || s->loss_code) {
       set_error("dec_persist_bwd: %d tiles per workgroup with a fused weight gradient / loss fold is not offered", R);
       return G2V_ERR_ARG;
     }
-    if (!mt_set[R - 1]) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess || !persist_fits(fn, lds)) {
-        set_error("dec_persist_bwd: the %d-tile kernel does not fit a CU", R);
-        return G2V_ERR_LAUNCH;
-      }
-      mt_set[R - 1] = true;
+    if (!g2v_internal_kernel_resident(fn, 256, lds)) {
+      set_error("dec_persist_bwd: the %d-tile kernel does not fit a CU", R);
+      return G2V_ERR_LAUNCH;
     }
     if (clear) (void)hipMemsetAsync(xbase, 0, PX_BYTES, st);
     if (R == 1) hipLaunchKernelGGL(dec_persist_bwd_mt_kernel<1>, dim3(nwg), dim3(256), lds, st, a, nwg);
@@ -2084,18 +2068,14 @@ int dec_persist_bwd_launch(const g2v_dec_weights* w, const g2v_dec_saved* s, con
     return G2V_OK;
   }
   const size_t lds = dec_persist_bwd_lds_bytes(fw);
-  static bool attr_set[2] = {false, false};
-  if (!attr_set[fw]) {
-    const void* fn = fw ? (const void*)dec_persist_bwd_kernel<true> : (const void*)dec_persist_bwd_kernel<false>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      set_error("dec_persist_bwd: cannot reserve %zu bytes of LDS", lds);
-      return G2V_ERR_LAUNCH;
-    }
-    if (!persist_fits(fn, lds)) {
-      set_error("dec_persist_bwd: the kernel does not fit a CU (occupancy query)");
-      return G2V_ERR_LAUNCH;
-    }
-    attr_set[fw] = true;
+  const void* fn = fw ? (const void*)dec_persist_bwd_kernel<true> : (const void*)dec_persist_bwd_kernel<false>;
+  if (!g2v_internal_lds_reserve(fn, lds)) {
+    set_error("dec_persist_bwd: cannot reserve %zu bytes of LDS", lds);
+    return G2V_ERR_LAUNCH;
+  }
+  if (!g2v_internal_kernel_resident(fn, 256, lds)) {
+    set_error("dec_persist_bwd: the kernel does not fit a CU (occupancy query)");
+    return G2V_ERR_LAUNCH;
   }
   if (clear) (void)hipMemsetAsync(xbase, 0, PX_BYTES, st);
   if (fw) hipLaunchKernelGGL(dec_persist_bwd_kernel<true>, dim3(a.nblk), dim3(256), lds, st, a);

@@ -2618,13 +2618,14 @@ struct DecFwdCall {
   hipStream_t st; bool prepared;
 };
 // STEP / STEP_FAST: one fused kernel per time step (also step 0 of SPLIT)
-static void dec_fwd_launch_steps(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws, int t_end) {
+static int dec_fwd_launch_steps(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws, int t_end) {
   const bool fast = dec_prepared_shape(c.D, c.H);
   auto* const kernel = !fast ? dec_step_fwd_kernel<0, 0> : dec_step_fwd_kernel<64, 135>;      // (same arguments)
-  if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (!g2v_internal_lds_reserve((const void*)kernel, pl.lds)) return G2V_ERR_LAUNCH;
   const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, c.training, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch, pl.vec ? 1 : 0};
   for (int t = 0; t < t_end; ++t)
     hipLaunchKernelGGL(kernel, dim3(pl.nblk), dim3(pl.block), pl.lds, c.st, c.target, c.h_init, *c.w, ws.pk, *c.s, c.keep95, c.keep_l0, dm, t);
+  return G2V_OK;
 }
 // CLUSTER: ONE launch for all steps while the tile grid has a CU per workgroup (dec_cluster_fwd_kernel)
 static int dec_fwd_launch_cluster(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws) {
@@ -2639,11 +2640,11 @@ static int dec_fwd_launch_cluster(const DecFwdCall& c, const DecRoutePlan& pl, c
   return G2V_OK;
 }
 // SPLIT: step 0 as the generic kernel, then steps t >= 1 as three launches over (rows x 16-unit tiles) workgroups (see the kernels)
-static void dec_fwd_launch_split(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws) {
+static int dec_fwd_launch_split(const DecFwdCall& c, const DecRoutePlan& pl, const DecFwdWs& ws) {
   const g2v_dec_weights* w = c.w; const g2v_dec_saved* s = c.s;
   const int T = c.T, B = c.B, D = c.D, H = c.H, training = c.training, nblk = pl.nblk;
   const float p_drop = c.p_drop;
-  dec_fwd_launch_steps(c, pl, ws, 1);
+  if (dec_fwd_launch_steps(c, pl, ws, 1) != G2V_OK) return G2V_ERR_LAUNCH;
   for (int t = 1; t < T; ++t) {
     const int64_t BH = (int64_t)B * H, BD = (int64_t)B * D;
     const bool drop = training && c.keep_l0 && p_drop > 0.f;
@@ -2673,15 +2674,12 @@ static void dec_fwd_launch_split(const DecFwdCall& c, const DecRoutePlan& pl, co
     o.t = t; o.T = T; o.has_next = t < T - 1 ? 1 : 0; o.teacher = (t < T - 1 && t < c.n_pre) ? 1 : 0; o.conditioned = c.conditioned;
     hipLaunchKernelGGL(dec_out_pre_split_kernel, grid, dim3(64), 0, c.st, o, B, D, H);
   }
+  return G2V_OK;
 }
-// Does the cluster kernel fit a CU (its dynamic LDS on top of ~60 KB of static arrays)?  The attribute is set once per process.
+// Does the cluster kernel fit a CU (its dynamic LDS on top of ~60 KB of static arrays)?
 static bool dec_cluster_resident(bool bwd) {
-  static bool attr_set[2] = {false, false};
   const void* fn = bwd ? (const void*)dec_cluster_bwd_kernel<DCL_KS> : (const void*)dec_cluster_fwd_kernel<DCL_KS>;
-  const size_t dyn = bwd ? dec_cluster_bwd_dyn_lds() : dec_cluster_fwd_dyn_lds();
-  int nocc = 0;
-  if (!attr_set[bwd]) attr_set[bwd] = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) == hipSuccess;
-  return attr_set[bwd] && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, dyn) == hipSuccess && nocc >= 1;
+  return g2v_internal_kernel_resident(fn, 256, bwd ? dec_cluster_bwd_dyn_lds() : dec_cluster_fwd_dyn_lds());
 }
 // the plan of a real call: the bound context's level, this device's CUs, the call's facts
 static DecRoutePlan dec_plan_call(bool bwd, int T, int B, int D, int H, bool training, DecCallFacts f) {
@@ -2741,8 +2739,12 @@ static int dec_rollout_fwd_impl(const float* target, const float* h_init, const 
         return G2V_ERR_LAUNCH;
       }
       break;
-    case G2V_DEC_ROUTE_SPLIT: dec_fwd_launch_split(c, pl, ws); break;
-    default: dec_fwd_launch_steps(c, pl, ws, T); break;      // STEP, STEP_FAST
+    case G2V_DEC_ROUTE_SPLIT:
+      if (dec_fwd_launch_split(c, pl, ws) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
+    default:      // STEP, STEP_FAST
+      if (dec_fwd_launch_steps(c, pl, ws, T) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
   }
   G2V_CHECK_LAUNCH();
   if (training && w->bn_running_mean) {      // (NULL: the caller commits them later, g2v_bn_running_update)
@@ -2940,13 +2942,14 @@ static void dec_bwd_launch_split(const DecBwdCall& c, const DecRoutePlan& pl, co
   }
 }
 // STEP / STEP_FAST: one fused kernel per time step
-static void dec_bwd_launch_steps(const DecBwdCall& c, const DecRoutePlan& pl, const DecBwdWs& ws) {
+static int dec_bwd_launch_steps(const DecBwdCall& c, const DecRoutePlan& pl, const DecBwdWs& ws) {
   const bool fast = dec_prepared_shape(c.D, c.H);
   auto* const kernel = !fast ? dec_step_bwd_kernel<0, 0> : dec_step_bwd_kernel<64, 135>;
-  if (pl.lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (!g2v_internal_lds_reserve((const void*)kernel, pl.lds)) return G2V_ERR_LAUNCH;
   const DecDims dm{c.T, c.B, c.D, c.H, c.p_drop, c.n_pre, c.conditioned, 1, pl.nblk, fast ? dec_wt_stores() : 0, pl.scratch, pl.vec ? 1 : 0};
   for (int t = c.T - 1; t >= 0; --t)
     hipLaunchKernelGGL(kernel, dim3(pl.nblk), dim3(pl.block), pl.lds, c.st, *c.w, ws.tw, *c.s, *c.g, c.keep95, c.keep_l0, dm, t);
+  return G2V_OK;
 }
 static int dec_rollout_bwd_impl(const g2v_dec_weights* w, const g2v_dec_saved* s, const g2v_dec_grads* g,
                                 const uint8_t* keep95, const uint8_t* keep_l0, float p_drop, int n_pre_poses,
@@ -3001,7 +3004,9 @@ static int dec_rollout_bwd_impl(const g2v_dec_weights* w, const g2v_dec_saved* s
       }
       break;
     case G2V_DEC_ROUTE_SPLIT: dec_bwd_launch_split(c, pl, ws); break;
-    default: dec_bwd_launch_steps(c, pl, ws); break;      // STEP, STEP_FAST
+    default:      // STEP, STEP_FAST
+      if (dec_bwd_launch_steps(c, pl, ws) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
   }
   G2V_CHECK_LAUNCH();
   return G2V_OK;

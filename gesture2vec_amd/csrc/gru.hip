@@ -2312,9 +2312,7 @@ static GruRoutePlan gru_route_plan(bool bwd, int T, int B, int H, int ndir, int 
 }
 // Is the cluster kernel resident with (at least) one 192-thread workgroup per CU?
 static bool gru_cluster_resident(bool bwd) {
-  int n = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bwd ? (const void*)gru_cluster_bwd_kernel : (const void*)gru_cluster_fwd_kernel, 192, 0) ==
-             hipSuccess && n >= 1;
+  return g2v_internal_kernel_resident(bwd ? (const void*)gru_cluster_bwd_kernel : (const void*)gru_cluster_fwd_kernel, 192, 0);
 }
 // the plan of a real call (the bound context's options, this device's CUs, the call's facts) ...
 static GruRoutePlan gru_plan_call(bool bwd, int T, int B, int H, int ndir, GruCallFacts f) {
@@ -2505,7 +2503,7 @@ static void gru_fwd_launch_steps(const GruFwdCall& c, const GruRoutePlan& pl, co
 }
 // RESIDENT (192 < H <= 208: W_hh in the CU for the whole sequence) and STREAM (W_hh streamed as fragment packs: coalesced 1 KiB
 // fragment loads, eight k-steps kept in flight by wave_gemm_p), with two row tiles, one row tile, or the scalar body
-static void gru_fwd_launch_packed_weights(const GruFwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+static int gru_fwd_launch_packed_weights(const GruFwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
   GruGenF g[2];
   for (int k = 0; k < c.ndir; ++k) {
     const g2v_gru_dir& d = c.dirs[k];
@@ -2514,8 +2512,9 @@ static void gru_fwd_launch_packed_weights(const GruFwdCall& c, const GruRoutePla
   if (c.ndir == 1) g[1] = g[0];
   auto* const kernel = pl.route == G2V_GRU_ROUTE_RESIDENT ? gru_res_fwd_kernel
                        : pl.variant == 2 ? gru_seq_fwd_kernel<2> : pl.variant == 1 ? gru_seq_fwd_kernel<1> : gru_seq_fwd_kernel<0>;
-  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (!g2v_internal_lds_reserve((const void*)kernel, pl.lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, g[0], g[1], c.lengths, c.hs_ld, c.T, c.B, c.H, c.ro);
+  return G2V_OK;
 }
 
 static int gru_seq_fwd_impl(const g2v_gru_dir* dirs, int ndir, const int32_t* lengths, int64_t hs_ld, int T, int B,
@@ -2568,7 +2567,9 @@ static int gru_seq_fwd_impl(const g2v_gru_dir* dirs, int ndir, const int32_t* le
       }
       break;
     case G2V_GRU_ROUTE_STEP: gru_fwd_launch_steps(c, pl, ws); break;
-    default: gru_fwd_launch_packed_weights(c, pl, ws); break;      // RESIDENT, STREAM
+    default:      // RESIDENT, STREAM
+      if (gru_fwd_launch_packed_weights(c, pl, ws) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
   }
   G2V_CHECK_LAUNCH();
   return G2V_OK;
@@ -2655,18 +2656,19 @@ static void gru_bwd_launch_steps(const GruBwdCall& c, const GruRoutePlan& pl, co
   }
 }
 // RESIDENT: H = 200, W_hh (read in place) resident in the CU for the whole sequence, one workgroup per row tile
-static void gru_bwd_launch_resident(const GruBwdCall& c, const GruRoutePlan& pl) {
+static int gru_bwd_launch_resident(const GruBwdCall& c, const GruRoutePlan& pl) {
   GruResB r[2];
   for (int k = 0; k < c.ndir; ++k) {
     const g2v_gru_dir_bwd& d = c.dirs[k];
     r[k] = GruResB{d.d_hs, d.d_hn, d.hs, d.h0, d.gates, d.w_hh, d.dgi, d.dgh, d.dh0, d.reverse};
   }
   if (c.ndir == 1) r[1] = r[0];
-  (void)hipFuncSetAttribute((const void*)gru_res_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (!g2v_internal_lds_reserve((const void*)gru_res_bwd_kernel, pl.lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(gru_res_bwd_kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, r[0], r[1], c.lengths, c.d_hs_ld, c.hs_ld, c.T, c.B, c.ro);
+  return G2V_OK;
 }
 // STREAM: W_hh^T streamed as fragment packs, the vector or the scalar body
-static void gru_bwd_launch_stream(const GruBwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
+static int gru_bwd_launch_stream(const GruBwdCall& c, const GruRoutePlan& pl, const GruWs& ws) {
   GruGenB g[2];
   for (int k = 0; k < c.ndir; ++k) {
     const g2v_gru_dir_bwd& d = c.dirs[k];
@@ -2674,8 +2676,9 @@ static void gru_bwd_launch_stream(const GruBwdCall& c, const GruRoutePlan& pl, c
   }
   if (c.ndir == 1) g[1] = g[0];
   auto* const kernel = pl.variant ? gru_seq_bwd_kernel<1> : gru_seq_bwd_kernel<0>;
-  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (!g2v_internal_lds_reserve((const void*)kernel, pl.lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(kernel, gru_grid(pl), dim3(pl.block), pl.lds, c.st, g[0], g[1], c.lengths, c.d_hs_ld, c.hs_ld, c.T, c.B, c.H, c.ro);
+  return G2V_OK;
 }
 
 static int gru_seq_bwd_impl(const g2v_gru_dir_bwd* dirs, int ndir, const int32_t* lengths, int64_t d_hs_ld,
@@ -2743,8 +2746,12 @@ static int gru_seq_bwd_impl(const g2v_gru_dir_bwd* dirs, int ndir, const int32_t
       }
       break;
     case G2V_GRU_ROUTE_STEP: gru_bwd_launch_steps(c, pl, ws); break;
-    case G2V_GRU_ROUTE_RESIDENT: gru_bwd_launch_resident(c, pl); break;
-    default: gru_bwd_launch_stream(c, pl, ws); break;
+    case G2V_GRU_ROUTE_RESIDENT:
+      if (gru_bwd_launch_resident(c, pl) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
+    default:
+      if (gru_bwd_launch_stream(c, pl, ws) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
   }
   G2V_CHECK_LAUNCH();
   return G2V_OK;

@@ -459,7 +459,6 @@ struct DensePlan {
   bool one_launch;      // pair: the TILED kernel with grid.z = 2; dual: gemm_smallm_dual_nt_kernel; false: two single calls
   dim3 grid;
   size_t lds;           // dynamic LDS bytes
-  bool set_attr;        // lds is above the 48 KB a kernel gets without hipFuncSetAttribute
 };
 static int dense_smallm_rows(int given) { return given < 0 ? g2v_internal_options().smallm_max_rows : given; }
 // K, N: the forward weight is [N][K] in every form (the data gradient contracts over N and writes K columns); ldx / ldy: row strides
@@ -507,7 +506,6 @@ static DensePlan dense_plan(int form, int M, int K, int N, int N_b, int act, boo
     const int gx = M >= 65536 ? cdiv(M, 16 * 4 * 4) : cdiv(M, 16 * 4);
     pl.grid = dim3(gx > 256 ? 256 : gx);
     pl.lds = (size_t)ntw * ks * 256 * sizeof(float);
-    pl.set_attr = pl.lds > 48 * 1024;
     return pl;
   }
   if (!bwd && !has_keep && N == 64 && K == 135 && M >= 4096 && (M & 15) == 0 && act != 2 && y_vec && bias_ok) {
@@ -559,13 +557,11 @@ int g2v_internal_cell_bwd_products(const float* dgh, const float* w_hh, float* d
 namespace g2v {
 
 template <bool TRANS_B>
-static void launch_stream(const DensePlan& pl, const float* A, int64_t lda, const float* Bm, int64_t ldb, const float* bias,
+static int launch_stream(const DensePlan& pl, const float* A, int64_t lda, const float* Bm, int64_t ldb, const float* bias,
                           float* Cout, int64_t ldc, int M, int C, int N, int act, int accumulate, hipStream_t st) {
 #define G2V_STREAM(NTW, KS)                                                                                              \
   do {                                                                                                                   \
-    if (pl.set_attr)                                                                                                     \
-      (void)hipFuncSetAttribute((const void*)gemm_nt_stream_kernel<NTW, KS, TRANS_B>,                                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);                                \
+    if (!g2v_internal_lds_reserve((const void*)gemm_nt_stream_kernel<NTW, KS, TRANS_B>, pl.lds)) return G2V_ERR_LAUNCH;  \
     hipLaunchKernelGGL((gemm_nt_stream_kernel<NTW, KS, TRANS_B>), pl.grid, dim3(256), pl.lds, st, A, lda, Bm, ldb, bias,  \
                        Cout, ldc, M, C, N, act, accumulate);                                                             \
   } while (0)
@@ -574,6 +570,7 @@ static void launch_stream(const DensePlan& pl, const float* A, int64_t lda, cons
   else if (pl.ntw == 8) G2V_STREAM(8, 8);            // VQ pre_linear              (128 -> 128)
   else G2V_STREAM(4, 4);                             // 64 -> 64
 #undef G2V_STREAM
+  return G2V_OK;
 }
 
 // ---- wave-autonomous forward for UNALIGNED / row-mapped inputs (encoder in_layer: x (B,T,135) read as (T,B,135)) ----
@@ -1414,7 +1411,9 @@ extern "C" int g2v_linear_fwd(const float* x, int64_t ldx, int rows_inner, int64
   const hipStream_t st = (hipStream_t)stream;
   switch (pl.route) {
     case G2V_DENSE_ROUTE_SMALLM: launch_smallm(pl, false, x, ldx, x_keep, x_scale, w, (int64_t)K, bias, y, ldy, M, K, N, act, 0, st); break;
-    case G2V_DENSE_ROUTE_STREAM: launch_stream<false>(pl, x, ldx, w, (int64_t)K, bias, y, ldy, M, K, N, act, 0, st); break;
+    case G2V_DENSE_ROUTE_STREAM:
+      if (launch_stream<false>(pl, x, ldx, w, (int64_t)K, bias, y, ldy, M, K, N, act, 0, st) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
     case G2V_DENSE_ROUTE_K4: launch_k4(pl, x, am, w, bias, y, ldy, M, K, act, st); break;
     default:
       if (pl.variant == 4)
@@ -1554,7 +1553,9 @@ extern "C" int g2v_linear_bwd_data(const float* dy, int64_t lddy, const float* w
   // output feature = k (K of them), contraction over n (N): Bop[k][n] = w[n*K + k]
   switch (pl.route) {
     case G2V_DENSE_ROUTE_SMALLM: launch_smallm(pl, true, dy, lddy, nullptr, 1.0f, w, (int64_t)K, nullptr, dx, lddx, M, N, K, 0, accumulate, st); break;
-    case G2V_DENSE_ROUTE_STREAM: launch_stream<true>(pl, dy, lddy, w, (int64_t)K, nullptr, dx, lddx, M, N, K, 0, accumulate, st); break;
+    case G2V_DENSE_ROUTE_STREAM:
+      if (launch_stream<true>(pl, dy, lddy, w, (int64_t)K, nullptr, dx, lddx, M, N, K, 0, accumulate, st) != G2V_OK) return G2V_ERR_LAUNCH;
+      break;
     default:
       if (pl.variant == 4)
         hipLaunchKernelGGL((gemm_nt_kernel<true, true>), pl.grid, dim3(256), 0, st, dy, am, (const uint8_t*)nullptr, 1.0f, w, (int64_t)K,
@@ -2140,7 +2141,7 @@ extern "C" int g2v_linear_bwd_weight_chain2(const float* p0, const float* p1, co
   G2V_REQUIRE(p0 && p1 && c0 && c1 && w_in && b_in && dw0 && dw1, "null pointer");
   G2V_REQUIRE(G > 0 && H > 0 && D > 0 && (int64_t)G * H < (int64_t)1 << 31, "bad size");
   const size_t lds = chain2_lds_bytes(H, D);
-  const int staged = lds <= 48 * 1024 && D <= CHAIN2_MAXD ? 1 : 0;
+  const int staged = lds <= LDS_NO_RESERVE_LIMIT && D <= CHAIN2_MAXD ? 1 : 0;
   hipLaunchKernelGGL(wgrad_chain2_kernel, dim3(cdiv(G, CHAIN2_ROWS), 2), dim3(256), staged ? lds : 0, (hipStream_t)stream, p0, p1, c0,
                      c1, w_in, b_in, dw0, dw1, G, H, D, accumulate ? 1 : 0, staged);
   G2V_CHECK_LAUNCH();
@@ -2163,7 +2164,7 @@ extern "C" int g2v_linear_bwd_weight_fold_chain2(const float* w0, const float* w
   G2V_REQUIRE(w0 && w1 && p0 && p1 && c0 && c1 && w_in && b_in && dw_in && db_in && dw0 && dw1, "null pointer");
   G2V_REQUIRE(G > 0 && H > 0 && D > 0, "non-positive size");
   const size_t lc = chain2_lds_bytes(H, D), lf = sizeof(float) * 15 * 256;
-  if (lc > 48 * 1024 || D > CHAIN2_MAXD) {      // the chain's staging does not fit: the two launches
+  if (lc > LDS_NO_RESERVE_LIMIT || D > CHAIN2_MAXD) {      // the chain's staging does not fit: the two launches
     const int rc = g2v_linear_bwd_weight_fold2(w0, w1, p0, p1, c0, c1, dw_in, db_in, G, H, D, 0, stream);
     if (rc != G2V_OK) return rc;
     return g2v_linear_bwd_weight_chain2(p0, p1, c0, c1, w_in, b_in, dw0, dw1, G, H, D, 0, stream);
@@ -2178,16 +2179,15 @@ extern "C" int g2v_linear_bwd_weight_fold_chain2(const float* w0, const float* w
 // the one-launch kernels keep the rows BELOW 4096 (every threshold of this section and its measurement: DESIGN.md §3.6.1)
 static constexpr int g_smallm_wgrad_rows = 4095;
 template <int TN, int TK, int NW>
-static void smw_lds_launch(const SmallWgradBatch& sb, int64_t lddy, int64_t ldx, int M, int K, int N, int accumulate, int nprob,
+static int smw_lds_launch(const SmallWgradBatch& sb, int64_t lddy, int64_t ldx, int M, int K, int N, int accumulate, int nprob,
                            int xpp, hipStream_t st) {
   const int groups = cdiv(cdiv(N, 16), TN) * cdiv(cdiv(K, 16), TK);
   constexpr int STG = 32 * (TN * 16 + TK * 16 + 4), RED = TN * TK * 256 + TN * 16;
   constexpr size_t lds = sizeof(float) * (size_t)(NW * STG > (NW - 1) * RED ? NW * STG : (NW - 1) * RED);
-  static bool attr = false;
-  if (!attr) attr = hipFuncSetAttribute((const void*)gemm_tn_smallm_lds_kernel<TN, TK, NW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds) == hipSuccess;
+  if (!g2v_internal_lds_reserve((const void*)gemm_tn_smallm_lds_kernel<TN, TK, NW>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL((gemm_tn_smallm_lds_kernel<TN, TK, NW>), xpp ? dim3(8 * cdiv(groups, xpp), 1) : dim3(groups, nprob), dim3(64 * NW),
                      lds, st, sb, lddy, ldx, M, K, N, accumulate, xpp);
+  return G2V_OK;
 }
 
 // (dy_a + dy_b)^T x is served by the wave-autonomous kernel's two-addend instantiation: 64 x 135-shaped dW, whole 16-row
@@ -2257,36 +2257,37 @@ static WgradPlan wgrad_plan(int M, int K, int N, int nprob, int flags, bool keep
 }
 
 template <int TN_, int TK_, int SN, int SK, int VW, bool BF, int NR, bool MP>
-static void tn_wave_launch_as(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
+static int tn_wave_launch_as(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
                               hipStream_t st) {
   const size_t lds = ((size_t)NR * TN_ * TK_ * 256 + 2 * NR * TN_ * 16) * sizeof(float);
-  (void)hipFuncSetAttribute((const void*)gemm_tn_wave_kernel<TN_, TK_, SN, SK, MP, VW, BF, NR>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!g2v_internal_lds_reserve((const void*)gemm_tn_wave_kernel<TN_, TK_, SN, SK, MP, VW, BF, NR>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL((gemm_tn_wave_kernel<TN_, TK_, SN, SK, MP, VW, BF, NR>), dim3(pl.splits, nprob), dim3(128 * NR), lds, st, bt, lddy,
                      xm, pl.M, K, N, pl.rpw);
+  return G2V_OK;
 }
 template <int TN_, int TK_, int SN, int SK, int VW>
-static void tn_wave_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
+static int tn_wave_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
                            hipStream_t st) {
-  if (pl.bf3 && pl.mapped) tn_wave_launch_as<TN_, TK_, SN, SK, VW, true, 4, true>(pl, bt, lddy, xm, K, N, nprob, st);
-  else if (pl.bf3) tn_wave_launch_as<TN_, TK_, SN, SK, VW, true, 4, false>(pl, bt, lddy, xm, K, N, nprob, st);
-  else if (pl.mapped) tn_wave_launch_as<TN_, TK_, SN, SK, VW, false, 2, true>(pl, bt, lddy, xm, K, N, nprob, st);
-  else tn_wave_launch_as<TN_, TK_, SN, SK, VW, false, 2, false>(pl, bt, lddy, xm, K, N, nprob, st);
+  if (pl.bf3 && pl.mapped) return tn_wave_launch_as<TN_, TK_, SN, SK, VW, true, 4, true>(pl, bt, lddy, xm, K, N, nprob, st);
+  if (pl.bf3) return tn_wave_launch_as<TN_, TK_, SN, SK, VW, true, 4, false>(pl, bt, lddy, xm, K, N, nprob, st);
+  if (pl.mapped) return tn_wave_launch_as<TN_, TK_, SN, SK, VW, false, 2, true>(pl, bt, lddy, xm, K, N, nprob, st);
+  return tn_wave_launch_as<TN_, TK_, SN, SK, VW, false, 2, false>(pl, bt, lddy, xm, K, N, nprob, st);
 }
 template <bool MP>
-static void tn_dual_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, hipStream_t st) {
+static int tn_dual_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, hipStream_t st) {
   const size_t lds = ((size_t)2 * 2 * 9 * 256 + 2 * 2 * 2 * 16) * sizeof(float);
-  (void)hipFuncSetAttribute((const void*)gemm_tn_wave_dual_kernel<MP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!g2v_internal_lds_reserve((const void*)gemm_tn_wave_dual_kernel<MP>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(gemm_tn_wave_dual_kernel<MP>, dim3(pl.splits, 1), dim3(256), lds, st, bt, lddy, xm, pl.M, K, N, pl.rpw);
+  return G2V_OK;
 }
 template <int TN_, int TK_, bool MP>
-static void tn_gen_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
+static int tn_gen_launch(const WgradPlan& pl, const TnBatch& bt, int64_t lddy, const RowMap& xm, int K, int N, int nprob,
                           hipStream_t st) {
   const size_t lds = ((size_t)2 * TN_ * TK_ * 256 + 4 * TN_ * 16) * sizeof(float);
-  (void)hipFuncSetAttribute((const void*)gemm_tn_wave_gen_kernel<TN_, TK_, 2, 1, MP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
+  if (!g2v_internal_lds_reserve((const void*)gemm_tn_wave_gen_kernel<TN_, TK_, 2, 1, MP>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL((gemm_tn_wave_gen_kernel<TN_, TK_, 2, 1, MP>), dim3(pl.splits, nprob, pl.gen_nob), dim3(256), lds, st, bt, lddy, xm,
                      pl.M, K, N, pl.rpw);
+  return G2V_OK;
 }
 // the operands of the small kernels: the items from row `row0` on (a row-mapped x keeps its base: the kernel adds the rows)
 static SmallWgradBatch smw_batch(const g2v_wgrad_item* it, int nprob, int64_t dy_off, int64_t x_off) {
@@ -2323,7 +2324,7 @@ static int wgrad_impl(const g2v_wgrad_item* it, int nprob, int64_t lddy, int64_t
     auto grid = [&](int groups) { return pl.xpp ? dim3(8 * cdiv(groups, pl.xpp), 1) : dim3(groups, nprob); };
     switch (pl.route) {
       case G2V_WGRAD_ROUTE_SMALL_LDS:
-        smw_lds_launch<2, 1, 4>(sb, lddy, ldx, M, K, N, accumulate, nprob, pl.xpp, st);
+        if (smw_lds_launch<2, 1, 4>(sb, lddy, ldx, M, K, N, accumulate, nprob, pl.xpp, st) != G2V_OK) return G2V_ERR_LAUNCH;
         break;
       case G2V_WGRAD_ROUTE_SMALL_RT:
         hipLaunchKernelGGL((gemm_tn_smallm_rt_kernel<2, 2, 4>), grid(cdiv(tn, 2) * cdiv(tk, 2)), dim3(256), 0, st, sb, lddy, ldx, M, K, N,
@@ -2363,25 +2364,27 @@ static int wgrad_impl(const g2v_wgrad_item* it, int nprob, int64_t lddy, int64_t
       bt.dy[p] = it[pp].dy; bt.x[p] = it[pp].x; bt.slab[p] = slab_of(pp); bt.slab_db[p] = slab_db_of(pp);
       bt.dy2[p] = dy2;
     }
+    int rc = G2V_OK;      // (a refused LDS reservation: nothing was launched)
     if (pl.route == G2V_WGRAD_ROUTE_WAVE_GEN) {
-      if (pl.gen_cfg == 0 && pl.mapped) tn_gen_launch<6, 4, true>(pl, bt, lddy, xm, K, N, nprob, st);
-      else if (pl.gen_cfg == 0) tn_gen_launch<6, 4, false>(pl, bt, lddy, xm, K, N, nprob, st);
-      else if (pl.mapped) tn_gen_launch<4, 7, true>(pl, bt, lddy, xm, K, N, nprob, st);
-      else tn_gen_launch<4, 7, false>(pl, bt, lddy, xm, K, N, nprob, st);
+      if (pl.gen_cfg == 0 && pl.mapped) rc = tn_gen_launch<6, 4, true>(pl, bt, lddy, xm, K, N, nprob, st);
+      else if (pl.gen_cfg == 0) rc = tn_gen_launch<6, 4, false>(pl, bt, lddy, xm, K, N, nprob, st);
+      else if (pl.mapped) rc = tn_gen_launch<4, 7, true>(pl, bt, lddy, xm, K, N, nprob, st);
+      else rc = tn_gen_launch<4, 7, false>(pl, bt, lddy, xm, K, N, nprob, st);
     } else if (pl.route == G2V_WGRAD_ROUTE_WAVE_DUAL) {
-      if (pl.mapped) tn_dual_launch<true>(pl, bt, lddy, xm, K, N, st);
-      else tn_dual_launch<false>(pl, bt, lddy, xm, K, N, st);
+      if (pl.mapped) rc = tn_dual_launch<true>(pl, bt, lddy, xm, K, N, st);
+      else rc = tn_dual_launch<false>(pl, bt, lddy, xm, K, N, st);
     } else if (tn == 12 && tk == 4) {
-      if (pl.vec2) tn_wave_launch<6, 4, 2, 1, 2>(pl, bt, lddy, xm, K, N, nprob, st);
-      else tn_wave_launch<6, 4, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
+      if (pl.vec2) rc = tn_wave_launch<6, 4, 2, 1, 2>(pl, bt, lddy, xm, K, N, nprob, st);
+      else rc = tn_wave_launch<6, 4, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
     } else if (tn == 4 && tk == 9) {
-      tn_wave_launch<2, 9, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
+      rc = tn_wave_launch<2, 9, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
     } else if (tn == 9 && tk == 4) {
-      tn_wave_launch<9, 2, 1, 2, 1>(pl, bt, lddy, xm, K, N, nprob, st);
+      rc = tn_wave_launch<9, 2, 1, 2, 1>(pl, bt, lddy, xm, K, N, nprob, st);
     } else {
-      if (pl.vec2) tn_wave_launch<2, 4, 2, 1, 2>(pl, bt, lddy, xm, K, N, nprob, st);
-      else tn_wave_launch<2, 4, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
+      if (pl.vec2) rc = tn_wave_launch<2, 4, 2, 1, 2>(pl, bt, lddy, xm, K, N, nprob, st);
+      else rc = tn_wave_launch<2, 4, 2, 1, 1>(pl, bt, lddy, xm, K, N, nprob, st);
     }
+    if (rc != G2V_OK) return rc;
   }
   G2V_CHECK_LAUNCH();
   if (pend && !pl.tail_rows) {       // the caller reduces later (g2v_linear_bwd_weight_reduce); the slabs stay in `workspace`

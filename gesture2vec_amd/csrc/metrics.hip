@@ -385,14 +385,9 @@ extern "C" int g2v_moments_accumulate(const float* x, int64_t ld, const float* s
     const float* xp = x + off * ld;
 #define G2V_MO_LAUNCH(TPW_, VEC_)                                                                                                 \
   do {                                                                                                                            \
-    static bool attr = false;                                                                                                     \
-    if (!attr) {                                                                                                                  \
-      if (hipFuncSetAttribute((const void*)moments_slab_kernel<TPW_, VEC_>, hipFuncAttributeMaxDynamicSharedMemorySize,           \
-                              (int)(((size_t)2 * 8 * MO_MAX_E * 4 + MO_MAX_E) * sizeof(float))) != hipSuccess) {                  \
-        set_error("g2v_moments_accumulate: cannot reserve LDS");                                                                  \
-        return G2V_ERR_LAUNCH;                                                                                                    \
-      }                                                                                                                           \
-      attr = true;                                                                                                                \
+    if (!g2v_internal_lds_reserve((const void*)moments_slab_kernel<TPW_, VEC_>, lds)) {                                           \
+      set_error("g2v_moments_accumulate: cannot reserve LDS");                                                                    \
+      return G2V_ERR_LAUNCH;                                                                                                      \
     }                                                                                                                             \
     hipLaunchKernelGGL((moments_slab_kernel<TPW_, VEC_>), dim3(slabs, g.groups), dim3(256), lds, st, xp, ld, shift, part, n, R,   \
                        E, g.ET, g.P, g.per_group);                                                                                \

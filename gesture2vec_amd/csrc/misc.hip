@@ -38,13 +38,40 @@ static g2v_ctx& ctx_or_cur(const g2v_ctx* ctx = nullptr) {      // `ctx`, else t
   return *(ctx ? const_cast<g2v_ctx*>(ctx) : (t_bound_ctx ? t_bound_ctx : &g_default_ctx));
 }
 G2vOptions& g2v_internal_options() { return ctx_or_cur().opt; }
+// ---- launch preconditions (launch_ledger.hpp): the one ledger, and the runtime calls it is allowed to make ---------------------------
+// Per device and mutex-guarded: facts about code objects, not switches, so it is shared by every context.  The library's only calls of
+// hipFuncSetAttribute and of the occupancy query are the ones below.
+static g2v::LaunchLedger g_ledger;
+static bool lds_raise(const void* fn, size_t bytes) {
+  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+static void lds_refused(size_t bytes) {
+  (void)hipGetLastError();      // (a refusal must not surface as the next launch check's error)
+  g2v::set_error("reserving %zu bytes of dynamic LDS for a kernel was refused", bytes);
+}
 int g2v_internal_device_cus() {
-  static int n = -1;
-  if (n < 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-  }
-  return n;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  return g_ledger.cus(dev, [](int d) {
+    int n = 0;
+    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess ? n : 0;
+  });
+}
+bool g2v_internal_lds_reserve(const void* fn, size_t bytes) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (g_ledger.reserve(dev, fn, bytes, lds_raise)) return true;
+  lds_refused(bytes);
+  return false;
+}
+bool g2v_internal_kernel_resident(const void* fn, int block, size_t bytes) {
+  if (!g2v_internal_lds_reserve(fn, bytes)) return false;      // (refused: the message is set; granted: the ledger's own reserve is a look-up)
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  return g_ledger.resident(dev, fn, block, bytes, lds_raise, [](const void* f, int blk, size_t n) {
+    int nocc = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, f, blk, n) == hipSuccess && nocc >= 1;
+  });
 }
 void g2v_internal_preclear_note(const void* p, size_t n) {
   g2v_ctx& c = ctx_or_cur();

@@ -246,17 +246,12 @@ extern "C" int g2v_ngram_clipped_counts(const int64_t* cand, const int64_t* cand
     hipLaunchKernelGGL(ngram_wave_kernel, dim3((unsigned)((B + NG_WAVE_PAIRS - 1) / NG_WAVE_PAIRS)), dim3(64 * NG_WAVE_PAIRS), 0, st, cand,
                        cand_start, cand_len, ref, ref_start, ref_len, clipped, bad, B, K, max_n, max_len);
   } else {
-    static bool attr = false;
-    if (!attr) {
-      if (hipFuncSetAttribute((const void*)ngram_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)ng_sort_lds(NG_MAX_LEN)) != hipSuccess) {
-        set_error("g2v_ngram_clipped_counts: cannot reserve LDS");
-        return G2V_ERR_LAUNCH;
-      }
-      attr = true;
-    }
     int P = 128;
     while (P < max_len) P <<= 1;
+    if (!g2v_internal_lds_reserve((const void*)ngram_sort_kernel, ng_sort_lds(P))) {
+      set_error("g2v_ngram_clipped_counts: cannot reserve LDS");
+      return G2V_ERR_LAUNCH;
+    }
     hipLaunchKernelGGL(ngram_sort_kernel, dim3((unsigned)B), dim3(256), ng_sort_lds(P), st, cand, cand_start, cand_len, ref, ref_start,
                        ref_len, clipped, bad, K, max_n, max_len, P);
   }

@@ -1051,7 +1051,7 @@ extern "C" int g2v_attn_fwd(const float* hp, const float* ep, const float* enc, 
   G2V_REQUIRE(hp && ep && enc && v && weights && ctx, "null pointer");
   G2V_REQUIRE(T > 0 && B > 0 && H > 0 && ldctx >= H, "bad size");
   const size_t lds = (size_t)T * sizeof(float);
-  G2V_REQUIRE(lds <= 48 * 1024, "sequence too long for the attention kernel");
+  G2V_REQUIRE(lds <= LDS_NO_RESERVE_LIMIT, "sequence too long for the attention kernel");
   hipLaunchKernelGGL(attn_fwd_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, hp, ep, enc, v, weights, ctx,
                      ldctx, T, B, H);
   G2V_CHECK_LAUNCH();
@@ -1064,7 +1064,7 @@ extern "C" int g2v_attn_step_fwd(const float* logits, int64_t ldl, int K, int64_
   G2V_REQUIRE(ids && table && ec && hp && ep && enc && v && weights, "null pointer");
   G2V_REQUIRE(T > 0 && B > 0 && H > 0 && K > 0 && ldec >= 2 * (int64_t)H && (!logits || ldl >= K), "bad size");
   const size_t lds = (size_t)T * sizeof(float);
-  G2V_REQUIRE(lds <= 48 * 1024, "sequence too long for the attention kernel");
+  G2V_REQUIRE(lds <= LDS_NO_RESERVE_LIMIT, "sequence too long for the attention kernel");
   hipLaunchKernelGGL(attn_step_fwd_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, logits, ldl, K, ids, table, keep, emb_scale,
                      ec, ldec, hp, ep, enc, v, weights, T, B, H);
   G2V_CHECK_LAUNCH();
@@ -1091,7 +1091,7 @@ extern "C" int g2v_attn_bwd(const float* d_ctx, int64_t ldd, const float* hp, co
     return G2V_ERR_WORKSPACE;
   }
   const size_t lds = (size_t)T * sizeof(float);
-  G2V_REQUIRE(lds <= 48 * 1024, "sequence too long for the attention kernel");
+  G2V_REQUIRE(lds <= LDS_NO_RESERVE_LIMIT, "sequence too long for the attention kernel");
   const int nblk = B;
   hipLaunchKernelGGL(attn_bwd_kernel, dim3(nblk), dim3(256), lds, (hipStream_t)stream, d_ctx, ldd, hp, ep, enc, v, weights,
                      d_hp, d_ep, d_enc, (float*)workspace, accumulate, T, B, H);

@@ -389,14 +389,9 @@ extern "C" int g2v_silhouette_samples(const float* x, int64_t ld, const int64_t*
     set_error("g2v_silhouette_samples: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)sil_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sil_lds_bytes(SIL_MAX_E)) != hipSuccess) {
-      set_error("g2v_silhouette_samples: cannot reserve LDS");
-      return G2V_ERR_LAUNCH;
-    }
-    attr = true;
+  if (!g2v_internal_lds_reserve((const void*)sil_tile_kernel, sil_lds_bytes(E))) {
+    set_error("g2v_silhouette_samples: cannot reserve LDS");
+    return G2V_ERR_LAUNCH;
   }
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;

@@ -363,8 +363,7 @@ extern "C" int g2v_latent_rollout_fwd(const float* target, const float* h_init, 
   const int scratch = ct_scratch((size_t)ct_fwd_lds(H, E, 0, 0).total);
   CodeDims dm{S1, B, H, E, E, 0, drop ? p_drop : 0.f, n_pre, 1, cdiv(B, 16), 0, scratch};
   const size_t lds = (size_t)ct_fwd_lds(H, E, 0, scratch).total * sizeof(float);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)latent_step_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!g2v_internal_lds_reserve((const void*)latent_step_fwd_kernel, lds)) return G2V_ERR_LAUNCH;
   for (int j = 0; j <= S1; ++j)
     hipLaunchKernelGGL(latent_step_fwd_kernel, dim3(dm.nblk), dim3(CT_NTHR), lds, st, target, h_init, *w, pk, *s,
                        drop ? keep_l0 : nullptr, dm, j);
@@ -448,8 +447,7 @@ extern "C" int g2v_latent_rollout_bwd(const float* d_out, const g2v_code_dec_wei
   const int scratch = (2 * Hp + 2048 <= 16 * (((3 * H + 15) & ~15) + 4)) ? 2048 : 1024;      // (Part A's reduction scratch lives in Gh)
   CodeDims dm{S1, B, H, E, E, 0, drop ? p_drop : 0.f, n_pre, 1, cdiv(B, 16), 0, scratch};
   const size_t lds = (size_t)ct_bwd_lds(H, E).total * sizeof(float);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)latent_step_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!g2v_internal_lds_reserve((const void*)latent_step_bwd_kernel, lds)) return G2V_ERR_LAUNCH;
   for (int t = S1 - 1; t >= -1; --t)
     hipLaunchKernelGGL(latent_step_bwd_kernel, dim3(dm.nblk), dim3(CT_NTHR), lds, st, a, dm, t, pre_t, dy);
   hipLaunchKernelGGL(code_small_sums_kernel, dim3(1), dim3(256), 0, st, a.bn_sums, S1, H, g->d_bn_w, g->d_bn_b, (const float*)nullptr,

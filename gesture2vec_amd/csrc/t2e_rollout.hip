@@ -1479,11 +1479,7 @@ extern "C" size_t g2v_code_cluster_bptt_workspace(int B, int H) { return code_pl
 
 // The entries' plan: residency of the cluster forward is asked only once a plan says cluster.
 static bool code_cluster_fwd_resident() {
-  static bool attr_set = false;
-  const void* fn = (const void*)code_cluster_fwd_kernel;
-  int nocc = 0;
-  if (!attr_set) attr_set = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)code_cluster_dyn_lds()) == hipSuccess;
-  return attr_set && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, fn, 256, code_cluster_dyn_lds()) == hipSuccess && nocc >= 1;
+  return g2v_internal_kernel_resident((const void*)code_cluster_fwd_kernel, 256, code_cluster_dyn_lds());
 }
 static CodeRoutePlan code_plan_call(CodeCall call, int S1, int B, int H, int K, int Tw, bool att, CodeCallFacts f) {
   const int level = g2v_internal_options().persist, cus = g2v_internal_device_cus();
@@ -1520,8 +1516,7 @@ extern "C" int g2v_code_cluster_bptt(const float* dh_top, const g2v_code_dec_wei
   const void* al[] = {dh_top, keep_l0, dgi0, dgh0, dgi1, dgh1, da, d_hidden0, s->gates0, s->gates1, s->h0, s->h1, workspace};
   for (const void* p : al) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
   hipStream_t st = (hipStream_t)stream;
-  int nocc = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nocc, (const void*)code_cluster_bptt_kernel, 256, 0) != hipSuccess || nocc < 1) {
+  if (!g2v_internal_kernel_resident((const void*)code_cluster_bptt_kernel, 256, 0)) {
     set_error("g2v_code_cluster_bptt: the kernel does not fit a CU");
     return G2V_ERR_LAUNCH;
   }
@@ -1587,8 +1582,7 @@ static int code_fwd_launch_steps(const CodeFwdCall& c, const CodeRoutePlan& pl) 
   launch_pack(pb, c.st);
   G2V_CHECK_LAUNCH();
   CodeDims dm{c.S1, c.B, H, K, Hin, c.att ? c.Tw : 0, c.p_drop, c.n_pre, c.training, pl.nblk, c.att, pl.scratch};
-  if (pl.lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)code_step_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (!g2v_internal_lds_reserve((const void*)code_step_fwd_kernel, pl.lds)) return G2V_ERR_LAUNCH;
   for (int j = 0; j <= c.S1; ++j)
     hipLaunchKernelGGL(code_step_fwd_kernel, dim3(pl.nblk), dim3(CT_NTHR), pl.lds, c.st, c.codes, c.h_init, c.enc, c.enc_proj, *w, pk, *c.s,
                        c.keep_emb, c.keep_l0, dm, j);
@@ -1687,7 +1681,7 @@ extern "C" int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc
   float* dwh = wae + (size_t)H * H;
   float* dwe = dwh + (size_t)H * H;
   if (pl.variant == 0) {      // no attention: the whole BPTT in one launch
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)code_bptt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (!g2v_internal_lds_reserve((const void*)code_bptt_kernel, lds)) return G2V_ERR_LAUNCH;
     hipLaunchKernelGGL(code_bptt_kernel, dim3(dm.nblk), dim3(CT_NTHR), lds, st, a, dm);
     hipLaunchKernelGGL(code_bn_bwd_apply_kernel, dim3(dm.nblk, S1), dim3(256), (2 * H + 1024) * sizeof(float), st, a, dm);
     G2V_CHECK_LAUNCH();
@@ -1695,8 +1689,7 @@ extern "C" int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc
     if ((rc = g2v_linear_bwd_data(a.du, H, w->w_pre, a.dec, H, M, H, H, 0, stream)) != G2V_OK) return rc;
   } else {                    // attention: one launch per step
     hipLaunchKernelGGL(code_split_cols_kernel, dim3(cdiv(H * H, 256)), dim3(256), 0, st, w->w_pre, w->w_attn, wpe, wae, H);
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)code_step_bwd_att_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (!g2v_internal_lds_reserve((const void*)code_step_bwd_att_kernel, lds)) return G2V_ERR_LAUNCH;
     for (int t = S1 - 1; t >= -1; --t)
       hipLaunchKernelGGL(code_step_bwd_att_kernel, dim3(dm.nblk), dim3(CT_NTHR), lds, st, a, dm, t);
     G2V_CHECK_LAUNCH();

@@ -340,14 +340,9 @@ extern "C" int g2v_tsne_affinities(const float* x, int64_t ld, int64_t N, int d,
     set_error("g2v_tsne_affinities: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)tsne_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(TSNE_MAX_N * sizeof(float))) != hipSuccess) {
-      set_error("g2v_tsne_affinities: cannot reserve LDS");
-      return G2V_ERR_LAUNCH;
-    }
-    attr = true;
+  if (!g2v_internal_lds_reserve((const void*)tsne_search_kernel, (size_t)N * sizeof(float))) {
+    set_error("g2v_tsne_affinities: cannot reserve LDS");
+    return G2V_ERR_LAUNCH;
   }
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;

@@ -446,14 +446,9 @@ extern "C" int g2v_tsne_place_neighbors(const float* X, int64_t ldx, int64_t N, 
     set_error("g2v_tsne_place_neighbors: workspace too small");
     return G2V_ERR_WORKSPACE;
   }
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)place_knn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            PD_TILE * PL_MAX_KK * 8) != hipSuccess) {
-      set_error("g2v_tsne_place_neighbors: cannot reserve LDS");
-      return G2V_ERR_LAUNCH;
-    }
-    attr = true;
+  if (!g2v_internal_lds_reserve((const void*)place_knn_kernel, (size_t)PD_TILE * kk * 8)) {
+    set_error("g2v_tsne_place_neighbors: cannot reserve LDS");
+    return G2V_ERR_LAUNCH;
   }
   hipStream_t st = (hipStream_t)stream;
   double* nx = (double*)workspace;

@@ -335,16 +335,16 @@ constexpr int VAE_WIDE_MAX_BLOCKS = 128;
 constexpr int VAE_NW_WIDE = 16;
 
 template <int NW>
-void launch_fwd(const VaeFwdArgs& a, int nblk, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vae_latent_fwd_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+int launch_fwd(const VaeFwdArgs& a, int nblk, size_t lds, hipStream_t st) {
+  if (!g2v_internal_lds_reserve((const void*)vae_latent_fwd_kernel<NW>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(vae_latent_fwd_kernel<NW>, dim3(nblk), dim3(64 * NW), lds, st, a);
+  return G2V_OK;
 }
 template <int NW>
-void launch_bwd(const VaeBwdArgs& a, int nblk, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vae_latent_bwd_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+int launch_bwd(const VaeBwdArgs& a, int nblk, size_t lds, hipStream_t st) {
+  if (!g2v_internal_lds_reserve((const void*)vae_latent_bwd_kernel<NW>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(vae_latent_bwd_kernel<NW>, dim3(nblk), dim3(64 * NW), lds, st, a);
+  return G2V_OK;
 }
 
 }  // namespace
@@ -387,10 +387,9 @@ extern "C" int g2v_vae_latent_fwd(const float* h, const float* w_mean, const flo
   a.B = B; a.E = E; a.H = H; a.sample = sample ? 1 : 0;
   const int nblk = g2v_vae_latent_blocks(B);
   const size_t lds = (size_t)(2 * VAE_ROWS * (E + 4) + VAE_NW_WIDE) * sizeof(float);
-  if (nblk <= VAE_WIDE_MAX_BLOCKS)
-    launch_fwd<VAE_NW_WIDE>(a, nblk, lds, (hipStream_t)stream);
-  else
-    launch_fwd<4>(a, nblk, lds, (hipStream_t)stream);
+  if ((nblk <= VAE_WIDE_MAX_BLOCKS ? launch_fwd<VAE_NW_WIDE>(a, nblk, lds, (hipStream_t)stream)
+                                   : launch_fwd<4>(a, nblk, lds, (hipStream_t)stream)) != G2V_OK)
+    return G2V_ERR_LAUNCH;
   G2V_CHECK_LAUNCH();
   hipLaunchKernelGGL(vae_kl_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a.kl_partial, nblk,
                      0.5f / ((float)B * (float)E), kl);
@@ -421,10 +420,9 @@ extern "C" int g2v_vae_latent_bwd(const float* g_d, const float* g_kl, const flo
   a.B = B; a.E = E; a.H = H;
   const size_t lds = (size_t)(3 * VAE_ROWS * (E + 4)) * sizeof(float);
   const int nblk = cdiv(B, VAE_ROWS);
-  if (nblk <= VAE_WIDE_MAX_BLOCKS)
-    launch_bwd<VAE_NW_WIDE>(a, nblk, lds, (hipStream_t)stream);
-  else
-    launch_bwd<4>(a, nblk, lds, (hipStream_t)stream);
+  if ((nblk <= VAE_WIDE_MAX_BLOCKS ? launch_bwd<VAE_NW_WIDE>(a, nblk, lds, (hipStream_t)stream)
+                                   : launch_bwd<4>(a, nblk, lds, (hipStream_t)stream)) != G2V_OK)
+    return G2V_ERR_LAUNCH;
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }

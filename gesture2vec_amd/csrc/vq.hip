@@ -2296,8 +2296,7 @@ static void vq_launch_tuned(const VqRoutePlan& pl, const VqRowsArgs& a) {      /
                        a.quantized, a.dist_min, a.sse_partial, a.N, a.K);
 }
 static int vq_launch_split(const VqRoutePlan& pl, const VqRowsArgs& a) {
-  if (pl.lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vq_assign_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (!g2v_internal_lds_reserve((const void*)vq_assign_split_kernel, pl.lds)) return G2V_ERR_LAUNCH;
   if (hipMemsetAsync(a.idx, 0xFF, sizeof(int64_t) * (size_t)a.N, a.st) != hipSuccess) {
     set_error("g2v_vq_assign_fwd: memset failed");
     return G2V_ERR_LAUNCH;
@@ -2309,31 +2308,31 @@ static int vq_launch_split(const VqRoutePlan& pl, const VqRowsArgs& a) {
                      a.codebook, a.quantized, a.dist_min, a.sse_partial, a.N, a.E);
   return G2V_OK;
 }
-static void vq_launch_generic(const VqRoutePlan& pl, const VqRowsArgs& a) {
-  if (pl.lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vq_assign_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+static int vq_launch_generic(const VqRoutePlan& pl, const VqRowsArgs& a) {
+  if (!g2v_internal_lds_reserve((const void*)vq_assign_kernel, pl.lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(vq_assign_kernel, dim3(pl.grid[0]), dim3(pl.block), pl.lds, a.st, a.flat, a.z, a.codebook, a.code_sqnorm, a.idx,
                      a.quantized, a.dist_min, a.sse_partial, a.N, a.E, a.K);
+  return G2V_OK;
 }
 template <int NR, int NT>
-static void vq_launch_packed_as(const VqRoutePlan& pl, const VqRowsArgs& a) {
-  if (pl.lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vq_assign_p_kernel<NR, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+static int vq_launch_packed_as(const VqRoutePlan& pl, const VqRowsArgs& a) {
+  if (!g2v_internal_lds_reserve((const void*)vq_assign_p_kernel<NR, NT>, pl.lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL((vq_assign_p_kernel<NR, NT>), dim3(pl.grid[0]), dim3(pl.block), pl.lds, a.st, a.flat, a.z, a.codebook, a.codebook_frag,
                      a.code_sqnorm, a.idx, a.quantized, a.dist_min, a.sse_partial, a.N, a.E, a.K);
+  return G2V_OK;
 }
-static void vq_launch_packed(const VqRoutePlan& pl, const VqRowsArgs& a) {
-  if (pl.variant == 4) vq_launch_packed_as<4, 2>(pl, a);
-  else if (pl.variant == 2) vq_launch_packed_as<2, 4>(pl, a);
-  else vq_launch_packed_as<1, 4>(pl, a);
+static int vq_launch_packed(const VqRoutePlan& pl, const VqRowsArgs& a) {
+  if (pl.variant == 4) return vq_launch_packed_as<4, 2>(pl, a);
+  if (pl.variant == 2) return vq_launch_packed_as<2, 4>(pl, a);
+  return vq_launch_packed_as<1, 4>(pl, a);
 }
 static int vq_launch_rows(const char* who, const VqRoutePlan& pl, const VqRowsArgs& a) {
   switch (pl.route) {
     case G2V_VQ_ROUTE_RT:
     case G2V_VQ_ROUTE_FAST: vq_launch_tuned(pl, a); break;
     case G2V_VQ_ROUTE_SPLIT: if (int rc = vq_launch_split(pl, a)) return rc; break;
-    case G2V_VQ_ROUTE_GENERIC: vq_launch_generic(pl, a); break;
-    case G2V_VQ_ROUTE_PACKED: vq_launch_packed(pl, a); break;
+    case G2V_VQ_ROUTE_GENERIC: if (int rc = vq_launch_generic(pl, a)) return rc; break;
+    case G2V_VQ_ROUTE_PACKED: if (int rc = vq_launch_packed(pl, a)) return rc; break;
     default: set_error("%s: %s", who, pl.msg ? pl.msg : "no route"); return pl.err ? pl.err : G2V_ERR_UNSUPPORTED;
   }
   G2V_CHECK_LAUNCH();
@@ -2499,13 +2498,9 @@ extern "C" int g2v_vq_bx_pack(const float* codebook, const float* code_sqnorm, c
   G2V_REQUIRE(ptr_aligned16(codebook) && ptr_aligned16(image), "16-byte aligned operands");
   const VqBxImage im(image, K, E);
   const size_t pack_lds = ((size_t)E * (E + 1) + 2 * 16 * (E + 4)) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)vq_bx_pack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pack_lds) != hipSuccess) {
-      set_error("g2v_vq_bx_pack: cannot reserve LDS");
-      return G2V_ERR_LAUNCH;
-    }
-    attr_set = true;
+  if (!g2v_internal_lds_reserve((const void*)vq_bx_pack_kernel, pack_lds)) {
+    set_error("g2v_vq_bx_pack: cannot reserve LDS");
+    return G2V_ERR_LAUNCH;
   }
   hipLaunchKernelGGL(vq_bx_pack_kernel, dim3(K / 16), dim3(256), pack_lds, (hipStream_t)stream, codebook, code_sqnorm, w_pre, b_pre,
                      im.Uhf, im.sprime, im.pqk, im.scal, K);

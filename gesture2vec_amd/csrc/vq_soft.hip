@@ -520,8 +520,7 @@ extern "C" int g2v_vq_soft_fused_fwd(const float* x, const float* w_mean, const 
   a.gcoef = 2.0f * g_scale / ((float)N * (float)E);
   a.N = N; a.K = K;
   const size_t lds = (size_t)(2 * 16 * (SOFT_E + 4) + 16 * (K + 4) + 64 + 4) * sizeof(float);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vq_soft_fused_fwd_kernel<SOFT_E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!g2v_internal_lds_reserve((const void*)vq_soft_fused_fwd_kernel<SOFT_E>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(vq_soft_fused_fwd_kernel<SOFT_E>, dim3(cdiv(N, 16)), dim3(256), lds, (hipStream_t)stream, a);
   G2V_CHECK_LAUNCH();
   return G2V_OK;
@@ -558,8 +557,7 @@ extern "C" int g2v_vq_soft_fused_bwd(const float* dh, const float* g_loss, const
   a.ccoef = 2.0f * beta / ((float)N * (float)E);
   a.N = N; a.K = K;
   const size_t lds = (size_t)(2 * 16 * (SOFT_E + 4) + 2 * 16 * (K + 4) + 64) * sizeof(float);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)vq_soft_fused_bwd_kernel<SOFT_E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (!g2v_internal_lds_reserve((const void*)vq_soft_fused_bwd_kernel<SOFT_E>, lds)) return G2V_ERR_LAUNCH;
   hipLaunchKernelGGL(vq_soft_fused_bwd_kernel<SOFT_E>, dim3(cdiv(N, 16)), dim3(256), lds, (hipStream_t)stream, a);
   G2V_CHECK_LAUNCH();
   return G2V_OK;
