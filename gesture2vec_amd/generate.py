@@ -14,7 +14,11 @@ of the next; then `DAE.decoder`, a blend across the chunk boundaries and the un-
 
 `AUTO_CHAIN_MIN_CLIPS` decides what route="auto" takes (DESIGN.md section 3.6d has the measured table it is set from).  Everything is
 forward-only and runs the net in eval mode (BatchNorm on its running statistics; the decoder's inline Dropout(0.95) stays
-active, as in the reference).  BVH writing, audio and word timing are out of scope."""
+active, as in the reference).
+
+`clip_angles` is the arithmetic every make_bvh of the reference runs on such a clip in front of pymo (csrc/clip_angles.hip, DESIGN.md
+section 3.6e): `rotmat_to_euler`, the per-frame Rotation.from_matrix(...).as_euler("ZXY", degrees=True), then `smoothing_spline`,
+csaps' cubic smoothing spline over every channel.  BVH writing, audio and word timing are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -346,6 +350,64 @@ def reconstruct_clips(dae, net, poses, mean, std, *, blend=10, smooth=None, **kw
             rows, ids = lat, None
         frames = decode_chunks(net, rows, ids, chunks=C_, start=enc[:, 0].contiguous(), teacher=chunks, **kw)
     return finish_clips(dae, frames, mean, std, n_poses=T, blend=blend, smooth=smooth)
+
+
+NEAREST = tuple(ops.ROT_METHODS)
+SPLINE_SMOOTH = 0.5                  # the reference's smooth_f (smoothing_function("spline", .) of every make_bvh)
+
+
+def rotmat_to_euler(frames, *, nearest="markley"):
+    """(..., 9 J) un-normalised row-major 3x3 matrices, joint-major -> (..., 3 J) joint angles in degrees, per joint (Z, X, Y) with
+    R = Rz(Z) Rx(X) Ry(Y): Rotation.from_matrix(frame.reshape(J, 3, 3)).as_euler("ZXY", degrees=True) of the reference's make_bvh
+    (inference_Autoencoder.py:584-592) for every frame in one launch (g2v_rotmat_to_euler).  The matrices are not orthogonal and
+    scipy's from_matrix is two functions: nearest="markley" is scipy 1.10.1's, the reference's pin (Markley's quaternion from the raw
+    entries), nearest="procrustes" scipy 1.15.3's (the nearest rotation first).  They agree on exact rotations only.
+    Raises ValueError, as scipy 1.15.3 does, when a matrix has a non-positive determinant, naming how many (one read-back)."""
+    _need_cuda(frames, "rotmat_to_euler")
+    if nearest not in NEAREST:
+        raise ValueError(f"rotmat_to_euler: nearest must be one of {NEAREST}, got {nearest!r}")
+    if frames.dim() < 1 or frames.shape[-1] == 0 or frames.shape[-1] % 9 != 0:
+        raise ValueError(f"rotmat_to_euler: the last dimension holds 9 entries per joint, got {tuple(frames.shape)}")
+    J = frames.shape[-1] // 9
+    lead = tuple(frames.shape[:-1])
+    flat = frames.detach().to(torch.float32).reshape(-1, 9 * J).contiguous()
+    if flat.shape[0] == 0:
+        return torch.empty(lead + (3 * J,), dtype=torch.float32, device=frames.device)
+    angles, bad = ops.rotmat_to_euler(flat, J, ops.ROT_METHODS[nearest])
+    n_bad = int(bad.item())
+    if n_bad:
+        raise ValueError(f"rotmat_to_euler: {n_bad} of {flat.shape[0] * J} matrices have a non-positive determinant (a zero matrix "
+                         "or a reflection): no rotation is nearest to them")
+    return angles.view(lead + (3 * J,))
+
+
+def smoothing_spline(y, smooth=SPLINE_SMOOTH):
+    """(B, F, Cn) -> (B, F, Cn): the cubic smoothing spline of every (clip, channel) along time at the frames themselves
+    (g2v_smoothing_spline): csaps.csaps(x, channel, x, smooth=smooth) of the reference's smoothing_function("spline", .), one
+    factorisation and B Cn solves in two launches.  smooth = 1 returns y, smooth = 0 the least-squares straight line."""
+    _need_cuda(y, "smoothing_spline")
+    if y.dim() != 3:
+        raise ValueError(f"smoothing_spline: y must be (B, F, Cn), got {tuple(y.shape)}")
+    p = float(smooth)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"smoothing_spline: smooth must lie in [0, 1], got {smooth!r}")
+    B, F, Cn = y.shape
+    if B < 1 or F < 2 or Cn < 1:
+        raise ValueError(f"smoothing_spline: needs B >= 1, F >= 2 and Cn >= 1, got {tuple(y.shape)}")
+    return ops.smoothing_spline(y.detach().to(torch.float32).contiguous(), p)
+
+
+def clip_angles(frames, *, nearest="markley", spline=SPLINE_SMOOTH):
+    """The tail of the reference's make_bvh in front of pymo's inverse_transform: frames (B, F, 9 J), as finish_clips returns them ->
+    (B, F, 3 J) joint angles, converted (rotmat_to_euler) and then smoothed along time (smoothing_spline with smooth = spline;
+    None: not smoothed).  As in the reference the angles are not unwrapped across +-180 degrees before the spline."""
+    _need_cuda(frames, "clip_angles")
+    if frames.dim() != 3:
+        raise ValueError(f"clip_angles: frames must be (B, F, 9 J), got {tuple(frames.shape)}")
+    if spline is not None and not 0.0 <= float(spline) <= 1.0:
+        raise ValueError(f"clip_angles: spline must be None or lie in [0, 1], got {spline!r}")
+    angles = rotmat_to_euler(frames, nearest=nearest)
+    return angles if spline is None else smoothing_spline(angles, spline)
 
 
 @torch.no_grad()

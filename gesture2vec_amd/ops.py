@@ -1243,6 +1243,43 @@ def ngram_clipped_counts(cand, cand_start, cand_len, ref, ref_start, ref_len, K,
     return clipped, bad
 
 
+# ------------------------------------------------------------------------------------------ joint angles (clip_angles.hip)
+ROT_METHODS = {"markley": _lib.ROT_MARKLEY, "procrustes": _lib.ROT_PROCRUSTES}
+
+
+def rotmat_to_euler(frames, J, method, out=None, bad=None):
+    """-> (angles (N, 3 J) degrees, bad (1,) int64) of frames (N, 9 J): per joint the intrinsic "ZXY" angles of its row-major 3x3
+    matrix (g2v_rotmat_to_euler); method: ROT_METHODS' values.  A matrix whose determinant is not > 0 has NaN in its three angles and
+    counts in bad[0], which is ADDED to (a fresh one starts at zero)."""
+    N = frames.shape[0]
+    if frames.dim() != 2 or frames.shape[1] != 9 * int(J):
+        raise ValueError(f"rotmat_to_euler: frames must be (N, {9 * int(J)}), got {tuple(frames.shape)}")
+    if out is None:
+        out = torch.empty((N, 3 * int(J)), dtype=torch.float32, device=frames.device)
+    if bad is None:
+        bad = torch.zeros((1,), dtype=torch.int64, device=frames.device)
+    check(_lib_().g2v_rotmat_to_euler(_p(_chk(frames, name="frames")), _p(_chk(out, name="out")), _p(_chk(bad, torch.int64, "bad")), N,
+                                      int(J), int(method), _stream()), "rotmat_to_euler")
+    return out, bad
+
+
+def smoothing_spline(y, smooth, out=None, ws=None):
+    """out (B, F, Cn) = the cubic smoothing spline of y (B, F, Cn) along F at the knots (g2v_smoothing_spline): csaps' `smooth` in
+    [0, 1].  out may be y itself.  ws: a uint8 workspace of at least g2v_smoothing_spline_workspace(B, F, Cn) bytes (default: the
+    reusable one)."""
+    if y.dim() != 3:
+        raise ValueError(f"smoothing_spline: y must be (B, F, Cn), got {tuple(y.shape)}")
+    B, F, Cn = y.shape
+    lib = _lib_()
+    if out is None:
+        out = torch.empty_like(y)
+    if ws is None:
+        ws = workspace(lib.g2v_smoothing_spline_workspace(B, F, Cn), y.device, "spline")
+    check(lib.g2v_smoothing_spline(_p(_chk(y, name="y")), _p(_chk(out, name="out")), float(smooth), B, F, Cn, _p(ws), ws.numel(),
+                                   _stream()), "smoothing_spline")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ k-means (kmeans.hip)
 KMEANS_STATE = ("done", "n_iter", "n_changed", "shift", "inertia", "n_relocated", "active", "tol_abs")   # the float64[8] state block
 

@@ -867,6 +867,43 @@ int g2v_dec_chain_fwd(const float* rows, int64_t R, const int64_t* ids, const fl
  *      last 25 (scipy's mode="interp").  Needs F >= 25 (else G2V_ERR_ARG) and tmp (B,F,Dr), distinct from r and out. */
 int g2v_clip_finish(const float* r, float* out, const float* mean, const float* std, const float* savgol, float* tmp, int T,
                     int blend, int B, int F, int Dr, g2v_stream_t stream);
+/* Joint angles from a finished clip (csrc/clip_angles.hip): what every make_bvh of the reference computes between the clip's 3x3
+ * matrices and the BVH writer (inference_Autoencoder.py:584-592, inference_text2embedding_GENEA.py:602-612).
+ *
+ * g2v_rotmat_to_euler: frames (N, 9 J) -> angles (N, 3 J) in degrees; columns joint-major, each joint's matrix row-major, its
+ * angles (Z, X, Y) with R = Rz(Z) Rx(X) Ry(Y): scipy's Rotation.from_matrix(m).as_euler("ZXY", degrees=True).  The matrices are a
+ * decoder's output and not orthogonal, and scipy's from_matrix is two functions across versions; `method` picks one:
+ *   G2V_ROT_MARKLEY     scipy 1.10.1, the reference's pin: Markley's quaternion from the RAW entries (the branch of the largest of
+ *                       m00, m11, m22, trace; the first on ties), normalised.
+ *   G2V_ROT_PROCRUSTES  scipy 1.15.3: the matrix is first replaced by the nearest rotation (its orthogonal polar factor, U V^T of
+ *                       its SVD; here by a scaled Newton iteration converged below 1e-13), then Markley.
+ * On exact rotations the two agree to rounding.  Past the quaternion both share scipy's rule: X in [-90, 90]; within 1e-7 rad of
+ * X = +-90 degrees Y is exactly 0 and Z carries the combined rotation; Z and Y lie in [-180, 180].  Arithmetic is float64 from the
+ * float32 entries with ONE rounding to float32 on output (at most 180 * 2^-24 = 1.07e-5 degrees).
+ * A matrix whose determinant is not > 0 (zero, a reflection, a NaN entry), under either method, gets NaN in its three angles and adds
+ * 1 to bad[0] (int64[1], cleared by the caller; an integer atomic); its neighbours are untouched.  N >= 1, J >= 1,
+ * N * J <= (2^31 - 1) * 256, method one of the two constants: G2V_ERR_ARG otherwise, nothing launched.  frames and angles must not
+ * overlap.  No workspace.
+ *
+ * g2v_smoothing_spline: y (B, F, Cn) -> out (B, F, Cn), de Boor's cubic smoothing spline of every (clip, channel) column along F at
+ * unit-spaced knots with unit weights, evaluated at the knots: csaps.csaps(x, y, x, smooth=p), the reference's
+ * smoothing_function("spline", .) with p = 0.5, which is scipy's make_smoothing_spline(x, y, lam=(1-p)/p)(x).  With n = F - 2:
+ *   (6 (1-p) Q^T Q + p R) u = Q^T y,   out = y - 6 (1-p) Q u,    Q (F, n) with columns (1, -2, 1),  R (n, n) tridiagonal (1, 4, 1).
+ * p = 1 returns y and p = 0 the least-squares straight line; F == 2 returns y.  The pentadiagonal matrix depends on F and p only: it
+ * is factored once per call (L D L^T, float64, 3 n doubles at the start of the workspace), then one lane per column solves in
+ * float64 and keeps its intermediate vector in the workspace as (n, B Cn) float64; one rounding to float32 on output.  Both launches
+ * go to `stream`; nothing is read back.  The same input gives the same bits and a clip's bits do not depend on the other clips.
+ * out may BE y (in place); any other overlap of the two is not allowed.
+ * 0 <= smooth <= 1, B >= 1, F >= 2, Cn >= 1 (G2V_ERR_ARG otherwise); F <= 2^20 and B Cn < 2^31 (G2V_ERR_UNSUPPORTED beyond).
+ * g2v_smoothing_spline_workspace: bytes, (3 + B Cn)(F - 2) * 8; 0 for F == 2 and outside those limits.  The workspace is 8-byte
+ * aligned, may hold anything on entry and is needed whatever smooth is; fewer bytes: G2V_ERR_WORKSPACE.  Every refusal comes before
+ * the first launch: nothing is written. */
+#define G2V_ROT_MARKLEY 0
+#define G2V_ROT_PROCRUSTES 1
+int g2v_rotmat_to_euler(const float* frames, float* angles, int64_t* bad, int64_t N, int J, int method, g2v_stream_t stream);
+size_t g2v_smoothing_spline_workspace(int B, int F, int Cn);
+int g2v_smoothing_spline(const float* y, float* out, double smooth, int B, int F, int Cn, void* workspace,
+                         size_t workspace_bytes, g2v_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * custom_loss forward + gradient (K10), train_eval/train_seq2seq.py:40-88.
