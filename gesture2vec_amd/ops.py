@@ -1385,6 +1385,62 @@ def silhouette_samples(x, labels, K):
     return res
 
 
+# ------------------------------------------------------------------------------------------ DBSCAN (dbscan.hip)
+def dbscan_max_rows() -> int:
+    return int(_lib_().g2v_dbscan_max_rows())
+
+
+def dbscan_workspace(N, E) -> int:
+    """bytes of workspace of dbscan_neighbors / dbscan_labels; 0 for a shape they refuse"""
+    return int(_lib_().g2v_dbscan_workspace(int(N), int(E)))
+
+
+def dbscan_neighbors(x, eps):
+    """-> (bitmap (N, ceil(N / 64)) int64, counts (N) int64) of the rows of x (N, E) fp32, unit column stride, row stride a multiple
+    of 4 (g2v_dbscan_neighbors): bit (j % 64) of word j // 64 of row i is set iff |x_i - x_j| <= eps, decided in float64; counts
+    is the popcount of each row.  The words are 64 bits each; int64 is the carrier."""
+    if not x.is_cuda:
+        raise _lib.G2VLibraryError("x must be a GPU tensor: the g2v kernels have no CPU path")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise TypeError("dbscan_neighbors: x must be a (N, E) fp32 tensor with unit column stride")
+    N, E = x.shape
+    if N > dbscan_max_rows():
+        raise ValueError(f"dbscan_neighbors: N = {N} exceeds {dbscan_max_rows()} rows (the adjacency bitmap is N^2 / 8 bytes)")
+    lib = _lib_()
+    nb = dbscan_workspace(N, E)
+    ws = workspace(max(nb, 16), x.device, "dbscan")
+    bitmap = torch.empty((N, (N + 63) // 64), dtype=torch.int64, device=x.device)
+    counts = torch.empty((N,), dtype=torch.int64, device=x.device)
+    check(lib.g2v_dbscan_neighbors(_p(x), int(x.stride(0)), N, E, float(eps), _p(bitmap), _p(counts), _p(ws), nb, _stream()),
+          "dbscan_neighbors")
+    return bitmap, counts
+
+
+def dbscan_propagate(bitmap, counts, min_samples, L, tmp, *, init, rounds=1):
+    """`rounds` rounds of min-propagation with pointer jumping over the core rows, in place on L (N) int32 (tmp: as L)
+    (g2v_dbscan_propagate) -> flags (rounds) int32 on the device, flags[r] = 1 iff round r changed a row.  init=True starts L."""
+    N = bitmap.shape[0]
+    flags = torch.empty((int(rounds),), dtype=torch.int32, device=bitmap.device)
+    check(_lib_().g2v_dbscan_propagate(_p(_chk(bitmap, torch.int64, "bitmap")), _p(_chk(counts, torch.int64, "counts")), N,
+                                       int(min_samples), 1 if init else 0, int(rounds), _p(_chk(L, torch.int32, "L")),
+                                       _p(_chk(tmp, torch.int32, "tmp")), _p(flags), _stream()), "dbscan_propagate")
+    return flags
+
+
+def dbscan_labels(bitmap, L):
+    """The converged L -> (labels (N) int64, core (N) uint8, out (3) int64 = [clusters, core rows, noise rows]) (g2v_dbscan_labels)"""
+    N = bitmap.shape[0]
+    dev = bitmap.device
+    labels = torch.empty((N,), dtype=torch.int64, device=dev)
+    core = torch.empty((N,), dtype=torch.uint8, device=dev)
+    out = torch.empty((3,), dtype=torch.int64, device=dev)
+    nb = dbscan_workspace(N, 1)
+    ws = workspace(max(nb, 16), dev, "dbscan")
+    check(_lib_().g2v_dbscan_labels(_p(_chk(bitmap, torch.int64, "bitmap")), _p(_chk(L, torch.int32, "L")), N, _p(labels), _p(core),
+                                    _p(out), _p(ws), nb, _stream()), "dbscan_labels")
+    return labels, core, out
+
+
 # ------------------------------------------------------------------------------------------ exact t-SNE (tsne.hip)
 def tsne_max_rows() -> int:
     return int(_lib_().g2v_tsne_max_rows())

@@ -1515,6 +1515,38 @@ int g2v_tsne_place_descent(const float* Y, int64_t N, const int32_t* idx, const 
                            float* velocity, float* gains, int n_iter, double exaggeration, float momentum, float learning_rate,
                            float max_grad_norm, double* kl, double* zsum, float* grad, g2v_stream_t stream);
 
+/* ---- DBSCAN over latent rows (dbscan.hip; gesture2vec_amd/dbscan.py) ----------------------------------------------------------------
+ * The other branch of the reference's clustering switch (Clustering.py:742-750, sklearn.cluster.DBSCAN(eps, min_samples).fit), with
+ * sklearn's labels, not merely an equivalent partition.  With adj(i,j) <=> |x_i - x_j| <= eps (a row is its own neighbour):
+ * core(i) <=> #{j : adj(i,j)} >= min_samples; root(i) = the smallest index in i's connected component of the core rows under adj;
+ * a component's cluster id = the rank of its root among all roots; a row that is not core gets the smallest id among its core
+ * neighbours, or -1 without one.  1 <= N <= g2v_dbscan_max_rows() = 131072 (the adjacency is a bitmap of N^2 / 8 bytes: 2 GiB at
+ * the limit), 1 <= E <= 512; G2V_ERR_UNSUPPORTED beyond.  Distances are formed once, in g2v_dbscan_neighbors; the other two read
+ * the bitmap.  No floating-point atomics: the same input gives the same bits.
+ *
+ * g2v_dbscan_neighbors: x (N,E) fp32 with row stride ld >= E, ld % 4 == 0, eps >= 0 -> bitmap: N rows of W = ceil(N / 64) 64-bit
+ *   words, bit (j % 64) of word j / 64 of row i = adj(i,j), bits past N zero, symmetric bit for bit; counts int64[N] = the popcount of
+ *   each row.  d^2 as g2v_tsne_affinities forms it (float64 norms, Gram tiles on the exact-fp32 MFMA in chains of 32 columns folded
+ *   in float64); adjacent iff d^2 <= eps * eps in float64.  A pair with |d^2 - eps^2| <= 2^-18 (|x_i|^2 + |x_j|^2), twice the
+ *   worst case of the Gram form's error, is evaluated again as sum (x_i - x_j)^2 in float64 and decided on that: every bit is the
+ *   float64 decision of the fp32 rows.  Columns E .. ld - 1 are never read.  x and workspace 16-byte aligned, bitmap 8-byte.
+ * g2v_dbscan_propagate: `rounds` >= 1 rounds of L'[i] = min(L[i], min {L[j] : adj(i,j), core(j)}) over the core rows, each followed
+ *   by pointer jumping L'[i] <- L'[L'[i]].  L, tmp: int32[N].  init != 0 first sets L[i] = i for core rows (counts[i] >= min_samples)
+ *   and N for the others; with init == 0 L continues from an earlier call and counts is not read.  flags int32[rounds]: flags[r] = 1
+ *   iff round r changed a row.  A round reads one array and writes the other, so neither its result nor the number of rounds
+ *   depends on the order of the workgroups, and no round waits on another workgroup.  Call until a flag stays 0 (at most N rounds):
+ *   then L[i] = root(i) for core rows.
+ * g2v_dbscan_labels: the converged L -> labels int64[N], core uint8[N], out int64[3] = { clusters, core rows, rows labelled -1 }.
+ * workspace (neighbors and labels): g2v_dbscan_workspace(N, E) bytes (0 for an unsupported shape), not trusted across calls. */
+int64_t g2v_dbscan_max_rows(void);
+size_t g2v_dbscan_workspace(int64_t N, int E);
+int g2v_dbscan_neighbors(const float* x, int64_t ld, int64_t N, int E, double eps, uint64_t* bitmap, int64_t* counts, void* workspace,
+                         size_t workspace_bytes, g2v_stream_t stream);
+int g2v_dbscan_propagate(const uint64_t* bitmap, const int64_t* counts, int64_t N, int64_t min_samples, int init, int rounds,
+                         int32_t* L, int32_t* tmp, int32_t* flags, g2v_stream_t stream);
+int g2v_dbscan_labels(const uint64_t* bitmap, const int32_t* L, int64_t N, int64_t* labels, uint8_t* core, int64_t* out,
+                      void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy [--n_clusters 300] [--scan-k 50:400:50]
                               [--silhouette-rows M | --no-silhouette]
+    python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm dbscan --eps 0.5 --min-samples 5
 
 `--chunks` holds (N, T, D) pose chunks in the autoencoder's input space.  Their latents (`chunk_latents`) are clustered with
 `KMeans(n_clusters, max_iter=2500, random_state=0)` and the model is pickled to `<checkpoint dir>/clusters/kmeans_model.pk`, where the
@@ -12,7 +13,10 @@ of the fitted labels are printed.
 `--scan-k a:b:step` prints the two curves of `Clustering.py:586-624` (`init="random", n_init=10, max_iter=300` per k), inertia and
 silhouette coefficient (gesture2vec_amd/silhouette.py, on the device), instead of writing a model, and returns `(k, inertia,
 silhouette)` triples.  The silhouette is taken over all latents up to 65 536 rows and over `--silhouette-rows M` rows sampled as
-sklearn's `sample_size` (seeded with `--seed`) beyond that or when M is given; `--no-silhouette` leaves it out (None in the triples)."""
+sklearn's `sample_size` (seeded with `--seed`) beyond that or when M is given; `--no-silhouette` leaves it out (None in the triples).
+`--algorithm dbscan` is the other branch of the reference's switch (`Clustering.py:742-750, 962-972`): `DBSCAN(eps, min_samples)` on
+the device (gesture2vec_amd/dbscan.py), the reference's two printed lines, and `labels` and the `core` mask in an `.npz` at `--out`
+(default `<checkpoint dir>/clusters/dbscan_labels.npz`)."""
 from __future__ import annotations
 
 import argparse
@@ -30,6 +34,7 @@ for _p in (_HERE, _ROOT):
         sys.path.insert(0, _p)
 
 from utils.train_utils import load_checkpoint_and_model  # noqa: E402
+from gesture2vec_amd.dbscan import DBSCAN  # noqa: E402
 from gesture2vec_amd.kmeans import KMeans  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents  # noqa: E402
 
@@ -55,7 +60,10 @@ def main(argv=None):
     ap.add_argument("--silhouette-rows", dest="silhouette_rows", type=int, default=None,
                     help="rows the silhouette is sampled over (default: all rows up to 65536, that many sampled beyond)")
     ap.add_argument("--no-silhouette", dest="silhouette", action="store_false", help="do not compute silhouette coefficients")
-    ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk)")
+    ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk; dbscan: the .npz of labels, dbscan_labels.npz there)")
+    ap.add_argument("--algorithm", choices=("kmeans", "dbscan"), default="kmeans")
+    ap.add_argument("--eps", type=float, default=0.5, help="dbscan: the neighbourhood radius")
+    ap.add_argument("--min-samples", dest="min_samples", type=int, default=5, help="dbscan: neighbours (itself included) of a core row")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -65,6 +73,19 @@ def main(argv=None):
     chunks = torch.from_numpy(np.load(a.chunks).astype(np.float32, copy=False)).to(dev)
     lat = latents_of(net, chunks, a.batch_rows)
     print(f"latents: {tuple(lat.shape)}")
+
+    if a.algorithm == "dbscan":
+        db = DBSCAN(eps=a.eps, min_samples=a.min_samples).fit(lat)
+        print("Estimated number of clusters: %d" % db.n_clusters_)
+        print("Estimated number of noise points: %d" % db.n_noise_)
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "clusters", "dbscan_labels.npz")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        core = np.zeros(lat.shape[0], dtype=bool)
+        core[db.core_sample_indices_.cpu().numpy()] = True
+        with open(out, "wb") as f:                               # (a file object: numpy appends no suffix of its own)
+            np.savez(f, labels=db.labels_.cpu().numpy(), core=core)
+        print(f"wrote {out}")
+        return db
 
     def silhouette_of(km):
         if not a.silhouette:
