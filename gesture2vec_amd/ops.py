@@ -1441,6 +1441,63 @@ def dbscan_labels(bitmap, L):
     return labels, core, out
 
 
+# ------------------------------------------------------------------------------------------ Ward linkage (ward.hip)
+def ward_max_rows() -> int:
+    return int(_lib_().g2v_ward_max_rows())
+
+
+def ward_workspace(N, E) -> int:
+    """bytes of workspace of ward_distances; 0 for a shape it refuses"""
+    return int(_lib_().g2v_ward_workspace(int(N), int(E)))
+
+
+def ward_distances(x):
+    """-> D (N, N) float64: the Euclidean (unsquared) distances between the rows of x (N, E) fp32, unit column stride, row stride a
+    multiple of 4 (g2v_ward_distances: the rows widened to float64, Gram tiles on the float64 MFMA, near pairs from differences);
+    +inf on the diagonal, bitwise symmetric."""
+    if not x.is_cuda:
+        raise _lib.G2VLibraryError("x must be a GPU tensor: the g2v kernels have no CPU path")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1:
+        raise TypeError("ward_distances: x must be a (N, E) fp32 tensor with unit column stride")
+    N, E = x.shape
+    if N > ward_max_rows():
+        raise ValueError(f"ward_distances: N = {N} exceeds {ward_max_rows()} rows (the distance matrix is 8 N^2 bytes)")
+    lib = _lib_()
+    nb = ward_workspace(N, E)
+    ws = workspace(max(nb, 16), x.device, "ward")
+    D = torch.empty((N, N), dtype=torch.float64, device=x.device)
+    check(lib.g2v_ward_distances(_p(x), int(x.stride(0)), N, E, _p(D), _p(ws), nb, _stream()), "ward_distances")
+    return D
+
+
+def ward_state(N, device):
+    """The tensors g2v_ward_rounds keeps between calls: size, nn, part int32 (N); pairs int32 (N - 1, 2), heights float64 (N - 1),
+    sizes int32 (N - 1): the merge log; counters int64 (4) = [merges logged, rounds that merged, the last round's merges, its base]"""
+    i32 = dict(dtype=torch.int32, device=device)
+    return {"size": torch.empty((N,), **i32), "nn": torch.empty((N,), **i32), "part": torch.empty((N,), **i32),
+            "pairs": torch.empty((max(N - 1, 1), 2), **i32), "heights": torch.empty((max(N - 1, 1),), dtype=torch.float64, device=device),
+            "sizes": torch.empty((max(N - 1, 1),), **i32), "counters": torch.empty((4,), dtype=torch.int64, device=device)}
+
+
+def ward_rounds(D, state, *, init, rounds=1):
+    """`rounds` rounds of mutual-nearest-neighbour merges over D (N, N) float64 from ward_distances, in place, logged into `state`
+    (ward_state) (g2v_ward_rounds) -> state["counters"] on the device.  init=True starts the state."""
+    N = D.shape[0]
+    if tuple(D.shape) != (N, N):
+        raise ValueError(f"ward_rounds: D must be square, got {tuple(D.shape)}")
+    s = state
+    for name in ("size", "nn", "part"):
+        if tuple(_chk(s[name], torch.int32, name).shape) != (N,):
+            raise ValueError(f"ward_rounds: {name} must be ({N},), got {tuple(s[name].shape)}")
+    if s["pairs"].shape[0] < N - 1 or s["heights"].shape[0] < N - 1 or s["sizes"].shape[0] < N - 1:
+        raise ValueError("ward_rounds: the merge log holds fewer than N - 1 entries")
+    check(_lib_().g2v_ward_rounds(_p(_chk(D, torch.float64, "D")), N, _p(s["size"]), _p(s["nn"]), _p(s["part"]), 1 if init else 0,
+                                  int(rounds), _p(_chk(s["pairs"], torch.int32, "pairs")), _p(_chk(s["heights"], torch.float64, "heights")),
+                                  _p(_chk(s["sizes"], torch.int32, "sizes")), _p(_chk(s["counters"], torch.int64, "counters")),
+                                  _stream()), "ward_rounds")
+    return s["counters"]
+
+
 # ------------------------------------------------------------------------------------------ exact t-SNE (tsne.hip)
 def tsne_max_rows() -> int:
     return int(_lib_().g2v_tsne_max_rows())

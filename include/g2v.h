@@ -1547,6 +1547,38 @@ int g2v_dbscan_propagate(const uint64_t* bitmap, const int64_t* counts, int64_t 
 int g2v_dbscan_labels(const uint64_t* bitmap, const int32_t* L, int64_t N, int64_t* labels, uint8_t* core, int64_t* out,
                       void* workspace, size_t workspace_bytes, g2v_stream_t stream);
 
+/* ---- Ward agglomerative clustering over latent rows (ward.hip; gesture2vec_amd/agglomerative.py) ------------------------------------
+ * The last sklearn branch of the reference's clustering switch (Clustering.py:751-755,
+ * AgglomerativeClustering(linkage="ward", n_clusters)), with the merges of scipy.cluster.hierarchy.ward.  Ward linkage is reducible,
+ * so clusters that are each other's nearest neighbour may be merged at any time: a round merges all such pairs at once.  A slot is
+ * a cluster; slot k starts as row k and a merged pair lives on in its smaller slot.  1 <= N <= g2v_ward_max_rows() = 32768 (the
+ * distance matrix is 8 N^2 bytes: 8 GiB at the limit), 1 <= E <= 512; G2V_ERR_UNSUPPORTED beyond, before any launch.  No
+ * floating-point atomics: the same input gives the same bits, whatever the order of the workgroups.
+ *
+ * g2v_ward_distances: x (N,E) fp32 with row stride ld >= E, ld % 4 == 0 -> D: N x N float64, row stride N, D[i][j] = |x_i - x_j| of
+ *   the rows widened to float64 (unsquared), +inf on the diagonal, D[i][j] and D[j][i] the same bits (one value, stored twice).
+ *   d^2 = |x_i|^2 + |x_j|^2 - 2 x_i.x_j with float64 norms and Gram tiles on the float64 MFMA; a pair with
+ *   d^2 < (|x_i|^2 + |x_j|^2) / 8 is evaluated again as sum (x_i - x_j)^2 in float64, so bitwise equal rows are 0 apart.  Columns
+ *   E .. ld - 1 are never read.  x and workspace 16-byte aligned, D 8-byte.  workspace: g2v_ward_workspace(N, E) bytes (0 for an
+ *   unsupported shape), not trusted across calls.
+ * g2v_ward_rounds: `rounds` >= 1 rounds over D, in place.  State: size int32[N] (rows of the slot's cluster, 0 = dead), nn int32[N]
+ *   (the cached nearest active slot), part int32[N] (the slot merged with in the last round, or -1); init != 0 starts them (and
+ *   zeroes counters) for N clusters of one row, with init == 0 they continue from an earlier call.  One round: (a) nn of every slot
+ *   that merged in the last round or whose cached nn did, ties to the smallest index (the others keep their cache, which
+ *   reducibility allows); (b) every mutual pair i < j is logged in ascending i behind the earlier rounds': pairs int32[N-1][2] =
+ *   (i, j), heights float64[N-1] = D[i][j], sizes int32[N-1] = rows of the union; (c) D[i][k] and D[k][i] of every surviving slot k
+ *   become scipy's Ward update sqrt(((n_i+n_k) d_ik^2 + (n_j+n_k) d_jk^2 - n_k d_ij^2) / (n_i+n_j+n_k)) of unsquared distances; where
+ *   k itself survives a pair of this round, its columns are merged first, then the rows, by one thread that writes both places.  j
+ *   is dead from then on and never read.  counters int64[4] = { merges logged, rounds that merged, merges of the last round, where
+ *   its log begins }.  A round with one active cluster changes nothing, so call until counters[0] == N - 1 (at most N - 1 rounds).
+ *   The log is in round order, not in height order. */
+int64_t g2v_ward_max_rows(void);
+size_t g2v_ward_workspace(int64_t N, int E);
+int g2v_ward_distances(const float* x, int64_t ld, int64_t N, int E, double* D, void* workspace, size_t workspace_bytes,
+                       g2v_stream_t stream);
+int g2v_ward_rounds(double* D, int64_t N, int32_t* size, int32_t* nn, int32_t* part, int init, int rounds, int32_t* pairs,
+                    double* heights, int32_t* sizes, int64_t* counters, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy [--n_clusters 300] [--scan-k 50:400:50]
                               [--silhouette-rows M | --no-silhouette]
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm dbscan --eps 0.5 --min-samples 5
+    python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm ward [--n_clusters 300 |
+                              --distance-threshold T] [--scan-k 50:400:50]
 
 `--chunks` holds (N, T, D) pose chunks in the autoencoder's input space.  Their latents (`chunk_latents`) are clustered with
 `KMeans(n_clusters, max_iter=2500, random_state=0)` and the model is pickled to `<checkpoint dir>/clusters/kmeans_model.pk`, where the
@@ -16,7 +18,11 @@ silhouette)` triples.  The silhouette is taken over all latents up to 65 536 row
 sklearn's `sample_size` (seeded with `--seed`) beyond that or when M is given; `--no-silhouette` leaves it out (None in the triples).
 `--algorithm dbscan` is the other branch of the reference's switch (`Clustering.py:742-750, 962-972`): `DBSCAN(eps, min_samples)` on
 the device (gesture2vec_amd/dbscan.py), the reference's two printed lines, and `labels` and the `core` mask in an `.npz` at `--out`
-(default `<checkpoint dir>/clusters/dbscan_labels.npz`)."""
+(default `<checkpoint dir>/clusters/dbscan_labels.npz`).
+`--algorithm ward` is the third (`Clustering.py:751-755`): `AgglomerativeClustering(linkage="ward", n_clusters)` on the device
+(gesture2vec_amd/agglomerative.py), cut at `--n_clusters` or, instead, at `--distance-threshold`; `labels`, `children` and the merge
+`heights` go to an `.npz` at `--out` (default `<checkpoint dir>/clusters/ward_labels.npz`).  With `--scan-k a:b:step` the tree is
+fitted once and the silhouette coefficient of `cut(k)` is printed per k; `(k, silhouette)` pairs are returned and nothing is written."""
 from __future__ import annotations
 
 import argparse
@@ -34,6 +40,7 @@ for _p in (_HERE, _ROOT):
         sys.path.insert(0, _p)
 
 from utils.train_utils import load_checkpoint_and_model  # noqa: E402
+from gesture2vec_amd.agglomerative import AgglomerativeClustering  # noqa: E402
 from gesture2vec_amd.dbscan import DBSCAN  # noqa: E402
 from gesture2vec_amd.kmeans import KMeans  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents  # noqa: E402
@@ -60,8 +67,12 @@ def main(argv=None):
     ap.add_argument("--silhouette-rows", dest="silhouette_rows", type=int, default=None,
                     help="rows the silhouette is sampled over (default: all rows up to 65536, that many sampled beyond)")
     ap.add_argument("--no-silhouette", dest="silhouette", action="store_false", help="do not compute silhouette coefficients")
-    ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk; dbscan: the .npz of labels, dbscan_labels.npz there)")
-    ap.add_argument("--algorithm", choices=("kmeans", "dbscan"), default="kmeans")
+    ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk; dbscan: the .npz of labels, dbscan_labels.npz there; ward: ward_labels.npz there)")
+    ap.add_argument("--algorithm", choices=("kmeans", "dbscan", "ward"), default="kmeans",
+                    help="the branch of the reference's clustering switch: {kmeans,dbscan} as before, or ward = "
+                         "AgglomerativeClustering(linkage='ward') cut at --n_clusters or --distance-threshold")
+    ap.add_argument("--distance-threshold", dest="distance_threshold", type=float, default=None,
+                    help="ward: cut the tree below this merge height instead of at --n_clusters")
     ap.add_argument("--eps", type=float, default=0.5, help="dbscan: the neighbourhood radius")
     ap.add_argument("--min-samples", dest="min_samples", type=int, default=5, help="dbscan: neighbours (itself included) of a core row")
     ap.add_argument("--batch_rows", type=int, default=65536)
@@ -86,6 +97,30 @@ def main(argv=None):
             np.savez(f, labels=db.labels_.cpu().numpy(), core=core)
         print(f"wrote {out}")
         return db
+
+    if a.algorithm == "ward":
+        from gesture2vec_amd.silhouette import silhouette_score
+        if a.scan_k:                                             # one tree answers every k: the fit's own cut is the first of them
+            lo, hi, step = (int(v) for v in a.scan_k.split(":"))
+            a.n_clusters, a.distance_threshold = lo, None
+        by_k = a.distance_threshold is None
+        ac = AgglomerativeClustering(n_clusters=a.n_clusters if by_k else None, distance_threshold=a.distance_threshold,
+                                     compute_distances=True, check_every=a.check_every).fit(lat)
+        print(f"rounds: {ac.n_rounds_}")
+        if a.scan_k:
+            curve = []
+            for k in range(lo, hi, step):
+                sil = silhouette_score(lat, ac.cut(k)) if a.silhouette else None
+                curve.append((k, sil))
+                print(f"k = {k}" + (f": silhouette {sil!r}" if a.silhouette else ""))
+            return curve
+        print("Number of clusters: %d" % ac.n_clusters_)
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "clusters", "ward_labels.npz")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "wb") as f:
+            np.savez(f, labels=ac.labels_.cpu().numpy(), children=ac.children_, heights=ac.distances_)
+        print(f"wrote {out}")
+        return ac
 
     def silhouette_of(km):
         if not a.silhouette:
