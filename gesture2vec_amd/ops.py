@@ -1498,6 +1498,99 @@ def ward_rounds(D, state, *, init, rounds=1):
     return s["counters"]
 
 
+# ------------------------------------------------------------------------------------------ DTW k-means (dtw.hip)
+def dtw_max_len() -> int:
+    return int(_lib_().g2v_dtw_max_len())
+
+
+def dtw_workspace(N, M, T, S, F) -> int:
+    """bytes of workspace of dtw_cdist / dtw_dba_accumulate against M centres; 0 for a shape they refuse"""
+    return int(_lib_().g2v_dtw_workspace(int(N), int(M), int(T), int(S), int(F)))
+
+
+def _dtw_operands(x, y, fn):
+    if not x.is_cuda or not y.is_cuda:
+        raise _lib.G2VLibraryError(f"{fn}: the series and the centres must be GPU tensors: the g2v kernels have no CPU path")
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError(f"{fn}: the series must be a contiguous (N, T, F) fp32 tensor")
+    if y.dim() != 3 or y.dtype != torch.float64 or not y.is_contiguous():
+        raise TypeError(f"{fn}: the centres must be a contiguous (M, S, F) float64 tensor")
+    if y.shape[2] != x.shape[2]:
+        raise ValueError(f"{fn}: the series have {x.shape[2]} columns and the centres {y.shape[2]}")
+    if x.shape[0] < 1 or y.shape[0] < 1:
+        raise ValueError(f"{fn}: needs at least one series and one centre")
+    return x.shape[0], x.shape[1], y.shape[0], y.shape[1], x.shape[2]
+
+
+def _dtw_ws(N, M, T, S, F, device):
+    nb = dtw_workspace(N, M, T, S, F)
+    return workspace(max(nb, 16), device, "dtw"), nb
+
+
+def dtw_cdist(x, y, *, squared=False, want_out=True, want_labels=False):
+    """x (N, T, F) fp32 series, y (M, S, F) float64 centres -> (out, labels, best) (g2v_dtw_cdist): out (N, M) float64 = dtw^2 with
+    squared=True, else its square root (None without want_out); labels (N) int64 = the argmin over the centres, lowest index on
+    ties, best (N) float64 = the minimal dtw^2 (None without want_labels)."""
+    N, T, M, S, F = _dtw_operands(x, y, "dtw_cdist")
+    if not (want_out or want_labels):
+        raise ValueError("dtw_cdist: nothing asked for")
+    dev = x.device
+    out = torch.empty((N, M), dtype=torch.float64, device=dev) if want_out else None
+    labels = torch.empty((N,), dtype=torch.int64, device=dev) if want_labels else None
+    best = torch.empty((N,), dtype=torch.float64, device=dev) if want_labels else None
+    ws, nb = _dtw_ws(N, M, T, S, F, dev)
+    check(_lib_().g2v_dtw_cdist(_p(x), N, T, _p(y), M, S, F, 1 if squared else 0, _p(out), _p(labels), _p(best), _p(ws), nb, _stream()),
+          "dtw_cdist")
+    return out, labels, best
+
+
+def dtw_dba_state(K, device):
+    """The stop-rule block of g2v_dtw_dba_update as one byte tensor -> (state, prev_cost (K) float64 view, live (K) uint8 view),
+    started at +inf and 1"""
+    state = torch.empty((9 * int(K),), dtype=torch.uint8, device=device)
+    prev, live = state[:8 * K].view(torch.float64), state[8 * K:]
+    prev.fill_(float("inf"))
+    live.fill_(1)
+    return state, prev, live
+
+
+def dtw_dba_accumulate(x, labels, centers, live=None, out=None):
+    """One DBA assignment pass (g2v_dtw_dba_accumulate): per live cluster k, over the warping paths of its rows against centers[k]
+    -> dict sums (K, S, F) float64, counts (K, S) int64, cost (K) float64; `out`: such a dict to write into (clusters that are not
+    live keep what it holds).  labels (N) int64; live (K) uint8 or None."""
+    N, T, K, S, F = _dtw_operands(x, centers, "dtw_dba_accumulate")
+    dev = x.device
+    if tuple(_chk(labels, torch.int64, "labels").shape) != (N,):
+        raise ValueError(f"dtw_dba_accumulate: labels must be ({N},), got {tuple(labels.shape)}")
+    if live is not None and tuple(_chk(live, torch.uint8, "live").shape) != (K,):
+        raise ValueError(f"dtw_dba_accumulate: live must be ({K},), got {tuple(live.shape)}")
+    if out is None:
+        out = {"sums": torch.zeros((K, S, F), dtype=torch.float64, device=dev),
+               "counts": torch.zeros((K, S), dtype=torch.int64, device=dev), "cost": torch.zeros((K,), dtype=torch.float64, device=dev)}
+    if tuple(_chk(out["sums"], torch.float64, "sums").shape) != (K, S, F) or \
+            tuple(_chk(out["counts"], torch.int64, "counts").shape) != (K, S) or \
+            tuple(_chk(out["cost"], torch.float64, "cost").shape) != (K,):
+        raise ValueError("dtw_dba_accumulate: out must hold sums (K, S, F), counts (K, S) and cost (K)")
+    ws, nb = _dtw_ws(N, K, T, S, F, dev)
+    check(_lib_().g2v_dtw_dba_accumulate(_p(x), N, T, _p(labels), _p(centers), K, S, F, _p(live), _p(out["sums"]), _p(out["counts"]),
+                                         _p(out["cost"]), _p(ws), nb, _stream()), "dtw_dba_accumulate")
+    return out
+
+
+def dtw_dba_update(acc, members, state, centers, tol):
+    """One barycentre step per live cluster, in place on centers (K, S, F) float64 and on state (dtw_dba_state)
+    (g2v_dtw_dba_update); acc: the dict of dtw_dba_accumulate, members (K) int64: the rows of each cluster."""
+    K, S, F = _chk(centers, torch.float64, "centers").shape
+    if state.dtype != torch.uint8 or state.numel() != 9 * K or not state.is_contiguous():
+        raise ValueError(f"dtw_dba_update: state must be the {9 * K} bytes of dtw_dba_state")
+    if tuple(_chk(members, torch.int64, "members").shape) != (K,):
+        raise ValueError(f"dtw_dba_update: members must be ({K},), got {tuple(members.shape)}")
+    check(_lib_().g2v_dtw_dba_update(_p(_chk(acc["sums"], torch.float64, "sums")), _p(_chk(acc["counts"], torch.int64, "counts")),
+                                     _p(_chk(acc["cost"], torch.float64, "cost")), _p(members), _p(_chk(state, torch.uint8, "state")),
+                                     _p(centers), K, S, F, float(tol), _stream()), "dtw_dba_update")
+    return centers
+
+
 # ------------------------------------------------------------------------------------------ exact t-SNE (tsne.hip)
 def tsne_max_rows() -> int:
     return int(_lib_().g2v_tsne_max_rows())

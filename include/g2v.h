@@ -1579,6 +1579,47 @@ int g2v_ward_distances(const float* x, int64_t ld, int64_t N, int E, double* D, 
 int g2v_ward_rounds(double* D, int64_t N, int32_t* size, int32_t* nn, int32_t* part, int init, int rounds, int32_t* pairs,
                     double* heights, int32_t* sizes, int64_t* counters, g2v_stream_t stream);
 
+/* ---- DTW k-means over chunk sequences (dtw.hip; gesture2vec_amd/timeseries.py) ------------------------------------------------------
+ * The reference's other clustering space (Clustering.py:629-669, tslearn's TimeSeriesKMeans(metric="dtw")): dynamic time warping
+ * between series and centres, and DTW barycentre averaging (DBA).  tslearn is not a dependency and no run of it stands behind this
+ * block: the algorithm is stated here, from tslearn's definition, and tested against a float64 restatement (tests/_dtw_ref.py).
+ *   Series x: fp32 (N, T, F), contiguous.  Centres / second operands y: float64 (M, S, F), contiguous (fp32 widens exactly).
+ *   cost(i, j) = sum_f (a_if - b_jf)^2 from the differences in float64, never from a Gram form: every term is non-negative and
+ *     identical series are exactly 0 apart.  The terms are added in ascending f, each fused into the running sum.
+ *   acc(i, j) = cost(i, j) + min(acc(i-1, j-1), acc(i-1, j), acc(i, j-1)); acc(0, 0) = cost(0, 0); absent predecessors are +inf.
+ *   dtw^2(a, b) = acc(T-1, S-1).
+ *   The path is walked back from (T-1, S-1) to (0, 0): from each cell to the smallest of (i-1, j-1), (i-1, j), (i, j-1), on equal
+ *     values the first of them in that order, on an edge the only move there is.
+ * Supported: 1 <= T, S <= g2v_dtw_max_len() = 64 and 1 <= F <= 512; beyond, G2V_ERR_UNSUPPORTED before any launch.  Everything is
+ * float64 (the planted test inputs decide a path cell by as little as 4e-7 relative).  No floating-point atomics: the same input
+ * gives the same bits on every call, whatever the number of workgroups or CUs.
+ *
+ * g2v_dtw_workspace(N, M, T, S, F): bytes for either call below with M centres (0 for an unsupported shape); 16-byte aligned, not
+ *   trusted across calls.
+ * g2v_dtw_cdist: out double (N, M) = dtw^2(x_n, y_m) when squared != 0, its square root otherwise; may be NULL.  labels int64[N] =
+ *   the argmin over m of dtw^2, the lowest index on ties; best double[N] = the minimal dtw^2; NULL together.
+ * g2v_dtw_dba_accumulate: over every row n with 0 <= labels[n] < K and live[labels[n]] != 0 (live NULL: every cluster is live), with
+ *   k = labels[n], the centre c_k as the first index i and the row as the second index j, over every cell (i, j) of the row's path:
+ *   sums[k][i][:] += x[n][j][:] (float64 (K, S, F)), counts[k][i] += 1 (int64 (K, S)), cost[k] += dtw^2 (double[K]).  The outputs of a
+ *   live cluster are overwritten, not added to (zeros for one without rows); rows with other ids are ignored; a cluster that is
+ *   not live is left untouched.  The rows of a cluster are added in ascending n, in slabs of a fixed number of rows that are folded
+ *   in slab order.
+ * g2v_dtw_dba_update: one barycentre step per live cluster.  state = double prev_cost[K] followed by uint8 live[K] (start: +inf and
+ *   1); members int64[K] = the rows of each cluster.  For a live k: centers[k][i][:] = sums[k][i][:] / counts[k][i] (every
+ *   counts[k][i] of a cluster with rows is >= 1: a path visits every i); then, with c = cost[k] / members[k], the cluster stops
+ *   (live = 0) if |prev - c| < tol or prev < c, otherwise prev = c.  The update is applied before the test.  A live cluster
+ *   without rows keeps its centre and stops.  A cluster that is not live is a no-op in both calls, so every step of a barycentre
+ *   can be enqueued without reading back: the same bits as checking after each. */
+int g2v_dtw_max_len(void);
+size_t g2v_dtw_workspace(int64_t N, int64_t M, int T, int S, int F);
+int g2v_dtw_cdist(const float* x, int64_t N, int T, const double* y, int64_t M, int S, int F, int squared, double* out, int64_t* labels,
+                  double* best, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+int g2v_dtw_dba_accumulate(const float* x, int64_t N, int T, const int64_t* labels, const double* centers, int K, int S, int F,
+                           const uint8_t* live, double* sums, int64_t* counts, double* cost, void* workspace, size_t workspace_bytes,
+                           g2v_stream_t stream);
+int g2v_dtw_dba_update(const double* sums, const int64_t* counts, const double* cost, const int64_t* members, void* state,
+                       double* centers, int K, int S, int F, double tol, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
