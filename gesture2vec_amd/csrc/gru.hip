@@ -2222,10 +2222,13 @@ static GruWs gru_ws(bool bwd, const float* const* w_hh, const float* const* w_ih
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------
 struct GruCallFacts {      // what the plan needs to know of ONE call beyond its sizes; the defaults are the queries' ideal call
-  // 16-byte alignment of every array a route reads or writes as float4s, over all directions.  Forward: split = gi, w_hh, b_hh, h0,
-  // gates, h_n, workspace; vec = gi, b_hh, hs, gates (resident: the same).  Backward: split = gates, dgi, dgh, d_hn, h0, dh0,
-  // workspace; vec = gates, dgi, dgh, hs, h0, dh0, d_hs; resident = vec and d_hn.
-  bool split_aligned = true, vec_aligned = true, res_aligned = true;
+  // 16-byte alignment of every array a route reads or writes as float4s, over all directions (the workspace is aligned by the entry
+  // points' contract).  Forward: split = gi, w_hh, b_hh, h0, gates, h_n; vec = gi, b_hh, hs, gates (resident: the same).  Backward:
+  // split = gates, dgi, dgh, d_hn, h0, dh0; vec = gates, dgi, dgh, hs, h0, dh0, d_hs; resident = vec and d_hn.
+  // FAST moves as float4s: forward gi, b_hh, hs, h_n, gates, x, b_ih; backward gates, dgi, dgh, hs, h0, dh0, d_hs, d_hn, dx, wslab
+  // (x: wgrad_complete).  It asks for split and vec (backward: resident) -- a superset: the forward's w_hh and h0 are on split though
+  // FAST reads them element-wise -- and fast = x, b_ih (forward) / dx, wslab (backward), so that one bit per list describes a call.
+  bool split_aligned = true, vec_aligned = true, res_aligned = true, fast_aligned = true;
   bool hs_ld4 = true, d_hs_ld4 = true;              // the leading dimensions are multiples of 4 (d_hs_ld: backward)
   bool packed = false, gathered = false, lengths = true;      // gi_row_off / dgi_row_off, gi_gather, lengths are set
   bool fused = false, in_dim_is_H = true;           // gi == NULL / dx != NULL; every direction's in_dim == H
@@ -2264,7 +2267,7 @@ static GruRoutePlan gru_route_plan(bool bwd, int T, int B, int H, int ndir, int 
   const bool ld4 = f.hs_ld4 && (!bwd || f.d_hs_ld4);
   const bool split_shape = B <= GRU_SPLIT_MAX_B && nblk * ndir <= 128 && (H & 3) == 0 && H <= 16 * GRU_STEP_KS && 3 * H <= 16 * GRU_STEP_KSB;
   const bool vec = (H & 3) == 0 && H <= 256 && ld4 && f.vec_aligned;
-  if (H == 64 && ld4) {
+  if (H == 64 && ld4 && f.split_aligned && (bwd ? f.res_aligned : f.vec_aligned) && f.fast_aligned) {
     launch(G2V_GRU_ROUTE_FAST, !bwd ? (f.fused ? 1 : 0) : f.wgrad ? 1 + f.wgrad : (f.fused ? 1 : 0), nblk, ndir, 1, 256, 0);
     pl.pack = !f.prepared;
   } else if (split_shape && f.split_aligned) {
@@ -2335,7 +2338,7 @@ extern "C" int g2v_gru_seq_route(int backward, int T, int B, int H, int ndir, in
   const bool bwd = backward != 0;
   GruCallFacts f;
   f.split_aligned = !(facts & G2V_GRU_PLAN_SPLIT_UNALIGNED); f.vec_aligned = !(facts & G2V_GRU_PLAN_VEC_UNALIGNED);
-  f.res_aligned = f.vec_aligned && !(facts & G2V_GRU_PLAN_D_HN_UNALIGNED);
+  f.res_aligned = f.vec_aligned && !(facts & G2V_GRU_PLAN_D_HN_UNALIGNED); f.fast_aligned = !(facts & G2V_GRU_PLAN_FAST_UNALIGNED);
   f.hs_ld4 = !(facts & G2V_GRU_PLAN_HS_LD); f.d_hs_ld4 = !(facts & G2V_GRU_PLAN_D_HS_LD);
   f.packed = facts & G2V_GRU_PLAN_PACKED; f.gathered = facts & G2V_GRU_PLAN_GATHERED; f.lengths = !(facts & G2V_GRU_PLAN_NO_LENGTHS);
   f.fused = facts & G2V_GRU_PLAN_FUSED; f.in_dim_is_H = !(facts & G2V_GRU_PLAN_IN_DIM);
@@ -2523,6 +2526,7 @@ static int gru_seq_fwd_impl(const g2v_gru_dir* dirs, int ndir, const int32_t* le
   G2V_REQUIRE(dirs && workspace, "null pointer");
   G2V_REQUIRE(ndir >= 1 && ndir <= 2, "1 or 2 directions per call");
   G2V_REQUIRE(T > 0 && B > 0 && H > 0 && hs_ld >= H, "bad size");
+  G2V_REQUIRE(aligned16((const char*)workspace), "the workspace must be 16-byte aligned");      // (the contract of g2v.h: packs, state, carry are moved as float4s)
   // gi == NULL: the input projection is fused (x, w_ih, b_ih given, in_dim == H == 64); all directions alike
   GruCallFacts f;
   f.gathered = dirs[0].gi_gather != nullptr; f.fused = dirs[0].gi == nullptr; f.packed = dirs[0].gi_row_off != nullptr;
@@ -2535,8 +2539,9 @@ static int gru_seq_fwd_impl(const g2v_gru_dir* dirs, int ndir, const int32_t* le
     G2V_REQUIRE((d.gi == nullptr) == f.fused, "directions must agree on gi / fused input projection");
     G2V_REQUIRE(!f.fused || (d.x && d.w_ih && d.b_ih), "gi == NULL needs x, w_ih, b_ih");
     G2V_REQUIRE((d.gi_row_off != nullptr) == f.packed, "packed gi: every direction or none");
-    f.split_aligned = f.split_aligned && aligned16(d.gi, d.w_hh, d.b_hh, d.h0, d.gates, d.h_n, (const char*)workspace);
+    f.split_aligned = f.split_aligned && aligned16(d.gi, d.w_hh, d.b_hh, d.h0, d.gates, d.h_n);
     f.vec_aligned = f.vec_aligned && aligned16(d.gi, d.b_hh, d.hs, d.gates);
+    f.fast_aligned = f.fast_aligned && aligned16(d.x, d.b_ih);
     f.in_dim_is_H = f.in_dim_is_H && d.in_dim == H;
     w_hh[k] = d.w_hh; w_ih[k] = d.w_ih; off[k] = d.gi_row_off;
   }
@@ -2688,6 +2693,7 @@ static int gru_seq_bwd_impl(const g2v_gru_dir_bwd* dirs, int ndir, const int32_t
   G2V_REQUIRE(dirs && workspace, "null pointer");
   G2V_REQUIRE(ndir >= 1 && ndir <= 2, "1 or 2 directions per call");
   G2V_REQUIRE(T > 0 && B > 0 && H > 0, "bad size");
+  G2V_REQUIRE(aligned16((const char*)workspace), "the workspace must be 16-byte aligned");      // (as the forward)
   // dx != NULL: the input gradient dx = dgi W_ih is fused (w_ih given, in_dim == H == 64); dw_hh != NULL: the weight gradients too,
   // W_hh only (dw_hh, db_hh, wslab) or W_hh and W_ih (plus dw_ih, db_ih, x); all directions alike
   GruCallFacts f;
@@ -2701,9 +2707,10 @@ static int gru_seq_bwd_impl(const g2v_gru_dir_bwd* dirs, int ndir, const int32_t
     G2V_REQUIRE((d.dx != nullptr) == f.fused, "directions must agree on the fused input gradient");
     G2V_REQUIRE(!f.fused || d.w_ih, "dx != NULL needs w_ih");
     G2V_REQUIRE((d.dgi_row_off != nullptr) == f.packed, "packed dgi: every direction or none");
-    f.split_aligned = f.split_aligned && aligned16(d.gates, d.dgi, d.dgh, d.d_hn, d.h0, d.dh0, (const float*)workspace);
+    f.split_aligned = f.split_aligned && aligned16(d.gates, d.dgi, d.dgh, d.d_hn, d.h0, d.dh0);
     f.vec_aligned = f.vec_aligned && aligned16(d.gates, d.dgi, d.dgh, d.hs, d.h0, d.dh0, d.d_hs);
     f.res_aligned = f.res_aligned && aligned16(d.gates, d.dgi, d.dgh, d.hs, d.h0, d.dh0, d.d_hs, d.d_hn);
+    f.fast_aligned = f.fast_aligned && aligned16(d.dx, d.wslab);
     f.in_dim_is_H = f.in_dim_is_H && d.in_dim == H;
     const bool hh = d.dw_hh && d.db_hh && d.wslab, ih = d.dw_ih && d.db_ih && d.x, no_ih = !d.dw_ih && !d.db_ih;
     f.wgrad_any = f.wgrad_any || d.dw_hh || d.db_hh || d.wslab || d.dw_ih || d.db_ih;

@@ -511,14 +511,19 @@ int g2v_cluster_exchange_preclear_drop(const void* workspace, size_t workspace_b
 /* Which implementation a g2v_gru_seq_fwd / _bwd call runs on (csrc/gru.hip: gru_route_plan).  Plain
  * arithmetic on the direction of travel, T, B, H, ndir, three options of the bound context, the device's CU count and the facts
  * of the call; first match wins.  "Aligned": 16-byte aligned in every direction, NULL counts as aligned.
- *   FAST      H == 64 and the leading dimensions (hs_ld; backward d_hs_ld too) multiples of 4.  The weights as fragment packs in the
- *             workspace (g2v_gru_seq_prepare).  The only route that fuses the input projection (gi == NULL) / the input gradient
- *             (dx != NULL), both with in_dim == H, and the weight gradients (dw_hh ...).  Variant forward: 0, 1 projection fused;
- *             backward: 0, 1 dx fused, 2 and dW_hh, db_hh, 3 and dW_ih, db_ih.
+ *   FAST      H == 64, the leading dimensions (hs_ld; backward d_hs_ld too) multiples of 4, and every array the kernels move as
+ *             16-byte vectors aligned: forward gi, b_hh, hs, h_n, gates, x, b_ih; backward gates, dgi, dgh, hs, h0, dh0, d_hs, d_hn,
+ *             dx, wslab.  Asked through the lists below, one fact per list: STEP's list and the vector body's (backward:
+ *             RESIDENT's) aligned, and x, b_ih / dx, wslab.  That is a superset: the forward's w_hh and h0 are on STEP's list
+ *             though FAST reads them element-wise.  An H == 64 call that misses it goes to the next route that admits it, as
+ *             one with hs_ld % 4 != 0 does.  The weights as fragment packs in the workspace (g2v_gru_seq_prepare).  The only
+ *             route that fuses the input projection (gi == NULL) / the input gradient (dx != NULL), both with in_dim == H,
+ *             and the weight gradients (dw_hh ...).  Variant forward: 0, 1 projection fused; backward: 0, 1 dx fused, 2 and
+ *             dW_hh, db_hh, 3 and dW_ih, db_ih.
  *   CLUSTER   the conditions of STEP, and G2V_OPT_GRU_CLUSTER != 0, 2 <= T <= 2^20, ceil(B/16) * ceil(H/16) * ndir <= CUs, the
  *             kernel resident with a workgroup per CU: ONE launch for all steps.
- *   STEP      B <= 1024, ceil(B/16) * ndir <= 128, H % 4 == 0, H <= 256, and aligned forward gi, w_hh, b_hh, h0, gates, h_n,
- *             workspace; backward gates, dgi, dgh, d_hn, h0, dh0, workspace: one launch per time step.
+ *   STEP      B <= 1024, ceil(B/16) * ndir <= 128, H % 4 == 0, H <= 256, and aligned forward gi, w_hh, b_hh, h0, gates, h_n;
+ *             backward gates, dgi, dgh, d_hn, h0, dh0: one launch per time step.
  *   RESIDENT  W_hh kept in the CU.  Forward: 192 < H <= 208, B >= G2V_OPT_GRU_RESIDENT_ROWS > 0 and the vector conditions of STREAM.
  *             Backward: H == 200, B >= G2V_OPT_GRU_RESIDENT_ROWS > 0, G2V_OPT_GRU_RESIDENT_BWD != 0, the leading dimensions
  *             multiples of 4, aligned gates, dgi, dgh, hs, h0, dh0, d_hs, d_hn.
@@ -559,11 +564,14 @@ int g2v_cluster_exchange_preclear_drop(const void* workspace, size_t workspace_b
 #define G2V_GRU_PLAN_PREPARED 65536        /* the *_prepared entry points: FAST launches no pack */
 #define G2V_GRU_PLAN_SMALL_WORKSPACE 131072 /* workspace_bytes below the queried size */
 #define G2V_GRU_PLAN_NOT_RESIDENT 262144   /* the cluster kernel does not fit a CU */
+#define G2V_GRU_PLAN_FAST_UNALIGNED 524288  /* x, b_ih (forward) / dx, wslab (backward): FAST's list beyond the three above */
 int g2v_gru_seq_route(int backward, int T, int B, int H, int ndir, int cluster, int resident_rows, int resident_bwd, int cus, int facts);
 
 /* Up to 2 directions per call run in ONE launch (the two directions of a bidirectional layer are independent).  The workspace is
  * the largest of three regions: the fragment packs (per direction W_hh and W_ih), the per-step launches' state, the cluster
- * kernels' exchange records (which depend on the device's CU count). */
+ * kernels' exchange records (which depend on the device's CU count).  workspace: 16-byte aligned, whatever the route
+ * (G2V_ERR_ARG otherwise): the routes that use it move the packs, the state and the carry as 16-byte vectors, and no alignment
+ * list of the plan carries it. */
 size_t g2v_gru_seq_fwd_workspace(int ndir, int H);
 int g2v_gru_seq_fwd(const g2v_gru_dir* dirs, int ndir, const int32_t* lengths, int64_t hs_ld,
                     int T, int B, int H, void* workspace, size_t workspace_bytes, g2v_stream_t stream);

@@ -164,10 +164,11 @@ def cap_of(name):
     return CAP_FWD if name in FWD_ARRAYS else CAP_GRAD
 
 
-def check(label, name, got, ref, e32, skip_first=False):
+def check(label, name, got, ref, e32, skip_first=False, cap=None, steps_of=None):
     """print the worst step's e_kernel, e32, their ratio and the bound; return (ok, line, ratio).  The ratio is e_kernel over
-    max(e32, 2u), the quantity the margin multiplies.  skip_first: step 0 is not compared (dy: the header calls that row ignored)."""
-    ek, bd = step_err(got, ref, name), bound(e32, cap_of(name))
+    max(e32, 2u), the quantity the margin multiplies.  skip_first: step 0 is not compared (dy: the header calls that row ignored).
+    cap, steps_of: another operation's cap for `name` and the array of this file whose time axis it has (tests/_gru_ref.py)."""
+    ek, bd = step_err(got, ref, steps_of or name), bound(e32, cap_of(name) if cap is None else cap)
     if skip_first:
         ek, bd, e32 = ek[1:], bd[1:], e32[1:]
     k = int(torch.argmax(ek / bd))

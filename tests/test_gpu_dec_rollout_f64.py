@@ -72,6 +72,7 @@ import pytest
 import torch
 
 import _dec_ref as R
+from _dev_arrays import Arrays as _Arrays
 from _dec_route_shapes import DEC_F64_CASES, route_name as dec_route_name
 
 pytestmark = pytest.mark.gpu
@@ -102,27 +103,6 @@ def _bits(t):
 
 def _same(a, b):
     return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-class _Arrays:
-    """device arrays of one call: 16-byte aligned as torch hands them out, or every one of them 4 bytes (uint8: 1 byte) past a
-    16-byte boundary -- one element more is allocated and [1:] is passed"""
-
-    def __init__(self, unaligned):
-        self.off = 1 if unaligned else 0
-
-    def full(self, shape, value, dtype=torch.float32):
-        n = 1
-        for s in shape:
-            n *= s
-        t = torch.full((n + self.off,), value, dtype=dtype, device=DEV)[self.off:].view(*shape)
-        assert t.is_contiguous() and (t.data_ptr() % 16 != 0) == bool(self.off)
-        return t
-
-    def put(self, src):
-        t = self.full(tuple(src.shape), 0, src.dtype)
-        t.copy_(src)
-        return t
 
 
 def _forward(ops, case, inp, arr, running=True):

@@ -51,7 +51,7 @@ def test_route_table_names_every_constant_of_the_header_in_both_directions():
         other = {"GATHERED"} if backward else {"WGRAD_HH", "WGRAD_IH", "WGRAD_PARTIAL", "HN", "HN_UNUSABLE", "NO_DGI"}      # (the other entry point's fields)
         assert facts == set(GS.FACTS) - other
     assert len(GS.ROUTES) == 5 and sorted(GS.ROUTES.values()) == [1, 2, 3, 4, 5]
-    assert sorted(GS.FACTS.values()) == [1 << k for k in range(19)]
+    assert sorted(GS.FACTS.values()) == [1 << k for k in range(20)]
     routes = {(bool(c.get("backward")), c["route"]) for c in GS.GRU_ROUTE_SHAPES}
     assert routes >= {(False, "FAST"), (False, "FAST*1"), (False, "STREAM"), (False, "STREAM*1"), (False, "STREAM*2"), (False, ""),
                       (True, "FAST"), (True, "FAST*1"), (True, "FAST*2"), (True, "FAST*3"), (True, "STREAM"), (True, "STREAM*1"), (True, "")}
