@@ -4,9 +4,7 @@
 //
 // One wave (a workgroup of 64 threads) owns one series n and DTW_G = 64 / P centres, P the power of two >= max(S, 16): lane l holds
 // column j = l % P of centre g = l / P.  dtw_fill:
-//   cost     the columns are walked in chunks of DTW_FC: the lane keeps its DTW_FC centre values in registers, the wave's T x DTW_FC
-//            slice of the series stands in LDS as fp32 and is read as a broadcast, and tile[i][l] (T x 64 float64 in LDS) gains
-//            sum_f (a_if - b_jf)^2, two rows i at a time, each term fused into the running sum (one rounding per term, f ascending)
+//   cost     dtw_cost_tile (dtw_tile.hpp, shared with softdtw.hip): tile[i][l] (T x 64 float64 in LDS) = sum_f (a_if - b_jf)^2
 //   sweep    the T + S - 1 anti-diagonals in order: lane j takes cell (d - j, j).  acc(i-1, j) is the lane's own last value,
 //            acc(i, j-1) the left neighbour's last value (one __shfl_up), acc(i-1, j-1) the one it sent a diagonal earlier; lanes
 //            outside the tile hold +inf, and a lane with j == 0 reads +inf, so groups do not leak into each other.  The lane that
@@ -16,7 +14,7 @@
 // of bank conflicts, and the cost phase's are consecutive.
 //
 //   dtw_pair_kernel    one workgroup per (n, group of G centres), the groups of one series next to each other: d2[n][m]
-//   dtw_argmin_kernel  one wave per n: out[n][:] = d2 or sqrt(d2), labels[n], best[n]; (value, index) lexicographic, lowest index
+//   dtw_argmin_kernel  (dtw_tile.hpp) one wave per n: out[n][:] = d2 or sqrt(d2), labels[n], best[n]; (value, index) lexicographic, lowest index
 //   dtw_path_kernel    one wave per member n of a live cluster k: the tile of (x_n, c_k), one lane walks the moves back from
 //                      (T-1, S-1) and notes, per centre row s, the range [lo, hi] of series rows matched with it (a warping path is
 //                      monotone: the rows matched with one s are consecutive) -> span[n][s] (2 bytes), d2row[n]
@@ -28,24 +26,15 @@
 //   dtw_update_kernel  one workgroup per cluster: centres = sums / counts, then the stop rule on the device
 // No floating-point atomics.
 #include "common.hpp"
+#include "dtw_tile.hpp"
 #include "km_sort.hpp"
 
 namespace g2v {
 namespace {
 
-constexpr int DTW_MAX_LEN = 64;
-constexpr int DTW_MAX_F = 512;
-constexpr int DTW_FC = 32;                  // columns per chunk: the lane's registers, the series slice in LDS
 constexpr int DTW_SLAB = 128;               // members of one cluster per partial sum
 // the header's moves in its order, the centre being its first index: both step back, the centre steps back, the series steps back
 enum { DTW_DIAG = 0, DTW_CENTRE = 1, DTW_SERIES = 2 };
-
-inline bool dtw_shape_ok(int64_t N, int64_t M, int T, int S, int F) {
-  return N >= 1 && M >= 1 && N <= 0x7fffffff && M <= 0x7fffffff && T >= 1 && S >= 1 && T <= DTW_MAX_LEN && S <= DTW_MAX_LEN && F >= 1 &&
-         F <= DTW_MAX_F;
-}
-inline int dtw_group_width(int S) { return S <= 16 ? 16 : (S <= 32 ? 32 : 64); }
-inline size_t dtw_lds_bytes(int T) { return (size_t)T * 64 * sizeof(double) + (size_t)T * DTW_FC * sizeof(float); }
 
 struct DtwLayout {
   int nb;                  // sort blocks
@@ -84,38 +73,7 @@ __device__ __forceinline__ double dtw_fill(const float* __restrict__ a, const do
   double* tile = reinterpret_cast<double*>(lds);
   float* as = reinterpret_cast<float*>(lds + (size_t)T * 64 * sizeof(double));
   const int lane = threadIdx.x;
-  for (int i = 0; i < T; ++i) tile[i * 64 + lane] = 0.0;
-  for (int f0 = 0; f0 < F; f0 += DTW_FC) {
-    __syncthreads();                                         // (the slice of the chunk before is read no more)
-    for (int e = lane; e < T * DTW_FC; e += 64) {
-      const int i = e / DTW_FC, f = f0 + (e % DTW_FC);
-      as[e] = f < F ? a[(size_t)i * F + f] : 0.f;
-    }
-    double bv[DTW_FC];
-#pragma unroll
-    for (int f = 0; f < DTW_FC; ++f) bv[f] = (active && f0 + f < F) ? b[f0 + f] : 0.0;     // past F both sides are 0: the term is +0
-    __syncthreads();
-    for (int i = 0; i < T; i += 2) {
-      const int i1 = min(i + 1, T - 1);
-      double s0 = tile[i * 64 + lane], s1 = tile[i1 * 64 + lane];
-      const float4* r0 = reinterpret_cast<const float4*>(as + i * DTW_FC);
-      const float4* r1 = reinterpret_cast<const float4*>(as + i1 * DTW_FC);
-#pragma unroll
-      for (int q = 0; q < DTW_FC / 4; ++q) {
-        const float4 u = r0[q], v = r1[q];
-        const double u4[4] = {u.x, u.y, u.z, u.w}, v4[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const double d0 = u4[e] - bv[4 * q + e], d1 = v4[e] - bv[4 * q + e];
-          s0 = fma(d0, d0, s0);
-          s1 = fma(d1, d1, s1);
-        }
-      }
-      tile[i * 64 + lane] = s0;
-      if (i + 1 < T) tile[i1 * 64 + lane] = s1;
-    }
-  }
-  __syncthreads();
+  dtw_cost_tile(a, b, active, T, F, tile, as);
   unsigned char* moves = reinterpret_cast<unsigned char*>(as);
   const double inf = (double)__builtin_inff();
   double cur = inf, left = inf;
@@ -192,39 +150,6 @@ __global__ __launch_bounds__(64) void dtw_path_kernel(const float* __restrict__ 
   if (lane < S) {
     span[((size_t)n * S + lane) * 2] = lo[lane];
     span[((size_t)n * S + lane) * 2 + 1] = hi[lane];
-  }
-}
-
-__global__ __launch_bounds__(256) void dtw_argmin_kernel(const double* __restrict__ d2, int64_t N, int64_t M, int squared,
-                                                        double* __restrict__ out, int64_t* __restrict__ labels,
-                                                        double* __restrict__ best) {
-  const int lane = threadIdx.x & 63;
-  const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (n >= N) return;                                        // (wave-uniform)
-  const double* row = d2 + n * M;
-  double bv = (double)__builtin_inff();
-  int64_t bm = -1;
-  for (int64_t m = lane; m < M; m += 64) {
-    const double v = row[m];
-    if (out) out[n * M + m] = squared ? v : sqrt(v);
-    if (bm < 0 || v < bv) {
-      bv = v;
-      bm = m;
-    }
-  }
-  if (!labels) return;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {                         // (value, index) in lexicographic order: ties to the lowest index
-    const double ob = __shfl_xor(bv, o);
-    const int64_t om = __shfl_xor(bm, o);
-    if (om >= 0 && (bm < 0 || ob < bv || (ob == bv && om < bm))) {
-      bv = ob;
-      bm = om;
-    }
-  }
-  if (lane == 0) {
-    labels[n] = bm;
-    best[n] = bv;
   }
 }
 

@@ -1591,6 +1591,70 @@ def dtw_dba_update(acc, members, state, centers, tol):
     return centers
 
 
+# ------------------------------------------------------------------------------------------ soft-DTW (softdtw.hip)
+def softdtw_workspace(N, M, T, S, F) -> int:
+    """bytes of workspace of softdtw_cdist over N series and M centres, or of softdtw_grad over N member rows (M = 1); 0 for a shape
+    they refuse"""
+    return int(_lib_().g2v_softdtw_workspace(int(N), int(M), int(T), int(S), int(F)))
+
+
+def _softdtw_ws(N, M, T, S, F, device):
+    nb = softdtw_workspace(N, M, T, S, F)
+    return workspace(max(nb, 16), device, "softdtw"), nb
+
+
+def softdtw_cdist(x, y, gamma, *, want_out=True, want_labels=False):
+    """x (N, T, F) fp32 series, y (M, S, F) float64 centres -> (out, labels, best) (g2v_softdtw_cdist): out (N, M) float64 =
+    sdtw_gamma(y_m, x_n) (None without want_out); labels (N) int64 = the argmin over the centres, lowest index on ties, best (N)
+    float64 = the minimal value (None without want_labels)."""
+    N, T, M, S, F = _dtw_operands(x, y, "softdtw_cdist")
+    if not (want_out or want_labels):
+        raise ValueError("softdtw_cdist: nothing asked for")
+    dev = x.device
+    out = torch.empty((N, M), dtype=torch.float64, device=dev) if want_out else None
+    labels = torch.empty((N,), dtype=torch.int64, device=dev) if want_labels else None
+    best = torch.empty((N,), dtype=torch.float64, device=dev) if want_labels else None
+    ws, nb = _softdtw_ws(N, M, T, S, F, dev)
+    check(_lib_().g2v_softdtw_cdist(_p(x), N, T, _p(y), M, S, F, float(gamma), _p(out), _p(labels), _p(best), _p(ws), nb, _stream()),
+          "softdtw_cdist")
+    return out, labels, best
+
+
+def softdtw_alignment(x, z, gamma):
+    """x (R, T, F) fp32 rows, z (S, F) float64: one centre -> (E (R, S, T) float64: the soft alignment matrix of every row, value (R)
+    float64 = sdtw_gamma(z, x_r)) (g2v_softdtw_alignment)"""
+    R, T, _, S, F = _dtw_operands(x, z[None] if z.dim() == 2 else z, "softdtw_alignment")
+    if z.dim() != 2:
+        raise TypeError("softdtw_alignment: the centre must be a (S, F) float64 tensor")
+    E = torch.empty((R, S, T), dtype=torch.float64, device=x.device)
+    value = torch.empty((R,), dtype=torch.float64, device=x.device)
+    check(_lib_().g2v_softdtw_alignment(_p(x), R, T, _p(z), S, F, float(gamma), _p(value), _p(E), _stream()), "softdtw_alignment")
+    return E, value
+
+
+def softdtw_grad(x, rows, z, gamma, weights=None, out=None):
+    """One evaluation of a barycentre objective (g2v_softdtw_grad): x (N, T, F) fp32, rows (R) int64 on the device, ascending member
+    row ids, z (S, F) float64, weights (R) float64 or None (all ones) -> (value (1), grad (S, F)): views of one float64 tensor of
+    1 + S F elements, `out` when given, so that both reach the host in one copy."""
+    N, T, _, S, F = _dtw_operands(x, z[None] if z.dim() == 2 else z, "softdtw_grad")
+    if z.dim() != 2:
+        raise TypeError("softdtw_grad: the centre must be a (S, F) float64 tensor")
+    R = _chk(rows, torch.int64, "rows").numel()
+    if rows.dim() != 1 or R < 1:
+        raise ValueError(f"softdtw_grad: rows must be a non-empty 1-D tensor, got {tuple(rows.shape)}")
+    if weights is not None and tuple(_chk(weights, torch.float64, "weights").shape) != (R,):
+        raise ValueError(f"softdtw_grad: weights must be ({R},), got {tuple(weights.shape)}")
+    if out is None:
+        out = torch.empty((1 + S * F,), dtype=torch.float64, device=x.device)
+    if tuple(_chk(out, torch.float64, "out").shape) != (1 + S * F,):
+        raise ValueError(f"softdtw_grad: out must be ({1 + S * F},) float64")
+    value, grad = out[:1], out[1:].view(S, F)
+    ws, nb = _softdtw_ws(R, 1, T, S, F, x.device)
+    check(_lib_().g2v_softdtw_grad(_p(x), N, T, _p(rows), R, _p(weights), _p(z), S, F, float(gamma), _p(value), _p(grad), _p(ws), nb,
+                                   _stream()), "softdtw_grad")
+    return value, grad
+
+
 # ------------------------------------------------------------------------------------------ exact t-SNE (tsne.hip)
 def tsne_max_rows() -> int:
     return int(_lib_().g2v_tsne_max_rows())

@@ -1628,6 +1628,52 @@ int g2v_dtw_dba_accumulate(const float* x, int64_t N, int T, const int64_t* labe
 int g2v_dtw_dba_update(const double* sums, const int64_t* counts, const double* cost, const int64_t* members, void* state,
                        double* centers, int K, int S, int F, double tol, g2v_stream_t stream);
 
+/* ---- Soft-DTW over chunk sequences (softdtw.hip; gesture2vec_amd/timeseries.py) ------------------------------------------------------
+ * The reference's third time-series branch (Clustering.py:670-691, tslearn's TimeSeriesKMeans(metric="softdtw")): the differentiable
+ * DTW of Cuturi & Blondel (2017), its soft alignment matrix, and value and gradient of a barycentre objective.  tslearn is not a
+ * dependency and no run of it stands behind this block: the algorithm is stated here, from tslearn's definition, and tested against
+ * a float64 restatement (tests/_softdtw_ref.py).  Everything is float64.
+ *   Operands.  Series x: fp32 (N, T, F), contiguous.  A centre or second operand z: float64 (S, F), contiguous.  gamma > 0.
+ *   Cost.  cost(i, j) = sum_f (z_if - x_jf)^2, formed exactly as the DTW block forms it (from differences, f ascending, each term
+ *     fused into the running sum; one piece of code, csrc/dtw_tile.hpp).  Not tslearn's Gram form: the two differ by rounding only.
+ *   Forward.  R(i, j) = cost(i, j) + softmin(R(i-1, j), R(i-1, j-1), R(i, j-1)); R(0, 0) = cost(0, 0); absent predecessors contribute
+ *     nothing.  softmin(a, b, c) = -gamma (log(e^(a'-m) + e^(b'-m) + e^(c'-m)) + m), a' = -a / gamma and so on, m = max(a', b', c').
+ *     sdtw(z, x) = R(S-1, T-1).  It can be negative.
+ *   Backward.  E(S-1, T-1) = 1, otherwise E(i, j) = E(i+1, j) a + E(i, j+1) b + E(i+1, j+1) c with
+ *     a = exp((R(i+1, j) - R(i, j) - cost(i+1, j)) / gamma), b = exp((R(i, j+1) - R(i, j) - cost(i, j+1)) / gamma),
+ *     c = exp((R(i+1, j+1) - R(i, j) - cost(i+1, j+1)) / gamma); a term whose successor lies outside the tile is 0.  Each of a, b, c
+ *     lies in (0, 1], and so does E (up to rounding).  E is tslearn's soft_dtw_alignment.
+ *   Objective of a barycentre z over member rows with weights w_n (all ones when absent, not normalised):
+ *     obj(z) = sum_n w_n sdtw(z, x_n),  G[i][f] = 2 (z_if sum_n w_n sum_j E_n(i, j) - sum_n w_n sum_j E_n(i, j) x_njf).
+ *   softdtw_barycenter(X, gamma, weights, max_iter, tol = 1e-3, init) = scipy.optimize.minimize(f, init.ravel(), method="L-BFGS-B",
+ *     jac=True, tol=tol, options=dict(maxiter=max_iter, disp=False)).x on the host, f = (obj, G) from the device; init = None starts
+ *     from the weighted Euclidean mean (equal lengths only); max_iter == 0 returns the init.
+ *   k-means loop (tslearn's TimeSeriesKMeans(metric="softdtw")).  Centres start as the init rows.  For it in range(max_iter):
+ *     labels = argmin_k sdtw(c_k, x_n), lowest index on ties; inertia = the mean of the minimal soft-DTW values (not squared, not the
+ *     DTW inertia); an empty cluster raises, or redraws with init="random"; every cluster becomes softdtw_barycenter(members, gamma,
+ *     max_iter=max_iter_barycenter, init=its current centre); stop after the update if |old - inertia| < tol.  labels_ and inertia_
+ *     are those of the last assignment; predict uses the final centres.
+ * Supported: the DTW limits, 1 <= T, S <= g2v_dtw_max_len() and 1 <= F <= 512; beyond, G2V_ERR_UNSUPPORTED before any launch.  gamma
+ * that is not finite or not > 0: G2V_ERR_ARG.  exp of a very negative argument underflows to 0; no NaN arises from finite inputs.
+ * No floating-point atomics, independent workgroups only: the same input gives the same bits on every call.
+ *
+ * g2v_softdtw_workspace(N, M, T, S, F): bytes for any call below over N rows (for g2v_softdtw_grad: R member rows) and M centres (1
+ *   for g2v_softdtw_grad); 0 for an unsupported shape; 16-byte aligned, not trusted across calls.
+ * g2v_softdtw_cdist: out double (N, M) = sdtw(y_m, x_n); may be NULL.  labels int64[N] = the argmin over m, the lowest index on
+ *   ties; best double[N] = the minimal value; NULL together.
+ * g2v_softdtw_alignment: every row of x (R, T, F) against the one centre z -> value double[R] = sdtw(z, x_r), E double (R, S, T).
+ * g2v_softdtw_grad: one evaluation of (obj, G) for the centre z over the member rows x[rows[r]], r < R: rows int64[R] on the device,
+ *   ascending row ids in [0, N) (an id outside contributes nothing); weights double[R] on the device, or NULL for all ones ->
+ *   value double[1], grad double (S, F).  Per (i, f) the members' sums over j (j ascending) are added in the order of `rows`, in
+ *   slabs of a fixed number of members that are folded in slab order: the order of every sum is a function of `rows` alone. */
+size_t g2v_softdtw_workspace(int64_t N, int64_t M, int T, int S, int F);
+int g2v_softdtw_cdist(const float* x, int64_t N, int T, const double* y, int64_t M, int S, int F, double gamma, double* out,
+                      int64_t* labels, double* best, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+int g2v_softdtw_alignment(const float* x, int64_t R, int T, const double* z, int S, int F, double gamma, double* value, double* E,
+                          g2v_stream_t stream);
+int g2v_softdtw_grad(const float* x, int64_t N, int T, const int64_t* rows, int64_t R, const double* weights, const double* z, int S,
+                     int F, double gamma, double* value, double* grad, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

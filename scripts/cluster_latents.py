@@ -9,6 +9,8 @@
                               --distance-threshold T] [--scan-k 50:400:50]
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm dtw --n_clusters 40 --max_iter 5
                               --max-iter-barycenter 5
+    python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm softdtw --gamma 0.5 --n_clusters 40
+                              --max_iter 5 --max-iter-barycenter 5
 
 `--chunks` holds (N, T, D) pose chunks in the autoencoder's input space.  Their latents (`chunk_latents`) are clustered with
 `KMeans(n_clusters, max_iter=2500, random_state=0)` and the model is pickled to `<checkpoint dir>/clusters/kmeans_model.pk`, where the
@@ -30,7 +32,10 @@ fitted once and the silhouette coefficient of `cut(k)` is printed per k; `(k, si
 own call is `--n_clusters 40 --max_iter 5 --max-iter-barycenter 5`) on the device (gesture2vec_amd/timeseries.py), with
 `--n_clusters`, `--max_iter`, `--n_init`, `--seed` and `--max-iter-barycenter`.  `--checkpoint` only names the default output directory
 then.  `n_iter`, inertia and the usage perplexity are printed and the model is pickled to `<checkpoint dir>/clusters/dtw_kmeans_model.pk`
-or `--out`."""
+or `--out`.
+`--algorithm softdtw` is the same under soft-DTW: the reference's `TimeSeriesKMeans(n_clusters=40, metric="softdtw", max_iter=5,
+max_iter_barycenter=5, metric_params={"gamma": 0.5}, random_state=0)` (`Clustering.py:670-691`) as `SoftDTWKMeans` with `--gamma`;
+the model is pickled to `<checkpoint dir>/clusters/softdtw_kmeans_model.pk` or `--out`."""
 from __future__ import annotations
 
 import argparse
@@ -52,7 +57,7 @@ from gesture2vec_amd.agglomerative import AgglomerativeClustering  # noqa: E402
 from gesture2vec_amd.dbscan import DBSCAN  # noqa: E402
 from gesture2vec_amd.kmeans import KMeans  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents  # noqa: E402
-from gesture2vec_amd.timeseries import TimeSeriesKMeans  # noqa: E402
+from gesture2vec_amd.timeseries import SoftDTWKMeans, TimeSeriesKMeans  # noqa: E402
 
 
 SILHOUETTE_ROWS = 65536        # latents beyond this many are sampled for the silhouette coefficient
@@ -76,14 +81,15 @@ def main(argv=None):
     ap.add_argument("--silhouette-rows", dest="silhouette_rows", type=int, default=None,
                     help="rows the silhouette is sampled over (default: all rows up to 65536, that many sampled beyond)")
     ap.add_argument("--no-silhouette", dest="silhouette", action="store_false", help="do not compute silhouette coefficients")
-    ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk; dbscan: the .npz of labels, dbscan_labels.npz there; ward: ward_labels.npz there; dtw: dtw_kmeans_model.pk there)")
-    ap.add_argument("--algorithm", choices=("kmeans", "dbscan", "ward", "dtw"), default="kmeans",
+    ap.add_argument("--out", default=None, help="model path (default: <checkpoint dir>/clusters/kmeans_model.pk; dbscan: the .npz of labels, dbscan_labels.npz there; ward: ward_labels.npz there; dtw: dtw_kmeans_model.pk there; softdtw: softdtw_kmeans_model.pk there)")
+    ap.add_argument("--algorithm", choices=("kmeans", "dbscan", "ward", "dtw", "softdtw"), default="kmeans",
                     help="the branch of the reference's clustering switch: {kmeans,dbscan} as before, or ward = "
                          "AgglomerativeClustering(linkage='ward') cut at --n_clusters or --distance-threshold; "
-                         "{kmeans,dbscan,ward} cluster the chunks' latents, dtw = TimeSeriesKMeans(metric='dtw') the chunk "
-                         "sequences themselves")
+                         "{kmeans,dbscan,ward} cluster the chunks' latents, dtw = TimeSeriesKMeans(metric='dtw') and softdtw = "
+                         "SoftDTWKMeans(gamma) the chunk sequences themselves")
     ap.add_argument("--max-iter-barycenter", dest="max_iter_barycenter", type=int, default=5,
-                    help="dtw: barycentre averaging steps per cluster and iteration")
+                    help="dtw: barycentre averaging steps per cluster and iteration; softdtw: L-BFGS-B iterations per barycentre")
+    ap.add_argument("--gamma", type=float, default=0.5, help="softdtw: the temperature of the soft minimum")
     ap.add_argument("--distance-threshold", dest="distance_threshold", type=float, default=None,
                     help="ward: cut the tree below this merge height instead of at --n_clusters")
     ap.add_argument("--eps", type=float, default=0.5, help="dbscan: the neighbourhood radius")
@@ -92,12 +98,13 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     dev = torch.device(a.device)
-    if a.algorithm == "dtw":                                     # the sequences themselves: no encoder pass, the checkpoint is not read
+    if a.algorithm in ("dtw", "softdtw"):                        # the sequences themselves: no encoder pass, the checkpoint is not read
         chunks = torch.from_numpy(np.load(a.chunks).astype(np.float32, copy=False)).to(dev)
         print(f"sequences: {tuple(chunks.shape)}")
-        ts = TimeSeriesKMeans(n_clusters=a.n_clusters, max_iter=a.max_iter, n_init=a.n_init, random_state=a.seed,
-                              max_iter_barycenter=a.max_iter_barycenter).fit(chunks)
-        out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "clusters", "dtw_kmeans_model.pk")
+        common = dict(n_clusters=a.n_clusters, max_iter=a.max_iter, n_init=a.n_init, random_state=a.seed,
+                      max_iter_barycenter=a.max_iter_barycenter)
+        ts = (TimeSeriesKMeans(**common) if a.algorithm == "dtw" else SoftDTWKMeans(gamma=a.gamma, **common)).fit(chunks)
+        out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "clusters", a.algorithm + "_kmeans_model.pk")
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "wb") as f:
             pickle.dump(ts, f)
