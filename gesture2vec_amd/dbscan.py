@@ -13,7 +13,7 @@ smallest id among its core neighbours, or -1.  `fit` is three kinds of calls (cs
                            enqueued per read-back of the flags
     ops.dbscan_labels      ranks of the roots, labels, the core mask, the three counts
 
-The same input gives the same bits."""
+The same input gives the same bits.  `k_distances(x, k)` is the sorted k-distance curve `eps` is usually read from."""
 from __future__ import annotations
 
 import numpy as np
@@ -30,6 +30,17 @@ def check_rows(N: int, what: str = "DBSCAN") -> None:
     limit = ops.dbscan_max_rows()
     if N > limit:
         raise ValueError(f"{what}: {N} rows exceed the limit of {limit} (the adjacency bitmap takes N^2 / 8 bytes, 2 GiB at the limit)")
+
+
+@torch.no_grad()
+def k_distances(x: torch.Tensor, k) -> torch.Tensor:
+    """The curve one reads `eps` from: the distance from each row of x (N, E) to its k-th nearest row COUNTING ITSELF, which is how
+    DBSCAN counts `min_samples` (k = 1 gives zeros), sorted ascending -> (N,) fp32 on the device.  `embedding.kneighbors` with the
+    rows as their own queries (exact neighbours, the N x N distances never stored) and one sort.  k <= min(N, 127)."""
+    from .embedding import kneighbors
+    _need_cuda(x, "k_distances")
+    dist, _ = kneighbors(x, k, queries=x)
+    return dist[:, int(k) - 1].sort().values
 
 
 class DBSCAN:

@@ -13,6 +13,9 @@ latents coloured by code (`Clustering.py:1046-1056`, `:1411-1417`).  Arguments, 
   stated exactly in DESIGN 3.5e (csrc/tsne_place.hip: exact neighbours among the fitted rows, their conditionals, a median start,
   then a per-row descent against the fixed map in one launch).  Every row is placed on its own, so a set of any size can be placed
   against an exactly fitted sample.  `LatentMap` is the reference's `(pca, MyTSNE)` pair as one picklable object.
+* `trustworthiness`, `continuity`, `map_quality`, `placement_quality`, `LatentMap.quality`: how far a map can be believed, by
+  sklearn's `trustworthiness` both ways round, at any number of rows (csrc/map_quality.hip ranks the neighbours of one space
+  among all rows of the other without forming a distance matrix); `kneighbors` is the exact neighbour search they share.
 
 Out of scope: numerical parity with openTSNE, Barnes-Hut / FFT approximations, 3-D maps, plots."""
 from __future__ import annotations
@@ -358,6 +361,174 @@ class LatentMap:
         if rest.numel():
             coords[rest] = self.transform(latents[rest].contiguous(), **place_kw)
         return coords, fitted
+
+
+    @torch.no_grad()
+    def quality(self, latents: torch.Tensor, coords: torch.Tensor, sample_idx=None, **kw) -> dict:
+        """How faithful is the map `coords` (N, 2) of `latents` (N, E), as `fit_all` returns it?  -> {"fitted": `map_quality` of the
+        rows `sample_idx` (default `rows_`, the rows the map was fitted on), "placed": `placement_quality` of every other row
+        against them, or None where there is none}, each with `rows`: the rows of `latents` its penalties belong to, in their
+        order.  The high-dimensional space is the one the map was made from: the PCA scores.  `kw`: n_neighbors."""
+        if self.coords_ is None:
+            raise ValueError("LatentMap.quality: not fitted")
+        latents, coords = _rows(latents, "LatentMap.quality"), _rows(coords, "LatentMap.quality")
+        N = latents.shape[0]
+        if tuple(coords.shape) != (N, 2):
+            raise ValueError(f"LatentMap.quality: coords must be ({N}, 2), got {tuple(coords.shape)}")
+        idx = self.rows_ if sample_idx is None else torch.as_tensor(sample_idx, dtype=torch.int64)
+        idx = idx.to(latents.device)
+        scores = self.pca.transform(latents)
+        placed = torch.ones((N,), dtype=torch.bool, device=latents.device)
+        placed[idx] = False
+        rest = placed.nonzero().flatten()
+        # (the rows the map was fitted on are kept: the very bits its neighbours were taken from)
+        xs = self.tsne.fit_rows_.to(latents.device) if sample_idx is None else scores[idx].contiguous()
+        ys = coords[idx].contiguous()
+        out = {"fitted": dict(map_quality(xs, ys, **kw), rows=idx), "placed": None}
+        if rest.numel():
+            out["placed"] = dict(placement_quality(xs, ys, scores[rest].contiguous(), coords[rest].contiguous(), **kw), rows=rest)
+        return out
+
+
+# ---- how faithful a map is: trustworthiness and continuity (csrc/map_quality.hip) ---------------------------------------------------
+# sklearn.manifold.trustworthiness (sklearn 1.7, Euclidean) without its two N x N float64 matrices and their argsorts: the k nearest
+# other rows in one space (ops.tsne_place_neighbors, exact, never storing the distances) are ranked among all rows of the other
+# space (ops.neighbor_ranks).  With r_X(i, j) the rank of j among the rows other than i by ascending X-distance to i (nearest: 1,
+# ties to the lower index) and N_k^Y(i) the k nearest other rows of i in the map:
+#   p_T(i) = sum_{j in N_k^Y(i)} max(0, r_X(i, j) - k)        trustworthiness = 1 - 2 / (N k (2 N - 3 k - 1)) sum_i p_T(i)
+# continuity is the same with X and Y swapped.  The penalties are integers and are summed as int64 on the device.
+_MAX_K = 127
+
+
+def _check_k(what, n_neighbors, N, half=True):
+    k = int(n_neighbors)
+    if k != n_neighbors or k < 1:
+        raise ValueError(f"{what}: n_neighbors must be a positive integer, got {n_neighbors!r}")
+    if half and k >= N / 2:
+        raise ValueError(f"{what}: n_neighbors ({k}) should be less than n_samples / 2 ({N / 2})")
+    if k > _MAX_K:
+        raise ValueError(f"{what}: n_neighbors ({k}) exceeds {_MAX_K}, the most the kernels rank per row")
+    return k
+
+
+def _pair(X, Y, what):
+    if not torch.is_tensor(X) or not torch.is_tensor(Y) or X.dim() != 2 or Y.dim() != 2 or X.shape[0] != Y.shape[0]:
+        raise ValueError(f"{what}: X (N, d) and Y (N, c) must be tensors with the same number of rows")
+    return X.shape[0]
+
+
+def _score(total, rows, N, k):
+    """sklearn's closing expression, in float64, from the integer sum of the penalties"""
+    return 1.0 - float(total) * (2.0 / (rows * k * (2.0 * N - 3.0 * k - 1.0)))
+
+
+@torch.no_grad()
+def kneighbors(x: torch.Tensor, k, queries=None, return_distance=True):
+    """The k nearest rows of x (N, d) under ascending (d^2, index), exactly (ops.tsne_place_neighbors: the distances are selected
+    from as they are formed and never stored) -> (distances (M, k) fp32, indices (M, k) int32) on the device, or the indices alone.
+    `queries` (M, d): the neighbours of those rows among x.  Without it every row of x is asked for its k nearest OTHER rows: k + 1
+    are found and the row itself is taken out; where it is not among them (more than k bitwise duplicates with lower indices
+    precede it) the last entry is.  Distances are the square roots of the correctly rounded d^2.  k <= 127."""
+    from . import ops
+    x = _rows(x, "kneighbors")
+    N, k = x.shape[0], int(k)
+    own = queries is None
+    if not 1 <= k <= min(N - 1 if own else N, _MAX_K):
+        raise ValueError(f"kneighbors: k ({k}) must be in [1, min({'N - 1' if own else 'N'}, {_MAX_K})] (N = {N})")
+    ref = _pitch4(x)
+    if own:
+        idx, d2 = ops.tsne_place_neighbors(ref, ref, k + 1)
+        me = torch.arange(N, dtype=torch.int32, device=x.device)[:, None]
+        hit = idx == me
+        drop = torch.where(hit.any(dim=1), hit.to(torch.int8).argmax(dim=1), torch.full_like(hit[:, 0], k, dtype=torch.int64))
+        keep = torch.arange(k + 1, device=x.device)[None, :] != drop[:, None]
+        idx, d2 = idx[keep].view(N, k), d2[keep].view(N, k)
+    else:
+        q = _rows(queries, "kneighbors")
+        if q.shape[1] != x.shape[1]:
+            raise ValueError(f"kneighbors: x has {x.shape[1]} columns and queries {q.shape[1]}")
+        idx, d2 = ops.tsne_place_neighbors(ref, _pitch4(q), k)
+    return (d2.sqrt(), idx) if return_distance else idx
+
+
+def _penalties(rank_space, pick_space, k):
+    """-> (penalty (N,) int64, redecided (1,) int64): neighbours picked in one space, ranked in the other, over the same rows"""
+    from . import ops
+    idx = kneighbors(pick_space, k, return_distance=False)
+    rows = _pitch4(rank_space)
+    me = torch.arange(rows.shape[0], dtype=torch.int64, device=rows.device)
+    rank, redo = ops.neighbor_ranks(rows, rows, idx, me)
+    return (rank.to(torch.int64) - k).clamp_(min=0).sum(dim=1), redo
+
+
+def _placed_penalties(rank_ref, rank_new, pick_ref, pick_new, k):
+    """the same for new rows against a fitted set: picked among pick_ref, ranked among rank_ref, no row left out"""
+    from . import ops
+    idx = kneighbors(pick_ref, k, queries=pick_new, return_distance=False)
+    rank, redo = ops.neighbor_ranks(_pitch4(rank_ref), _pitch4(rank_new), idx, None)
+    return (rank.to(torch.int64) - k).clamp_(min=0).sum(dim=1), redo
+
+
+def _quality(pen_t, redo_t, pen_c, redo_c, rows, N, k):
+    sums = torch.stack([pen_t.sum(), pen_c.sum(), (redo_t + redo_c)[0]]).cpu().numpy()       # the one read-back
+    return {"trustworthiness": _score(int(sums[0]), rows, N, k), "continuity": _score(int(sums[1]), rows, N, k),
+            "penalty_t": pen_t, "penalty_c": pen_c, "n_neighbors": k, "redecided": int(sums[2])}
+
+
+@torch.no_grad()
+def map_quality(X: torch.Tensor, Y: torch.Tensor, n_neighbors=5, sample_size=None, random_state=None) -> dict:
+    """Both scores of the map Y (N, c) of the rows X (N, d), fp32 on the device -> {"trustworthiness", "continuity" (floats),
+    "penalty_t", "penalty_c" ((N,) int64 on the device: each row's share, so the badly mapped rows can be found), "n_neighbors",
+    "redecided" (the pairs the kernel decided again in float64)}.  `sample_size` / `random_state` score the sub-map of the rows
+    `RandomState(random_state).permutation(N)[:sample_size]`, as `silhouette_score` draws them."""
+    N = _pair(X, Y, "map_quality")
+    if sample_size is not None:
+        N = min(N, int(sample_size))
+    k = _check_k("map_quality", n_neighbors, N)
+    X, Y = _rows(X, "map_quality"), _rows(Y, "map_quality")
+    if sample_size is not None:
+        idx = torch.from_numpy(_rng(random_state).permutation(X.shape[0])[:int(sample_size)].astype(np.int64)).to(X.device)
+        X, Y = X[idx].contiguous(), Y[idx].contiguous()            # a gather: layout only
+    pen_t, redo_t = _penalties(X, Y, k)
+    pen_c, redo_c = _penalties(Y, X, k)
+    return _quality(pen_t, redo_t, pen_c, redo_c, N, N, k)
+
+
+@torch.no_grad()
+def trustworthiness(X: torch.Tensor, Y: torch.Tensor, *, n_neighbors=5, metric="euclidean") -> float:
+    """`sklearn.manifold.trustworthiness(X, X_embedded, n_neighbors=5, metric="euclidean")` for fp32 rows on the device: to what
+    extent the map's neighbourhoods are neighbourhoods of X."""
+    if metric != "euclidean":
+        raise ValueError(f"trustworthiness: metric must be 'euclidean', got {metric!r}")
+    N = _pair(X, Y, "trustworthiness")
+    k = _check_k("trustworthiness", n_neighbors, N)
+    pen, _ = _penalties(_rows(X, "trustworthiness"), _rows(Y, "trustworthiness"), k)
+    return _score(int(pen.sum().item()), N, N, k)
+
+
+@torch.no_grad()
+def continuity(X: torch.Tensor, Y: torch.Tensor, *, n_neighbors=5) -> float:
+    """Trustworthiness the other way round: to what extent the neighbourhoods of X stay neighbourhoods in the map."""
+    N = _pair(X, Y, "continuity")
+    k = _check_k("continuity", n_neighbors, N)
+    pen, _ = _penalties(_rows(Y, "continuity"), _rows(X, "continuity"), k)
+    return _score(int(pen.sum().item()), N, N, k)
+
+
+@torch.no_grad()
+def placement_quality(X_ref: torch.Tensor, Y_ref: torch.Tensor, Z: torch.Tensor, y: torch.Tensor, n_neighbors=5) -> dict:
+    """The same two scores for M rows Z (M, d) placed at y (M, c) against a fitted set X_ref (N, d) with the map Y_ref (N, c)
+    (`TSNE.transform`): every neighbour and every rank is among the N fitted rows, none is left out, and the sums are normalised by
+    M k (2 N - 3 k - 1) / 2.  Trustworthiness: the map-neighbours of y among Y_ref, ranked by distance from Z among X_ref;
+    continuity the other way round.  -> the dict of `map_quality`, the penalties (M,)."""
+    N, M = _pair(X_ref, Y_ref, "placement_quality"), _pair(Z, y, "placement_quality")
+    k = _check_k("placement_quality", n_neighbors, N)
+    X_ref, Y_ref, Z, y = (_rows(t, "placement_quality") for t in (X_ref, Y_ref, Z, y))
+    if Z.shape[1] != X_ref.shape[1] or y.shape[1] != Y_ref.shape[1]:
+        raise ValueError("placement_quality: Z must have the columns of X_ref and y those of Y_ref")
+    pen_t, redo_t = _placed_penalties(X_ref, Z, Y_ref, y, k)
+    pen_c, redo_c = _placed_penalties(Y_ref, y, X_ref, Z, k)
+    return _quality(pen_t, redo_t, pen_c, redo_c, M, N, k)
 
 
 @torch.no_grad()

@@ -1801,3 +1801,33 @@ def tsne_place_descent(Y, idx, p, y, velocity=None, gains=None, n_iter=250, exag
                                          _p(out.get("kl")), _p(out.get("zsum")), _p(out.get("grad")), _stream()),
           "tsne_place_descent")
     return out
+
+
+# ------------------------------------------------------------------- ranks of given neighbours among all rows (map_quality.hip)
+def neighbor_ranks(x, z, idx, self_rows=None):
+    """-> (rank (M, k) int32, redecided (1,) int64 on the device): rank[m][s] = 1 + the number of rows l of x (N, d), l != self_rows[m],
+    with (|z_m - x_l|^2, l) < (|z_m - x_j|^2, j) for j = idx[m][s], distances in float64 from the differences; 0 where j is outside
+    [0, N) or equal to self_rows[m] (g2v_neighbor_ranks; the M x N distances are never stored).  z (M, d) are the query rows, idx
+    (M, k) int32 rows of x, self_rows (M,) int64 the row of x that is query m (-1 or None: none).  redecided counts the pairs
+    whose fp32 distance lay too close to a threshold to decide on and that were evaluated again in float64."""
+    fn = "neighbor_ranks"
+    x, z = _place_rows(x, "x", fn), _place_rows(z, "z", fn)
+    (N, d), M = x.shape, z.shape[0]
+    if z.shape[1] != d:
+        raise ValueError(f"{fn}: x has {d} columns and z {z.shape[1]}")
+    if _chk(idx, torch.int32, "idx").dim() != 2 or idx.shape[0] != M:
+        raise ValueError(f"{fn}: idx must be ({M}, k), got {tuple(idx.shape)}")
+    k = int(idx.shape[1])
+    if self_rows is not None and tuple(_chk(self_rows, torch.int64, "self_rows").shape) != (M,):
+        raise ValueError(f"{fn}: self_rows must be ({M},), got {tuple(self_rows.shape)}")
+    lib = _lib_()
+    nb = int(lib.g2v_neighbor_ranks_workspace(N, M, d, k))
+    if nb == 0:
+        raise ValueError(f"{fn}: needs 1 <= d <= 512, 1 <= k <= 127, 1 <= N < 2^24 and 1 <= M < 2^31 (N = {N}, M = {M}, d = {d}, "
+                         f"k = {k})")
+    ws = workspace(nb, x.device, "neighbor_ranks")
+    rank = torch.empty((M, k), dtype=torch.int32, device=x.device)
+    redecided = torch.empty((1,), dtype=torch.int64, device=x.device)
+    check(lib.g2v_neighbor_ranks(_p(x), int(x.stride(0)), N, _p(z), int(z.stride(0)), M, d, _p(self_rows), _p(idx), k, _p(rank),
+                                 _p(redecided), _p(ws), nb, _stream()), fn)
+    return rank, redecided

@@ -1523,6 +1523,32 @@ int g2v_tsne_place_descent(const float* Y, int64_t N, const int32_t* idx, const 
                            float* velocity, float* gains, int n_iter, double exaggeration, float momentum, float learning_rate,
                            float max_grad_norm, double* kl, double* zsum, float* grad, g2v_stream_t stream);
 
+/* ---- ranks of given neighbours among all rows (map_quality.hip; gesture2vec_amd/embedding.py: trustworthiness, continuity) ---------
+ * What sklearn.manifold.trustworthiness (sklearn 1.7, Euclidean) takes from two N x N float64 matrices and a full argsort of each,
+ * without forming either: the neighbours of one space (g2v_tsne_place_neighbors) are ranked in the other.  X (N,d) fp32 with row
+ * stride ldx are the reference rows, Z (M,d) fp32 with row stride ldz the query rows (Z = X for a map scored against itself; placed
+ * rows against the fitted sample otherwise), idx int32 (M,k) lists rows of X per query, self int64 (M) or NULL names the row of X
+ * that IS query m (-1: none), which is left out of every count.
+ *   rank[m][s] = 1 + #{ l in [0,N), l != self[m] : (D(m,l), l) < (D(m,j), j) },  j = idx[m][s], in lexicographic order: the nearest
+ *   other row has rank 1 and equal distances go to the lower index.  D(m,l) = sum (z_m - x_l)^2 in float64 from the differences.
+ *   An entry j outside [0,N), or equal to self[m], gives rank 0.  rank: int32 (M,k).
+ * The thresholds D(m,j) of the M k listed pairs are evaluated exactly first.  Every other d^2 is formed as g2v_tsne_affinities forms
+ * it (float64 norms, Gram tiles on the exact-fp32 MFMA in chains of 32 columns folded in float64, rounded to fp32 once) and compared
+ * with the k thresholds of its row; a comparison with |d^2 - D(m,j)| <= 2^-18 (|z_m|^2 + |x_l|^2), twice the worst case of the Gram
+ * form's error, is decided again on sum (z_m - x_l)^2 in float64, so every count is the float64 count of the fp32 rows.
+ * redecided (may be NULL): int64[1] = the pairs (m,l) evaluated again (a listed pair itself is not one: it is never below itself).
+ * Counts are integers, added with integer operations only: the same input gives the same bits, however the columns are shared out
+ * among workgroups.  Columns d .. ld - 1 are never read; the M x N distances are never stored.
+ * Served: 1 <= d <= 512, ldx and ldz multiples of 4 and >= d, 1 <= k <= 127, 1 <= N < 2^24, 1 <= M < 2^31; anything else is
+ * G2V_ERR_UNSUPPORTED before any launch, with rank untouched.  g2v_neighbor_ranks_ok: 1 where (N, M, d, k) is served.  X, Z and
+ * workspace 16-byte aligned; workspace: g2v_neighbor_ranks_workspace(N, M, d, k) bytes (0 for an unsupported shape), not trusted
+ * across calls. */
+int g2v_neighbor_ranks_ok(int64_t N, int64_t M, int d, int k);
+size_t g2v_neighbor_ranks_workspace(int64_t N, int64_t M, int d, int k);
+int g2v_neighbor_ranks(const float* X, int64_t ldx, int64_t N, const float* Z, int64_t ldz, int64_t M, int d, const int64_t* self,
+                       const int32_t* idx, int k, int32_t* rank, int64_t* redecided, void* workspace, size_t workspace_bytes,
+                       g2v_stream_t stream);
+
 /* ---- DBSCAN over latent rows (dbscan.hip; gesture2vec_amd/dbscan.py) ----------------------------------------------------------------
  * The other branch of the reference's clustering switch (Clustering.py:742-750, sklearn.cluster.DBSCAN(eps, min_samples).fit), with
  * sklearn's labels, not merely an equivalent partition.  With adj(i,j) <=> |x_i - x_j| <= eps (a row is its own neighbour):

@@ -5,6 +5,7 @@
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy [--n_clusters 300] [--scan-k 50:400:50]
                               [--silhouette-rows M | --no-silhouette]
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm dbscan --eps 0.5 --min-samples 5
+                              [--k-distances K]
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm ward [--n_clusters 300 |
                               --distance-threshold T] [--scan-k 50:400:50]
     python cluster_latents.py --checkpoint autoencoder_checkpoint.bin --chunks x.npy --algorithm dtw --n_clusters 40 --max_iter 5
@@ -22,7 +23,9 @@ silhouette)` triples.  The silhouette is taken over all latents up to 65 536 row
 sklearn's `sample_size` (seeded with `--seed`) beyond that or when M is given; `--no-silhouette` leaves it out (None in the triples).
 `--algorithm dbscan` is the other branch of the reference's switch (`Clustering.py:742-750, 962-972`): `DBSCAN(eps, min_samples)` on
 the device (gesture2vec_amd/dbscan.py), the reference's two printed lines, and `labels` and the `core` mask in an `.npz` at `--out`
-(default `<checkpoint dir>/clusters/dbscan_labels.npz`).
+(default `<checkpoint dir>/clusters/dbscan_labels.npz`).  `--k-distances K` adds the curve one reads `eps` from, as `k_distances`:
+every row's distance to its K-th nearest row counting itself (K = the `min_samples` one has in mind), sorted ascending
+(`dbscan.k_distances`); its quartiles are printed.
 `--algorithm ward` is the third (`Clustering.py:751-755`): `AgglomerativeClustering(linkage="ward", n_clusters)` on the device
 (gesture2vec_amd/agglomerative.py), cut at `--n_clusters` or, instead, at `--distance-threshold`; `labels`, `children` and the merge
 `heights` go to an `.npz` at `--out` (default `<checkpoint dir>/clusters/ward_labels.npz`).  With `--scan-k a:b:step` the tree is
@@ -54,7 +57,7 @@ for _p in (_HERE, _ROOT):
 
 from utils.train_utils import load_checkpoint_and_model  # noqa: E402
 from gesture2vec_amd.agglomerative import AgglomerativeClustering  # noqa: E402
-from gesture2vec_amd.dbscan import DBSCAN  # noqa: E402
+from gesture2vec_amd.dbscan import DBSCAN, k_distances  # noqa: E402
 from gesture2vec_amd.kmeans import KMeans  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents  # noqa: E402
 from gesture2vec_amd.timeseries import SoftDTWKMeans, TimeSeriesKMeans  # noqa: E402
@@ -94,9 +97,13 @@ def main(argv=None):
                     help="ward: cut the tree below this merge height instead of at --n_clusters")
     ap.add_argument("--eps", type=float, default=0.5, help="dbscan: the neighbourhood radius")
     ap.add_argument("--min-samples", dest="min_samples", type=int, default=5, help="dbscan: neighbours (itself included) of a core row")
+    ap.add_argument("--k-distances", dest="k_distances", type=int, default=None, metavar="K",
+                    help="dbscan: also write every row's distance to its K-th nearest row (itself included), sorted: the curve eps is read from")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    if a.k_distances is not None and a.algorithm != "dbscan":
+        ap.error("--k-distances goes with --algorithm dbscan")
     dev = torch.device(a.device)
     if a.algorithm in ("dtw", "softdtw"):                        # the sequences themselves: no encoder pass, the checkpoint is not read
         chunks = torch.from_numpy(np.load(a.chunks).astype(np.float32, copy=False)).to(dev)
@@ -127,8 +134,13 @@ def main(argv=None):
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         core = np.zeros(lat.shape[0], dtype=bool)
         core[db.core_sample_indices_.cpu().numpy()] = True
+        arrays = {"labels": db.labels_.cpu().numpy(), "core": core}
+        if a.k_distances is not None:
+            arrays["k_distances"] = k_distances(lat, a.k_distances).cpu().numpy()
+            print(f"{a.k_distances}-distances: quartiles " + ", ".join(repr(float(v)) for v in
+                                                                   np.quantile(arrays["k_distances"], (0.25, 0.5, 0.75))))
         with open(out, "wb") as f:                               # (a file object: numpy appends no suffix of its own)
-            np.savez(f, labels=db.labels_.cpu().numpy(), core=core)
+            np.savez(f, **arrays)
         print(f"wrote {out}")
         return db
 

@@ -3,7 +3,7 @@
 reference's `PCA(50)` + `TSNE(2, perplexity=30)` picture of all latents coloured by code (`Clustering.py:1046-1056`, `:1411-1417`).
 
     python embed_latents.py --checkpoint ckpt.bin --chunks x.npy [--kmeans model.pk] [--sample-rows M] [--out map.npz]
-                            [--scatter-txt scatter.txt] [--place-rest] [--save-map map.pk] [--map map.pk]
+                            [--scatter-txt scatter.txt] [--place-rest] [--save-map map.pk] [--map map.pk] [--quality K]
 
 `--chunks` holds (N, T, D) pose chunks in the autoencoder's input space.  Their latents and code ids (`chunks_to_codes`; for an
 autoencoder without a quantiser the ids of the pickled `--kmeans` model, or none) are taken on the device, `--sample-rows M` rows are
@@ -16,7 +16,13 @@ With `--sample-rows M --place-rest` every row of `--chunks` is mapped, however m
 placed into the sample's map (`LatentMap.fit_all`); `coords`, `codes` and `rows` then cover all rows in input order and `fitted` (N,)
 bool marks the sample.  `--save-map PATH` pickles the fitted `LatentMap`.  `--map PATH` fits nothing: the rows of `--chunks` (a
 generated set, say) are placed into that saved map, which is how the reference's `Metrics_analysis` draws a generated sequence as a
-trajectory through the map of the real data (`Clustering.py:1318-1350`)."""
+trajectory through the map of the real data (`Clustering.py:1318-1350`).
+
+`--quality K` says how far the map can be believed: trustworthiness and continuity over K neighbours (`embedding.map_quality`,
+sklearn's definition, between the PCA scores the map was made from and the map) are printed, and each row's share of the two
+penalty sums goes to the `.npz` as `penalty_t` and `penalty_c` (int64, in the order of `rows`), so that badly mapped rows can be
+found.  With `--place-rest` the two numbers are printed separately for the sample and for the placed rows, the latter scored
+against the sample (`embedding.placement_quality`); with `--map`, for the placed rows against the saved map's own rows."""
 from __future__ import annotations
 
 import argparse
@@ -34,7 +40,7 @@ for _p in (_HERE, _ROOT):
         sys.path.insert(0, _p)
 
 from utils.train_utils import load_checkpoint_and_model  # noqa: E402
-from gesture2vec_amd.embedding import LatentMap, latent_map  # noqa: E402
+from gesture2vec_amd.embedding import LatentMap, latent_map, placement_quality  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents, chunks_to_codes  # noqa: E402
 
 
@@ -60,6 +66,8 @@ def main(argv=None):
                     help="with --sample-rows: place every other row into the sample's map and write all rows")
     ap.add_argument("--save-map", dest="save_map", default=None, help="pickle the fitted LatentMap here")
     ap.add_argument("--map", dest="map", default=None, help="a pickled LatentMap: fit nothing, place the rows of --chunks into it")
+    ap.add_argument("--quality", type=int, default=None, metavar="K",
+                    help="print trustworthiness and continuity over K neighbours and write each row's penalties")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -86,18 +94,24 @@ def main(argv=None):
     lat = torch.cat(lats)
     codes = None if ids[0] is None else torch.cat(ids)
     print(f"latents: {tuple(lat.shape)}")
-    fitted = None
+    fitted, quality = None, None
     if a.map:
         with open(a.map, "rb") as f:
             lm = pickle.load(f)
         coords, rows = lm.transform(lat), torch.arange(lat.shape[0], device=dev)
-    elif a.place_rest or a.save_map:
+        if a.quality:
+            quality = {"fitted": None, "placed": placement_quality(lm.tsne.fit_rows_.to(dev), lm.coords_.to(dev), lm.pca.transform(lat),
+                                                                   coords, n_neighbors=a.quality)}
+    elif a.place_rest or a.save_map or a.quality:
         lm = LatentMap(n_pca=a.n_pca, sample_size=a.sample_rows, random_state=a.seed, perplexity=a.perplexity, max_iter=a.max_iter)
         if a.place_rest:
             (coords, fitted), rows = lm.fit_all(lat), torch.arange(lat.shape[0], device=dev)
         else:
             lm.fit(lat)
             coords, rows = lm.coords_, lm.rows_
+        if a.quality:
+            quality = (lm.quality(lat, coords, n_neighbors=a.quality) if a.place_rest else
+                       lm.quality(lat[rows].contiguous(), coords, sample_idx=torch.arange(rows.shape[0]), n_neighbors=a.quality))
         if a.save_map:
             with open(a.save_map, "wb") as f:
                 pickle.dump(lm, f)
@@ -109,9 +123,20 @@ def main(argv=None):
            "codes": np.full(rows.shape[0], -1, np.int64) if codes is None else codes[rows].cpu().numpy()}
     if fitted is not None:
         res["fitted"] = fitted.cpu().numpy()
+    if quality is not None:
+        res["penalty_t"], res["penalty_c"] = (np.zeros(rows.shape[0], np.int64) for _ in range(2))
+        for part, name in (("fitted", "sample" if quality["placed"] is not None else "map"), ("placed", "placed rows")):
+            q = quality[part]
+            if q is not None:
+                print(f"{name}: trustworthiness {q['trustworthiness']!r}, continuity {q['continuity']!r} over {q['n_neighbors']} "
+                      f"neighbours of {q['penalty_t'].shape[0]} rows")
+                at = q["rows"].cpu().numpy() if "rows" in q else slice(None)          # (LatentMap.quality names the rows of each part)
+                res["penalty_t"][at] = q["penalty_t"].cpu().numpy()
+                res["penalty_c"][at] = q["penalty_c"].cpu().numpy()
+        res["quality"] = {part: None if q is None else (q["trustworthiness"], q["continuity"]) for part, q in quality.items()}
     out = a.out or os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "plots", "latent_map.npz")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    np.savez(out, **res)
+    np.savez(out, **{name: v for name, v in res.items() if name != "quality"})
     print(f"wrote {out}: {res['coords'].shape[0]} rows")
     if a.scatter_txt:
         with open(a.scatter_txt, "w") as f:
