@@ -28,6 +28,13 @@
 
 namespace g2v {
 
+// Biased batch variance from the sums over the batch of c = u - b_pre: s2 = sum c^2, mv = sum c / B.  One row has no spread: its
+// variance is 0, not what the difference leaves -- the compiler contracts it to fma(-mv, mv, s2), which at B = 1 is the rounding
+// residue of mv^2, up to 2^-24 c^2, and against eps = 1e-5 that moved 1 / sqrt(var + eps) by 2e-3 at |c| of a few.
+__device__ __forceinline__ float bn_batch_var(float s2, float mv, int B) {
+  return B > 1 ? fmaxf(s2 / (float)B - mv * mv, 0.f) : 0.f;
+}
+
 // =====================================================================================================================
 // forward: launch j of S1 + 1
 // =====================================================================================================================
@@ -112,7 +119,7 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_fwd_kernel(const int64_t* _
       for (int f = tid; f < H; f += NTHR) {
         const float s1 = red[f], s2 = red[H + f];
         const float mv = s1 / (float)B;
-        const float var = fmaxf(s2 / (float)B - mv * mv, 0.f);   // biased batch variance
+        const float var = bn_batch_var(s2, mv, B);
         const float mean = mv + w.b_pre[f];
         const float invstd = bn_invstd_(var);
         st[f] = mean;
@@ -778,7 +785,7 @@ __global__ __launch_bounds__(256) void code_cluster_fwd_kernel(CodeClArgs a) {
           float s1, s2;
           cx_sum_partials(a.xp + (size_t)ppar * nblk * prec, nblk, Hp, f, tag, a.fault, s1, s2);
           const float mv = s1 / (float)B;
-          const float var = fmaxf(s2 / (float)B - mv * mv, 0.f);   // biased batch variance
+          const float var = bn_batch_var(s2, mv, B);
           mean = mv + w.b_pre[f];
           invstd = bn_invstd_(var);
           if (ft == 0 && rg == 0) {
@@ -1610,9 +1617,13 @@ extern "C" int g2v_attn_code_rollout_fwd(const int64_t* codes, const float* h_in
   f.workspace_bytes = workspace_bytes; f.saved = !training || saved;
   const CodeRoutePlan pl = code_plan_call(CODE_FWD, S1, B, H, K, Tw, att != 0, f);
   CODE_REFUSE(pl);
-  const void* al[] = {h_init, enc, enc_proj, w->emb, w->b_pre, w->bn_w, w->bn_b, w->b_ih0, w->b_hh0, w->b_ih1, w->b_hh1, w->b_out,
-                      w->b_attn, w->v_attn, s->ec, s->u, s->a, s->h0, s->h1, s->x1, s->gates0, s->gates1, s->logits, s->bn_partial,
-                      s->hp, keep_emb, keep_l0, workspace};
+  // Every array a kernel behind this entry moves as float4s or as words of four keep flags.  The weight matrices are among them:
+  // the step kernels read them through launch_pack, element by element, but code_cluster_fwd_kernel loads its rows of w_pre, w_ih*,
+  // w_hh* and w_out as float4s.  Element-wise on every route, and so served at 4 bytes: w_attn (packed), bn_running_mean / _var,
+  // bn_stats, attw; codes and ids are read and written one int64 at a time.
+  const void* al[] = {h_init, enc, enc_proj, w->emb, w->w_pre, w->b_pre, w->bn_w, w->bn_b, w->w_ih0, w->w_hh0, w->b_ih0, w->b_hh0,
+                      w->w_ih1, w->w_hh1, w->b_ih1, w->b_hh1, w->w_out, w->b_out, w->b_attn, w->v_attn, s->ec, s->u, s->a, s->h0, s->h1,
+                      s->x1, s->gates0, s->gates1, s->logits, s->bn_partial, s->hp, keep_emb, keep_l0, workspace};
   for (const void* p : al) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
   const CodeFwdCall c{codes, h_init, enc, enc_proj, w, s, keep_emb, keep_l0, p_drop, n_pre, training, S1, B, H, K, Tw, att,
                       workspace, (hipStream_t)stream};
@@ -1643,7 +1654,20 @@ extern "C" int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc
   const CodeRoutePlan pl = code_plan_call(CODE_BWD, S1, B, H, K, Tw, att != 0, f);
   CODE_REFUSE(pl);
   const CtBwdWs& L = pl.bw;
-  G2V_REQUIRE(ct_al16(workspace) && ct_al16(d_logits) && ct_al16(g->d_hidden0), "16-byte alignment");
+  // Every array a kernel behind this entry moves as float4s or as words of four keep flags: code_bptt_kernel, code_bn_bwd_apply_kernel
+  // and code_step_bwd_att_kernel read the saved arrays, bn_stats, bn_w, v_attn, the masks, enc and enc_proj so and write d_hidden0
+  // and d_enc so; the dense, weight-gradient and embedding-gradient calls of the tail get w_pre, ids, the saved arrays and every
+  // gradient array and choose their own widths.  Element-wise, and so served at 4 bytes: w_ih*, w_hh*, w_out and w_attn, which
+  // only launch_pack and code_split_cols_kernel read.
+  const void* al[] = {workspace, d_logits, w->w_pre, w->bn_w, s->ids, s->ec, s->u, s->a, s->bn_stats, s->h0, s->h1, drop ? s->x1 : nullptr,
+                      s->gates0, s->gates1, keep_emb, drop ? keep_l0 : nullptr, g->d_hidden0, g->d_emb, g->d_w_pre, g->d_b_pre, g->d_bn_w,
+                      g->d_bn_b, g->d_w_ih0, g->d_w_hh0, g->d_b_ih0, g->d_b_hh0, g->d_w_ih1, g->d_w_hh1, g->d_b_ih1, g->d_b_hh1, g->d_w_out,
+                      g->d_b_out};
+  for (const void* p : al) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
+  if (att) {      // (read with attention only)
+    const void* al_att[] = {enc, enc_proj, w->v_attn, s->hp, s->attw, g->d_w_attn, g->d_b_attn, g->d_v_attn, g->d_enc};
+    for (const void* p : al_att) G2V_REQUIRE(ct_al16(p), "16-byte alignment");
+  }
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)workspace;
   const int Hin = att ? 2 * H : H, G = 3 * H, M = S1 * B;

@@ -1259,7 +1259,18 @@ int g2v_attn_code_rollout_fwd(const int64_t* codes, const float* h_init, const f
                               const uint8_t* keep_l0, float p_drop, int n_pre, int training, int S1, int B, int H, int K,
                               int Tw, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
 size_t g2v_attn_code_rollout_bwd_workspace(int S1, int B, int H, int K, int Tw, int attention);
-/* d_logits (S1,B,K); everything else as passed to the forward of the same call. */
+/* d_logits (S1,B,K); everything else as passed to the forward of the same call.
+ * Alignment.  The three entries refuse, before any launch, with "16-byte alignment" (G2V_ERR_ARG), an array their
+ * kernels move as float4s or as words of four keep flags that does not start on a 16-byte boundary; the arrays they move one
+ * element at a time need their element's alignment only.
+ *   g2v_attn_code_rollout_fwd   16 bytes: h_init, enc, enc_proj, keep_emb, keep_l0, workspace, every member of the weights but
+ *                               w_attn and bn_running_mean / _var, every member of the saved arrays but ids, bn_stats and attw.
+ *                               Element-wise: codes, ids, w_attn, bn_running_mean / _var, bn_stats, attw.
+ *   g2v_attn_code_rollout_bwd   16 bytes: d_logits, enc, enc_proj, keep_emb, keep_l0, workspace, w_pre, bn_w, v_attn, every saved
+ *                               array it is passed (ids included), every member of the gradients.  Element-wise: w_ih0 / w_hh0 /
+ *                               w_ih1 / w_hh1, w_out, w_attn.  The other weights are not read.
+ *   g2v_code_cluster_bptt       16 bytes: dh_top, keep_l0, dgi0 / dgh0 / dgi1 / dgh1, da, d_hidden0, gates0 / gates1, h0, h1,
+ *                               workspace.  Element-wise: w_ih0 / w_hh0 / w_ih1 / w_hh1.  Nothing else is read. */
 int g2v_attn_code_rollout_bwd(const float* d_logits, const float* enc, const float* enc_proj, const g2v_code_dec_weights* w,
                               const g2v_code_dec_saved* s, const g2v_code_dec_grads* g, const uint8_t* keep_emb,
                               const uint8_t* keep_l0, float p_drop, int S1, int B, int H, int K, int Tw, void* workspace,

@@ -138,3 +138,80 @@ T2E_ROUTE_SHAPES = (
     _case("bptt refused: S1 = 0", "", 16, 48, S1=0, bptt=True),
     _case("bptt refused: workspace too small", "", 16, 48, facts=("WS_SMALL",), bptt=True),
 )
+
+
+# ---- CODE_F64_CASES: the calls tests/test_gpu_code_rollout_f64.py holds to the float64 restatement of tests/_code_ref.py, and
+# tests/test_code_ref_host.py to the conditions of that reference.  Each names the forward and backward route the ENTRY must select
+# at its level on 256 CUs (route_name(..., facts=("ENTRY",))).  kind "pair": g2v_attn_code_rollout_fwd, then (training)
+# g2v_attn_code_rollout_bwd on the arrays it saved; with bptt also g2v_code_cluster_bptt on them, fed dh_top = d_logits W_out formed
+# in float64.  S1 = 2 or 3; 4 where n_pre = 3 must leave a free-running step; 1 at the smallest shape.
+# emb_drop False: keep_emb = NULL.  deferred: also run with bn_running_* = NULL and commit with g2v_bn_running_update_invstd.
+# tie = (k1, k2, gain, lift): tests/_code_ref.py.  The seed of a case is the first at which tests/_code_ref.py's admissible() holds
+# (_CODE_SEEDS; 0 where it is not listed).
+_CODE_SEEDS = {}
+
+
+def _f64(tag, route, B, H, K=40, *, S1=2, Tw=0, att=False, level=1, p=0.0, n_pre=1, training=True, emb_drop=True, deferred=False,
+         bptt=False, tie=None):
+    fwd, bwd = route.split("/")
+    cid = f"{fwd}-{B}x{H}x{K}" + (f"xTw{Tw}" if att else "") + f"-{tag}"
+    return dict(id=cid, route=fwd, route_bwd=bwd if training else "", S1=S1, B=B, H=H, K=K, Tw=Tw, att=att, level=level, p=p, n_pre=n_pre,
+                training=training, emb_drop=emb_drop, deferred=deferred, bptt=bptt and training, tie=tie, seed=_CODE_SEEDS.get(cid, 0))
+
+
+_S, _A, _C = "STEP/STEP", "STEP/STEP*1", "CLUSTER/STEP"
+CODE_F64_CASES = (
+    # ---- STEP / STEP, no attention: level 0, or a shape off the cluster grid at level 1
+    _f64("one-row", _S, 1, 16, 4, S1=1, level=0),                           # B = 1 in training: variance 0
+    _f64("plain", _S, 16, 48, S1=3, level=0, deferred=True),
+    _f64("npre0", _S, 17, 48, S1=3, level=0, n_pre=0),                      # a second row group holding one row
+    _f64("drop", _S, 33, 48, S1=3, level=0, p=0.2),                         # a third row group holding one row
+    _f64("no-keep-emb", _S, 16, 20, level=0, emb_drop=False),               # H = 20 padded to 32
+    _f64("drop", _S, 24, 200, 512, level=0, p=0.2),                         # H = 200 padded to 208
+    _f64("npre3", _S, 16, 212, S1=4, n_pre=3),                              # H = 212: STEP at every level
+    _f64("lds-bound", _S, 16, 224),                                         # the backward's LDS carve at its 160 KB bound in H
+    _f64("lds-bound", _S, 16, 200, 688),                                    # ... and in K at H = 200
+    _f64("forced", _S, 16, 48, 44, level=0, n_pre=9),                       # n_pre = S1 + 7: every step is fed from `codes`
+    _f64("second-pass-one-tile", _S, 16, 48, 528),                          # out layer: 33 K tiles, 32 per pass
+    _f64("second-pass-full", _S, 16, 48, 1024),                             # ... 64 K tiles
+    _f64("one-k-tile-over", _S, 16, 48, 148),                               # ceil(K / 16) = 3 nt + 1: off the cluster grid
+    # reduce_partials' 16-row unrolled loop (csrc/common.hpp) runs where a row segment holds per = ceil(nblk / nseg) >= 16 row
+    # groups, nseg = min(threads, scratch / 4) / (2H / 4).  At H = 224 (112 float4 columns, the fewest segments a served H has):
+    # code_step_fwd_kernel has 512 threads and, at every served shape, the 2048-float scratch (ct_scratch: its carve stays under
+    # 160 KB - 8 KB), so nseg = 4 and per >= 16 from nblk = 61; code_bn_bwd_apply_kernel has 256 threads and 1024 floats, nseg = 2,
+    # per >= 16 from nblk = 31.  B = 961 = 60 * 16 + 1 gives nblk = 61: per = 16 forward (three full segments, one of 13), per = 31
+    # backward (16 unrolled + 15), and a last row group of one row.  (The 1024-float scratch the plan can hand the step kernels is
+    # taken by the attention backward only, at H = 20, where 10 float4 columns leave nseg = 25.)
+    _f64("unrolled-reduce", _S, 961, 224),
+    _f64("eval", _S, 16, 48, S1=3, level=0, training=False),
+    # ---- STEP / STEP*1: attention
+    _f64("plain", _A, 24, 48, S1=3, Tw=5, att=True, deferred=True),
+    _f64("one-position", _A, 24, 48, Tw=1, att=True),
+    _f64("tw-fills-the-tile", _A, 24, 48, Tw=26, att=True),
+    _f64("tw-max", _A, 24, 200, 512, Tw=64, att=True),
+    _f64("smallest-h", _A, 24, 20, Tw=5, att=True),
+    _f64("ragged", _A, 7, 48, Tw=5, att=True),
+    _f64("drop-npre2", _A, 24, 48, S1=3, Tw=5, att=True, p=0.2, n_pre=2),
+    # ---- CLUSTER forward through the entry at level 1, the STEP backward and the cluster BPTT behind it on the arrays it saved
+    _f64("plain", _C, 16, 48, S1=3, deferred=True, bptt=True),
+    _f64("one-row", _C, 1, 16, 4, S1=1, bptt=True),
+    _f64("shipped-dims", _C, 17, 200, 512, bptt=True),
+    _f64("h52", _C, 16, 52, bptt=True),
+    _f64("h208", _C, 16, 208, bptt=True),
+    _f64("k-tiles-3nt", _C, 16, 48, 144, bptt=True),
+    _f64("k-tiles-3nt", _C, 16, 200, 624, bptt=True),
+    _f64("largest-grid", _C, 304, 200, 512, bptt=True),                     # 13 x 19 workgroups
+    _f64("npre3", _C, 16, 48, S1=4, n_pre=3, bptt=True),
+    _f64("eval", _C, 16, 48, S1=3, training=False),
+    # ---- ... with inter-layer dropout, over the same H / B set
+    _f64("drop", _C, 16, 48, S1=3, p=0.2, bptt=True),
+    _f64("one-row-drop", _C, 1, 16, 4, S1=1, p=0.2, bptt=True),
+    _f64("drop", _C, 17, 200, p=0.2, bptt=True),
+    _f64("drop", _C, 16, 52, p=0.2, bptt=True),
+    _f64("drop", _C, 16, 208, p=0.2, bptt=True),
+    _f64("drop", _C, 304, 200, p=0.2, bptt=True),
+    # ---- a tie per forward kernel: codes 3 and 21 sit in different K tiles, which different waves (step) and different workgroups
+    # (cluster) reduce; the pair is preferred at the free-running steps
+    _f64("tie", _S, 16, 48, S1=3, level=0, tie=(3, 21, 3.0, 0.75)),
+    _f64("tie", _C, 16, 48, S1=3, tie=(3, 21, 3.0, 0.75)),
+)
