@@ -16,6 +16,9 @@ needs scipy or sklearn.  For an autoencoder without a quantiser the code ids com
   the ids are.  torchtext forms the score in float32 and is not installed where this was written: parity with it is claimed from its
   definition, to float32 rounding, not from a recorded run.
 
+* `energy_distance`: a second two-sample distance between the latents, beside the Frechet distance (not a reference column, and
+  not part of `gesture_metrics`).
+
 Out of scope: the plots (the PCA + t-SNE maps are `gesture2vec_amd.embedding`)."""
 from __future__ import annotations
 
@@ -153,6 +156,19 @@ def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
     lam = np.linalg.eigvalsh(0.5 * (m + m.T))
     diff = mu1 - mu2
     return float(diff @ diff + np.trace(s1) + np.trace(s2) - 2.0 * np.sqrt(np.clip(lam, 0.0, None)).sum())
+
+
+def energy_distance(x: torch.Tensor, y: torch.Tensor) -> float:
+    """The energy distance 2 E|x - y| - E|x - x'| - E|y - y'| between two sets of rows (n, E) and (m, E), fp32 on the GPU: a
+    two-sample distance between the latents of real and generated chunks that, unlike the Frechet distance, assumes no Gaussians.
+    0 for equal sets, symmetric.  The expectations are over ordered pairs (x' and y' independent copies, the n zero distances of a
+    row to itself included): E|x - x'| = 2 sum_{i<j} |x_i - x_j| / n^2.  Three passes of repdist.pairwise_distance_stats; no
+    distance is stored."""
+    from .repdist import pairwise_distance_stats
+    xy = pairwise_distance_stats(x, y)
+    xx, yy = pairwise_distance_stats(x), pairwise_distance_stats(y)
+    n, m = int(x.shape[0]), int(y.shape[0])
+    return 2.0 * xy["mean"] - 2.0 * xx["sum"] / (float(n) * n) - 2.0 * yy["sum"] / (float(m) * m)
 
 
 def code_histogram(idx: torch.Tensor, K: int) -> np.ndarray:
@@ -316,6 +332,20 @@ def _scan(net, chunks: torch.Tensor, dae, batch_rows: int, K: Optional[int], kme
     if keep_ids:
         return mom, counts, torch.cat(kept)
     return mom, counts
+
+
+@torch.no_grad()
+def set_latents(net, chunks: torch.Tensor, dae=None, batch_rows: int = 65536) -> torch.Tensor:
+    """The latent rows `gesture_metrics` scans, kept: (N, T, D) chunks -> [dae.encode per frame ->] chunk_latents -> (N, E) fp32"""
+    _need_cuda(chunks, "set_latents")
+    rows = []
+    for a in range(0, chunks.shape[0], int(batch_rows)):
+        x = chunks[a:a + int(batch_rows)]
+        if dae is not None and dae.encoder is not None:
+            B, T, D = x.shape
+            x = dae.encode(x.reshape(B * T, D).contiguous()).view(B, T, -1)
+        rows.append(chunk_latents(net, x))
+    return torch.cat(rows)
 
 
 @torch.no_grad()

@@ -1501,6 +1501,88 @@ def ward_rounds(D, state, *, init, rounds=1):
     return s["counters"]
 
 
+# ------------------------------------------------------------------------------------------ pairwise-distance statistics (pair_stats.hip)
+def pair_stats_max_rows() -> int:
+    return int(_lib_().g2v_pair_stats_max_rows())
+
+
+def pair_stats_max_bins() -> int:
+    return int(_lib_().g2v_pair_stats_max_bins())
+
+
+def pair_stats_run(N, M=0) -> int:
+    """64-row tiles of the second set (of x itself with M == 0) that one workgroup of pair_stats takes: a function of the row counts
+    alone; 0 for a shape it refuses"""
+    return int(_lib_().g2v_pair_stats_run(int(N), int(M)))
+
+
+def pair_stats_workspace(N, M, E, bins=0) -> int:
+    """bytes of workspace of pair_stats; 0 for a shape it refuses"""
+    return int(_lib_().g2v_pair_stats_workspace(int(N), int(M), int(E), int(bins)))
+
+
+def _pair_rows(t, name, what):
+    if not t.is_cuda:
+        raise _lib.G2VLibraryError(f"{name} must be a GPU tensor: the g2v kernels have no CPU path")
+    if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+        raise TypeError(f"{what}: {name} must be a (N, E) fp32 tensor with unit column stride")
+
+
+def pair_stats(x, y=None, edges=None, *, ws=None):
+    """-> (out (4) float64 = [sum d, sum d^2, min d, max d], counts (2) int64 = [pairs, pairs not finite], hist (bins) int64 or None)
+    over the Euclidean distances between the rows of x (N, E) fp32, unit column stride, row stride a multiple of 4: the pairs i < j
+    of x, or with y (M, E) all N M pairs (g2v_pair_stats: Gram tiles on the float64 MFMA, near pairs from differences, no distance
+    stored).  edges: (bins + 1) float64 on the device, ascending (not checked here), counted by numpy.histogram's rule.  ws: a byte
+    buffer of at least pair_stats_workspace bytes to use instead of the cached one.  Nothing is read back."""
+    _pair_rows(x, "x", "pair_stats")
+    N, E = x.shape
+    M = 0
+    if y is not None:
+        _pair_rows(y, "y", "pair_stats")
+        M = y.shape[0]
+        if y.shape[1] != E or y.device != x.device:
+            raise ValueError(f"pair_stats: y must be (M, {E}) on the device of x, got {tuple(y.shape)} on {y.device}")
+        if M < 1:
+            raise ValueError("pair_stats: y has no rows")
+    bins = 0
+    if edges is not None:
+        bins = _chk(edges, torch.float64, "edges").numel() - 1
+        if edges.dim() != 1 or bins < 1:
+            raise ValueError(f"pair_stats: edges must be 1-D with at least 2 entries, got {tuple(edges.shape)}")
+    lib = _lib_()
+    nb = pair_stats_workspace(N, M, E, bins)
+    if nb == 0:
+        raise ValueError(f"pair_stats: unsupported shape N = {N}, M = {M}, E = {E}, bins = {bins} (1 <= N, M <= {pair_stats_max_rows()}, "
+                         f"1 <= E <= 512, bins <= {pair_stats_max_bins()})")
+    if ws is None:
+        ws = workspace(max(nb, 16), x.device, "pair_stats")
+    elif not ws.is_cuda or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nb:
+        raise ValueError(f"pair_stats: ws must be a contiguous uint8 GPU tensor of at least {nb} bytes")
+    out = torch.empty((4,), dtype=torch.float64, device=x.device)
+    counts = torch.empty((2,), dtype=torch.int64, device=x.device)
+    hist = torch.empty((bins,), dtype=torch.int64, device=x.device) if bins else None
+    check(lib.g2v_pair_stats(_p(x), int(x.stride(0)), N, _p(y), int(y.stride(0)) if y is not None else 0, M, E, _p(edges), bins, _p(out),
+                             _p(counts), _p(hist), _p(ws), nb, _stream()), "pair_stats")
+    return out, counts, hist
+
+
+def lag_distances(x, lags, clip_ids=None):
+    """-> (n_lags, N) float64: out[l][i] = (|x_{i - lag} - x_i| + |x_{i + lag} - x_i|) / 2 over the rows of x (N, E) fp32, unit column
+    stride, row stride a multiple of 4 (g2v_lag_distances); NaN where a neighbour is past either end or, with clip_ids (N) int64,
+    carries another id than row i.  lags: up to 8 host integers >= 1."""
+    _pair_rows(x, "x", "lag_distances")
+    N, E = x.shape
+    lags = [int(v) for v in lags]
+    if not 1 <= len(lags) <= 8 or min(lags) < 1 or max(lags) >= 2 ** 31:
+        raise ValueError(f"lag_distances: needs 1 to 8 lags, each >= 1, got {lags}")
+    if clip_ids is not None and tuple(_chk(clip_ids, torch.int64, "clip_ids").shape) != (N,):
+        raise ValueError(f"lag_distances: clip_ids must be ({N},), got {tuple(clip_ids.shape)}")
+    out = torch.empty((len(lags), N), dtype=torch.float64, device=x.device)
+    arr = (C.c_int32 * len(lags))(*lags)
+    check(_lib_().g2v_lag_distances(_p(x), int(x.stride(0)), N, E, arr, len(lags), _p(clip_ids), _p(out), _stream()), "lag_distances")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ DTW k-means (dtw.hip)
 def dtw_max_len() -> int:
     return int(_lib_().g2v_dtw_max_len())

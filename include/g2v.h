@@ -1624,6 +1624,39 @@ int g2v_ward_distances(const float* x, int64_t ld, int64_t N, int E, double* D, 
 int g2v_ward_rounds(double* D, int64_t N, int32_t* size, int32_t* nn, int32_t* part, int init, int rounds, int32_t* pairs,
                     double* heights, int32_t* sizes, int64_t* counters, g2v_stream_t stream);
 
+/* ---- Pairwise-distance statistics and temporal-neighbour distances (pair_stats.hip; gesture2vec_amd/repdist.py) --------------------
+ * The reference's representation-similarity metric (Clustering.py:410-505, calculate_distances): np.mean(pdist(latents)) stores
+ * N (N - 1) / 2 float64 distances.  Here the pairs are reduced as they are formed and none is stored.  1 <= N, M <=
+ * g2v_pair_stats_max_rows() = 2^24 (the index width, not memory), 1 <= E <= 512, 0 <= bins <= g2v_pair_stats_max_bins() = 1024 (the
+ * edges and a workgroup's counters live in LDS); G2V_ERR_UNSUPPORTED beyond, before any launch.  No floating-point atomics, and how the
+ * work is split is a function of (N, M) alone: the same input gives the same bits on any device.
+ *
+ * g2v_pair_stats: x (N,E) fp32 with row stride ldx >= E, ldx % 4 == 0; y (M,E) with ldy likewise, or y == NULL and M == 0.  Without y
+ *   the pairs are the unordered pairs i < j of x (N (N - 1) / 2 of them), with y all N M pairs (i, j).  d = sqrt(d^2) with d^2 as
+ *   g2v_ward_distances forms it (float64 norms, Gram tiles on the float64 MFMA, a pair with d^2 < (|a|^2 + |b|^2) / 8 again from
+ *   differences, so bitwise equal rows are 0 apart).  All outputs are written by the device:
+ *     out    double[4]  = { sum d, sum d^2 (of the d^2 themselves), min d, max d }; without a pair { 0, 0, +inf, -inf }.  A NaN
+ *                         distance makes the sums NaN and is passed over by min and max.
+ *     counts int64[2]   = { pairs, pairs whose distance is NaN or infinite }
+ *     hist   int64[bins], with bins > 0, over edges double[bins + 1] (device memory, ascending: the caller's to ensure), by
+ *                         numpy.histogram's rule: bin b holds edges[b] <= d < edges[b + 1], the last bin also d == edges[bins];
+ *                         anything else, NaN included, is in no bin.  bins == 0: edges and hist are not read and may be NULL.
+ *   One workgroup takes 64 rows of x and g2v_pair_stats_run(N, M) consecutive 64-row tiles of the other set and writes one partial to
+ *   its own slot of the workspace; a second launch folds the slots in a fixed order.  x, y and workspace 16-byte aligned, the other
+ *   arrays 8-byte.  Columns E .. ld - 1 are never read.  workspace: g2v_pair_stats_workspace(N, M, E, bins) bytes (0 for an unsupported
+ *   shape), not trusted across calls.
+ * g2v_lag_distances: x (N,E) as above, lags: n_lags <= 8 host integers >= 1, clip_ids int64[N] or NULL -> out double[n_lags][N],
+ *   out[l][i] = (|x_{i - lag} - x_i| + |x_{i + lag} - x_i|) / 2, each distance the square root of a float64 sum of squared differences;
+ *   NaN where i - lag < 0, i + lag >= N, or (with clip_ids) either neighbour carries another id than row i. */
+int64_t g2v_pair_stats_max_rows(void);
+int g2v_pair_stats_max_bins(void);
+int g2v_pair_stats_run(int64_t N, int64_t M);
+size_t g2v_pair_stats_workspace(int64_t N, int64_t M, int E, int bins);
+int g2v_pair_stats(const float* x, int64_t ldx, int64_t N, const float* y, int64_t ldy, int64_t M, int E, const double* edges, int bins,
+                   double* out, int64_t* counts, int64_t* hist, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+int g2v_lag_distances(const float* x, int64_t ld, int64_t N, int E, G2V_HOST const int32_t* lags, int n_lags, const int64_t* clip_ids,
+                      double* out, g2v_stream_t stream);
+
 /* ---- DTW k-means over chunk sequences (dtw.hip; gesture2vec_amd/timeseries.py) ------------------------------------------------------
  * The reference's other clustering space (Clustering.py:629-669, tslearn's TimeSeriesKMeans(metric="dtw")): dynamic time warping
  * between series and centres, and DTW barycentre averaging (DBA).  tslearn is not a dependency and no run of it stands behind this

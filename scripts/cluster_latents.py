@@ -38,7 +38,11 @@ then.  `n_iter`, inertia and the usage perplexity are printed and the model is p
 or `--out`.
 `--algorithm softdtw` is the same under soft-DTW: the reference's `TimeSeriesKMeans(n_clusters=40, metric="softdtw", max_iter=5,
 max_iter_barycenter=5, metric_params={"gamma": 0.5}, random_state=0)` (`Clustering.py:670-691`) as `SoftDTWKMeans` with `--gamma`;
-the model is pickled to `<checkpoint dir>/clusters/softdtw_kmeans_model.pk` or `--out`."""
+the model is pickled to `<checkpoint dir>/clusters/softdtw_kmeans_model.pk` or `--out`.
+`--rep-distance [--rep-seed S]` also writes the reference's `Rep_distance.txt` (`calculate_distances`, `Clustering.py:410-505`, whose call
+at `:580` is commented out because `pdist` cannot hold the pairs at scale) next to the model or labels file, and prints it: the
+representation-similarity numbers of the latents, both methods (gesture2vec_amd/repdist.py; at least 1004 latents, the reference
+samples 1000 of them).  It needs the latents, so it does not go with `--algorithm dtw|softdtw`."""
 from __future__ import annotations
 
 import argparse
@@ -60,6 +64,7 @@ from gesture2vec_amd.agglomerative import AgglomerativeClustering  # noqa: E402
 from gesture2vec_amd.dbscan import DBSCAN, k_distances  # noqa: E402
 from gesture2vec_amd.kmeans import KMeans  # noqa: E402
 from gesture2vec_amd.pipeline import chunk_latents  # noqa: E402
+from gesture2vec_amd.repdist import representation_report  # noqa: E402
 from gesture2vec_amd.timeseries import SoftDTWKMeans, TimeSeriesKMeans  # noqa: E402
 
 
@@ -99,9 +104,16 @@ def main(argv=None):
     ap.add_argument("--min-samples", dest="min_samples", type=int, default=5, help="dbscan: neighbours (itself included) of a core row")
     ap.add_argument("--k-distances", dest="k_distances", type=int, default=None, metavar="K",
                     help="dbscan: also write every row's distance to its K-th nearest row (itself included), sorted: the curve eps is read from")
+    ap.add_argument("--rep-distance", dest="rep_distance", action="store_true",
+                    help="also write and print Rep_distance.txt, the reference's representation-similarity numbers of the latents")
+    ap.add_argument("--rep-seed", dest="rep_seed", type=int, default=None, help="--rep-distance: seed of the 1000 sampled rows")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    if a.rep_distance and a.algorithm in ("dtw", "softdtw"):
+        ap.error("--rep-distance measures the latents: --algorithm dtw and softdtw have none")
+    if a.rep_seed is not None and not a.rep_distance:
+        ap.error("--rep-seed goes with --rep-distance")
     if a.k_distances is not None and a.algorithm != "dbscan":
         ap.error("--k-distances goes with --algorithm dbscan")
     dev = torch.device(a.device)
@@ -125,6 +137,14 @@ def main(argv=None):
     chunks = torch.from_numpy(np.load(a.chunks).astype(np.float32, copy=False)).to(dev)
     lat = latents_of(net, chunks, a.batch_rows)
     print(f"latents: {tuple(lat.shape)}")
+    if a.rep_distance:
+        rep_dir = os.path.dirname(os.path.abspath(a.out)) if a.out else os.path.join(os.path.dirname(os.path.abspath(a.checkpoint)), "clusters")
+        os.makedirs(rep_dir, exist_ok=True)
+        text = representation_report(lat, seed=a.rep_seed)
+        print(text)
+        with open(os.path.join(rep_dir, "Rep_distance.txt"), "w") as f:
+            f.write(text)
+        print(f"wrote {os.path.join(rep_dir, 'Rep_distance.txt')}")
 
     if a.algorithm == "dbscan":
         db = DBSCAN(eps=a.eps, min_samples=a.min_samples).fit(lat)

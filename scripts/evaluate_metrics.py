@@ -11,7 +11,12 @@ the reference's Metrics.txt lines (:1546-1558); the code metrics read "None" for
     ... --real_clips a.npy --generated_clips b.npy        (or --clip_chunks N: every clip holds N chunks)
 
 adds the BLEU line (:1601-1608): the code sequence of generated clip i scored against that of real clip i.  Both .npy files hold
-the number of consecutive chunks of each clip.  t-SNE, k-means and the plots of `Metrics_analysis` are not computed."""
+the number of consecutive chunks of each clip.
+
+    ... --energy
+
+adds one line, `Energy distance --> v`: the energy distance between the two sets' latents (gesture2vec_amd.metrics.energy_distance),
+a two-sample distance that assumes no Gaussians; not a reference column.  t-SNE, k-means and the plots of `Metrics_analysis` are not computed."""
 from __future__ import annotations
 
 import argparse
@@ -28,7 +33,7 @@ for _p in (_HERE, _ROOT):
         sys.path.insert(0, _p)
 
 from utils.train_utils import load_checkpoint_and_model  # noqa: E402
-from gesture2vec_amd.metrics import gesture_metrics  # noqa: E402
+from gesture2vec_amd.metrics import energy_distance, gesture_metrics, set_latents  # noqa: E402
 
 
 def main(argv=None):
@@ -40,6 +45,7 @@ def main(argv=None):
     ap.add_argument("--real_clips", default=None, help=".npy of ints: chunks per ground-truth clip (adds the BLEU line)")
     ap.add_argument("--generated_clips", default=None, help=".npy of ints: chunks per generated clip")
     ap.add_argument("--clip_chunks", type=int, default=None, help="shorthand: every clip of both sets holds this many chunks")
+    ap.add_argument("--energy", action="store_true", help="add the energy distance between the two sets' latents (one more line)")
     ap.add_argument("--batch_rows", type=int, default=65536)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -70,6 +76,9 @@ def main(argv=None):
     print("wasserstein_distance -> " + repr(m["wasserstein"]))
     if clips:
         print(" BLEU: " + repr(m["bleu_sum"]) + " AVG_BLEU Score:" + repr(m["bleu"]) + " +-" + repr(m["bleu_var"]))
+    if a.energy:
+        m["energy"] = energy_distance(set_latents(net, real, dae, a.batch_rows), set_latents(net, gen, dae, a.batch_rows))
+        print("Energy distance --> " + repr(m["energy"]))
     return m
 
 
