@@ -1131,7 +1131,7 @@ __global__ __launch_bounds__(256) void vq_ema_scalars_kernel(const float* __rest
                                                              const float* __restrict__ sse_partial, int n_sse,
                                                              float* __restrict__ cs, float* __restrict__ scalars,
                                                              int N_loss, int N_cnt, int E, int K, float beta,
-                                                             float decay, float eps, int update,
+                                                             float decay, float one_minus_decay, float eps, int update,
                                                              const unsigned* __restrict__ fault) {
   __shared__ float red[3][4];
   __shared__ float bc[1];
@@ -1144,7 +1144,7 @@ __global__ __launch_bounds__(256) void vq_ema_scalars_kernel(const float* __rest
     const float p = cnt / (float)N_cnt;
     ent += p * logf(p + 1e-10f);
     if (update) {
-      const float c = cs[k] * decay + (1.0f - decay) * cnt;   // :1263-1265
+      const float c = cs[k] * decay + one_minus_decay * cnt;   // :1263-1265
       cs[k] = c;
       nsum += c;
     }
@@ -1174,7 +1174,7 @@ __global__ __launch_bounds__(256) void vq_ema_scalars_kernel(const float* __rest
 // ---- K4 rows: ema_w, codebook, ||W||^2 (one wave per code) -------------------------------------------
 __global__ void vq_ema_rows_kernel(const float* __restrict__ stats, const float* __restrict__ cs,
                                    float* __restrict__ ema_w, float* __restrict__ W, float* __restrict__ wsq, int E,
-                                   int K, float decay, const unsigned* __restrict__ fault) {
+                                   int K, float decay, float one_minus_decay, const unsigned* __restrict__ fault) {
   const int code = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (code >= K || (fault && *fault != 0u)) return;
   const float* dw = stats + K + (int64_t)code * E;
@@ -1183,7 +1183,7 @@ __global__ void vq_ema_rows_kernel(const float* __restrict__ stats, const float*
   const float c = cs[code];
   float s = 0.f;
   for (int e = lane; e < E; e += 64) {
-    const float v = ew[e] * decay + (1.0f - decay) * dw[e];   // :1276-1278
+    const float v = ew[e] * decay + one_minus_decay * dw[e];   // :1276-1278
     ew[e] = v;
     const float wv = v / c;                                    // :1280-1282
     w[e] = wv;
@@ -2567,24 +2567,42 @@ extern "C" int g2v_vq_stats(const int64_t* idx, const float* flat, float* stats,
   return G2V_OK;
 }
 
+// one_minus_decay: 1.0f - decay in fp32 (g2v_vq_ema_update, what it always computed), or (float)(1.0 - decay) formed in double as
+// torch forms the reference's Python scalar (g2v_vq_ema_update_exact): at decay 0.99 the two differ by 9.3e-7 of their value.
+static int vq_ema_update_launch(const float* stats, const float* sse_partial, int n_sse_partial, float* ema_cluster_size,
+                                float* ema_w, float* codebook, float* code_sqnorm, float* scalars, int N_loss, int N_cnt, int E,
+                                int K, float beta, float decay, float one_minus_decay, float eps, int update, g2v_stream_t stream,
+                                const char* who) {
+  if (!(stats && scalars)) { set_error("%s: null pointer", who); return G2V_ERR_ARG; }
+  if (update && !(ema_cluster_size && ema_w && codebook && code_sqnorm)) { set_error("%s: null EMA state", who); return G2V_ERR_ARG; }
+  if (!(N_loss > 0 && N_cnt > 0 && E > 0 && K > 0)) { set_error("%s: non-positive size", who); return G2V_ERR_ARG; }
+  const unsigned* fault = g2v_internal_persist_fault_ptr();
+  hipLaunchKernelGGL(vq_ema_scalars_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, sse_partial,
+                     sse_partial ? n_sse_partial : 0, ema_cluster_size, scalars, N_loss, N_cnt, E, K, beta, decay, one_minus_decay,
+                     eps, update, fault);
+  G2V_CHECK_LAUNCH();
+  if (update) {
+    hipLaunchKernelGGL(vq_ema_rows_kernel, dim3(cdiv((int64_t)K * 64, 256)), dim3(256), 0, (hipStream_t)stream, stats,
+                       ema_cluster_size, ema_w, codebook, code_sqnorm, E, K, decay, one_minus_decay, fault);
+    G2V_CHECK_LAUNCH();
+  }
+  return G2V_OK;
+}
+
 extern "C" int g2v_vq_ema_update(const float* stats, const float* sse_partial, int n_sse_partial,
                                  float* ema_cluster_size, float* ema_w, float* codebook, float* code_sqnorm,
                                  float* scalars, int N_loss, int N_cnt, int E, int K, float beta, float decay,
                                  float eps, int update, g2v_stream_t stream) {
-  G2V_REQUIRE(stats && scalars, "null pointer");
-  G2V_REQUIRE(!update || (ema_cluster_size && ema_w && codebook && code_sqnorm), "null EMA state");
-  G2V_REQUIRE(N_loss > 0 && N_cnt > 0 && E > 0 && K > 0, "non-positive size");
-  const unsigned* fault = g2v_internal_persist_fault_ptr();
-  hipLaunchKernelGGL(vq_ema_scalars_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, stats, sse_partial,
-                     sse_partial ? n_sse_partial : 0, ema_cluster_size, scalars, N_loss, N_cnt, E, K, beta, decay, eps,
-                     update, fault);
-  G2V_CHECK_LAUNCH();
-  if (update) {
-    hipLaunchKernelGGL(vq_ema_rows_kernel, dim3(cdiv((int64_t)K * 64, 256)), dim3(256), 0, (hipStream_t)stream, stats,
-                       ema_cluster_size, ema_w, codebook, code_sqnorm, E, K, decay, fault);
-    G2V_CHECK_LAUNCH();
-  }
-  return G2V_OK;
+  return vq_ema_update_launch(stats, sse_partial, n_sse_partial, ema_cluster_size, ema_w, codebook, code_sqnorm, scalars, N_loss,
+                              N_cnt, E, K, beta, decay, 1.0f - decay, eps, update, stream, "g2v_vq_ema_update");
+}
+
+extern "C" int g2v_vq_ema_update_exact(const float* stats, const float* sse_partial, int n_sse_partial,
+                                       float* ema_cluster_size, float* ema_w, float* codebook, float* code_sqnorm,
+                                       float* scalars, int N_loss, int N_cnt, int E, int K, float beta, double decay,
+                                       float eps, int update, g2v_stream_t stream) {
+  return vq_ema_update_launch(stats, sse_partial, n_sse_partial, ema_cluster_size, ema_w, codebook, code_sqnorm, scalars, N_loss,
+                              N_cnt, E, K, beta, (float)decay, (float)(1.0 - decay), eps, update, stream, "g2v_vq_ema_update_exact");
 }
 
 extern "C" int g2v_vq_bwd(const float* g_quantized, const float* g_loss, const float* z, const float* codebook,

@@ -317,7 +317,8 @@ class _VQFn(torch.autograd.Function):
         idx, quant, _, sse = ops.vq_assign(flat, z, W, wsq)
         stats = ops.vq_stats(idx, flat, K)
         scalars = ops.vq_ema_update(stats, sse, mod._ema_cluster_size, mod._ema_w.data, W, wsq, N, N, E, K,
-                                    mod._commitment_cost, mod._decay, mod._epsilon, mod.training)
+                                    mod._commitment_cost, mod._decay, mod._epsilon, mod.training,
+                                    exact_decay=getattr(mod, "_exact_decay", False))
         encodings = torch.zeros((N, K), dtype=torch.float32, device=z.device)
         encodings.scatter_(1, idx.unsqueeze(1), 1.0)     # layout glue: the (N,K) one-hot callers argmax over (:1246-1250)
         ctx.set_materialize_grads(False)

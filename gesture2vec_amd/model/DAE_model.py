@@ -1,7 +1,10 @@
 """Part a: frame-level denoising autoencoder -- mirror of `scripts/model/DAE_model.py::DAE_Network` (:22-114) on the
 MI355X dense-layer kernels.  Dropout(0.2) -> Linear(motion_dim, latent) + ReLU -> Linear(latent, motion_dim).
 state_dict keys `encoder.0.*`, `decoder.0.*` as in the reference.  Sentinels: latent_dim == -1 is the identity
-(:52-55), latent_dim == -2 is a linear 200-d bottleneck with 30 % dropout (:58-66)."""
+(:52-55), latent_dim == -2 is a linear 200-d bottleneck with 30 % dropout (:58-66).
+
+`VQ_Frame` (:118-275) with its own `VQ_Payam_EMA` (:351-482) is the frame-level QUANTISED autoencoder (autoencoder_vq "True"):
+Dropout(0.5) -> Linear -> BatchNorm1d (`bachnorm`, the reference's spelling) -> nearest of K codes (EMA codebook) -> Linear."""
 from __future__ import annotations
 
 import torch
@@ -9,6 +12,7 @@ import torch.nn as nn
 
 from .. import functional as Fn
 from .. import ops
+from .Autoencoder_VQVAE_model import _VQFn
 
 
 class DAE_Network(nn.Module):
@@ -67,3 +71,217 @@ class DAE_Network(nn.Module):
         out = self.decode(lat)
         out = torch.unsqueeze(out, 2)
         return (out, lat.detach().clone()) if get_latent else out
+
+
+class VQ_Payam_EMA(nn.Module):
+    """The frame-level EMA quantiser (reference DAE_model.py:351-482).  It is not Part b's class: the codebook starts
+    uniform(-1/K, 1/K), and `pre_linear` is part of the state_dict but NOT applied -- distances, loss and straight-through all act
+    on the input rows.  forward(inputs) -> (loss, quantized, perplexity, encodings).  `_ema_w`, `_embedding.weight` and
+    `pre_linear.*` never receive a gradient (the reference re-creates the first two every training forward, so its optimiser never
+    moves them either); here they are updated in place by the kernels."""
+
+    def __init__(self, num_embeddings: int, embedding_dim: int, commitment_cost: float, decay: float, epsilon: float = 1e-5):
+        super().__init__()
+        self._embedding_dim, self._num_embeddings = embedding_dim, num_embeddings
+        self.pre_linear = nn.Linear(embedding_dim, embedding_dim)
+        self._embedding = nn.Embedding(num_embeddings, embedding_dim)
+        self._embedding.weight.data.uniform_(-1 / num_embeddings, 1 / num_embeddings)      # :383-385
+        self._commitment_cost = commitment_cost
+        self.register_buffer("_ema_cluster_size", torch.zeros(num_embeddings))
+        self._ema_w = nn.Parameter(torch.Tensor(num_embeddings, embedding_dim))
+        self._ema_w.data.normal_()
+        self._decay, self._epsilon = decay, epsilon
+        # 1 - decay as torch forms the Python scalar (in double): a cluster size that starts from ZERO is (1 - decay) count after the
+        # first update, so the 9.3e-7 between that and 1.0f - 0.99f reaches the second step's codebook and loss undiluted
+        self._exact_decay = True
+        for p in (self._ema_w, self._embedding.weight, self.pre_linear.weight, self.pre_linear.bias):
+            p.requires_grad_(False)
+
+    def forward(self, inputs: torch.Tensor):
+        return _VQFn.apply(inputs, self, False)
+
+
+class VQ_Frame(nn.Module):
+    """forward(x) -> (out (B,D,1), loss_vq, perplexity); forward(x, Inference=True) -> (out, latent, encodings (N,K) one-hot).
+
+    Two routes behind one forward, chosen by the attribute `route` = "auto" | "fused" | "staged":
+      staged  the per-operator kernels under autograd (linear, batchnorm, the quantiser node, linear): every shape, eval mode,
+              `skip_vq`; the yardstick of the fused kernel.
+      fused   training: g2v_vqframe_step, forward AND backward of the batch in one launch.  The backward needs the target, so the
+              launch is driven by `fused_step` (train_iter_DAE calls it); a training `forward` on route "fused" says so.
+              eval: g2v_vqframe_infer serves `codes`, `encode` and `forward(x, Inference=True)`.
+      auto    asks g2v_vqframe_plan (ops.vqframe_plan) -- here, in `resolve`, and nowhere else."""
+
+    route = "auto"
+
+    def __init__(self, motion_dim: int, latent_dim: int, vae: bool, vq_components: int):
+        super().__init__()
+        if vae:
+            raise NotImplementedError("VQ_Frame(vae=True) (the frame-level variational block, VAE_fc_mean / VAE_fc_std / "
+                                      "VAE_fc_decoder) is out of scope; vae=False is served")
+        self.encoder = nn.Sequential(nn.Linear(motion_dim, latent_dim))
+        nn.init.xavier_normal_(self.encoder[0].weight)
+        self.bachnorm = nn.BatchNorm1d(latent_dim)
+        self.skip_vq = False
+        self.vq_components = vq_components
+        self.commitment_cost = 0.25
+        self.vq_layer = VQ_Payam_EMA(self.vq_components, latent_dim, self.commitment_cost, 0.99)
+        self.gs_soft = False
+        self.decoder = nn.Sequential(nn.Linear(latent_dim, motion_dim))
+        nn.init.xavier_normal_(self.decoder[0].weight)
+        self.dropout = nn.Dropout()                # p = 0.5; container for p only, masks come from the Philox kernel
+        self.vae = vae
+        self._explicit_keep = None
+        self._rng_counter = None
+        self.rng_seed = 0
+        self._pending_batches = 0                  # training forwards not yet added to bachnorm.num_batches_tracked
+        self._routes = {}
+
+    # ---- bookkeeping -------------------------------------------------------------------------------------------------------
+    def set_dropout_mask(self, keep):
+        """Explicit uint8 keep mask for the next training forwards (parity tests)."""
+        self._explicit_keep = keep
+
+    def state_dict(self, *args, **kwargs):
+        # num_batches_tracked counts training forwards; they are counted on the host and added here, not by a launch per iteration
+        if self._pending_batches:
+            self.bachnorm.num_batches_tracked += self._pending_batches
+            self._pending_batches = 0
+        return super().state_dict(*args, **kwargs)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._pending_batches = 0
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _dims(self):
+        e = self.encoder[0]
+        return e.in_features, e.out_features, self.vq_components
+
+    def resolve(self, rows: int, training: bool) -> str:
+        """"fused" or "staged" for a call of `rows` frames; `auto` takes the plan's answer.  An explicit "fused" that the kernel does
+        not admit raises with the plan's reason."""
+        if self.route not in ("auto", "fused", "staged"):
+            raise ValueError(f"VQ_Frame.route must be 'auto', 'fused' or 'staged', got {self.route!r}")
+        if self.route == "staged":
+            return "staged"
+        key = (rows, training)
+        if key not in self._routes:
+            self._routes[key] = ops.vqframe_plan(rows, *self._dims(), training)
+        auto, fused_ok, reason = self._routes[key]
+        if self.route == "fused":
+            if not fused_ok:
+                raise ValueError(f"VQ_Frame.route = 'fused': {reason}")
+            return "fused"
+        if auto == "":
+            raise ValueError(f"VQ_Frame: {reason}")
+        return auto
+
+    def _rows(self, x: torch.Tensor) -> torch.Tensor:
+        D = self.encoder[0].in_features
+        if not x.is_cuda:
+            raise RuntimeError("VQ_Frame runs on the MI355X kernels only (no CPU fallback)")
+        return x.reshape(-1, D).contiguous()
+
+    def _keep(self, inp: torch.Tensor):
+        if self._explicit_keep is not None:
+            return self._explicit_keep
+        if self._rng_counter is None or self._rng_counter.device != inp.device:
+            self._rng_counter = torch.zeros(1, dtype=torch.int64, device=inp.device)
+        return ops.keep_mask(torch.empty(inp.shape, dtype=torch.uint8, device=inp.device), 1.0 - self.dropout.p, self.rng_seed,
+                             self._rng_counter)
+
+    def _train_input(self, x: torch.Tensor) -> torch.Tensor:
+        inp = torch.squeeze(x)
+        if inp.dim() != 2 or inp.shape[0] < 2:
+            raise ValueError("VQ_Frame in training needs a batch of at least 2 frames (BatchNorm1d on batch statistics; squeeze "
+                             f"drops the row axis of a single frame), got {tuple(x.shape)}")
+        if not inp.is_cuda:
+            raise RuntimeError("VQ_Frame runs on the MI355X kernels only (no CPU fallback)")
+        return inp.contiguous()
+
+    def _infer_args(self):
+        e, bn, q = self.encoder[0], self.bachnorm, self.vq_layer
+        return (e.weight.data, e.bias.data, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, q._embedding.weight.data)
+
+    # ---- eval-mode entry points ----------------------------------------------------------------------------------------------
+    def _encode_staged(self, rows: torch.Tensor) -> torch.Tensor:
+        e, bn = self.encoder[0], self.bachnorm
+        y = ops.linear_fwd(rows, e.weight.data, e.bias.data)
+        return ops.batchnorm_fwd(y, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, False, False)[0]
+
+    def encode(self, x: torch.Tensor) -> torch.Tensor:
+        """The eval-mode z = bachnorm(encoder(x)) of any number of frames, (N,D) or (N,D,1) -> (N,L): what the datasets would call."""
+        rows = self._rows(x)
+        if self.resolve(rows.shape[0], False) == "fused":
+            return ops.vqframe_infer(rows, *self._infer_args(), want_latent=True)[1]
+        return self._encode_staged(rows)
+
+    def codes(self, x: torch.Tensor) -> torch.Tensor:
+        """int64 code ids (N,) of any number of frames in eval mode; the (N,K) one-hot is never formed."""
+        rows = self._rows(x)
+        if self.resolve(rows.shape[0], False) == "fused":
+            return ops.vqframe_infer(rows, *self._infer_args())[0]
+        z, W = self._encode_staged(rows), self.vq_layer._embedding.weight.data
+        return ops.vq_assign(z, z, W, ops.vq_code_sqnorm(W))[0]
+
+    # ---- the fused training step ---------------------------------------------------------------------------------------------
+    def trainable(self):
+        e, bn, d = self.encoder[0], self.bachnorm, self.decoder[0]
+        return [e.weight, e.bias, bn.weight, bn.bias, d.weight, d.bias]
+
+    def fused_step(self, x: torch.Tensor, target: torch.Tensor, grads, want_latent: bool = False, want_out: bool = False):
+        """One launch: forward and backward of the batch (g2v_vqframe_step).  `grads`: six buffers for the gradients of
+        `trainable()`.  The running statistics and the quantiser's state are updated in place.
+        -> (scalars (3,) = reconstruction mse, loss_vq, perplexity; ids (B,); latent or None; out (B,D) or None)"""
+        if not self.training or self.skip_vq:
+            raise RuntimeError("VQ_Frame.fused_step is the training step with the quantiser on")
+        inp = self._train_input(x)
+        tgt = torch.squeeze(target).contiguous()
+        e, bn, d, q = self.encoder[0], self.bachnorm, self.decoder[0], self.vq_layer
+        momentum = 0.1 if bn.momentum is None else bn.momentum
+        keep = self._keep(inp)
+        res = ops.vqframe_step(inp, tgt, keep, 1.0 / (1.0 - self.dropout.p), e.weight.data, e.bias.data, bn.weight.data,
+                               bn.bias.data, bn.running_mean, bn.running_var, momentum, d.weight.data, d.bias.data,
+                               q._embedding.weight.data, q._ema_w.data, q._ema_cluster_size, q._commitment_cost, q._decay,
+                               q._epsilon, grads, want_latent=want_latent, want_out=want_out)
+        self._pending_batches += 1
+        return res
+
+    # ---- forward -------------------------------------------------------------------------------------------------------------
+    def forward(self, x: torch.Tensor, Inference: bool = False):
+        if self.training:
+            inp = self._train_input(x)
+            if self.route == "fused" and not self.skip_vq:
+                raise RuntimeError("VQ_Frame.route = 'fused': the fused training step computes forward and backward in one launch and "
+                                   "needs the target; call fused_step(x, target, grads) or train_iter_DAE, or set route = 'staged'")
+            keep, scale = self._keep(inp), 1.0 / (1.0 - self.dropout.p)
+            self._pending_batches += 1
+        else:
+            inp = torch.squeeze(x)
+            if not inp.is_cuda:
+                raise RuntimeError("VQ_Frame runs on the MI355X kernels only (no CPU fallback)")
+            if inp.dim() != 2:
+                raise ValueError(f"VQ_Frame.forward expects (B, motion_dim, 1) frames with B >= 2, got {tuple(x.shape)}; "
+                                 "codes(x) / encode(x) take any number of frames")
+            inp = inp.contiguous()
+            keep, scale = None, 1.0
+            if Inference and not self.skip_vq and self.resolve(inp.shape[0], False) == "fused":
+                d = self.decoder[0]
+                ids, latent, out = ops.vqframe_infer(inp, *self._infer_args(), w_dec=d.weight.data, b_dec=d.bias.data,
+                                                     want_latent=True, want_out=True)
+                encodings = torch.zeros((inp.shape[0], self.vq_components), dtype=torch.float32, device=inp.device)
+                encodings.scatter_(1, ids.unsqueeze(1), 1.0)       # layout glue: the one-hot the reference's callers argmax over
+                return out.unsqueeze(2), latent, encodings
+        e, bn, d = self.encoder[0], self.bachnorm, self.decoder[0]
+        y = Fn.linear(inp, e.weight, e.bias, keep=keep, scale=scale)
+        z = Fn.BatchNormReluFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, self.training, False)
+        latent = z.detach().clone()
+        encodings = None
+        if not self.skip_vq:
+            loss_vq, z, perplexity_vq, encodings = self.vq_layer(z)
+        else:
+            loss_vq, perplexity_vq = torch.tensor(0), torch.tensor(0)
+        out = torch.unsqueeze(Fn.linear(z, d.weight, d.bias), 2)
+        if Inference:
+            return out, latent, encodings
+        return out, loss_vq, perplexity_vq

@@ -547,13 +547,15 @@ def vq_stats(idx, flat, K, out=None):
 
 
 def vq_ema_update(stats, sse_partial, ema_cluster_size, ema_w, codebook, code_sqnorm, N_loss, N_cnt, E, K,
-                  beta, decay, eps, update, scalars=None):
+                  beta, decay, eps, update, scalars=None, exact_decay=False):
+    """exact_decay: the weight of the new statistics is (float)(1.0 - decay) formed in double, as torch forms the reference's Python
+    scalar (g2v_vq_ema_update_exact); otherwise 1.0f - (float)decay, what the chunk quantiser's path has always computed"""
     if scalars is None:
         scalars = torch.empty((2,), dtype=torch.float32, device=stats.device)
-    check(_lib_().g2v_vq_ema_update(_p(stats), _p(sse_partial), 0 if sse_partial is None else sse_partial.numel(),
-                                    _p(ema_cluster_size), _p(ema_w), _p(codebook), _p(code_sqnorm), _p(scalars),
-                                    N_loss, N_cnt, E, K, float(beta), float(decay), float(eps), int(update),
-                                    _stream()), "vq_ema_update")
+    fn = _lib_().g2v_vq_ema_update_exact if exact_decay else _lib_().g2v_vq_ema_update
+    check(fn(_p(stats), _p(sse_partial), 0 if sse_partial is None else sse_partial.numel(),
+             _p(ema_cluster_size), _p(ema_w), _p(codebook), _p(code_sqnorm), _p(scalars),
+             N_loss, N_cnt, E, K, float(beta), float(decay), float(eps), int(update), _stream()), "vq_ema_update")
     return scalars
 
 
@@ -1916,3 +1918,67 @@ def neighbor_ranks(x, z, idx, self_rows=None):
     check(lib.g2v_neighbor_ranks(_p(x), int(x.stride(0)), N, _p(z), int(z.stride(0)), M, d, _p(self_rows), _p(idx), k, _p(rank),
                                  _p(redecided), _p(ws), nb, _stream()), fn)
     return rank, redecided
+
+
+# ------------------------------------------------------------------- the frame-level quantised autoencoder of Part a (vq_frame.hip)
+def vqframe_plan(B, D, L, K, training):
+    """g2v_vqframe_plan in words -> (route, fused_ok, reason): route "fused" / "staged" is what `auto` takes, "" a refused shape;
+    fused_ok says whether the fused kernel of that mode admits the shape at all."""
+    lib, c = _lib_(), _lib.CONSTANTS
+    args = (int(B), int(D), int(L), int(K), int(bool(training)))
+    r = int(lib.g2v_vqframe_plan(*args))
+    route = {c["G2V_VQFRAME_FUSED"]: "fused", c["G2V_VQFRAME_STAGED"]: "staged"}.get(r & 255, "")
+    return route, bool(r & c["G2V_VQFRAME_FUSED_OK"]), lib.g2v_vqframe_plan_reason(*args).decode()
+
+
+def vqframe_step(x, target, keep, scale, w_enc, b_enc, bn_w, bn_b, running_mean, running_var, momentum, w_dec, b_dec, codebook,
+                 ema_w, ema_cs, commitment, decay, epsilon, grads, want_latent=False, want_out=False):
+    """g2v_vqframe_step: training forward + backward of one (B,D) batch in one launch.  grads: the six gradient buffers in the
+    order (w_enc, b_enc, bn_w, bn_b, w_dec, b_dec) -- slices of an optimiser's flat gradient, say.  Updates the running statistics
+    and the quantiser's state in place -> (scalars (3,) = mse, loss_vq, perplexity; ids int64 (B,); latent or None; out or None)."""
+    lib = _lib_()
+    B, D = x.shape
+    L, K = w_enc.shape[0], codebook.shape[0]
+    nb = int(lib.g2v_vqframe_workspace(B, D, L, K, 1))
+    if nb == 0:
+        raise ValueError("vqframe_step: " + lib.g2v_vqframe_plan_reason(B, D, L, K, 1).decode())
+    dev = x.device
+    ws = workspace(nb, dev, "vqframe_step")
+    scalars = torch.empty((3,), dtype=torch.float32, device=dev)
+    ids = torch.empty((B,), dtype=torch.int64, device=dev)
+    latent = torch.empty((B, L), dtype=torch.float32, device=dev) if want_latent else None
+    out = torch.empty((B, D), dtype=torch.float32, device=dev) if want_out else None
+    if keep is not None and tuple(_chk(keep, torch.uint8, "keep").shape) != (B, D):
+        raise ValueError(f"vqframe_step: keep must be ({B}, {D}), got {tuple(keep.shape)}")
+    if tuple(target.shape) != (B, D):
+        raise ValueError(f"vqframe_step: target must be ({B}, {D}), got {tuple(target.shape)}")
+    for g, ref in zip(grads, (w_enc, b_enc, bn_w, bn_b, w_dec, b_dec)):
+        if _chk(g, name="grad").numel() != ref.numel():
+            raise ValueError("vqframe_step: a gradient buffer does not match its parameter")
+    check(lib.g2v_vqframe_step(_p(_chk(x, name="x")), _p(_chk(target, name="target")), _p(keep), float(scale), _p(_chk(w_enc)),
+                               _p(_chk(b_enc)), _p(_chk(bn_w)), _p(_chk(bn_b)), _p(_chk(running_mean)), _p(_chk(running_var)),
+                               float(momentum), _p(_chk(w_dec)), _p(_chk(b_dec)), _p(_chk(codebook)), _p(_chk(ema_w)),
+                               _p(_chk(ema_cs)), float(commitment), float(decay), float(epsilon), *[_p(g) for g in grads],
+                               _p(scalars), _p(ids), _p(latent), _p(out), _p(ws), nb, B, D, L, K, _stream()), "vqframe_step")
+    return scalars, ids, latent, out
+
+
+def vqframe_infer(x, w_enc, b_enc, bn_w, bn_b, running_mean, running_var, codebook, w_dec=None, b_dec=None, want_latent=False,
+                  want_out=False):
+    """g2v_vqframe_infer: eval-mode code ids of N frames (running statistics, no dropout) -> (ids int64 (N,), latent or None, out or None)"""
+    lib = _lib_()
+    N, D = x.shape
+    L, K = w_enc.shape[0], codebook.shape[0]
+    nb = int(lib.g2v_vqframe_workspace(N, D, L, K, 0))
+    if nb == 0:
+        raise ValueError("vqframe_infer: " + lib.g2v_vqframe_plan_reason(N, D, L, K, 0).decode())
+    dev = x.device
+    ws = workspace(nb, dev, "vqframe_infer")
+    ids = torch.empty((N,), dtype=torch.int64, device=dev)
+    latent = torch.empty((N, L), dtype=torch.float32, device=dev) if want_latent else None
+    out = torch.empty((N, D), dtype=torch.float32, device=dev) if want_out else None
+    check(lib.g2v_vqframe_infer(_p(_chk(x, name="x")), N, _p(_chk(w_enc)), _p(_chk(b_enc)), _p(_chk(bn_w)), _p(_chk(bn_b)),
+                                _p(_chk(running_mean)), _p(_chk(running_var)), _p(_chk(codebook)),
+                                _p(w_dec) if want_out else None, _p(b_dec) if want_out else None, _p(ids), _p(latent), _p(out),
+                                _p(ws), nb, D, L, K, _stream()), "vqframe_infer")
+    return ids, latent, out

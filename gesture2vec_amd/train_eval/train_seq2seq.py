@@ -335,20 +335,59 @@ _GRAPH_SLOTS = 4
 
 
 def train_iter_DAE(args, epoch: int, noisy_poses: torch.Tensor, target_poses: torch.Tensor, net: torch.nn.Module, optim):
-    """One training iteration of the Part-a frame DAE (reference :161-241, autoencoder_vq/vae == "False"):
-    MSE(outputs, target) -> backward -> clip_grad_norm_(5) + Adam (fused in `optim`, a gesture2vec_amd.flat.FlatClipAdam)."""
+    """One training iteration of a Part-a frame model (reference :161-241): MSE(outputs, target) [+ loss_vq] -> backward ->
+    clip_grad_norm_(5) + Adam (fused in `optim`, a gesture2vec_amd.flat.FlatClipAdam).
+    autoencoder_vq "False": DAE_Network -> {"loss": loss}.  autoencoder_vq "True" (VQ_Frame): ({"loss": reconstruction loss alone},
+    perplexity tensor), as the reference returns it.  autoencoder_vae "True" raises."""
     from ..flat import FlatClipAdam
     from ..functional import mse_loss
     if not isinstance(optim, FlatClipAdam):
         raise TypeError("use gesture2vec_amd.flat.FlatClipAdam (clip + Adam are one fused HIP launch)")
-    if getattr(args, "autoencoder_vq", "False") == "True" or getattr(args, "autoencoder_vae", "False") == "True":
-        raise NotImplementedError("VQ_Frame / VAE_Network variants of Part a are outside the accelerated hot path")
+    if getattr(args, "autoencoder_vae", "False") == "True":
+        raise NotImplementedError("autoencoder_vae 'True' (VAE_Network, VQ_Frame(vae=True)) is outside the accelerated hot path")
+    if getattr(args, "autoencoder_vq", "False") == "True":
+        return _train_iter_vq_frame(noisy_poses, target_poses, net, optim)
     optim.zero_grad()
     outputs = net(noisy_poses)
     loss = mse_loss(outputs, target_poses)
     loss.backward()
     optim.step()
     return {"loss": loss.item()}
+
+
+def _train_iter_vq_frame(noisy_poses, target_poses, net, optim):
+    """The VQ_Frame iteration.  On the fused route (VQ_Frame.resolve) it is three launches and one read-back: the keep mask, the
+    step -- which writes the six gradients straight into the optimiser's flat gradient --, clip + Adam, and the loss's .item().
+    The quantiser's tensors carry no gradient on either route and are not in the optimiser."""
+    from ..functional import mse_loss
+    from ..model.DAE_model import VQ_Frame
+    if not isinstance(net, VQ_Frame):
+        raise TypeError("autoencoder_vq 'True' trains a gesture2vec_amd.model.DAE_model.VQ_Frame")
+    fp = optim.fp
+    rows = noisy_poses.shape[0]
+    if not net.training:
+        raise RuntimeError("train_iter_DAE needs the model in training mode")
+    params = net.trainable()
+    fused = (not net.skip_vq and net.resolve(rows, True) == "fused")
+    if fused and not (len(fp.params) == len(params) and all(a is b for a, b in zip(fp.params, params))):
+        if net.route == "fused":
+            raise ValueError("VQ_Frame.route = 'fused': the optimiser must hold exactly the model's parameters, "
+                             "FlatClipAdam(net.parameters(), ...)")
+        fused = False
+    optim.zero_grad()
+    if fused:
+        grads = [fp.gflat[o:o + p.numel()] for p, o in zip(fp.params, fp.offsets)]
+        scalars = net.fused_step(noisy_poses, target_poses, grads)[0]
+        for p, g in zip(params, grads):
+            p.grad = g.view(p.shape)
+        fp.skipped = []
+        fp.step(optim.lr, optim.betas, optim.eps, optim.max_norm)
+        return {"loss": scalars[0].item()}, scalars[2]
+    outputs, vq_loss, perplexity_vq = net(noisy_poses)
+    rec_loss = mse_loss(outputs, target_poses)
+    (rec_loss + vq_loss).backward()
+    optim.step()
+    return {"loss": rec_loss.item()}, perplexity_vq
 
 
 def _code_loss(outputs, codes):

@@ -425,6 +425,13 @@ int g2v_vq_ema_update(const float* stats, const float* sse_partial, int n_sse_pa
                       float* ema_cluster_size, float* ema_w, float* codebook, float* code_sqnorm,
                       float* scalars, int N_loss, int N_cnt, int E, int K,
                       float beta, float decay, float eps, int update, g2v_stream_t stream);
+/* The same with the weight of the new statistics formed as torch forms the reference's Python scalar: (float)(1.0 - decay) in double,
+ * where g2v_vq_ema_update takes 1.0f - (float)decay (9.3e-7 apart at decay 0.99; it shows where a cluster size starts from zero,
+ * as the frame-level quantiser of Part a does). */
+int g2v_vq_ema_update_exact(const float* stats, const float* sse_partial, int n_sse_partial,
+                            float* ema_cluster_size, float* ema_w, float* codebook, float* code_sqnorm,
+                            float* scalars, int N_loss, int N_cnt, int E, int K,
+                            float beta, double decay, float eps, int update, g2v_stream_t stream);
 
 /* K5': gz = g_quantized + g_loss * 2*beta/(N*E) * (z - W[idx])   (autograd of :1285-1292).
  * g_loss is a device scalar (d total / d loss_vq), g_quantized may be NULL.
@@ -1743,6 +1750,45 @@ int g2v_softdtw_alignment(const float* x, int64_t R, int T, const double* z, int
                           g2v_stream_t stream);
 int g2v_softdtw_grad(const float* x, int64_t N, int T, const int64_t* rows, int64_t R, const double* weights, const double* z, int S,
                      int F, double gamma, double* value, double* grad, void* workspace, size_t workspace_bytes, g2v_stream_t stream);
+
+/* ---- The frame-level quantised autoencoder of Part a (VQ_Frame, reference scripts/model/DAE_model.py:118-275, :351-482):
+ *   x (B,D) -> Dropout -> y = x We^T + be -> z = BatchNorm1d(y) -> id = argmin_k (|z|^2 + |e_k|^2) - 2 z.e_k (lowest k on ties),
+ *   q = e_id -> out = q Wd^T + bd;  loss = mse(out, target) + commitment mse(q.detach(), z);  the quantiser's state moves by the EMA
+ *   of the batch's code statistics (counts, Laplace smoothing, dw = onehot^T z), never by a gradient.  No pre_linear is applied.
+ * g2v_vqframe_plan(B, D, L, K, training): host arithmetic only.  Bits 0-7: what `auto` takes, G2V_VQFRAME_FUSED (training: the
+ *   one-workgroup step g2v_vqframe_step; eval, B = rows: the grid kernel g2v_vqframe_infer), G2V_VQFRAME_STAGED (the per-operator
+ *   kernels: linear, batchnorm, vq_assign ...), or G2V_VQFRAME_REFUSED (0: no route, e.g. B < 2 in training).  G2V_VQFRAME_FUSED_OK
+ *   is set where the fused kernel admits the shape whatever `auto` takes: training 2 <= B, L <= 256, K <= 256 and the LDS layout
+ *   (vq_frame.hip) within 160 KB -- B <= 256 at D = 135, L <= 45, K <= 128 --; eval D, L <= 256, K <= 4096.  `auto` is FUSED only
+ *   where it was measured faster.  g2v_vqframe_plan_reason: the same answer in words (a static string).
+ * g2v_vqframe_workspace: bytes of workspace for the fused kernel of that mode (0: not admitted); g2v_vqframe_step_lds: the
+ *   step's dynamic LDS in bytes (0: not admitted).
+ * g2v_vqframe_step: training forward and backward of one batch in ONE workgroup.  keep: uint8 (B,D) or NULL (no dropout), kept
+ *   inputs are multiplied by scale.  In place: running_mean / running_var (momentum; unbiased variance), codebook, ema_w (K,L) and
+ *   ema_cluster_size (K), updated AFTER q was taken from the old codebook.  Writes the six gradients (no dx), scalars[3] = (mse,
+ *   loss_vq, perplexity), ids int64[B], and, where not NULL, latent = z (B,L) and out (B,D).  No atomics: the same input gives the
+ *   same bits.  G2V_ERR_UNSUPPORTED for a shape the plan does not admit.
+ * g2v_vqframe_infer: the eval-mode forward of N rows (running statistics, no dropout) over independent tiles of 16 rows: ids
+ *   int64[N], and, where not NULL, latent (N,L) and out (N,D) (then w_dec, b_dec).  A row's bits do not depend on the other rows. */
+#define G2V_VQFRAME_REFUSED 0
+#define G2V_VQFRAME_FUSED 1
+#define G2V_VQFRAME_STAGED 2
+#define G2V_VQFRAME_FUSED_OK 256
+int g2v_vqframe_plan(int B, int D, int L, int K, int training);
+const char* g2v_vqframe_plan_reason(int B, int D, int L, int K, int training);
+size_t g2v_vqframe_workspace(int B, int D, int L, int K, int training);
+size_t g2v_vqframe_step_lds(int B, int D, int L, int K);
+int g2v_vqframe_step(const float* x, const float* target, const uint8_t* keep, float scale, const float* w_enc,
+                     const float* b_enc, const float* bn_weight, const float* bn_bias, float* running_mean,
+                     float* running_var, float momentum, const float* w_dec, const float* b_dec, float* codebook,
+                     float* ema_w, float* ema_cluster_size, float commitment, double decay, double epsilon,
+                     float* g_w_enc, float* g_b_enc, float* g_bn_weight, float* g_bn_bias, float* g_w_dec, float* g_b_dec,
+                     float* scalars, int64_t* ids, float* latent, float* out, void* workspace, size_t workspace_bytes,
+                     int B, int D, int L, int K, g2v_stream_t stream);
+int g2v_vqframe_infer(const float* x, int64_t N, const float* w_enc, const float* b_enc, const float* bn_weight,
+                      const float* bn_bias, const float* running_mean, const float* running_var, const float* codebook,
+                      const float* w_dec, const float* b_dec, int64_t* ids, float* latent, float* out, void* workspace,
+                      size_t workspace_bytes, int D, int L, int K, g2v_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -6,9 +6,13 @@
 Same surface: `init_model(args, lang_model, pose_dim, _device)` -> (DAE_Network(input_motion_dim, hidden_size), MSE),
 `train_epochs` (Adam(lr, betas=(0.5, 0.999)) :190-192, checkpoint every 20 epochs with the keys
 `args, epoch, lang_model, pose_dim, gen_dict` and the name `<name>_H<hidden>_checkpoint_<epoch>.bin` :203-222),
-`evaluate_testset` (mean MSE of the eval-mode reconstruction :314-371), `main`.  Only the plain denoising autoencoder
-branch (`autoencoder_vq == autoencoder_vae == "False"`, config/DAE.yml) is on the accelerated path; `VQ_Frame` /
-`VAE_Network` raise.  The LMDB frame dataset is not ported: `--synthetic` feeds (noisy, original) frame batches of shape
+`evaluate_testset` (mean MSE of the eval-mode reconstruction :314-371), `main`.  The plain denoising autoencoder
+(`autoencoder_vq == autoencoder_vae == "False"`, config/DAE.yml) and the frame-level quantised autoencoder `VQ_Frame`
+(`autoencoder_vq: "True"`, :102-108) are served; `autoencoder_vae: "True"` (`VAE_Network`, `VQ_Frame(vae=True)`) raises.  In the
+VQ mode every batch trains twice (:276-284) -- on (original, original), whose reconstruction loss and perplexity are the two
+per-iteration curves, then on (noisy, original) -- and each epoch starts by writing the curves so far to
+`<model_save_path>/plots/Error_Epoch(<n>).npz` (arrays `recon_error`, `perplexity`) where the reference saves the picture (:564).
+The LMDB frame dataset is not ported: `--synthetic` feeds (noisy, original) frame batches of shape
 (B, input_motion_dim, 1) like `TrinityDataset_DAE` does (original = N(0,1) frames, noisy = original + 0.1 N(0,1))."""
 from __future__ import annotations
 
@@ -29,7 +33,7 @@ for _p in (_HERE, _ROOT):
         sys.path.insert(0, _p)
 
 from config.parse_args import parse_args  # noqa: E402
-from model.DAE_model import DAE_Network  # noqa: E402
+from model.DAE_model import DAE_Network, VQ_Frame  # noqa: E402
 from train_eval.train_seq2seq import train_iter_DAE  # noqa: E402
 import utils.train_utils  # noqa: E402
 from utils.average_meter import AverageMeter  # noqa: E402
@@ -42,8 +46,11 @@ Global_loss_eval = []
 
 
 def init_model(args, lang_model, pose_dim: int, _device):
-    if args.autoencoder_vq == "True" or args.autoencoder_vae == "True":
-        raise NotImplementedError("VQ_Frame / VAE_Network (frame-level VQ / VAE) are outside the accelerated hot path")
+    if args.autoencoder_vae == "True":
+        raise NotImplementedError("autoencoder_vae: 'True' (VAE_Network, VQ_Frame(vae=True)) is outside the accelerated hot path")
+    if args.autoencoder_vq == "True":
+        network = VQ_Frame(args.input_motion_dim, args.hidden_size, False, int(args.autoencoder_vq_components)).to(_device)
+        return network, Fn.mse_loss
     network = DAE_Network(args.input_motion_dim, args.hidden_size).to(_device)
     return network, Fn.mse_loss
 
@@ -71,13 +78,25 @@ def evaluate_testset(test_data_loader, generator, loss_fn, args) -> float:
     with torch.no_grad():
         for noisy, original in test_data_loader:
             noisy, original = noisy.to(device), original.to(device)
-            out_poses = generator(noisy)
+            if args.autoencoder_vq == "True":
+                out_poses, _vq_loss, _perplexity = generator(noisy)
+            else:
+                out_poses = generator(noisy)
             loss = loss_fn(out_poses, original)
             losses.update(loss.item(), original.size(0))
     generator.train(True)
     logging.info("[VAL] loss: {:.3f} / {:.1f}s".format(losses.avg, time.time() - start))
     Global_loss_eval.append(losses.avg)
     return losses.avg
+
+
+def save_curves(args, epoch: int, recon_error, perplexity) -> str:
+    """The two per-iteration curves of the VQ mode, as data, where the reference's plot_embedding saves Error_Epoch(<n>).png"""
+    address = os.path.join(args.model_save_path, "plots")
+    os.makedirs(address, exist_ok=True)
+    address = os.path.join(address, "Error_Epoch({}).npz".format(epoch))
+    np.savez(address, recon_error=np.asarray(recon_error, dtype=np.float64), perplexity=np.asarray(perplexity, dtype=np.float64))
+    return address
 
 
 def train_epochs(args, train_data_loader, test_data_loader, lang_model, pose_dim: int, trial_id=None) -> None:
@@ -88,7 +107,11 @@ def train_epochs(args, train_data_loader, test_data_loader, lang_model, pose_dim
     generator, loss_fn = init_model(args, lang_model, pose_dim, device)
     gen_optimizer = FlatClipAdam(generator.parameters(), lr=args.learning_rate, betas=(0.5, 0.999))   # clip_grad_norm_(5) fused
     global_iter = 0
+    vq = args.autoencoder_vq == "True"
+    train_res_recon_error, train_res_perplexity = [], []
     for epoch in range(1, args.epochs + 1):
+        if vq:
+            save_curves(args, epoch, train_res_recon_error, train_res_perplexity)
         evaluate_testset(test_data_loader, generator, loss_fn, args)
         if epoch % save_model_epoch_interval == 0 and epoch > 0:
             save_name = "{}/{}_H{}_checkpoint_{:03d}.bin".format(args.model_save_path, args.name, args.hidden_size, epoch)
@@ -98,7 +121,16 @@ def train_epochs(args, train_data_loader, test_data_loader, lang_model, pose_dim
         for iter_idx, (noisy, original) in enumerate(train_data_loader, 0):
             global_iter += 1
             batch_size = original.size(0)
-            loss = train_iter_DAE(args, epoch, noisy.to(device), original.to(device), generator, gen_optimizer)
+            noisy, original = noisy.to(device), original.to(device)
+            if vq:
+                # :276-284 -- the clean pass feeds the two curves; the second result is a (dict, tensor) tuple there, so the
+                # reference's meters never see it: here it is unpacked and the meter gets the reconstruction loss
+                loss, perplexity = train_iter_DAE(args, epoch, original, original, generator, gen_optimizer)
+                train_res_recon_error.append(loss["loss"])
+                train_res_perplexity.append(perplexity.item())
+                loss, _ = train_iter_DAE(args, epoch, noisy, original, generator, gen_optimizer)
+            else:
+                loss = train_iter_DAE(args, epoch, noisy, original, generator, gen_optimizer)
             for m in loss_meters:
                 if m.name in loss:
                     m.update(loss[m.name], batch_size)
