@@ -19,6 +19,7 @@
 // Determinism: no atomics; every sum has a fixed order, so the same inputs give the same bits.
 // Served: E % 16 == 0, E <= 512 (g2v_vae_latent_ok); any B >= 1.
 #include "common.hpp"
+#include "vae_noise.hpp"      // philox_normal4 (the noise), vae_kl_finish_kernel (KLD = 0.5 sum(partials) / (B E))
 
 namespace g2v {
 namespace {
@@ -82,23 +83,6 @@ __device__ __forceinline__ void wave_gemm_t(f32x4 (&acc)[NT], const float* __res
 __device__ __forceinline__ int64_t seg_off(int64_t n, int c, int B, int H) {
   const int l = c / H;
   return ((int64_t)l * B + n) * H + (c - l * H);
-}
-
-// four normal deviates from one Philox block: two Box-Muller pairs; u in (0, 1] for the logarithm, 24-bit uniforms
-__device__ __forceinline__ void philox_normal4(int64_t g, uint64_t off, uint64_t seed, float (&out)[4]) {
-  uint32_t c[4];
-  philox4x32(g, off, seed, c);
-  constexpr float S = 1.0f / 16777216.0f;
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float u1 = ((float)(c[2 * p] >> 8) + 1.0f) * S;
-    const float u2 = (float)(c[2 * p + 1] >> 8) * S;
-    const float r = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(2.0f * u2, &sn, &cs);
-    out[2 * p] = r * cs;
-    out[2 * p + 1] = r * sn;
-  }
 }
 
 struct VaeFwdArgs {
@@ -219,19 +203,6 @@ __global__ __launch_bounds__(64 * NW) void vae_latent_fwd_kernel(VaeFwdArgs a) {
       store_d(t, acc[0]);
     }
   }
-}
-
-// KLD = 0.5 sum(partials) / (B E): one workgroup, thread t sums partials t, t + 256, ... in order, then a fixed tree.
-__global__ __launch_bounds__(256) void vae_kl_finish_kernel(const float* __restrict__ partial, int nblk, float half_inv_n,
-                                                            float* __restrict__ kl) {
-  __shared__ float red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float s = 0.f;
-  for (int j = tid; j < nblk; j += 256) s += partial[j];
-  s = wave_sum(s);
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (tid == 0) kl[0] = ((red[0] + red[1]) + (red[2] + red[3])) * half_inv_n;
 }
 
 struct VaeBwdArgs {

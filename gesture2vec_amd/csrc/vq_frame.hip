@@ -27,6 +27,7 @@
 //
 // g2v_vqframe_plan: host arithmetic only -- which route serves a shape and what `auto` takes.
 #include "common.hpp"
+#include "frame_tile.hpp"      // frame_ld (the ld(n) above), tile_mma, q_sum, quad_sum: shared with vae_frame.hip
 
 namespace g2v {
 namespace {
@@ -44,16 +45,14 @@ constexpr int VQF_AUTO_STEP_MAX_B = 256, VQF_AUTO_STEP_MAX_D = 135, VQF_AUTO_STE
 constexpr int64_t VQF_AUTO_INFER_MIN_ROWS = 1 << 20;
 constexpr int VQF_AUTO_INFER_MAX_D = 135, VQF_AUTO_INFER_MAX_L = 200, VQF_AUTO_INFER_MAX_K = 100;
 
-__host__ __device__ inline int vqf_ld(int n) { return ((n + 3) / 8) * 8 + 4; }
-
 struct VqfLayout {
   int ldl, ldd;
   size_t a, xh, wd, ec, ist, cs, hs, red, idx, total;      // offsets in floats, total in floats
 };
 __host__ __device__ inline VqfLayout vqf_layout(int B, int D, int L, int K) {
   VqfLayout o;
-  o.ldl = vqf_ld(L);
-  o.ldd = vqf_ld(D);
+  o.ldl = frame_ld(L);
+  o.ldd = frame_ld(D);
   const size_t za = (size_t)B * o.ldl, wa = (size_t)L * o.ldd;
   o.a = 0;
   o.xh = o.a + (za > wa ? za : wa);
@@ -66,53 +65,6 @@ __host__ __device__ inline VqfLayout vqf_layout(int B, int D, int L, int K) {
   o.idx = o.red + 48;
   o.total = o.idx + (B + 1) / 2;
   return o;
-}
-
-struct Side {
-  float sa, saa, sbb;      // this lane's sums of a, a^2, b^2 over its k
-};
-
-// One 16x16 output tile: acc[r] = sum_k A[i = 4 q + r][k] B[k][j = lane & 15], k ascending in steps of 4.  a_at(i, k) and b_at(k, j)
-// return 0 outside their matrices.
-template <class FA, class FB>
-__device__ __forceinline__ f32x4 tile_mma(int Kd, int lane, FA a_at, FB b_at, Side& s) {
-  const int i = lane & 15, q = lane >> 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  s.sa = s.saa = s.sbb = 0.f;
-  // eight k-steps' operands are fetched before the first of their MFMAs: the fetches are independent, so a wave pays one
-  // memory latency per eight steps (an operand read from global memory costs an L2 round trip), and the sums keep their order
-  constexpr int U = 8;
-  for (int k0 = 0; k0 < Kd; k0 += 4 * U) {
-    float a[U], b[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = k0 + 4 * u + q;
-      a[u] = k < Kd ? a_at(i, k) : 0.f;
-      b[u] = k < Kd ? b_at(k, i) : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (k0 + 4 * u < Kd) {      // (wave-uniform)
-        s.sa += a[u];
-        s.saa = fmaf(a[u], a[u], s.saa);
-        s.sbb = fmaf(b[u], b[u], s.sbb);
-        acc = mfma16(a[u], b[u], acc);
-      }
-    }
-  }
-  return acc;
-}
-// sum over the four lanes (q = 0 .. 3) that share lane & 15, in every lane
-__device__ __forceinline__ float q_sum(float v) {
-  v += __shfl_xor(v, 16);
-  v += __shfl_xor(v, 32);
-  return v;
-}
-// sum over the four neighbouring lanes tid & 3 = 0 .. 3, in every lane
-__device__ __forceinline__ float quad_sum(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  return v;
 }
 
 struct VqfStepArgs {
@@ -471,7 +423,7 @@ struct VqfInferArgs {
 __global__ __launch_bounds__(64 * VQF_INFER_NW) void vqframe_infer_kernel(VqfInferArgs p) {
   extern __shared__ __align__(16) float smem[];
   const int D = p.D, L = p.L, K = p.K;
-  const int ldl = vqf_ld(L);
+  const int ldl = frame_ld(L);
   float* Z = smem;
   float* ZZ = Z + 16 * ldl;
   float* BD = ZZ + 16;
@@ -668,7 +620,7 @@ extern "C" int g2v_vqframe_infer(const float* x, int64_t N, const float* w_enc, 
   hipLaunchKernelGGL(vqframe_sqnorm_kernel, dim3(cdiv(K, 256)), dim3(256), 0, (hipStream_t)stream, codebook, K, L,
                      static_cast<float*>(workspace));
   G2V_CHECK_LAUNCH();
-  const size_t lds = (size_t)(16 * vqf_ld(L) + 16 + 32 * VQF_INFER_NW + 16) * sizeof(float);
+  const size_t lds = (size_t)(16 * frame_ld(L) + 16 + 32 * VQF_INFER_NW + 16) * sizeof(float);
   hipLaunchKernelGGL(vqframe_infer_kernel, dim3(cdiv(N, VQF_INFER_ROWS)), dim3(64 * VQF_INFER_NW), lds, (hipStream_t)stream, a);
   G2V_CHECK_LAUNCH();
   return G2V_OK;

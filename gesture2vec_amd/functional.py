@@ -38,8 +38,8 @@ class LinearFn(torch.autograd.Function):
         g = gy.contiguous().view(-1, N)
         if ctx.act == 1:                       # ReLU: gate the gradient with the saved output
             g = _ReluBwd.apply_mask(g, y)
-        elif ctx.act == 2:
-            raise NotImplementedError("tanh backward")
+        elif ctx.act == 2:                     # tanh: dpre = g (1 - y^2) from the saved output
+            g = ops.tanh_bwd(g, y)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.linear_bwd_data(g, w)
@@ -118,6 +118,34 @@ class LinearPairFn(torch.autograd.Function):
         if dx is not None and keep is not None:
             dx = ops.mask_mul(dx, keep, ctx.scale, positive_of=False)
         return (dx.view(ctx.xshape) if dx is not None else None), out[0], out[1], out[2], out[3], None, None
+
+
+class ReparamFn(torch.autograd.Function):
+    """(z, kl) = (mean + exp(logvar / 2) eps, mean(exp(logvar) - logvar - 1 + mean^2)) over tensors of any shape
+    (ops.reparam_fwd / reparam_bwd).  eps: the noise, or None to draw it from the Philox stream (seed, counter: a device int64 the
+    call advances by 1); sample False: z = mean."""
+
+    @staticmethod
+    def forward(ctx, mean, logvar, eps, seed, counter, sample):
+        mean, logvar = mean.contiguous(), logvar.contiguous()
+        z, used, kl = ops.reparam_fwd(mean, logvar, eps=eps.contiguous() if eps is not None else None, seed=seed,
+                                      offset_counter=counter, sample=sample)
+        ctx.save_for_backward(mean, logvar, used)
+        ctx.set_materialize_grads(False)
+        return z, kl
+
+    @staticmethod
+    def backward(ctx, gz, gkl):
+        mean, logvar, used = ctx.saved_tensors
+        if gz is None and gkl is None:
+            return (None,) * 6
+        dmean, dlogvar = ops.reparam_bwd(gz.contiguous() if gz is not None else None,
+                                         gkl.reshape(1).contiguous() if gkl is not None else None, mean, logvar, used)
+        return dmean, dlogvar, None, None, None, None
+
+
+def reparam(mean, logvar, eps=None, seed=0, counter=None, sample=True):
+    return ReparamFn.apply(mean, logvar, eps, int(seed), counter, bool(sample))
 
 
 class MseFn(torch.autograd.Function):

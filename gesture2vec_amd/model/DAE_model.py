@@ -4,7 +4,10 @@ state_dict keys `encoder.0.*`, `decoder.0.*` as in the reference.  Sentinels: la
 (:52-55), latent_dim == -2 is a linear 200-d bottleneck with 30 % dropout (:58-66).
 
 `VQ_Frame` (:118-275) with its own `VQ_Payam_EMA` (:351-482) is the frame-level QUANTISED autoencoder (autoencoder_vq "True"):
-Dropout(0.5) -> Linear -> BatchNorm1d (`bachnorm`, the reference's spelling) -> nearest of K codes (EMA codebook) -> Linear."""
+Dropout(0.5) -> Linear -> BatchNorm1d (`bachnorm`, the reference's spelling) -> nearest of K codes (EMA codebook) -> Linear.
+
+`VAE_Network` (:600-725) is the frame-level VARIATIONAL autoencoder (autoencoder_vq "False", autoencoder_vae "True"):
+Dropout(0.5) -> tanh(Linear) -> mean, logvar -> z = mean + exp(logvar / 2) eps -> Linear -> Linear."""
 from __future__ import annotations
 
 import torch
@@ -285,3 +288,166 @@ class VQ_Frame(nn.Module):
         if Inference:
             return out, latent, encodings
         return out, loss_vq, perplexity_vq
+
+
+class VAE_Network(nn.Module):
+    """The frame-level VARIATIONAL autoencoder (reference DAE_model.py:600-725; autoencoder_vq "False", autoencoder_vae "True"):
+    Dropout(0.5) -> tanh(Linear(D, L)) = h -> mean = VAE_fc_mean(h), logvar = VAE_fc_std(h) -> z = mean + exp(logvar / 2) eps ->
+    VAE_fc_decoder -> Linear(L, D).  forward(x) -> (out (B,D,1), logvar, mean) -- logvar first, as the reference returns them;
+    forward(x, get_latent=True) -> (out, latent = h.detach()).  The noise is added in eval mode too (the reference calls
+    reparameterize with its default train=True); `reconstruct(x, sample=False)` is the deterministic z = mean path.
+
+    Two routes behind one model, chosen by the attribute `route` = "auto" | "fused" | "staged":
+      staged  the per-operator kernels under autograd (five dense layers, tanh, the reparameterisation node): every shape, eval mode.
+      fused   training: g2v_vaeframe_step, forward AND backward of the batch in one launch.  The backward needs the target, so the
+              launch is driven by `fused_step` (train_iter_DAE calls it); a training `forward` on route "fused" says so.
+      auto    asks g2v_vaeframe_plan (ops.vaeframe_plan) -- here, in `resolve`, and nowhere else."""
+
+    route = "auto"
+    KL_WEIGHT = 12.5            # train_seq2seq.py:224-230: 5 x (-2.5 mean(mean(1 + logvar - exp(logvar) - mean^2, 1)))
+
+    def __init__(self, motion_dim: int, latent_dim: int):
+        super().__init__()
+        self.encoder = nn.Sequential(nn.Linear(motion_dim, latent_dim), nn.Tanh())
+        self.decoder = nn.Sequential(nn.Linear(latent_dim, motion_dim))
+        self.dropout = nn.Dropout()                # p = 0.5; container for p only, masks come from the Philox kernel
+        self.vae = True
+        self.VAE_fc_mean = nn.Linear(latent_dim, latent_dim)
+        self.VAE_fc_std = nn.Linear(latent_dim, latent_dim)
+        self.VAE_fc_decoder = nn.Linear(latent_dim, latent_dim)
+        self._explicit_keep = None
+        self._explicit_eps = None
+        self._rng_counter = None
+        self.rng_seed = 0
+        self._routes = {}
+        self.last_kl = None                        # the KL mean of the last staged forward (part of its autograd graph)
+
+    # ---- bookkeeping -------------------------------------------------------------------------------------------------------
+    def set_dropout_mask(self, keep):
+        """Explicit uint8 keep mask for the next training forwards (parity tests)."""
+        self._explicit_keep = keep
+
+    def set_latent_noise(self, eps):
+        """Explicit eps (B, L) for the next forwards, training or eval (parity tests); None draws again."""
+        self._explicit_eps = eps
+
+    def _dims(self):
+        e = self.encoder[0]
+        return e.in_features, e.out_features
+
+    def resolve(self, rows: int, training: bool) -> str:
+        """"fused" or "staged" for a call of `rows` frames; `auto` takes the plan's answer.  An explicit "fused" that the kernel does
+        not admit raises with the plan's reason."""
+        if self.route not in ("auto", "fused", "staged"):
+            raise ValueError(f"VAE_Network.route must be 'auto', 'fused' or 'staged', got {self.route!r}")
+        key = (rows, training)
+        if key not in self._routes:
+            self._routes[key] = ops.vaeframe_plan(rows, *self._dims(), training)
+        auto, fused_ok, reason = self._routes[key]
+        if auto == "":
+            raise ValueError(f"VAE_Network: {reason}")
+        if self.route == "staged":
+            return "staged"
+        if self.route == "fused":
+            if not fused_ok:
+                raise ValueError(f"VAE_Network.route = 'fused': {reason}")
+            return "fused"
+        return auto
+
+    def _counter(self, device):
+        if self._rng_counter is None or self._rng_counter.device != device:
+            self._rng_counter = torch.zeros(1, dtype=torch.int64, device=device)
+        return self._rng_counter
+
+    def _keep(self, inp: torch.Tensor):
+        if self._explicit_keep is not None:
+            return self._explicit_keep
+        return ops.keep_mask(torch.empty(inp.shape, dtype=torch.uint8, device=inp.device), 1.0 - self.dropout.p, self.rng_seed,
+                             self._counter(inp.device))
+
+    def _input(self, x: torch.Tensor) -> torch.Tensor:
+        inp = torch.squeeze(x)
+        if inp.dim() != 2 or inp.shape[0] < 2:
+            raise ValueError("VAE_Network needs a batch of at least 2 frames (the reference's squeeze drops the row axis of a single "
+                             f"frame and its unsqueeze(2) then fails), got {tuple(x.shape)}; encode(x) takes any number of frames")
+        if not inp.is_cuda:
+            raise RuntimeError("VAE_Network runs on the MI355X kernels only (no CPU fallback)")
+        return inp.contiguous()
+
+    def _rows(self, x: torch.Tensor, width: int) -> torch.Tensor:
+        if not x.is_cuda:
+            raise RuntimeError("VAE_Network runs on the MI355X kernels only (no CPU fallback)")
+        return x.reshape(-1, width).contiguous()
+
+    def trainable(self):
+        """the ten tensors in state_dict order: what FlatClipAdam(net.parameters()) holds and g2v_vaeframe_step writes gradients for"""
+        e, d = self.encoder[0], self.decoder[0]
+        return [e.weight, e.bias, d.weight, d.bias, self.VAE_fc_mean.weight, self.VAE_fc_mean.bias, self.VAE_fc_std.weight,
+                self.VAE_fc_std.bias, self.VAE_fc_decoder.weight, self.VAE_fc_decoder.bias]
+
+    @staticmethod
+    def _kernel_order(ten):
+        """trainable() order -> the kernel's (enc, mean, std, fc, dec)"""
+        return [ten[0], ten[1], ten[4], ten[5], ten[6], ten[7], ten[8], ten[9], ten[2], ten[3]]
+
+    # ---- the row-wise pieces the datasets and the generators call ----------------------------------------------------------------
+    def encode(self, x: torch.Tensor) -> torch.Tensor:
+        """h = tanh(Linear(x)) of any number of frames, (N,D) or (N,D,1) -> (N,L), no dropout: `rep_model.encoder(x)`."""
+        e = self.encoder[0]
+        return ops.linear_fwd(self._rows(x, e.in_features), e.weight.data, e.bias.data, act=2)
+
+    def decode(self, lat: torch.Tensor) -> torch.Tensor:
+        """the last Linear on (N,L) rows -> (N,D), as generate.finish_clips uses `dae.decode`"""
+        d = self.decoder[0]
+        return Fn.linear(lat, d.weight, d.bias)
+
+    def generate(self, z: torch.Tensor) -> torch.Tensor:
+        """decoder(VAE_fc_decoder(z)) for latents z (N,L) drawn from the prior -> (N,D)"""
+        f = self.VAE_fc_decoder
+        return self.decode(Fn.linear(self._rows(z, f.in_features), f.weight, f.bias))
+
+    def reconstruct(self, x: torch.Tensor, sample: bool = True) -> torch.Tensor:
+        """the eval-mode forward (no dropout) of (B,D,1) frames -> (B,D,1); sample=False: z = mean, no noise"""
+        with torch.no_grad():
+            return self._staged(self._input(x), None, 1.0, sample)[0]
+
+    # ---- the fused training step ---------------------------------------------------------------------------------------------
+    def fused_step(self, x: torch.Tensor, target: torch.Tensor, grads, want_latent: bool = False, want_stats: bool = False,
+                   want_out: bool = False):
+        """One launch: forward and backward of the batch (g2v_vaeframe_step).  `grads`: ten buffers for the gradients of
+        `trainable()`, in its order.  -> ops.vaeframe_step's dict: scalars (3,) = mse, kl, mse + 12.5 kl; eps; latent, mean,
+        logvar, out where asked for."""
+        if not self.training:
+            raise RuntimeError("VAE_Network.fused_step is the training step")
+        inp = self._input(x)
+        tgt = torch.squeeze(target).contiguous()
+        keep = self._keep(inp)
+        return ops.vaeframe_step(inp, tgt, keep, 1.0 / (1.0 - self.dropout.p), self._kernel_order([p.data for p in self.trainable()]),
+                                 self.KL_WEIGHT, self._kernel_order(list(grads)), eps=self._explicit_eps, seed=self.rng_seed,
+                                 offset_counter=self._counter(inp.device), want_latent=want_latent, want_stats=want_stats,
+                                 want_out=want_out)
+
+    # ---- forward -------------------------------------------------------------------------------------------------------------
+    def _staged(self, inp, keep, scale, sample=True):
+        e, d = self.encoder[0], self.decoder[0]
+        h = Fn.linear(inp, e.weight, e.bias, keep=keep, scale=scale, act=2)
+        mean = Fn.linear(h, self.VAE_fc_mean.weight, self.VAE_fc_mean.bias)
+        logvar = Fn.linear(h, self.VAE_fc_std.weight, self.VAE_fc_std.bias)
+        z, kl = Fn.reparam(mean, logvar, self._explicit_eps if sample else None, self.rng_seed, self._counter(inp.device), sample)
+        c = Fn.linear(z, self.VAE_fc_decoder.weight, self.VAE_fc_decoder.bias)
+        out = torch.unsqueeze(Fn.linear(c, d.weight, d.bias), 2)
+        return out, logvar, mean, h, kl
+
+    def forward(self, x: torch.Tensor, get_latent: bool = False):
+        inp = self._input(x)
+        keep, scale = None, 1.0
+        if self.training:
+            if self.route == "fused":
+                raise RuntimeError("VAE_Network.route = 'fused': the fused training step computes forward and backward in one launch "
+                                   "and needs the target; call fused_step(x, target, grads) or train_iter_DAE, or set route = 'staged'")
+            keep, scale = self._keep(inp), 1.0 / (1.0 - self.dropout.p)
+        out, logvar, mean, h, kl = self._staged(inp, keep, scale)
+        self.last_kl = kl
+        if get_latent:
+            return out, h.detach().clone()
+        return out, logvar, mean

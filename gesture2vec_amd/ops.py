@@ -1982,3 +1982,86 @@ def vqframe_infer(x, w_enc, b_enc, bn_w, bn_b, running_mean, running_var, codebo
                                 _p(w_dec) if want_out else None, _p(b_dec) if want_out else None, _p(ids), _p(latent), _p(out),
                                 _p(ws), nb, D, L, K, _stream()), "vqframe_infer")
     return ids, latent, out
+
+
+# ------------------------------------------------------------------- the frame-level variational autoencoder of Part a (vae_frame.hip)
+def vaeframe_plan(B, D, L, training):
+    """g2v_vaeframe_plan in words -> (route, fused_ok, reason), as vqframe_plan: route "fused" / "staged" is what `auto` takes, ""
+    a refused shape; fused_ok says whether the fused step admits the shape at all."""
+    lib, c = _lib_(), _lib.CONSTANTS
+    args = (int(B), int(D), int(L), int(bool(training)))
+    r = int(lib.g2v_vaeframe_plan(*args))
+    route = {c["G2V_VQFRAME_FUSED"]: "fused", c["G2V_VQFRAME_STAGED"]: "staged"}.get(r & 255, "")
+    return route, bool(r & c["G2V_VQFRAME_FUSED_OK"]), lib.g2v_vaeframe_plan_reason(*args).decode()
+
+
+def vaeframe_step(x, target, keep, scale, weights, kl_weight, grads, *, eps=None, seed=0, offset_counter=None, want_latent=False,
+                  want_stats=False, want_out=False):
+    """g2v_vaeframe_step: training forward + backward of one (B,D) batch in one launch.  weights / grads: the ten tensors / gradient
+    buffers in the order (w_enc, b_enc, w_mean, b_mean, w_std, b_std, w_fc, b_fc, w_dec, b_dec) -- slices of an optimiser's flat
+    gradient, say.  Noise: `eps` (B,L), or drawn from the Philox stream (seed, offset_counter: device int64, advanced by 1).
+    -> dict scalars (3,) = mse, kl, mse + kl_weight kl; eps (the noise used); latent, mean, logvar (B,L) and out (B,D) or None."""
+    lib = _lib_()
+    B, D = x.shape
+    L = weights[0].shape[0]
+    nb = int(lib.g2v_vaeframe_workspace(B, D, L))
+    if nb == 0:
+        raise ValueError("vaeframe_step: " + lib.g2v_vaeframe_plan_reason(B, D, L, 1).decode())
+    dev = x.device
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)      # noqa: E731
+    ws = workspace(nb, dev, "vaeframe_step")
+    if keep is not None and tuple(_chk(keep, torch.uint8, "keep").shape) != (B, D):
+        raise ValueError(f"vaeframe_step: keep must be ({B}, {D}), got {tuple(keep.shape)}")
+    if tuple(target.shape) != (B, D):
+        raise ValueError(f"vaeframe_step: target must be ({B}, {D}), got {tuple(target.shape)}")
+    shapes = ((L, D), (L,), (L, L), (L,), (L, L), (L,), (L, L), (L,), (D, L), (D,))
+    if len(weights) != 10 or len(grads) != 10:
+        raise ValueError("vaeframe_step: ten weights and ten gradient buffers")
+    for wt, g, s in zip(weights, grads, shapes):
+        if tuple(_chk(wt, name="weight").shape) != s or _chk(g, name="grad").numel() != wt.numel():
+            raise ValueError(f"vaeframe_step: expected a weight of shape {s} and a gradient buffer of its size")
+    if eps is not None and tuple(_chk(eps, name="eps").shape) != (B, L):
+        raise ValueError(f"vaeframe_step: eps must be ({B}, {L}), got {tuple(eps.shape)}")
+    if eps is None and offset_counter is None:
+        raise ValueError("vaeframe_step: drawing the noise needs offset_counter")
+    o = {"scalars": f(3), "eps": f(B, L) if eps is None else eps, "latent": f(B, L) if want_latent else None,
+         "mean": f(B, L) if want_stats else None, "logvar": f(B, L) if want_stats else None, "out": f(B, D) if want_out else None}
+    check(lib.g2v_vaeframe_step(_p(_chk(x, name="x")), _p(_chk(target, name="target")), _p(keep), float(scale),
+                                *[_p(wt) for wt in weights], float(kl_weight), _p(eps), int(seed), _p(offset_counter),
+                                *[_p(g) for g in grads], _p(o["scalars"]), _p(o["latent"]), _p(o["mean"]), _p(o["logvar"]), _p(o["out"]),
+                                _p(o["eps"]) if eps is None else None, _p(ws), nb, B, D, L, _stream()), "vaeframe_step")
+    return o
+
+
+def tanh_bwd(dy, y):
+    """dpre = dy (1 - y^2), y = tanh(pre)"""
+    dpre = torch.empty_like(y)
+    check(_lib_().g2v_tanh_bwd(_p(_chk(dy, name="dy")), _p(_chk(y, name="y")), _p(dpre), y.numel(), _stream()), "tanh_bwd")
+    return dpre
+
+
+def reparam_fwd(mean, logvar, *, eps=None, seed=0, offset_counter=None, sample=True):
+    """z = mean + exp(logvar / 2) eps over any shape, kl (1,) = mean(exp(logvar) - logvar - 1 + mean^2) -> (z, eps used or None, kl).
+    Noise as in vae_latent_fwd: `eps`, or drawn from the Philox stream (seed, offset_counter, advanced by 1); sample=False: z = mean."""
+    lib = _lib_()
+    n = mean.numel()
+    draw = bool(sample) and eps is None
+    z, kl = torch.empty_like(mean), torch.empty((1,), dtype=torch.float32, device=mean.device)
+    used = (torch.empty_like(mean) if draw else eps) if sample else None
+    nb = int(lib.g2v_reparam_workspace(n))
+    ws = workspace(nb, mean.device, "reparam")
+    check(lib.g2v_reparam_fwd(_p(_chk(mean, name="mean")), _p(_chk(logvar, name="logvar")),
+                              _p(_chk(eps, name="eps")) if eps is not None else None, int(seed), _p(offset_counter), int(bool(sample)),
+                              _p(z), _p(used) if draw else None, _p(kl), _p(ws), nb, n, _stream()), "reparam_fwd")
+    return z, used, kl
+
+
+def reparam_bwd(dz, g_kl, mean, logvar, eps, g_mean=None, g_logvar=None):
+    """Backward of reparam_fwd: dz = d loss / d z or None (0), g_kl = device scalar d loss / d kl or None (0), eps None when the forward
+    did not sample, g_mean / g_logvar = gradients reaching mean / logvar directly or None -> (dmean, dlogvar)."""
+    dmean, dlogvar = torch.empty_like(mean), torch.empty_like(mean)
+    opt = lambda t, name: _p(_chk(t, name=name)) if t is not None else None      # noqa: E731
+    check(_lib_().g2v_reparam_bwd(opt(dz, "dz"), _p(g_kl), opt(g_mean, "g_mean"), opt(g_logvar, "g_logvar"), _p(_chk(mean, name="mean")),
+                                  _p(_chk(logvar, name="logvar")), opt(eps, "eps"), _p(dmean), _p(dlogvar), mean.numel(), _stream()),
+          "reparam_bwd")
+    return dmean, dlogvar

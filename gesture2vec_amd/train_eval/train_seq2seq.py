@@ -338,14 +338,18 @@ def train_iter_DAE(args, epoch: int, noisy_poses: torch.Tensor, target_poses: to
     """One training iteration of a Part-a frame model (reference :161-241): MSE(outputs, target) [+ loss_vq] -> backward ->
     clip_grad_norm_(5) + Adam (fused in `optim`, a gesture2vec_amd.flat.FlatClipAdam).
     autoencoder_vq "False": DAE_Network -> {"loss": loss}.  autoencoder_vq "True" (VQ_Frame): ({"loss": reconstruction loss alone},
-    perplexity tensor), as the reference returns it.  autoencoder_vae "True" raises."""
+    perplexity tensor), as the reference returns it.  autoencoder_vq "False" with autoencoder_vae "True" (VAE_Network):
+    {"loss": mse + 12.5 kl}, the total.  Both switches "True" (VQ_Frame(vae=True)) raises."""
     from ..flat import FlatClipAdam
     from ..functional import mse_loss
     if not isinstance(optim, FlatClipAdam):
         raise TypeError("use gesture2vec_amd.flat.FlatClipAdam (clip + Adam are one fused HIP launch)")
-    if getattr(args, "autoencoder_vae", "False") == "True":
+    vq, vae = getattr(args, "autoencoder_vq", "False") == "True", getattr(args, "autoencoder_vae", "False") == "True"
+    if vq and vae:
         raise NotImplementedError("autoencoder_vae 'True' (VAE_Network, VQ_Frame(vae=True)) is outside the accelerated hot path")
-    if getattr(args, "autoencoder_vq", "False") == "True":
+    if vae:
+        return _train_iter_vae_frame(noisy_poses, target_poses, net, optim)
+    if vq:
         return _train_iter_vq_frame(noisy_poses, target_poses, net, optim)
     optim.zero_grad()
     outputs = net(noisy_poses)
@@ -388,6 +392,41 @@ def _train_iter_vq_frame(noisy_poses, target_poses, net, optim):
     (rec_loss + vq_loss).backward()
     optim.step()
     return {"loss": rec_loss.item()}, perplexity_vq
+
+
+def _train_iter_vae_frame(noisy_poses, target_poses, net, optim):
+    """The VAE_Network iteration (reference :202-241 with autoencoder_vq "False", autoencoder_vae "True"): loss = mse + 5 x (-2.5
+    mean(mean(1 + logvar - exp(logvar) - mean^2, 1))) = mse + 12.5 kl.  On the fused route (VAE_Network.resolve) it is three launches
+    and one read-back: the keep mask, the step -- which draws its noise and writes the ten gradients straight into the optimiser's
+    flat gradient --, clip + Adam, and the loss's .item().  Otherwise the staged route under autograd."""
+    from ..functional import mse_loss
+    from ..model.DAE_model import VAE_Network
+    if not isinstance(net, VAE_Network):
+        raise TypeError("autoencoder_vae 'True' (with autoencoder_vq 'False') trains a gesture2vec_amd.model.DAE_model.VAE_Network")
+    if not net.training:
+        raise RuntimeError("train_iter_DAE needs the model in training mode")
+    fp = optim.fp
+    params = net.trainable()
+    fused = net.resolve(noisy_poses.shape[0], True) == "fused"
+    if fused and not (len(fp.params) == len(params) and all(a is b for a, b in zip(fp.params, params))):
+        if net.route == "fused":
+            raise ValueError("VAE_Network.route = 'fused': the optimiser must hold exactly the model's parameters, "
+                             "FlatClipAdam(net.parameters(), ...)")
+        fused = False
+    optim.zero_grad()
+    if fused:
+        grads = [fp.gflat[o:o + p.numel()] for p, o in zip(fp.params, fp.offsets)]
+        scalars = net.fused_step(noisy_poses, target_poses, grads)["scalars"]
+        for p, g in zip(params, grads):
+            p.grad = g.view(p.shape)
+        fp.skipped = []
+        fp.step(optim.lr, optim.betas, optim.eps, optim.max_norm)
+        return {"loss": scalars[2].item()}
+    outputs, _logvar, _mean = net(noisy_poses)
+    loss = mse_loss(outputs, target_poses) + net.KL_WEIGHT * net.last_kl[0]
+    loss.backward()
+    optim.step()
+    return {"loss": loss.item()}
 
 
 def _code_loss(outputs, codes):

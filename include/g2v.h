@@ -1790,6 +1790,54 @@ int g2v_vqframe_infer(const float* x, int64_t N, const float* w_enc, const float
                       const float* w_dec, const float* b_dec, int64_t* ids, float* latent, float* out, void* workspace,
                       size_t workspace_bytes, int D, int L, int K, g2v_stream_t stream);
 
+/* ---- The frame-level variational autoencoder of Part a (VAE_Network, reference scripts/model/DAE_model.py:600-725;
+ * train_eval/train_seq2seq.py:161-241), autoencoder_vq "False" with autoencoder_vae "True":
+ *   x (B,D) -> Dropout -> h = tanh(x We^T + be) -> mean = h Wm^T + bm, logvar = h Ws^T + bs -> z = mean + exp(logvar / 2) eps
+ *   -> c = z Wf^T + bf -> out = c Wd^T + bd;  loss = mse(out, target) + kl_weight kl,  kl = mean(exp(logvar) - logvar - 1 + mean^2)
+ *   over the B L elements (the reference's 5 x -2.5 mean(mean(1 + logvar - exp(logvar) - mean^2, 1)) is kl_weight = 12.5).
+ * Noise, here and in g2v_reparam_fwd: eps_in (B,L) when given, else drawn from the g2v_keep_mask stream exactly as
+ *   g2v_vae_latent_fwd draws it (seed, offset_counter[0]; Philox block g <-> elements 4g .. 4g+3 of the row-major (B,L) array, two
+ *   Box-Muller pairs per block; one device function serves all three kernels); the counter then advances by 1 and eps_out (B,L)
+ *   receives the eps used (required when drawn, else may be NULL).
+ * g2v_vaeframe_plan(B, D, L, training): host arithmetic only, with the constants and bit layout of g2v_vqframe_plan
+ *   (G2V_VQFRAME_FUSED / _STAGED / _REFUSED in bits 0-7, G2V_VQFRAME_FUSED_OK).  The fused step is admitted for training,
+ *   2 <= B, where its LDS layout (vae_frame.hip: six (B, ld(L)) row arrays + 32 floats) stays within 160 KB -- B <= 155 at L = 40,
+ *   B <= 131 at L = 45, whatever D is.  B = 1 is refused (the reference's squeeze drops the row axis of a single frame).  Eval
+ *   mode has no fused kernel: STAGED.  `auto` is FUSED only where it was measured faster: admitted shapes with B <= 155,
+ *   D <= 135, L <= 45.
+ *   g2v_vaeframe_plan_reason: the same answer in words (a static string).  g2v_vaeframe_workspace: bytes of workspace of the
+ *   fused step (0: not admitted); g2v_vaeframe_step_lds: its dynamic LDS in bytes (0: not admitted).
+ * g2v_vaeframe_step: training forward and backward of one batch in ONE workgroup.  keep: uint8 (B,D) or NULL (no dropout), kept
+ *   inputs are multiplied by scale.  Writes the ten gradients (no dx), scalars[3] = (mse, kl, mse + kl_weight kl), and, where not
+ *   NULL, latent = h, mean, logvar (B,L) and out (B,D).  It moves no weight.  Every product is a chain of fp32 MFMAs per 16 x 16
+ *   tile with k ascending, every other sum has a fixed tree, no atomics: the same input gives the same bits.
+ *   G2V_ERR_UNSUPPORTED for a shape the plan does not admit.
+ * The staged route's operators (the dense layers are g2v_linear_*), any n >= 1 elements:
+ *   g2v_tanh_bwd     dpre[i] = dy[i] (1 - y[i]^2), y = tanh(pre).
+ *   g2v_reparam_fwd  z = mean + exp(logvar / 2) eps (sample != 0; noise as above) or z = mean bit for bit (sample == 0: eps is
+ *                    neither read nor written); kl[0] = mean(exp(logvar) - logvar - 1 + mean^2) by per-workgroup partials in a
+ *                    fixed order and a one-workgroup finish.  workspace >= g2v_reparam_workspace(n) bytes.
+ *   g2v_reparam_bwd  c = g_kl[0] / n (g_kl: device scalar d loss / d kl, NULL = 0);  dmean = dz + 2 c mean + g_mean,
+ *                    dlogvar = dz 0.5 exp(logvar / 2) eps + c (exp(logvar) - 1) + g_logvar.  eps NULL: the forward had sample == 0.
+ *                    dz, g_mean, g_logvar (n; NULL = 0): the gradients reaching z, mean and logvar. */
+int g2v_vaeframe_plan(int B, int D, int L, int training);
+const char* g2v_vaeframe_plan_reason(int B, int D, int L, int training);
+size_t g2v_vaeframe_workspace(int B, int D, int L);
+size_t g2v_vaeframe_step_lds(int B, int D, int L);
+int g2v_vaeframe_step(const float* x, const float* target, const uint8_t* keep, float scale, const float* w_enc,
+                      const float* b_enc, const float* w_mean, const float* b_mean, const float* w_std, const float* b_std,
+                      const float* w_fc, const float* b_fc, const float* w_dec, const float* b_dec, float kl_weight,
+                      const float* eps_in, uint64_t seed, int64_t* offset_counter, float* g_w_enc, float* g_b_enc, float* g_w_mean,
+                      float* g_b_mean, float* g_w_std, float* g_b_std, float* g_w_fc, float* g_b_fc, float* g_w_dec, float* g_b_dec,
+                      float* scalars, float* latent, float* mean, float* logvar, float* out, float* eps_out, void* workspace,
+                      size_t workspace_bytes, int B, int D, int L, g2v_stream_t stream);
+int g2v_tanh_bwd(const float* dy, const float* y, float* dpre, int64_t n, g2v_stream_t stream);
+size_t g2v_reparam_workspace(int64_t n);
+int g2v_reparam_fwd(const float* mean, const float* logvar, const float* eps_in, uint64_t seed, int64_t* offset_counter, int sample,
+                    float* z, float* eps_out, float* kl, void* workspace, size_t workspace_bytes, int64_t n, g2v_stream_t stream);
+int g2v_reparam_bwd(const float* dz, const float* g_kl, const float* g_mean, const float* g_logvar, const float* mean,
+                    const float* logvar, const float* eps, float* dmean, float* dlogvar, int64_t n, g2v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

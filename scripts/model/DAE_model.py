@@ -7,4 +7,4 @@ _ROOT = _os.path.dirname(_os.path.dirname(_os.path.dirname(_os.path.abspath(__fi
 if _ROOT not in _sys.path:
     _sys.path.insert(0, _ROOT)
 
-from gesture2vec_amd.model.DAE_model import DAE_Network, VQ_Frame, VQ_Payam_EMA  # noqa: E402,F401
+from gesture2vec_amd.model.DAE_model import DAE_Network, VAE_Network, VQ_Frame, VQ_Payam_EMA  # noqa: E402,F401

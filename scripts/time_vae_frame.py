@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Times the two routes of the frame-level variational autoencoder (VAE_Network) against each other on the device, in one process:
+
+    python scripts/time_vae_frame.py [--iters 300] [--rounds 5] [--out profiles/vaeframe_times.jsonl]
+
+  * train_iter_DAE (keep mask + step + clip/Adam + the loss read-back) per iteration, fused against staged, at B in {16, 128, the
+    largest batch the plan admits} for (D, L) = (135, 40) and (135, 45);
+  * the staged route alone at (1024, 135, 200), which the fused step does not admit.
+The routes alternate round by round inside one timed loop each (device events around `iters` iterations after a warm-up); the
+figure reported per route is the median of the rounds, with the spread (min, max) beside it.  One JSON line per measurement, appended
+to `--out`.  `--kernel-only ITERS` runs just the fused calls (for a kernel trace taken in a run of its own)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+
+from gesture2vec_amd import ops  # noqa: E402
+from gesture2vec_amd.flat import FlatClipAdam  # noqa: E402
+from gesture2vec_amd.model.DAE_model import VAE_Network  # noqa: E402
+from gesture2vec_amd.train_eval.train_seq2seq import train_iter_DAE  # noqa: E402
+
+DEV = "cuda:0"
+ARGS = argparse.Namespace(autoencoder_vq="False", autoencoder_vae="True")
+
+
+def largest_batch(D, L):
+    B = 2
+    while ops.vaeframe_plan(B + 1, D, L, True)[1]:
+        B += 1
+    return B
+
+
+def timed(fn, iters):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop) * 1e3 / iters      # microseconds per call
+
+
+def compare(fns, iters, rounds, warmup):
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, iters))
+    return {k: dict(median_us=round(statistics.median(v), 2), min_us=round(min(v), 2), max_us=round(max(v), 2)) for k, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--kernel-only", type=int, default=0)
+    cli = ap.parse_args()
+    lines = []
+
+    def emit(**kw):
+        lines.append(kw)
+        print(json.dumps(kw), flush=True)
+
+    shapes = [(B, 135, L) for L in (40, 45) for B in (16, 128, largest_batch(135, L))] + [(1024, 135, 200)]
+    for shape in shapes:
+        B, D, L = shape
+        auto, fused_ok, reason = ops.vaeframe_plan(B, D, L, True)
+        x = torch.randn(B, D, 1, device=DEV)
+        noisy = x + 0.1 * torch.randn_like(x)
+        fns = {}
+        for route in (("fused", "staged") if fused_ok else ("staged",)):
+            if cli.kernel_only and route != "fused":
+                continue
+            torch.manual_seed(0)
+            net = VAE_Network(D, L).to(DEV)
+            net.train(True)
+            net.route = route
+            optim = FlatClipAdam(net.parameters(), lr=5e-4, betas=(0.5, 0.999))
+            fns[route] = (lambda net=net, optim=optim: train_iter_DAE(ARGS, 1, noisy, x, net, optim))
+        if cli.kernel_only:
+            for fn in fns.values():
+                for _ in range(cli.kernel_only):
+                    fn()
+            continue
+        emit(what="train_iter_DAE vae", shape=shape, iters=cli.iters, rounds=cli.rounds, fused_admitted=fused_ok, auto=auto, plan=reason,
+             **compare(fns, cli.iters, cli.rounds, 30))
+    torch.cuda.synchronize()
+    if cli.out:
+        with open(cli.out, "a") as f:
+            for kw in lines:
+                f.write(json.dumps(kw) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -8,7 +8,9 @@ Same surface: `init_model(args, lang_model, pose_dim, _device)` -> (DAE_Network(
 `args, epoch, lang_model, pose_dim, gen_dict` and the name `<name>_H<hidden>_checkpoint_<epoch>.bin` :203-222),
 `evaluate_testset` (mean MSE of the eval-mode reconstruction :314-371), `main`.  The plain denoising autoencoder
 (`autoencoder_vq == autoencoder_vae == "False"`, config/DAE.yml) and the frame-level quantised autoencoder `VQ_Frame`
-(`autoencoder_vq: "True"`, :102-108) are served; `autoencoder_vae: "True"` (`VAE_Network`, `VQ_Frame(vae=True)`) raises.  In the
+(`autoencoder_vq: "True"`, :102-108) are served, and so is the frame-level variational autoencoder `VAE_Network`
+(`autoencoder_vq: "False"` with `autoencoder_vae: "True"`, :109-112; config/DAE_VAE_synthetic.yml): one iteration per batch, loss =
+mse + 12.5 kl, the noise added in evaluation too, as the reference does.  Both switches "True" (`VQ_Frame(vae=True)`) raises.  In the
 VQ mode every batch trains twice (:276-284) -- on (original, original), whose reconstruction loss and perplexity are the two
 per-iteration curves, then on (noisy, original) -- and each epoch starts by writing the curves so far to
 `<model_save_path>/plots/Error_Epoch(<n>).npz` (arrays `recon_error`, `perplexity`) where the reference saves the picture (:564).
@@ -33,7 +35,7 @@ for _p in (_HERE, _ROOT):
         sys.path.insert(0, _p)
 
 from config.parse_args import parse_args  # noqa: E402
-from model.DAE_model import DAE_Network, VQ_Frame  # noqa: E402
+from model.DAE_model import DAE_Network, VAE_Network, VQ_Frame  # noqa: E402
 from train_eval.train_seq2seq import train_iter_DAE  # noqa: E402
 import utils.train_utils  # noqa: E402
 from utils.average_meter import AverageMeter  # noqa: E402
@@ -46,8 +48,10 @@ Global_loss_eval = []
 
 
 def init_model(args, lang_model, pose_dim: int, _device):
-    if args.autoencoder_vae == "True":
+    if args.autoencoder_vae == "True" and args.autoencoder_vq == "True":
         raise NotImplementedError("autoencoder_vae: 'True' (VAE_Network, VQ_Frame(vae=True)) is outside the accelerated hot path")
+    if args.autoencoder_vae == "True":
+        return VAE_Network(args.input_motion_dim, args.hidden_size).to(_device), Fn.mse_loss
     if args.autoencoder_vq == "True":
         network = VQ_Frame(args.input_motion_dim, args.hidden_size, False, int(args.autoencoder_vq_components)).to(_device)
         return network, Fn.mse_loss
@@ -80,6 +84,8 @@ def evaluate_testset(test_data_loader, generator, loss_fn, args) -> float:
             noisy, original = noisy.to(device), original.to(device)
             if args.autoencoder_vq == "True":
                 out_poses, _vq_loss, _perplexity = generator(noisy)
+            elif args.autoencoder_vae == "True":
+                out_poses, _logvar, _mean = generator(noisy)      # (the noisy eval forward: reparameterize's default train=True)
             else:
                 out_poses = generator(noisy)
             loss = loss_fn(out_poses, original)
