@@ -31,7 +31,7 @@ __global__ __launch_bounds__(CT_NTHR) void latent_step_fwd_kernel(const float* _
                                                                   g2v_code_dec_weights w, CodePackF pk, g2v_code_dec_saved sv,
                                                                   const uint8_t* __restrict__ keep_l0, CodeDims dm, int j) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int NTHR = CT_NTHR, NW = CT_NW;
+  constexpr int NTHR = CT_NTHR;
   const int S1 = dm.S1, B = dm.B, H = dm.H, E = dm.K;
   const int Hp = (H + 15) & ~15, ldh = Hp + 4, Ep = (E + 15) & ~15, ldx = Ep + 4;
   const CtFwdLds L = ct_fwd_lds(H, E, 0, dm.scratch);
@@ -48,37 +48,14 @@ __global__ __launch_bounds__(CT_NTHR) void latent_step_fwd_kernel(const float* _
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b0 = blockIdx.x * 16;
   const int nrows = min(16, B - b0);
-  const int i = lane & 15, q = lane >> 4;
-  const int H4 = H >> 2;
   const bool has_tail = j > 0, has_head = j < S1;
   const int t = j - 1;                                   // the step whose tail this launch runs
   const int npre = max(1, min(dm.n_pre, S1));            // steps fed from `target` (teacher forcing :734-737; step 0 always)
   const bool feed = has_tail && has_head && j >= npre;   // step j reads this tile's own y_{j-1}
 
   // ---- prefetch this block's rows of u_t, h0_t, h1_t (written by the previous launch on some other CU) -------------------
-  constexpr int NPF = 2;                                  // 16 x H / 4 <= 1024 float4 (H <= 256)
-  float4 pu[NPF], ph0[NPF], ph1[NPF];
-  int pr[NPF], pc[NPF];
-  bool pv[NPF];
-#pragma unroll
-  for (int k = 0; k < NPF; ++k) {
-    const int e = tid + k * NTHR;
-    pr[k] = e / H4;
-    pc[k] = (e - pr[k] * H4) * 4;
-    pv[k] = e < 16 * H4 && pr[k] < nrows;
-    pu[k] = ph0[k] = ph1[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pv[k]) {
-      if (has_tail) {
-        const int64_t row = ((int64_t)t * B + b0 + pr[k]) * H + pc[k];
-        pu[k] = *reinterpret_cast<const float4*>(sv.u + row);
-        ph0[k] = *reinterpret_cast<const float4*>(sv.h0 + row);
-        ph1[k] = *reinterpret_cast<const float4*>(sv.h1 + row);
-      } else {
-        ph0[k] = *reinterpret_cast<const float4*>(h_init + (int64_t)(b0 + pr[k]) * H + pc[k]);
-        ph1[k] = *reinterpret_cast<const float4*>(h_init + ((int64_t)B + b0 + pr[k]) * H + pc[k]);
-      }
-    }
-  }
+  CtRowPf pf;
+  ct_fwd_prefetch(pf, sv, h_init, t, has_tail, B, H, b0, nrows, tid);
   // zero what the MFMA contractions must see as zero: padding columns, rows >= nrows
   if (nrows < 16 || Hp != H || Ep != E) {
     for (int e = tid; e < 5 * 16 * ldh + 16 * ldx; e += NTHR) smem[e] = 0.f;
@@ -87,89 +64,20 @@ __global__ __launch_bounds__(CT_NTHR) void latent_step_fwd_kernel(const float* _
 
   if (!has_tail) {
     // state in front of step 0 = encoder_hidden[:2] (:667-669)
-#pragma unroll
-    for (int k = 0; k < NPF; ++k)
-      if (pv[k]) {
-        *reinterpret_cast<float4*>(sv.h0 + (int64_t)(b0 + pr[k]) * H + pc[k]) = ph0[k];
-        *reinterpret_cast<float4*>(sv.h1 + (int64_t)(b0 + pr[k]) * H + pc[k]) = ph1[k];
-      }
+    ct_fwd_init_state(pf, sv, B, H, b0, nullptr, ldh);
   } else {
     // ---- (a) BatchNorm statistics of u_t (batch statistics: this rollout is the training forward) ------------------------
-    {
-      const float* part = sv.bn_partial + (int64_t)(t & 1) * dm.nblk * 2 * H;
-      reduce_partials<NTHR>(part, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch);
-      for (int f = tid; f < H; f += NTHR) {
-        const float s1 = red[f], s2 = red[H + f];
-        const float mv = s1 / (float)B;
-        const float var = fmaxf(s2 / (float)B - mv * mv, 0.f);   // biased batch variance
-        const float mean = mv + w.b_pre[f];
-        const float invstd = bn_invstd_(var);
-        st[f] = mean;
-        st[Hp + f] = invstd;
-        if (blockIdx.x == 0) {
-          sv.bn_stats[(int64_t)t * 2 * H + f] = mean;
-          sv.bn_stats[(int64_t)t * 2 * H + H + f] = invstd;
-          // running statistics: momentum 0.1, unbiased variance; one update per decode step, in step order (stream order)
-          // (bn_running_mean == NULL: the caller commits them behind the backward, g2v_bn_running_update_invstd)
-          if (w.bn_running_mean) {
-            const float unb = (B > 1) ? var * (float)B / (float)(B - 1) : var;
-            w.bn_running_mean[f] = 0.9f * w.bn_running_mean[f] + 0.1f * mean;
-            w.bn_running_var[f] = 0.9f * w.bn_running_var[f] + 0.1f * unb;
-          }
-        }
-      }
-    }
+    ct_bn_finish_fwd<false>(w, sv, dm, t, st, red, red_scratch, tid);
     lds_barrier();
     // ---- (b) a_t = ReLU(BN(u_t)); stage the previous hidden states -----------------------------------------------------
-#pragma unroll
-    for (int k = 0; k < NPF; ++k)
-      if (pv[k]) {
-        const int c = pc[k];
-        const float4 g4 = *reinterpret_cast<const float4*>(w.bn_w + c), b4 = *reinterpret_cast<const float4*>(w.bn_b + c);
-        const float4 m4 = *reinterpret_cast<const float4*>(st + c), i4 = *reinterpret_cast<const float4*>(st + Hp + c);
-        float4 a4;
-        a4.x = fmaxf((pu[k].x - m4.x) * i4.x * g4.x + b4.x, 0.f);
-        a4.y = fmaxf((pu[k].y - m4.y) * i4.y * g4.y + b4.y, 0.f);
-        a4.z = fmaxf((pu[k].z - m4.z) * i4.z * g4.z + b4.z, 0.f);
-        a4.w = fmaxf((pu[k].w - m4.w) * i4.w * g4.w + b4.w, 0.f);
-        *reinterpret_cast<float4*>(Xa + pr[k] * ldh + c) = a4;
-        *reinterpret_cast<float4*>(Xh0 + pr[k] * ldh + c) = ph0[k];
-        *reinterpret_cast<float4*>(Xh1 + pr[k] * ldh + c) = ph1[k];
-        *reinterpret_cast<float4*>(sv.a + ((int64_t)t * B + b0 + pr[k]) * H + c) = a4;
-      }
+    ct_bn_relu_stage(pf, w, sv, st, Xa, Xh0, Xh1, ldh, t, B, H, b0);
     lds_barrier();
     // ---- (c) GRU layer 0, (d) GRU layer 1 ------------------------------------------------------------------------------
     const bool drop = keep_l0 && dm.p_drop > 0.f;
-    gru_cell_fwd<0>(pk.ih0, pk.hh0, w.b_ih0, w.b_hh0, Xa, Xh0, ldh, H, Hp, Xx1, sv.h0 + ((int64_t)(t + 1) * B + b0) * H,
-                    sv.gates0 + ((int64_t)t * B + b0) * 4 * H, drop ? keep_l0 + ((int64_t)t * B + b0) * H : nullptr,
-                    1.0f / (1.0f - dm.p_drop), (drop && sv.x1) ? sv.x1 + ((int64_t)t * B + b0) * H : nullptr, nrows, lane, wave, NW);
-    lds_barrier();
-    gru_cell_fwd<0>(pk.ih1, pk.hh1, w.b_ih1, w.b_hh1, Xx1, Xh1, ldh, H, Hp, Xh1n, sv.h1 + ((int64_t)(t + 1) * B + b0) * H,
-                    sv.gates1 + ((int64_t)t * B + b0) * 4 * H, nullptr, 1.0f, nullptr, nrows, lane, wave, NW);
-    lds_barrier();
+    ct_cells_fwd(pk, w, sv, keep_l0, drop, dm, t, b0, nrows, Xa, Xh0, Xh1, Xx1, Xh1n, lane, wave);
     // ---- (e) y_t = out(h1_{t+1}) -> outputs[t + 1]; fed back: also the x tile of step j and its saved row -----------------
-    {
-      const int ntile = (E + 15) >> 4;
-      for (int base = 0; base < ntile; base += 4 * NW) {
-        f32x4 acc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        wave_gemm_p<4, 0>(acc, pk.out, Hp >> 4, base + wave, NW, Xh1n, ldh, lane);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int k0 = 16 * (base + wave + NW * u) + 4 * q;
-          if (k0 + 3 < E) {        // (E % 4 == 0: a lane's group of four outputs is whole or padding)
-            const float4 bo = *reinterpret_cast<const float4*>(w.b_out + k0);
-            const float4 v = make_float4(acc[u][0] + bo.x, acc[u][1] + bo.y, acc[u][2] + bo.z, acc[u][3] + bo.w);
-            if (i < nrows) *reinterpret_cast<float4*>(sv.logits + ((int64_t)t * B + b0 + i) * E + k0) = v;
-            if (feed) {
-              *reinterpret_cast<float4*>(Xe + i * ldx + k0) = (i < nrows) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-              if (i < nrows) *reinterpret_cast<float4*>(sv.ec + ((int64_t)j * B + b0 + i) * E + k0) = v;
-            }
-          }
-        }
-      }
-    }
+    ct_out_feed_fwd(pk.out, w.b_out, Xh1n, ldh, Hp, E, sv.logits + ((int64_t)t * B + b0) * E, feed, Xe, ldx,
+                    sv.ec + ((int64_t)j * B + b0) * E, E, nrows, lane, wave);
   }
   if (!has_head) return;
   // ---- head of step j: x_j = target_j while teacher-forced (else the tile the out layer just left in LDS) ------------------
@@ -185,33 +93,7 @@ __global__ __launch_bounds__(CT_NTHR) void latent_step_fwd_kernel(const float* _
   }
   lds_barrier();
   // ---- u_j = pre_linear.0(x_j) and per-workgroup BatchNorm partial sums of (u - b) --------------------------------------------
-  {
-    const int ntile = Hp >> 4;
-    float* part = sv.bn_partial + ((int64_t)(j & 1) * dm.nblk + blockIdx.x) * 2 * H;
-    for (int ft = wave; ft < ntile; ft += NW) {
-      const int f0 = 16 * ft + 4 * q;
-      const bool vec = f0 + 3 < H;       // (H % 4 == 0: a lane's group of four features is whole or padding)
-      float4 bp = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (vec) bp = *reinterpret_cast<const float4*>(w.b_pre + f0);
-      f32x4 acc[1] = {(f32x4){0.f, 0.f, 0.f, 0.f}};
-      wave_gemm_p<1, 0>(acc, pk.pre, Ep >> 4, ft, 0, Xe, ldx, lane);      // (every lane of the wave: an MFMA is not predicated)
-      if (!vec) continue;               // (uniform per DPP row of 16 lanes: the reductions below stay whole)
-      float s1[4], s2[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = (i < nrows) ? acc[0][r] : 0.f;
-        s1[r] = reduce16(v);
-        s2[r] = reduce16(v * v);
-      }
-      if (i < nrows)
-        *reinterpret_cast<float4*>(sv.u + ((int64_t)j * B + b0 + i) * H + f0) =
-            make_float4(acc[0][0] + bp.x, acc[0][1] + bp.y, acc[0][2] + bp.z, acc[0][3] + bp.w);
-      if (i == 0) {
-        *reinterpret_cast<float4*>(part + f0) = make_float4(s1[0], s1[1], s1[2], s1[3]);
-        *reinterpret_cast<float4*>(part + H + f0) = make_float4(s2[0], s2[1], s2[2], s2[3]);
-      }
-    }
-  }
+  ct_pre_linear_partials(pk.pre, Ep >> 4, Xe, nullptr, 0, nullptr, ldx, w, sv, dm, j, b0, nrows, lane, wave);
 }
 
 // =====================================================================================================================
@@ -227,7 +109,7 @@ __global__ __launch_bounds__(CT_NTHR) void latent_step_bwd_kernel(CodeBwdArgs a,
   constexpr int NTHR = CT_NTHR, NW = CT_NW;
   const CtBwdLds L = ct_bwd_lds(dm.H, dm.K);
   const int S1 = dm.S1, B = dm.B, H = dm.H, E = dm.K;
-  const int Hp = (H + 15) & ~15, ldh = Hp + 4, H4 = H >> 2, Ep = (E + 15) & ~15, ldk = Ep + 4;
+  const int Hp = (H + 15) & ~15, ldh = Hp + 4, Ep = (E + 15) & ~15, ldk = Ep + 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = lane & 15, q = lane >> 4;
   const int b0 = blockIdx.x * 16, nrows = min(16, B - b0);
@@ -243,40 +125,10 @@ __global__ __launch_bounds__(CT_NTHR) void latent_step_bwd_kernel(CodeBwdArgs a,
   for (int e = tid; e < L.total; e += NTHR) smem[e] = 0.f;
   lds_barrier();
   if (!last) {
-    // carries of step t+1 (written by the previous launch)
-    if (t >= 0)
-      for (int e = tid; e < 16 * H4; e += NTHR) {
-        const int r = e / H4, c = (e - r * H4) * 4;
-        if (r >= nrows) continue;
-        *reinterpret_cast<float4*>(C0 + r * ldh + c) = *reinterpret_cast<const float4*>(a.d_hidden0 + (int64_t)(b0 + r) * H + c);
-        *reinterpret_cast<float4*>(C1 + r * ldh + c) = *reinterpret_cast<const float4*>(a.d_hidden0 + ((int64_t)B + b0 + r) * H + c);
-      }
+    if (t >= 0) ct_bwd_load_carries(a, dm, C0, C1, b0, nrows, tid);      // carries of step t+1 (written by the previous launch)
     // ================= Part A: BatchNorm backward of step s = t+1 =========================================================
     const int s = t + 1;
-    reduce_partials<NTHR>(a.bn_part + (int64_t)s * dm.nblk * 2 * H, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch);
-    if (blockIdx.x == 0)
-      for (int f = tid; f < 2 * H; f += NTHR) a.bn_sums[(int64_t)s * 2 * H + f] = red[f];
-    const float invB = 1.0f / (float)B;
-    const float* stats = a.sv.bn_stats + (int64_t)s * 2 * H;
-    for (int e = tid; e < 16 * H4; e += NTHR) {
-      const int r = e / H4, c = (e - r * H4) * 4;
-      if (r >= nrows) continue;
-      const int64_t row = ((int64_t)s * B + b0 + r) * H + c;
-      const float4 u4 = *reinterpret_cast<const float4*>(a.sv.u + row), d4 = *reinterpret_cast<const float4*>(a.dbn + row);
-      const float4 m4 = *reinterpret_cast<const float4*>(stats + c), i4 = *reinterpret_cast<const float4*>(stats + H + c);
-      const float4 g4 = *reinterpret_cast<const float4*>(a.w.bn_w + c);
-      const float uu[4] = {u4.x, u4.y, u4.z, u4.w}, db[4] = {d4.x, d4.y, d4.z, d4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w},
-                  ii[4] = {i4.x, i4.y, i4.z, i4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
-      float du[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float xhat = (uu[k] - mm[k]) * ii[k];
-        du[k] = gg[k] * ii[k] * (db[k] - red[c + k] * invB - xhat * red[H + c + k] * invB);
-      }
-      const float4 du4 = make_float4(du[0], du[1], du[2], du[3]);
-      *reinterpret_cast<float4*>(a.du + row) = du4;
-      *reinterpret_cast<float4*>(Xdu + r * ldh + c) = du4;
-    }
+    ct_bn_bwd_finish(a, dm, s, red, red_scratch, Xdu, b0, nrows, tid);
     if (t < 0) return;
     lds_barrier();
     // the feedback term: d y_t += du_s W_pre   (rows = output feature e, contraction over the H outputs of pre_linear)

@@ -28,13 +28,6 @@
 
 namespace g2v {
 
-// Biased batch variance from the sums over the batch of c = u - b_pre: s2 = sum c^2, mv = sum c / B.  One row has no spread: its
-// variance is 0, not what the difference leaves -- the compiler contracts it to fma(-mv, mv, s2), which at B = 1 is the rounding
-// residue of mv^2, up to 2^-24 c^2, and against eps = 1e-5 that moved 1 / sqrt(var + eps) by 2e-3 at |c| of a few.
-__device__ __forceinline__ float bn_batch_var(float s2, float mv, int B) {
-  return B > 1 ? fmaxf(s2 / (float)B - mv * mv, 0.f) : 0.f;
-}
-
 // =====================================================================================================================
 // forward: launch j of S1 + 1
 // =====================================================================================================================
@@ -66,36 +59,14 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_fwd_kernel(const int64_t* _
   const int b0 = blockIdx.x * 16;
   const int nrows = min(16, B - b0);
   const int i = lane & 15, q = lane >> 4;
-  const int H4 = H >> 2;
   const bool training = dm.training != 0;
   const bool has_tail = j > 0, has_head = j < S1;
   const int t = j - 1;                                   // the step whose tail this launch runs
   const int npre = max(1, min(dm.n_pre, S1));            // steps fed from `codes` (teacher forcing :737-739; step 0 always)
 
   // ---- prefetch this block's rows of u_t, h0_t, h1_t (written by the previous launch on some other CU) -------------------
-  constexpr int NPF = 2;                                  // 16 x H / 4 <= 1024 float4 (H <= 256)
-  float4 pu[NPF], ph0[NPF], ph1[NPF];
-  int pr[NPF], pc[NPF];
-  bool pv[NPF];
-#pragma unroll
-  for (int k = 0; k < NPF; ++k) {
-    const int e = tid + k * NTHR;
-    pr[k] = e / H4;
-    pc[k] = (e - pr[k] * H4) * 4;
-    pv[k] = e < 16 * H4 && pr[k] < nrows;
-    pu[k] = ph0[k] = ph1[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pv[k]) {
-      if (has_tail) {
-        const int64_t row = ((int64_t)t * B + b0 + pr[k]) * H + pc[k];
-        pu[k] = *reinterpret_cast<const float4*>(sv.u + row);
-        ph0[k] = *reinterpret_cast<const float4*>(sv.h0 + row);
-        ph1[k] = *reinterpret_cast<const float4*>(sv.h1 + row);
-      } else {
-        ph0[k] = *reinterpret_cast<const float4*>(h_init + (int64_t)(b0 + pr[k]) * H + pc[k]);
-        ph1[k] = *reinterpret_cast<const float4*>(h_init + ((int64_t)B + b0 + pr[k]) * H + pc[k]);
-      }
-    }
-  }
+  CtRowPf pf;
+  ct_fwd_prefetch(pf, sv, h_init, t, has_tail, B, H, b0, nrows, tid);
   // zero what the MFMA contractions must see as zero: padding columns, rows >= nrows
   if (nrows < 16 || Hp != H || Hinp != Hin) {
     for (int e = tid; e < 5 * 16 * ldh + 16 * ldx; e += NTHR) smem[e] = 0.f;
@@ -104,38 +75,11 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_fwd_kernel(const int64_t* _
 
   if (!has_tail) {
     // state in front of step 0 = encoder_hidden[:2] (:667-669)
-#pragma unroll
-    for (int k = 0; k < NPF; ++k)
-      if (pv[k]) {
-        *reinterpret_cast<float4*>(sv.h0 + (int64_t)(b0 + pr[k]) * H + pc[k]) = ph0[k];
-        *reinterpret_cast<float4*>(sv.h1 + (int64_t)(b0 + pr[k]) * H + pc[k]) = ph1[k];
-        *reinterpret_cast<float4*>(Xh1n + pr[k] * ldh + pc[k]) = ph1[k];      // (attention of step 0 scores h1_0)
-      }
+    ct_fwd_init_state(pf, sv, B, H, b0, Xh1n, ldh);      // (attention of step 0 scores h1_0)
   } else {
     // ---- (a) BatchNorm statistics of u_t -------------------------------------------------------------------------------
     if (training) {
-      const float* part = sv.bn_partial + (int64_t)(t & 1) * dm.nblk * 2 * H;
-      reduce_partials<NTHR>(part, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch);
-      for (int f = tid; f < H; f += NTHR) {
-        const float s1 = red[f], s2 = red[H + f];
-        const float mv = s1 / (float)B;
-        const float var = bn_batch_var(s2, mv, B);
-        const float mean = mv + w.b_pre[f];
-        const float invstd = bn_invstd_(var);
-        st[f] = mean;
-        st[Hp + f] = invstd;
-        if (blockIdx.x == 0) {
-          sv.bn_stats[(int64_t)t * 2 * H + f] = mean;
-          sv.bn_stats[(int64_t)t * 2 * H + H + f] = invstd;
-          // running statistics: momentum 0.1, unbiased variance; one update per decode step, in step order (stream order)
-          // (bn_running_mean == NULL while training: the caller commits them behind the backward, g2v_bn_running_update_invstd)
-          if (w.bn_running_mean) {
-            const float unb = (B > 1) ? var * (float)B / (float)(B - 1) : var;
-            w.bn_running_mean[f] = 0.9f * w.bn_running_mean[f] + 0.1f * mean;
-            w.bn_running_var[f] = 0.9f * w.bn_running_var[f] + 0.1f * unb;
-          }
-        }
-      }
+      ct_bn_finish_fwd<true>(w, sv, dm, t, st, red, red_scratch, tid);
     } else {
       for (int f = tid; f < H; f += NTHR) {
         st[f] = w.bn_running_mean[f];
@@ -144,34 +88,11 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_fwd_kernel(const int64_t* _
     }
     lds_barrier();
     // ---- (b) a_t = ReLU(BN(u_t)); stage the previous hidden states -----------------------------------------------------
-#pragma unroll
-    for (int k = 0; k < NPF; ++k)
-      if (pv[k]) {
-        const int c = pc[k];
-        const float4 g4 = *reinterpret_cast<const float4*>(w.bn_w + c), b4 = *reinterpret_cast<const float4*>(w.bn_b + c);
-        const float4 m4 = *reinterpret_cast<const float4*>(st + c), i4 = *reinterpret_cast<const float4*>(st + Hp + c);
-        float4 a4;
-        a4.x = fmaxf((pu[k].x - m4.x) * i4.x * g4.x + b4.x, 0.f);
-        a4.y = fmaxf((pu[k].y - m4.y) * i4.y * g4.y + b4.y, 0.f);
-        a4.z = fmaxf((pu[k].z - m4.z) * i4.z * g4.z + b4.z, 0.f);
-        a4.w = fmaxf((pu[k].w - m4.w) * i4.w * g4.w + b4.w, 0.f);
-        *reinterpret_cast<float4*>(Xa + pr[k] * ldh + c) = a4;
-        *reinterpret_cast<float4*>(Xh0 + pr[k] * ldh + c) = ph0[k];
-        *reinterpret_cast<float4*>(Xh1 + pr[k] * ldh + c) = ph1[k];
-        if (sv.a) *reinterpret_cast<float4*>(sv.a + ((int64_t)t * B + b0 + pr[k]) * H + c) = a4;
-      }
+    ct_bn_relu_stage(pf, w, sv, st, Xa, Xh0, Xh1, ldh, t, B, H, b0);
     lds_barrier();
     // ---- (c) GRU layer 0, (d) GRU layer 1 ------------------------------------------------------------------------------
     const bool drop = training && keep_l0 && dm.p_drop > 0.f;
-    gru_cell_fwd<0>(pk.ih0, pk.hh0, w.b_ih0, w.b_hh0, Xa, Xh0, ldh, H, Hp, Xx1, sv.h0 + ((int64_t)(t + 1) * B + b0) * H,
-                    sv.gates0 ? sv.gates0 + ((int64_t)t * B + b0) * 4 * H : nullptr,
-                    drop ? keep_l0 + ((int64_t)t * B + b0) * H : nullptr, 1.0f / (1.0f - dm.p_drop),
-                    (drop && sv.x1) ? sv.x1 + ((int64_t)t * B + b0) * H : nullptr, nrows, lane, wave, NW);
-    lds_barrier();
-    gru_cell_fwd<0>(pk.ih1, pk.hh1, w.b_ih1, w.b_hh1, Xx1, Xh1, ldh, H, Hp, Xh1n, sv.h1 + ((int64_t)(t + 1) * B + b0) * H,
-                    sv.gates1 ? sv.gates1 + ((int64_t)t * B + b0) * 4 * H : nullptr, nullptr, 1.0f, nullptr, nrows, lane, wave,
-                    NW);
-    lds_barrier();
+    ct_cells_fwd(pk, w, sv, keep_l0, drop, dm, t, b0, nrows, Xa, Xh0, Xh1, Xx1, Xh1n, lane, wave);
     // ---- (e) logits_t = out(h1_{t+1}); row argmax (greedy feedback :740-744) -------------------------------------------
     {
       const int ntile = (K + 15) >> 4;
@@ -249,9 +170,9 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_fwd_kernel(const int64_t* _
   {
     const bool edrop = training && keep_emb != nullptr;
 #pragma unroll
-    for (int k = 0; k < NPF; ++k)
-      if (pv[k]) {
-        const int r = pr[k], c = pc[k];
+    for (int k = 0; k < CT_NPF; ++k)
+      if (pf.v[k]) {
+        const int r = pf.r[k], c = pf.c[k];
         float4 e4 = *reinterpret_cast<const float4*>(w.emb + (int64_t)ids_l[r] * H + c);
         if (edrop) {
           const uint32_t kp = *reinterpret_cast<const uint32_t*>(keep_emb + ((int64_t)j * B + b0 + r) * H + c);
@@ -265,99 +186,12 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_fwd_kernel(const int64_t* _
       }
   }
   // ---- Bahdanau attention on h1_j (Attn.forward / score :160-198, context :353-359) ----------------------------------------
-  if (dm.att) {
-    float* Xhp = Xa;                   // a_t is dead
-    const int ntile = Hp >> 4;
-    lds_barrier();                     // (Xa readers of cell 0 are long past; ids / Xe writes above)
-    for (int ft = wave; ft < ntile; ft += NW) {
-      const int f0 = 16 * ft + 4 * q;
-      f32x4 acc[1] = {(f32x4){0.f, 0.f, 0.f, 0.f}};
-      wave_gemm_p<1, 0>(acc, pk.attn_h, Hp >> 4, ft, 0, Xh1n, ldh, lane);
-      if (f0 + 3 < H) {
-        const float4 ba = *reinterpret_cast<const float4*>(w.b_attn + f0);
-        const float4 h4 = make_float4(acc[0][0] + ba.x, acc[0][1] + ba.y, acc[0][2] + ba.z, acc[0][3] + ba.w);
-        *reinterpret_cast<float4*>(Xhp + i * ldh + f0) = h4;
-        if (i < nrows && sv.hp) *reinterpret_cast<float4*>(sv.hp + ((int64_t)j * B + b0 + i) * H + f0) = h4;
-      }
-    }
-    lds_barrier();
-    // scores: one thread per (row, position); 16 x Tw <= 1024 pairs
-    for (int p = tid; p < 16 * Tw; p += NTHR) {
-      const int r = p / Tw, tw = p - r * Tw;
-      float e = 0.f;
-      if (r < nrows) {
-        const float* epr = ep + ((int64_t)tw * B + b0 + r) * H;
-        const float* hpr = Xhp + r * ldh;
-        float e0 = 0.f, e1 = 0.f, e2 = 0.f, e3 = 0.f;
-        for (int c = 0; c < H; c += 4) {
-          const float4 p4 = *reinterpret_cast<const float4*>(epr + c), h4 = *reinterpret_cast<const float4*>(hpr + c);
-          const float4 v4 = *reinterpret_cast<const float4*>(w.v_attn + c);
-          e0 += v4.x * tanhf_(h4.x + p4.x);
-          e1 += v4.y * tanhf_(h4.y + p4.y);
-          e2 += v4.z * tanhf_(h4.z + p4.z);
-          e3 += v4.w * tanhf_(h4.w + p4.w);
-        }
-        e = (e0 + e1) + (e2 + e3);
-      }
-      sc[r * Tw + tw] = e;
-    }
-    lds_barrier();
-    if (tid < 16 && tid < nrows) {      // softmax over ALL Tw positions (the reference does not mask padded positions)
-      float mx = -INFINITY;
-      for (int tw = 0; tw < Tw; ++tw) mx = fmaxf(mx, sc[tid * Tw + tw]);
-      float sum = 0.f;
-      for (int tw = 0; tw < Tw; ++tw) sum += expf(sc[tid * Tw + tw] - mx);
-      const float inv = 1.0f / sum;
-      for (int tw = 0; tw < Tw; ++tw) {
-        const float ww = expf(sc[tid * Tw + tw] - mx) * inv;
-        sc[tid * Tw + tw] = ww;
-        if (sv.attw) sv.attw[((int64_t)j * B + b0 + tid) * Tw + tw] = ww;
-      }
-    }
-    lds_barrier();
-#pragma unroll
-    for (int k = 0; k < NPF; ++k)
-      if (pv[k]) {
-        const int r = pr[k], c = pc[k];
-        float4 c4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int tw = 0; tw < Tw; ++tw) {
-          const float ww = sc[r * Tw + tw];
-          const float4 n4 = *reinterpret_cast<const float4*>(enc + ((int64_t)tw * B + b0 + r) * H + c);
-          c4.x += ww * n4.x; c4.y += ww * n4.y; c4.z += ww * n4.z; c4.w += ww * n4.w;
-        }
-        *reinterpret_cast<float4*>(Xe + r * ldx + H + c) = c4;
-        *reinterpret_cast<float4*>(sv.ec + ((int64_t)j * B + b0 + r) * Hin + H + c) = c4;
-      }
-  }
+  if (dm.att)      // (a_t is dead: hp takes its tile)
+    ct_attn_head_fwd(pk.attn_h, w, sv, enc, ep, Xh1n, Xa, sc, Xe + H, ldx, sv.ec + ((int64_t)j * B + b0) * Hin + H, Hin, true, pf, dm,
+                     j, b0, nrows, tid);
   lds_barrier();
   // ---- u_j = pre_linear.0(x_j) and per-workgroup BatchNorm partial sums of (u - b) --------------------------------------------
-  {
-    const int ntile = Hp >> 4;
-    float* part = sv.bn_partial + ((int64_t)(j & 1) * dm.nblk + blockIdx.x) * 2 * H;
-    for (int ft = wave; ft < ntile; ft += NW) {
-      const int f0 = 16 * ft + 4 * q;
-      const bool vec = f0 + 3 < H;       // (H % 4 == 0: a lane's group of four features is whole or padding)
-      float4 bp = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (vec) bp = *reinterpret_cast<const float4*>(w.b_pre + f0);
-      f32x4 acc[1] = {(f32x4){0.f, 0.f, 0.f, 0.f}};
-      wave_gemm_p<1, 0>(acc, pk.pre, Hinp >> 4, ft, 0, Xe, ldx, lane);      // (every lane of the wave: an MFMA is not predicated)
-      if (!vec) continue;               // (uniform per DPP row of 16 lanes: the reductions below stay whole)
-      float s1[4], s2[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = (i < nrows) ? acc[0][r] : 0.f;
-        s1[r] = reduce16(v);
-        s2[r] = reduce16(v * v);
-      }
-      if (i < nrows)
-        *reinterpret_cast<float4*>(sv.u + ((int64_t)j * B + b0 + i) * H + f0) =
-            make_float4(acc[0][0] + bp.x, acc[0][1] + bp.y, acc[0][2] + bp.z, acc[0][3] + bp.w);
-      if (i == 0) {
-        *reinterpret_cast<float4*>(part + f0) = make_float4(s1[0], s1[1], s1[2], s1[3]);
-        *reinterpret_cast<float4*>(part + H + f0) = make_float4(s2[0], s2[1], s2[2], s2[3]);
-      }
-    }
-  }
+  ct_pre_linear_partials(pk.pre, Hinp >> 4, Xe, nullptr, 0, nullptr, ldx, w, sv, dm, j, b0, nrows, lane, wave);
 }
 
 // no attention: the whole BPTT in one launch
@@ -434,7 +268,7 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_bwd_att_kernel(CodeBwdArgs 
   constexpr int NTHR = CT_NTHR, NW = CT_NW;
   const CtBwdLds L = ct_bwd_lds(dm.H, dm.K);
   const int S1 = dm.S1, B = dm.B, H = dm.H, Tw = dm.Tw;
-  const int Hp = (H + 15) & ~15, ldh = Hp + 4, H4 = H >> 2;
+  const int Hp = (H + 15) & ~15, ldh = Hp + 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = lane & 15, q = lane >> 4;
   const int b0 = blockIdx.x * 16, nrows = min(16, B - b0);
@@ -451,44 +285,10 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_bwd_att_kernel(CodeBwdArgs 
   for (int e = tid; e < L.total; e += NTHR) smem[e] = 0.f;
   lds_barrier();
   if (!last) {
-    // carries of step t+1 (written by the previous launch)
-    for (int e = tid; e < 16 * H4; e += NTHR) {
-      const int r = e / H4, c = (e - r * H4) * 4;
-      if (r >= nrows) continue;
-      *reinterpret_cast<float4*>(C0 + r * ldh + c) = *reinterpret_cast<const float4*>(a.d_hidden0 + (int64_t)(b0 + r) * H + c);
-      *reinterpret_cast<float4*>(C1 + r * ldh + c) = *reinterpret_cast<const float4*>(a.d_hidden0 + ((int64_t)B + b0 + r) * H + c);
-    }
+    ct_bwd_load_carries(a, dm, C0, C1, b0, nrows, tid);      // carries of step t+1 (written by the previous launch)
     // ================= Part A: BatchNorm backward of step s = t+1, attention backward of step s ==========================
     const int s = t + 1;
-    reduce_partials<NTHR>(a.bn_part + (int64_t)s * dm.nblk * 2 * H, dm.nblk, 2 * H, red, red_scratch, tid, dm.scratch);
-    if (blockIdx.x == 0)
-      for (int f = tid; f < 2 * H; f += NTHR) a.bn_sums[(int64_t)s * 2 * H + f] = red[f];
-    const float invB = 1.0f / (float)B;
-    const float* stats = a.sv.bn_stats + (int64_t)s * 2 * H;
-    for (int e = tid; e < 16 * H4; e += NTHR) {
-      const int r = e / H4, c = (e - r * H4) * 4;
-      if (r >= nrows) continue;
-      const int64_t row = ((int64_t)s * B + b0 + r) * H + c;
-      const float4 u4 = *reinterpret_cast<const float4*>(a.sv.u + row), d4 = *reinterpret_cast<const float4*>(a.dbn + row);
-      const float4 m4 = *reinterpret_cast<const float4*>(stats + c), i4 = *reinterpret_cast<const float4*>(stats + H + c);
-      const float4 g4 = *reinterpret_cast<const float4*>(a.w.bn_w + c);
-      const float uu[4] = {u4.x, u4.y, u4.z, u4.w}, db[4] = {d4.x, d4.y, d4.z, d4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w},
-                  ii[4] = {i4.x, i4.y, i4.z, i4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
-      float du[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float xhat = (uu[k] - mm[k]) * ii[k];
-        du[k] = gg[k] * ii[k] * (db[k] - red[c + k] * invB - xhat * red[H + c + k] * invB);
-      }
-      const float4 du4 = make_float4(du[0], du[1], du[2], du[3]);
-      *reinterpret_cast<float4*>(a.du + row) = du4;
-      *reinterpret_cast<float4*>(Xdu + r * ldh + c) = du4;
-    }
-    // attention weights of step s
-    for (int p = tid; p < 16 * Tw; p += NTHR) {
-      const int r = p / Tw, tw = p - r * Tw;
-      wsc[p] = (r < nrows) ? a.sv.attw[((int64_t)s * B + b0 + r) * Tw + tw] : 0.f;
-    }
+    ct_bn_bwd_finish(a, dm, s, red, red_scratch, Xdu, b0, nrows, tid);
     lds_barrier();
     // d ctx_s = du_s W_pre[:, H:2H]   (rows = context feature, contraction over the H outputs of pre_linear)
     const int nth = Hp >> 4;
@@ -502,89 +302,8 @@ __global__ __launch_bounds__(CT_NTHR) void code_step_bwd_att_kernel(CodeBwdArgs 
       }
     }
     lds_barrier();
-    // d_w[r][tw] = <d ctx[r], enc[tw, r]>
-    for (int p = tid; p < 16 * Tw; p += NTHR) {
-      const int r = p / Tw, tw = p - r * Tw;
-      float e = 0.f;
-      if (r < nrows) {
-        const float* er = a.enc + ((int64_t)tw * B + b0 + r) * H;
-        const float* dc = Xdc + r * ldh;
-        float e0 = 0.f, e1 = 0.f, e2 = 0.f, e3 = 0.f;
-        for (int c = 0; c < H; c += 4) {
-          const float4 n4 = *reinterpret_cast<const float4*>(er + c), d4 = *reinterpret_cast<const float4*>(dc + c);
-          e0 += d4.x * n4.x; e1 += d4.y * n4.y; e2 += d4.z * n4.z; e3 += d4.w * n4.w;
-        }
-        e = (e0 + e1) + (e2 + e3);
-      }
-      dsc[p] = e;
-    }
-    lds_barrier();
-    if (tid < 16) {     // softmax backward: ds = w (d_w - <w, d_w>)
-      float dot = 0.f;
-      for (int tw = 0; tw < Tw; ++tw) dot += wsc[tid * Tw + tw] * dsc[tid * Tw + tw];
-      for (int tw = 0; tw < Tw; ++tw) dsc[tid * Tw + tw] = wsc[tid * Tw + tw] * (dsc[tid * Tw + tw] - dot);
-    }
-    lds_barrier();
-    // per (row, feature group): d hp, d v partial, d_ep / d_enc rows (accumulated over the steps by this workgroup alone)
-    {
-      float* dvp = smem + L.gh;        // [16][ldh] d v contributions per row (Gh is free until the cells)
-      const bool acc_steps = (s != S1 - 1);
-      for (int e = tid; e < 16 * H4; e += NTHR) {
-        const int r = e / H4, c = (e - r * H4) * 4;
-        float dh[4] = {0.f, 0.f, 0.f, 0.f}, dv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (r < nrows) {
-          const float4 hp4 = *reinterpret_cast<const float4*>(a.sv.hp + ((int64_t)s * B + b0 + r) * H + c);
-          const float4 v4 = *reinterpret_cast<const float4*>(a.w.v_attn + c);
-          const float4 dc4 = *reinterpret_cast<const float4*>(Xdc + r * ldh + c);
-          const float hp[4] = {hp4.x, hp4.y, hp4.z, hp4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, dc[4] = {dc4.x, dc4.y, dc4.z, dc4.w};
-          for (int tw = 0; tw < Tw; ++tw) {
-            const int64_t row = ((int64_t)tw * B + b0 + r) * H + c;
-            const float4 p4 = *reinterpret_cast<const float4*>(a.ep + row);
-            const float pp[4] = {p4.x, p4.y, p4.z, p4.w};
-            const float ds = dsc[r * Tw + tw], ww = wsc[r * Tw + tw];
-            float de[4], dn[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const float en = tanhf_(hp[k] + pp[k]);
-              de[k] = ds * vv[k] * (1.0f - en * en);
-              dh[k] += de[k];
-              dv[k] += ds * en;
-              dn[k] = ww * dc[k];
-            }
-            float4 o1 = make_float4(de[0], de[1], de[2], de[3]), o2 = make_float4(dn[0], dn[1], dn[2], dn[3]);
-            if (acc_steps) {
-              const float4 q1 = *reinterpret_cast<const float4*>(a.d_ep + row), q2 = *reinterpret_cast<const float4*>(a.d_enc + row);
-              o1.x += q1.x; o1.y += q1.y; o1.z += q1.z; o1.w += q1.w;
-              o2.x += q2.x; o2.y += q2.y; o2.z += q2.z; o2.w += q2.w;
-            }
-            *reinterpret_cast<float4*>(a.d_ep + row) = o1;
-            *reinterpret_cast<float4*>(a.d_enc + row) = o2;
-          }
-          *reinterpret_cast<float4*>(a.dhp + ((int64_t)s * B + b0 + r) * H + c) = make_float4(dh[0], dh[1], dh[2], dh[3]);
-        }
-        *reinterpret_cast<float4*>(Xdhp + r * ldh + c) = make_float4(dh[0], dh[1], dh[2], dh[3]);
-        *reinterpret_cast<float4*>(dvp + r * ldh + c) = make_float4(dv[0], dv[1], dv[2], dv[3]);
-      }
-      lds_barrier();
-      for (int f = tid; f < H; f += NTHR) {
-        float sdv = 0.f;
-        for (int r = 0; r < 16; ++r) sdv += dvp[r * ldh + f];
-        float* o = a.dv_partial + (int64_t)blockIdx.x * H + f;
-        *o = acc_steps ? *o + sdv : sdv;
-      }
-    }
-    // carry1 += d hp W_attn[:, :H]     (the state the attention of step s scored = h1 in front of step s = output of step t)
-    for (int ft = wave; ft < nth; ft += NW) {
-      const int f0 = 16 * ft + 4 * q;
-      f32x4 acc[1] = {(f32x4){0.f, 0.f, 0.f, 0.f}};
-      wave_gemm_p<1, 0>(acc, a.tw.attn_h_t, Hp >> 4, ft, 0, Xdhp, ldh, lane);
-      if (f0 + 3 < H) {
-        float4 c4 = *reinterpret_cast<const float4*>(C1 + i * ldh + f0);
-        c4.x += acc[0][0]; c4.y += acc[0][1]; c4.z += acc[0][2]; c4.w += acc[0][3];
-        *reinterpret_cast<float4*>(C1 + i * ldh + f0) = c4;
-      }
-    }
-    lds_barrier();
+    // (Gh is free until the cells: the BatchNorm sums are dead before the d v rows land)
+    ct_attn_bwd_step(a, dm, s, Xdc, Xdhp, dsc, wsc, smem + L.gh, C1, b0, nrows, tid);
     // Xdl / Gi / Gh / Dd were borrowed: padding back to zero for the cells
     for (int e = tid; e < L.c0; e += NTHR) smem[e] = 0.f;
     lds_barrier();

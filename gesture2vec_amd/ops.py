@@ -820,6 +820,43 @@ def latent_rollout_bwd(d_out, weights: dict, saved: dict, grads: dict, keep_l0, 
           "latent_rollout_bwd")
 
 
+# ------------------------------------------------------------------------------------------ the text -> pose baseline (Seq2SeqNet)
+def pose_attn_rollout_ok(S1, B, H, D, Tw) -> bool:
+    return bool(_lib_().g2v_pose_attn_rollout_ok(int(S1), int(B), int(H), int(D), int(Tw)))
+
+
+def pose_attn_rollout_plan(S1, B, H, D, Tw, fused_min_rows) -> int:
+    """g2v_pose_attn_rollout_plan: 0 the per-operator chain, 1 the fused step kernels (host arithmetic only)."""
+    return int(_lib_().g2v_pose_attn_rollout_plan(int(S1), int(B), int(H), int(D), int(Tw), int(min(fused_min_rows, 2 ** 31 - 1))))
+
+
+def pose_attn_ldec(H, D) -> int:
+    """Row stride of the saved input rows [x | c] (include/g2v.h: g2v_pose_attn_rollout_fwd)."""
+    return (D + H + 3) & ~3
+
+
+def pose_attn_rollout_fwd(target, h_init, enc, enc_proj, weights: dict, saved: dict, keep_l0, p_drop, n_pre, S1, B, H, D, Tw,
+                          workspace_bytes=None):
+    """g2v_pose_attn_rollout_fwd: S1 + 1 launches of the fused decoder-step kernel of the attention decoder with continuous
+    feedback (weights / saved: dicts of tensors named as the fields of g2v_code_dec_weights / g2v_code_dec_saved with K := D;
+    missing = NULL).  workspace_bytes: what the entry is told it has (tests of the refusal)."""
+    lib = _lib_()
+    ws = workspace(lib.g2v_pose_attn_rollout_fwd_workspace(H, D), h_init.device, "posefwd")
+    check(lib.g2v_pose_attn_rollout_fwd(_p(target), _p(h_init), _p(enc), _p(enc_proj), C.byref(struct_from(CodeDecWeights, weights)),
+                                        C.byref(struct_from(CodeDecSaved, saved)), _p(keep_l0), float(p_drop), int(n_pre), S1, B, H, D,
+                                        int(Tw), _p(ws), ws.numel() if workspace_bytes is None else int(workspace_bytes), _stream()),
+          "pose_attn_rollout_fwd")
+
+
+def pose_attn_rollout_bwd(d_out, enc, enc_proj, weights: dict, saved: dict, grads: dict, keep_l0, p_drop, n_pre, S1, B, H, D, Tw):
+    lib = _lib_()
+    ws = workspace(lib.g2v_pose_attn_rollout_bwd_workspace(S1, B, H, D, int(Tw)), d_out.device, "posebwd")
+    check(lib.g2v_pose_attn_rollout_bwd(_p(_chk(d_out)), _p(enc), _p(enc_proj), C.byref(struct_from(CodeDecWeights, weights)),
+                                        C.byref(struct_from(CodeDecSaved, saved)), C.byref(struct_from(CodeDecGrads, grads)),
+                                        _p(keep_l0), float(p_drop), int(n_pre), S1, B, H, D, int(Tw), _p(ws), ws.numel(), _stream()),
+          "pose_attn_rollout_bwd")
+
+
 # ------------------------------------------------------------------------------------------ loss / optimiser / rng
 def custom_loss_fwd_bwd(y_tbd, target_btd, w_l1, w_cont, w_var, g_scale=1.0, want_grad=True):
     T, B, D = y_tbd.shape

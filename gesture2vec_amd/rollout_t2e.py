@@ -483,3 +483,92 @@ class LatentDecoderRollout(torch.autograd.Function):
         return (gr["d_hidden0"], None, gr["d_w_pre"], gr["d_b_pre"], gr["d_bn_w"], gr["d_bn_b"],
                 gr["d_w_ih0"], gr["d_w_hh0"], gr["d_b_ih0"], gr["d_b_hh0"], gr["d_w_ih1"], gr["d_w_hh1"], gr["d_b_ih1"], gr["d_b_hh1"],
                 gr["d_w_out"], gr["d_b_out"])
+
+
+# ---- the text -> pose baseline (Seq2SeqNet): attention AND continuous feedback with its gradient --------------------------------
+# Batch size from which the fused step kernels of csrc/pose_attn.hip (g2v_pose_attn_rollout_fwd / _bwd) serve the training forward
+# of model/seq2seq_net.py; below it the steps are chained from the per-operator autograd nodes.  The decision itself is the
+# library's (include/g2v.h: g2v_pose_attn_rollout_plan); this is its fused_min_rows argument.  MEASURED (scripts/time_baseline.py,
+# profiles/baseline_timing.jsonl): 128 is the smallest batch timed, and the fused route already takes 7.7 ms there
+# against 24.7 ms per iteration, far outside the run-to-run spread; nothing smaller was timed, so nothing smaller is claimed.
+POSE_FUSED_MIN_ROWS = 128
+POSE_FUSED_CALLS = 0
+
+
+def pose_decoder_params(dec) -> List[torch.Tensor]:
+    """Parameter order of PoseAttnRollout for a continuous BahdanauAttnDecoderRNN with attention."""
+    return latent_decoder_params(dec) + [dec.attn.attn.weight, dec.attn.attn.bias, dec.attn.v]
+
+
+def pose_plan(B: int, H: int, D: int, Tw: int, steps: int, L: int) -> int:
+    """0 the per-operator chain, 1 the fused step kernels."""
+    return ops.pose_attn_rollout_plan(steps, B, H, D, Tw, POSE_FUSED_MIN_ROWS) if L == 2 else 0
+
+
+class PoseAttnRollout(torch.autograd.Function):
+    """(hidden0 (2,B,H), encoder_outputs (Tw,B,H), enc_proj (Tw,B,H), spec, *pose_decoder_params) -> outputs (S,B,D) [slot 0 =
+    target[0], slots 1.. = the S-1 decode steps' outputs], attention weights (S-1,B,Tw) (not differentiable).  spec.cod = the
+    targets (S,B,D) float, step-major.  enc_proj = Attn.project_encoder(encoder_outputs) is an INPUT: its gradient comes back from
+    here and the caller's autograd runs the encoder half of attn.attn.weight (the entry leaves d_w_attn[:, H:] zero)."""
+
+    @staticmethod
+    def forward(ctx, hidden0, enc_out, enc_proj, spec: RolloutSpec, *params):
+        global POSE_FUSED_CALLS
+        POSE_FUSED_CALLS += 1
+        S1 = spec.steps
+        B, H = hidden0.shape[1], hidden0.shape[2]
+        Tw = enc_out.shape[0]
+        pre_w, pre_b, bn_w, bn_b = params[:4]
+        (w_ih0, w_hh0, b_ih0, b_hh0), (w_ih1, w_hh1, b_ih1, b_hh1) = params[4:8], params[8:12]
+        out_w, out_b = params[12:14]
+        attn_w, attn_b, attn_v = params[14:17]
+        D = out_w.shape[0]
+        dev = hidden0.device
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+        wd = dict(w_pre=pre_w.contiguous(), b_pre=pre_b, bn_w=bn_w, bn_b=bn_b, bn_running_mean=spec.bn_running_mean,
+                  bn_running_var=spec.bn_running_var, w_ih0=w_ih0.contiguous(), w_hh0=w_hh0.contiguous(), b_ih0=b_ih0, b_hh0=b_hh0,
+                  w_ih1=w_ih1.contiguous(), w_hh1=w_hh1.contiguous(), b_ih1=b_ih1, b_hh1=b_hh1, w_out=out_w.contiguous(), b_out=out_b,
+                  w_attn=attn_w.contiguous(), b_attn=attn_b, v_attn=attn_v.contiguous())
+        drop = spec.dropout_p > 0 and spec.mask_l0 is not None
+        mask_l0 = spec.mask_l0.contiguous() if drop else None
+        nblk = (B + 15) // 16
+        sv = dict(ec=f32(S1, B, ops.pose_attn_ldec(H, D)), u=f32(S1, B, H), a=f32(S1, B, H), bn_stats=f32(S1, 2, H),
+                  h0=f32(S1 + 1, B, H), h1=f32(S1 + 1, B, H), x1=f32(S1, B, H) if drop else None, gates0=f32(S1, B, 4 * H),
+                  gates1=f32(S1, B, 4 * H), bn_partial=f32(2, nblk, 2, H), hp=f32(S1, B, H), attw=f32(S1, B, Tw))
+        target = spec.cod
+        full = f32(S1 + 1, B, D)
+        full[0].copy_(target[0])                                       # outputs[0] = poses[0]
+        sv["logits"] = full[1:]
+        enc, ep = enc_out.contiguous(), enc_proj.contiguous()
+        ops.pose_attn_rollout_fwd(target, hidden0.contiguous(), enc, ep, wd, sv, mask_l0, spec.dropout_p if drop else 0.0,
+                                  spec.n_pre, S1, B, H, D, Tw)
+        if spec.defer_bn is not None:
+            spec.defer_bn.append((sv["bn_stats"], sv["bn_stats"].view(-1)[H:], 2 * H, S1, B, H))
+        ctx.save_for_backward(hidden0, enc_out, enc_proj, *params)
+        ctx.spec, ctx.dims = spec, (S1, B, H, D, Tw)
+        # (the outputs are this node's OUTPUT: see _entry_forward on why they are not kept on ctx)
+        ctx.bufs = dict(wd=wd, sv={k: t for k, t in sv.items() if k != "logits"}, enc=enc, ep=ep, mask_l0=mask_l0, drop=drop)
+        AW = sv["attw"]
+        ctx.mark_non_differentiable(AW)
+        ctx.set_materialize_grads(False)
+        return full, AW
+
+    @staticmethod
+    def backward(ctx, dFULL, _dAW):
+        S1, B, H, D, Tw = ctx.dims
+        if dFULL is None:
+            return (None,) * (4 + 17)
+        b, spec = ctx.bufs, ctx.spec
+        d_out = dFULL.contiguous()[1:]                                  # slot 0 is a constant
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=d_out.device)
+        G = 3 * H
+        gr = dict(d_hidden0=f32(2, B, H), d_emb=f32(Tw, B, H), d_w_pre=f32(H, D + H), d_b_pre=f32(H), d_bn_w=f32(H), d_bn_b=f32(H),
+                  d_w_ih0=f32(G, H), d_w_hh0=f32(G, H), d_b_ih0=f32(G), d_b_hh0=f32(G),
+                  d_w_ih1=f32(G, H), d_w_hh1=f32(G, H), d_b_ih1=f32(G), d_b_hh1=f32(G), d_w_out=f32(D, H), d_b_out=f32(D),
+                  d_w_attn=f32(H, 2 * H), d_b_attn=f32(H), d_v_attn=f32(H), d_enc=f32(Tw, B, H))
+        ops.pose_attn_rollout_bwd(d_out, b["enc"], b["ep"], b["wd"], b["sv"], gr, b["mask_l0"], spec.dropout_p if b["drop"] else 0.0,
+                                  spec.n_pre, S1, B, H, D, Tw)
+        # gr["d_emb"] carries d loss / d enc_proj in this mode (include/g2v.h)
+        return (gr["d_hidden0"], gr["d_enc"], gr["d_emb"], None, gr["d_w_pre"], gr["d_b_pre"], gr["d_bn_w"], gr["d_bn_b"],
+                gr["d_w_ih0"], gr["d_w_hh0"], gr["d_b_ih0"], gr["d_b_hh0"], gr["d_w_ih1"], gr["d_w_hh1"], gr["d_b_ih1"], gr["d_b_hh1"],
+                gr["d_w_out"], gr["d_b_out"], gr["d_w_attn"], gr["d_b_attn"], gr["d_v_attn"])

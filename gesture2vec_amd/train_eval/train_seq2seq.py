@@ -675,3 +675,57 @@ class GraphedText2EmbeddingStep:
         """the last replay's loss as a float, behind a fault check (the value of an unapplied replay is never returned)"""
         self.check_faults()
         return float(self.loss.detach())
+
+
+def _baseline_step(args, net, optim, in_text, in_lengths, target_poses):
+    """One iteration of the text -> pose baseline -> (loss, outputs).  BatchNorm's running statistics are held back until the
+    backward is through (committed in front of clip + Adam); whatever is raised, net.deferred_bn is reset."""
+    defer = hasattr(net, "commit_bn_running_stats")
+    optim.zero_grad()
+    try:
+        if defer:
+            net.deferred_bn = []
+        outputs = net(in_text, in_lengths, target_poses, None)
+        loss = custom_loss(outputs, target_poses[:, : outputs.shape[1]], args)
+        loss.backward()
+        if defer:
+            net.commit_bn_running_stats()
+    finally:
+        if defer:
+            net.deferred_bn = None
+    optim.step()
+    return loss.detach(), outputs
+
+
+def train_iter_seq2seq(args, epoch: int, in_text, in_lengths, target_poses, net: torch.nn.Module, optim):
+    """One training iteration of the text -> pose baseline (reference :91-133; net = model.seq2seq_net.Seq2SeqNet): custom_loss over
+    ALL n_frames frames of the outputs (frame 0 is the seed pose itself), backward, clip_grad_norm_(5) + Adam (fused in `optim`, a
+    gesture2vec_amd.flat.FlatClipAdam) -> {"loss": float}.  Data-parallel training and graph replay of this trainer are not built:
+    a wrapped net is refused by name."""
+    from ..flat import FlatClipAdam
+    if not isinstance(optim, FlatClipAdam):
+        raise TypeError("use gesture2vec_amd.flat.FlatClipAdam (clip + Adam are one fused HIP launch)")
+    if hasattr(net, "module"):
+        raise NotImplementedError("data-parallel training of the baseline (a wrapped net) is not built")
+    if torch.cuda.is_current_stream_capturing():
+        raise NotImplementedError("graph replay of train_iter_seq2seq is not built")
+    from .. import _lib
+    from ..fault_policy import POLICY
+    lib = _lib.load()
+    for attempt in (0, 1):
+        loss, outputs = _baseline_step(args, net, optim, in_text, in_lengths, target_poses)
+        ret = {"loss": loss.item()}
+        # the encoder's small-batch GRU kernels may latch the persistent kernels' fault word (see train_iter_text2embedding): such an
+        # iteration changed nothing -- clip + Adam and the BatchNorm commit read the latch on the device -- and is repeated once
+        f = int(lib.g2v_dec_rollout_persist_fault(0))
+        if f == 0:
+            POLICY.tick()
+            return ret
+        POLICY.on_fault()
+        if attempt == 1:
+            raise RuntimeError(f"persistent kernel fault latch {f} set again on the per-step kernels")
+        import warnings
+        warnings.warn(f"persistent GRU kernels: fault latch {f}; the iteration was not applied and is repeated on the per-step "
+                      "kernels", RuntimeWarning)
+        _uncount_decode_steps(net, outputs.shape[1] - 1)
+    return ret

@@ -1312,6 +1312,58 @@ int g2v_latent_rollout_bwd(const float* d_out, const g2v_code_dec_weights* w, co
                            void* workspace, size_t workspace_bytes, g2v_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The text -> pose seq2seq baseline (reference model/seq2seq_net.py:92-257, Seq2SeqNet): the continuous decoder WITH Bahdanau
+ * attention, fed back with its gradient, as fused per-step kernels (csrc/pose_attn.hip).
+ *   x_t   = target[t] while t < max(1, n_pre), else y_{t-1} -- the previous OUTPUT, with its gradient (:252-255)       (D)
+ *   w_t   = softmax_tw( v . tanh(h1_t W_attn[:, :H]^T + b_attn + enc_proj[tw]) ) over ALL Tw positions (no length mask)
+ *   c_t   = sum_tw w_t[tw] enc[tw]                                                                                   (H)
+ *   u_t   = [x_t | c_t] W_pre^T + b_pre;  a_t = ReLU(BatchNorm1d(u_t))  (batch statistics: this is the training forward)
+ *   h0_{t+1}, h1_{t+1} = GRU(a_t; h0_t, h1_t)  (inter-layer dropout p on h0: keep_l0);   y_t = h1_{t+1} W_out^T + b_out
+ * for t = 0 .. S1-1; h1_t is the top state in front of the step's GRU.  Forward: S1 + 1 launches of one kernel; backward: S1 + 1
+ * launches of one kernel, descending (the launch of step t finishes BatchNorm's backward of step t+1, splits du_{t+1} W_pre into
+ * the feedback into d y_t and d c_{t+1}, and runs the attention backward of step t+1 in front of the cells of step t); a kernel
+ * boundary is the only grid-wide seam, no kernel waits on another workgroup, no float atomics.  Every weight and bias gradient is
+ * one batched product over the S1 x B rows behind the loop.
+ * The structs of the code decoder are reused with K := D (as g2v_latent_rollout_*): w_pre (H, D + H), w_out (D,H), b_out (D),
+ * w_attn (H,2H), b_attn, v_attn; s->logits (S1,B,D) = y; s->hp (S1,B,H), s->attw (S1,B,Tw); s->ec (S1,B,ldec) = the input rows
+ * [x | c], D + H floats at the row stride ldec = round_up(D + H, 4); emb, ids are not read.
+ * Gradients: everything in g2v_code_dec_grads but d_emb is what its name says, with
+ *   d_enc    (Tw,B,H)  the CONTEXT term only (sum_t w_t[tw] d c_t);
+ *   d_emb    (Tw,B,H)  this mode has no embedding: the member carries d loss / d enc_proj, so that no struct changes;
+ *   d_w_attn (H,2H)    [:, :H] = the state half, [:, H:] = 0.
+ * The enc_proj -> enc path through W_attn[:, H:] stays with the caller, as for g2v_attn_bwd: d W_attn[:, H:] = d_enc_proj^T enc
+ * (g2v_linear_bwd_weight) and d enc += d_enc_proj W_attn[:, H:] (g2v_linear_bwd_data).
+ * Served (g2v_pose_attn_rollout_ok): S1 >= 1, B >= 2 (train-mode BatchNorm has no variance at one row), 16 <= H <= 256, H % 4 == 0,
+ * 1 <= D <= 256 -- D % 4 != 0 included: D = 135 is the width the model is trained at --, 1 <= Tw <= 64, both LDS carves within
+ * 160 KB (which in effect ends H at 224).  g2v_pose_attn_rollout_plan is the ONE decision between the per-operator chain (0) and
+ * these entries (1): served and B >= fused_min_rows; C and Python ask it.
+ * target (S1+1,B,D) step-major (slots 0 .. max(1, n_pre) - 1 are read); h_init (2,B,H); enc, enc_proj (Tw,B,H);
+ * d_out (S1,B,D) = d loss / d y as the loss alone gives it; keep_l0 (S1,B,H) uint8 or NULL.
+ * Alignment.  Both entries refuse, before any launch, with "16-byte alignment" (G2V_ERR_ARG), an array their kernels move as
+ * float4s or as words of four keep flags that does not start on a 16-byte boundary; the arrays they move one element at a time
+ * need their element's alignment only.  At D % 4 != 0 the rows of target, y (s->logits) and d_out are not 16-byte aligned: those
+ * arrays, b_out and the context half of an ec row move element-wise; nothing is staged at a padded stride of its own.
+ *   g2v_pose_attn_rollout_fwd   16 bytes: h_init, enc, enc_proj, keep_l0, workspace, every bias, bn_w / bn_b, v_attn, every saved
+ *                               array but bn_stats and attw; at D % 4 == 0 also target, s->logits and b_out.  Element-wise: the
+ *                               weight matrices, bn_running_mean / _var, bn_stats, attw.
+ *   g2v_pose_attn_rollout_bwd   16 bytes: enc, enc_proj, keep_l0, workspace, bn_w, v_attn, every saved array it reads but attw
+ *                               (bn_stats included), d_hidden0, d_enc, d_emb; at D % 4 == 0 also d_out.  Element-wise: the weight
+ *                               matrices, attw; the other gradients go to the dense kernels, which choose their own widths.
+ * ------------------------------------------------------------------------------------------ */
+int g2v_pose_attn_rollout_ok(int S1, int B, int H, int D, int Tw);
+int g2v_pose_attn_rollout_plan(int S1, int B, int H, int D, int Tw, int fused_min_rows);
+size_t g2v_pose_attn_rollout_fwd_workspace(int H, int D);
+int g2v_pose_attn_rollout_fwd(const float* target, const float* h_init, const float* enc, const float* enc_proj,
+                              const g2v_code_dec_weights* w, const g2v_code_dec_saved* s, const uint8_t* keep_l0, float p_drop,
+                              int n_pre, int S1, int B, int H, int D, int Tw, void* workspace, size_t workspace_bytes,
+                              g2v_stream_t stream);
+size_t g2v_pose_attn_rollout_bwd_workspace(int S1, int B, int H, int D, int Tw);
+int g2v_pose_attn_rollout_bwd(const float* d_out, const float* enc, const float* enc_proj, const g2v_code_dec_weights* w,
+                              const g2v_code_dec_saved* s, const g2v_code_dec_grads* g, const uint8_t* keep_l0, float p_drop,
+                              int n_pre, int S1, int B, int H, int D, int Tw, void* workspace, size_t workspace_bytes,
+                              g2v_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Calibration probes used by bench.py to report what the box sustains next to the datasheet peaks (no counterpart in the
  * reference): g2v_probe_mfma_f32 runs `blocks` x 4 waves x `iters` x 8 independent v_mfma_f32_16x16x4_f32 (2048 flop each)
  * without memory traffic (scratch: blocks * 256 floats); g2v_probe_copy streams n floats from src to dst.

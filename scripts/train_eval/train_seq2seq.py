@@ -8,4 +8,4 @@ if _ROOT not in _sys.path:
 
 from gesture2vec_amd.train_eval.train_seq2seq import (  # noqa: E402,F401
     FusedClipAdam, GraphedText2EmbeddingStep, custom_loss, train_iter_Autoencoder_VQ_seq2seq,
-    train_iter_Autoencoder_VQ_seq2seq_dp, train_iter_DAE, train_iter_text2embedding)
+    train_iter_Autoencoder_VQ_seq2seq_dp, train_iter_DAE, train_iter_seq2seq, train_iter_text2embedding)

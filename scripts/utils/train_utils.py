@@ -1,7 +1,7 @@
 """Logging / checkpoint helpers with the reference's contract (scripts/utils/train_utils.py:43-175):
 checkpoint = torch.save({"args", "epoch", "lang_model", "pose_dim", "gen_dict"[, "val_metrics_list", "loss_list"]}),
 `load_checkpoint_and_model(path, device, what)` rebuilds the model through the matching train script's init_model.
-The three model kinds on the accelerated path exist here ("autoencoder_vq", "DAE", "text2embedding"); others raise."""
+The model kinds on the accelerated path exist here ("autoencoder_vq", "DAE", "text2embedding", "baseline"); others raise."""
 from __future__ import annotations
 
 import logging
@@ -68,6 +68,11 @@ def load_checkpoint_and_model(checkpoint_path, _device="cpu", what: str = ""):
     elif what == "text2embedding":
         from train_text2embedding import init_model as t2e_init
         generator, loss_fn = t2e_init(args, lang_model, pose_dim, "cpu")
+        generator.load_state_dict(checkpoint["gen_dict"], strict=True)
+        generator = generator.to(_device)
+    elif what == "baseline":
+        from train import init_model as baseline_init
+        generator, loss_fn = baseline_init(args, lang_model, pose_dim, "cpu")
         generator.load_state_dict(checkpoint["gen_dict"], strict=True)
         generator = generator.to(_device)
     else:
