@@ -991,7 +991,8 @@ __global__ __launch_bounds__(256) void vq_fused_assign_kernel(const float* __res
 // ---- K3, tile-owner form: one workgroup OWNS a 16-code x 16-column tile of dw (and, for column tile 0, the 16 counts) and
 // contracts over ALL rows: onehot(idx)^T (16 codes x rows) * flat (rows x 16 columns) on MFMA, the four waves taking a
 // quarter of the rows each, one in-workgroup sum at the end.  No slabs, no second launch, deterministic; cost independent
-// of how the codes are distributed (a collapsed codebook sends every row to one code).  N % 16 == 0, E % 16 == 0, K % 16 == 0.
+// of how the codes are distributed (a collapsed codebook sends every row to one code).  E % 16 == 0, K % 16 == 0, and
+// N >= 48 so that 3 * per < N and every wave has a row (the launcher sends N >= 1024).
 __global__ __launch_bounds__(256) void vq_stats_owner_kernel(const int64_t* __restrict__ idx, const float* __restrict__ flat,
                                                              float* __restrict__ cnt, float* __restrict__ dw, int N, int E,
                                                              int K) {
@@ -1005,7 +1006,8 @@ __global__ __launch_bounds__(256) void vq_stats_owner_kernel(const int64_t* __re
   // L2s pulled the whole array, 17.3 MB of HBM traffic for 2.4 MB algorithmic).  Speed only, never correctness.
   const int c0 = blockIdx.y * 16, e0 = blockIdx.x * 16;
   const int mycode = c0 + i;
-  const int per = ((N / 4) + 3) & ~3;                  // rows per wave (multiple of 4)
+  const int per = (((N + 3) / 4) + 3) & ~3;            // rows per wave: ceil(N / 4) up to a multiple of 4, so that 4 * per >= N
+                                                       // (from N / 4 the last 1..3 rows of an N with N % 16 in {1, 2, 3} had no wave)
   const int mb = wave * per, me = min(N, mb + per);
   const int* idx32 = reinterpret_cast<const int*>(idx);          // low dwords of the int64 indices
   f32x4 acc = {0.f, 0.f, 0.f, 0.f}, accn = {0.f, 0.f, 0.f, 0.f};
