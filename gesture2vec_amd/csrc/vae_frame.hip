@@ -4,7 +4,8 @@
 //     -> c = z Wf^T + bf -> out = c Wd^T + bd;  loss = mse(out, t) + kl_weight mean(exp(logvar) - logvar - 1 + mean^2)
 //
 // g2v_vaeframe_step: the whole training forward AND backward of one batch as ONE workgroup of sixteen waves, on the design of
-// g2v_vqframe_step (vq_frame.hip; the tile, the four-lane sums and the ld() rule are frame_tile.hpp's).  Nothing is exchanged with
+// g2v_vqframe_step (vq_frame.hip; the tile and its two stage shapes, the tile guard, the dropped-out input, the reconstruction
+// epilogue, the four-lane sums and the ld() rule are frame_tile.hpp's).  Nothing is exchanged with
 // another workgroup: no flag, no spin, no atomic.
 //   LDS (floats; ld = frame_ld(L)): six row arrays of B ld each, every one used at least twice, and 32 floats of partial sums:
 //     H    h                                    (S1; read by S2, the dWm / dWs products and the tanh backward)
@@ -90,15 +91,10 @@ __global__ __launch_bounds__(VAF_THREADS) void vaeframe_step_kernel(VafStepArgs 
   float* C = smem + o.c;
   float* RED = smem + o.red;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int j = lane & 15, q = lane >> 4;
   const int nrt = (B + 15) >> 4, nlt = (L + 15) >> 4, ndt = (D + 15) >> 4;
   const int n = B * L;
 
-  auto xm_at = [&](int b, int d) -> float {      // the dropped-out input; b < B and d < D
-    const int64_t e = (int64_t)b * D + d;
-    const float v = p.x[e];
-    return (p.keep == nullptr) ? v : (p.keep[e] ? v * p.scale : 0.f);
-  };
+  auto xm_at = [&](int b, int d) { return dropped_at(p.x, p.keep, p.scale, D, b, d); };
 
   // ---- S0: the noise into LDS: given, or Philox block g4 <-> elements 4 g4 .. 4 g4 + 3 of the row-major (B,L) array
   const bool draw = p.eps_in == nullptr;
@@ -127,26 +123,13 @@ __global__ __launch_bounds__(VAF_THREADS) void vaeframe_step_kernel(VafStepArgs 
   }
 
   // ---- S1: h = tanh(xm We^T + be) -> H
-  for (int tt = w; tt < nrt * nlt; tt += VAF_NW) {
-    const int r0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-    Side s;
-    const f32x4 acc = tile_mma(
-        D, lane, [&](int i, int k) { return r0 + i < B ? xm_at(r0 + i, k) : 0.f; },
-        [&](int k, int jj) { return l0 + jj < L ? p.we[(int64_t)(l0 + jj) * D + k] : 0.f; }, s);
-    const int l = l0 + j;
-    if (l < L) {
-      const float bias = p.be[l];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = r0 + 4 * q + r;
-        if (b < B) {
-          const float h = tanhf(acc[r] + bias);
-          H[b * ldl + l] = h;
-          if (p.latent) p.latent[(int64_t)b * L + l] = h;
-        }
-      }
-    }
-  }
+  for (int tt = w; tt < nrt * nlt; tt += VAF_NW)
+    rows_tile(D, lane, (tt / nlt) * 16, B, (tt % nlt) * 16, L, xm_at, [&](int k, int l) { return p.we[(int64_t)l * D + k]; },
+              [&](int b, int l, float v) {
+                const float h = tanhf(v + p.be[l]);
+                H[b * ldl + l] = h;
+                if (p.latent) p.latent[(int64_t)b * L + l] = h;
+              });
   __syncthreads();
   if (draw && tid == 0) p.counter[0] = (int64_t)(off + 1);      // (every thread has read the counter: the barrier above)
 
@@ -156,27 +139,20 @@ __global__ __launch_bounds__(VAF_THREADS) void vaeframe_step_kernel(VafStepArgs 
     for (int tt = w; tt < nrt * nlt; tt += VAF_NW) {
       const int r0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
       Side s;
-      auto h_at = [&](int i, int k) { return r0 + i < B ? H[(r0 + i) * ldl + k] : 0.f; };
-      const f32x4 am = tile_mma(L, lane, h_at, [&](int k, int jj) { return l0 + jj < L ? p.wm[(l0 + jj) * L + k] : 0.f; }, s);
-      const f32x4 as = tile_mma(L, lane, h_at, [&](int k, int jj) { return l0 + jj < L ? p.ws[(l0 + jj) * L + k] : 0.f; }, s);
-      const int l = l0 + j;
-      if (l < L) {
-        const float bm = p.bm[l], bs = p.bs[l];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int b = r0 + 4 * q + r;
-          if (b < B) {
-            const float mu = am[r] + bm, lv = as[r] + bs;
-            const float zz = fmaf(expf(0.5f * lv), EPS[b * ldl + l], mu);
-            kl += ((expf(lv) - lv) - 1.0f) + mu * mu;
-            M[b * ldl + l] = mu;
-            V[b * ldl + l] = lv;
-            Z[b * ldl + l] = zz;
-            if (p.mean) p.mean[(int64_t)b * L + l] = mu;
-            if (p.logvar) p.logvar[(int64_t)b * L + l] = lv;
-          }
-        }
-      }
+      auto h_at = [&](int b, int k) { return H[b * ldl + k]; };
+      // (not rows_tile: two accumulators meet in one epilogue)
+      const f32x4 am = tile_guarded(L, lane, r0, B, l0, L, h_at, [&](int k, int l) { return p.wm[l * L + k]; }, s);
+      const f32x4 as = tile_guarded(L, lane, r0, B, l0, L, h_at, [&](int k, int l) { return p.ws[l * L + k]; }, s);
+      tile_each(lane, r0, B, l0, L, [&](int r, int b, int l) {
+        const float mu = am[r] + p.bm[l], lv = as[r] + p.bs[l];
+        const float zz = fmaf(expf(0.5f * lv), EPS[b * ldl + l], mu);
+        kl += ((expf(lv) - lv) - 1.0f) + mu * mu;
+        M[b * ldl + l] = mu;
+        V[b * ldl + l] = lv;
+        Z[b * ldl + l] = zz;
+        if (p.mean) p.mean[(int64_t)b * L + l] = mu;
+        if (p.logvar) p.logvar[(int64_t)b * L + l] = lv;
+      });
     }
     kl = wave_sum(kl);
     if (lane == 0) RED[w] = kl;
@@ -184,51 +160,19 @@ __global__ __launch_bounds__(VAF_THREADS) void vaeframe_step_kernel(VafStepArgs 
   __syncthreads();
 
   // ---- S3: c = z Wf^T + bf -> C
-  for (int tt = w; tt < nrt * nlt; tt += VAF_NW) {
-    const int r0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-    Side s;
-    const f32x4 acc = tile_mma(
-        L, lane, [&](int i, int k) { return r0 + i < B ? Z[(r0 + i) * ldl + k] : 0.f; },
-        [&](int k, int jj) { return l0 + jj < L ? p.wf[(l0 + jj) * L + k] : 0.f; }, s);
-    const int l = l0 + j;
-    if (l < L) {
-      const float bias = p.bf[l];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = r0 + 4 * q + r;
-        if (b < B) C[b * ldl + l] = acc[r] + bias;
-      }
-    }
-  }
+  for (int tt = w; tt < nrt * nlt; tt += VAF_NW)
+    rows_tile(L, lane, (tt / nlt) * 16, B, (tt % nlt) * 16, L, [&](int b, int k) { return Z[b * ldl + k]; },
+              [&](int k, int l) { return p.wf[l * L + k]; }, [&](int b, int l, float v) { C[b * ldl + l] = v + p.bf[l]; });
   __syncthreads();
 
   // ---- S4: out = c Wd^T + bd, g = 2 (out - t) / (B D), the mse partial sums
   {
     float rec = 0.f;
     const float gsc = 2.0f / ((float)B * (float)D);
-    for (int tt = w; tt < nrt * ndt; tt += VAF_NW) {
-      const int r0 = (tt / ndt) * 16, d0 = (tt % ndt) * 16;
-      Side s;
-      const f32x4 acc = tile_mma(
-          L, lane, [&](int i, int k) { return r0 + i < B ? C[(r0 + i) * ldl + k] : 0.f; },
-          [&](int k, int jj) { return d0 + jj < D ? p.wd[(int64_t)(d0 + jj) * L + k] : 0.f; }, s);
-      const int d = d0 + j;
-      if (d < D) {
-        const float bias = p.bd[d];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int b = r0 + 4 * q + r;
-          if (b < B) {
-            const int64_t e = (int64_t)b * D + d;
-            const float ov = acc[r] + bias;
-            if (p.out) p.out[e] = ov;
-            const float df = ov - p.t[e];
-            rec = fmaf(df, df, rec);
-            p.g[e] = gsc * df;
-          }
-        }
-      }
-    }
+    for (int tt = w; tt < nrt * ndt; tt += VAF_NW)
+      rows_tile(L, lane, (tt / ndt) * 16, B, (tt % ndt) * 16, D, [&](int b, int k) { return C[b * ldl + k]; },
+                [&](int k, int d) { return p.wd[(int64_t)d * L + k]; },
+                [&](int b, int d, float v) { recon_epilogue(v, p.bd[d], (int64_t)b * D + d, p.t, gsc, p.out, p.g, rec); });
     rec = wave_sum(rec);
     if (lane == 0) RED[VAF_NW + w] = rec;
   }
@@ -245,42 +189,17 @@ __global__ __launch_bounds__(VAF_THREADS) void vaeframe_step_kernel(VafStepArgs 
     p.scalars[2] = mse + p.kl_weight * klm;
   }
 
+  auto g_at = [&](int b, int d) { return p.g[(int64_t)b * D + d]; };
+
   // ---- S5a: dWd = g^T c, dbd = sum_b g
-  for (int tt = w; tt < ndt * nlt; tt += VAF_NW) {
-    const int d0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-    Side s;
-    const f32x4 acc = tile_mma(
-        B, lane, [&](int i, int k) { return d0 + i < D ? p.g[(int64_t)k * D + d0 + i] : 0.f; },
-        [&](int k, int jj) { return l0 + jj < L ? C[k * ldl + l0 + jj] : 0.f; }, s);
-    const float colsum = q_sum(s.sa);
-    if (l0 == 0 && q == 0 && d0 + j < D) p.g_bd[d0 + j] = colsum;
-    const int l = l0 + j;
-    if (l < L) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int d = d0 + 4 * q + r;
-        if (d < D) p.g_wd[(int64_t)d * L + l] = acc[r];
-      }
-    }
-  }
+  for (int tt = w; tt < ndt * nlt; tt += VAF_NW)
+    wgrad_tile(B, lane, (tt / nlt) * 16, D, (tt % nlt) * 16, L, g_at, [&](int b, int l) { return C[b * ldl + l]; }, p.g_wd, p.g_bd);
   __syncthreads();
 
   // ---- S5b: dc = g Wd in place of c
-  for (int tt = w; tt < nrt * nlt; tt += VAF_NW) {
-    const int r0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-    Side s;
-    const f32x4 acc = tile_mma(
-        D, lane, [&](int i, int k) { return r0 + i < B ? p.g[(int64_t)(r0 + i) * D + k] : 0.f; },
-        [&](int k, int jj) { return l0 + jj < L ? p.wd[(int64_t)k * L + l0 + jj] : 0.f; }, s);
-    const int l = l0 + j;
-    if (l < L) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = r0 + 4 * q + r;
-        if (b < B) C[b * ldl + l] = acc[r];
-      }
-    }
-  }
+  for (int tt = w; tt < nrt * nlt; tt += VAF_NW)
+    rows_tile(D, lane, (tt / nlt) * 16, B, (tt % nlt) * 16, L, g_at, [&](int k, int l) { return p.wd[(int64_t)k * L + l]; },
+              [&](int b, int l, float v) { C[b * ldl + l] = v; });
   __syncthreads();
 
   // ---- S6: dWf = dc^T z, dbf = sum_b dc | S7: dz = dc Wf (registers only) -> dmean in place of mean, dlogvar in place of logvar.
@@ -288,41 +207,19 @@ __global__ __launch_bounds__(VAF_THREADS) void vaeframe_step_kernel(VafStepArgs 
   {
     const int n6 = nlt * nlt, n7 = nrt * nlt;
     const float kap = p.kl_weight / ((float)B * (float)L);
+    auto c_at = [&](int b, int l) { return C[b * ldl + l]; };
     for (int tt = w; tt < n6 + n7; tt += VAF_NW) {
-      Side s;
       if (tt < n6) {
-        const int o0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-        const f32x4 acc = tile_mma(
-            B, lane, [&](int i, int k) { return o0 + i < L ? C[k * ldl + o0 + i] : 0.f; },
-            [&](int k, int jj) { return l0 + jj < L ? Z[k * ldl + l0 + jj] : 0.f; }, s);
-        const float colsum = q_sum(s.sa);
-        if (l0 == 0 && q == 0 && o0 + j < L) p.g_bf[o0 + j] = colsum;
-        const int l = l0 + j;
-        if (l < L) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int oo = o0 + 4 * q + r;
-            if (oo < L) p.g_wf[oo * L + l] = acc[r];
-          }
-        }
+        wgrad_tile(B, lane, (tt / nlt) * 16, L, (tt % nlt) * 16, L, c_at, [&](int b, int l) { return Z[b * ldl + l]; }, p.g_wf,
+                   p.g_bf);
       } else {
         const int t7 = tt - n6;
-        const int r0 = (t7 / nlt) * 16, l0 = (t7 % nlt) * 16;
-        const f32x4 acc = tile_mma(
-            L, lane, [&](int i, int k) { return r0 + i < B ? C[(r0 + i) * ldl + k] : 0.f; },
-            [&](int k, int jj) { return l0 + jj < L ? p.wf[k * L + l0 + jj] : 0.f; }, s);
-        const int l = l0 + j;
-        if (l < L) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int b = r0 + 4 * q + r;
-            if (b < B) {
-              const float mu = M[b * ldl + l], lv = V[b * ldl + l], ep = EPS[b * ldl + l];
-              M[b * ldl + l] = acc[r] + 2.0f * kap * mu;
-              V[b * ldl + l] = acc[r] * (0.5f * expf(0.5f * lv) * ep) + kap * (expf(lv) - 1.0f);
-            }
-          }
-        }
+        rows_tile(L, lane, (t7 / nlt) * 16, B, (t7 % nlt) * 16, L, c_at, [&](int k, int l) { return p.wf[k * L + l]; },
+                  [&](int b, int l, float v) {
+                    const float mu = M[b * ldl + l], lv = V[b * ldl + l], ep = EPS[b * ldl + l];
+                    M[b * ldl + l] = v + 2.0f * kap * mu;
+                    V[b * ldl + l] = v * (0.5f * expf(0.5f * lv) * ep) + kap * (expf(lv) - 1.0f);
+                  });
       }
     }
   }
@@ -333,68 +230,29 @@ __global__ __launch_bounds__(VAF_THREADS) void vaeframe_step_kernel(VafStepArgs 
   {
     const int n8 = nlt * nlt, n8b = nrt * nlt;
     for (int tt = w; tt < 2 * n8 + n8b; tt += VAF_NW) {
-      Side s;
       if (tt < 2 * n8) {
         const bool second = tt >= n8;
         const int t8 = second ? tt - n8 : tt;
         const float* S = second ? V : M;
-        float* gw = second ? p.g_ws : p.g_wm;
-        float* gb = second ? p.g_bs : p.g_bm;
-        const int o0 = (t8 / nlt) * 16, l0 = (t8 % nlt) * 16;
-        const f32x4 acc = tile_mma(
-            B, lane, [&](int i, int k) { return o0 + i < L ? S[k * ldl + o0 + i] : 0.f; },
-            [&](int k, int jj) { return l0 + jj < L ? H[k * ldl + l0 + jj] : 0.f; }, s);
-        const float colsum = q_sum(s.sa);
-        if (l0 == 0 && q == 0 && o0 + j < L) gb[o0 + j] = colsum;
-        const int l = l0 + j;
-        if (l < L) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int oo = o0 + 4 * q + r;
-            if (oo < L) gw[oo * L + l] = acc[r];
-          }
-        }
+        wgrad_tile(B, lane, (t8 / nlt) * 16, L, (t8 % nlt) * 16, L, [&](int b, int o2) { return S[b * ldl + o2]; },
+                   [&](int b, int l) { return H[b * ldl + l]; }, second ? p.g_ws : p.g_wm, second ? p.g_bs : p.g_bm);
       } else {
         const int t8 = tt - 2 * n8;
-        const int r0 = (t8 / nlt) * 16, l0 = (t8 % nlt) * 16;
-        const f32x4 acc = tile_mma(
-            2 * L, lane,
-            [&](int i, int k) { return r0 + i < B ? (k < L ? M[(r0 + i) * ldl + k] : V[(r0 + i) * ldl + k - L]) : 0.f; },
-            [&](int k, int jj) { return l0 + jj < L ? (k < L ? p.wm[k * L + l0 + jj] : p.ws[(k - L) * L + l0 + jj]) : 0.f; }, s);
-        const int l = l0 + j;
-        if (l < L) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int b = r0 + 4 * q + r;
-            if (b < B) {
-              const float h = H[b * ldl + l];
-              Z[b * ldl + l] = acc[r] * (1.0f - h * h);
-            }
-          }
-        }
+        rows_tile(2 * L, lane, (t8 / nlt) * 16, B, (t8 % nlt) * 16, L,
+                  [&](int b, int k) { return k < L ? M[b * ldl + k] : V[b * ldl + k - L]; },
+                  [&](int k, int l) { return k < L ? p.wm[k * L + l] : p.ws[(k - L) * L + l]; },
+                  [&](int b, int l, float v) {
+                    const float h = H[b * ldl + l];
+                    Z[b * ldl + l] = v * (1.0f - h * h);
+                  });
       }
     }
   }
   __syncthreads();
 
   // ---- S9: dWe = dpre^T xm, dbe = sum_b dpre
-  for (int tt = w; tt < nlt * ndt; tt += VAF_NW) {
-    const int l0 = (tt / ndt) * 16, d0 = (tt % ndt) * 16;
-    Side s;
-    const f32x4 acc = tile_mma(
-        B, lane, [&](int i, int k) { return l0 + i < L ? Z[k * ldl + l0 + i] : 0.f; },
-        [&](int k, int jj) { return d0 + jj < D ? xm_at(k, d0 + jj) : 0.f; }, s);
-    const float colsum = q_sum(s.sa);
-    if (d0 == 0 && q == 0 && l0 + j < L) p.g_be[l0 + j] = colsum;
-    const int d = d0 + j;
-    if (d < D) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int l = l0 + 4 * q + r;
-        if (l < L) p.g_we[(int64_t)l * D + d] = acc[r];
-      }
-    }
-  }
+  for (int tt = w; tt < nlt * ndt; tt += VAF_NW)
+    wgrad_tile(B, lane, (tt / ndt) * 16, L, (tt % ndt) * 16, D, [&](int b, int l) { return Z[b * ldl + l]; }, xm_at, p.g_we, p.g_be);
 }
 
 // dpre = dy (1 - y^2)

@@ -27,7 +27,9 @@
 //
 // g2v_vqframe_plan: host arithmetic only -- which route serves a shape and what `auto` takes.
 #include "common.hpp"
-#include "frame_tile.hpp"      // frame_ld (the ld(n) above), tile_mma, q_sum, quad_sum: shared with vae_frame.hip
+// shared with vae_frame.hip: frame_ld (the ld(n) above), tile_mma, q_sum, quad_sum, the tile guard (tile_guarded, tile_each), the two
+// stage shapes (rows_tile, wgrad_tile), dropped_at, recon_epilogue, argmin_merge16
+#include "frame_tile.hpp"
 
 namespace g2v {
 namespace {
@@ -102,11 +104,7 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
   const int nrt = (B + 15) >> 4, nlt = (L + 15) >> 4, ndt = (D + 15) >> 4, nkt = (K + 15) >> 4;
   const float invB = 1.0f / (float)B;
 
-  auto xm_at = [&](int b, int d) -> float {      // the dropped-out input; b < B and d < D
-    const int64_t e = (int64_t)b * D + d;
-    const float v = p.x[e];
-    return (p.keep == nullptr) ? v : (p.keep[e] ? v * p.scale : 0.f);
-  };
+  auto xm_at = [&](int b, int d) { return dropped_at(p.x, p.keep, p.scale, D, b, d); };
 
   // ---- S0: the weights and the old codebook into LDS
   for (int e = tid; e < L * D; e += VQF_THREADS) A[(e / D) * ldd + (e % D)] = p.we[e];
@@ -115,22 +113,9 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
   __syncthreads();
 
   // ---- S1: y = xm We^T + be -> XH
-  for (int tt = w; tt < nrt * nlt; tt += VQF_NW) {
-    const int r0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-    Side s;
-    const f32x4 acc = tile_mma(
-        D, lane, [&](int i, int k) { return r0 + i < B ? xm_at(r0 + i, k) : 0.f; },
-        [&](int k, int jj) { return l0 + jj < L ? A[(l0 + jj) * ldd + k] : 0.f; }, s);
-    const int l = l0 + j;
-    if (l < L) {
-      const float bias = p.be[l];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int b = r0 + 4 * q + r;
-        if (b < B) XH[b * ldl + l] = acc[r] + bias;
-      }
-    }
-  }
+  for (int tt = w; tt < nrt * nlt; tt += VQF_NW)
+    rows_tile(D, lane, (tt / nlt) * 16, B, (tt % nlt) * 16, L, xm_at, [&](int k, int l) { return A[l * ldd + k]; },
+              [&](int b, int l, float v) { XH[b * ldl + l] = v + p.be[l]; });
   __syncthreads();
 
   // ---- S2: batch statistics of column c (four threads per column, rows b = rr mod 4), the running statistics, xh and z
@@ -168,6 +153,7 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
   __syncthreads();
 
   // ---- S3: id[b] = argmin_k (|z_b|^2 + |e_k|^2) - 2 z_b . e_k, lowest k on ties; one wave per row tile, the code tiles in turn
+  //      (not rows_tile: the tile's own |z|^2 and |e|^2 enter, every lane of a column merges, and one result is kept across tiles)
   for (int rt = w; rt < nrt; rt += VQF_NW) {
     const int r0 = rt * 16;
     float bd_[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
@@ -175,9 +161,8 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
     for (int kt = 0; kt < nkt; ++kt) {
       const int c0 = kt * 16;
       Side s;
-      const f32x4 acc = tile_mma(
-          L, lane, [&](int i, int k) { return r0 + i < B ? A[(r0 + i) * ldl + k] : 0.f; },
-          [&](int k, int jj) { return c0 + jj < K ? EC[(c0 + jj) * ldl + k] : 0.f; }, s);
+      const f32x4 acc = tile_guarded(
+          L, lane, r0, B, c0, K, [&](int b, int k) { return A[b * ldl + k]; }, [&](int k, int c) { return EC[c * ldl + k]; }, s);
       const float zz = q_sum(s.saa);      // |z|^2 of row r0 + (lane & 15)
       const float ee = q_sum(s.sbb);      // |e|^2 of code c0 + (lane & 15)
 #pragma unroll
@@ -189,12 +174,7 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int m = 1; m < 16; m <<= 1) {
-        const float d2 = __shfl_xor(bd_[r], m);
-        const int k2 = __shfl_xor(bk_[r], m);
-        argmin_merge(bd_[r], bk_[r], d2, k2);
-      }
+      argmin_merge16(bd_[r], bk_[r]);
       const int b = r0 + 4 * q + r;
       if (j == 0 && b < B) {
         IDX[b] = (unsigned short)bk_[r];
@@ -254,45 +234,19 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
     const int n4b = nkt * nlt, n5 = nrt * ndt;
     const float gsc = 2.0f / ((float)B * (float)D);
     for (int tt = w; tt < n4b + n5; tt += VQF_NW) {
-      Side s;
       if (tt < n4b) {
-        const int c0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-        const f32x4 acc = tile_mma(
-            B, lane, [&](int i, int k) { return IDX[k] == c0 + i ? 1.0f : 0.f; },
-            [&](int k, int jj) { return l0 + jj < L ? A[k * ldl + l0 + jj] : 0.f; }, s);
-        const int l = l0 + j;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = c0 + 4 * q + r;
-          if (c < K && l < L) {
-            const int64_t e = (int64_t)c * L + l;
-            const float ew = p.ema_w[e] * p.decay + p.one_minus_decay * acc[r];
-            p.ema_w[e] = ew;
-            p.code[e] = ew / CS[c];
-          }
-        }
+        rows_tile(B, lane, (tt / nlt) * 16, K, (tt % nlt) * 16, L, [&](int c, int b) { return IDX[b] == c ? 1.0f : 0.f; },
+                  [&](int b, int l) { return A[b * ldl + l]; }, [&](int c, int l, float v) {
+                    const int64_t e = (int64_t)c * L + l;
+                    const float ew = p.ema_w[e] * p.decay + p.one_minus_decay * v;
+                    p.ema_w[e] = ew;
+                    p.code[e] = ew / CS[c];
+                  });
       } else {
         const int t5 = tt - n4b;
-        const int r0 = (t5 / ndt) * 16, d0 = (t5 % ndt) * 16;
-        const f32x4 acc = tile_mma(
-            L, lane, [&](int i, int k) { return r0 + i < B ? EC[IDX[r0 + i] * ldl + k] : 0.f; },
-            [&](int k, int jj) { return d0 + jj < D ? WD[(d0 + jj) * ldl + k] : 0.f; }, s);
-        const int d = d0 + j;
-        if (d < D) {
-          const float bias = p.bd[d];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int b = r0 + 4 * q + r;
-            if (b < B) {
-              const int64_t e = (int64_t)b * D + d;
-              const float ov = acc[r] + bias;
-              if (p.out) p.out[e] = ov;
-              const float df = ov - p.t[e];
-              rec = fmaf(df, df, rec);
-              p.g[e] = gsc * df;
-            }
-          }
-        }
+        rows_tile(L, lane, (t5 / ndt) * 16, B, (t5 % ndt) * 16, D, [&](int b, int k) { return EC[IDX[b] * ldl + k]; },
+                  [&](int k, int d) { return WD[d * ldl + k]; },
+                  [&](int b, int d, float v) { recon_epilogue(v, p.bd[d], (int64_t)b * D + d, p.t, gsc, p.out, p.g, rec); });
       }
     }
     rec = wave_sum(rec);
@@ -314,40 +268,18 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
   {
     const int n6a = nrt * nlt, n6b = ndt * nlt;
     const float cc = 2.0f * p.commitment / ((float)B * (float)L);
+    auto g_at = [&](int b, int d) { return p.g[(int64_t)b * D + d]; };
     for (int tt = w; tt < n6a + n6b; tt += VQF_NW) {
-      Side s;
       if (tt < n6a) {
-        const int r0 = (tt / nlt) * 16, l0 = (tt % nlt) * 16;
-        const f32x4 acc = tile_mma(
-            D, lane, [&](int i, int k) { return r0 + i < B ? p.g[(int64_t)(r0 + i) * D + k] : 0.f; },
-            [&](int k, int jj) { return l0 + jj < L ? WD[k * ldl + l0 + jj] : 0.f; }, s);
-        const int l = l0 + j;
-        if (l < L) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int b = r0 + 4 * q + r;
-            if (b < B) {
-              const float z = A[b * ldl + l];
-              A[b * ldl + l] = acc[r] + cc * (z - EC[IDX[b] * ldl + l]);
-            }
-          }
-        }
+        rows_tile(D, lane, (tt / nlt) * 16, B, (tt % nlt) * 16, L, g_at, [&](int k, int l) { return WD[k * ldl + l]; },
+                  [&](int b, int l, float v) {
+                    const float z = A[b * ldl + l];
+                    A[b * ldl + l] = v + cc * (z - EC[IDX[b] * ldl + l]);
+                  });
       } else {
         const int t6 = tt - n6a;
-        const int d0 = (t6 / nlt) * 16, l0 = (t6 % nlt) * 16;
-        const f32x4 acc = tile_mma(
-            B, lane, [&](int i, int k) { return d0 + i < D ? p.g[(int64_t)k * D + d0 + i] : 0.f; },
-            [&](int k, int jj) { return l0 + jj < L ? EC[IDX[k] * ldl + l0 + jj] : 0.f; }, s);
-        const float colsum = q_sum(s.sa);
-        if (l0 == 0 && q == 0 && d0 + j < D) p.g_bd[d0 + j] = colsum;
-        const int l = l0 + j;
-        if (l < L) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int d = d0 + 4 * q + r;
-            if (d < D) p.g_wd[(int64_t)d * L + l] = acc[r];
-          }
-        }
+        wgrad_tile(B, lane, (t6 / nlt) * 16, D, (t6 % nlt) * 16, L, g_at, [&](int b, int l) { return EC[IDX[b] * ldl + l]; }, p.g_wd,
+                   p.g_bd);
       }
     }
   }
@@ -378,23 +310,8 @@ __global__ __launch_bounds__(VQF_THREADS) void vqframe_step_kernel(VqfStepArgs p
   __syncthreads();
 
   // ---- S8: dWe = dy^T xm, dbe = sum_b dy
-  for (int tt = w; tt < nlt * ndt; tt += VQF_NW) {
-    const int l0 = (tt / ndt) * 16, d0 = (tt % ndt) * 16;
-    Side s;
-    const f32x4 acc = tile_mma(
-        B, lane, [&](int i, int k) { return l0 + i < L ? A[k * ldl + l0 + i] : 0.f; },
-        [&](int k, int jj) { return d0 + jj < D ? xm_at(k, d0 + jj) : 0.f; }, s);
-    const float colsum = q_sum(s.sa);
-    if (d0 == 0 && q == 0 && l0 + j < L) p.g_be[l0 + j] = colsum;
-    const int d = d0 + j;
-    if (d < D) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int l = l0 + 4 * q + r;
-        if (l < L) p.g_we[(int64_t)l * D + d] = acc[r];
-      }
-    }
-  }
+  for (int tt = w; tt < nlt * ndt; tt += VQF_NW)
+    wgrad_tile(B, lane, (tt / ndt) * 16, L, (tt % ndt) * 16, D, [&](int b, int l) { return A[b * ldl + l]; }, xm_at, p.g_we, p.g_be);
 }
 
 // |e_k|^2 of the codebook, one thread per code, l ascending
@@ -432,14 +349,16 @@ __global__ __launch_bounds__(64 * VQF_INFER_NW) void vqframe_infer_kernel(VqfInf
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int j = lane & 15, q = lane >> 4;
   const int64_t r0 = (int64_t)blockIdx.x * VQF_INFER_ROWS;
+  const int rows = p.N - r0 < VQF_INFER_ROWS ? (int)(p.N - r0) : VQF_INFER_ROWS;      // of this tile; i below is a row of the tile
   const int nlt = (L + 15) >> 4, ndt = (D + 15) >> 4, nkt = (K + 15) >> 4;
   Side s;
 
   for (int lt = w; lt < nlt; lt += VQF_INFER_NW) {
     const int l0 = lt * 16;
-    const f32x4 acc = tile_mma(
-        D, lane, [&](int i, int k) { return r0 + i < p.N ? p.x[(r0 + i) * D + k] : 0.f; },
-        [&](int k, int jj) { return l0 + jj < L ? p.we[(int64_t)(l0 + jj) * D + k] : 0.f; }, s);
+    const f32x4 acc = tile_guarded(
+        D, lane, 0, rows, l0, L, [&](int i, int k) { return p.x[(r0 + i) * D + k]; },
+        [&](int k, int l) { return p.we[(int64_t)l * D + k]; }, s);
+    // (not rows_tile: Z takes all sixteen rows, the ones past N too, and five column constants are formed once for the four rows)
     const int l = l0 + j;
     if (l < L) {
       const float bias = p.be[l], mu = p.rmean[l], istd = 1.0f / sqrtf(p.rvar[l] + p.bn_eps), ga = p.gamma[l], be = p.beta[l];
@@ -448,7 +367,7 @@ __global__ __launch_bounds__(64 * VQF_INFER_NW) void vqframe_infer_kernel(VqfInf
         const int i = 4 * q + r;
         const float z = ((acc[r] + bias) - mu) * istd * ga + be;
         Z[i * ldl + l] = z;
-        if (p.latent && r0 + i < p.N) p.latent[(r0 + i) * L + l] = z;
+        if (p.latent && i < rows) p.latent[(r0 + i) * L + l] = z;
       }
     }
   }
@@ -464,23 +383,15 @@ __global__ __launch_bounds__(64 * VQF_INFER_NW) void vqframe_infer_kernel(VqfInf
     int bk_[4] = {0, 0, 0, 0};
     for (int kt = w; kt < nkt; kt += VQF_INFER_NW) {
       const int c0 = kt * 16;
-      const f32x4 acc = tile_mma(
-          L, lane, [&](int i, int k) { return Z[i * ldl + k]; },
-          [&](int k, int jj) { return c0 + jj < K ? p.code[(int64_t)(c0 + jj) * L + k] : 0.f; }, s);
-      if (c0 + j < K) {
-        const float ee = p.esq[c0 + j];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) argmin_merge(bd_[r], bk_[r], (ZZ[4 * q + r] + ee) - 2.0f * acc[r], c0 + j);
-      }
+      // (not rows_tile: the merge needs the accumulator's index r; all sixteen rows of Z are defined)
+      const f32x4 acc = tile_guarded(
+          L, lane, 0, 16, c0, K, [&](int i, int k) { return Z[i * ldl + k]; }, [&](int k, int c) { return p.code[(int64_t)c * L + k]; },
+          s);
+      tile_each(lane, 0, 16, c0, K, [&](int r, int i, int c) { argmin_merge(bd_[r], bk_[r], (ZZ[i] + p.esq[c]) - 2.0f * acc[r], c); });
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int m = 1; m < 16; m <<= 1) {
-        const float d2 = __shfl_xor(bd_[r], m);
-        const int k2 = __shfl_xor(bk_[r], m);
-        argmin_merge(bd_[r], bk_[r], d2, k2);
-      }
+      argmin_merge16(bd_[r], bk_[r]);
       if (j == 0) {
         BD[w * 16 + 4 * q + r] = bd_[r];
         BK[w * 16 + 4 * q + r] = bk_[r];
@@ -493,25 +404,14 @@ __global__ __launch_bounds__(64 * VQF_INFER_NW) void vqframe_infer_kernel(VqfInf
     int k = BK[tid];
     for (int ww = 1; ww < VQF_INFER_NW; ++ww) argmin_merge(d, k, BD[ww * 16 + tid], BK[ww * 16 + tid]);
     ID[tid] = k;
-    if (r0 + tid < p.N) p.ids[r0 + tid] = k;
+    if (tid < rows) p.ids[r0 + tid] = k;
   }
   if (p.out == nullptr) return;
   __syncthreads();
-  for (int dt = w; dt < ndt; dt += VQF_INFER_NW) {
-    const int d0 = dt * 16;
-    const f32x4 acc = tile_mma(
-        L, lane, [&](int i, int k) { return p.code[(int64_t)ID[i] * L + k]; },
-        [&](int k, int jj) { return d0 + jj < D ? p.wd[(int64_t)(d0 + jj) * L + k] : 0.f; }, s);
-    const int d = d0 + j;
-    if (d < D) {
-      const float bias = p.bd[d];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = r0 + 4 * q + r;
-        if (row < p.N) p.out[row * D + d] = acc[r] + bias;
-      }
-    }
-  }
+  for (int dt = w; dt < ndt; dt += VQF_INFER_NW)
+    rows_tile(L, lane, 0, rows, dt * 16, D, [&](int i, int k) { return p.code[(int64_t)ID[i] * L + k]; },
+              [&](int k, int d) { return p.wd[(int64_t)d * L + k]; },
+              [&](int i, int d, float v) { p.out[(r0 + i) * D + d] = v + p.bd[d]; });
 }
 
 const char* step_refusal(int B, int D, int L, int K) {

@@ -18,14 +18,74 @@ from .. import ops
 from .Autoencoder_VQVAE_model import _VQFn
 
 
-class DAE_Network(nn.Module):
+class _FramePlumbing:
+    """What the three frame models share besides their layers: the keep mask (given or drawn), the Philox offset counter, the input
+    checks and the route resolver.  A plain mixin in front of nn.Module: it adds no child, buffer or parameter, so no state_dict
+    moves.  A class names itself in `_name` (error messages), says what `_batch` answers a wrong batch with in `_batch_msg`
+    ({} = the shape), and, if it has routes, provides `_plan(rows, training)` and a dict `_routes`."""
+
+    _name = ""
+    _batch_msg = ""
+    _refuses_when_staged = False      # VAE_Network: a shape the plan refuses raises on every route, "staged" included
+    _explicit_keep = None
+    _rng_counter = None
+    rng_seed = 0
+
+    def set_dropout_mask(self, keep):
+        """Explicit uint8 keep mask for the next training forwards (parity tests)."""
+        self._explicit_keep = keep
+
+    def _counter(self, device):
+        if self._rng_counter is None or self._rng_counter.device != device:
+            self._rng_counter = torch.zeros(1, dtype=torch.int64, device=device)
+        return self._rng_counter
+
+    def _keep(self, inp: torch.Tensor):
+        if self._explicit_keep is not None:
+            return self._explicit_keep
+        return ops.keep_mask(torch.empty(inp.shape, dtype=torch.uint8, device=inp.device), 1.0 - self.dropout.p, self.rng_seed,
+                             self._counter(inp.device))
+
+    def _on_device(self, x: torch.Tensor) -> torch.Tensor:
+        if not x.is_cuda:
+            raise RuntimeError(f"{self._name} runs on the MI355X kernels only (no CPU fallback)")
+        return x
+
+    def _batch(self, x: torch.Tensor) -> torch.Tensor:
+        """(B,D,1) or (B,D) -> contiguous (B,D) with B >= 2"""
+        inp = torch.squeeze(x)
+        if inp.dim() != 2 or inp.shape[0] < 2:
+            raise ValueError(self._batch_msg.format(tuple(x.shape)))
+        return self._on_device(inp).contiguous()
+
+    def _rows(self, x: torch.Tensor, width: int) -> torch.Tensor:
+        return self._on_device(x).reshape(-1, width).contiguous()
+
+    def resolve(self, rows: int, training: bool) -> str:
+        """"fused" or "staged" for a call of `rows` frames; `auto` takes the plan's answer.  An explicit "fused" that the kernel does
+        not admit raises with the plan's reason."""
+        if self.route not in ("auto", "fused", "staged"):
+            raise ValueError(f"{self._name}.route must be 'auto', 'fused' or 'staged', got {self.route!r}")
+        if self.route == "staged" and not self._refuses_when_staged:
+            return "staged"
+        key = (rows, training)
+        if key not in self._routes:
+            self._routes[key] = self._plan(rows, training)
+        auto, fused_ok, reason = self._routes[key]
+        if auto == "" and (self._refuses_when_staged or self.route == "auto"):
+            raise ValueError(f"{self._name}: {reason}")
+        if self.route == "fused" and not fused_ok:
+            raise ValueError(f"{self._name}.route = 'fused': {reason}")
+        return auto if self.route == "auto" else self.route
+
+
+class DAE_Network(_FramePlumbing, nn.Module):
+    _name = "DAE_Network"
+
     def __init__(self, motion_dim: int, latent_dim: int):
         super().__init__()
         self.dropout = nn.Dropout(0.2)             # container for p only; masks come from the Philox kernel
         self._relu = True
-        self._explicit_keep = None
-        self._rng_counter = None
-        self.rng_seed = 0
         if latent_dim == -1:
             self.encoder = None
             self.decoder = None
@@ -39,10 +99,6 @@ class DAE_Network(nn.Module):
         self.encoder = nn.Sequential(nn.Linear(motion_dim, latent_dim), nn.ReLU())
         self.decoder = nn.Sequential(nn.Linear(latent_dim, motion_dim))
 
-    def set_dropout_mask(self, keep):
-        """Explicit uint8 keep mask for the next training forward (parity tests)."""
-        self._explicit_keep = keep
-
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         """`rep_model.encoder(x)` as the datasets call it (lmdb_data_loader.py:649-653): Linear(+ReLU), no dropout."""
         e = self.encoder[0]
@@ -55,20 +111,10 @@ class DAE_Network(nn.Module):
     def forward(self, x: torch.Tensor, get_latent: bool = False):
         if self.encoder is None:
             return (x, x) if get_latent else x
-        inp = torch.squeeze(x)
-        if not inp.is_cuda:
-            raise RuntimeError("DAE_Network runs on the MI355X kernels only (no CPU fallback)")
+        inp = self._on_device(torch.squeeze(x))
         keep, scale = None, 1.0
         if self.training:
-            p = self.dropout.p
-            if self._explicit_keep is not None:
-                keep = self._explicit_keep
-            else:
-                if self._rng_counter is None or self._rng_counter.device != inp.device:
-                    self._rng_counter = torch.zeros(1, dtype=torch.int64, device=inp.device)
-                keep = ops.keep_mask(torch.empty(inp.shape, dtype=torch.uint8, device=inp.device), 1.0 - p, self.rng_seed,
-                                     self._rng_counter)
-            scale = 1.0 / (1.0 - p)
+            keep, scale = self._keep(inp), 1.0 / (1.0 - self.dropout.p)
         e = self.encoder[0]
         lat = Fn.linear(inp, e.weight, e.bias, keep=keep, scale=scale, act=1 if self._relu else 0)
         out = self.decode(lat)
@@ -104,7 +150,7 @@ class VQ_Payam_EMA(nn.Module):
         return _VQFn.apply(inputs, self, False)
 
 
-class VQ_Frame(nn.Module):
+class VQ_Frame(_FramePlumbing, nn.Module):
     """forward(x) -> (out (B,D,1), loss_vq, perplexity); forward(x, Inference=True) -> (out, latent, encodings (N,K) one-hot).
 
     Two routes behind one forward, chosen by the attribute `route` = "auto" | "fused" | "staged":
@@ -116,6 +162,9 @@ class VQ_Frame(nn.Module):
       auto    asks g2v_vqframe_plan (ops.vqframe_plan) -- here, in `resolve`, and nowhere else."""
 
     route = "auto"
+    _name = "VQ_Frame"
+    _batch_msg = ("VQ_Frame in training needs a batch of at least 2 frames (BatchNorm1d on batch statistics; squeeze drops the row "
+                  "axis of a single frame), got {}")
 
     def __init__(self, motion_dim: int, latent_dim: int, vae: bool, vq_components: int):
         super().__init__()
@@ -134,17 +183,10 @@ class VQ_Frame(nn.Module):
         nn.init.xavier_normal_(self.decoder[0].weight)
         self.dropout = nn.Dropout()                # p = 0.5; container for p only, masks come from the Philox kernel
         self.vae = vae
-        self._explicit_keep = None
-        self._rng_counter = None
-        self.rng_seed = 0
         self._pending_batches = 0                  # training forwards not yet added to bachnorm.num_batches_tracked
         self._routes = {}
 
     # ---- bookkeeping -------------------------------------------------------------------------------------------------------
-    def set_dropout_mask(self, keep):
-        """Explicit uint8 keep mask for the next training forwards (parity tests)."""
-        self._explicit_keep = keep
-
     def state_dict(self, *args, **kwargs):
         # num_batches_tracked counts training forwards; they are counted on the host and added here, not by a launch per iteration
         if self._pending_batches:
@@ -160,47 +202,8 @@ class VQ_Frame(nn.Module):
         e = self.encoder[0]
         return e.in_features, e.out_features, self.vq_components
 
-    def resolve(self, rows: int, training: bool) -> str:
-        """"fused" or "staged" for a call of `rows` frames; `auto` takes the plan's answer.  An explicit "fused" that the kernel does
-        not admit raises with the plan's reason."""
-        if self.route not in ("auto", "fused", "staged"):
-            raise ValueError(f"VQ_Frame.route must be 'auto', 'fused' or 'staged', got {self.route!r}")
-        if self.route == "staged":
-            return "staged"
-        key = (rows, training)
-        if key not in self._routes:
-            self._routes[key] = ops.vqframe_plan(rows, *self._dims(), training)
-        auto, fused_ok, reason = self._routes[key]
-        if self.route == "fused":
-            if not fused_ok:
-                raise ValueError(f"VQ_Frame.route = 'fused': {reason}")
-            return "fused"
-        if auto == "":
-            raise ValueError(f"VQ_Frame: {reason}")
-        return auto
-
-    def _rows(self, x: torch.Tensor) -> torch.Tensor:
-        D = self.encoder[0].in_features
-        if not x.is_cuda:
-            raise RuntimeError("VQ_Frame runs on the MI355X kernels only (no CPU fallback)")
-        return x.reshape(-1, D).contiguous()
-
-    def _keep(self, inp: torch.Tensor):
-        if self._explicit_keep is not None:
-            return self._explicit_keep
-        if self._rng_counter is None or self._rng_counter.device != inp.device:
-            self._rng_counter = torch.zeros(1, dtype=torch.int64, device=inp.device)
-        return ops.keep_mask(torch.empty(inp.shape, dtype=torch.uint8, device=inp.device), 1.0 - self.dropout.p, self.rng_seed,
-                             self._rng_counter)
-
-    def _train_input(self, x: torch.Tensor) -> torch.Tensor:
-        inp = torch.squeeze(x)
-        if inp.dim() != 2 or inp.shape[0] < 2:
-            raise ValueError("VQ_Frame in training needs a batch of at least 2 frames (BatchNorm1d on batch statistics; squeeze "
-                             f"drops the row axis of a single frame), got {tuple(x.shape)}")
-        if not inp.is_cuda:
-            raise RuntimeError("VQ_Frame runs on the MI355X kernels only (no CPU fallback)")
-        return inp.contiguous()
+    def _plan(self, rows: int, training: bool):
+        return ops.vqframe_plan(rows, *self._dims(), training)
 
     def _infer_args(self):
         e, bn, q = self.encoder[0], self.bachnorm, self.vq_layer
@@ -214,14 +217,14 @@ class VQ_Frame(nn.Module):
 
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         """The eval-mode z = bachnorm(encoder(x)) of any number of frames, (N,D) or (N,D,1) -> (N,L): what the datasets would call."""
-        rows = self._rows(x)
+        rows = self._rows(x, self.encoder[0].in_features)
         if self.resolve(rows.shape[0], False) == "fused":
             return ops.vqframe_infer(rows, *self._infer_args(), want_latent=True)[1]
         return self._encode_staged(rows)
 
     def codes(self, x: torch.Tensor) -> torch.Tensor:
         """int64 code ids (N,) of any number of frames in eval mode; the (N,K) one-hot is never formed."""
-        rows = self._rows(x)
+        rows = self._rows(x, self.encoder[0].in_features)
         if self.resolve(rows.shape[0], False) == "fused":
             return ops.vqframe_infer(rows, *self._infer_args())[0]
         z, W = self._encode_staged(rows), self.vq_layer._embedding.weight.data
@@ -238,7 +241,7 @@ class VQ_Frame(nn.Module):
         -> (scalars (3,) = reconstruction mse, loss_vq, perplexity; ids (B,); latent or None; out (B,D) or None)"""
         if not self.training or self.skip_vq:
             raise RuntimeError("VQ_Frame.fused_step is the training step with the quantiser on")
-        inp = self._train_input(x)
+        inp = self._batch(x)
         tgt = torch.squeeze(target).contiguous()
         e, bn, d, q = self.encoder[0], self.bachnorm, self.decoder[0], self.vq_layer
         momentum = 0.1 if bn.momentum is None else bn.momentum
@@ -253,16 +256,14 @@ class VQ_Frame(nn.Module):
     # ---- forward -------------------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, Inference: bool = False):
         if self.training:
-            inp = self._train_input(x)
+            inp = self._batch(x)
             if self.route == "fused" and not self.skip_vq:
                 raise RuntimeError("VQ_Frame.route = 'fused': the fused training step computes forward and backward in one launch and "
                                    "needs the target; call fused_step(x, target, grads) or train_iter_DAE, or set route = 'staged'")
             keep, scale = self._keep(inp), 1.0 / (1.0 - self.dropout.p)
             self._pending_batches += 1
         else:
-            inp = torch.squeeze(x)
-            if not inp.is_cuda:
-                raise RuntimeError("VQ_Frame runs on the MI355X kernels only (no CPU fallback)")
+            inp = self._on_device(torch.squeeze(x))
             if inp.dim() != 2:
                 raise ValueError(f"VQ_Frame.forward expects (B, motion_dim, 1) frames with B >= 2, got {tuple(x.shape)}; "
                                  "codes(x) / encode(x) take any number of frames")
@@ -290,7 +291,7 @@ class VQ_Frame(nn.Module):
         return out, loss_vq, perplexity_vq
 
 
-class VAE_Network(nn.Module):
+class VAE_Network(_FramePlumbing, nn.Module):
     """The frame-level VARIATIONAL autoencoder (reference DAE_model.py:600-725; autoencoder_vq "False", autoencoder_vae "True"):
     Dropout(0.5) -> tanh(Linear(D, L)) = h -> mean = VAE_fc_mean(h), logvar = VAE_fc_std(h) -> z = mean + exp(logvar / 2) eps ->
     VAE_fc_decoder -> Linear(L, D).  forward(x) -> (out (B,D,1), logvar, mean) -- logvar first, as the reference returns them;
@@ -304,6 +305,10 @@ class VAE_Network(nn.Module):
       auto    asks g2v_vaeframe_plan (ops.vaeframe_plan) -- here, in `resolve`, and nowhere else."""
 
     route = "auto"
+    _name = "VAE_Network"
+    _batch_msg = ("VAE_Network needs a batch of at least 2 frames (the reference's squeeze drops the row axis of a single frame and "
+                  "its unsqueeze(2) then fails), got {}; encode(x) takes any number of frames")
+    _refuses_when_staged = True
     KL_WEIGHT = 12.5            # train_seq2seq.py:224-230: 5 x (-2.5 mean(mean(1 + logvar - exp(logvar) - mean^2, 1)))
 
     def __init__(self, motion_dim: int, latent_dim: int):
@@ -315,18 +320,11 @@ class VAE_Network(nn.Module):
         self.VAE_fc_mean = nn.Linear(latent_dim, latent_dim)
         self.VAE_fc_std = nn.Linear(latent_dim, latent_dim)
         self.VAE_fc_decoder = nn.Linear(latent_dim, latent_dim)
-        self._explicit_keep = None
         self._explicit_eps = None
-        self._rng_counter = None
-        self.rng_seed = 0
         self._routes = {}
         self.last_kl = None                        # the KL mean of the last staged forward (part of its autograd graph)
 
     # ---- bookkeeping -------------------------------------------------------------------------------------------------------
-    def set_dropout_mask(self, keep):
-        """Explicit uint8 keep mask for the next training forwards (parity tests)."""
-        self._explicit_keep = keep
-
     def set_latent_noise(self, eps):
         """Explicit eps (B, L) for the next forwards, training or eval (parity tests); None draws again."""
         self._explicit_eps = eps
@@ -335,49 +333,8 @@ class VAE_Network(nn.Module):
         e = self.encoder[0]
         return e.in_features, e.out_features
 
-    def resolve(self, rows: int, training: bool) -> str:
-        """"fused" or "staged" for a call of `rows` frames; `auto` takes the plan's answer.  An explicit "fused" that the kernel does
-        not admit raises with the plan's reason."""
-        if self.route not in ("auto", "fused", "staged"):
-            raise ValueError(f"VAE_Network.route must be 'auto', 'fused' or 'staged', got {self.route!r}")
-        key = (rows, training)
-        if key not in self._routes:
-            self._routes[key] = ops.vaeframe_plan(rows, *self._dims(), training)
-        auto, fused_ok, reason = self._routes[key]
-        if auto == "":
-            raise ValueError(f"VAE_Network: {reason}")
-        if self.route == "staged":
-            return "staged"
-        if self.route == "fused":
-            if not fused_ok:
-                raise ValueError(f"VAE_Network.route = 'fused': {reason}")
-            return "fused"
-        return auto
-
-    def _counter(self, device):
-        if self._rng_counter is None or self._rng_counter.device != device:
-            self._rng_counter = torch.zeros(1, dtype=torch.int64, device=device)
-        return self._rng_counter
-
-    def _keep(self, inp: torch.Tensor):
-        if self._explicit_keep is not None:
-            return self._explicit_keep
-        return ops.keep_mask(torch.empty(inp.shape, dtype=torch.uint8, device=inp.device), 1.0 - self.dropout.p, self.rng_seed,
-                             self._counter(inp.device))
-
-    def _input(self, x: torch.Tensor) -> torch.Tensor:
-        inp = torch.squeeze(x)
-        if inp.dim() != 2 or inp.shape[0] < 2:
-            raise ValueError("VAE_Network needs a batch of at least 2 frames (the reference's squeeze drops the row axis of a single "
-                             f"frame and its unsqueeze(2) then fails), got {tuple(x.shape)}; encode(x) takes any number of frames")
-        if not inp.is_cuda:
-            raise RuntimeError("VAE_Network runs on the MI355X kernels only (no CPU fallback)")
-        return inp.contiguous()
-
-    def _rows(self, x: torch.Tensor, width: int) -> torch.Tensor:
-        if not x.is_cuda:
-            raise RuntimeError("VAE_Network runs on the MI355X kernels only (no CPU fallback)")
-        return x.reshape(-1, width).contiguous()
+    def _plan(self, rows: int, training: bool):
+        return ops.vaeframe_plan(rows, *self._dims(), training)
 
     def trainable(self):
         """the ten tensors in state_dict order: what FlatClipAdam(net.parameters()) holds and g2v_vaeframe_step writes gradients for"""
@@ -409,7 +366,7 @@ class VAE_Network(nn.Module):
     def reconstruct(self, x: torch.Tensor, sample: bool = True) -> torch.Tensor:
         """the eval-mode forward (no dropout) of (B,D,1) frames -> (B,D,1); sample=False: z = mean, no noise"""
         with torch.no_grad():
-            return self._staged(self._input(x), None, 1.0, sample)[0]
+            return self._staged(self._batch(x), None, 1.0, sample)[0]
 
     # ---- the fused training step ---------------------------------------------------------------------------------------------
     def fused_step(self, x: torch.Tensor, target: torch.Tensor, grads, want_latent: bool = False, want_stats: bool = False,
@@ -419,7 +376,7 @@ class VAE_Network(nn.Module):
         logvar, out where asked for."""
         if not self.training:
             raise RuntimeError("VAE_Network.fused_step is the training step")
-        inp = self._input(x)
+        inp = self._batch(x)
         tgt = torch.squeeze(target).contiguous()
         keep = self._keep(inp)
         return ops.vaeframe_step(inp, tgt, keep, 1.0 / (1.0 - self.dropout.p), self._kernel_order([p.data for p in self.trainable()]),
@@ -439,7 +396,7 @@ class VAE_Network(nn.Module):
         return out, logvar, mean, h, kl
 
     def forward(self, x: torch.Tensor, get_latent: bool = False):
-        inp = self._input(x)
+        inp = self._batch(x)
         keep, scale = None, 1.0
         if self.training:
             if self.route == "fused":

@@ -359,34 +359,42 @@ def train_iter_DAE(args, epoch: int, noisy_poses: torch.Tensor, target_poses: to
     return {"loss": loss.item()}
 
 
+def _frame_fused_step(noisy_poses, target_poses, net, optim, allowed=True):
+    """The fused route of a frame model's iteration (net.resolve): the step writes its gradients straight into the optimiser's flat
+    gradient, then clip + Adam -> net.fused_step's result.  None where the iteration takes the staged route instead: `allowed` is
+    False, resolve says so, or the optimiser does not hold exactly the model's parameters (an error on an explicit route "fused").
+    The gradients are zeroed either way."""
+    if not net.training:
+        raise RuntimeError("train_iter_DAE needs the model in training mode")
+    fp, params = optim.fp, net.trainable()
+    fused = allowed and net.resolve(noisy_poses.shape[0], True) == "fused"
+    if fused and not (len(fp.params) == len(params) and all(a is b for a, b in zip(fp.params, params))):
+        if net.route == "fused":
+            raise ValueError(f"{net._name}.route = 'fused': the optimiser must hold exactly the model's parameters, "
+                             "FlatClipAdam(net.parameters(), ...)")
+        fused = False
+    optim.zero_grad()
+    if not fused:
+        return None
+    grads = [fp.gflat[o:o + p.numel()] for p, o in zip(fp.params, fp.offsets)]
+    res = net.fused_step(noisy_poses, target_poses, grads)
+    for p, g in zip(params, grads):
+        p.grad = g.view(p.shape)
+    fp.skipped = []
+    fp.step(optim.lr, optim.betas, optim.eps, optim.max_norm)
+    return res
+
+
 def _train_iter_vq_frame(noisy_poses, target_poses, net, optim):
-    """The VQ_Frame iteration.  On the fused route (VQ_Frame.resolve) it is three launches and one read-back: the keep mask, the
-    step -- which writes the six gradients straight into the optimiser's flat gradient --, clip + Adam, and the loss's .item().
-    The quantiser's tensors carry no gradient on either route and are not in the optimiser."""
+    """The VQ_Frame iteration.  On the fused route it is three launches and one read-back: the keep mask, the step (six gradients),
+    clip + Adam, and the loss's .item().  The quantiser's tensors carry no gradient on either route and are not in the optimiser."""
     from ..functional import mse_loss
     from ..model.DAE_model import VQ_Frame
     if not isinstance(net, VQ_Frame):
         raise TypeError("autoencoder_vq 'True' trains a gesture2vec_amd.model.DAE_model.VQ_Frame")
-    fp = optim.fp
-    rows = noisy_poses.shape[0]
-    if not net.training:
-        raise RuntimeError("train_iter_DAE needs the model in training mode")
-    params = net.trainable()
-    fused = (not net.skip_vq and net.resolve(rows, True) == "fused")
-    if fused and not (len(fp.params) == len(params) and all(a is b for a, b in zip(fp.params, params))):
-        if net.route == "fused":
-            raise ValueError("VQ_Frame.route = 'fused': the optimiser must hold exactly the model's parameters, "
-                             "FlatClipAdam(net.parameters(), ...)")
-        fused = False
-    optim.zero_grad()
-    if fused:
-        grads = [fp.gflat[o:o + p.numel()] for p, o in zip(fp.params, fp.offsets)]
-        scalars = net.fused_step(noisy_poses, target_poses, grads)[0]
-        for p, g in zip(params, grads):
-            p.grad = g.view(p.shape)
-        fp.skipped = []
-        fp.step(optim.lr, optim.betas, optim.eps, optim.max_norm)
-        return {"loss": scalars[0].item()}, scalars[2]
+    res = _frame_fused_step(noisy_poses, target_poses, net, optim, allowed=not net.skip_vq)
+    if res is not None:
+        return {"loss": res[0][0].item()}, res[0][2]
     outputs, vq_loss, perplexity_vq = net(noisy_poses)
     rec_loss = mse_loss(outputs, target_poses)
     (rec_loss + vq_loss).backward()
@@ -396,32 +404,16 @@ def _train_iter_vq_frame(noisy_poses, target_poses, net, optim):
 
 def _train_iter_vae_frame(noisy_poses, target_poses, net, optim):
     """The VAE_Network iteration (reference :202-241 with autoencoder_vq "False", autoencoder_vae "True"): loss = mse + 5 x (-2.5
-    mean(mean(1 + logvar - exp(logvar) - mean^2, 1))) = mse + 12.5 kl.  On the fused route (VAE_Network.resolve) it is three launches
-    and one read-back: the keep mask, the step -- which draws its noise and writes the ten gradients straight into the optimiser's
-    flat gradient --, clip + Adam, and the loss's .item().  Otherwise the staged route under autograd."""
+    mean(mean(1 + logvar - exp(logvar) - mean^2, 1))) = mse + 12.5 kl.  On the fused route it is three launches and one read-back:
+    the keep mask, the step -- which draws its noise too (ten gradients) --, clip + Adam, and the loss's .item().  Otherwise the
+    staged route under autograd."""
     from ..functional import mse_loss
     from ..model.DAE_model import VAE_Network
     if not isinstance(net, VAE_Network):
         raise TypeError("autoencoder_vae 'True' (with autoencoder_vq 'False') trains a gesture2vec_amd.model.DAE_model.VAE_Network")
-    if not net.training:
-        raise RuntimeError("train_iter_DAE needs the model in training mode")
-    fp = optim.fp
-    params = net.trainable()
-    fused = net.resolve(noisy_poses.shape[0], True) == "fused"
-    if fused and not (len(fp.params) == len(params) and all(a is b for a, b in zip(fp.params, params))):
-        if net.route == "fused":
-            raise ValueError("VAE_Network.route = 'fused': the optimiser must hold exactly the model's parameters, "
-                             "FlatClipAdam(net.parameters(), ...)")
-        fused = False
-    optim.zero_grad()
-    if fused:
-        grads = [fp.gflat[o:o + p.numel()] for p, o in zip(fp.params, fp.offsets)]
-        scalars = net.fused_step(noisy_poses, target_poses, grads)["scalars"]
-        for p, g in zip(params, grads):
-            p.grad = g.view(p.shape)
-        fp.skipped = []
-        fp.step(optim.lr, optim.betas, optim.eps, optim.max_norm)
-        return {"loss": scalars[2].item()}
+    res = _frame_fused_step(noisy_poses, target_poses, net, optim)
+    if res is not None:
+        return {"loss": res["scalars"][2].item()}
     outputs, _logvar, _mean = net(noisy_poses)
     loss = mse_loss(outputs, target_poses) + net.KL_WEIGHT * net.last_kl[0]
     loss.backward()

@@ -14,19 +14,21 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if _ROOT not in sys.path:
-    sys.path.insert(0, _ROOT)
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(_HERE)
+for _p in (_HERE, _ROOT):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 
 from gesture2vec_amd import ops  # noqa: E402
 from gesture2vec_amd.flat import FlatClipAdam  # noqa: E402
 from gesture2vec_amd.model.DAE_model import VAE_Network  # noqa: E402
 from gesture2vec_amd.train_eval.train_seq2seq import train_iter_DAE  # noqa: E402
+from utils.route_timing import compare  # noqa: E402
 
 DEV = "cuda:0"
 ARGS = argparse.Namespace(autoencoder_vq="False", autoencoder_vae="True")
@@ -37,28 +39,6 @@ def largest_batch(D, L):
     while ops.vaeframe_plan(B + 1, D, L, True)[1]:
         B += 1
     return B
-
-
-def timed(fn, iters):
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop) * 1e3 / iters      # microseconds per call
-
-
-def compare(fns, iters, rounds, warmup):
-    for fn in fns.values():
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(rounds):
-        for k, fn in fns.items():
-            times[k].append(timed(fn, iters))
-    return {k: dict(median_us=round(statistics.median(v), 2), min_us=round(min(v), 2), max_us=round(max(v), 2)) for k, v in times.items()}
 
 
 def main():

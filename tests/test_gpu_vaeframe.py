@@ -162,7 +162,8 @@ def largest_batch(D, L):
     return B
 
 
-STEP_SHAPES = [(2, 135, 40), (16, 135, 40), (17, 135, 45), (128, 135, 40), (37, 20, 8), "largest"]
+STEP_SHAPES = [(2, 135, 40), (16, 135, 40), (17, 135, 45), (128, 135, 40), (37, 20, 8), "largest",
+               (3, 7, 5)]      # the last: every dimension inside one partial tile, none a multiple of 4
 
 
 @pytest.mark.parametrize("shape", STEP_SHAPES, ids=str)

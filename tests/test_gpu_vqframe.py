@@ -229,7 +229,7 @@ def largest_batch(D, L, K):
 
 
 STEP_SHAPES = [(2, 135, 40, 80), (16, 135, 40, 80), (100, 135, 45, 100), (128, 135, 40, 1), (128, 135, 40, 128), "largest",
-               (37, 20, 8, 5)]
+               (37, 20, 8, 5), (3, 7, 5, 3)]      # the last: every dimension inside one partial tile, none a multiple of 4
 
 
 @pytest.mark.parametrize("shape", STEP_SHAPES, ids=str)
